@@ -12,14 +12,19 @@ SAME grid is cut into N contiguous state slabs (strong scaling) with one RCCL al
 by libsdpgpu.so itself (sdpgpu_solve_sharded); torch.distributed carries the 128-byte communicator id and the
 contract's barrier, nothing else.
 
-Order of business ("parity gates run before any timing is accepted"):
+Order of business at N = 1, plain run (what the headline figure needs, nothing else):
+  1. one sweep, W warm-up sweeps (at least two), K timed sweeps.
+  2. --dump-outputs DIR: the tables the last timed sweep left (`dump_outputs`).
+  3. the JSON line; its `parity_gate` says that the gate was not run.
+With --full ("parity gates run before any timing is accepted"), as every run did before the option:
   1. one sweep, then the PARITY GATE: sampled states of every checked period (slab and grid edges + random) are
      evaluated by the CPU oracle fed the GPU's own V_{t+1}; values and policy indices must be bit-identical.
      A failed gate ends the run with a non-zero exit and no bench line.
   2. W warm-up sweeps, K timed sweeps between barriers; max over ranks.
-  3. one more sweep with a HIP-event pair around every period launch (un-profiled per-launch times).
-  4. N = 1 on the default workload: the other BASELINE configs as `secondary` entries (each gated and timed the same
+  3. one more sweep with a HIP-event pair around every period launch (un-profiled per-launch times) -> `roofline`.
+  4. the default workload: the other BASELINE configs as `secondary` entries (each gated and timed the same
      way, a few sweeps), then the CPU oracle timed on a bounded sample (`cpu_baseline`).
+N > 1 always runs the gate, the schedule calibration and the per-launch sweep: they choose and check the sharded schedule.
 
 Rank 0 prints ONE JSON line.  `roofline` names the unit that binds the dominant kernel: fp64 VALU issue (the
 reference's arithmetic executed without FMA, 16 lanes/clk/SIMD), with the HBM traffic from the rocprofv3 counters
@@ -61,6 +66,7 @@ FAMILY_NAME = {"target": "F1 backorder (capacitated.CLSP.f lambdas)", "cfg2": "F
 REFERENCE_FLOPS_PER_CELL = {"target": 14, "cfg2": 14, "cfg5": 14, "cfg4": 14, "cfg4p": 14, "cfg3": 25, "cfg3t": 25}
 # the entries of `secondary` beyond the BASELINE configs: configs[4] at full width and the SURVEY 8(f)-3 / 8(f)-4 rows
 FAMILY_WORKLOADS = ("f5_spl", "staff", "custom_clsp", "custom_clsp_level", "separable_target", "separable_f5", "multilead_kat2")
+PLAIN_GATE = "not run (plain run: bench.py --full gates every entry)"  # `parity_gate.status` of a line without --full
 
 
 def parse_args():
@@ -76,8 +82,13 @@ def parse_args():
     ap.add_argument("--weak", action="store_true",
                     help="weak scaling instead of strong: every rank keeps --states states (default 1e4 for cfg2, 1e6 otherwise)")
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 gather, 2 window, 3 separable (opt-in: F1 to 1e-9, F2 exact)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other BASELINE configs (N = 1, default workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also the parity gate, the per-launch sweep and `roofline`, the `secondary` entries (default "
+                         "workload) and `cpu_baseline`; without it the run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the tables of the last timed step as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the other BASELINE configs (N = 1, default workload)")
     ap.add_argument("--no-gate", action="store_true", help="skip the parity gate (profiling runs only: the line says so)")
     ap.add_argument("--gate-cells", type=float, default=3e9, help="oracle work of the parity gate, in cells")
     ap.add_argument("--exchange", default="native",
@@ -148,6 +159,65 @@ def build_identity():
 def algorithmic_bytes(cells: float, states_periods: float) -> float:
     """SURVEY.md section 8(d)'s byte MODEL: 8 B per cell (one fp64 gather of V_{t+1}) + 12 B per state-period."""
     return 8.0 * cells + 12.0 * states_periods
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 60 << 20  # below the 64 MiB the option may write, the .npy headers included
+DUMP_SEED = 20250101
+
+
+def engine_tables(eng, T, slab_only=False):
+    """What a caller of the sweep receives: per period V_t and the policy's action indices (of this rank's slab).  A value table
+    the engine did not keep (two ping-pong tables: only V_1 and V_2 outlive the sweep) is None.  `slab_only`: V_t cut to the
+    rank's slab as well (N > 1: only the slab of V_1 is this rank's to give)."""
+    from stochastic_inventory_amd.engine import SdpgpuError
+    tables = []
+    for p in range(1, T + 1):
+        try:
+            v = eng.values(p)
+        except SdpgpuError:
+            v = None
+        if v is not None and slab_only:
+            _, lo, hi = eng.slab(p)
+            v = v[lo:hi]
+        tables.append((p, v, eng.policy(p)))
+    return tables
+
+
+def dump_outputs(outdir, tables, extra=None):
+    """Write the outputs of the last timed step: `tables` = [(period, V_t or None, policy indices or None)] as
+    outdir/values_p<t>.npy (float64) and outdir/policy_p<t>.npy (float32, exact: indices < 2**24); `extra` = {name: array},
+    written whole as float64.  Where the tables exceed DUMP_LIMIT_BYTES, every period is cut to a seeded sample of its states
+    (the same in every run: it depends on DUMP_SEED, the period and the table's length only), the indices of which are written
+    as outdir/states_p<t>.npy (float64)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    extra = {k: np.asarray(a, dtype=np.float64).ravel() for k, a in (extra or {}).items()}
+    whole = sum(a.nbytes for a in extra.values())
+    per_state = []
+    for p, v, pol in tables:
+        n = len(v) if v is not None else len(pol) if pol is not None else 0
+        if v is not None and pol is not None and len(v) != len(pol):
+            raise ValueError(f"period {p}: {len(v)} values but {len(pol)} policy entries")
+        per_state.append((n, (8 if v is not None else 0) + (4 if pol is not None else 0)))
+    full = whole + sum(n * b for n, b in per_state)
+    frac = 1.0
+    if full > DUMP_LIMIT_BYTES:  # (a sampled state also writes its index: 8 more bytes)
+        frac = (DUMP_LIMIT_BYTES - whole) / sum(n * (b + 8) for n, b in per_state)
+    for (p, v, pol), (n, _) in zip(tables, per_state):
+        idx = None
+        if frac < 1.0 and n:
+            rng = np.random.default_rng([DUMP_SEED, p, n])
+            idx = np.unique(rng.integers(0, n, size=max(1, int(n * frac))))
+            np.save(os.path.join(outdir, f"states_p{p}.npy"), idx.astype(np.float64))
+        if v is not None:
+            np.save(os.path.join(outdir, f"values_p{p}.npy"), np.asarray(v if idx is None else v[idx], dtype=np.float64))
+        if pol is not None:
+            np.save(os.path.join(outdir, f"policy_p{p}.npy"), np.asarray(pol if idx is None else pol[idx], dtype=np.float32))
+    for k, a in extra.items():
+        np.save(os.path.join(outdir, f"{k}.npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -254,12 +324,13 @@ def staff_gate(eng, w, budget_cells: float, seed: int = 5):
     return not bad, rec
 
 
-def run_multilead(steps: int, no_gate: bool):
+def run_multilead(steps: int, no_gate: bool, warmup: int = 0, full: bool = True, dump: str = ""):
     """The two-product overdraft recursion on its reachable set (sdpgpu_multilead_solve; csrc/sdpgpu_sparse.hip) at the size of
     the reference's slowest RECORDED run: "3 periods ... final optimal cash is -76.56 ... Q1 = 30, Q2 = 15, running time is
     1568.0s" (MultiProductLeadtime.java:45-50).  The gate is that recorded output itself (tests/golden/kat_reference.json holds
     the parameters and the number): the value must be THE double nearest -76.56 and the first order (30, 15).  A step = one whole
-    solve (forward expansion of the reachable set + backward recursion), device buffers allocated and freed inside the call."""
+    solve (forward expansion of the reachable set + backward recursion), device buffers allocated and freed inside the call.
+    The first solve is untimed (with `full`, it is the gate's), then `warmup` untimed and `steps` timed solves."""
     from stochastic_inventory_amd.multiitem import multilead_solve
     k = json.load(open(os.path.join(ROOT, "tests", "golden", "kat_reference.json")))["kat2_slow"]
     keys = ("T", "q_bound", "price", "vari_cost", "sal_value", "ini_cash", "ini_i1", "ini_i2", "r0", "r1", "r2", "limit",
@@ -273,8 +344,12 @@ def run_multilead(steps: int, no_gate: bool):
                        "Q1 = 30, Q2 = 15 -- all 17 digits of the value, both quantities"}
     if no_gate:
         gate = {"status": "skipped (--no-gate)"}
+    elif not full:
+        gate = {"status": PLAIN_GATE}
     elif not ok:
         raise SystemExit(f"PARITY GATE FAILED on multilead_kat2: {json.dumps(gate)} -- no timing accepted")
+    for _ in range(warmup):
+        multilead_solve(**kw)
     walls, gpus = [], []
     for _ in range(steps):
         t0 = time.perf_counter()
@@ -283,6 +358,16 @@ def run_multilead(steps: int, no_gate: bool):
         gpus.append(r.gpu_ms)
     wall = sum(walls) / len(walls)
     name = f"multilead_kat2_T{k['T']}_Q{k['q_bound']}"
+    if dump:
+        dump_outputs(dump, [], {"final_value": [r.finalValue], "first_order": [r.firstAction, r.secondAction],
+                                "states_per_period": r.statesPerPeriod})
+    out = {"workload": name, "family": FAMILY_NAME["multilead_kat2"], "value": r.cells / wall, "unit": "cells/s",
+           "ms_per_step": wall * 1e3, "steps": steps, "periods": k["T"], "states": int(sum(r.statesPerPeriod)),
+           "states_per_period": [int(v) for v in r.statesPerPeriod], "cells_per_step": int(r.cells), "parity_gate": gate,
+           "kernel": "reachable-set engine (expand, sort, rank, backward)",
+           "reference_remark": "1568 s (the reference author's own comment; hardware and JVM unstated)"}
+    if not full:
+        return out
     rf = {"bound": "valu-issue", "achieved": None, "peak": VALU_PEAK_LANE_OPS / 1e12, "unit": "T lane-op/s", "frac": None,
           "device_ms_per_solve": sum(gpus) / len(gpus), "traffic": None, "hbm": None,
           "note": "no counter summary in profiles/ for this build of csrc/sdpgpu_sparse.hip"}
@@ -301,11 +386,8 @@ def run_multilead(steps: int, no_gate: bool):
                    "note": f"SQ_INSTS_VALU x 64 lanes of the recursion kernel's launches of one solve / their rocprofv3 duration ({pmc['_file']})"})
         if not (0.0 < rf["frac"] <= 1.0):
             rf.update({"frac": None, "achieved": None})
-    return {"workload": name, "family": FAMILY_NAME["multilead_kat2"], "value": r.cells / wall, "unit": "cells/s",
-            "ms_per_step": wall * 1e3, "steps": steps, "periods": k["T"], "states": int(sum(r.statesPerPeriod)),
-            "states_per_period": [int(v) for v in r.statesPerPeriod], "cells_per_step": int(r.cells), "parity_gate": gate,
-            "roofline": rf, "kernel": "reachable-set engine (expand, sort, rank, backward)",
-            "reference_remark": "1568 s (the reference author's own comment; hardware and JVM unstated)"}
+    out["roofline"] = rf
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -504,11 +586,13 @@ def roofline_block(w, st, T, cells_rank, states_rank, dev_ms_per_sweep, per_laun
 # ---------------------------------------------------------------------------------------------------------------
 # one workload on one GPU (the headline at N = 1 and every secondary entry)
 # ---------------------------------------------------------------------------------------------------------------
-def run_single(sia, torch, dev, name, w, steps, warmup, kernel, gate_cells, no_gate, ping_pong=False, min_warmup=2):
+def run_single(sia, torch, dev, name, w, steps, warmup, kernel, gate_cells, no_gate, ping_pong=False, min_warmup=2, full=True,
+               dump=""):
     """`ping_pong`: two value tables instead of one per period (store_all_values = 0; what configs[4]'s full horizon runs
-    on) -- only V_1 and V_2 outlive the sweep, so the gate checks period 1."""
+    on) -- only V_1 and V_2 outlive the sweep, so the gate checks period 1.  `full`: the parity gate and the per-launch
+    sweep behind `roofline` as well (a plain run: the timed sweeps only).  `dump`: --dump-outputs."""
     if name == "multilead_kat2":
-        return run_multilead(steps, no_gate)
+        return run_multilead(steps, no_gate, warmup=warmup, full=full, dump=dump)
     d = w.desc()
     d.device = dev.index
     d.kernel = 3 if name in ("separable_target", "separable_f5") else kernel
@@ -519,6 +603,8 @@ def run_single(sia, torch, dev, name, w, steps, warmup, kernel, gate_cells, no_g
     def gate_of(eng, budget, seed=5):
         if no_gate:
             return True, {"status": "skipped (--no-gate)"}
+        if not full:
+            return True, {"status": PLAIN_GATE}
         if getattr(w, "level_pmf", None) is not None:
             return staff_gate(eng, w, budget, seed=seed)
         return parity_gate(eng, w, budget, seed=seed, periods=[1] if ping_pong else None,
@@ -538,13 +624,14 @@ def run_single(sia, torch, dev, name, w, steps, warmup, kernel, gate_cells, no_g
         for _ in range(max(warmup, min_warmup)):
             eng.solve(sync=False)
         torch.cuda.synchronize(dev)
-        if not no_gate and eng.stats().graph_replays > 0:
+        if full and not no_gate and eng.stats().graph_replays > 0:
             # the timed sweeps are graph replays: their tables must be the gated (eager) sweep's, bit for bit
             import numpy as np
             ok2, gate2 = gate_of(eng, gate_cells / 4, seed=11)
             if not ok2:
                 raise SystemExit(f"PARITY GATE FAILED on the graph-replayed sweep of {w.name}: {json.dumps(gate2)}")
             gate["graph_replay_gate"] = {"status": gate2["status"], "states_checked": gate2["states_checked"]}
+        # (the events are read by --full only; a plain run records them too, so that both time the same loop)
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
         t0 = time.perf_counter()
         for k in range(steps):
@@ -553,25 +640,30 @@ def run_single(sia, torch, dev, name, w, steps, warmup, kernel, gate_cells, no_g
             ev[k][1].record()
         torch.cuda.synchronize(dev)
         elapsed = time.perf_counter() - t0
-        dev_ms = sum(a.elapsed_time(b) for a, b in ev) / steps
         st = eng.stats()
-        replays = int(st.graph_replays)
-        eng.set_profiling(True)
-        eng.solve(sync=True)
-        per_launch = [eng.period_ms(p) for p in range(T, 0, -1)]
-        per_launch_cells = [eng.period_cells(p) for p in range(T, 0, -1)]
-        eng.set_profiling(False)
+        if dump:
+            dump_outputs(dump, engine_tables(eng, T))
+        rf = None
+        if full:
+            dev_ms = sum(a.elapsed_time(b) for a, b in ev) / steps
+            replays = int(st.graph_replays)
+            eng.set_profiling(True)
+            eng.solve(sync=True)
+            per_launch = [eng.period_ms(p) for p in range(T, 0, -1)]
+            per_launch_cells = [eng.period_cells(p) for p in range(T, 0, -1)]
+            eng.set_profiling(False)
+            rf = roofline_block(w, st, T, int(st.cells_evaluated), int(st.states_total), dev_ms, per_launch, per_launch_cells)
+            rf["sweep_issue"] = ("one hipGraphLaunch per sweep (captured inside sdpgpu_solve)" if replays >= steps
+                                 else "eager: one launch per period")
+            rf["wall_over_device"] = (elapsed / steps * 1e3) / dev_ms if dev_ms > 0 else None
         cells = int(st.cells_evaluated)
-        states = int(st.states_total)
-        rf = roofline_block(w, st, T, cells, states, dev_ms, per_launch, per_launch_cells)
-        rf["sweep_issue"] = ("one hipGraphLaunch per sweep (captured inside sdpgpu_solve)" if replays >= steps
-                             else "eager: one launch per period")
-        rf["wall_over_device"] = (elapsed / steps * 1e3) / dev_ms if dev_ms > 0 else None
         n_states = max(eng.num_states(p) for p in range(1, T + 1))  # (unclamped families grow with the period: the widest)
     out = {"workload": w.name, "family": FAMILY_NAME.get(name, name), "value": cells * steps / elapsed, "unit": "cells/s",
            "ms_per_step": elapsed / steps * 1e3, "steps": steps, "periods": T, "states": n_states,
-           "cells_per_step": cells, "parity_gate": gate, "roofline": rf,
+           "cells_per_step": cells, "parity_gate": gate,
            "kernel": {0: "auto", 1: "gather", 2: "specialised (window / shift / row)", 3: "separable"}[int(st.kernel_used)]}
+    if rf is not None:
+        out["roofline"] = rf
     if ping_pong:
         out["tables"] = "two ping-pong value tables (store_all_values = 0), as the full 100-period horizon runs"
     if getattr(w, "custom_source", None):
@@ -754,7 +846,8 @@ def main():
 
     if not sharded_path:
         head = run_single(sia, torch, dev, args.workload, w, args.steps, args.warmup, args.kernel, args.gate_cells,
-                          args.no_gate, ping_pong=(args.workload == "cfg5" and not args.states))
+                          args.no_gate, ping_pong=(args.workload == "cfg5" and not args.states), full=args.full,
+                          dump=args.dump_outputs)
         f = getattr(w, "functor", None)
         out = {
             "metric": "(state,action,demand) cell evals/sec",
@@ -767,9 +860,12 @@ def main():
                        "cells_per_step": head["cells_per_step"], "parallelism": "single GPU", "exchange": "single rank",
                        "kernel": head["kernel"]},
             "parity_gate": head["parity_gate"],
-            "roofline": head["roofline"],
             "build": build_identity(),
         }
+        if not args.full:
+            print(json.dumps(out), flush=True)
+            return
+        out["roofline"] = head["roofline"]
         flops = REFERENCE_FLOPS_PER_CELL.get(args.workload, 14)
         if "algorithmic" in head["roofline"]:
             out["side_by_side"] = {
@@ -976,6 +1072,9 @@ def main():
             ev[k][1].record()
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:  # (rank 0's slab of every table)
+        with wd.phase("dump outputs", 300):
+            dump_outputs(args.dump_outputs, engine_tables(eng, T, slab_only=True))
 
     st = eng.stats()
     cells_step_all = int(st.cells_all_ranks)

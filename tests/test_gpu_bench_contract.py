@@ -1,5 +1,6 @@
 """bench.py's one-line JSON contract at N = 1 (the line the driver parses): every key, its type and the relations
-between them, on a short run of the default workload (reduced horizon) and of two others."""
+between them, on a short --full run of the default workload (reduced horizon) and of two others; and the plain run's line
+with the tables --dump-outputs writes."""
 import json
 import os
 import subprocess
@@ -11,9 +12,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra):
+def _run(*extra, full=True):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--cpu-seconds", "2", *extra], capture_output=True, text=True, timeout=400, cwd=ROOT)
+                          *(["--full", "--cpu-seconds", "2"] if full else []), *extra],
+                         capture_output=True, text=True, timeout=400, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "exactly one JSON line on stdout"
@@ -99,3 +101,35 @@ def test_a_failing_secondary_entry_does_not_take_the_headline_down(monkeypatch):
     assert set(by) == {"cfg2", "staff", "custom"}
     assert by["staff"]["value"] is None and by["staff"]["parity_gate"]["status"] == "FAILED" and "injected" in by["staff"]["error"]
     assert by["cfg2"]["parity_gate"]["status"] == "ok" and by["custom"]["parity_gate"]["status"] == "ok"
+
+
+def test_plain_run_times_the_headline_and_dumps_its_tables(tmp_path, oracle):
+    """No --full: the headline alone (no gate, roofline, secondary entries or CPU baseline), its keys meaning what they mean in
+    a --full line; --dump-outputs holds the tables of the last timed sweep, which the oracle reproduces."""
+    import numpy as np
+
+    from stochastic_inventory_amd import workloads
+
+    r = _run("--periods", "3", "--dump-outputs", str(tmp_path), full=False)
+    assert r["metric"] == "(state,action,demand) cell evals/sec" and r["unit"] == "cells/s" and r["dtype"] == "f64"
+    assert r["higher_is_better"] is True and r["steps"] == 3 and r["warmup"] == 1
+    assert r["config"]["workload"] == "target_f1_1000000x500x200x3" and r["value"] > 1e11 and r["ms_per_step"] > 0
+    assert abs(r["value"] - r["config"]["cells_per_step"] / (r["ms_per_step"] * 1e-3)) <= 0.02 * r["value"]
+    assert r["parity_gate"]["status"].startswith("not run") and r["build"]["match"] is True
+    for key in ("roofline", "secondary", "cpu_baseline", "side_by_side"):
+        assert key not in r, key
+    names = sorted(os.listdir(tmp_path))
+    assert names == sorted(f"{k}_p{p}.npy" for p in (1, 2, 3) for k in ("values", "policy"))
+    assert sum(os.path.getsize(tmp_path / n) for n in names) <= 64 << 20
+    # sampled states of every period against the oracle fed the dumped V_{t+1}: bit-identical values and action indices
+    w = workloads.target_grid(T=3)
+    P = oracle.Problem(w.desc(), w.pmf, w.overhead())
+    rng = np.random.default_rng(7)
+    for p in (3, 2, 1):
+        v, pol = np.load(tmp_path / f"values_p{p}.npy"), np.load(tmp_path / f"policy_p{p}.npy")
+        assert v.dtype == np.float64 and pol.dtype == np.float32 and len(v) == len(pol) == P.S[p - 1] == 1000000
+        pick = np.unique(rng.integers(0, len(v), size=200))
+        v_next = np.load(tmp_path / f"values_p{p + 1}.npy") if p < 3 else None
+        x = P.grids[p - 1].x_lo + pick.astype(np.float64) * P.desc.step
+        ov, oa = P.eval_states(p, v_next, x, nthreads=4)
+        assert np.array_equal(v[pick], ov) and np.array_equal(pol[pick], oa.astype(np.float32)), p

@@ -35,7 +35,7 @@ def main():
                 env[k] = str(v)
             else:
                 env.pop(k, None)
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "5", "--warmup", "1",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", workload, "--steps", "5", "--warmup", "1",
                "--no-cpu-baseline", "--no-secondary", "--gate-cells", "1e9", *extra]
         if states:
             cmd += ["--states", str(states)]

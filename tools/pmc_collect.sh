@@ -15,7 +15,7 @@ TOP=$R/gpurun_out/prof_${RND}_$W
 OUT=$TOP/run_$(date +%Y%m%d%H%M%S)
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --workload $W --no-secondary $*"
+BENCH="python3 $R/bench.py --full --workload $W --no-secondary $*"
 timeout -k 10 500 $BENCH --cpu-seconds 5 > $OUT/bench.json 2> $OUT/bench.err
 PROF="--workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --no-gate $*"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py $PROF > $OUT/stats.log 2>&1

@@ -7,7 +7,7 @@ OUT=$R/gpurun_out/pmc_diag_bands
 {
 for b in 0 1; do
   export SDPGPU_CASH_DIAG_BANDS=$b
-  python3 $R/bench.py --workload cfg3 --steps 5 --warmup 2 --no-cpu-baseline > $OUT.bench$b.json 2>/dev/null
+  python3 $R/bench.py --full --workload cfg3 --steps 5 --warmup 2 --no-cpu-baseline > $OUT.bench$b.json 2>/dev/null
   python3 -c "
 import json;d=json.loads(open('$OUT.bench$b.json').read().strip().splitlines()[-1]);print('bands=$b: %.3f ms per sweep, %.4e cells/s, per-launch ms %s, gate %s' % (d['ms_per_step'], d['value'], d['roofline']['per_launch_ms_events'], d['parity_gate']['status']))"
   for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_INSTS_VALU SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do

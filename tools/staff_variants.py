@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for label, env in (("default", {}), ("pair + window S=4 everywhere", {"SDPGPU_STAFF_PAIR": "1", "SDPGPU_STAFF_WIN": "4"}),
                    ("pair + window S=2 everywhere", {"SDPGPU_STAFF_PAIR": "1", "SDPGPU_STAFF_WIN": "2"}),
                    ("pair kernel, no window", {"SDPGPU_STAFF_PAIR": "1", "SDPGPU_STAFF_WIN": "0"})):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "staff", "--no-secondary", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "staff", "--no-secondary", "--no-cpu-baseline",
                           "--steps", "5", "--warmup", "2"], capture_output=True, text=True, env=dict(os.environ, **env))
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if not lines:
