@@ -541,8 +541,9 @@ typedef struct sdpgpu_plan {
   int32_t kernel;            /* SDPGPU_KERNEL_WINDOW or SDPGPU_KERNEL_GATHER */
   int32_t r, s;              /* register block: actions x adjacent states per lane */
   int32_t chunks;            /* tasks per state tile (1: no chunk rows, no key atomics, no finalize pass) */
-  int32_t chunk_blocks;      /* register blocks of the action axis per task */
-  int32_t tiles, tasks;      /* state tiles of 64 s states of this slab; tiles x chunks */
+  int32_t chunk_blocks;      /* register blocks of the action axis per task; 0: the action-major level kernel, whose
+                                tasks are level bands x blocks of 64 r actions */
+  int32_t tiles, tasks;      /* state tiles of 64 s states of this slab; tiles x chunks (level kernel: bands; tasks) */
   int32_t workgroups_per_cu; /* workgroups (four tasks each) the LDS lets a compute unit hold at once */
   int64_t lds_bytes;         /* dynamic LDS per workgroup */
 } sdpgpu_plan;

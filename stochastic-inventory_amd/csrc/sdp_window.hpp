@@ -370,6 +370,245 @@ __global__ __launch_bounds__(256) void window_f1_kernel(WinParams W, const doubl
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------
+// ACTION-MAJOR LEVEL KERNEL for F1 (window_f1_level_kernel).  In window_f1_kernel a lane owns states, and the product
+// p_j * V(m) that every (state, action) pair of post-order level y = i + k needs at step j (m = y - j) is formed again by
+// every lane and every R-block that meets it.  Here a lane owns ACTIONS k = kb + lane + 64 r (r < R) and walks the levels
+// y in blocks of S consecutive levels y0 + s: the cell (lane, r, s) is the pair (state y0 + s - k, action k), and at
+// step j its level m = y0 + s - j is the same in all 64 lanes.  So p_j, M(m) and p_j * V(m) are wave-uniform: the wave
+// forms the S products of 64 steps lane-parallel (one v_mul_f64 gives 64 of them) into a table in its own LDS region,
+// and the step loop reads them back as broadcasts.  The immediate cost c0[k] + M(m) of level s at step j is that of level
+// s - 1 at step j - 1 (a ring of S registers per action): R new adds per step.  Operations per cell:
+//     p * imm, acc += , acc += p V                3
+//     c0 + M, once per (action, m)                R / (R S)
+//     p * V, once per (step, m) and wave          S / 64 / (R S)
+// each of them an operation the reference performs on the same operands, in its order (j ascending, += p imm then += p V,
+// from +0.0).  Padded cells -- actions >= A, levels whose state lies outside the slab, demand steps past D (p = 0) -- read
+// clamped, finite table entries.
+//
+// A task (one wave) is (band of `band` levels, block of 64 R actions).  A state's cells are spread over lanes, over the
+// level blocks of the band and, near the band's ends and across action blocks, over tasks:
+//   * within a task they meet in a per-state (value, action) slot in LDS, updated after every level block in R S passes;
+//     one pass (r, s) touches 64 distinct states, and the passes go s ascending, which for any one state is action
+//     ascending -- so a strict < / > keeps the lowest action of a tie, the reference's rule (Recursion.java:146-157);
+//   * across tasks through the chunk rows, the key atomics and finalize_kernel: the piece of state i held by task
+//     (band b, action block a) goes to chunk row (b - band(i)) + a, band(i) = the band of level i.  Along the action axis
+//     of one state both b and a are non-decreasing, so a lower row always holds lower actions; where a band boundary and
+//     an action-block boundary fall on the same action, the row skipped in between gets a NaN value, which the finalize
+//     never takes.  Rows above a state's last piece are never reached: the value it looks for is in one below.
+// ---------------------------------------------------------------------------------------------
+struct LevelParams {
+  int32_t band;       // levels per task (a multiple of S)
+  int32_t n_ablocks;  // action blocks of 64 R
+  int32_t n_tasks;    // bands x action blocks; task = band * n_ablocks + block
+  int32_t d_pad;      // demand steps rounded up to S; the padded steps carry p = 0
+  int32_t lo;         // first state of the slab = first level (state lo, action 0)
+  int32_t n_states;   // hi - lo
+  int32_t y_hi;       // one past the last level: hi + A - 1
+  int32_t n_chunks;   // chunk rows: ceil((A - 1) / band) + n_ablocks
+};
+
+template <int S>
+struct LevelShape {
+  static constexpr int DB = (64 / S) * S;  // demand steps per product table (a whole number of S-step rotations)
+  static constexpr int ROW = S + 2;        // doubles per table row: p_j, M(y0 - j - 1), p_j * V(y0 + s - j) for s < S
+};
+// LDS of one wave: its product table, then (band + 64 R) slots of {value, action}
+__host__ __device__ inline size_t level_wave_lds(int band, int R, int S) {
+  const int db = (64 / S) * S;
+  return (((size_t)db * (S + 2) * 8 + (size_t)(band + 64 * R) * 12) + 15) & ~(size_t)15;
+}
+__host__ __device__ inline int level_chunks(int n_actions, int band, int n_ablocks) {
+  return (n_actions - 1 + band - 1) / band + n_ablocks;
+}
+
+// V_{t+1}(clamp m) of window_entry, alone
+template <bool KEYED_IN>
+__device__ __forceinline__ double level_v(const WinParams& W, const double* __restrict__ v_next,
+                                          const unsigned long long* __restrict__ k_next, int m) {
+  int idx = m + W.idx_off;
+  idx = idx > W.next_last ? W.next_last : idx;
+  idx = idx < 0 ? 0 : idx;
+  if constexpr (KEYED_IN)
+    return f64_unkey(k_next[idx]);
+  else
+    return v_next[idx];
+}
+
+template <int R, int S, bool FUTURE, bool KEYED_IN>
+__global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, LevelParams L, const double* __restrict__ v_next,
+                                                              const unsigned long long* __restrict__ k_next,
+                                                              double* __restrict__ out_val, int32_t* __restrict__ out_idx,
+                                                              unsigned long long* __restrict__ k_cur,
+                                                              const double* __restrict__ pmf_p) {
+  constexpr int DB = LevelShape<S>::DB, ROW = LevelShape<S>::ROW, NA = 64 * R;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int task = blockIdx.x * 4 + wave;
+  if (task >= L.n_tasks) return;  // no workgroup barrier below
+  const bool MAXDIR = W.maxdir != 0;
+  const double ident = MAXDIR ? -1.7976931348623157e308 : 1.7976931348623157e308;
+  const int ab = task % L.n_ablocks;
+  const int b = task / L.n_ablocks;
+  const int kb = ab * NA;
+  const int yb = L.lo + b * L.band;
+  const int ye = min(yb + L.band, L.y_hi);
+  const int i_min = yb - kb - NA + 1;  // slot q holds state i_min + q; states i_min .. ye - 1 - kb
+  const int n_slot = ye - yb + NA - 1;
+  char* mine = smem + (size_t)wave * level_wave_lds(L.band, R, S);
+  double* s_row = reinterpret_cast<double*>(mine);
+  double* s_val = s_row + DB * ROW;
+  int* s_idx = reinterpret_cast<int*>(s_val + L.band + NA);
+  for (int q = lane; q < n_slot; q += 64) {
+    s_val[q] = ident;
+    s_idx[q] = 0;
+  }
+  double c0[R];
+  bool kreal[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int k = kb + lane + 64 * r;
+    kreal[r] = k < W.n_actions;
+    const double a = (double)k * W.step;
+    if (W.c_tab)  // (a padded action reads the last entry: finite, never selected)
+      c0[r] = W.c_tab[k < W.n_actions ? k : W.n_actions - 1];
+    else
+      c0[r] = (a > 0 ? W.K : 0.0) + W.v * a;
+  }
+
+  for (int y0 = yb; y0 < ye; y0 += S) {
+    if (W.prio_fair) {
+      // Priority by progress, as in window_f1_kernel: the four waves of a workgroup free its LDS only together, and a plan
+      // of two rounds of equal tasks loses a tenth of the issue rate when the resident waves of a SIMD drift apart by age
+      // (the one left behind then runs alone, at 0.6 of the rate, while the slot of the finished one stays empty).
+      const unsigned pr = 3u - (4u * (unsigned)(y0 - yb)) / (unsigned)(ye - yb + 1);
+      if (pr == 0) __builtin_amdgcn_s_setprio(0);
+      else if (pr == 1) __builtin_amdgcn_s_setprio(1);
+      else if (pr == 2) __builtin_amdgcn_s_setprio(2);
+      else __builtin_amdgcn_s_setprio(3);
+    }
+    double acc[R][S];
+    double imm[R][S];  // ring: at step j, cell s uses imm[r][(s - j) mod S] = c0[r] + M(y0 + s - j)
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const double ms = window_entry<false, false>(W, nullptr, nullptr, y0 + s).x;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        acc[r][s] = 0.0;
+        imm[r][s] = c0[r] + ms;
+      }
+    }
+    for (int j0 = 0; j0 < L.d_pad; j0 += DB) {
+      const int nj = min(DB, L.d_pad - j0);
+      // the table of steps j0 .. j0 + nj - 1: lane t forms row t (rows past nj repeat the last step and are not read)
+      __builtin_amdgcn_wave_barrier();
+      if (lane < DB) {
+        const int j = j0 + min(lane, nj - 1);
+        const double p = pmf_p[j];  // (the array ends in kPmfPad zeros: d_pad < D + S stays inside)
+        double* row = s_row + lane * ROW;
+        double vv[S];
+        if constexpr (FUTURE) {
+#pragma unroll
+          for (int s = 0; s < S; ++s) vv[s] = level_v<KEYED_IN>(W, v_next, k_next, y0 + s - j);
+        }
+        row[0] = p;
+        row[1] = window_entry<false, false>(W, nullptr, nullptr, y0 - j - 1).x;
+        if constexpr (FUTURE) {
+#pragma unroll
+          for (int s = 0; s < S; ++s) row[2 + s] = p * vv[s];
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      // Each step reads the NEXT step's row (a broadcast ds_read_b128 per two doubles) before its own 100 fp64
+      // instructions, which then cover the LDS latency; the row past the block's last step lies inside the wave's region
+      // and is not used.
+      constexpr int NQ = FUTURE ? ROW / 2 : 1;
+      double2 nxt[NQ];
+#pragma unroll
+      for (int u = 0; u < NQ; ++u) nxt[u] = reinterpret_cast<const double2*>(s_row)[u];
+#pragma unroll 1
+      for (int t0 = 0; t0 < nj; t0 += S) {
+        const double* rows = s_row + t0 * ROW;
+#pragma unroll
+        for (int t = 0; t < S; ++t) {
+          double2 cur[NQ];
+#pragma unroll
+          for (int u = 0; u < NQ; ++u) {
+            cur[u] = nxt[u];
+            nxt[u] = reinterpret_cast<const double2*>(rows + (t + 1) * ROW)[u];
+          }
+          // (fences: left to itself the scheduler pulls the next step's products up to the reads and waits on them at once)
+          __builtin_amdgcn_sched_barrier(0);
+          const double2 pm = cur[0];
+          const double p = pm.x;
+          double pv[S];
+          if constexpr (FUTURE) {
+#pragma unroll
+            for (int s = 0; s < S; s += 2) {
+              pv[s] = cur[1 + s / 2].x;
+              if (s + 1 < S) pv[s + 1] = cur[1 + s / 2].y;
+            }
+          }
+#pragma unroll
+          for (int s = 0; s < S; ++s) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+              acc[r][s] += p * imm[r][(s - t + S) % S];
+              if constexpr (FUTURE) acc[r][s] += pv[s];
+            }
+          }
+          // level 0 at step j + 1 takes the slot level S - 1 has just used
+#pragma unroll
+          for (int r = 0; r < R; ++r) imm[r][(2 * S - 1 - t) % S] = c0[r] + pm.y;
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    }
+    // into the per-state slots: cell (r, s) is state y0 + s - k, slot (y0 - yb) + s - lane - 64 r + NA - 1
+    const int sb = (y0 - yb) - lane + NA - 1;
+    const int ib = y0 - kb - lane - L.lo;  // state - lo of cell (0, 0)
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int rel = ib + s - 64 * r;
+        if (kreal[r] && rel >= 0 && rel < L.n_states) {
+          const int q = sb + s - 64 * r;
+          const double cur = s_val[q];
+          if (MAXDIR ? (acc[r][s] > cur) : (acc[r][s] < cur)) {
+            s_val[q] = acc[r][s];
+            s_idx[q] = kb + lane + 64 * r;
+          }
+        }
+      }
+    }
+  }
+
+  // every state of the task's range that has a real action here: its piece, in chunk row (b - band(i)) + ab
+  __builtin_amdgcn_wave_barrier();
+  for (int q = lane; q < n_slot; q += 64) {
+    const int i = i_min + q;
+    const int rel = i - L.lo;
+    if (rel < 0 || rel >= L.n_states) continue;
+    const int kf = max(kb, yb - i);  // lowest action of the piece
+    if (kf >= W.n_actions) continue;
+    const int c = (b - rel / L.band) + ab;
+    const double v = s_val[q];
+    const int64_t o = (int64_t)c * W.partial_stride + i;
+    out_val[o] = v;
+    out_idx[o] = s_idx[q];
+    if (kb > 0 && yb - i == kb) {  // both boundaries at action kf: row c - 1 holds no piece of this state
+      out_val[o - W.partial_stride] = __builtin_nan("");
+      out_idx[o - W.partial_stride] = 0;
+    }
+    if (MAXDIR)
+      atomicMax(k_cur + i, f64_key(v));
+    else
+      atomicMin(k_cur + i, f64_key(v));
+  }
+}
+
 // Fill the key rows with the reduction identity (+-Double.MAX_VALUE, the `val` initialiser of
 // Recursion.java:132-133).
 __global__ __launch_bounds__(256) void key_fill_kernel(unsigned long long* __restrict__ keys, int64_t n, int maxdir) {

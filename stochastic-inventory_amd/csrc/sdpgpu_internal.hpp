@@ -44,6 +44,10 @@ constexpr size_t kPmfPad = 16;  // zero-probability tail: demand loop in blocks 
 struct WinPlan {
   int R = 0, S = 1, d_pad = 0, n_chunks = 1, chunk_blocks = 0, n_tiles = 0, n_tasks = 0;
   size_t smem = 0;
+  // window_f1_level_kernel (action-major lanes): tasks = n_tiles level bands of `band` levels x n_ablocks blocks of 64 R
+  // actions; d_pad, n_chunks and smem are then its own
+  bool level = false;
+  int band = 0, n_ablocks = 0;
   int tile_states() const { return 64 * S; }
 };
 
@@ -53,7 +57,7 @@ struct WinPlan {
 struct WinPlanCache {
   bool valid = false;
   int64_t lo = 0, hi = 0;
-  int win_r = 0, win_s = 0, win_nch = 0;
+  int win_r = 0, win_s = 0, win_nch = 0, win_level = -1;
   bool may_chunk = false;
   WinPlan plan;
   std::string why;
@@ -141,6 +145,7 @@ struct sdpgpu_handle {
   bool use_cash_row = true;   // SDPGPU_CASH_ROW=0 turns the cash row kernel off (generic kernel instead)
   int win_prio_fair = 1;  // window kernel: s_setprio by progress (SDPGPU_WIN_PRIO=0 turns it off)
   int win_r = 0, win_nch = 0, win_s = 0;  // tuning overrides (SDPGPU_WIN_R / SDPGPU_WIN_NCH / SDPGPU_WIN_S), 0 = heuristic
+  int win_level = -1;  // SDPGPU_WIN_LEVEL: 1 = the action-major level kernel wherever it can run, 0 = never, -1 = where it wins
   uint8_t* d_reach = nullptr;      // reachable masks, period t at reach_off[t-1]
   std::vector<size_t> reach_off;
   bool reach_done = false;

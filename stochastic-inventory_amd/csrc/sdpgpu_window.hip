@@ -27,18 +27,74 @@ bool window_eligible(const sdpgpu_handle* h, int period) {
 // ((5 + 4(S-1)) / S, see window_f1_kernel) but bigger, fewer tasks: small grids keep S low.
 static WinPlan plan_window_search(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, std::string* why);
 
+// The action-major level kernel (window_f1_level_kernel), where it can run and -- unless SDPGPU_WIN_LEVEL=1 asks for it
+// -- where it wins: a whole single-rank slab (no halo, no interior / boundary split), chunk rows allowed (every state's
+// actions meet across tasks), nothing forced about the state-major blocks, and a grid that fills the chip with tasks
+// whose lanes are nearly all real actions.  Its fp64 count per cell, 3 + 1/S + 1/(64 R) against 3 + 1/S + (R+S-1)/(RS),
+// is then what decides; the 64 R-action blocks pad A up to a multiple of 256 (A = 500: 2.4 %), and small grids or few
+// actions stay on window_f1_kernel.  (R, S) = (4, 8): 232 VGPRs, two waves per SIMD, five broadcast ds_read_b128 per step
+// against 100 fp64 instructions ((4, 10) needs 277 VGPRs: one wave per SIMD).  The band is sized against the 2048 wave slots (two waves per SIMD): whole rounds of tasks,
+// each wave's table and slots within 16 KiB (64 KiB per workgroup).
+static WinPlan plan_level(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi) {
+  WinPlan pl;
+  if (h->win_level == 0 || h->win_r || h->win_s || h->win_nch) return pl;
+  const PeriodInfo& p = h->per[period - 1];
+  if (h->d.world_size != 1 || h->halo != 0 || lo != p.lo || hi != p.hi || hi <= lo) return pl;
+  if (!(h->fuse_combine && h->d.store_all_values)) return pl;
+  const int A = h->n_actions_full, D = p.nD_win;
+  const int64_t n = hi - lo;
+  constexpr int R = 4, NA = 64 * R;
+  const int nb = (A + NA - 1) / NA;
+  // (period T has no future term: 2 + 1/S operations per cell on either kernel, and the action padding and the
+  // per-level-block overheads leave the level kernel behind -- measured 6.44 against 6.28 ms on the target grid)
+  if (h->win_level < 0 && !(period < h->T && n >= 262144 && (double)nb * NA <= 1.06 * A && D >= 16)) return pl;
+  constexpr int S = 8;
+  const int64_t ny = n + A - 1;
+  int band_max = 0;
+  while (4 * sdp::level_wave_lds(band_max + S, R, S) <= kLdsLegacy) band_max += S;
+  if (band_max < S) return pl;
+  int band = band_max;
+  for (int64_t q = 1; q <= 64; ++q) {
+    const int64_t per_round = std::max<int64_t>(1, 2048 * q / nb);
+    const int64_t want = ((ny + per_round - 1) / per_round + S - 1) / S * S;
+    if (want <= band_max) {
+      band = (int)want;
+      break;
+    }
+  }
+  const int64_t n_bands = (ny + band - 1) / band;
+  if (n_bands * nb > INT32_MAX / 2) return pl;
+  pl.level = true;
+  pl.R = R;
+  pl.S = S;
+  pl.d_pad = (D + S - 1) / S * S;
+  pl.band = band;
+  pl.n_ablocks = nb;
+  pl.n_tiles = (int)n_bands;
+  pl.n_tasks = (int)(n_bands * nb);
+  pl.n_chunks = std::max(2, sdp::level_chunks(A, band, nb));  // (always chunk rows: a state's pieces meet in the finalize)
+  pl.chunk_blocks = 0;
+  pl.smem = 4 * sdp::level_wave_lds(band, R, S);
+  return pl;
+}
+
 WinPlan plan_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, std::string* why) {
   WinPlanCache& c = h->per[period - 1].win_plan;
   const bool may_chunk = h->fuse_combine && h->d.store_all_values;
   if (!(c.valid && c.lo == lo && c.hi == hi && c.win_r == h->win_r && c.win_s == h->win_s && c.win_nch == h->win_nch &&
-        c.may_chunk == may_chunk)) {
+        c.win_level == h->win_level && c.may_chunk == may_chunk)) {
     c.why.clear();
     c.plan = plan_window_search(h, period, lo, hi, &c.why);
+    if (c.plan.R) {
+      const WinPlan lv = plan_level(h, period, lo, hi);
+      if (lv.R) c.plan = lv;
+    }
     c.lo = lo;
     c.hi = hi;
     c.win_r = h->win_r;
     c.win_s = h->win_s;
     c.win_nch = h->win_nch;
+    c.win_level = h->win_level;
     c.may_chunk = may_chunk;
     c.valid = true;
   }
@@ -402,12 +458,18 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
   WinPlan pl = plan_window(h, period, lo, hi, &h->plan_error);
   if (!pl.R) return hipErrorInvalidValue;
   if (period == h->T && std::getenv("SDPGPU_DEBUG_PLAN"))
-    std::fprintf(stderr, "[sdpgpu] window plan: R=%d S=%d chunks=%d blocks/chunk=%d tiles=%d tasks=%d lds=%zu\n", pl.R, pl.S,
-                 pl.n_chunks, pl.chunk_blocks, pl.n_tiles, pl.n_tasks, pl.smem);
+    std::fprintf(stderr, "[sdpgpu] window plan: %s R=%d S=%d chunks=%d blocks/chunk=%d tiles=%d tasks=%d lds=%zu band=%d\n",
+                 pl.level ? "level" : "state", pl.R, pl.S, pl.n_chunks, pl.chunk_blocks, pl.n_tiles, pl.n_tasks, pl.smem, pl.band);
   const bool future = period < h->T;
-  // c0 + M once per (action, m): 1/S; p * imm: 1; p * V once per window entry: (R + S - 1)/(R S); two accumulations
-  p.ops_cell = future ? 3.0 + 1.0 / pl.S + (pl.R + pl.S - 1.0) / (pl.R * pl.S) : 2.0 + 1.0 / pl.S;
-  p.lds_cell = 24.0 / (pl.R * pl.S);  // one {M, V} entry and one probability per demand step and lane
+  if (pl.level) {
+    // c0 + M once per (action, m): 1/S; p * V once per (step, m) and wave: 1/(64 R); p * imm and two accumulations
+    p.ops_cell = future ? 3.0 + 1.0 / pl.S + 1.0 / (64.0 * pl.R) : 2.0 + 1.0 / pl.S;
+    p.lds_cell = 8.0 * (pl.S + 2) / (pl.R * pl.S);  // one broadcast table row per demand step and lane
+  } else {
+    // c0 + M once per (action, m): 1/S; p * imm: 1; p * V once per window entry: (R + S - 1)/(R S); two accumulations
+    p.ops_cell = future ? 3.0 + 1.0 / pl.S + (pl.R + pl.S - 1.0) / (pl.R * pl.S) : 2.0 + 1.0 / pl.S;
+    p.lds_cell = 24.0 / (pl.R * pl.S);  // one {M, V} entry and one probability per demand step and lane
+  }
   const bool chunked = pl.n_chunks > 1;
   // a period is never re-run on top of its own pending rows, and a new sweep (period T) first
   // finalizes what the previous one left: the key rows are about to be reset
@@ -474,6 +536,58 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
     W.m_tab_n = h->level_m_n[(size_t)period - 1];
   }
   W.n_actions = h->n_actions_full;
+  W.maxdir = P.maxdir;
+  W.n_demand = p.nD_win;
+  if (pl.level) {
+    const unsigned long long* k_next = keyed_in ? h->d_keys + (size_t)period * h->key_stride : nullptr;
+    sdp::LevelParams L{};
+    L.band = pl.band;
+    L.n_ablocks = pl.n_ablocks;
+    L.n_tasks = pl.n_tasks;
+    L.d_pad = pl.d_pad;
+    L.lo = (int32_t)lo;
+    L.n_states = (int32_t)(hi - lo);
+    L.y_hi = (int32_t)(hi + W.n_actions - 1);
+    L.n_chunks = pl.n_chunks;
+    W.prio_fair = h->win_prio_fair;
+    W.partial_stride = chunk_row_cap(h, p);
+    double* out_val = h->d_chunk_val + h->chunk_off[period - 1] - chunk_row_lo(h, p);  // (rows indexed by flat state index)
+    int32_t* out_idx = h->d_chunk_idx + h->chunk_off[period - 1] - chunk_row_lo(h, p);
+    unsigned long long* k_cur = h->d_keys + (size_t)(period - 1) * h->key_stride;
+    if (!grid_ok((pl.n_tasks + 3) / 4)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((pl.n_tasks + 3) / 4));
+    bool launched = false;
+#define SDP_LVL_GO(RR, SS, FU, KI)                                                                                             \
+  do {                                                                                                                         \
+    static LdsMark mark;                                                                                                       \
+    hipError_t ea = lds_allow(sdp::window_f1_level_kernel<RR, SS, FU, KI>, pl.smem, &mark);                                    \
+    if (ea != hipSuccess) return ea;                                                                                           \
+    hipLaunchKernelGGL((sdp::window_f1_level_kernel<RR, SS, FU, KI>), grid, dim3(256), pl.smem, st, W, L, v_next, k_next,      \
+                       out_val, out_idx, k_cur, pmf_p);                                                                        \
+  } while (0)
+#define SDP_LVL_R(RR, SS)               \
+  if (pl.R == RR && pl.S == SS) {       \
+    if (!future)                        \
+      SDP_LVL_GO(RR, SS, false, false); \
+    else if (keyed_in)                  \
+      SDP_LVL_GO(RR, SS, true, true);   \
+    else                                \
+      SDP_LVL_GO(RR, SS, true, false);  \
+    launched = true;                    \
+  }
+    SDP_LVL_R(4, 8)
+#undef SDP_LVL_R
+#undef SDP_LVL_GO
+    if (!launched) return hipErrorInvalidValue;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (h->pending_chunks[period - 1] == 0) {
+      h->pending_chunks[period - 1] = pl.n_chunks;
+      h->n_pending++;
+      h->key_row_clean[period - 1] = 0;
+    }
+    return hipSuccess;
+  }
   W.d_pad = pl.d_pad;
   W.d_main = p.nD_win / (pl.R + pl.S - 1) * (pl.R + pl.S - 1);
   W.maxdir = P.maxdir;
