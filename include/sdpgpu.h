@@ -640,6 +640,64 @@ double sdpgpu_period_ms(sdpgpu_handle* h, int32_t period);
  * not counted yet (the period has not run) or not known per period. */
 int64_t sdpgpu_period_cells(sdpgpu_handle* h, int32_t period);
 
+/* ---- batched solve: many backorder-family instances of ONE grid shape ------------------------------------------------
+ * The reference's parameter sweeps -- capacitated.CLSPTesting.main (CLSPTesting.java:33-141: 10 demand patterns x 2 v x
+ * 3 pi x 3 K x 3 coeVar = 540 instances of the grid x in [-500, 500], Q = 0..500, T = 8), LevelFitsS, CLSPforDraw -- build
+ * a new Recursion per parameter set and call getExpectedValue(initialState) / getAction(initialState) on each
+ * (CLSPTesting.java:108-118).  A batch holds n such instances and runs period t of ALL of them in ONE kernel launch; every
+ * instance's tables are bit for bit those of its own sdpgpu_handle.  Additive to ABI 6; an object of its own, separate from
+ * sdpgpu_handle.
+ *
+ * Must agree between the n descriptors: family (SDPGPU_FAMILY_BACKORDER), direction, periods, step, min_inventory,
+ * max_inventory, max_order_quantity, clamp_inventory (1), device, store_all_values, world_size (1).  May differ per instance:
+ * fixed_order_cost, unit_order_cost, holding_cost, penalty_cost, ini_inventory (a grid point) -- and every pmf.  kernel:
+ * SDPGPU_KERNEL_AUTO or _WINDOW.  A mismatch returns SDPGPU_ERR_ARG and names the instance and the field; what is out of
+ * scope (another family, clamp_inventory = 0, world_size > 1, another kernel) returns SDPGPU_ERR_UNSUPPORTED with the reason.
+ * n = 1 is legal.  Rules as for a handle: status codes; the text of the last failure through sdpgpu_batch_last_error
+ * (NULL = the last failed sdpgpu_batch_create of this thread); validation and host layout first, device tables on first
+ * use; pmfs frozen once the device tables exist; no C++ exception crosses the boundary; the caller's current device is
+ * restored; one batch is not thread-safe.  store_all_values = 1 keeps n x T value tables, 0 two ping-pong tables per instance
+ * (V_1 and V_2 survive); the policy tables of all periods are kept either way. */
+typedef struct sdpgpu_batch sdpgpu_batch;
+typedef struct sdpgpu_batch_stats {
+  int32_t instances;
+  int32_t periods_run;       /* period launches since the last sdpgpu_batch_solve began */
+  int32_t period_launches;   /* launches of the period kernel by the last solve: T -- one per period for all instances */
+  int32_t finalize_launches; /* other launches of the last solve: 0 when no period chunks the action axis (large n), else the
+                                reset of the key rows and the one finalize pass */
+  int32_t window_r;          /* register block of period 1's plan: actions ... */
+  int32_t window_s;          /* ... x adjacent states per lane */
+  int32_t window_chunks;     /* largest number of action chunks per state tile over the periods (1: no key atomics) */
+  int32_t reserved;
+  int64_t lds_bytes;         /* largest dynamic LDS per workgroup over the periods */
+  int64_t cells_evaluated;   /* sum over instances and periods of states x actions x D: what n handles would report */
+  double  solve_ms;          /* HIP-event time of the last sdpgpu_batch_solve on its stream */
+} sdpgpu_batch_stats;
+int sdpgpu_batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out);
+void sdpgpu_batch_destroy(sdpgpu_batch* b);
+const char* sdpgpu_batch_last_error(const sdpgpu_batch* b);
+/* pmf of period index t (0-based, as sdpgpu_set_pmf takes it) of one instance.  n (= D) and demand[0] may differ between
+ * instances and between periods; demand[0] may be negative (GetPmf truncates a negative lower quantile toward zero,
+ * GetPmf.java:87: NormalDist(54, 16.2) has the support -6 .. 114).  Validated as sdpgpu_set_pmf does (multiples of step,
+ * strictly ascending); additionally the spacing must be exactly `step`, which the window needs. */
+int sdpgpu_batch_set_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, const double* demand, const double* prob, int32_t n);
+int sdpgpu_batch_set_stream(sdpgpu_batch* b, void* hip_stream);
+/* Record a HIP event between the period launches of the next solves (read back through sdpgpu_batch_period_ms). */
+int sdpgpu_batch_set_profiling(sdpgpu_batch* b, int32_t on);
+/* Whole backward sweep t = T..1 of all instances: T launches of the period kernel (+ the key reset and one finalize pass
+ * when the plan of a small batch chunks the action axis).  Asynchronous on the batch's stream unless `sync` != 0. */
+int sdpgpu_batch_solve(sdpgpu_batch* b, int32_t sync);
+int sdpgpu_batch_synchronize(sdpgpu_batch* b);
+/* V_period[0..n) / the arg-opt action INDEX table (action = index * step) of one instance (1-based period). */
+int sdpgpu_batch_values(sdpgpu_batch* b, int32_t instance, int32_t period, double* out, int64_t n);
+int sdpgpu_batch_policy(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* out, int64_t n);
+/* What the sweep mains record (CLSPTesting.java:115-118): V_1(ini_inventory_i) and its action INDEX for all n instances,
+ * gathered on the device and copied once. */
+int sdpgpu_batch_initial(sdpgpu_batch* b, double* out_value, int32_t* out_action_index);
+int sdpgpu_batch_stats_get(sdpgpu_batch* b, sdpgpu_batch_stats* out);
+/* Time of period t's launch in the last solve (ms; needs sdpgpu_batch_set_profiling), -1 when there is none. */
+double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -117,6 +117,15 @@ class SdpgpuPlan(C.Structure):
                 ("workgroups_per_cu", C.c_int32), ("lds_bytes", C.c_int64)]
 
 
+class SdpgpuBatchStats(C.Structure):
+    """struct sdpgpu_batch_stats (include/sdpgpu.h)."""
+
+    _fields_ = [("instances", C.c_int32), ("periods_run", C.c_int32), ("period_launches", C.c_int32),
+                ("finalize_launches", C.c_int32), ("window_r", C.c_int32), ("window_s", C.c_int32),
+                ("window_chunks", C.c_int32), ("reserved", C.c_int32), ("lds_bytes", C.c_int64),
+                ("cells_evaluated", C.c_int64), ("solve_ms", C.c_double)]
+
+
 def desc_defaults() -> SdpgpuDesc:
     """Python twin of sdpgpu_desc_init (usable without loading the library)."""
     d = SdpgpuDesc()
@@ -276,6 +285,19 @@ EXPORTS = {
     "sdpgpu_multi_set_table": (None, [C.POINTER(SdpgpuMultiTable)]),
     "sdpgpu_multicash_solve": (C.c_int, [C.POINTER(SdpgpuMulticash), _DP, _IP, _IP, _LP, _LP, _DP]),
     "sdpgpu_multixr_solve": (C.c_int, [C.POINTER(SdpgpuMulticash), C.c_double, _DP, _IP, _IP, _LP, _LP, _DP]),
+    "sdpgpu_batch_create": (C.c_int, [C.POINTER(SdpgpuDesc), C.c_int32, C.POINTER(_P)]),
+    "sdpgpu_batch_destroy": (None, [_P]),
+    "sdpgpu_batch_last_error": (C.c_char_p, [_P]),
+    "sdpgpu_batch_set_pmf": (C.c_int, [_P, C.c_int32, C.c_int32, _DP, _DP, C.c_int32]),
+    "sdpgpu_batch_set_stream": (C.c_int, [_P, _P]),
+    "sdpgpu_batch_set_profiling": (C.c_int, [_P, C.c_int32]),
+    "sdpgpu_batch_solve": (C.c_int, [_P, C.c_int32]),
+    "sdpgpu_batch_synchronize": (C.c_int, [_P]),
+    "sdpgpu_batch_values": (C.c_int, [_P, C.c_int32, C.c_int32, _DP, C.c_int64]),
+    "sdpgpu_batch_policy": (C.c_int, [_P, C.c_int32, C.c_int32, _IP, C.c_int64]),
+    "sdpgpu_batch_initial": (C.c_int, [_P, _DP, _IP]),
+    "sdpgpu_batch_stats_get": (C.c_int, [_P, C.POINTER(SdpgpuBatchStats)]),
+    "sdpgpu_batch_period_ms": (C.c_double, [_P, C.c_int32]),
 }
 
 _lib = None

@@ -1,0 +1,110 @@
+"""Thin object wrapper over one sdpgpu_batch (include/sdpgpu.h): N backorder-family instances of ONE grid shape, period t
+of all of them in one kernel launch -- the parameter sweeps of the reference's *Testing mains (CLSPTesting.java:33-141).
+
+`pmfs[i]` is instance i's `double[][][] pmf` (Recursion.java:38): pmfs[i][t][j] = [demand, prob].
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence
+
+import numpy as np
+
+from . import _abi
+from ._abi import SdpgpuBatchStats, SdpgpuDesc, SdpgpuError
+from .engine import _dp, _ip, split_pmf
+
+
+class SdpBatch:
+    """N independent problems of one shape on one GPU; results per instance are those of N SdpEngines, bit for bit."""
+
+    def __init__(self, descs: Sequence[SdpgpuDesc], pmfs, *, device: int = -1):
+        self._lib = _abi.load()
+        self._b = C.c_void_p()
+        descs = list(descs)
+        if len(descs) != len(pmfs):
+            raise ValueError(f"{len(descs)} descriptors but {len(pmfs)} pmfs")
+        arr = (SdpgpuDesc * max(len(descs), 1))()
+        for i, d in enumerate(descs):
+            C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(SdpgpuDesc))
+            if device >= 0:
+                arr[i].device = device
+        self.n = len(descs)
+        rc = self._lib.sdpgpu_batch_create(arr, self.n, C.byref(self._b))
+        if rc:
+            raise SdpgpuError(rc, self._lib.sdpgpu_batch_last_error(None).decode())
+        self.T = int(arr[0].periods)
+        self.step = float(arr[0].step)
+        self.num_states = int((arr[0].max_inventory - arr[0].min_inventory) / arr[0].step) + 1
+        try:
+            for i, pmf in enumerate(pmfs):
+                tiles = split_pmf(pmf)
+                if len(tiles) != self.T:
+                    raise ValueError(f"pmf of instance {i} has {len(tiles)} periods, the descriptors say {self.T}")
+                for t, (d, p) in enumerate(tiles):
+                    self._check(self._lib.sdpgpu_batch_set_pmf(self._b, i, t, _dp(d), _dp(p), len(d)))
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        if rc:
+            raise SdpgpuError(rc, self._lib.sdpgpu_batch_last_error(self._b).decode())
+
+    def close(self):
+        if getattr(self, "_b", None) is not None and self._b:
+            self._lib.sdpgpu_batch_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return self.n
+
+    def set_stream(self, hip_stream: int):
+        self._check(self._lib.sdpgpu_batch_set_stream(self._b, C.c_void_p(hip_stream)))
+
+    def set_profiling(self, on: bool):
+        self._check(self._lib.sdpgpu_batch_set_profiling(self._b, 1 if on else 0))
+
+    def solve(self, sync: bool = True):
+        self._check(self._lib.sdpgpu_batch_solve(self._b, 1 if sync else 0))
+
+    def synchronize(self):
+        self._check(self._lib.sdpgpu_batch_synchronize(self._b))
+
+    def values(self, i: int, period: int) -> np.ndarray:
+        out = np.empty(self.num_states, dtype=np.float64)
+        self._check(self._lib.sdpgpu_batch_values(self._b, i, period, _dp(out), len(out)))
+        return out
+
+    def policy(self, i: int, period: int) -> np.ndarray:
+        """Arg-opt action INDEX of every state (action = index * step)."""
+        out = np.empty(self.num_states, dtype=np.int32)
+        self._check(self._lib.sdpgpu_batch_policy(self._b, i, period, _ip(out), len(out)))
+        return out
+
+    def initial(self):
+        """(values[n], action_index[n]): V_1(ini_inventory_i) and its action index, all instances, one copy."""
+        val = np.empty(self.n, dtype=np.float64)
+        act = np.empty(self.n, dtype=np.int32)
+        self._check(self._lib.sdpgpu_batch_initial(self._b, _dp(val), _ip(act)))
+        return val, act
+
+    def stats(self) -> SdpgpuBatchStats:
+        st = SdpgpuBatchStats()
+        self._check(self._lib.sdpgpu_batch_stats_get(self._b, C.byref(st)))
+        return st
+
+    def period_ms(self, period: int) -> float:
+        return float(self._lib.sdpgpu_batch_period_ms(self._b, period))

@@ -1,0 +1,739 @@
+// sdpgpu_batch.hip -- a BATCH of backorder-family (F1) instances of one grid shape (include/sdpgpu.h, sdpgpu_batch_*): the
+// parameter sweeps of the reference's *Testing mains (capacitated.CLSPTesting.main: 540 instances of one grid).  Period t
+// of ALL instances runs in one launch of window_f1_batch_kernel (sdp_batch.hpp); this file holds the validation, the host
+// layout, the plan of a period, the launcher and the entry points.  Separate from sdpgpu_handle on purpose: a batch has no
+// slabs, no exchange, no user functors -- and the handle does not grow.
+#include "sdpgpu_internal.hpp"
+#include "sdp_batch.hpp"
+
+namespace sdpgpu_detail {
+int validate(const sdpgpu_desc& d);                 // sdpgpu.hip
+int32_t full_action_count(const sdpgpu_desc& d);    // sdpgpu.hip
+}  // namespace sdpgpu_detail
+
+// (R, S, chunks) of one period for the whole batch
+struct BatchPlan {
+  int R = 0, S = 0, n_chunks = 1, chunk_blocks = 0, n_tiles = 0, tasks_per_inst = 0, span_max = 0, p_slots_max = 0;
+  size_t smem = 0;
+};
+
+struct sdpgpu_batch {
+  std::vector<sdpgpu_desc> d;
+  int32_t N = 0, T = 0;
+  int32_t nx = 0, A = 0;  // states and actions of the shared grid
+  std::vector<double> d0;                  // [i * T + t]: first demand value
+  std::vector<std::vector<double>> pmf_p;  // [i * T + t]
+  std::vector<char> pmf_set;
+  int win_r = 0, win_s = 0, win_nch = 0;   // SDPGPU_WIN_R / _S / _NCH, read at create time as for a handle
+  bool laid_out = false, allocated = false, solved = false, profiling = false;
+  std::vector<BatchPlan> plan;             // [t]
+  std::vector<sdp::BatchInst> inst;        // [t * N + rank], longest demand first
+  std::vector<size_t> pmf_off;             // [i * T + t]
+  bool any_chunked = false;
+  size_t values_elems = 0, policy_elems = 0, pmf_elems = 0, key_elems = 0, chunk_elems = 0;
+  int64_t total_final = 0;                 // states the finalize pass resolves
+  std::vector<sdp::FinalizeJob> jobs;
+  int64_t cells = 0;
+  // device
+  int device = -1;
+  hipStream_t stream = nullptr;
+  bool own_stream = false, stream_given = false;
+  double* d_values = nullptr;
+  int32_t* d_policy = nullptr;
+  double* d_pmf = nullptr;
+  sdp::BatchInst* d_inst = nullptr;
+  unsigned long long* d_keys = nullptr;
+  double* d_chunk_val = nullptr;
+  int32_t* d_chunk_idx = nullptr;
+  sdp::FinalizeJob* d_jobs = nullptr;
+  int64_t* d_ini_off = nullptr;  // [2 N]: value and policy offsets of every instance's period-1 initial state
+  char* d_ini_out = nullptr;     // N doubles, then N int32
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::vector<hipEvent_t> ev_period;  // [T + 1] when profiling
+  bool timed = false, periods_timed = false;
+  int32_t period_launches = 0, finalize_launches = 0, periods_run = 0;
+  std::string err;
+};
+
+namespace {
+
+using namespace sdpgpu_detail;
+
+int bfail(sdpgpu_batch* b, int code, const char* fmt, ...) {
+  char buf[640];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (b)
+    b->err = buf;
+  else
+    g_create_error = buf;
+  return code;
+}
+
+#define BHIP_TRY(b, expr)                                                                              \
+  do {                                                                                                 \
+    hipError_t e_ = (expr);                                                                            \
+    if (e_ != hipSuccess) return bfail(b, SDPGPU_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+// No C++ exception crosses the C ABI: the same barrier as the two-product entry points (sdpgpu_sparse.hip).
+template <class F>
+int guarded(sdpgpu_batch* b, const char* who, F&& body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc&) {
+    return bfail(b, SDPGPU_ERR_ALLOC, "%s: host allocation failed (std::bad_alloc)", who);
+  } catch (const std::exception& e) {
+    return bfail(b, SDPGPU_ERR_INTERNAL, "%s: internal error: %s", who, e.what());
+  } catch (...) {
+    return bfail(b, SDPGPU_ERR_INTERNAL, "%s: internal error (unknown exception)", who);
+  }
+}
+
+// The batch's device for the length of a call; the caller's current device comes back at the end.
+struct DeviceScope {
+  int prev = -1;
+  bool switched = false;
+  hipError_t enter(int device) {
+    if (device < 0) return hipSuccess;
+    hipError_t e = hipGetDevice(&prev);
+    if (e != hipSuccess) return e;
+    if (prev == device) return hipSuccess;
+    e = hipSetDevice(device);
+    switched = e == hipSuccess;
+    return e;
+  }
+  ~DeviceScope() {
+    if (switched) (void)hipSetDevice(prev);
+  }
+};
+
+inline int rup(int v, int r) { return (v + r - 1) / r * r; }
+
+// The register blocks the planner may choose: R = 4 throughout (A = 501 pads to 504 with R = 4 or 8 alike, and the four
+// S cover tiles of 64 .. 512 states); `waves` = waves a SIMD holds within 512 VGPRs (hipcc's resource report).
+struct Cand {
+  int r, s, waves;
+};
+// (VGPRs with the future term: 59 / 73 / 125 / 240 for S = 1 / 2 / 4 / 8, no scratch)
+constexpr Cand kCand[] = {{4, 1, 8}, {4, 2, 6}, {4, 4, 4}, {4, 8, 2}};
+
+// One plan per period for the whole batch, by the reasoning of the single-handle planner (plan_window_search): a launch
+// costs what its busiest SIMD executes.  Tasks differ in length (D differs per instance) and are dispatched longest first,
+// so the estimate is the larger of the mean load per SIMD and the longest task, at the issue rate the resident waves
+// sustain, plus one shortest task for the tail.  Chunking the action axis (key atomics + finalize pass) is considered only
+// for a SMALL batch: when 64-state tiles alone give every SIMD four tasks (N * ceil(nx / 64) >= 4096) the plan is always one
+// task per (instance, tile) -- no key rows, no finalize launch.
+int plan_period(sdpgpu_batch* b, int t, BatchPlan* out) {
+  const int N = b->N, T = b->T, A = b->A, nx = b->nx;
+  int d_max = 0;
+  for (int i = 0; i < N; ++i) {
+    const int D = (int)b->pmf_p[(size_t)i * T + t].size();
+    d_max = std::max(d_max, D);
+  }
+  const bool may_chunk = b->d[0].store_all_values && (int64_t)N * ((nx + 63) / 64) < 4096;
+  BatchPlan best;
+  double best_cost = -1;
+  bool shape_seen = false;
+  size_t lds_least = 0;
+  for (const Cand& c : kCand) {
+    if (b->win_r && c.r != b->win_r) continue;
+    if (b->win_s && c.s != b->win_s) continue;
+    shape_seen = true;
+    const int r = c.r, sl = c.s, nw = r + sl - 1, ts = 64 * sl;
+    const int n_tiles = (nx + ts - 1) / ts;
+    const int blocks_total = rup(A, r) / r;
+    const double step_ops = 3.0 * r * sl + r + (r + sl - 1) + 3.0;  // fp64 instructions of one demand step of one R-block
+    int forced_nch = 0;
+    if (b->win_nch) {
+      const int want = std::max(1, std::min(b->win_nch, blocks_total));
+      const int bpc_w = (blocks_total + want - 1) / want;
+      forced_nch = (blocks_total + bpc_w - 1) / bpc_w;
+    }
+    for (int nch = 1; nch <= blocks_total; ++nch) {
+      if (forced_nch && nch != forced_nch) continue;
+      const int bpc = (blocks_total + nch - 1) / nch;
+      if ((blocks_total + bpc - 1) / bpc != nch) continue;  // same plan as a smaller nch
+      if (nch > 1 && !may_chunk && !forced_nch) break;
+      if (nch > 1 && !b->d[0].store_all_values) break;  // chunk rows need every period's rows (as for a handle)
+      const int span_max = ts + bpc * r + rup(d_max, nw) + sl;
+      const int p_slots = sdp::win_p_slots(d_max);
+      const size_t smem = sdp::batch_wg_lds(span_max, p_slots);
+      const int wg = std::min(c.waves, lds_workgroups(smem));
+      if (wg < 1) {
+        lds_least = lds_least ? std::min(lds_least, smem) : smem;
+        continue;
+      }
+      double total = 0, longest = 0, shortest = 0;
+      for (int i = 0; i < N; ++i) {
+        const int D = (int)b->pmf_p[(size_t)i * T + t].size();
+        const double task = bpc * (D * step_ops + 60.0 + 2.0 * (sl - 1) * r) + 400.0 + 4.0 * (ts + bpc * r + rup(D, nw) + sl);
+        total += task;
+        longest = std::max(longest, task);
+        shortest = shortest == 0 ? task : std::min(shortest, task);
+      }
+      const int64_t tasks = (int64_t)N * n_tiles * nch;
+      total *= (double)n_tiles * nch;
+      const int64_t resident = std::min<int64_t>(wg, (tasks + 1023) / 1024);
+      auto eff = [&](int64_t w) { return w >= 8 ? 0.97 : (w >= 4 ? 0.94 : (w >= 3 ? 0.91 : (w >= 2 ? (r * sl >= 32 ? 0.93 : 0.85) : 0.60))); };
+      const double cost = std::max(total / 1024.0, longest) / eff(resident) + shortest / 0.60;
+      if (best_cost < 0 || cost < best_cost * 0.999) {
+        best_cost = cost;
+        best.R = r;
+        best.S = sl;
+        best.n_chunks = nch;
+        best.chunk_blocks = bpc;
+        best.n_tiles = n_tiles;
+        best.tasks_per_inst = n_tiles * nch;
+        best.span_max = span_max;
+        best.p_slots_max = p_slots;
+        best.smem = smem;
+      }
+    }
+  }
+  if (!best.R) {
+    if (!shape_seen)
+      return bfail(b, SDPGPU_ERR_ARG, "batch kernel: no instantiation for the forced block SDPGPU_WIN_R=%d SDPGPU_WIN_S=%d (have R x S = 4x1 4x2 4x4 4x8)",
+                   b->win_r, b->win_s);
+    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "batch kernel: %d actions x %d demand steps (period %d) need %zu B of LDS per workgroup, over the %zu B of a "
+                 "compute unit", A, d_max, t + 1, lds_least, kLdsPerCU);
+  }
+  if ((int64_t)N * best.tasks_per_inst > INT32_MAX / 2) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "batch kernel: too many tasks in one launch");
+  *out = best;
+  return SDPGPU_OK;
+}
+
+size_t value_row(const sdpgpu_batch* b, int i, int t) {
+  if (b->d[0].store_all_values) return ((size_t)i * b->T + t) * (size_t)b->nx;
+  return ((size_t)i * 2 + (size_t)(t & 1)) * (size_t)b->nx;  // two ping-pong tables per instance
+}
+size_t policy_row(const sdpgpu_batch* b, int i, int t) { return ((size_t)i * b->T + t) * (size_t)b->nx; }
+
+// host layout: plans, arena offsets, the per-(period, instance) records in task order, the finalize jobs
+int layout(sdpgpu_batch* b) {
+  if (b->laid_out) return SDPGPU_OK;
+  const int N = b->N, T = b->T;
+  for (int i = 0; i < N; ++i)
+    for (int t = 0; t < T; ++t)
+      if (!b->pmf_set[(size_t)i * T + t]) return bfail(b, SDPGPU_ERR_STATE, "pmf of instance %d, period %d not set", i, t + 1);
+  b->plan.assign((size_t)T, BatchPlan());
+  b->any_chunked = false;
+  for (int t = 0; t < T; ++t) {
+    int rc = plan_period(b, t, &b->plan[(size_t)t]);
+    if (rc) return rc;
+    if (b->plan[(size_t)t].n_chunks > 1) b->any_chunked = true;
+  }
+  b->values_elems = (size_t)N * (b->d[0].store_all_values ? T : 2) * (size_t)b->nx;
+  b->policy_elems = (size_t)N * T * (size_t)b->nx;
+  b->pmf_off.assign((size_t)N * T, 0);
+  size_t off = 0;
+  b->cells = 0;
+  for (int i = 0; i < N; ++i)
+    for (int t = 0; t < T; ++t) {
+      b->pmf_off[(size_t)i * T + t] = off;
+      const size_t D = b->pmf_p[(size_t)i * T + t].size();
+      off += D + kPmfPad;  // the probabilities are followed by kPmfPad zeros
+      b->cells += (int64_t)b->nx * b->A * (int64_t)D;
+    }
+  b->pmf_elems = off;
+  b->key_elems = b->any_chunked ? (size_t)N * T * (size_t)b->nx : 0;
+  b->inst.assign((size_t)T * N, sdp::BatchInst());
+  b->jobs.clear();
+  size_t chunk_off = 0;
+  int64_t first = 0;
+  std::vector<int> order((size_t)N);
+  for (int t = 0; t < T; ++t) {
+    const BatchPlan& pl = b->plan[(size_t)t];
+    const int nw = pl.R + pl.S - 1;
+    for (int i = 0; i < N; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int c) {
+      return b->pmf_p[(size_t)a * T + t].size() > b->pmf_p[(size_t)c * T + t].size();
+    });
+    for (int rank = 0; rank < N; ++rank) {
+      const int i = order[(size_t)rank];
+      const sdpgpu_desc& d = b->d[(size_t)i];
+      const int D = (int)b->pmf_p[(size_t)i * T + t].size();
+      sdp::BatchInst I{};
+      const double d0 = b->d0[(size_t)i * T + t];
+      I.lev0 = d.min_inventory - d0;
+      I.h = d.holding_cost;
+      I.pi = d.penalty_cost;
+      I.K = d.fixed_order_cost;
+      I.v = d.unit_order_cost;
+      I.idx_off = (int32_t)((I.lev0 - d.min_inventory) / d.step);
+      I.n_demand = D;
+      I.d_pad = rup(D, nw);
+      I.d_main = D / nw * nw;
+      I.pmf_off = (int64_t)b->pmf_off[(size_t)i * T + t];
+      I.v_cur_off = (int64_t)value_row(b, i, t);
+      I.v_next_off = t + 1 < T ? (int64_t)value_row(b, i, t + 1) : 0;
+      I.pol_off = (int64_t)policy_row(b, i, t);
+      I.key_cur_off = (int64_t)(((size_t)i * T + t) * (size_t)b->nx);
+      I.key_next_off = t + 1 < T ? (int64_t)(((size_t)i * T + t + 1) * (size_t)b->nx) : 0;
+      I.chunk_off = 0;
+      if (pl.n_chunks > 1) {
+        I.chunk_off = (int64_t)chunk_off;
+        chunk_off += (size_t)pl.n_chunks * (size_t)b->nx;
+        sdp::FinalizeJob J{};
+        J.stride = b->nx;
+        J.lo = J.vlo = 0;
+        J.hi = J.vhi = b->nx;
+        J.first = first;
+        J.n_chunks = pl.n_chunks;
+        // (device addresses are filled in at allocation; the offsets travel in the pointer fields until then)
+        J.keys = reinterpret_cast<const unsigned long long*>((uintptr_t)I.key_cur_off);
+        J.part_val = reinterpret_cast<const double*>((uintptr_t)I.chunk_off);
+        J.v_out = reinterpret_cast<double*>((uintptr_t)I.v_cur_off);
+        J.pol_out = reinterpret_cast<int32_t*>((uintptr_t)I.pol_off);
+        first += b->nx;
+        b->jobs.push_back(J);
+      }
+      b->inst[(size_t)t * N + rank] = I;
+    }
+  }
+  b->chunk_elems = chunk_off;
+  b->total_final = first;
+  b->laid_out = true;
+  return SDPGPU_OK;
+}
+
+int allocate(sdpgpu_batch* b) {
+  if (b->allocated) return SDPGPU_OK;
+  int rc = layout(b);
+  if (rc) return rc;
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev < 1)
+    return bfail(b, SDPGPU_ERR_DEVICE, "no HIP device available (%s); this library has no CPU path",
+                 e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+  if (!b->stream && !b->stream_given) {
+    BHIP_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    b->own_stream = true;
+  }
+  const int N = b->N, T = b->T;
+  BHIP_TRY(b, hipMalloc((void**)&b->d_values, std::max<size_t>(b->values_elems, 1) * sizeof(double)));
+  BHIP_TRY(b, hipMalloc((void**)&b->d_policy, std::max<size_t>(b->policy_elems, 1) * sizeof(int32_t)));
+  BHIP_TRY(b, hipMalloc((void**)&b->d_pmf, std::max<size_t>(b->pmf_elems, 1) * sizeof(double)));
+  {
+    std::vector<double> host(b->pmf_elems, 0.0);
+    for (size_t k = 0; k < (size_t)N * T; ++k)
+      std::memcpy(&host[b->pmf_off[k]], b->pmf_p[k].data(), b->pmf_p[k].size() * sizeof(double));
+    BHIP_TRY(b, hipMemcpy(b->d_pmf, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  BHIP_TRY(b, hipMalloc((void**)&b->d_inst, b->inst.size() * sizeof(sdp::BatchInst)));
+  BHIP_TRY(b, hipMemcpy(b->d_inst, b->inst.data(), b->inst.size() * sizeof(sdp::BatchInst), hipMemcpyHostToDevice));
+  if (b->any_chunked) {
+    BHIP_TRY(b, hipMalloc((void**)&b->d_keys, b->key_elems * sizeof(unsigned long long)));
+    BHIP_TRY(b, hipMalloc((void**)&b->d_chunk_val, std::max<size_t>(b->chunk_elems, 1) * sizeof(double)));
+    BHIP_TRY(b, hipMalloc((void**)&b->d_chunk_idx, std::max<size_t>(b->chunk_elems, 1) * sizeof(int32_t)));
+    std::vector<sdp::FinalizeJob> jobs = b->jobs;
+    for (sdp::FinalizeJob& J : jobs) {
+      const size_t chunk_off = (size_t)(uintptr_t)J.part_val;
+      J.keys = b->d_keys + (size_t)(uintptr_t)J.keys;
+      J.part_val = b->d_chunk_val + chunk_off;
+      J.part_idx = b->d_chunk_idx + chunk_off;
+      J.v_out = b->d_values + (size_t)(uintptr_t)J.v_out;
+      J.pol_out = b->d_policy + (size_t)(uintptr_t)J.pol_out;
+    }
+    BHIP_TRY(b, hipMalloc((void**)&b->d_jobs, jobs.size() * sizeof(sdp::FinalizeJob)));
+    BHIP_TRY(b, hipMemcpy(b->d_jobs, jobs.data(), jobs.size() * sizeof(sdp::FinalizeJob), hipMemcpyHostToDevice));
+  }
+  {
+    // the period-1 initial state of every instance (validated at create: a grid point)
+    std::vector<int64_t> offs((size_t)2 * N);
+    for (int i = 0; i < N; ++i) {
+      const sdpgpu_desc& d = b->d[(size_t)i];
+      const int64_t ix = (int64_t)((d.ini_inventory - d.min_inventory) / d.step);
+      offs[(size_t)i] = (int64_t)value_row(b, i, 0) + ix;
+      offs[(size_t)N + i] = (int64_t)policy_row(b, i, 0) + ix;
+    }
+    BHIP_TRY(b, hipMalloc((void**)&b->d_ini_off, offs.size() * sizeof(int64_t)));
+    BHIP_TRY(b, hipMemcpy(b->d_ini_off, offs.data(), offs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    BHIP_TRY(b, hipMalloc((void**)&b->d_ini_out, (size_t)N * 12));
+  }
+  BHIP_TRY(b, hipEventCreate(&b->ev0));
+  BHIP_TRY(b, hipEventCreate(&b->ev1));
+  b->allocated = true;
+  return SDPGPU_OK;
+}
+
+template <int R, int S>
+hipError_t launch_rs(sdpgpu_batch* b, const sdp::BatchLaunch& L, const BatchPlan& pl, const sdp::BatchInst* inst, bool future,
+                     bool keyed_in) {
+  const dim3 grid((unsigned)((L.n_tasks + 3) / 4));
+#define SDP_BATCH_GO(FU, KI)                                                                                         \
+  do {                                                                                                               \
+    static LdsMark mark;                                                                                             \
+    hipError_t ea = lds_allow(sdp::window_f1_batch_kernel<R, S, FU, KI>, pl.smem, &mark);                            \
+    if (ea != hipSuccess) return ea;                                                                                 \
+    hipLaunchKernelGGL((sdp::window_f1_batch_kernel<R, S, FU, KI>), grid, dim3(256), pl.smem, b->stream, L, inst,    \
+                       b->d_values, b->d_policy, b->d_pmf, b->d_keys, b->d_chunk_val, b->d_chunk_idx);               \
+  } while (0)
+  if (!future)
+    SDP_BATCH_GO(false, false);
+  else if (keyed_in)
+    SDP_BATCH_GO(true, true);
+  else
+    SDP_BATCH_GO(true, false);
+#undef SDP_BATCH_GO
+  return hipGetLastError();
+}
+
+hipError_t launch_period(sdpgpu_batch* b, int t) {
+  const BatchPlan& pl = b->plan[(size_t)t];
+  sdp::BatchLaunch L{};
+  L.step = b->d[0].step;
+  L.n_states = b->nx;
+  L.n_actions = b->A;
+  L.n_tiles = pl.n_tiles;
+  L.n_chunks = pl.n_chunks;
+  L.chunk_blocks = pl.chunk_blocks;
+  L.tasks_per_inst = pl.tasks_per_inst;
+  L.n_tasks = b->N * pl.tasks_per_inst;
+  L.span_max = pl.span_max;
+  L.p_slots_max = pl.p_slots_max;
+  L.maxdir = b->d[0].direction == SDPGPU_MAX;
+  if (!grid_ok((L.n_tasks + 3) / 4)) return hipErrorInvalidValue;
+  const bool future = t + 1 < b->T;
+  // V_{t+1} is read from its key row while that period's final rows are still pending (they are written by the one
+  // finalize pass at the end of the sweep)
+  const bool keyed_in = future && b->plan[(size_t)t + 1].n_chunks > 1;
+  const sdp::BatchInst* inst = b->d_inst + (size_t)t * b->N;
+  if (pl.R == 4 && pl.S == 1) return launch_rs<4, 1>(b, L, pl, inst, future, keyed_in);
+  if (pl.R == 4 && pl.S == 2) return launch_rs<4, 2>(b, L, pl, inst, future, keyed_in);
+  if (pl.R == 4 && pl.S == 4) return launch_rs<4, 4>(b, L, pl, inst, future, keyed_in);
+  if (pl.R == 4 && pl.S == 8) return launch_rs<4, 8>(b, L, pl, inst, future, keyed_in);
+  return hipErrorInvalidValue;
+}
+
+// what differs between instance k and instance 0 although the batch needs it shared (nullptr: nothing)
+const char* shape_mismatch(const sdpgpu_desc& a, const sdpgpu_desc& c, char* buf, size_t n) {
+#define SDP_SAME_I(f) \
+  if (a.f != c.f) { std::snprintf(buf, n, #f " %d differs from instance 0's %d", (int)c.f, (int)a.f); return buf; }
+#define SDP_SAME_D(f) \
+  if (a.f != c.f) { std::snprintf(buf, n, #f " %g differs from instance 0's %g", (double)c.f, (double)a.f); return buf; }
+  SDP_SAME_I(direction)
+  SDP_SAME_I(periods)
+  SDP_SAME_D(step)
+  SDP_SAME_D(min_inventory)
+  SDP_SAME_D(max_inventory)
+  SDP_SAME_D(max_order_quantity)
+  SDP_SAME_I(device)
+  SDP_SAME_I(store_all_values)
+#undef SDP_SAME_I
+#undef SDP_SAME_D
+  return nullptr;
+}
+
+}  // namespace
+
+// =================================================================================================
+// C ABI
+// =================================================================================================
+extern "C" {
+
+int sdpgpu_batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out) {
+  g_create_error.clear();
+  if (!descs || !out) return bfail(nullptr, SDPGPU_ERR_ARG, "batch_create: null argument (descs, out)");
+  *out = nullptr;
+  if (n < 1 || n > 1000000) return bfail(nullptr, SDPGPU_ERR_ARG, "batch_create: n = %d instances (1 .. 1000000)", n);
+  return guarded(nullptr, "sdpgpu_batch_create", [&]() -> int {
+    for (int32_t k = 0; k < n; ++k) {
+      const sdpgpu_desc& d = descs[k];
+      int rc = validate(d);
+      if (rc) {
+        const std::string why = g_create_error;
+        return bfail(nullptr, rc, "instance %d: %s", k, why.c_str());
+      }
+      if (d.family != SDPGPU_FAMILY_BACKORDER)
+        return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "instance %d: family %d -- a batch holds the backorder family (SDPGPU_FAMILY_BACKORDER) only", k, d.family);
+      if (!d.clamp_inventory)
+        return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "instance %d: clamp_inventory = 0 -- a batch needs one fixed grid for all periods", k);
+      if (d.world_size != 1)
+        return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "instance %d: world_size %d -- a batch runs on one device (split the instance list per rank on the host)", k, d.world_size);
+      if (d.kernel != SDPGPU_KERNEL_AUTO && d.kernel != SDPGPU_KERNEL_WINDOW)
+        return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "instance %d: kernel %d -- a batch runs the window kernel (SDPGPU_KERNEL_AUTO or _WINDOW)", k, d.kernel);
+      char buf[160];
+      if (const char* why = shape_mismatch(descs[0], d, buf, sizeof buf))
+        return bfail(nullptr, SDPGPU_ERR_ARG, "instance %d: %s (the instances of a batch share one grid shape)", k, why);
+      if (std::fmod(d.ini_inventory, d.step) != 0 || d.ini_inventory < d.min_inventory || d.ini_inventory > d.max_inventory)
+        return bfail(nullptr, SDPGPU_ERR_ARG, "instance %d: ini_inventory %g is not a point of the grid [%g, %g]", k, d.ini_inventory, d.min_inventory, d.max_inventory);
+    }
+    const sdpgpu_desc& d = descs[0];
+    const int64_t nx = (int64_t)((d.max_inventory - d.min_inventory) / d.step) + 1;
+    const int32_t A = full_action_count(d);
+    if (nx >= 2147483647LL - 4096 || (int64_t)A + nx > 2000000000LL) return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "axis longer than 2^31");
+    if ((double)nx * d.periods * n > 4.0e9) return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "batch tables of %d x %d x %lld states are too large", n, d.periods, (long long)nx);
+    sdpgpu_batch* b = new sdpgpu_batch();
+    try {
+      b->d.assign(descs, descs + n);
+      b->N = n;
+      b->T = d.periods;
+      b->nx = (int32_t)nx;
+      b->A = A;
+      b->device = d.device;
+      b->d0.assign((size_t)n * b->T, 0.0);
+      b->pmf_p.resize((size_t)n * b->T);
+      b->pmf_set.assign((size_t)n * b->T, 0);
+      if (const char* e = std::getenv("SDPGPU_WIN_R")) b->win_r = std::atoi(e);
+      if (const char* e = std::getenv("SDPGPU_WIN_NCH")) b->win_nch = std::atoi(e);
+      if (const char* e = std::getenv("SDPGPU_WIN_S")) b->win_s = std::atoi(e);
+    } catch (...) {
+      delete b;
+      throw;
+    }
+    *out = b;
+    return SDPGPU_OK;
+  });
+}
+
+void sdpgpu_batch_destroy(sdpgpu_batch* b) {
+  if (!b) return;
+  {
+    DeviceScope dev;
+    if (b->allocated || b->d_values || b->d_pmf) {
+      (void)dev.enter(b->device);
+      if (b->stream) (void)hipStreamSynchronize(b->stream);
+    }
+    if (b->ev0) (void)hipEventDestroy(b->ev0);
+    if (b->ev1) (void)hipEventDestroy(b->ev1);
+    for (hipEvent_t e : b->ev_period)
+      if (e) (void)hipEventDestroy(e);
+    if (b->d_values) (void)hipFree(b->d_values);
+    if (b->d_policy) (void)hipFree(b->d_policy);
+    if (b->d_pmf) (void)hipFree(b->d_pmf);
+    if (b->d_inst) (void)hipFree(b->d_inst);
+    if (b->d_keys) (void)hipFree(b->d_keys);
+    if (b->d_chunk_val) (void)hipFree(b->d_chunk_val);
+    if (b->d_chunk_idx) (void)hipFree(b->d_chunk_idx);
+    if (b->d_jobs) (void)hipFree(b->d_jobs);
+    if (b->d_ini_off) (void)hipFree(b->d_ini_off);
+    if (b->d_ini_out) (void)hipFree(b->d_ini_out);
+    if (b->stream && b->own_stream) (void)hipStreamDestroy(b->stream);
+  }
+  delete b;
+}
+
+const char* sdpgpu_batch_last_error(const sdpgpu_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+
+int sdpgpu_batch_set_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, const double* demand, const double* prob, int32_t n) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_set_pmf", [&]() -> int {
+    if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "batch_set_pmf: instance %d outside 0 .. %d", instance, b->N - 1);
+    if (t < 0 || t >= b->T) return bfail(b, SDPGPU_ERR_ARG, "batch_set_pmf: period index %d outside 0 .. %d", t, b->T - 1);
+    if (!demand || !prob || n < 1) return bfail(b, SDPGPU_ERR_ARG, "batch_set_pmf: bad argument (instance %d, t=%d, n=%d)", instance, t, n);
+    if (b->allocated) return bfail(b, SDPGPU_ERR_STATE, "pmf is frozen once the device tables exist");
+    const double step = b->d[0].step;
+    for (int32_t j = 0; j < n; ++j) {
+      if (std::fmod(demand[j], step) != 0)
+        return bfail(b, SDPGPU_ERR_ARG, "demand %g of instance %d, period %d is not a multiple of step", demand[j], instance, t + 1);
+      if (j && !(demand[j] > demand[j - 1]))
+        return bfail(b, SDPGPU_ERR_ARG, "demands of instance %d, period %d must be strictly ascending", instance, t + 1);
+      if (j && demand[j] - demand[j - 1] != step)
+        return bfail(b, SDPGPU_ERR_ARG, "demands of instance %d, period %d: spacing %g between points %d and %d, the batch kernel needs "
+                     "spacing = step (%g)", instance, t + 1, demand[j] - demand[j - 1], j - 1, j, step);
+    }
+    if (std::fabs(demand[0]) > 1.0e9 || n > 3000 || (int64_t)b->A + n > 3500)
+      return bfail(b, SDPGPU_ERR_UNSUPPORTED, "instance %d, period %d: %d actions + %d demand points exceed the window kernel's 3500", instance, t + 1, b->A, n);
+    const size_t k = (size_t)instance * b->T + t;
+    b->pmf_p[k].assign(prob, prob + n);
+    b->d0[k] = demand[0];
+    b->pmf_set[k] = 1;
+    b->laid_out = false;
+    return SDPGPU_OK;
+  });
+}
+
+int sdpgpu_batch_set_stream(sdpgpu_batch* b, void* hip_stream) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  if (b->own_stream && b->stream) {
+    DeviceScope dev;
+    BHIP_TRY(b, dev.enter(b->device));
+    (void)hipStreamSynchronize(b->stream);
+    (void)hipStreamDestroy(b->stream);
+  }
+  b->stream = (hipStream_t)hip_stream;
+  b->own_stream = false;
+  b->stream_given = true;
+  return SDPGPU_OK;
+}
+
+int sdpgpu_batch_set_profiling(sdpgpu_batch* b, int32_t on) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  b->profiling = on != 0;
+  return SDPGPU_OK;
+}
+
+int sdpgpu_batch_solve(sdpgpu_batch* b, int32_t sync) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_solve", [&]() -> int {
+    int rc = layout(b);  // (argument and state errors before the device is touched)
+    if (rc) return rc;
+    DeviceScope dev;
+    BHIP_TRY(b, dev.enter(b->device));
+    rc = allocate(b);
+    if (rc) return rc;
+    const int T = b->T;
+    if (b->profiling && b->ev_period.empty()) {
+      b->ev_period.assign((size_t)T + 1, nullptr);
+      for (hipEvent_t& e : b->ev_period) BHIP_TRY(b, hipEventCreate(&e));
+    }
+    b->period_launches = b->finalize_launches = b->periods_run = 0;
+    b->periods_timed = false;
+    BHIP_TRY(b, hipEventRecord(b->ev0, b->stream));
+    if (b->any_chunked) {  // key rows back to the reduction identity
+      const int64_t nk = (int64_t)b->key_elems;
+      if (!grid_ok((nk + 255) / 256)) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "key rows too long for one launch");
+      hipLaunchKernelGGL(sdp::batch_key_fill_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, b->stream, b->d_keys, nk,
+                         (int)(b->d[0].direction == SDPGPU_MAX));
+      BHIP_TRY(b, hipGetLastError());
+      b->finalize_launches++;
+    }
+    for (int t = T - 1; t >= 0; --t) {
+      if (b->profiling) BHIP_TRY(b, hipEventRecord(b->ev_period[(size_t)t + 1], b->stream));
+      hipError_t e = launch_period(b, t);
+      if (e != hipSuccess) return bfail(b, SDPGPU_ERR_DEVICE, "batch period %d: %s", t + 1, hipGetErrorString(e));
+      b->period_launches++;
+      b->periods_run++;
+    }
+    if (b->profiling) BHIP_TRY(b, hipEventRecord(b->ev_period[0], b->stream));
+    if (b->any_chunked && b->total_final > 0) {  // V_t = unkey(K_t), policy = action of the lowest chunk that attains it: one launch
+      if (!grid_ok((b->total_final + 255) / 256)) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "finalize pass too long for one launch");
+      hipLaunchKernelGGL(sdp::batch_finalize_kernel, dim3((unsigned)((b->total_final + 255) / 256)), dim3(256), 0, b->stream, b->d_jobs,
+                         (int)b->jobs.size(), b->total_final);
+      BHIP_TRY(b, hipGetLastError());
+      b->finalize_launches++;
+    }
+    BHIP_TRY(b, hipEventRecord(b->ev1, b->stream));
+    b->timed = true;
+    b->periods_timed = b->profiling;
+    b->solved = true;
+    if (sync) BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return SDPGPU_OK;
+  });
+}
+
+int sdpgpu_batch_synchronize(sdpgpu_batch* b) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  if (!b->allocated) return SDPGPU_OK;
+  DeviceScope dev;
+  BHIP_TRY(b, dev.enter(b->device));
+  BHIP_TRY(b, hipStreamSynchronize(b->stream));
+  return SDPGPU_OK;
+}
+
+static int read_check(sdpgpu_batch* b, const char* who, int32_t instance, int32_t period, const void* out, int64_t n, bool is_values) {
+  if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, b->N - 1);
+  if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, b->T);
+  if (!out || n < 0 || n > b->nx) return bfail(b, SDPGPU_ERR_ARG, "%s: bad output (n = %lld, the grid has %d states)", who, (long long)n, b->nx);
+  if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+  if (is_values && !b->d[0].store_all_values && period > 2)
+    return bfail(b, SDPGPU_ERR_STATE, "%s: V_%d was overwritten (store_all_values = 0 keeps two ping-pong tables: periods 1 and 2 survive)", who, period);
+  return SDPGPU_OK;
+}
+
+int sdpgpu_batch_values(sdpgpu_batch* b, int32_t instance, int32_t period, double* out, int64_t n) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  int rc = read_check(b, "sdpgpu_batch_values", instance, period, out, n, true);
+  if (rc) return rc;
+  DeviceScope dev;
+  BHIP_TRY(b, dev.enter(b->device));
+  BHIP_TRY(b, hipStreamSynchronize(b->stream));
+  BHIP_TRY(b, hipMemcpy(out, b->d_values + value_row(b, instance, period - 1), (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  return SDPGPU_OK;
+}
+
+int sdpgpu_batch_policy(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* out, int64_t n) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  int rc = read_check(b, "sdpgpu_batch_policy", instance, period, out, n, false);
+  if (rc) return rc;
+  DeviceScope dev;
+  BHIP_TRY(b, dev.enter(b->device));
+  BHIP_TRY(b, hipStreamSynchronize(b->stream));
+  BHIP_TRY(b, hipMemcpy(out, b->d_policy + policy_row(b, instance, period - 1), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return SDPGPU_OK;
+}
+
+int sdpgpu_batch_initial(sdpgpu_batch* b, double* out_value, int32_t* out_action_index) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  if (!out_value || !out_action_index) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_initial: null output");
+  if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "sdpgpu_batch_initial before sdpgpu_batch_solve");
+  return guarded(b, "sdpgpu_batch_initial", [&]() -> int {
+    DeviceScope dev;
+    BHIP_TRY(b, dev.enter(b->device));
+    const int N = b->N;
+    double* dv = reinterpret_cast<double*>(b->d_ini_out);
+    int32_t* di = reinterpret_cast<int32_t*>(b->d_ini_out + (size_t)N * 8);
+    hipLaunchKernelGGL(sdp::batch_initial_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, b->d_values, b->d_policy,
+                       b->d_ini_off, b->d_ini_off + N, N, dv, di);
+    BHIP_TRY(b, hipGetLastError());
+    std::vector<char> host((size_t)N * 12);
+    BHIP_TRY(b, hipMemcpyAsync(host.data(), b->d_ini_out, host.size(), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    std::memcpy(out_value, host.data(), (size_t)N * 8);
+    std::memcpy(out_action_index, host.data() + (size_t)N * 8, (size_t)N * 4);
+    return SDPGPU_OK;
+  });
+}
+
+int sdpgpu_batch_stats_get(sdpgpu_batch* b, sdpgpu_batch_stats* out) {
+  if (!b || !out) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_stats_get", [&]() -> int {
+    std::memset(out, 0, sizeof *out);
+    out->instances = b->N;
+    out->periods_run = b->periods_run;
+    out->period_launches = b->period_launches;
+    out->finalize_launches = b->finalize_launches;
+    bool all_set = true;
+    for (char c : b->pmf_set) all_set = all_set && c;
+    if (all_set) {  // the plan is host arithmetic: available before anything has run
+      int rc = layout(b);
+      if (rc) return rc;
+      out->window_r = b->plan[0].R;
+      out->window_s = b->plan[0].S;
+      for (const BatchPlan& p : b->plan) {
+        out->window_chunks = std::max(out->window_chunks, p.n_chunks);
+        out->lds_bytes = std::max<int64_t>(out->lds_bytes, (int64_t)p.smem);
+      }
+      out->cells_evaluated = b->solved ? b->cells : 0;
+    }
+    if (b->timed) {
+      DeviceScope dev;
+      BHIP_TRY(b, dev.enter(b->device));
+      BHIP_TRY(b, hipEventSynchronize(b->ev1));
+      float ms = 0;
+      BHIP_TRY(b, hipEventElapsedTime(&ms, b->ev0, b->ev1));
+      out->solve_ms = ms;
+    }
+    return SDPGPU_OK;
+  });
+}
+
+double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period) {
+  if (!b) return -1.0;
+  b->err.clear();
+  if (period < 1 || period > b->T || !b->periods_timed) {
+    (void)bfail(b, SDPGPU_ERR_STATE, "sdpgpu_batch_period_ms: period %d has no timing (sdpgpu_batch_set_profiling before the solve)", period);
+    return -1.0;
+  }
+  DeviceScope dev;
+  if (dev.enter(b->device) != hipSuccess) return -1.0;
+  // period t was launched between the events t and t - 1 (the sweep runs t = T .. 1)
+  if (hipEventSynchronize(b->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, b->ev_period[(size_t)period], b->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
+  return ms;
+}
+
+}  // extern "C"

@@ -388,3 +388,75 @@ class CashLeadtimeRecursion(_GpuRecursionBase):
 
     def _ncols(self):
         return 5
+
+
+class RecursionBatch:
+    """Many sdp.inventory.Recursion objects of ONE grid shape behind one solve: the body of a parameter sweep such as
+    capacitated.CLSPTesting.main (CLSPTesting.java:58-118), which builds a Recursion per parameter set and asks each for
+    getExpectedValue(initialState) and getAction(initialState).  `functors[i]` / `pmfs[i]` describe instance i (backorder
+    family, same inventory bounds, order limit, step and horizon; costs, initial inventory and demand tiles are the
+    instance's own).  The first query runs period t of ALL instances in one kernel launch per period (SdpBatch); every
+    instance's answers are those of its own Recursion, bit for bit.  There is no CPU fallback."""
+
+    def __init__(self, functors, pmfs, optDirection: OptDirection = OptDirection.MIN, device: int = -1):
+        from .batch import SdpBatch
+        self.functors = list(functors)
+        self.pmfs = pmfs  # shared by reference, never copied (Recursion.java:54)
+        if not self.functors:
+            raise ValueError("a batch needs at least one instance")
+        if len(self.functors) != len(pmfs):
+            raise ValueError(f"{len(self.functors)} functors but {len(pmfs)} pmfs")
+        self.optDirection = optDirection
+        self.T = len(pmfs[0])
+        descs = [f.to_desc(self.T, optDirection) for f in self.functors]
+        self._batch = SdpBatch(descs, pmfs, device=device)
+        self._solved = False
+        self._values: Dict[tuple, np.ndarray] = {}
+        self._policy: Dict[tuple, np.ndarray] = {}
+        self._initial = None
+
+    def __len__(self):
+        return len(self.functors)
+
+    @property
+    def batch(self):
+        return self._batch
+
+    def close(self):
+        self._batch.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _solve(self):
+        if not self._solved:
+            self._batch.solve(sync=True)
+            self._solved = True
+
+    def _lookup(self, i: int, state):
+        self._solve()
+        f = self.functors[i]
+        period = state.getPeriod()
+        if period < 1 or period > self.T:
+            raise IndexError(f"period {period} outside 1..{self.T}")
+        x = state.getIniInventory()
+        pos = (x - f.minInventory) / f.stepSize
+        if pos != int(pos) or not 0 <= pos < self._batch.num_states:
+            raise ValueError(f"state {x} is not a point of the batch's grid [{f.minInventory}, {f.maxInventory}]")
+        if period == 1 and x == f.iniInventory:  # what a sweep asks of every instance: one gathered copy for all of them
+            if self._initial is None:
+                self._initial = self._batch.initial()
+            return float(self._initial[0][i]), int(self._initial[1][i])
+        if (i, period) not in self._values:
+            self._values[(i, period)] = self._batch.values(i, period)
+            self._policy[(i, period)] = self._batch.policy(i, period)
+        return float(self._values[(i, period)][int(pos)]), int(self._policy[(i, period)][int(pos)])
+
+    def getExpectedValue(self, i: int, state) -> float:
+        return self._lookup(i, state)[0]
+
+    def getAction(self, i: int, state) -> float:
+        return self._lookup(i, state)[1] * self.functors[i].stepSize

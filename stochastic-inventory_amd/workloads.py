@@ -253,6 +253,53 @@ def custom_clsp_level(**kw) -> Workload:
     return w
 
 
+# capacitated.CLSPTesting.main (CLSPTesting.java:33-56): the mean demands of its ten demand patterns and its cost grid
+CLSP_TESTING_DEMANDS = (
+    (10, 10, 10, 10, 10, 10, 10, 10),
+    (15, 16, 15, 14, 11, 7, 6, 3),
+    (3, 6, 7, 11, 14, 15, 16, 15),
+    (15, 4, 4, 10, 18, 4, 4, 10),
+    (12, 7, 7, 10, 13, 7, 7, 12),
+    (2, 4, 7, 3, 10, 10, 3, 3),
+    (5, 15, 26, 44, 24, 15, 22, 10),
+    (4, 23, 28, 50, 39, 26, 19, 32),
+    (11, 14, 7, 11, 16, 31, 11, 48),
+    (18, 6, 22, 22, 51, 54, 22, 21),
+)
+CLSP_TESTING_K = (200.0, 300.0, 400.0)
+CLSP_TESTING_V = (0.0, 1.0)
+CLSP_TESTING_PAI = (5.0, 10.0, 20.0)
+CLSP_TESTING_COEVAR = (0.1, 0.2, 0.3)
+
+
+def clsp_testing_sweep(patterns=None) -> List[Workload]:
+    """The instances of capacitated.CLSPTesting.main in its loop order (demand pattern, v, pai, K, coeVar;
+    CLSPTesting.java:58-62): 10 x 2 x 3 x 3 x 3 = 540 F1 problems of ONE grid -- x in [-500, 500], orders 0..500, T = 8,
+    h = 1, NormalDist(mean, coeVar * mean) demands through GetPmf at the 0.9999 quantile.  `patterns`: a subset of the
+    demand patterns, numbered 1..10 as the reference's result file numbers them (54 instances each).  Every workload
+    carries `pattern` and `coeVar`.  With coeVar 0.3 a mean of 9 or more puts the lower quantile below zero and GetPmf's
+    (int) cast truncates it toward zero (GetPmf.java:87): those supports start at a negative demand."""
+    from .pmf import GetPmf, NormalDist
+    out = []
+    tiles = {}  # (pattern, coeVar) -> pmf: the 18 cost combinations of a pattern share their demand tiles
+    for ip in (range(1, len(CLSP_TESTING_DEMANDS) + 1) if patterns is None else patterns):
+        mean = CLSP_TESTING_DEMANDS[ip - 1]
+        for v in CLSP_TESTING_V:
+            for pai in CLSP_TESTING_PAI:
+                for K in CLSP_TESTING_K:
+                    for cv in CLSP_TESTING_COEVAR:
+                        if (ip, cv) not in tiles:
+                            dists = [NormalDist(m, cv * m) for m in mean]
+                            tiles[(ip, cv)] = [np.asarray(t, dtype=np.float64) for t in GetPmf(dists, 0.9999, 1).getpmf()]
+                        f = BackorderFunctor(fixedOrderingCost=K, variOrderingCost=v, holdingCost=1, penaltyCost=pai,
+                                             minInventory=-500, maxInventory=500, maxOrderQuantity=500, iniInventory=0)
+                        w = Workload(f"clsp_testing_p{ip}_v{v:g}_pai{pai:g}_K{K:g}_cv{cv:g}", f, OptDirection.MIN,
+                                     tiles[(ip, cv)], "CLSPTesting.main instance")
+                        w.pattern, w.coeVar = ip, cv
+                        out.append(w)
+    return out
+
+
 def by_name(name: str, **kw) -> Workload:
     table = {"cfg1": cfg1_sS, "cfg2": cfg2_clsp, "cfg3": cfg3_cash, "cfg3t": cfg3_tenths, "cfg4": cfg4_leadtime,
              "cfg4p": cfg4_pipeline, "target": target_grid, "f5_spl": f5_single_product_leadtime, "staff": staff_testing,

@@ -1,0 +1,206 @@
+"""The batch object (sdpgpu_batch_*, include/sdpgpu.h) as far as it goes without a GPU: descriptor validation with
+instance index and field in the error text, sdpgpu_batch_set_pmf's checks, call-order errors, the host-side plan, and the
+CLSPTesting sweep the batch exists for (workloads.clsp_testing_sweep)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+
+@pytest.fixture(scope="module")
+def lib(sia):
+    return sia._abi.load()
+
+
+def _descs(sia, n, T=3, **kw):
+    arr = (sia.SdpgpuDesc * n)()
+    for i in range(n):
+        d = sia.desc_defaults()
+        d.periods = T
+        d.min_inventory, d.max_inventory, d.max_order_quantity = -20.0, 30.0, 12.0
+        d.fixed_order_cost, d.unit_order_cost, d.holding_cost, d.penalty_cost = 10.0 + i, float(i % 2), 1.0, 5.0 + i
+        for k, v in kw.items():
+            setattr(d, k, v)
+        C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(sia.SdpgpuDesc))
+    return arr
+
+
+def _create(lib, arr, n):
+    b = C.c_void_p()
+    rc = lib.sdpgpu_batch_create(arr, n, C.byref(b))
+    return rc, b, lib.sdpgpu_batch_last_error(None).decode()
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def test_a_well_formed_batch_creates_and_destroys(sia, lib):
+    rc, b, err = _create(lib, _descs(sia, 3), 3)
+    assert rc == 0 and b.value and err == ""
+    assert lib.sdpgpu_batch_last_error(b) == b""
+    lib.sdpgpu_batch_destroy(b)
+    lib.sdpgpu_batch_destroy(None)  # like free(NULL)
+    rc, b, _ = _create(lib, _descs(sia, 1), 1)  # n = 1 is legal
+    assert rc == 0
+    lib.sdpgpu_batch_destroy(b)
+
+
+def test_create_rejects_an_empty_or_null_list(sia, lib):
+    rc, b, err = _create(lib, _descs(sia, 1), 0)
+    assert rc == 1 and not b.value and "n = 0" in err
+    rc, b, err = _create(lib, None, 3)
+    assert rc == 1 and not b.value and "null" in err
+    assert lib.sdpgpu_batch_create(_descs(sia, 1), 1, None) == 1
+
+
+@pytest.mark.parametrize("field,value,code", [
+    ("max_inventory", 31.0, 1), ("min_inventory", -21.0, 1), ("periods", 4, 1), ("step", 2.0, 1),
+    ("max_order_quantity", 13.0, 1), ("direction", 1, 1), ("store_all_values", 0, 1), ("device", 3, 1),
+    ("family", 2, 4), ("clamp_inventory", 0, 4), ("world_size", 2, 4), ("kernel", 3, 4), ("kernel", 1, 4),
+])
+def test_create_names_the_instance_and_the_field(sia, lib, field, value, code):
+    arr = _descs(sia, 3)
+    if field == "step":  # (keep the bounds multiples of the new step: the mismatch is what must be reported)
+        arr[2].min_inventory, arr[2].max_inventory = -20.0, 30.0
+    setattr(arr[2], field, value)
+    rc, b, err = _create(lib, arr, 3)
+    assert rc == code and not b.value
+    assert "instance 2" in err and field in err, err
+
+
+def test_create_reports_an_invalid_descriptor_with_its_instance(sia, lib):
+    arr = _descs(sia, 2)
+    arr[1].abi_version = 5
+    rc, _, err = _create(lib, arr, 2)
+    assert rc == 1 and "instance 1" in err and "abi_version" in err
+    arr = _descs(sia, 2)
+    arr[1].ini_inventory = 31.0  # off the grid: sdpgpu_batch_initial could not answer
+    rc, _, err = _create(lib, arr, 2)
+    assert rc == 1 and "instance 1" in err and "ini_inventory" in err
+
+
+def test_set_pmf_validation(sia, lib):
+    rc, b, _ = _create(lib, _descs(sia, 2), 2)
+    assert rc == 0
+    try:
+        d = np.arange(4, dtype=np.float64)
+        p = np.full(4, 0.25)
+        err = lambda: lib.sdpgpu_batch_last_error(b).decode()
+        assert lib.sdpgpu_batch_set_pmf(b, 2, 0, _dp(d), _dp(p), 4) == 1 and "instance 2" in err()
+        assert lib.sdpgpu_batch_set_pmf(b, -1, 0, _dp(d), _dp(p), 4) == 1 and "instance -1" in err()
+        assert lib.sdpgpu_batch_set_pmf(b, 0, 3, _dp(d), _dp(p), 4) == 1 and "period index 3" in err()
+        assert lib.sdpgpu_batch_set_pmf(b, 0, -1, _dp(d), _dp(p), 4) == 1
+        assert lib.sdpgpu_batch_set_pmf(b, 0, 0, _dp(d), _dp(p), 0) == 1 and "n=0" in err()
+        assert lib.sdpgpu_batch_set_pmf(b, 0, 0, None, _dp(p), 4) == 1
+        desc = np.array([3.0, 2.0, 1.0, 0.0])
+        assert lib.sdpgpu_batch_set_pmf(b, 1, 1, _dp(desc), _dp(p), 4) == 1
+        assert "ascending" in err() and "instance 1" in err() and "period 2" in err()
+        wide = np.array([0.0, 2.0, 4.0, 6.0])  # a spacing of 2 x step: fine for a handle, not for the batch window
+        assert lib.sdpgpu_batch_set_pmf(b, 1, 0, _dp(wide), _dp(p), 4) == 1 and "spacing" in err()
+        frac = np.array([0.5, 1.5, 2.5, 3.5])
+        assert lib.sdpgpu_batch_set_pmf(b, 1, 0, _dp(frac), _dp(p), 4) == 1 and "multiple of step" in err()
+        neg = np.array([-2.0, -1.0, 0.0, 1.0])  # GetPmf's truncation toward zero: the support may start below zero
+        assert lib.sdpgpu_batch_set_pmf(b, 0, 0, _dp(neg), _dp(p), 4) == 0 and err() == ""
+        one = np.array([7.0])
+        assert lib.sdpgpu_batch_set_pmf(b, 0, 1, _dp(one), _dp(np.ones(1)), 1) == 0
+    finally:
+        lib.sdpgpu_batch_destroy(b)
+
+
+def test_results_before_a_solve_are_a_state_error(sia, lib):
+    rc, b, _ = _create(lib, _descs(sia, 2), 2)
+    assert rc == 0
+    try:
+        v = np.zeros(51)
+        k = np.zeros(51, dtype=np.int32)
+        kp = k.ctypes.data_as(C.POINTER(C.c_int32))
+        assert lib.sdpgpu_batch_values(b, 0, 1, _dp(v), 51) == 2
+        assert b"before sdpgpu_batch_solve" in lib.sdpgpu_batch_last_error(b)
+        assert lib.sdpgpu_batch_policy(b, 1, 3, kp, 51) == 2
+        assert lib.sdpgpu_batch_initial(b, _dp(v), kp) == 2
+        assert lib.sdpgpu_batch_values(b, 2, 1, _dp(v), 51) == 1  # argument errors come first
+        assert lib.sdpgpu_batch_values(b, 0, 4, _dp(v), 51) == 1
+        assert lib.sdpgpu_batch_values(b, 0, 1, _dp(v), 52) == 1
+        assert lib.sdpgpu_batch_solve(b, 1) == 2  # no pmf yet: says which
+        assert b"instance 0, period 1" in lib.sdpgpu_batch_last_error(b)
+        assert lib.sdpgpu_batch_synchronize(b) == 0  # nothing queued
+        assert lib.sdpgpu_batch_period_ms(b, 1) == -1.0
+    finally:
+        lib.sdpgpu_batch_destroy(b)
+
+
+def test_python_wrapper_raises_with_the_library_text(sia):
+    descs = [sia.BackorderFunctor(minInventory=-5, maxInventory=5 + i, maxOrderQuantity=3).to_desc(2) for i in range(2)]
+    tile = np.array([[0.0, 0.5], [1.0, 0.5]])
+    with pytest.raises(sia.SdpgpuError) as e:
+        sia.SdpBatch(descs, [[tile, tile]] * 2)
+    assert e.value.code == 1 and "instance 1" in e.value.message and "max_inventory" in e.value.message
+    with pytest.raises(ValueError):
+        sia.SdpBatch(descs[:1], [[tile, tile]] * 2)
+    with pytest.raises(sia.SdpgpuError) as e:
+        sia.SdpBatch(descs[:1], [[tile, np.array([[0.0, 0.5], [2.0, 0.5]])]])
+    assert "spacing" in e.value.message
+
+
+@pytest.fixture(scope="module")
+def sweep():
+    from stochastic_inventory_amd import workloads
+    return workloads.clsp_testing_sweep()
+
+
+def test_clsp_testing_sweep_has_the_reference_shape(sia, sweep):
+    assert len(sweep) == 540
+    negative = []
+    for w in sweep:
+        d = w.desc()
+        assert w.T == 8 and d.periods == 8 and d.family == sia.FAMILY_BACKORDER
+        assert int((d.max_inventory - d.min_inventory) / d.step) + 1 == 1001
+        assert int(d.max_order_quantity / d.step) + 1 == 501
+        assert d.holding_cost == 1 and d.ini_inventory == 0
+        for tile in w.pmf:
+            assert abs(tile[:, 1].sum() - 1.0) <= 1e-12
+            assert np.all(np.diff(tile[:, 0]) == 1.0)
+        negative.append(any(tile[0, 0] < 0 for tile in w.pmf))
+    assert sum(negative) == 180
+    assert all(neg == (w.coeVar == 0.3) for neg, w in zip(negative, sweep))
+    # the reference's loop order: demand pattern outermost, coeVar innermost (CLSPTesting.java:58-62)
+    assert [w.coeVar for w in sweep[:3]] == [0.1, 0.2, 0.3] and sweep[0].pattern == 1 and sweep[-1].pattern == 10
+    assert sweep[0].functor.fixedOrderingCost == 200 and sweep[3].functor.fixedOrderingCost == 300
+    assert len({(w.pattern, w.coeVar, w.functor.fixedOrderingCost, w.functor.variOrderingCost, w.functor.penaltyCost)
+                for w in sweep}) == 540
+
+
+def test_clsp_testing_subset_keeps_whole_patterns(sia):
+    from stochastic_inventory_amd import workloads
+    sub = workloads.clsp_testing_sweep(patterns=(1, 7))
+    assert len(sub) == 108 and {w.pattern for w in sub} == {1, 7}
+    assert sub[54].pmf[3][:, 0].min() < 0 or sub[56].pmf[3][:, 0].min() < 0  # pattern 7, mean 44, coeVar 0.3
+
+
+def test_the_sweep_plans_one_task_per_tile_and_no_finalize(sia, sweep):
+    """540 instances give every SIMD several tasks without cutting the action axis: one period-kernel launch per period,
+    no key rows, no finalize pass -- decided on the host, visible before anything runs."""
+    with sia.SdpBatch([w.desc() for w in sweep], [w.pmf for w in sweep]) as b:
+        st = b.stats()
+        assert st.instances == 540 and st.window_chunks == 1 and st.window_r == 4 and st.window_s in (1, 2, 4, 8)
+        assert 0 < st.lds_bytes <= 160 * 1024
+        assert st.period_launches == 0 and st.cells_evaluated == 0  # nothing has run
+    w = sweep[:1]
+    with sia.SdpBatch([w[0].desc()], [w[0].pmf]) as b:  # one instance of 1001 states: the action axis is cut
+        assert b.stats().window_chunks > 1
+    d = w[0].desc()
+    d.store_all_values = 0  # ping-pong tables cannot hold chunk rows, as for a handle
+    with sia.SdpBatch([d], [w[0].pmf]) as b:
+        assert b.stats().window_chunks == 1
+
+
+def test_recursion_batch_checks_its_arguments(sia):
+    tile = np.array([[0.0, 0.5], [1.0, 0.5]])
+    f = sia.BackorderFunctor(minInventory=-5, maxInventory=5, maxOrderQuantity=3)
+    with pytest.raises(ValueError):
+        sia.RecursionBatch([], [])
+    with pytest.raises(ValueError):
+        sia.RecursionBatch([f, f], [[tile]])
+    with sia.RecursionBatch([f, f], [[tile, tile]] * 2) as rb:
+        assert len(rb) == 2 and rb.T == 2 and len(rb.batch) == 2
