@@ -1,11 +1,8 @@
 // sdp_batch.hpp -- period kernel of a BATCH of backorder-family (F1) instances of one grid shape: period t of all N
 // instances in ONE launch (sdpgpu_batch_solve, sdpgpu_batch.hip).
 //
-// The per-cell arithmetic is window_f1_kernel's (sdp_window.hpp), operation for operation: a lane owns S adjacent states
-// and R actions in registers and walks the demand index j = 0..D-1 serially,
-//     imm = c0[r] + W.x;  t = p_j*imm;  acc += t;  u = p_j*W.y;  acc += u;
-// separate multiplies and adds, strict compare in ascending action order -- so every instance's tables are bit for bit
-// those of a single handle.  New is what surrounds it:
+// What a wave does with its task is window_f1_kernel's, by the very same code: f1_stage_window and f1_cells
+// (sdp_f1_cells.hpp) -- so every instance's tables are bit for bit those of a single handle.  New is what surrounds it:
 //
 //   * a TASK (one wave) is (instance, state tile, action chunk); tasks are packed four to a workgroup regardless of the
 //     instance, so a workgroup may hold four different instances.  Everything an instance owns -- its cost constants, the
@@ -19,16 +16,7 @@
 //
 // Global memory is written with ordinary vector stores from plain C++ only.
 #pragma once
-// sdp_window.hpp defines three non-template kernels, which a second translation unit cannot define again under the same
-// names.  This unit takes its own copies under batch_* names (it launches two of them: the key reset and the finalize
-// pass); the header itself stays as it is, its digest pins the stored counter summaries of the bench workloads.
-#define key_fill_kernel batch_key_fill_kernel
-#define finalize_kernel batch_finalize_kernel
-#define separable_f2_expand_kernel batch_unused_f2_expand_kernel
-#include "sdp_window.hpp"
-#undef key_fill_kernel
-#undef finalize_kernel
-#undef separable_f2_expand_kernel
+#include "sdp_f1_cells.hpp"
 
 namespace sdp {
 
@@ -73,7 +61,6 @@ __global__ __launch_bounds__(256) void window_f1_batch_kernel(BatchLaunch L, con
                                                               const double* __restrict__ pmf,
                                                               unsigned long long* __restrict__ keys,
                                                               double* __restrict__ chunk_val, int32_t* __restrict__ chunk_idx) {
-  constexpr int NW = R + S - 1;  // register window entries = demand steps per unrolled block
   constexpr int TS = 64 * S;     // states per tile
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -86,7 +73,7 @@ __global__ __launch_bounds__(256) void window_f1_batch_kernel(BatchLaunch L, con
   const int chunk = local / L.n_tiles;
   const int tile = local - chunk * L.n_tiles;
   const BatchInst& I = inst[rank];  // (wave-uniform)
-  // the instance's constants in the shape window_entry takes them
+  // the instance's constants in the shape the shared F1 code takes them (m_tab / c_tab null: the built-in CLSP costs)
   WinParams W{};
   W.lev0 = I.lev0;
   W.step = L.step;
@@ -101,6 +88,8 @@ __global__ __launch_bounds__(256) void window_f1_batch_kernel(BatchLaunch L, con
   W.d_main = I.d_main;
   W.n_demand = I.n_demand;
   W.chunk_blocks = L.chunk_blocks;
+  W.prio_fair = 1;  // (always: the resident waves of a SIMD are tasks of different lengths here)
+  W.maxdir = L.maxdir;
   const bool MAXDIR = L.maxdir != 0;
   const double* __restrict__ v_next = FUTURE && !KEYED_IN ? values + I.v_next_off : nullptr;
   const unsigned long long* __restrict__ k_next = KEYED_IN ? keys + I.key_next_off : nullptr;
@@ -114,170 +103,13 @@ __global__ __launch_bounds__(256) void window_f1_batch_kernel(BatchLaunch L, con
   const int i0 = tile * TS;
   const int kA = chunk * chunk_actions;
 
-  // stage this wave's window: slot q holds m = m_lo + q (four entries per pass, their loads in flight together; slots past
-  // the span are computed from clamped indices and land in the spare slot 0 -- see window_f1_kernel)
+  // stage this wave's window: slot q holds m = m_lo + q
   const int m_lo = i0 + kA - W.d_pad;
-  for (int q0 = lane; q0 < span; q0 += 256) {
-    double2 e[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) e[u] = window_entry<FUTURE, KEYED_IN>(W, v_next, k_next, m_lo + q0 + 64 * u);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) s_win[q0 + 64 * u < span ? q0 + 64 * u : 0] = e[u];
-  }
-  {
-    const int p_cnt = win_p_slots(W.n_demand) - 2;  // (the array ends in kPmfPad = 16 zeros: D + 3 stays inside)
-    for (int q0 = lane; q0 < p_cnt; q0 += 256) {
-      double pv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) pv[u] = pmf_p[q0 + 64 * u < p_cnt ? q0 + 64 * u : p_cnt - 1];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s_p[q0 + 64 * u < p_cnt ? q0 + 64 * u : p_cnt] = pv[u];
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
+  f1_stage_window<FUTURE, KEYED_IN>(W, v_next, k_next, pmf_p, s_win, s_p, span, m_lo, lane);
 
   double best[S];
   int bestk[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    best[s] = MAXDIR ? -1.7976931348623157e308 : 1.7976931348623157e308;
-    bestk[s] = 0;
-  }
-  for (int rb = 0; rb < W.chunk_blocks; ++rb) {
-    const int k0 = kA + rb * R;
-    if (k0 >= W.n_actions) break;
-    double c0[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      double a = (double)(k0 + r) * W.step;
-      c0[r] = (a > 0 ? W.K : 0.0) + W.v * a;  // fixedCost + variableCost (wave-uniform)
-    }
-    // slot of (lane, s, r, j):  S*lane + s + (k0 - kA) + r - j + d_pad;  window entry q at step j: base - j + q
-    const int base = S * lane + (k0 - kA) + W.d_pad;
-    double2 win[NW];
-    double acc[S][R];
-    double immc[S][R];  // immc[s][r], s >= 1: immediate cost of (state s, action r) at the current demand step
-#pragma unroll
-    for (int q = 0; q < NW; ++q) win[q] = s_win[base + q];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        acc[s][r] = 0.0;
-        immc[s][r] = c0[r] + win[r + s].x;  // (s = 0 unused)
-      }
-    }
-    double p_cur = s_p[0];  // p_j of the step at hand; every step requests the next one's
-#pragma unroll 1
-    for (int jb = 0; jb < W.d_main; jb += NW) {
-      {
-        // priority by progress, as in window_f1_kernel: the resident waves of a SIMD -- here tasks of different lengths
-        // -- advance by the same FRACTION of their work, so a short task does not wait behind a long one's age
-        const unsigned done = (unsigned)(rb * W.d_main + jb);
-        const unsigned pr = 3u - (4u * done) / (unsigned)(W.chunk_blocks * W.d_main + 1);
-        if (pr == 0) __builtin_amdgcn_s_setprio(0);
-        else if (pr == 1) __builtin_amdgcn_s_setprio(1);
-        else if (pr == 2) __builtin_amdgcn_s_setprio(2);
-        else __builtin_amdgcn_s_setprio(3);
-      }
-      const double2* nxt = s_win + (base - jb - NW);  // slots base-jb-NW ... base-jb-1
-      const double* pq = s_p + jb + 1;
-#pragma unroll
-      for (int t = 0; t < NW; ++t) {
-        const double p = p_cur;
-        // the cell (s = S-1, r = R-1) goes first: it alone reads the window's top entry, so the slide is requested at
-        // the start of the step (see window_f1_kernel); every accumulator still sees its two adds in the reference's order
-        if constexpr (S > 1) {
-          acc[S - 1][R - 1] += p * immc[S - 1][R - 1];
-          if constexpr (FUTURE) acc[S - 1][R - 1] += p * win[(R + S - 2 - t + NW) % NW].y;
-        } else {
-          const double2 wt = win[(R - 1 - t + NW) % NW];
-          acc[0][R - 1] += p * (c0[R - 1] + wt.x);
-          if constexpr (FUTURE) acc[0][R - 1] += p * wt.y;
-        }
-        win[(NW - 1 - t) % NW] = nxt[NW - 1 - t];
-        p_cur = pq[t];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          if (S == 1 && r == R - 1) continue;
-          const double2 w0 = win[(r - t + NW) % NW];
-          const double imm0 = c0[r] + w0.x;
-          acc[0][r] += p * imm0;
-          if constexpr (FUTURE) acc[0][r] += p * w0.y;
-#pragma unroll
-          for (int s = 1; s < S; ++s) {
-            if (r == R - 1 && s == S - 1) continue;
-            acc[s][r] += p * immc[s][r];
-            // (cells with the same r + s read the same entry: the product p * V is formed once for them)
-            if constexpr (FUTURE) acc[s][r] += p * win[(r + s - t + NW) % NW].y;
-          }
-#pragma unroll
-          for (int s = S - 1; s > 1; --s) immc[s][r] = immc[s - 1][r];
-          if constexpr (S > 1) immc[1][r] = imm0;
-        }
-      }
-    }
-    // the last D mod NW demand steps: the same unrolled body under wave-uniform guards
-    if (W.d_main < W.n_demand) {
-      const int jb = W.d_main;
-      const int rem = W.n_demand - W.d_main;
-      const double2* nxt = s_win + (base - jb - NW);
-#pragma unroll
-      for (int t = 0; t < NW - 1; ++t) {
-        if (t < rem) {
-          const double p = p_cur;
-          p_cur = s_p[jb + t + 1];
-#pragma unroll
-          for (int r = 0; r < R; ++r) {
-            const double2 w0 = win[(r - t + NW) % NW];
-            const double imm0 = c0[r] + w0.x;
-            acc[0][r] += p * imm0;
-            if constexpr (FUTURE) acc[0][r] += p * w0.y;
-#pragma unroll
-            for (int s = 1; s < S; ++s) {
-              acc[s][r] += p * immc[s][r];
-              if constexpr (FUTURE) acc[s][r] += p * win[(r + s - t + NW) % NW].y;
-            }
-#pragma unroll
-            for (int s = S - 1; s > 1; --s) immc[s][r] = immc[s - 1][r];
-            if constexpr (S > 1) immc[1][r] = imm0;
-          }
-          win[(NW - 1 - t) % NW] = nxt[NW - 1 - t];
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int k = k0 + r;
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        if (k < W.n_actions && (MAXDIR ? (acc[s][r] > best[s]) : (acc[s][r] < best[s]))) {
-          best[s] = acc[s][r];
-          bestk[s] = k;
-        }
-      }
-    }
-  }
-
-  // results leave through the wave's own LDS region (its window is dead by now) so that every store instruction writes 64
-  // CONSECUTIVE states: lane l owns states S*l .. S*l+S-1, but stores state 64*u + l
-  if constexpr (S > 1) {
-    __builtin_amdgcn_wave_barrier();
-    double* t_val = reinterpret_cast<double*>(s_win);
-    int* t_idx = reinterpret_cast<int*>(t_val + TS);
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      t_val[S * lane + s] = best[s];
-      t_idx[S * lane + s] = bestk[s];
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int u = 0; u < S; ++u) {
-      best[u] = t_val[64 * u + lane];
-      bestk[u] = t_idx[64 * u + lane];
-    }
-  }
+  f1_cells<R, S, FUTURE>(W, s_win, s_p, lane, kA, best, bestk);  // (best[u]: state 64*u + lane of the tile)
   const bool chunked = L.n_chunks > 1;
   double* __restrict__ out_val = chunked ? chunk_val + I.chunk_off + (int64_t)chunk * L.n_states : values + I.v_cur_off;
   int32_t* __restrict__ out_idx = chunked ? chunk_idx + I.chunk_off + (int64_t)chunk * L.n_states : policy + I.pol_off;

@@ -299,7 +299,7 @@ __device__ inline void custom_period_body(
 
 #ifdef SDP_SHAPE_LEVEL
 // M(m) = sdp_level_cost(lev0 + m step) for the n_m window levels of a period starting at m_min, c(a) = sdp_action_cost(a step):
-// what the library's F1 window kernel reads in place of its built-in costs (sdp_window.hpp: WinParams::m_tab / c_tab).
+// what the library's F1 window kernel reads in place of its built-in costs (sdp_f1_cells.hpp: WinParams::m_tab / c_tab).
 extern "C" __global__ __launch_bounds__(256) void sdp_custom_tabulate(CParams P, double lev0, int m_min, int n_m,
                                                                      double* __restrict__ m_tab, int n_a,
                                                                      double* __restrict__ c_tab) {

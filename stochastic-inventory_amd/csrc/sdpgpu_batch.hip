@@ -117,7 +117,7 @@ inline int rup(int v, int r) { return (v + r - 1) / r * r; }
 struct Cand {
   int r, s, waves;
 };
-// (VGPRs with the future term: 59 / 73 / 125 / 240 for S = 1 / 2 / 4 / 8, no scratch)
+// (VGPRs with the future term: 59 / 73 / 123 / 238 for S = 1 / 2 / 4 / 8, no scratch)
 constexpr Cand kCand[] = {{4, 1, 8}, {4, 2, 6}, {4, 4, 4}, {4, 8, 2}};
 
 // One plan per period for the whole batch, by the reasoning of the single-handle planner (plan_window_search): a launch
@@ -590,9 +590,7 @@ int sdpgpu_batch_solve(sdpgpu_batch* b, int32_t sync) {
     if (b->any_chunked) {  // key rows back to the reduction identity
       const int64_t nk = (int64_t)b->key_elems;
       if (!grid_ok((nk + 255) / 256)) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "key rows too long for one launch");
-      hipLaunchKernelGGL(sdp::batch_key_fill_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, b->stream, b->d_keys, nk,
-                         (int)(b->d[0].direction == SDPGPU_MAX));
-      BHIP_TRY(b, hipGetLastError());
+      BHIP_TRY(b, launch_key_fill(b->d_keys, nk, (int)(b->d[0].direction == SDPGPU_MAX), b->stream));
       b->finalize_launches++;
     }
     for (int t = T - 1; t >= 0; --t) {
@@ -605,9 +603,7 @@ int sdpgpu_batch_solve(sdpgpu_batch* b, int32_t sync) {
     if (b->profiling) BHIP_TRY(b, hipEventRecord(b->ev_period[0], b->stream));
     if (b->any_chunked && b->total_final > 0) {  // V_t = unkey(K_t), policy = action of the lowest chunk that attains it: one launch
       if (!grid_ok((b->total_final + 255) / 256)) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "finalize pass too long for one launch");
-      hipLaunchKernelGGL(sdp::batch_finalize_kernel, dim3((unsigned)((b->total_final + 255) / 256)), dim3(256), 0, b->stream, b->d_jobs,
-                         (int)b->jobs.size(), b->total_final);
-      BHIP_TRY(b, hipGetLastError());
+      BHIP_TRY(b, launch_finalize(b->d_jobs, (int)b->jobs.size(), b->total_final, b->stream));
       b->finalize_launches++;
     }
     BHIP_TRY(b, hipEventRecord(b->ev1, b->stream));

@@ -342,6 +342,10 @@ bool window_eligible(const sdpgpu_handle* h, int period);
 // (why: receives the reason when no plan exists -- a forced plan that is infeasible, or a period too big for the LDS)
 WinPlan plan_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, std::string* why = nullptr);
 hipError_t flush_pending(sdpgpu_handle* h);
+// the two kernels of chunked periods, defined in this unit only (the batched solve launches them too): key rows to the
+// reduction identity of the direction; V_t and policy rows from keys + chunk rows (`total` states over `n_jobs` jobs)
+hipError_t launch_key_fill(unsigned long long* keys, int64_t n, int maxdir, hipStream_t st);
+hipError_t launch_finalize(const sdp::FinalizeJob* d_jobs, int n_jobs, int64_t total, hipStream_t st);
 bool window_interior_tiles(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, int* first, int* count);
 hipError_t launch_separable_f2(sdpgpu_handle* h, const DevParams& P, int period, const double* v_next, double* v_cur,
                                int32_t* pol, const double* pd, const double* pp);

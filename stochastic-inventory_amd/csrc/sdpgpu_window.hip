@@ -115,7 +115,7 @@ static WinPlan plan_window_search(const sdpgpu_handle* h, int period, int64_t lo
   struct Cand {
     int r, s, occupancy;  // occupancy: waves a SIMD can hold within the register budget
   };
-  // (VGPRs: 107 / 62 / 54 for S = 1, R = 8 / 5 / 4; 130 / 116 / 73 for S = 2; 125 for R = 4, S = 4; 244 for R = 4, S = 8)
+  // (VGPRs: 108 / 72 / 62 for S = 1, R = 8 / 5 / 4; 130 / 74 for S = 2, R = 8 / 4; 124 for R = 4, S = 4; 240 for R = 4, S = 8)
   const Cand cand[] = {{8, 1, 6}, {5, 1, 8}, {4, 1, 9}, {8, 2, 3}, {4, 2, 5}, {4, 4, 3}, {8, 4, 2}, {4, 8, 2}};
   const bool may_chunk = h->fuse_combine && h->d.store_all_values;
   bool shape_seen = false, lds_rejected = false, chunk_rejected = false;
@@ -229,6 +229,16 @@ hipError_t launch_combine(const double* pv, const int32_t* pi, int n_chunks, int
   return hipGetLastError();
 }
 
+hipError_t launch_key_fill(unsigned long long* keys, int64_t n, int maxdir, hipStream_t st) {
+  hipLaunchKernelGGL(sdp::key_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n, maxdir);
+  return hipGetLastError();
+}
+
+hipError_t launch_finalize(const sdp::FinalizeJob* d_jobs, int n_jobs, int64_t total, hipStream_t st) {
+  hipLaunchKernelGGL(sdp::finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_jobs, n_jobs, total);
+  return hipGetLastError();
+}
+
 // Turn every pending period's keys + chunk rows into its final V_t / policy rows: one launch.
 hipError_t flush_pending(sdpgpu_handle* h) {
   if (h->n_pending == 0) return hipSuccess;
@@ -269,9 +279,7 @@ hipError_t flush_pending(sdpgpu_handle* h) {
   hipError_t e = hipMemcpyAsync(h->d_jobs, jobs, n_jobs * sizeof(sdp::FinalizeJob), hipMemcpyHostToDevice, h->stream);
   if (e != hipSuccess) return e;
   h->flush_uploads++;
-  hipLaunchKernelGGL(sdp::finalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->d_jobs,
-                     (int)n_jobs, total);
-  return hipGetLastError();
+  return launch_finalize(h->d_jobs, (int)n_jobs, total, h->stream);
 }
 
 // ---- row-window kernel (F2) ---------------------------------------------------------------
@@ -508,8 +516,7 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
       const bool all = h->n_pending == 0;
       const int64_t n = (all ? (int64_t)h->T : 1) * (int64_t)h->key_stride;
       unsigned long long* base = all ? h->d_keys : h->d_keys + (size_t)(period - 1) * h->key_stride;
-      hipLaunchKernelGGL(sdp::key_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, base, n, (int)P.maxdir);
-      hipError_t e = hipGetLastError();
+      hipError_t e = launch_key_fill(base, n, (int)P.maxdir, st);
       if (e != hipSuccess) return e;
       if (all)
         std::fill(h->key_row_clean.begin(), h->key_row_clean.end(), 1);
