@@ -698,6 +698,54 @@ int sdpgpu_batch_stats_get(sdpgpu_batch* b, sdpgpu_batch_stats* out);
 /* Time of period t's launch in the last solve (ms; needs sdpgpu_batch_set_profiling), -1 when there is none. */
 double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period);
 
+/* ---- batched simulation: roll the policies of ALL instances of a solved batch along demand paths, one launch ------------
+ * What CLSPTesting.main does after every solve -- `new Simulation(distributions, 10000, recursion)
+ * .simulateSDPGivenSamplNum(initialState)` (CLSPTesting.java:120-124; Simulation.java:53-74) -- for the whole batch.  Per path
+ * and instance, periods 1..T in order: action index of the current grid state from the instance's policy row,
+ * `sum += immediateValue(state, action, demand)`, `state = stateTransition(...)` (Simulation.java:59-69 on the lambdas of
+ * CLSPTesting.java:89-106).  A path's sum is bit for bit what sdpgpu_simulate gives on a handle of the instance with
+ * discount 1.0.  Demands need not lie in the pmf support and may be negative: the grid is clamped.  Works with
+ * store_all_values 0 and 1 (the policy rows of all periods are kept either way).  Additive to ABI 6.
+ *
+ * n_paths: 1 .. 2^24.  ini_x: NULL = every descriptor's ini_inventory, else n grid points.  out_mean[n]: mean of the
+ * instance's path sums, formed on the device in a fixed order (the same bits on every call).  out_sum: NULL, or
+ * n x n_paths path sums (instance-major).  Errors as for the rest of the batch: SDPGPU_ERR_ARG names the instance and the
+ * field, SDPGPU_ERR_STATE when nothing has been solved; validation comes before any device call. */
+/* Explicit demands: demand[i * instance_stride + p * T + t] is the demand of path p of instance i in period t + 1, already
+ * rounded by the caller as Simulation.java:64 does; instance_stride = 0 shares ONE set of n_paths x T between all
+ * instances, otherwise it is >= n_paths * T. */
+int sdpgpu_batch_simulate(sdpgpu_batch* b, int32_t n_paths, const double* demand, int64_t instance_stride, const double* ini_x,
+                          double* out_mean, double* out_sum);
+/* Sampled demands: the latin hypercube of Sampling.generateLHSamples (Sampling.java:86-103) drawn ON the device, seeded and
+ * reproducible (Math.random() makes the reference's unrepeatable): path p of (instance i, period t) takes the stratum
+ * j = sigma(p) of [0, n_paths) -- sigma a keyed bijection, the per-column shuffle of Sampling.java:326-335 --, a = 53 bits of
+ * Philox4x32-10 at counter (j, t, i, 0) under `seed`, u = j / n + a / n (:94), and the demand Math.round(inverseF(u)) (:95,
+ * Simulation.java:64) by ONE binary search in a threshold table the host made.  i is the instance's POSITION in the batch.
+ * The exact construction is DESIGN.md 4 ("Batched simulation").  Needs step == 1 (Math.round yields integers), else
+ * SDPGPU_ERR_UNSUPPORTED.
+ * sdpgpu_batch_set_sampler chooses the distribution of (instance, period index t): a spec (any kind of sdpgpu_dist_spec;
+ * thresholds = sdpgpu_sample_table) or NULL = the instance's own pmf tile of that period (thresholds = the running fp64
+ * sum of its probabilities, the last one +infinity), which is also the default.  Paths drawn from the tile make the mean
+ * an unbiased estimate of V_1(ini); with specs it carries the truncation bias of GetPmf's quantile, as the reference's. */
+int sdpgpu_batch_set_sampler(sdpgpu_batch* b, int32_t instance, int32_t t, const sdpgpu_dist_spec* spec);
+int sdpgpu_batch_simulate_sampled(sdpgpu_batch* b, int32_t n_paths, uint64_t seed, const double* ini_x, double* out_mean,
+                                  double* out_sum);
+/* The demands (and, when out_u is not NULL, the uniforms) sdpgpu_batch_simulate_sampled uses for ONE instance, produced by
+ * the same device code: out[p * T + t].  Needs the pmfs and a device, not a solve. */
+int sdpgpu_batch_sample_demands(sdpgpu_batch* b, int32_t instance, int32_t n_paths, uint64_t seed, double* out_demand,
+                                double* out_u);
+/* HIP-event time (ms) of the kernels of the last sdpgpu_batch_simulate* call on the batch's stream (rollout + means; the
+ * copies are outside), -1 when there is none. */
+double sdpgpu_batch_simulate_ms(sdpgpu_batch* b);
+/* The threshold table of one distribution, host arithmetic only (no device), like sdpgpu_getpmf: ascending c_0 .. c_{n-1},
+ * c_q = F(k_lo + q + 0.5) for a continuous distribution (demand = k_lo + #{c <= u}: Math.round(inverseF(u)) = k exactly when
+ * F(k - 0.5) <= u < F(k + 0.5)) and F(k_lo + q) for an integer-valued one (demand = k_lo + #{c < u}: inverseF(u) =
+ * min{k : F(k) >= u}), over every k whose threshold lies in (2^-64, 1) in fp64; a u below c_0 takes k_lo.  capacity = 0
+ * is a sizing call.  More than SDPGPU_SAMPLE_TABLE_CAP thresholds: SDPGPU_ERR_UNSUPPORTED.  Errors through
+ * sdpgpu_last_error(NULL). */
+#define SDPGPU_SAMPLE_TABLE_CAP 65536
+int sdpgpu_sample_table(const sdpgpu_dist_spec* spec, int32_t* k_lo_out, double* thresholds, int32_t capacity, int32_t* n_out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

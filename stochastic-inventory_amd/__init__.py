@@ -15,7 +15,7 @@ from .multiitem import (Actions, CashRecursionMulti, CashRecursionMultiLead, Cas
                         CashStateMultiLead, CashStateMultiXR, MultiLeadResult, multicash_solve, multilead_solve, multixr_solve)
 from .pmf import BinomialDist, DiscreteDistribution, GammaDist, GetPmf, NormalDist, PoissonDist, UniformIntDist, staff_level_pmf
 from .recursion import CLSP, CashLeadtimeRecursion, CashRecursion, CashRecursionXR, LeadtimeRecursion, Recursion, RecursionBatch, RiskRecursion
-from .simulation import RiskSimulation, Sampling, Simulation
+from .simulation import RiskSimulation, Sampling, Simulation, SimulationBatch
 from .workforce import StaffFunctor, StaffRecursion, StaffState
 from .states import CashLeadtimeState, CashState, CashStateXR, LeadtimeState, OptDirection, RiskState, State
 
@@ -26,6 +26,6 @@ __all__ = [
     "StaffRecursion", "StaffFunctor", "StaffState", "BinomialDist", "staff_level_pmf",
     "multilead_solve", "multicash_solve", "multixr_solve", "MultiLeadResult", "Actions", "CashRecursionMulti",
     "CashRecursionMultiLead", "CashRecursionMultiXR", "CashStateMulti", "CashStateMultiLead", "CashStateMultiXR",
-    "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "RiskSimulation", "Sampling",
+    "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "SimulationBatch", "RiskSimulation", "Sampling",
     "State", "LeadtimeState", "CashState", "CashStateXR", "CashLeadtimeState", "RiskState", "OptDirection", "java_round",
 ]

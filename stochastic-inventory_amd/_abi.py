@@ -298,6 +298,12 @@ EXPORTS = {
     "sdpgpu_batch_initial": (C.c_int, [_P, _DP, _IP]),
     "sdpgpu_batch_stats_get": (C.c_int, [_P, C.POINTER(SdpgpuBatchStats)]),
     "sdpgpu_batch_period_ms": (C.c_double, [_P, C.c_int32]),
+    "sdpgpu_batch_simulate": (C.c_int, [_P, C.c_int32, _DP, C.c_int64, _DP, _DP, _DP]),
+    "sdpgpu_batch_set_sampler": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(SdpgpuDistSpec)]),
+    "sdpgpu_batch_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, _DP, _DP, _DP]),
+    "sdpgpu_batch_sample_demands": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint64, _DP, _DP]),
+    "sdpgpu_batch_simulate_ms": (C.c_double, [_P]),
+    "sdpgpu_sample_table": (C.c_int, [C.POINTER(SdpgpuDistSpec), _IP, _DP, C.c_int32, _IP]),
 }
 
 _lib = None

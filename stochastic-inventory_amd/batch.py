@@ -108,3 +108,64 @@ class SdpBatch:
 
     def period_ms(self, period: int) -> float:
         return float(self._lib.sdpgpu_batch_period_ms(self._b, period))
+
+    # ---- simulation of all instances (sdpgpu_batch_simulate*; Simulation.java:53-74 for the whole sweep) ----
+    def _ini(self, ini_x):
+        if ini_x is None:
+            return None, None
+        arr = np.ascontiguousarray(ini_x, dtype=np.float64)
+        if arr.shape != (self.n,):
+            raise ValueError(f"ini_x has shape {arr.shape}, the batch holds {self.n} instances")
+        return arr, _dp(arr)
+
+    def _sim_result(self, mean, sums, want_sums):
+        return (mean, sums) if want_sums else mean
+
+    def simulate(self, demands, ini_x=None, want_sums: bool = False):
+        """Roll every instance's policy along given demand paths: `demands` is [n_paths, T] (one set shared by all
+        instances) or [n, n_paths, T] (a set per instance), already rounded as Simulation.java:64 does.  Returns the n
+        means, or (means, sums[n, n_paths]) with want_sums."""
+        dem = np.ascontiguousarray(demands, dtype=np.float64)
+        if dem.ndim == 2 and dem.shape[1] == self.T:
+            n_paths, stride = dem.shape[0], 0
+        elif dem.ndim == 3 and dem.shape[0] == self.n and dem.shape[2] == self.T:
+            n_paths, stride = dem.shape[1], dem.shape[1] * self.T
+        else:
+            raise ValueError(f"demands of shape {dem.shape}: expected [n_paths, {self.T}] or [{self.n}, n_paths, {self.T}]")
+        ini, ini_p = self._ini(ini_x)
+        mean = np.empty(self.n, dtype=np.float64)
+        sums = np.empty((self.n, n_paths), dtype=np.float64) if want_sums else None
+        self._check(self._lib.sdpgpu_batch_simulate(self._b, n_paths, _dp(dem), stride, ini_p, _dp(mean),
+                                                    _dp(sums) if want_sums else None))
+        return self._sim_result(mean, sums, want_sums)
+
+    def set_sampler(self, i: int, t: int, dist=None):
+        """Distribution the device sampler draws period index `t` of instance `i` from: None = the instance's own pmf tile
+        (the default), a pmf.py distribution (PoissonDist / NormalDist / GammaDist / UniformIntDist), an SdpgpuDistSpec, or
+        a (kind, a, b) tuple."""
+        if dist is None:
+            self._check(self._lib.sdpgpu_batch_set_sampler(self._b, i, t, None))
+            return
+        from .pmf import dist_spec
+        spec = dist_spec(dist)
+        self._check(self._lib.sdpgpu_batch_set_sampler(self._b, i, t, C.byref(spec)))
+
+    def simulate_sampled(self, n_paths: int, seed: int, ini_x=None, want_sums: bool = False):
+        """Draw n_paths latin-hypercube demand paths per instance ON the device (seeded, reproducible) and roll
+        the policies along them in the same launch."""
+        ini, ini_p = self._ini(ini_x)
+        mean = np.empty(self.n, dtype=np.float64)
+        sums = np.empty((self.n, int(n_paths)), dtype=np.float64) if want_sums and n_paths > 0 else None
+        self._check(self._lib.sdpgpu_batch_simulate_sampled(self._b, int(n_paths), C.c_uint64(seed & (2**64 - 1)), ini_p, _dp(mean),
+                                                            _dp(sums) if sums is not None else None))
+        return self._sim_result(mean, sums, want_sums)
+
+    def sample_demands(self, i: int, n_paths: int, seed: int):
+        """(demands[n_paths, T], uniforms[n_paths, T]) simulate_sampled uses for instance i, from the same device code."""
+        dem = np.empty((max(int(n_paths), 0), self.T), dtype=np.float64)
+        u = np.empty_like(dem)
+        self._check(self._lib.sdpgpu_batch_sample_demands(self._b, i, int(n_paths), C.c_uint64(seed & (2**64 - 1)), _dp(dem), _dp(u)))
+        return dem, u
+
+    def simulate_ms(self) -> float:
+        return float(self._lib.sdpgpu_batch_simulate_ms(self._b))

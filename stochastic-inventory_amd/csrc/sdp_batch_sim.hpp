@@ -1,0 +1,203 @@
+// sdp_batch_sim.hpp -- forward simulation of ALL instances of a solved batch in one launch (sdpgpu_batch_simulate*,
+// sdpgpu_batch.hip): the loop of Simulation.simulateSDPGivenSamplNum (Simulation.java:59-69) on every instance's own
+// CLSPTesting lambdas (CLSPTesting.java:89-106), one demand path per lane, with the demand of a (path, period) either read
+// from memory or DRAWN here (Sampling.generateLHSamples, Sampling.java:86-103, made reproducible).
+//
+//   * a wave's 64 paths belong to ONE instance (the paths of an instance are padded to whole waves), so the instance's cost
+//     record, its sampler records and its policy-row offsets are wave-uniform loads;
+//   * the rollout statements are cell<FAM_BACKORDER> of sdp_device.hpp word for word (simulate_kernel of sdp_gather.hpp with
+//     discount 1.0: `1.0 * imm` is `imm`), so a path's sum has the bits sdpgpu_simulate gives on a handle of the instance;
+//   * the sampler ("Batched simulation"): stratum j = sigma(p) of path p, a = 53 bits of Philox4x32-10 at counter
+//     (j, t, instance, 0) under the caller's seed, u = j / n + a / n, demand = k_lo + #{thresholds <= u} (or < u for an
+//     integer-valued distribution) by binary search in the host-made table of the (instance, period).  The tables are a few
+//     KB per instance and shared by every lane of its waves: they are read through L1/L2, not staged in LDS;
+//   * the mean of an instance is formed in a fixed order -- xor-butterfly over the wave, then the wave partials of the
+//     instance in index order by one thread (batch_sim_mean_kernel): no floating-point atomics, the same bits every call.
+//
+// Global memory is written with ordinary vector stores from plain C++ only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace sdp {
+
+struct SimInst {
+  double h, pi, K, v;
+};
+
+// threshold table of one (instance, period), [instance * T + t]
+struct SimSampler {
+  int64_t off;     // element offset of the ascending thresholds in the threshold arena
+  int32_t k_lo;    // demand of a u below the first threshold
+  int32_t m;       // thresholds
+  int32_t strict;  // 1: demand = k_lo + #{c < u} (inverseF of an integer-valued distribution); 0: #{c <= u}
+  int32_t pad;
+};
+
+struct SimLaunch {
+  double step, inv_step, min_inventory, max_inventory;
+  int32_t T, n_states, n_inst, n_paths;
+  int32_t waves_per_inst;  // ceil(n_paths / 64)
+  int32_t half_bits;       // sigma: smallest h >= 1 with 4^h >= n_paths
+  int64_t demand_stride;   // explicit demands: elements between the demand sets of two instances (0: one shared set)
+  uint32_t seed_lo, seed_hi;
+};
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11)
+struct Philox4 {
+  uint32_t v[4];
+};
+__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0;
+    c1 = lo1;
+    c2 = n2;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{{c0, c1, c2, c3}};
+}
+
+// the round function of sigma's Feistel network: a 32-bit integer finaliser ("lowbias32")
+__device__ __forceinline__ uint32_t sim_mix32(uint32_t x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// sigma_{instance, t}: a bijection of [0, n).  Eight Feistel rounds over 2 h bits (4^h >= n), round keys = the eight words
+// Philox gives at the counters (0, t, instance, 1) and (1, t, instance, 1); a result >= n is fed through again (cycle walking).
+__device__ __forceinline__ uint32_t sim_sigma(uint32_t p, uint32_t n, int h, const uint32_t* rk) {
+  const uint32_t mask = (1u << h) - 1u;
+  uint32_t x = p;
+  do {
+    uint32_t l = x >> h, r = x & mask;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const uint32_t f = sim_mix32(r + rk[q]) & mask;
+      const uint32_t nl = r;
+      r = l ^ f;
+      l = nl;
+    }
+    x = (l << h) | r;
+  } while (x >= n);
+  return x;
+}
+
+// demand of path p of (instance, t), and the uniform it came from
+__device__ __forceinline__ double sim_draw(const SimLaunch& L, const SimSampler& S, const double* __restrict__ thr, int inst, int t,
+                                           uint32_t p, double* u_out) {
+  const uint32_t n = (uint32_t)L.n_paths;
+  const Philox4 ka = philox4x32_10(0u, (uint32_t)t, (uint32_t)inst, 1u, L.seed_lo, L.seed_hi);
+  const Philox4 kb = philox4x32_10(1u, (uint32_t)t, (uint32_t)inst, 1u, L.seed_lo, L.seed_hi);
+  const uint32_t rk[8] = {ka.v[0], ka.v[1], ka.v[2], ka.v[3], kb.v[0], kb.v[1], kb.v[2], kb.v[3]};
+  const uint32_t j = sim_sigma(p, n, L.half_bits, rk);
+  const Philox4 r = philox4x32_10(j, (uint32_t)t, (uint32_t)inst, 0u, L.seed_lo, L.seed_hi);
+  const uint64_t bits = (((uint64_t)r.v[0] << 32) | (uint64_t)r.v[1]) >> 11;
+  const double a = (double)bits * 0x1p-53;                       // [0, 1), as Math.random()
+  const double u = (double)j / (double)n + a / (double)n;        // Sampling.java:94
+  const double* __restrict__ c = thr + S.off;
+  int lo = 0, hi = S.m;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const double cv = c[mid];
+    const bool below = S.strict ? cv < u : cv <= u;
+    if (below)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  *u_out = u;
+  return (double)(S.k_lo + lo);
+}
+
+template <bool SAMPLED>
+__global__ __launch_bounds__(256) void batch_sim_kernel(SimLaunch L, const SimInst* __restrict__ inst, const int32_t* __restrict__ ini_idx,
+                                                        const int32_t* __restrict__ policy, const double* __restrict__ demand,
+                                                        const SimSampler* __restrict__ samp, const double* __restrict__ thr,
+                                                        double* __restrict__ partial, double* __restrict__ out_sum) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
+  if (gw >= (int64_t)L.n_inst * L.waves_per_inst) return;  // no workgroup barrier below: a wave may leave on its own
+  const int i = (int)(gw / L.waves_per_inst);              // (wave-uniform)
+  const int w = (int)(gw - (int64_t)i * L.waves_per_inst);
+  const int p = w * 64 + lane;
+  const SimInst I = inst[i];
+  double sum = 0.0;
+  if (p < L.n_paths) {
+    int idx = ini_idx[i];
+    const int32_t* __restrict__ pol = policy + (int64_t)i * L.T * L.n_states;
+    const double* __restrict__ dem = SAMPLED ? nullptr : demand + (int64_t)i * L.demand_stride + (int64_t)p * L.T;
+    for (int t = 0; t < L.T; ++t) {
+      double d;
+      if constexpr (SAMPLED) {
+        double u;
+        d = sim_draw(L, samp[(int64_t)i * L.T + t], thr, i, t, (uint32_t)p, &u);
+      } else {
+        d = dem[t];
+      }
+      // decode_state / action_setup / cell of the backorder family (sdp_device.hpp; CLSP.java:255-272)
+      const double x = L.min_inventory + (double)idx * L.step;
+      const int k = pol[(int64_t)t * L.n_states + idx];
+      const double a = (double)k * L.step;
+      const double fixed = a > 0 ? I.K : 0.0;
+      const double var = I.v * a;
+      const double fv = fixed + var;
+      const double base = x + a;
+      const double level = base - d;
+      const double hold = I.h * fmax(level, 0.0);
+      const double pen = I.pi * fmax(-level, 0.0);
+      const double imm = fv + hold + pen;
+      sum += imm;
+      if (t + 1 < L.T) {
+        double nx = level;
+        nx = nx > L.max_inventory ? L.max_inventory : nx;
+        nx = nx < L.min_inventory ? L.min_inventory : nx;
+        idx = (int)((nx - L.min_inventory) * L.inv_step);
+        idx = idx < 0 ? 0 : (idx >= L.n_states ? L.n_states - 1 : idx);  // (a NaN demand must not leave the policy row)
+      }
+    }
+    if (out_sum) out_sum[(int64_t)i * L.n_paths + p] = sum;
+  }
+  // wave total in a fixed order (lanes past n_paths hold 0.0); every lane ends with the same bits
+  double tot = sum;
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) tot += __shfl_xor(tot, s, 64);
+  if (lane == 0) partial[gw] = tot;
+}
+
+// mean of every instance: its wave partials in index order, then one division
+__global__ __launch_bounds__(256) void batch_sim_mean_kernel(const double* __restrict__ partial, int n_inst, int waves_per_inst, int n_paths,
+                                                             double* __restrict__ out_mean) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_inst) return;
+  double s = 0.0;
+  for (int w = 0; w < waves_per_inst; ++w) s += partial[(int64_t)i * waves_per_inst + w];
+  out_mean[i] = s / (double)n_paths;
+}
+
+// the demands (and uniforms) batch_sim_kernel<true> uses for ONE instance, by the same sim_draw: out[p * T + t]
+__global__ __launch_bounds__(256) void batch_sim_draw_kernel(SimLaunch L, int inst, const SimSampler* __restrict__ samp,
+                                                             const double* __restrict__ thr, double* __restrict__ out_demand,
+                                                             double* __restrict__ out_u) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= L.n_paths) return;
+  for (int t = 0; t < L.T; ++t) {
+    double u;
+    const double d = sim_draw(L, samp[(int64_t)inst * L.T + t], thr, inst, t, (uint32_t)p, &u);
+    out_demand[p * L.T + t] = d;
+    if (out_u) out_u[p * L.T + t] = u;
+  }
+}
+
+}  // namespace sdp

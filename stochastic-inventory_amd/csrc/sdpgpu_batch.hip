@@ -5,6 +5,7 @@
 // slabs, no exchange, no user functors -- and the handle does not grow.
 #include "sdpgpu_internal.hpp"
 #include "sdp_batch.hpp"
+#include "sdp_batch_sim.hpp"
 
 namespace sdpgpu_detail {
 int validate(const sdpgpu_desc& d);                 // sdpgpu.hip
@@ -52,6 +53,18 @@ struct sdpgpu_batch {
   std::vector<hipEvent_t> ev_period;  // [T + 1] when profiling
   bool timed = false, periods_timed = false;
   int32_t period_launches = 0, finalize_launches = 0, periods_run = 0;
+  // ---- simulation (sdp_batch_sim.hpp) ----
+  std::vector<char> samp_spec_set;             // [i * T + t]: 1 = a distribution spec, 0 = the pmf tile
+  std::vector<int32_t> samp_klo, samp_strict;  // of the spec tables
+  std::vector<std::vector<double>> samp_thr;
+  bool samp_dirty = true;
+  sdp::SimSampler* d_samp = nullptr;
+  double* d_thr = nullptr;
+  sdp::SimInst* d_sim_inst = nullptr;
+  char* d_sim_scratch = nullptr;  // grow-only: start indices, wave partials, means, path sums, demands
+  size_t sim_scratch_bytes = 0;
+  hipEvent_t sim_ev0 = nullptr, sim_ev1 = nullptr;
+  bool sim_timed = false;
   std::string err;
 };
 
@@ -477,6 +490,10 @@ int sdpgpu_batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out)
       b->d0.assign((size_t)n * b->T, 0.0);
       b->pmf_p.resize((size_t)n * b->T);
       b->pmf_set.assign((size_t)n * b->T, 0);
+      b->samp_spec_set.assign((size_t)n * b->T, 0);
+      b->samp_klo.assign((size_t)n * b->T, 0);
+      b->samp_strict.assign((size_t)n * b->T, 0);
+      b->samp_thr.resize((size_t)n * b->T);
       if (const char* e = std::getenv("SDPGPU_WIN_R")) b->win_r = std::atoi(e);
       if (const char* e = std::getenv("SDPGPU_WIN_NCH")) b->win_nch = std::atoi(e);
       if (const char* e = std::getenv("SDPGPU_WIN_S")) b->win_s = std::atoi(e);
@@ -511,6 +528,12 @@ void sdpgpu_batch_destroy(sdpgpu_batch* b) {
     if (b->d_jobs) (void)hipFree(b->d_jobs);
     if (b->d_ini_off) (void)hipFree(b->d_ini_off);
     if (b->d_ini_out) (void)hipFree(b->d_ini_out);
+    if (b->d_samp) (void)hipFree(b->d_samp);
+    if (b->d_thr) (void)hipFree(b->d_thr);
+    if (b->d_sim_inst) (void)hipFree(b->d_sim_inst);
+    if (b->d_sim_scratch) (void)hipFree(b->d_sim_scratch);
+    if (b->sim_ev0) (void)hipEventDestroy(b->sim_ev0);
+    if (b->sim_ev1) (void)hipEventDestroy(b->sim_ev1);
     if (b->stream && b->own_stream) (void)hipStreamDestroy(b->stream);
   }
   delete b;
@@ -729,6 +752,280 @@ double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period) {
   if (hipEventSynchronize(b->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
   float ms = 0;
   if (hipEventElapsedTime(&ms, b->ev_period[(size_t)period], b->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
+  return ms;
+}
+
+}  // extern "C"
+
+// =================================================================================================
+// Batched simulation (sdp_batch_sim.hpp)
+// =================================================================================================
+namespace {
+
+constexpr int32_t kSimMaxPaths = 1 << 24;
+
+// sampler records + threshold arena on the device (spec tables as set; tile tables = the running sum of the tile)
+int sim_upload_samplers(sdpgpu_batch* b) {
+  if (!b->samp_dirty && b->d_samp) return SDPGPU_OK;
+  const size_t NT = (size_t)b->N * b->T;
+  std::vector<sdp::SimSampler> rec(NT);
+  std::vector<double> arena;
+  for (size_t k = 0; k < NT; ++k) {
+    sdp::SimSampler S{};
+    S.off = (int64_t)arena.size();
+    if (b->samp_spec_set[k]) {
+      S.k_lo = b->samp_klo[k];
+      S.strict = b->samp_strict[k];
+      S.m = (int32_t)b->samp_thr[k].size();
+      arena.insert(arena.end(), b->samp_thr[k].begin(), b->samp_thr[k].end());
+    } else {
+      const std::vector<double>& p = b->pmf_p[k];
+      S.k_lo = (int32_t)b->d0[k];
+      S.strict = 0;
+      S.m = (int32_t)p.size();
+      double s = 0.0;
+      for (size_t j = 0; j < p.size(); ++j) {
+        s += p[j];
+        arena.push_back(j + 1 == p.size() ? HUGE_VAL : s);
+      }
+    }
+    rec[k] = S;
+  }
+  if (b->d_samp) (void)hipFree(b->d_samp);
+  if (b->d_thr) (void)hipFree(b->d_thr);
+  b->d_samp = nullptr;
+  b->d_thr = nullptr;
+  BHIP_TRY(b, hipMalloc((void**)&b->d_samp, NT * sizeof(sdp::SimSampler)));
+  BHIP_TRY(b, hipMalloc((void**)&b->d_thr, std::max<size_t>(arena.size(), 1) * sizeof(double)));
+  BHIP_TRY(b, hipMemcpy(b->d_samp, rec.data(), NT * sizeof(sdp::SimSampler), hipMemcpyHostToDevice));
+  if (!arena.empty()) BHIP_TRY(b, hipMemcpy(b->d_thr, arena.data(), arena.size() * sizeof(double), hipMemcpyHostToDevice));
+  b->samp_dirty = false;
+  return SDPGPU_OK;
+}
+
+int sim_scratch(sdpgpu_batch* b, size_t bytes) {
+  if (bytes <= b->sim_scratch_bytes && b->d_sim_scratch) return SDPGPU_OK;
+  if (b->d_sim_scratch) {
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    (void)hipFree(b->d_sim_scratch);
+    b->d_sim_scratch = nullptr;
+    b->sim_scratch_bytes = 0;
+  }
+  BHIP_TRY(b, hipMalloc((void**)&b->d_sim_scratch, bytes));
+  b->sim_scratch_bytes = bytes;
+  return SDPGPU_OK;
+}
+
+sdp::SimLaunch sim_launch_params(const sdpgpu_batch* b, int32_t n_paths, uint64_t seed, int64_t stride) {
+  sdp::SimLaunch L{};
+  const sdpgpu_desc& d = b->d[0];
+  L.step = d.step;
+  L.inv_step = 1.0 / d.step;  // exact: step is a power of two (validate)
+  L.min_inventory = d.min_inventory;
+  L.max_inventory = d.max_inventory;
+  L.T = b->T;
+  L.n_states = b->nx;
+  L.n_inst = b->N;
+  L.n_paths = n_paths;
+  L.waves_per_inst = (n_paths + 63) / 64;
+  int h = 1;
+  while (((int64_t)1 << (2 * h)) < (int64_t)n_paths) ++h;
+  L.half_bits = h;
+  L.demand_stride = stride;
+  L.seed_lo = (uint32_t)(seed & 0xffffffffu);
+  L.seed_hi = (uint32_t)(seed >> 32);
+  return L;
+}
+
+int sim_needs_unit_step(sdpgpu_batch* b, const char* who) {
+  if (b->d[0].step != 1.0)
+    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: step %g -- sampled demands are Math.round's integers (Simulation.java:64), the sampler needs step == 1",
+                 who, b->d[0].step);
+  return SDPGPU_OK;
+}
+
+int sim_run(sdpgpu_batch* b, const char* who, int32_t n_paths, const double* demand, int64_t stride, bool sampled, uint64_t seed,
+            const double* ini_x, double* out_mean, double* out_sum) {
+  const int N = b->N, T = b->T;
+  if (!out_mean) return bfail(b, SDPGPU_ERR_ARG, "%s: out_mean is null", who);
+  if (n_paths <= 0) return bfail(b, SDPGPU_ERR_ARG, "%s: n_paths = %d (1 .. %d)", who, n_paths, kSimMaxPaths);
+  if (n_paths > kSimMaxPaths) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: n_paths = %d exceeds %d", who, n_paths, kSimMaxPaths);
+  if (!sampled) {
+    if (!demand) return bfail(b, SDPGPU_ERR_ARG, "%s: demand is null", who);
+    if (stride != 0 && stride < (int64_t)n_paths * T)
+      return bfail(b, SDPGPU_ERR_ARG, "%s: instance_stride %lld is neither 0 (one shared set) nor >= n_paths * T = %lld", who, (long long)stride,
+                   (long long)n_paths * T);
+  }
+  const sdpgpu_desc& d0 = b->d[0];
+  std::vector<int32_t> ini((size_t)N);
+  for (int i = 0; i < N; ++i) {
+    const double x = ini_x ? ini_x[i] : b->d[(size_t)i].ini_inventory;
+    if (!(x >= d0.min_inventory && x <= d0.max_inventory) || std::fmod(x, d0.step) != 0)
+      return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d: ini_x %g is not a point of the grid [%g, %g]", who, i, x, d0.min_inventory, d0.max_inventory);
+    ini[(size_t)i] = (int32_t)((x - d0.min_inventory) / d0.step);
+  }
+  if (sampled) {
+    int rc = sim_needs_unit_step(b, who);
+    if (rc) return rc;
+  }
+  if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+  const int64_t wpi = (n_paths + 63) / 64;
+  const int64_t waves = (int64_t)N * wpi;
+  if (!grid_ok((waves + 3) / 4) || (double)N * n_paths > 2.0e9)
+    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: %d instances x %d paths are too many for one launch", who, N, n_paths);
+
+  DeviceScope dev;
+  BHIP_TRY(b, dev.enter(b->device));
+  if (!b->d_sim_inst) {
+    std::vector<sdp::SimInst> inst((size_t)N);
+    for (int i = 0; i < N; ++i) {
+      const sdpgpu_desc& d = b->d[(size_t)i];
+      inst[(size_t)i] = sdp::SimInst{d.holding_cost, d.penalty_cost, d.fixed_order_cost, d.unit_order_cost};
+    }
+    BHIP_TRY(b, hipMalloc((void**)&b->d_sim_inst, inst.size() * sizeof(sdp::SimInst)));
+    BHIP_TRY(b, hipMemcpy(b->d_sim_inst, inst.data(), inst.size() * sizeof(sdp::SimInst), hipMemcpyHostToDevice));
+  }
+  if (!b->sim_ev0) {
+    BHIP_TRY(b, hipEventCreate(&b->sim_ev0));
+    BHIP_TRY(b, hipEventCreate(&b->sim_ev1));
+  }
+  if (sampled) {
+    int rc = sim_upload_samplers(b);
+    if (rc) return rc;
+  }
+  // scratch: [ini N x i32, padded to 8] [partials] [means] [sums] [demands]
+  auto up8 = [](size_t v) { return (v + 7) / 8 * 8; };
+  const size_t o_ini = 0, o_part = up8((size_t)N * 4), o_mean = o_part + (size_t)waves * 8, o_sum = o_mean + (size_t)N * 8;
+  const size_t sum_bytes = out_sum ? (size_t)N * n_paths * 8 : 0;
+  const size_t o_dem = o_sum + sum_bytes;
+  const size_t dem_elems = sampled ? 0 : (stride == 0 ? (size_t)n_paths * T : (size_t)(N - 1) * (size_t)stride + (size_t)n_paths * T);
+  int rc = sim_scratch(b, o_dem + dem_elems * 8);
+  if (rc) return rc;
+  char* base = b->d_sim_scratch;
+  int32_t* d_ini = reinterpret_cast<int32_t*>(base + o_ini);
+  double* d_part = reinterpret_cast<double*>(base + o_part);
+  double* d_mean = reinterpret_cast<double*>(base + o_mean);
+  double* d_sum = out_sum ? reinterpret_cast<double*>(base + o_sum) : nullptr;
+  double* d_dem = sampled ? nullptr : reinterpret_cast<double*>(base + o_dem);
+  BHIP_TRY(b, hipMemcpyAsync(d_ini, ini.data(), (size_t)N * 4, hipMemcpyHostToDevice, b->stream));
+  if (!sampled) BHIP_TRY(b, hipMemcpyAsync(d_dem, demand, dem_elems * 8, hipMemcpyHostToDevice, b->stream));
+  const sdp::SimLaunch L = sim_launch_params(b, n_paths, seed, stride);
+  const dim3 grid((unsigned)((waves + 3) / 4));
+  BHIP_TRY(b, hipEventRecord(b->sim_ev0, b->stream));
+  if (sampled)
+    hipLaunchKernelGGL((sdp::batch_sim_kernel<true>), grid, dim3(256), 0, b->stream, L, b->d_sim_inst, d_ini, b->d_policy, nullptr, b->d_samp,
+                       b->d_thr, d_part, d_sum);
+  else
+    hipLaunchKernelGGL((sdp::batch_sim_kernel<false>), grid, dim3(256), 0, b->stream, L, b->d_sim_inst, d_ini, b->d_policy, d_dem, nullptr,
+                       nullptr, d_part, d_sum);
+  BHIP_TRY(b, hipGetLastError());
+  hipLaunchKernelGGL(sdp::batch_sim_mean_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, d_part, N, (int)wpi, n_paths, d_mean);
+  BHIP_TRY(b, hipGetLastError());
+  BHIP_TRY(b, hipEventRecord(b->sim_ev1, b->stream));
+  b->sim_timed = true;
+  BHIP_TRY(b, hipMemcpyAsync(out_mean, d_mean, (size_t)N * 8, hipMemcpyDeviceToHost, b->stream));
+  if (out_sum) BHIP_TRY(b, hipMemcpyAsync(out_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost, b->stream));
+  BHIP_TRY(b, hipStreamSynchronize(b->stream));
+  return SDPGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdpgpu_batch_simulate(sdpgpu_batch* b, int32_t n_paths, const double* demand, int64_t instance_stride, const double* ini_x,
+                          double* out_mean, double* out_sum) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_simulate", [&]() -> int {
+    return sim_run(b, "sdpgpu_batch_simulate", n_paths, demand, instance_stride, false, 0, ini_x, out_mean, out_sum);
+  });
+}
+
+int sdpgpu_batch_simulate_sampled(sdpgpu_batch* b, int32_t n_paths, uint64_t seed, const double* ini_x, double* out_mean, double* out_sum) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_simulate_sampled", [&]() -> int {
+    return sim_run(b, "sdpgpu_batch_simulate_sampled", n_paths, nullptr, 0, true, seed, ini_x, out_mean, out_sum);
+  });
+}
+
+int sdpgpu_batch_set_sampler(sdpgpu_batch* b, int32_t instance, int32_t t, const sdpgpu_dist_spec* spec) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_set_sampler", [&]() -> int {
+    if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "batch_set_sampler: instance %d outside 0 .. %d", instance, b->N - 1);
+    if (t < 0 || t >= b->T) return bfail(b, SDPGPU_ERR_ARG, "batch_set_sampler: period index %d outside 0 .. %d", t, b->T - 1);
+    int rc = sim_needs_unit_step(b, "batch_set_sampler");
+    if (rc) return rc;
+    const size_t k = (size_t)instance * b->T + t;
+    if (!spec) {
+      b->samp_spec_set[k] = 0;
+      b->samp_thr[k].clear();
+      b->samp_dirty = true;
+      return SDPGPU_OK;
+    }
+    std::vector<double> thr;
+    std::string why;
+    int32_t k_lo = 0, strict = 0;
+    rc = sample_table_build(*spec, &k_lo, &thr, &strict, &why);
+    if (rc) return bfail(b, rc, "batch_set_sampler: instance %d, period %d: spec: %s", instance, t + 1, why.c_str());
+    b->samp_thr[k].swap(thr);
+    b->samp_klo[k] = k_lo;
+    b->samp_strict[k] = strict;
+    b->samp_spec_set[k] = 1;
+    b->samp_dirty = true;
+    return SDPGPU_OK;
+  });
+}
+
+int sdpgpu_batch_sample_demands(sdpgpu_batch* b, int32_t instance, int32_t n_paths, uint64_t seed, double* out_demand, double* out_u) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_sample_demands", [&]() -> int {
+    const char* who = "sdpgpu_batch_sample_demands";
+    if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, b->N - 1);
+    if (!out_demand) return bfail(b, SDPGPU_ERR_ARG, "%s: out_demand is null", who);
+    if (n_paths <= 0) return bfail(b, SDPGPU_ERR_ARG, "%s: n_paths = %d (1 .. %d)", who, n_paths, kSimMaxPaths);
+    if (n_paths > kSimMaxPaths) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: n_paths = %d exceeds %d", who, n_paths, kSimMaxPaths);
+    int rc = sim_needs_unit_step(b, who);
+    if (rc) return rc;
+    rc = layout(b);  // (every pmf set: the tile samplers read them)
+    if (rc) return rc;
+    DeviceScope dev;
+    BHIP_TRY(b, dev.enter(b->device));
+    rc = allocate(b);
+    if (rc) return rc;
+    rc = sim_upload_samplers(b);
+    if (rc) return rc;
+    const size_t elems = (size_t)n_paths * b->T;
+    rc = sim_scratch(b, elems * 8 * (out_u ? 2 : 1));
+    if (rc) return rc;
+    double* d_dem = reinterpret_cast<double*>(b->d_sim_scratch);
+    double* d_u = out_u ? d_dem + elems : nullptr;
+    const sdp::SimLaunch L = sim_launch_params(b, n_paths, seed, 0);
+    hipLaunchKernelGGL(sdp::batch_sim_draw_kernel, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, b->stream, L, (int)instance, b->d_samp,
+                       b->d_thr, d_dem, d_u);
+    BHIP_TRY(b, hipGetLastError());
+    BHIP_TRY(b, hipMemcpyAsync(out_demand, d_dem, elems * 8, hipMemcpyDeviceToHost, b->stream));
+    if (out_u) BHIP_TRY(b, hipMemcpyAsync(out_u, d_u, elems * 8, hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return SDPGPU_OK;
+  });
+}
+
+double sdpgpu_batch_simulate_ms(sdpgpu_batch* b) {
+  if (!b) return -1.0;
+  b->err.clear();
+  if (!b->sim_timed) {
+    (void)bfail(b, SDPGPU_ERR_STATE, "sdpgpu_batch_simulate_ms: no simulation has run");
+    return -1.0;
+  }
+  DeviceScope dev;
+  if (dev.enter(b->device) != hipSuccess) return -1.0;
+  if (hipEventSynchronize(b->sim_ev1) != hipSuccess) return -1.0;
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, b->sim_ev0, b->sim_ev1) != hipSuccess) return -1.0;
   return ms;
 }
 

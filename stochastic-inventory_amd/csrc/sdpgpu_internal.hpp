@@ -337,6 +337,11 @@ hipError_t launch_cash_row(sdpgpu_handle* h, const DevParams& P, int period, con
 // representative row per level, this copies it to the level's other rows
 hipError_t launch_level_fill(sdpgpu_handle* h, int period, double* v_cur, int32_t* pol, hipStream_t st);
 
+// ---- sdpgpu_pmf.hip ----------------------------------------------------------------------------------------
+// threshold table of one distribution for the batch sampler (host arithmetic): demand = k_lo + #{thr <= u}, or #{thr < u} when
+// *strict; a failure leaves its reason in *why
+int sample_table_build(const sdpgpu_dist_spec& spec, int32_t* k_lo, std::vector<double>* thr, int32_t* strict, std::string* why);
+
 // ---- sdpgpu_window.hip -------------------------------------------------------------------------------------
 bool window_eligible(const sdpgpu_handle* h, int period);
 // (why: receives the reason when no plan exists -- a forced plan that is infeasible, or a period too big for the LDS)

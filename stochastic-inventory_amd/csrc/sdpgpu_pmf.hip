@@ -206,16 +206,19 @@ double d_prob(const Dist& d, int64_t j) {
   return 0.0;
 }
 
+bool spec_ok(const sdpgpu_dist_spec& s) {
+  return (s.kind == SDPGPU_DIST_POISSON && s.a > 0 && s.a < 1e7) || (s.kind == SDPGPU_DIST_NORMAL && s.b > 0) ||
+         (s.kind == SDPGPU_DIST_GAMMA && s.a > 0 && s.b > 0) ||
+         (s.kind == SDPGPU_DIST_UNIFORM_INT && s.a == std::floor(s.a) && s.b == std::floor(s.b) && s.b >= s.a);
+}
+
 int check(const sdpgpu_dist_spec* dists, int32_t T, double q, double step, int32_t t) {
   if (!dists || T < 1 || t < 0 || t >= T) return fail(nullptr, SDPGPU_ERR_ARG, "getpmf: bad period / distribution list");
   if (!(q > 0.5 && q < 1.0)) return fail(nullptr, SDPGPU_ERR_ARG, "getpmf: truncation quantile %g not in (0.5, 1)", q);
   if (!(step > 0)) return fail(nullptr, SDPGPU_ERR_ARG, "getpmf: step %g", step);
   for (int32_t i = 0; i < T; ++i) {
     const sdpgpu_dist_spec& s = dists[i];
-    const bool ok = (s.kind == SDPGPU_DIST_POISSON && s.a > 0 && s.a < 1e7) || (s.kind == SDPGPU_DIST_NORMAL && s.b > 0) ||
-                    (s.kind == SDPGPU_DIST_GAMMA && s.a > 0 && s.b > 0) ||
-                    (s.kind == SDPGPU_DIST_UNIFORM_INT && s.a == std::floor(s.a) && s.b == std::floor(s.b) && s.b >= s.a);
-    if (!ok) return fail(nullptr, SDPGPU_ERR_ARG, "getpmf: distribution %d (kind %d, %g, %g)", i, s.kind, s.a, s.b);
+    if (!spec_ok(s)) return fail(nullptr, SDPGPU_ERR_ARG, "getpmf: distribution %d (kind %d, %g, %g)", i, s.kind, s.a, s.b);
   }
   return SDPGPU_OK;
 }
@@ -272,6 +275,106 @@ extern "C" int sdpgpu_getpmf(const sdpgpu_dist_spec* dists, int32_t T, double tr
     if ((size_t)capacity < dv.size()) return fail(nullptr, SDPGPU_ERR_ARG, "getpmf: %zu points, capacity %d", dv.size(), capacity);
     std::memcpy(demand, dv.data(), dv.size() * sizeof(double));
     std::memcpy(prob, pv.data(), pv.size() * sizeof(double));
+    return SDPGPU_OK;
+  } catch (const std::exception& e) {
+    return fail(nullptr, SDPGPU_ERR_ARG, "exception: %s", e.what());
+  } catch (...) {
+    return fail(nullptr, SDPGPU_ERR_ARG, "unknown exception");
+  }
+}
+
+// ---- threshold table of the batch sampler (sdpgpu_sample_table, sdpgpu_batch_set_sampler) ------------------------------
+// Math.round(inverseF(u)) = k exactly when F(k - 0.5) <= u < F(k + 0.5) (continuous), inverseF(u) = min{k : F(k) >= u}
+// (integer-valued): the quantile and the rounding of Sampling.java:95 / Simulation.java:64 become ONE search over the
+// ascending thresholds c_k = F(k + 0.5) resp. F(k), tabulated with the d_cdf above over every k whose threshold lies in
+// (2^-64, 1).  A cdf that steps back by rounding is held at the running maximum, so that the table is ascending.
+namespace sdpgpu_detail {
+
+int sample_table_build(const sdpgpu_dist_spec& spec, int32_t* k_lo, std::vector<double>* thr, int32_t* strict, std::string* why) {
+  char buf[200];
+  auto bad = [&](int code, const char* what) {
+    std::snprintf(buf, sizeof buf, "%s (kind %d, %g, %g)", what, spec.kind, spec.a, spec.b);
+    *why = buf;
+    return code;
+  };
+  thr->clear();
+  if (!spec_ok(spec) || !std::isfinite(spec.a) || !std::isfinite(spec.b) || std::fabs(spec.a) > 1e9 || std::fabs(spec.b) > 1e9)
+    return bad(SDPGPU_ERR_ARG, "invalid distribution spec");
+  const Dist d{spec.kind, spec.a, spec.b};
+  const double tiny = 0x1p-64;
+  const size_t cap = (size_t)SDPGPU_SAMPLE_TABLE_CAP;
+  const char* too_long = "threshold table longer than SDPGPU_SAMPLE_TABLE_CAP entries";
+  *strict = d.discrete_int() ? 1 : 0;
+  if (d.kind == SDPGPU_DIST_UNIFORM_INT) {
+    if (d.b - d.a > (double)cap) return bad(SDPGPU_ERR_UNSUPPORTED, too_long);
+    *k_lo = (int32_t)d.a;
+    for (double k = d.a; k < d.b; k += 1.0) thr->push_back(d_cdf(d, k));
+    return SDPGPU_OK;
+  }
+  if (d.kind == SDPGPU_DIST_POISSON) {  // the running sum IS poisson_cdf's (same terms, same order)
+    double s = 0.0;
+    bool started = false;
+    for (int64_t k = 0;; ++k) {
+      const double before = s;
+      s += poisson_prob(d.a, k);
+      const double F = s > 1.0 ? 1.0 : s;
+      if (!started && F > tiny) {
+        started = true;
+        *k_lo = (int32_t)k;
+      }
+      if (started) {
+        if (!(F < 1.0) || ((double)k > d.a && s == before)) break;
+        thr->push_back(F);
+        if (thr->size() > cap) return bad(SDPGPU_ERR_UNSUPPORTED, too_long);
+      }
+    }
+    return SDPGPU_OK;
+  }
+  auto c = [&](int64_t k) { return d_cdf(d, (double)k + 0.5); };
+  const double med = d_inverse(d, 0.5);
+  if (!std::isfinite(med) || std::fabs(med) > 1e9) return bad(SDPGPU_ERR_ARG, "median outside +-1e9");
+  int64_t k = (int64_t)std::floor(med);
+  size_t steps = 0;
+  if (c(k) > tiny) {
+    while (c(k - 1) > tiny) {
+      --k;
+      if (++steps > cap) return bad(SDPGPU_ERR_UNSUPPORTED, too_long);
+    }
+  } else {
+    while (!(c(k) > tiny)) {
+      ++k;
+      if (++steps > cap) return bad(SDPGPU_ERR_UNSUPPORTED, too_long);
+    }
+  }
+  *k_lo = (int32_t)k;
+  double prev = 0.0;
+  for (;; ++k) {
+    double v = c(k);
+    if (!(v < 1.0)) break;
+    if (v < prev) v = prev;
+    thr->push_back(v);
+    prev = v;
+    if (thr->size() > cap) return bad(SDPGPU_ERR_UNSUPPORTED, too_long);
+  }
+  return SDPGPU_OK;
+}
+
+}  // namespace sdpgpu_detail
+
+extern "C" int sdpgpu_sample_table(const sdpgpu_dist_spec* spec, int32_t* k_lo_out, double* thresholds, int32_t capacity, int32_t* n_out) {
+  g_create_error.clear();
+  try {
+    if (!spec || !k_lo_out || !n_out || capacity < 0 || (capacity > 0 && !thresholds))
+      return fail(nullptr, SDPGPU_ERR_ARG, "sample_table: null argument");
+    std::vector<double> thr;
+    std::string why;
+    int32_t strict = 0;
+    int rc = sample_table_build(*spec, k_lo_out, &thr, &strict, &why);
+    if (rc) return fail(nullptr, rc, "sample_table: %s", why.c_str());
+    *n_out = (int32_t)thr.size();
+    if (capacity == 0) return SDPGPU_OK;  // sizing call
+    if ((size_t)capacity < thr.size()) return fail(nullptr, SDPGPU_ERR_ARG, "sample_table: %zu thresholds, capacity %d", thr.size(), capacity);
+    if (!thr.empty()) std::memcpy(thresholds, thr.data(), thr.size() * sizeof(double));
     return SDPGPU_OK;
   } catch (const std::exception& e) {
     return fail(nullptr, SDPGPU_ERR_ARG, "exception: %s", e.what());

@@ -302,3 +302,43 @@ def getpmf_native(distributions: Sequence[Distribution], truncationQuantile: flo
             raise _abi.SdpgpuError(rc, lib.sdpgpu_last_error(None).decode())
         out.append(np.stack([dem, pr], axis=1))
     return out
+
+
+def dist_spec(d):
+    """sdpgpu_dist_spec of a PoissonDist / NormalDist / UniformIntDist / GammaDist (or of a (kind, a, b) tuple)."""
+    from . import _abi
+    spec = _abi.SdpgpuDistSpec()
+    if isinstance(d, _abi.SdpgpuDistSpec):
+        return d
+    if isinstance(d, PoissonDist):
+        spec.kind, spec.a, spec.b = _abi.DIST_POISSON, d.lam, 0.0
+    elif isinstance(d, NormalDist):
+        spec.kind, spec.a, spec.b = _abi.DIST_NORMAL, d.mu, d.sigma
+    elif isinstance(d, UniformIntDist):
+        spec.kind, spec.a, spec.b = _abi.DIST_UNIFORM_INT, float(d.getI()), float(d.getJ())
+    elif isinstance(d, GammaDist):
+        spec.kind, spec.a, spec.b = _abi.DIST_GAMMA, d.alpha, d.lam
+    elif isinstance(d, (tuple, list)) and len(d) == 3:
+        spec.kind, spec.a, spec.b = int(d[0]), float(d[1]), float(d[2])
+    else:
+        raise TypeError(f"no sdpgpu_dist_spec for {type(d).__name__}")
+    return spec
+
+
+def sample_table(dist):
+    """(k_lo, thresholds, strict) of the batch sampler's table for one distribution (sdpgpu_sample_table, host arithmetic):
+    demand = k_lo + #{thresholds <= u}, or #{thresholds < u} when `strict` (integer-valued distributions)."""
+    import ctypes as C
+
+    from . import _abi
+    lib = _abi.load()
+    spec = dist_spec(dist)
+    k_lo, n = C.c_int32(0), C.c_int32(0)
+    rc = lib.sdpgpu_sample_table(C.byref(spec), C.byref(k_lo), None, 0, C.byref(n))
+    if rc:
+        raise _abi.SdpgpuError(rc, lib.sdpgpu_last_error(None).decode())
+    thr = np.zeros(max(n.value, 1))
+    rc = lib.sdpgpu_sample_table(C.byref(spec), C.byref(k_lo), thr.ctypes.data_as(C.POINTER(C.c_double)), len(thr), C.byref(n))
+    if rc:
+        raise _abi.SdpgpuError(rc, lib.sdpgpu_last_error(None).decode())
+    return int(k_lo.value), thr[:n.value].copy(), spec.kind in (_abi.DIST_POISSON, _abi.DIST_UNIFORM_INT)

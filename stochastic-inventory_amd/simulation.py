@@ -186,3 +186,41 @@ class RiskSimulation:
                     bankrupt[i] = 1
                     countBeforeBankrupt = True
         return [1 - bankrupt.sum() / float(len(demands)), lost / float(len(demands))]
+
+
+class SimulationBatch:
+    """`new Simulation(distributions, sampleNum, recursion).simulateSDPGivenSamplNum(initialState)` for every instance of
+    a sweep at once (CLSPTesting.java:120-124): `distributions_per_instance[i]` are instance i's T demand distributions
+    (None = draw from the instance's own pmf tiles), `recursion_batch` a RecursionBatch.  Sampling (latin hypercube,
+    seeded) and rollout happen on the device in one launch (SdpBatch.simulate_sampled); there is no host sampling."""
+
+    def __init__(self, distributions_per_instance, sampleNum: int, recursion_batch, seed: int = 12345):
+        self.recursion = recursion_batch
+        self.sampleNum = int(sampleNum)
+        self.seed = int(seed)
+        self.last_values = None
+        batch = recursion_batch.batch
+        if distributions_per_instance is not None:
+            if len(distributions_per_instance) != len(recursion_batch):
+                raise ValueError(f"{len(distributions_per_instance)} distribution lists but {len(recursion_batch)} instances")
+            for i, dists in enumerate(distributions_per_instance):
+                if dists is None:
+                    continue
+                if len(dists) != recursion_batch.T:
+                    raise ValueError(f"instance {i}: {len(dists)} distributions, the horizon is {recursion_batch.T}")
+                for t, d in enumerate(dists):
+                    batch.set_sampler(i, t, d)
+
+    def setSampleNum(self, n: int):
+        self.sampleNum = int(n)
+
+    def simulateSDPGivenSamplNum(self, iniStates=None, want_sums: bool = False) -> np.ndarray:
+        """The n means (Simulation.java:53-74 per instance).  iniStates: None = every functor's iniInventory, or one
+        State per instance."""
+        self.recursion._solve()
+        ini = None if iniStates is None else [s.getIniInventory() for s in iniStates]
+        out = self.recursion.batch.simulate_sampled(self.sampleNum, self.seed, ini_x=ini, want_sums=want_sums)
+        if want_sums:
+            self.last_values = out[1]
+            return out[0]
+        return out
