@@ -746,6 +746,57 @@ double sdpgpu_batch_simulate_ms(sdpgpu_batch* b);
 #define SDPGPU_SAMPLE_TABLE_CAP 65536
 int sdpgpu_sample_table(const sdpgpu_dist_spec* spec, int32_t* k_lo_out, double* thresholds, int32_t capacity, int32_t* n_out);
 
+/* ---- sampled simulation on a handle: demand paths drawn ON the device, rolled and reduced there ------------------------
+ * What every driver does after its solve -- `new Simulation(distributions, sampleNum, recursion)
+ * .simulateSDPGivenSamplNum(initialState)` (Simulation.java:53-74; CashSimulation.java:85-118 for the cash classes;
+ * RiskSimulation.java:206-241 for the survival objective) and simulateSDPwithErrorConfidence (Simulation.java:76-107) -- with
+ * the SAMPLING (Sampling.generateLHSamples, Sampling.java:86-103; generateRanSamples, :50-60; Math.round, Simulation.java:64)
+ * done by the kernel that rolls the paths, for every family sdpgpu_simulate serves.  A handful of numbers cross to the host
+ * instead of n_paths x T doubles.  The exact construction is DESIGN.md 4 ("Sampled simulation on a handle").  Additive to
+ * ABI 6.
+ *
+ * SDPGPU_SAMPLE_LHS: the batch's latin hypercube with the instance position fixed at 0 -- path p of period index t takes the
+ * stratum j = sigma(p), a = 53 bits of Philox4x32-10 at counter (j, t, 0, 0) under `seed`, u = j / n + a / n; an F1 handle
+ * draws what a batch of ONE built from the same descriptor and pmfs draws.  first_path must be 0.
+ * SDPGPU_SAMPLE_RANDOM: path P = first_path + p (64 bits), (w0, w1, ., .) = Philox at counter (P mod 2^32, t, P div 2^32, 2),
+ * u = ((w0 * 2^32 + w1) >> 11) * 2^-53: calls with (first_path, n) = (0, a) then (a, b) draw what one call (0, a + b) draws.
+ * Demand from u, per period index t: a spec set by sdpgpu_set_sampler (thresholds = sdpgpu_sample_table, demand =
+ * k_lo + #{c <= u} resp. #{c < u}) or -- the default -- the handle's own pmf tile of that period: thresholds = the running
+ * fp64 sum of its probabilities in ascending order, the last one +infinity, demand = the tile's q-th demand VALUE,
+ * q = #{c <= u} (a tile may have gaps and any step).  Tile samplers draw from the very distribution the recursion used: every
+ * path stays on the grid and the mean estimates V_1(ini) without bias. */
+#define SDPGPU_SAMPLE_LHS 0
+#define SDPGPU_SAMPLE_RANDOM 1
+/* The distribution of period index t (0-based): a spec, or NULL = back to the pmf tile.  Validated like
+ * sdpgpu_batch_set_sampler (period index, kind, parameters, SDPGPU_SAMPLE_TABLE_CAP).  A spec needs step == 1
+ * (SDPGPU_ERR_UNSUPPORTED otherwise); a tile works at any step.  Host arithmetic only. */
+int sdpgpu_set_sampler(sdpgpu_handle* h, int32_t t, const sdpgpu_dist_spec* spec);
+typedef struct sdpgpu_sim_result {
+  int32_t n_paths;
+  int32_t n_valid;   /* paths with bit 0 of their flags set (they stayed on the grid) */
+  int32_t n_lost;    /* family SURVIVAL: paths with bit 1 set (a demand was lost), else 0 */
+  int32_t reserved;
+  double mean;       /* mean of the path sums; SURVIVAL: the share of paths that held negative cash */
+  double m2;         /* sum over paths of (sum_p - mean)^2, a second pass over the device-resident sums */
+  double kernel_ms;  /* HIP-event time of the kernels of this call (rollout, both reductions; the copies are outside) */
+} sdpgpu_sim_result;
+/* Sample n_paths (1 .. 2^24) demand paths, roll the computed policy along them and reduce, all on the device.  discount:
+ * NULL = all 1.0 (the bits of an explicit array of ones), else T weights as in sdpgpu_simulate.  Start state, off-grid start
+ * and the meaning of a path's sum and flags as in sdpgpu_simulate, whose per-period statements this kernel shares: out_sum
+ * (NULL or n_paths) and out_valid (NULL or n_paths) equal sdpgpu_simulate on the demands sdpgpu_sample_demands returns, bit for
+ * bit.  mean and m2 are formed in an order fixed by n_paths alone, without floating-point atomics: the same bits on every
+ * call with the same arguments.  If any path left the grid (n_valid < n_paths: an unclamped family under a spec whose draws
+ * leave the pmf support) mean and m2 are NaN and the status is still SDPGPU_OK.  Refusals as sdpgpu_simulate (STAFF, user
+ * functors, cash_formula 2, world_size != 1, nothing solved); argument errors name the argument; all validation comes before
+ * the first device call. */
+int sdpgpu_simulate_sampled(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t mode, uint64_t first_path,
+                            const double* discount, double ini_x, double ini_cash, double ini_preq, sdpgpu_sim_result* result,
+                            double* out_sum, uint8_t* out_valid);
+/* The demands (and, when out_u is not NULL, the uniforms) sdpgpu_simulate_sampled uses, from the same device functions:
+ * out[p * T + t].  Needs the pmfs (or specs) and a device, not a solve. */
+int sdpgpu_sample_demands(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t mode, uint64_t first_path, double* out_demand,
+                          double* out_u);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

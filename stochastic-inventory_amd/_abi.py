@@ -217,6 +217,14 @@ class SdpgpuDistSpec(C.Structure):
 
 
 DIST_POISSON, DIST_NORMAL, DIST_UNIFORM_INT, DIST_GAMMA = 1, 2, 3, 4
+SAMPLE_LHS, SAMPLE_RANDOM = 0, 1
+
+
+class SdpgpuSimResult(C.Structure):
+    """struct sdpgpu_sim_result (include/sdpgpu.h)."""
+
+    _fields_ = [("n_paths", C.c_int32), ("n_valid", C.c_int32), ("n_lost", C.c_int32), ("reserved", C.c_int32),
+                ("mean", C.c_double), ("m2", C.c_double), ("kernel_ms", C.c_double)]
 PMF_GETPMF, PMF_CLSP = 0, 1
 
 
@@ -304,6 +312,10 @@ EXPORTS = {
     "sdpgpu_batch_sample_demands": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint64, _DP, _DP]),
     "sdpgpu_batch_simulate_ms": (C.c_double, [_P]),
     "sdpgpu_sample_table": (C.c_int, [C.POINTER(SdpgpuDistSpec), _IP, _DP, C.c_int32, _IP]),
+    "sdpgpu_set_sampler": (C.c_int, [_P, C.c_int32, C.POINTER(SdpgpuDistSpec)]),
+    "sdpgpu_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_double,
+                                          C.POINTER(SdpgpuSimResult), _DP, C.POINTER(C.c_uint8)]),
+    "sdpgpu_sample_demands": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, _DP]),
 }
 
 _lib = None

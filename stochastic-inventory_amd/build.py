@@ -31,7 +31,7 @@ HIPCC_FLAGS = [
 def sources():
     return [os.path.join(CSRC, f) for f in ("sdpgpu.hip", "sdpgpu_generic.hip", "sdpgpu_window.hip", "sdpgpu_cash.hip",
                                             "sdpgpu_staff.hip", "sdpgpu_sparse.hip", "sdpgpu_comm.hip", "sdpgpu_pmf.hip",
-                                            "sdpgpu_batch.hip")]
+                                            "sdpgpu_batch.hip", "sdpgpu_simsample.hip")]
 
 
 def deps():
@@ -90,7 +90,7 @@ def build(force: bool = False, extra_flags=(), verbose: bool = True) -> str:
         subprocess.run(cmd, check=True)
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=min(10, os.cpu_count() or 1)) as ex:
         objs = list(ex.map(compile_one, sources()))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", OUT, *objs, "-lhiprtc"]
     if verbose:
@@ -135,7 +135,7 @@ def build_host_asan(force: bool = False, verbose: bool = False) -> str:
         subprocess.run(cmd, check=True)
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(7, os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=min(10, os.cpu_count() or 1)) as ex:
         objs = list(ex.map(compile_one, sources()))
     subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *san, "-o", ASAN_OUT, *objs, "-lhiprtc"], check=True)
     return ASAN_OUT

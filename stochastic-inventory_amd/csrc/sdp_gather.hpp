@@ -211,6 +211,55 @@ struct SimPeriod {
   int64_t n_states;
 };
 
+// One period of one path: the policy gather at the current state, the family's immediate value and transition.  The
+// statements of simulate_kernel and of sim_sampled_kernel (sdp_sim_sampled.hpp) -- they exist here once, so that a path's
+// sum has the same bits whether its demands were uploaded or drawn on the device.  `off_grid_first`: period 1 from an
+// off-grid initial state, whose action (first_k) comes from sdpgpu_eval_states.
+template <int FAM>
+__device__ __forceinline__ void sim_period_step(const SimPeriod& R, const int32_t* __restrict__ pol, bool off_grid_first, int first_k,
+                                                double d, double disc_t, int64_t& idx, StateT& s, double& sum, bool& valid,
+                                                bool& lost) {
+  const DevParams& P = R.P;
+  int k;
+  if (off_grid_first) {
+    k = first_k;
+  } else {
+    decode_state<FAM>(P, idx, s);
+    k = pol[R.pol_off + idx];
+  }
+  if constexpr (FAM == FAM_SURVIVAL) {
+    // RiskSimulation.simulateLostSale (RiskSimulation.java:213-234): sum = 1 once the path has held negative
+    // cash, bit 1 of the flags once a demand was lost; the walk itself continues through bankrupt states
+    if (s.cash < 0) k = 0;
+    ActionCtx c;
+    action_setup<FAM>(P, s, k, c);
+    if (c.base < d) lost = true;
+    int64_t ni = 0;
+    const double imm = cell<FAM>(P, s, c, d, ni);
+    if (s.cash + imm < 0) sum = 1.0;
+    if (!P.is_last) {  // cell() marks a bankrupt successor with -1: the rollout needs its index all the same
+      double ninv = jmax(0.0, c.base - d);
+      ninv = ninv > P.max_inventory ? P.max_inventory : ninv;
+      ninv = ninv < P.min_inventory ? P.min_inventory : ninv;
+      idx = (int64_t)inv_index(P, ninv) * P.next.nc + cash_index(P, s.cash + imm);
+    }
+  } else {
+    ActionCtx c;
+    action_setup<FAM>(P, s, k, c);
+    int64_t ni = 0;
+    const double imm = cell<FAM>(P, s, c, d, ni);
+    sum += disc_t * imm;
+    if (!P.is_last) {
+      if (!P.clamp_inventory) {  // unclamped boxes cover the PMF support only
+        const double level = c.base - d;
+        const double hi = P.next.x_lo + (double)(P.next.nx - 1) * P.step;
+        if (level < P.next.x_lo || level > hi) valid = false;
+      }
+      idx = ni;
+    }
+  }
+}
+
 template <int FAM>
 __global__ __launch_bounds__(256) void simulate_kernel(const SimPeriod* __restrict__ per, int T,
                                                        const int32_t* __restrict__ pol, const double* __restrict__ demand,
@@ -224,49 +273,8 @@ __global__ __launch_bounds__(256) void simulate_kernel(const SimPeriod* __restri
   StateT s = ini;
   bool valid = true;
   bool lost = false;
-  for (int t = 0; t < T && valid; ++t) {
-    const DevParams& P = per[t].P;
-    int k;
-    if (t == 0 && idx0 < 0) {
-      k = first_k;  // off-grid initial state: its action comes from sdpgpu_eval_states
-    } else {
-      decode_state<FAM>(P, idx, s);
-      k = pol[per[t].pol_off + idx];
-    }
-    if constexpr (FAM == FAM_SURVIVAL) {
-      // RiskSimulation.simulateLostSale (RiskSimulation.java:213-234): sum = 1 once the path has held negative
-      // cash, bit 1 of the flags once a demand was lost; the walk itself continues through bankrupt states
-      if (s.cash < 0) k = 0;
-      ActionCtx c;
-      action_setup<FAM>(P, s, k, c);
-      const double d = demand[i * T + t];
-      if (c.base < d) lost = true;
-      int64_t ni = 0;
-      const double imm = cell<FAM>(P, s, c, d, ni);
-      if (s.cash + imm < 0) sum = 1.0;
-      if (!P.is_last) {  // cell() marks a bankrupt successor with -1: the rollout needs its index all the same
-        double ninv = jmax(0.0, c.base - d);
-        ninv = ninv > P.max_inventory ? P.max_inventory : ninv;
-        ninv = ninv < P.min_inventory ? P.min_inventory : ninv;
-        idx = (int64_t)inv_index(P, ninv) * P.next.nc + cash_index(P, s.cash + imm);
-      }
-      continue;
-    }
-    ActionCtx c;
-    action_setup<FAM>(P, s, k, c);
-    const double d = demand[i * T + t];
-    int64_t ni = 0;
-    const double imm = cell<FAM>(P, s, c, d, ni);
-    sum += disc[t] * imm;
-    if (!P.is_last) {
-      if (!P.clamp_inventory) {  // unclamped boxes cover the PMF support only
-        const double level = c.base - d;
-        const double hi = P.next.x_lo + (double)(P.next.nx - 1) * P.step;
-        if (level < P.next.x_lo || level > hi) valid = false;
-      }
-      idx = ni;
-    }
-  }
+  for (int t = 0; t < T && valid; ++t)
+    sim_period_step<FAM>(per[t], pol, t == 0 && idx0 < 0, first_k, demand[i * T + t], disc[t], idx, s, sum, valid, lost);
   out_sum[i] = sum;
   out_valid[i] = (valid ? 1 : 0) | (lost ? 2 : 0);
 }

@@ -776,7 +776,7 @@ int sdpgpu_create_custom(const sdpgpu_desc* desc, const char* functor_source, co
 
 void sdpgpu_destroy(sdpgpu_handle* h) {
   if (!h) return;
-  if (h->allocated || h->d_policy || h->d_pmf || !h->staff_owned.empty()) {
+  if (h->allocated || h->d_policy || h->d_pmf || h->d_sim_scratch || !h->staff_owned.empty()) {
     if (h->device >= 0) (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
   }
@@ -814,6 +814,9 @@ void sdpgpu_destroy(sdpgpu_handle* h) {
   if (h->d_custom_cells) (void)hipFree(h->d_custom_cells);
   if (h->d_custom_err) (void)hipFree(h->d_custom_err);
   if (h->d_level_tabs) (void)hipFree(h->d_level_tabs);
+  if (h->d_sim_scratch) (void)hipFree(h->d_sim_scratch);
+  if (h->sim_ev0) (void)hipEventDestroy(h->sim_ev0);
+  if (h->sim_ev1) (void)hipEventDestroy(h->sim_ev1);
   if (h->custom_mod) (void)hipModuleUnload(h->custom_mod);
   comm_release(h);
   if (h->stream && h->own_stream) (void)hipStreamDestroy(h->stream);

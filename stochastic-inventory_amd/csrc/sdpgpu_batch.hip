@@ -773,6 +773,7 @@ int sim_upload_samplers(sdpgpu_batch* b) {
   for (size_t k = 0; k < NT; ++k) {
     sdp::SimSampler S{};
     S.off = (int64_t)arena.size();
+    S.val_off = -1;  // demand = k_lo + q (validate: step 1 and a gapless tile)
     if (b->samp_spec_set[k]) {
       S.k_lo = b->samp_klo[k];
       S.strict = b->samp_strict[k];

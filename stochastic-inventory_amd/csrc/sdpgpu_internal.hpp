@@ -8,6 +8,7 @@
 //   sdpgpu_staff.hip    STAFF family (workforce.StaffRecursion): level-dependent pmf tables, its period kernel
 //   sdpgpu_sparse.hip   reachable-set engine of the two-product lead-time family (own entry point)
 //   sdpgpu_pmf.hip      GetPmf.getpmf / CLSP.main's inline pmf (host arithmetic) behind the ABI
+//   sdpgpu_simsample.hip  demand paths drawn on the device for a handle's policy simulation (sampler, fused rollout, reduction)
 //   sdpgpu_comm.hip     multi-GPU: RCCL communicators (loaded on first use), per-period all-gather, sharded sweeps
 #pragma once
 #include "../../include/sdpgpu.h"
@@ -204,6 +205,15 @@ struct sdpgpu_handle {
   hipGraphExec_t sweep_exec = nullptr;
   int64_t graph_replays = 0;
   int flush_uploads = 0;  // job-list uploads of flush_pending since the counter was last reset (sdpgpu_solve's capture)
+  // sdpgpu_set_sampler / sdpgpu_simulate_sampled / sdpgpu_sample_demands (sdpgpu_simsample.hip): per period index the spec's
+  // threshold table (empty vectors: every period draws from its pmf tile), and ONE device block for the period records,
+  // sampler records, threshold / value arenas, sums, flags and partials of a call
+  std::vector<char> samp_spec_set;
+  std::vector<int32_t> samp_klo, samp_strict;
+  std::vector<std::vector<double>> samp_thr;
+  char* d_sim_scratch = nullptr;
+  size_t sim_scratch_bytes = 0;
+  hipEvent_t sim_ev0 = nullptr, sim_ev1 = nullptr;
   std::string err;
   std::string plan_error;  // set by a launcher that rejects a period's plan (run_period_impl reports it as SDPGPU_ERR_ARG)
   int device = -1;

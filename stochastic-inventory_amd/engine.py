@@ -314,6 +314,57 @@ class SdpEngine:
         self.last_sim_flags = valid  # bit 0: path stayed on the grid; bit 1 (family SURVIVAL): a demand was lost
         return out, (valid & 1).astype(bool)
 
+    def set_sampler(self, t: int, dist=None):
+        """Distribution the device sampler draws period index `t` from: None = the handle's own pmf tile of that period (the
+        default; any step, gaps allowed), a pmf.py distribution, an SdpgpuDistSpec, or a (kind, a, b) tuple (step 1 only)."""
+        if dist is None:
+            self._check(self._lib.sdpgpu_set_sampler(self._h, int(t), None))
+            return
+        from .pmf import dist_spec
+        spec = dist_spec(dist)
+        self._check(self._lib.sdpgpu_set_sampler(self._h, int(t), C.byref(spec)))
+
+    @staticmethod
+    def _sample_mode(mode) -> int:
+        if mode in ("lhs", _abi.SAMPLE_LHS):
+            return _abi.SAMPLE_LHS
+        if mode in ("random", _abi.SAMPLE_RANDOM):
+            return _abi.SAMPLE_RANDOM
+        raise ValueError(f"mode {mode!r}: 'lhs' or 'random'")
+
+    def simulate_sampled(self, n_paths: int, seed: int, ini_x: float, ini_cash: float = 0.0, ini_preq: float = 0.0, *,
+                         mode="lhs", first_path: int = 0, discount=None, want_sums: bool = False):
+        """Draw n_paths demand paths ON the device (latin hypercube or plain random, seeded), roll the policy along
+        them and reduce there, in one call.  Returns the SdpgpuSimResult (n_paths, n_valid, n_lost, mean, m2, kernel_ms);
+        with want_sums also (sums[n], flags[n]) -- bit 0 of a flag: the path stayed on the grid, bit 1 (SURVIVAL): a demand
+        was lost."""
+        disc = None
+        if discount is not None:
+            disc = np.ascontiguousarray(discount, dtype=np.float64)
+            if disc.shape != (self.T,):
+                raise ValueError("discount must have one entry per period")
+        n = int(n_paths)
+        res = _abi.SdpgpuSimResult()
+        sums = np.empty(max(n, 0), dtype=np.float64) if want_sums else None
+        flags = np.empty(max(n, 0), dtype=np.uint8) if want_sums else None
+        self._check(self._lib.sdpgpu_simulate_sampled(
+            self._h, n, C.c_uint64(int(seed) & (2**64 - 1)), self._sample_mode(mode), C.c_uint64(int(first_path) & (2**64 - 1)),
+            None if disc is None else _dp(disc), float(ini_x), float(ini_cash), float(ini_preq), C.byref(res),
+            None if sums is None else _dp(sums), None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_uint8))))
+        if want_sums:
+            self.last_sim_flags = flags
+            return res, sums, flags
+        return res
+
+    def sample_demands(self, n_paths: int, seed: int, *, mode="lhs", first_path: int = 0):
+        """(demands[n_paths, T], uniforms[n_paths, T]) simulate_sampled uses, from the same device code.  Needs no solve."""
+        n = max(int(n_paths), 0)
+        dem = np.empty((n, self.T), dtype=np.float64)
+        u = np.empty_like(dem)
+        self._check(self._lib.sdpgpu_sample_demands(self._h, int(n_paths), C.c_uint64(int(seed) & (2**64 - 1)), self._sample_mode(mode),
+                                                    C.c_uint64(int(first_path) & (2**64 - 1)), _dp(dem), _dp(u)))
+        return dem, u
+
     def stats(self) -> SdpgpuStats:
         st = SdpgpuStats()
         self._check(self._lib.sdpgpu_stats_get(self._h, C.byref(st)))

@@ -62,20 +62,56 @@ def round_demands(samples: np.ndarray) -> np.ndarray:
     return np.array([[float(java_round(float(v))) for v in row] for row in samples], dtype=np.float64)
 
 
+def _check_sampler(sampler: str) -> str:
+    if sampler not in ("host", "device"):
+        raise ValueError(f"sampler {sampler!r}: 'host' or 'device'")
+    return sampler
+
+
+def _hand_samplers(recursion, distributions):
+    """sampler="device": every distribution to the engine's sampler of its period index; None keeps the pmf tile."""
+    T = recursion.T
+    if distributions is not None and len(distributions) != T:
+        raise ValueError(f"{len(distributions)} distributions, the horizon is {T}")
+    for t in range(T):
+        recursion.engine.set_sampler(t, None if distributions is None else distributions[t])
+
+
+def merge_moments(na: int, mean_a: float, m2_a: float, nb: int, mean_b: float, m2_b: float):
+    """(n, mean, M2) of the union of two samples from theirs (Chan, Golub, LeVeque: "Updating formulae and a pairwise algorithm
+    for computing sample variances", 1979): M2 = sum of squared deviations from the mean."""
+    if na == 0:
+        return nb, mean_b, m2_b
+    if nb == 0:
+        return na, mean_a, m2_a
+    n = na + nb
+    delta = mean_b - mean_a
+    return n, mean_a + delta * (nb / n), m2_a + m2_b + delta * delta * (na * nb / n)
+
+
 class Simulation:
     """sdp.inventory.Simulation(distributions, sampleNum, recursion) -- also serves the cash classes
     (CashSimulation adds `Math.pow(discountFactor, t)` weights and `+ iniCash`, :108,114)."""
 
     def __init__(self, distributions: Sequence, sampleNum: int, recursion, discountFactor: float = 1.0,
-                 seed: int = 12345):
-        self.distributions = list(distributions)
+                 seed: int = 12345, sampler: str = "host"):
+        """sampler="host" (the default): sample through inverseF in Python, upload, roll on the device.  sampler="device":
+        sample, roll and reduce on the device in one call (SdpEngine.simulate_sampled; seeded and reproducible) --
+        each distribution goes to the engine's sampler of its period; a None entry, or distributions=None, draws that
+        period from the recursion's own pmf tile."""
+        self.sampler = _check_sampler(sampler)
+        self.distributions = None if distributions is None else list(distributions)
         self.sampleNum = int(sampleNum)
         self.recursion = recursion
         self.discountFactor = float(discountFactor)
         self.stateTransition = recursion.getStateTransitionFunction()
         self.immediateValue = recursion.getImmediateValueFunction()
+        self.seed = int(seed)
         self.sampling = Sampling(seed)
         self.last_values = None
+        self.last_result = None
+        if self.sampler == "device":
+            _hand_samplers(recursion, self.distributions)
 
     def setSampleNum(self, n: int):
         self.sampleNum = int(n)
@@ -92,8 +128,31 @@ class Simulation:
                                "of an unclamped family); the reference would re-enter the recursion there")
         return sums
 
+    def _discount(self):
+        return np.array([math.pow(self.discountFactor, t) for t in range(self.recursion.T)], dtype=np.float64)
+
+    def _device_call(self, iniState, n: int, mode: str, first_path: int = 0):
+        """One sample-and-roll call on the device; raises as _rollout does when paths left the grid."""
+        rec = self.recursion
+        rec.getExpectedValue(iniState)  # solves on first use, as Simulation.java:62 does
+        x, cash, preq = rec.functor.tuple_of(iniState)
+        res, sums, _ = rec.engine.simulate_sampled(n, self.seed, x, cash, preq, mode=mode, first_path=first_path,
+                                                   discount=self._discount(), want_sums=True)
+        if res.n_valid != res.n_paths:
+            raise RuntimeError(f"{res.n_paths - res.n_valid} sample paths left the state grid (demand outside the PMF support "
+                               "of an unclamped family); the reference would re-enter the recursion there")
+        self.last_result = res
+        return res, sums
+
     def simulateSDPGivenSamplNum(self, iniState) -> float:
         """Simulation.java:53-74: mean of the simulated totals over `sampleNum` LHS paths."""
+        if self.sampler == "device":
+            res, sums = self._device_call(iniState, self.sampleNum, "lhs")
+            self.last_values = sums
+            mean = res.mean
+            if hasattr(iniState, "getIniCash"):  # CashSimulation.java:114
+                mean += iniState.getIniCash()
+            return mean
         samples = self.sampling.generateLHSamples(self.distributions, self.sampleNum)
         sums = self._rollout(iniState, round_demands(samples))
         self.last_values = sums
@@ -108,6 +167,20 @@ class Simulation:
         (at least 1000 runs).  Paths are rolled in batches on the device."""
         from scipy import stats as _st
         z = float(_st.norm.ppf(0.5 + confidence / 2.0))
+        if self.sampler == "device":
+            # rounds of plain-random paths continuing ONE stream (first_path = paths drawn so far); the rounds' (n, mean, m2)
+            # merged by the pairwise update of Chan, Golub and LeVeque
+            n, mean, m2 = 0, 0.0, 0.0
+            chunks = []
+            center, radius = 0.0, math.inf
+            while n < 1000 or (radius >= center * error and n < maxRuns):
+                res, sums = self._device_call(iniState, batch, "random", first_path=n)
+                n, mean, m2 = merge_moments(n, mean, m2, res.n_paths, res.mean, res.m2)
+                chunks.append(sums)
+                center = mean
+                radius = z * math.sqrt(m2 / (n - 1)) / math.sqrt(n) if n > 1 else math.inf
+            self.last_values = np.concatenate(chunks)
+            return [center, radius]
         vals = np.empty(0)
         center, radius = 0.0, math.inf
         while len(vals) < 1000 or (radius >= center * error and len(vals) < maxRuns):
@@ -139,15 +212,31 @@ class RiskSimulation:
     paths that ever hold negative cash and the paths that ever lose a demand.  The walk runs on the device
     (`sdpgpu_simulate`, family SURVIVAL); sampling and the two ratios stay on the host."""
 
-    def __init__(self, distributions: Sequence, sampleNum: int, recursion, seed: int = 12345):
-        self.distributions = list(distributions)
+    def __init__(self, distributions: Sequence, sampleNum: int, recursion, seed: int = 12345, sampler: str = "host"):
+        """sampler="device": sampling, walk and both counts on the device in one call (see Simulation)."""
+        self.sampler = _check_sampler(sampler)
+        self.distributions = None if distributions is None else list(distributions)
         self.sampleNum = int(sampleNum)
         self.recursion = recursion
+        self.seed = int(seed)
         self.sampling = Sampling(seed)
         self.last_flags = None
+        self.last_result = None
+        if self.sampler == "device":
+            _hand_samplers(recursion, self.distributions)
 
     def simulateLostSale(self, iniState, immediateValue=None):
         """Returns [simulated survival probability, lost-sale rate] (RiskSimulation.java:237-240)."""
+        if self.sampler == "device":
+            rec = self.recursion
+            rec.getSurvProb(iniState)
+            x, cash, _ = rec.functor.tuple_of(iniState)
+            res, _, flags = rec.engine.simulate_sampled(self.sampleNum, self.seed, x, cash, 0.0, mode="lhs", want_sums=True)
+            if res.n_valid != res.n_paths:
+                raise RuntimeError("a sample path left the state grid")
+            self.last_flags = flags
+            self.last_result = res
+            return [1 - res.mean, res.n_lost / float(self.sampleNum)]
         samples = self.sampling.generateLHSamples(self.distributions, self.sampleNum)
         return self.simulateLostSaleOnDemands(iniState, round_demands(samples))
 
