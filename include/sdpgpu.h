@@ -640,7 +640,7 @@ double sdpgpu_period_ms(sdpgpu_handle* h, int32_t period);
  * not counted yet (the period has not run) or not known per period. */
 int64_t sdpgpu_period_cells(sdpgpu_handle* h, int32_t period);
 
-/* ---- batched solve: many backorder-family instances of ONE grid shape ------------------------------------------------
+/* ---- batched solve: many backorder-family instances, of ONE grid shape or each with its own ----------------------------
  * The reference's parameter sweeps -- capacitated.CLSPTesting.main (CLSPTesting.java:33-141: 10 demand patterns x 2 v x
  * 3 pi x 3 K x 3 coeVar = 540 instances of the grid x in [-500, 500], Q = 0..500, T = 8), LevelFitsS, CLSPforDraw -- build
  * a new Recursion per parameter set and call getExpectedValue(initialState) / getAction(initialState) on each
@@ -657,7 +657,17 @@ int64_t sdpgpu_period_cells(sdpgpu_handle* h, int32_t period);
  * (NULL = the last failed sdpgpu_batch_create of this thread); validation and host layout first, device tables on first
  * use; pmfs frozen once the device tables exist; no C++ exception crosses the boundary; the caller's current device is
  * restored; one batch is not thread-safe.  store_all_values = 1 keeps n x T value tables, 0 two ping-pong tables per instance
- * (V_1 and V_2 survive); the policy tables of all periods are kept either way. */
+ * (V_1 and V_2 survive); the policy tables of all periods are kept either way.
+ *
+ * RAGGED batches (sdpgpu_batch_create_ragged): the reference's other F1 sweeps -- capacitated.fitss.OneLevelFitsSTest,
+ * TwoLevelFitsSTest, ThreeLevelFitsSTest (810 instances each), SimOpt -- take the order limit from the instance
+ * (ThreeLevelFitsSTest.java:76-77: 27 distinct limits in one sweep), so the number of actions differs from row to row.  There
+ * min_inventory, max_inventory and max_order_quantity may differ per instance as well, and ini_inventory is a point of the
+ * instance's OWN grid; family, direction, periods, step, clamp_inventory (1), device, store_all_values, world_size (1) and
+ * the kernel still agree, and a mismatch names the instance and the field in the same way.  The object is the same
+ * sdpgpu_batch: every other sdpgpu_batch_* entry point works on it, sizes are per instance (sdpgpu_batch_num_states /
+ * _num_actions), and the size refusals count the SUM of the instances' states.  sdpgpu_batch_create itself still refuses
+ * differing bounds and order limits. */
 typedef struct sdpgpu_batch sdpgpu_batch;
 typedef struct sdpgpu_batch_stats {
   int32_t instances;
@@ -667,13 +677,19 @@ typedef struct sdpgpu_batch_stats {
                                 reset of the key rows and the one finalize pass */
   int32_t window_r;          /* register block of period 1's plan: actions ... */
   int32_t window_s;          /* ... x adjacent states per lane */
-  int32_t window_chunks;     /* largest number of action chunks per state tile over the periods (1: no key atomics) */
+  int32_t window_chunks;     /* largest number of action chunks per state tile of any instance, over the periods (1: no
+                                key atomics) */
   int32_t reserved;
   int64_t lds_bytes;         /* largest dynamic LDS per workgroup over the periods */
   int64_t cells_evaluated;   /* sum over instances and periods of states x actions x D: what n handles would report */
   double  solve_ms;          /* HIP-event time of the last sdpgpu_batch_solve on its stream */
 } sdpgpu_batch_stats;
 int sdpgpu_batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out);
+int sdpgpu_batch_create_ragged(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out);
+/* States / actions (order quantities 0 .. max_order_quantity in steps) of one instance; -1 for a bad argument.  In a batch
+ * of one shape every instance answers alike. */
+int64_t sdpgpu_batch_num_states(const sdpgpu_batch* b, int32_t instance);
+int32_t sdpgpu_batch_num_actions(const sdpgpu_batch* b, int32_t instance);
 void sdpgpu_batch_destroy(sdpgpu_batch* b);
 const char* sdpgpu_batch_last_error(const sdpgpu_batch* b);
 /* pmf of period index t (0-based, as sdpgpu_set_pmf takes it) of one instance.  n (= D) and demand[0] may differ between
@@ -688,7 +704,8 @@ int sdpgpu_batch_set_profiling(sdpgpu_batch* b, int32_t on);
  * when the plan of a small batch chunks the action axis).  Asynchronous on the batch's stream unless `sync` != 0. */
 int sdpgpu_batch_solve(sdpgpu_batch* b, int32_t sync);
 int sdpgpu_batch_synchronize(sdpgpu_batch* b);
-/* V_period[0..n) / the arg-opt action INDEX table (action = index * step) of one instance (1-based period). */
+/* V_period[0..n) / the arg-opt action INDEX table (action = index * step) of one instance (1-based period); n is checked
+ * against the instance's own number of states. */
 int sdpgpu_batch_values(sdpgpu_batch* b, int32_t instance, int32_t period, double* out, int64_t n);
 int sdpgpu_batch_policy(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* out, int64_t n);
 /* What the sweep mains record (CLSPTesting.java:115-118): V_1(ini_inventory_i) and its action INDEX for all n instances,
@@ -697,6 +714,22 @@ int sdpgpu_batch_initial(sdpgpu_batch* b, double* out_value, int32_t* out_action
 int sdpgpu_batch_stats_get(sdpgpu_batch* b, sdpgpu_batch_stats* out);
 /* Time of period t's launch in the last solve (ms; needs sdpgpu_batch_set_profiling), -1 when there is none. */
 double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period);
+/* The launch plan of one period (1-based) of the whole batch, as sdpgpu_plan_period is for a handle: host arithmetic only,
+ * available once every pmf is set, before a device is touched (SDPGPU_ERR_STATE names the first pmf that is missing).  One
+ * register block and ONE chunk_blocks hold for all instances of the period; instance i has ceil(its r-blocks / chunk_blocks)
+ * chunks, and the period is chunked -- key rows, one finalize pass per sweep -- as soon as one instance has two.  A forced
+ * block that does not exist (SDPGPU_WIN_R / _S) returns SDPGPU_ERR_ARG, a plan whose window exceeds the LDS of a compute
+ * unit SDPGPU_ERR_UNSUPPORTED, with the planner's reason. */
+typedef struct sdpgpu_batch_plan {
+  int32_t r, s;              /* register block: actions x adjacent states per lane */
+  int32_t chunk_blocks;      /* register blocks of the action axis per task (an instance with fewer runs its own count) */
+  int32_t chunked;           /* 1: some instance has more than one chunk, all instances go through key rows */
+  int32_t max_chunks;        /* largest ... */
+  int32_t min_chunks;        /* ... and smallest chunk count of an instance */
+  int64_t tasks;             /* waves of the launch: sum over instances of state tiles x chunks */
+  int64_t lds_bytes;         /* dynamic LDS per workgroup (four tasks), sized for the widest instance */
+} sdpgpu_batch_plan;
+int sdpgpu_batch_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_plan* out);
 
 /* ---- batched simulation: roll the policies of ALL instances of a solved batch along demand paths, one launch ------------
  * What CLSPTesting.main does after every solve -- `new Simulation(distributions, 10000, recursion)
@@ -707,7 +740,7 @@ double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period);
  * discount 1.0.  Demands need not lie in the pmf support and may be negative: the grid is clamped.  Works with
  * store_all_values 0 and 1 (the policy rows of all periods are kept either way).  Additive to ABI 6.
  *
- * n_paths: 1 .. 2^24.  ini_x: NULL = every descriptor's ini_inventory, else n grid points.  out_mean[n]: mean of the
+ * n_paths: 1 .. 2^24.  ini_x: NULL = every descriptor's ini_inventory, else n grid points (ini_x[i] on instance i's grid).  out_mean[n]: mean of the
  * instance's path sums, formed on the device in a fixed order (the same bits on every call).  out_sum: NULL, or
  * n x n_paths path sums (instance-major).  Errors as for the rest of the batch: SDPGPU_ERR_ARG names the instance and the
  * field, SDPGPU_ERR_STATE when nothing has been solved; validation comes before any device call. */

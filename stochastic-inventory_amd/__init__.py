@@ -6,7 +6,7 @@ The directory name carries a hyphen (it is fixed by the build contract); import 
 """
 from . import _abi
 from ._abi import (FAMILY_BACKORDER, FAMILY_CASH, FAMILY_CASH_LEADTIME, FAMILY_LEADTIME, FAMILY_OVERDRAFT,
-                   FAMILY_STAFF, FAMILY_SURVIVAL, KERNEL_AUTO, KERNEL_GATHER, KERNEL_WINDOW, SdpgpuBatchStats, SdpgpuDesc, SdpgpuError, SdpgpuStats, desc_defaults)
+                   FAMILY_STAFF, FAMILY_SURVIVAL, KERNEL_AUTO, KERNEL_GATHER, KERNEL_WINDOW, SdpgpuBatchPlan, SdpgpuBatchStats, SdpgpuDesc, SdpgpuError, SdpgpuStats, desc_defaults)
 from .batch import SdpBatch
 from .engine import SdpEngine
 from .functors import (BackorderFunctor, CashFunctor, CashXRFunctor, CashLeadtimeFunctor, CustomFunctor, LeadtimeFunctor, OverdraftFunctor,
@@ -20,7 +20,7 @@ from .workforce import StaffFunctor, StaffRecursion, StaffState
 from .states import CashLeadtimeState, CashState, CashStateXR, LeadtimeState, OptDirection, RiskState, State
 
 __all__ = [
-    "SdpEngine", "SdpBatch", "SdpgpuBatchStats", "RecursionBatch", "SdpgpuDesc", "SdpgpuError", "SdpgpuStats", "desc_defaults",
+    "SdpEngine", "SdpBatch", "SdpgpuBatchPlan", "SdpgpuBatchStats", "RecursionBatch", "SdpgpuDesc", "SdpgpuError", "SdpgpuStats", "desc_defaults",
     "BackorderFunctor", "LeadtimeFunctor", "CashFunctor", "CashXRFunctor", "OverdraftFunctor", "CashLeadtimeFunctor", "SurvivalFunctor", "CustomFunctor",
     "Recursion", "CLSP", "LeadtimeRecursion", "CashRecursion", "CashRecursionXR", "CashLeadtimeRecursion", "RiskRecursion",
     "StaffRecursion", "StaffFunctor", "StaffState", "BinomialDist", "staff_level_pmf",

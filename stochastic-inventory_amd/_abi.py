@@ -126,6 +126,13 @@ class SdpgpuBatchStats(C.Structure):
                 ("cells_evaluated", C.c_int64), ("solve_ms", C.c_double)]
 
 
+class SdpgpuBatchPlan(C.Structure):
+    """struct sdpgpu_batch_plan (include/sdpgpu.h)."""
+
+    _fields_ = [("r", C.c_int32), ("s", C.c_int32), ("chunk_blocks", C.c_int32), ("chunked", C.c_int32),
+                ("max_chunks", C.c_int32), ("min_chunks", C.c_int32), ("tasks", C.c_int64), ("lds_bytes", C.c_int64)]
+
+
 def desc_defaults() -> SdpgpuDesc:
     """Python twin of sdpgpu_desc_init (usable without loading the library)."""
     d = SdpgpuDesc()
@@ -294,6 +301,10 @@ EXPORTS = {
     "sdpgpu_multicash_solve": (C.c_int, [C.POINTER(SdpgpuMulticash), _DP, _IP, _IP, _LP, _LP, _DP]),
     "sdpgpu_multixr_solve": (C.c_int, [C.POINTER(SdpgpuMulticash), C.c_double, _DP, _IP, _IP, _LP, _LP, _DP]),
     "sdpgpu_batch_create": (C.c_int, [C.POINTER(SdpgpuDesc), C.c_int32, C.POINTER(_P)]),
+    "sdpgpu_batch_create_ragged": (C.c_int, [C.POINTER(SdpgpuDesc), C.c_int32, C.POINTER(_P)]),
+    "sdpgpu_batch_num_states": (C.c_int64, [_P, C.c_int32]),
+    "sdpgpu_batch_num_actions": (C.c_int32, [_P, C.c_int32]),
+    "sdpgpu_batch_plan_period": (C.c_int, [_P, C.c_int32, C.POINTER(SdpgpuBatchPlan)]),
     "sdpgpu_batch_destroy": (None, [_P]),
     "sdpgpu_batch_last_error": (C.c_char_p, [_P]),
     "sdpgpu_batch_set_pmf": (C.c_int, [_P, C.c_int32, C.c_int32, _DP, _DP, C.c_int32]),

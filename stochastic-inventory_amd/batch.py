@@ -1,5 +1,7 @@
-"""Thin object wrapper over one sdpgpu_batch (include/sdpgpu.h): N backorder-family instances of ONE grid shape, period t
-of all of them in one kernel launch -- the parameter sweeps of the reference's *Testing mains (CLSPTesting.java:33-141).
+"""Thin object wrapper over one sdpgpu_batch (include/sdpgpu.h): N backorder-family instances, period t of all of them in
+one kernel launch -- the parameter sweeps of the reference's *Testing mains.  The instances share ONE grid shape
+(CLSPTesting.java:33-141) or, with `ragged=True`, each has its own inventory bounds and order limit
+(ThreeLevelFitsSTest.java:67-77).
 
 `pmfs[i]` is instance i's `double[][][] pmf` (Recursion.java:38): pmfs[i][t][j] = [demand, prob].
 """
@@ -11,14 +13,15 @@ from typing import Sequence
 import numpy as np
 
 from . import _abi
-from ._abi import SdpgpuBatchStats, SdpgpuDesc, SdpgpuError
+from ._abi import SdpgpuBatchPlan, SdpgpuBatchStats, SdpgpuDesc, SdpgpuError
 from .engine import _dp, _ip, split_pmf
 
 
 class SdpBatch:
-    """N independent problems of one shape on one GPU; results per instance are those of N SdpEngines, bit for bit."""
+    """N independent problems on one GPU -- of one shape, or (ragged=True) each with its own bounds and order limit;
+    results per instance are those of N SdpEngines, bit for bit."""
 
-    def __init__(self, descs: Sequence[SdpgpuDesc], pmfs, *, device: int = -1):
+    def __init__(self, descs: Sequence[SdpgpuDesc], pmfs, ragged: bool = False, *, device: int = -1):
         self._lib = _abi.load()
         self._b = C.c_void_p()
         descs = list(descs)
@@ -30,12 +33,14 @@ class SdpBatch:
             if device >= 0:
                 arr[i].device = device
         self.n = len(descs)
-        rc = self._lib.sdpgpu_batch_create(arr, self.n, C.byref(self._b))
+        self.ragged = bool(ragged)
+        create = self._lib.sdpgpu_batch_create_ragged if self.ragged else self._lib.sdpgpu_batch_create
+        rc = create(arr, self.n, C.byref(self._b))
         if rc:
             raise SdpgpuError(rc, self._lib.sdpgpu_batch_last_error(None).decode())
         self.T = int(arr[0].periods)
         self.step = float(arr[0].step)
-        self.num_states = int((arr[0].max_inventory - arr[0].min_inventory) / arr[0].step) + 1
+        self.num_states = int((arr[0].max_inventory - arr[0].min_inventory) / arr[0].step) + 1  # (of instance 0)
         try:
             for i, pmf in enumerate(pmfs):
                 tiles = split_pmf(pmf)
@@ -83,14 +88,34 @@ class SdpBatch:
     def synchronize(self):
         self._check(self._lib.sdpgpu_batch_synchronize(self._b))
 
+    def num_states_of(self, i: int) -> int:
+        """States of instance i's own grid."""
+        n = int(self._lib.sdpgpu_batch_num_states(self._b, i))
+        if n < 0:
+            raise IndexError(f"instance {i} outside 0 .. {self.n - 1}")
+        return n
+
+    def num_actions_of(self, i: int) -> int:
+        """Actions (order quantities 0 .. maxOrderQuantity in steps) of instance i."""
+        n = int(self._lib.sdpgpu_batch_num_actions(self._b, i))
+        if n < 0:
+            raise IndexError(f"instance {i} outside 0 .. {self.n - 1}")
+        return n
+
+    def plan(self, period: int) -> SdpgpuBatchPlan:
+        """The launch plan of one period (1-based) for the whole batch: host arithmetic, no device needed."""
+        pl = SdpgpuBatchPlan()
+        self._check(self._lib.sdpgpu_batch_plan_period(self._b, period, C.byref(pl)))
+        return pl
+
     def values(self, i: int, period: int) -> np.ndarray:
-        out = np.empty(self.num_states, dtype=np.float64)
+        out = np.empty(self.num_states_of(i), dtype=np.float64)
         self._check(self._lib.sdpgpu_batch_values(self._b, i, period, _dp(out), len(out)))
         return out
 
     def policy(self, i: int, period: int) -> np.ndarray:
         """Arg-opt action INDEX of every state (action = index * step)."""
-        out = np.empty(self.num_states, dtype=np.int32)
+        out = np.empty(self.num_states_of(i), dtype=np.int32)
         self._check(self._lib.sdpgpu_batch_policy(self._b, i, period, _ip(out), len(out)))
         return out
 

@@ -1,17 +1,23 @@
-// sdp_batch.hpp -- period kernel of a BATCH of backorder-family (F1) instances of one grid shape: period t of all N
-// instances in ONE launch (sdpgpu_batch_solve, sdpgpu_batch.hip).
+// sdp_batch.hpp -- period kernel of a BATCH of backorder-family (F1) instances: period t of all N instances in ONE launch
+// (sdpgpu_batch_solve, sdpgpu_batch.hip).  The instances may share one grid shape (sdpgpu_batch_create) or each have its
+// own inventory bounds and order limit (sdpgpu_batch_create_ragged): a uniform batch is the ragged one with equal records.
 //
 // What a wave does with its task is window_f1_kernel's, by the very same code: f1_stage_window and f1_cells
 // (sdp_f1_cells.hpp) -- so every instance's tables are bit for bit those of a single handle.  New is what surrounds it:
 //
 //   * a TASK (one wave) is (instance, state tile, action chunk); tasks are packed four to a workgroup regardless of the
 //     instance, so a workgroup may hold four different instances.  Everything an instance owns -- its cost constants, the
-//     level of m = 0, its demand count and the places of its probabilities and tables in the batch's arenas -- comes
-//     from a small per-(period, instance) record (BatchInst) read with wave-uniform loads; the probabilities are staged in
-//     LDS per WAVE (window_f1_kernel keeps one copy per workgroup, which all four waves write alike).
-//   * the records of a period are sorted by demand count, longest first (stable): D differs between instances by up to
-//     ~30x (NormalDist(3, 0.3): 4 points, NormalDist(54, 16.2): 121), tasks are dispatched in index order, and the
-//     tail of the launch is then made of short tasks.
+//     level of m = 0, its demand count, its numbers of states, actions, tiles and chunks and the places of its
+//     probabilities and tables in the batch's arenas -- comes from a small per-(period, instance) record (BatchInst) read
+//     with wave-uniform loads; the probabilities are staged in LDS per WAVE (window_f1_kernel keeps one copy per workgroup,
+//     which all four waves write alike).
+//   * which record a task belongs to comes from the period's TASK TABLE (BatchTask, 8 bytes per task, made on the host once
+//     per layout): instances have different numbers of tasks, so `task / tasks_per_instance` does not find the instance.
+//     One wave-uniform 8-byte load replaces that division; a prefix array would cost a binary search of dependent loads.
+//   * the records of a period are sorted by estimated task length -- R-blocks per task x demand count --, longest first
+//     (stable): D differs between instances by up to ~30x (NormalDist(3, 0.3): 4 points, NormalDist(54, 16.2): 121) and
+//     the order limit by 10x (ThreeLevelFitsSTest: 26 .. 288), tasks are dispatched in index order, and the tail of the
+//     launch is then made of short tasks.
 //   * the LDS of a launch is sized for the period's widest instance; a narrower one uses the front of its wave's region.
 //
 // Global memory is written with ordinary vector stores from plain C++ only.
@@ -34,20 +40,27 @@ struct BatchInst {
   int64_t pol_off;     // policy row (int32 arena)
   int64_t key_cur_off, key_next_off;  // key rows of V_t / V_{t+1} (chunked plans)
   int64_t chunk_off;   // chunk rows [n_chunks][n_states] of this (instance, period) (chunked plans)
+  int32_t n_states;    // states of the instance's own grid
+  int32_t n_actions;   // A of the instance
+  int32_t n_tiles;     // its state tiles of 64 S states
+  int32_t n_chunks;    // its tasks per state tile: ceil(its R-blocks / the period's chunk_blocks)
+  int32_t chunk_blocks;  // R-blocks per task: the period's, or all of the instance's when it has fewer
+  int32_t pad;
+};
+
+// One task of a period, in dispatch order: the record it belongs to and chunk * n_tiles + tile within that instance.
+struct BatchTask {
+  int32_t rank, local;
 };
 
 struct BatchLaunch {
   double step;
-  int32_t n_states;       // states of the shared grid
-  int32_t n_actions;      // A
-  int32_t n_tiles;        // state tiles of 64 S states per instance
-  int32_t n_chunks;       // tasks per state tile
-  int32_t chunk_blocks;   // R-blocks per task
-  int32_t tasks_per_inst; // n_tiles * n_chunks; task = rank * tasks_per_inst + chunk * n_tiles + tile
   int32_t n_tasks;
   int32_t span_max;       // window entries of a wave's LDS region (the period's widest instance)
   int32_t p_slots_max;    // doubles of a wave's probability copy
   int32_t maxdir;
+  int32_t chunked;        // some instance has several chunks: EVERY instance writes chunk rows and key rows
+  int32_t pad;
 };
 
 // LDS of a workgroup: four windows and four probability copies
@@ -57,6 +70,7 @@ __host__ __device__ inline size_t batch_wg_lds(int span_max, int p_slots_max) {
 
 template <int R, int S, bool FUTURE, bool KEYED_IN>
 __global__ __launch_bounds__(256) void window_f1_batch_kernel(BatchLaunch L, const BatchInst* __restrict__ inst,
+                                                              const BatchTask* __restrict__ tasks,
                                                               double* __restrict__ values, int32_t* __restrict__ policy,
                                                               const double* __restrict__ pmf,
                                                               unsigned long long* __restrict__ keys,
@@ -68,11 +82,10 @@ __global__ __launch_bounds__(256) void window_f1_batch_kernel(BatchLaunch L, con
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int task = blockIdx.x * 4 + wave;
   if (task >= L.n_tasks) return;  // no workgroup barrier below: a wave may leave on its own
-  const int rank = task / L.tasks_per_inst;
-  const int local = task - rank * L.tasks_per_inst;
-  const int chunk = local / L.n_tiles;
-  const int tile = local - chunk * L.n_tiles;
-  const BatchInst& I = inst[rank];  // (wave-uniform)
+  const BatchTask tk = tasks[task];     // (wave-uniform, as everything derived from it)
+  const BatchInst& I = inst[tk.rank];
+  const int chunk = tk.local / I.n_tiles;
+  const int tile = tk.local - chunk * I.n_tiles;
   // the instance's constants in the shape the shared F1 code takes them (m_tab / c_tab null: the built-in CLSP costs)
   WinParams W{};
   W.lev0 = I.lev0;
@@ -82,19 +95,19 @@ __global__ __launch_bounds__(256) void window_f1_batch_kernel(BatchLaunch L, con
   W.K = I.K;
   W.v = I.v;
   W.idx_off = I.idx_off;
-  W.next_last = L.n_states - 1;
-  W.n_actions = L.n_actions;
+  W.next_last = I.n_states - 1;
+  W.n_actions = I.n_actions;
   W.d_pad = I.d_pad;
   W.d_main = I.d_main;
   W.n_demand = I.n_demand;
-  W.chunk_blocks = L.chunk_blocks;
+  W.chunk_blocks = I.chunk_blocks;
   W.prio_fair = 1;  // (always: the resident waves of a SIMD are tasks of different lengths here)
   W.maxdir = L.maxdir;
   const bool MAXDIR = L.maxdir != 0;
   const double* __restrict__ v_next = FUTURE && !KEYED_IN ? values + I.v_next_off : nullptr;
   const unsigned long long* __restrict__ k_next = KEYED_IN ? keys + I.key_next_off : nullptr;
   const double* __restrict__ pmf_p = pmf + I.pmf_off;
-  const int hi = L.n_states;
+  const int hi = I.n_states;
 
   const int chunk_actions = W.chunk_blocks * R;
   const int span = TS + chunk_actions + W.d_pad + S;  // entries [0, span): slot 0 is a spare; span <= L.span_max
@@ -110,9 +123,9 @@ __global__ __launch_bounds__(256) void window_f1_batch_kernel(BatchLaunch L, con
   double best[S];
   int bestk[S];
   f1_cells<R, S, FUTURE>(W, s_win, s_p, lane, kA, best, bestk);  // (best[u]: state 64*u + lane of the tile)
-  const bool chunked = L.n_chunks > 1;
-  double* __restrict__ out_val = chunked ? chunk_val + I.chunk_off + (int64_t)chunk * L.n_states : values + I.v_cur_off;
-  int32_t* __restrict__ out_idx = chunked ? chunk_idx + I.chunk_off + (int64_t)chunk * L.n_states : policy + I.pol_off;
+  const bool chunked = L.chunked != 0;
+  double* __restrict__ out_val = chunked ? chunk_val + I.chunk_off + (int64_t)chunk * I.n_states : values + I.v_cur_off;
+  int32_t* __restrict__ out_idx = chunked ? chunk_idx + I.chunk_off + (int64_t)chunk * I.n_states : policy + I.pol_off;
   unsigned long long* __restrict__ k_cur = chunked ? keys + I.key_cur_off : nullptr;
 #pragma unroll
   for (int u = 0; u < S; ++u) {

@@ -3,8 +3,9 @@
 // CLSPTesting lambdas (CLSPTesting.java:89-106), one demand path per lane, with the demand of a (path, period) either read
 // from memory or DRAWN here (Sampling.generateLHSamples, Sampling.java:86-103, made reproducible).
 //
-//   * a wave's 64 paths belong to ONE instance (the paths of an instance are padded to whole waves), so the instance's cost
-//     record, its sampler records and its policy-row offsets are wave-uniform loads;
+//   * a wave's 64 paths belong to ONE instance (the paths of an instance are padded to whole waves), so the instance's
+//     record -- costs, inventory bounds, state count, the base of its policy rows --, its sampler records and its policy-row
+//     offsets are wave-uniform loads;
 //   * the rollout statements are cell<FAM_BACKORDER> of sdp_device.hpp word for word (simulate_kernel of sdp_gather.hpp with
 //     discount 1.0: `1.0 * imm` is `imm`), so a path's sum has the bits sdpgpu_simulate gives on a handle of the instance;
 //   * the sampler ("Batched simulation"): stratum j = sigma(p) of path p, a = 53 bits of Philox4x32-10 at counter
@@ -20,13 +21,17 @@
 
 namespace sdp {
 
+// An instance's costs and its OWN grid (the instances of a ragged batch differ in it); wave-uniform in the rollout.
 struct SimInst {
   double h, pi, K, v;
+  double min_inventory, max_inventory;
+  int64_t pol_base;  // the instance's policy rows [T][n_states] in the batch's policy arena
+  int32_t n_states, pad;
 };
 
 struct SimLaunch {
-  double step, inv_step, min_inventory, max_inventory;
-  int32_t T, n_states, n_inst, n_paths;
+  double step, inv_step;
+  int32_t T, n_inst, n_paths;
   int32_t waves_per_inst;  // ceil(n_paths / 64)
   int32_t half_bits;       // sigma: smallest h >= 1 with 4^h >= n_paths
   int64_t demand_stride;   // explicit demands: elements between the demand sets of two instances (0: one shared set)
@@ -57,7 +62,7 @@ __global__ __launch_bounds__(256) void batch_sim_kernel(SimLaunch L, const SimIn
   double sum = 0.0;
   if (p < L.n_paths) {
     int idx = ini_idx[i];
-    const int32_t* __restrict__ pol = policy + (int64_t)i * L.T * L.n_states;
+    const int32_t* __restrict__ pol = policy + I.pol_base;
     const double* __restrict__ dem = SAMPLED ? nullptr : demand + (int64_t)i * L.demand_stride + (int64_t)p * L.T;
     for (int t = 0; t < L.T; ++t) {
       double d;
@@ -68,8 +73,8 @@ __global__ __launch_bounds__(256) void batch_sim_kernel(SimLaunch L, const SimIn
         d = dem[t];
       }
       // decode_state / action_setup / cell of the backorder family (sdp_device.hpp; CLSP.java:255-272)
-      const double x = L.min_inventory + (double)idx * L.step;
-      const int k = pol[(int64_t)t * L.n_states + idx];
+      const double x = I.min_inventory + (double)idx * L.step;
+      const int k = pol[(int64_t)t * I.n_states + idx];
       const double a = (double)k * L.step;
       const double fixed = a > 0 ? I.K : 0.0;
       const double var = I.v * a;
@@ -82,10 +87,10 @@ __global__ __launch_bounds__(256) void batch_sim_kernel(SimLaunch L, const SimIn
       sum += imm;
       if (t + 1 < L.T) {
         double nx = level;
-        nx = nx > L.max_inventory ? L.max_inventory : nx;
-        nx = nx < L.min_inventory ? L.min_inventory : nx;
-        idx = (int)((nx - L.min_inventory) * L.inv_step);
-        idx = idx < 0 ? 0 : (idx >= L.n_states ? L.n_states - 1 : idx);  // (a NaN demand must not leave the policy row)
+        nx = nx > I.max_inventory ? I.max_inventory : nx;
+        nx = nx < I.min_inventory ? I.min_inventory : nx;
+        idx = (int)((nx - I.min_inventory) * L.inv_step);
+        idx = idx < 0 ? 0 : (idx >= I.n_states ? I.n_states - 1 : idx);  // (a NaN demand must not leave the policy row)
       }
     }
     if (out_sum) out_sum[(int64_t)i * L.n_paths + p] = sum;

@@ -1,7 +1,9 @@
-// sdpgpu_batch.hip -- a BATCH of backorder-family (F1) instances of one grid shape (include/sdpgpu.h, sdpgpu_batch_*): the
-// parameter sweeps of the reference's *Testing mains (capacitated.CLSPTesting.main: 540 instances of one grid).  Period t
-// of ALL instances runs in one launch of window_f1_batch_kernel (sdp_batch.hpp); this file holds the validation, the host
-// layout, the plan of a period, the launcher and the entry points.  Separate from sdpgpu_handle on purpose: a batch has no
+// sdpgpu_batch.hip -- a BATCH of backorder-family (F1) instances (include/sdpgpu.h, sdpgpu_batch_*): the parameter sweeps of
+// the reference's *Testing mains -- of one grid shape (capacitated.CLSPTesting.main: 540 instances of one grid;
+// sdpgpu_batch_create) or with inventory bounds and an order limit of their own (capacitated.fitss.ThreeLevelFitsSTest.main:
+// 810 instances with 27 order limits; sdpgpu_batch_create_ragged).  Period t of ALL instances runs in one launch of
+// window_f1_batch_kernel (sdp_batch.hpp); this file holds the validation, the host layout with its prefix-sum arenas, the
+// plan of a period, the task table, the launcher and the entry points.  Separate from sdpgpu_handle on purpose: a batch has no
 // slabs, no exchange, no user functors -- and the handle does not grow.
 #include "sdpgpu_internal.hpp"
 #include "sdp_batch.hpp"
@@ -14,14 +16,19 @@ int32_t full_action_count(const sdpgpu_desc& d);    // sdpgpu.hip
 
 // (R, S, chunks) of one period for the whole batch
 struct BatchPlan {
-  int R = 0, S = 0, n_chunks = 1, chunk_blocks = 0, n_tiles = 0, tasks_per_inst = 0, span_max = 0, p_slots_max = 0;
+  int R = 0, S = 0, chunk_blocks = 0, span_max = 0, p_slots_max = 0;
+  int n_chunks = 1, min_chunks = 1;  // largest / smallest chunk count of an instance: ceil(its R-blocks / chunk_blocks)
+  int64_t n_tasks = 0;               // sum over instances of tiles x chunks
   size_t smem = 0;
 };
 
 struct sdpgpu_batch {
   std::vector<sdpgpu_desc> d;
   int32_t N = 0, T = 0;
-  int32_t nx = 0, A = 0;  // states and actions of the shared grid
+  bool ragged = false;             // sdpgpu_batch_create_ragged: bounds and order limit are the instance's own
+  std::vector<int32_t> nxs, As;    // [i]: states and actions of instance i
+  std::vector<size_t> val_base, pol_base;  // [i]: prefix sums -- instance i's value rows / policy (and key) rows
+  int64_t sum_nx = 0;
   std::vector<double> d0;                  // [i * T + t]: first demand value
   std::vector<std::vector<double>> pmf_p;  // [i * T + t]
   std::vector<char> pmf_set;
@@ -30,6 +37,8 @@ struct sdpgpu_batch {
   std::vector<BatchPlan> plan;             // [t]
   std::vector<sdp::BatchInst> inst;        // [t * N + rank], longest demand first
   std::vector<size_t> pmf_off;             // [i * T + t]
+  std::vector<sdp::BatchTask> tasks;       // the periods' task tables, one after the other
+  std::vector<size_t> task_off;            // [t]: first task of period t
   bool any_chunked = false;
   size_t values_elems = 0, policy_elems = 0, pmf_elems = 0, key_elems = 0, chunk_elems = 0;
   int64_t total_final = 0;                 // states the finalize pass resolves
@@ -43,6 +52,7 @@ struct sdpgpu_batch {
   int32_t* d_policy = nullptr;
   double* d_pmf = nullptr;
   sdp::BatchInst* d_inst = nullptr;
+  sdp::BatchTask* d_tasks = nullptr;
   unsigned long long* d_keys = nullptr;
   double* d_chunk_val = nullptr;
   int32_t* d_chunk_idx = nullptr;
@@ -134,19 +144,24 @@ struct Cand {
 constexpr Cand kCand[] = {{4, 1, 8}, {4, 2, 6}, {4, 4, 4}, {4, 8, 2}};
 
 // One plan per period for the whole batch, by the reasoning of the single-handle planner (plan_window_search): a launch
-// costs what its busiest SIMD executes.  Tasks differ in length (D differs per instance) and are dispatched longest first,
-// so the estimate is the larger of the mean load per SIMD and the longest task, at the issue rate the resident waves
-// sustain, plus one shortest task for the tail.  Chunking the action axis (key atomics + finalize pass) is considered only
-// for a SMALL batch: when 64-state tiles alone give every SIMD four tasks (N * ceil(nx / 64) >= 4096) the plan is always one
-// task per (instance, tile) -- no key rows, no finalize launch.
+// costs what its busiest SIMD executes.  Tasks differ in length (D, and in a ragged batch the order limit, differ per instance)
+// and are dispatched longest first, so the estimate is the larger of the mean load per SIMD and the longest task, at the issue
+// rate the resident waves sustain, plus one shortest task for the tail.  An instance's task length comes from its own
+// R-blocks and its own D, its tile count from its own states.  Chunking the action axis (key atomics + finalize pass) is
+// considered only for a SMALL batch: when 64-state tiles alone give every SIMD four tasks (sum of ceil(nx_i / 64) >= 4096) the
+// plan is always one task per (instance, tile) -- no key rows, no finalize launch.  There is ONE chunk_blocks per period:
+// instance i has ceil(blocks_i / chunk_blocks) chunks, and a period is chunked as soon as one instance has two.
 int plan_period(sdpgpu_batch* b, int t, BatchPlan* out) {
-  const int N = b->N, T = b->T, A = b->A, nx = b->nx;
-  int d_max = 0;
+  const int N = b->N, T = b->T;
+  int d_max = 0, a_max = 0;
+  int64_t tiles64 = 0;
   for (int i = 0; i < N; ++i) {
     const int D = (int)b->pmf_p[(size_t)i * T + t].size();
     d_max = std::max(d_max, D);
+    a_max = std::max(a_max, (int)b->As[(size_t)i]);
+    tiles64 += (b->nxs[(size_t)i] + 63) / 64;
   }
-  const bool may_chunk = b->d[0].store_all_values && (int64_t)N * ((nx + 63) / 64) < 4096;
+  const bool may_chunk = b->d[0].store_all_values && tiles64 < 4096;
   BatchPlan best;
   double best_cost = -1;
   bool shape_seen = false;
@@ -156,8 +171,7 @@ int plan_period(sdpgpu_batch* b, int t, BatchPlan* out) {
     if (b->win_s && c.s != b->win_s) continue;
     shape_seen = true;
     const int r = c.r, sl = c.s, nw = r + sl - 1, ts = 64 * sl;
-    const int n_tiles = (nx + ts - 1) / ts;
-    const int blocks_total = rup(A, r) / r;
+    const int blocks_total = rup(a_max, r) / r;  // of the instance with the most actions
     const double step_ops = 3.0 * r * sl + r + (r + sl - 1) + 3.0;  // fp64 instructions of one demand step of one R-block
     int forced_nch = 0;
     if (b->win_nch) {
@@ -171,7 +185,24 @@ int plan_period(sdpgpu_batch* b, int t, BatchPlan* out) {
       if ((blocks_total + bpc - 1) / bpc != nch) continue;  // same plan as a smaller nch
       if (nch > 1 && !may_chunk && !forced_nch) break;
       if (nch > 1 && !b->d[0].store_all_values) break;  // chunk rows need every period's rows (as for a handle)
-      const int span_max = ts + bpc * r + rup(d_max, nw) + sl;
+      int span_max = 0, min_chunks = nch;
+      int64_t tasks = 0;
+      double total = 0, longest = 0, shortest = 0;
+      for (int i = 0; i < N; ++i) {
+        const int D = (int)b->pmf_p[(size_t)i * T + t].size();
+        const int blocks = rup(b->As[(size_t)i], r) / r;
+        const int cb = std::min(bpc, blocks);        // R-blocks of one task of this instance
+        const int chunks = (blocks + bpc - 1) / bpc;
+        const int64_t tiles = (b->nxs[(size_t)i] + ts - 1) / ts;
+        const int span = ts + cb * r + rup(D, nw) + sl;
+        span_max = std::max(span_max, span);
+        min_chunks = std::min(min_chunks, chunks);
+        tasks += tiles * chunks;
+        const double task = cb * (D * step_ops + 60.0 + 2.0 * (sl - 1) * r) + 400.0 + 4.0 * span;
+        total += task * (double)(tiles * chunks);
+        longest = std::max(longest, task);
+        shortest = shortest == 0 ? task : std::min(shortest, task);
+      }
       const int p_slots = sdp::win_p_slots(d_max);
       const size_t smem = sdp::batch_wg_lds(span_max, p_slots);
       const int wg = std::min(c.waves, lds_workgroups(smem));
@@ -179,16 +210,6 @@ int plan_period(sdpgpu_batch* b, int t, BatchPlan* out) {
         lds_least = lds_least ? std::min(lds_least, smem) : smem;
         continue;
       }
-      double total = 0, longest = 0, shortest = 0;
-      for (int i = 0; i < N; ++i) {
-        const int D = (int)b->pmf_p[(size_t)i * T + t].size();
-        const double task = bpc * (D * step_ops + 60.0 + 2.0 * (sl - 1) * r) + 400.0 + 4.0 * (ts + bpc * r + rup(D, nw) + sl);
-        total += task;
-        longest = std::max(longest, task);
-        shortest = shortest == 0 ? task : std::min(shortest, task);
-      }
-      const int64_t tasks = (int64_t)N * n_tiles * nch;
-      total *= (double)n_tiles * nch;
       const int64_t resident = std::min<int64_t>(wg, (tasks + 1023) / 1024);
       auto eff = [&](int64_t w) { return w >= 8 ? 0.97 : (w >= 4 ? 0.94 : (w >= 3 ? 0.91 : (w >= 2 ? (r * sl >= 32 ? 0.93 : 0.85) : 0.60))); };
       const double cost = std::max(total / 1024.0, longest) / eff(resident) + shortest / 0.60;
@@ -197,9 +218,9 @@ int plan_period(sdpgpu_batch* b, int t, BatchPlan* out) {
         best.R = r;
         best.S = sl;
         best.n_chunks = nch;
+        best.min_chunks = min_chunks;
         best.chunk_blocks = bpc;
-        best.n_tiles = n_tiles;
-        best.tasks_per_inst = n_tiles * nch;
+        best.n_tasks = tasks;
         best.span_max = span_max;
         best.p_slots_max = p_slots;
         best.smem = smem;
@@ -211,18 +232,19 @@ int plan_period(sdpgpu_batch* b, int t, BatchPlan* out) {
       return bfail(b, SDPGPU_ERR_ARG, "batch kernel: no instantiation for the forced block SDPGPU_WIN_R=%d SDPGPU_WIN_S=%d (have R x S = 4x1 4x2 4x4 4x8)",
                    b->win_r, b->win_s);
     return bfail(b, SDPGPU_ERR_UNSUPPORTED, "batch kernel: %d actions x %d demand steps (period %d) need %zu B of LDS per workgroup, over the %zu B of a "
-                 "compute unit", A, d_max, t + 1, lds_least, kLdsPerCU);
+                 "compute unit", a_max, d_max, t + 1, lds_least, kLdsPerCU);
   }
-  if ((int64_t)N * best.tasks_per_inst > INT32_MAX / 2) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "batch kernel: too many tasks in one launch");
+  if (best.n_tasks > INT32_MAX / 2) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "batch kernel: too many tasks in one launch");
   *out = best;
   return SDPGPU_OK;
 }
 
+// rows of instance i in the arenas: the instances follow each other, each with its own row length (prefix sums)
 size_t value_row(const sdpgpu_batch* b, int i, int t) {
-  if (b->d[0].store_all_values) return ((size_t)i * b->T + t) * (size_t)b->nx;
-  return ((size_t)i * 2 + (size_t)(t & 1)) * (size_t)b->nx;  // two ping-pong tables per instance
+  const size_t row = b->d[0].store_all_values ? (size_t)t : (size_t)(t & 1);  // (or two ping-pong tables per instance)
+  return b->val_base[(size_t)i] + row * (size_t)b->nxs[(size_t)i];
 }
-size_t policy_row(const sdpgpu_batch* b, int i, int t) { return ((size_t)i * b->T + t) * (size_t)b->nx; }
+size_t policy_row(const sdpgpu_batch* b, int i, int t) { return b->pol_base[(size_t)i] + (size_t)t * (size_t)b->nxs[(size_t)i]; }
 
 // host layout: plans, arena offsets, the per-(period, instance) records in task order, the finalize jobs
 int layout(sdpgpu_batch* b) {
@@ -238,8 +260,8 @@ int layout(sdpgpu_batch* b) {
     if (rc) return rc;
     if (b->plan[(size_t)t].n_chunks > 1) b->any_chunked = true;
   }
-  b->values_elems = (size_t)N * (b->d[0].store_all_values ? T : 2) * (size_t)b->nx;
-  b->policy_elems = (size_t)N * T * (size_t)b->nx;
+  b->values_elems = (size_t)b->sum_nx * (size_t)(b->d[0].store_all_values ? T : 2);
+  b->policy_elems = (size_t)b->sum_nx * (size_t)T;
   b->pmf_off.assign((size_t)N * T, 0);
   size_t off = 0;
   b->cells = 0;
@@ -248,22 +270,29 @@ int layout(sdpgpu_batch* b) {
       b->pmf_off[(size_t)i * T + t] = off;
       const size_t D = b->pmf_p[(size_t)i * T + t].size();
       off += D + kPmfPad;  // the probabilities are followed by kPmfPad zeros
-      b->cells += (int64_t)b->nx * b->A * (int64_t)D;
+      b->cells += (int64_t)b->nxs[(size_t)i] * b->As[(size_t)i] * (int64_t)D;
     }
   b->pmf_elems = off;
-  b->key_elems = b->any_chunked ? (size_t)N * T * (size_t)b->nx : 0;
+  b->key_elems = b->any_chunked ? b->policy_elems : 0;  // (a key row per policy row, at the same offsets)
   b->inst.assign((size_t)T * N, sdp::BatchInst());
   b->jobs.clear();
   size_t chunk_off = 0;
   int64_t first = 0;
   std::vector<int> order((size_t)N);
+  std::vector<int64_t> length((size_t)N);
+  b->tasks.clear();
+  b->task_off.assign((size_t)T, 0);
   for (int t = 0; t < T; ++t) {
     const BatchPlan& pl = b->plan[(size_t)t];
-    const int nw = pl.R + pl.S - 1;
-    for (int i = 0; i < N; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int c) {
-      return b->pmf_p[(size_t)a * T + t].size() > b->pmf_p[(size_t)c * T + t].size();
-    });
+    const int nw = pl.R + pl.S - 1, ts = 64 * pl.S;
+    // longest estimated task first: the instance's R-blocks per task x its demand count
+    for (int i = 0; i < N; ++i) {
+      order[(size_t)i] = i;
+      const int blocks = rup(b->As[(size_t)i], pl.R) / pl.R;
+      length[(size_t)i] = (int64_t)std::min(pl.chunk_blocks, blocks) * (int64_t)b->pmf_p[(size_t)i * T + t].size();
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return length[(size_t)a] > length[(size_t)c]; });
+    b->task_off[(size_t)t] = b->tasks.size();
     for (int rank = 0; rank < N; ++rank) {
       const int i = order[(size_t)rank];
       const sdpgpu_desc& d = b->d[(size_t)i];
@@ -283,28 +312,39 @@ int layout(sdpgpu_batch* b) {
       I.v_cur_off = (int64_t)value_row(b, i, t);
       I.v_next_off = t + 1 < T ? (int64_t)value_row(b, i, t + 1) : 0;
       I.pol_off = (int64_t)policy_row(b, i, t);
-      I.key_cur_off = (int64_t)(((size_t)i * T + t) * (size_t)b->nx);
-      I.key_next_off = t + 1 < T ? (int64_t)(((size_t)i * T + t + 1) * (size_t)b->nx) : 0;
+      I.key_cur_off = (int64_t)policy_row(b, i, t);
+      I.key_next_off = t + 1 < T ? (int64_t)policy_row(b, i, t + 1) : 0;
+      const int32_t nx = b->nxs[(size_t)i];
+      const int blocks = rup(b->As[(size_t)i], pl.R) / pl.R;
+      I.n_states = nx;
+      I.n_actions = b->As[(size_t)i];
+      I.n_tiles = (nx + ts - 1) / ts;
+      I.n_chunks = (blocks + pl.chunk_blocks - 1) / pl.chunk_blocks;
+      I.chunk_blocks = std::min(pl.chunk_blocks, blocks);
+      for (int32_t local = 0; local < I.n_tiles * I.n_chunks; ++local) b->tasks.push_back(sdp::BatchTask{rank, local});
       I.chunk_off = 0;
-      if (pl.n_chunks > 1) {
+      if (pl.n_chunks > 1) {  // a chunked period: every instance goes through chunk rows and key rows, with its own count
         I.chunk_off = (int64_t)chunk_off;
-        chunk_off += (size_t)pl.n_chunks * (size_t)b->nx;
+        chunk_off += (size_t)I.n_chunks * (size_t)nx;
         sdp::FinalizeJob J{};
-        J.stride = b->nx;
+        J.stride = nx;
         J.lo = J.vlo = 0;
-        J.hi = J.vhi = b->nx;
+        J.hi = J.vhi = nx;
         J.first = first;
-        J.n_chunks = pl.n_chunks;
+        J.n_chunks = I.n_chunks;
         // (device addresses are filled in at allocation; the offsets travel in the pointer fields until then)
         J.keys = reinterpret_cast<const unsigned long long*>((uintptr_t)I.key_cur_off);
         J.part_val = reinterpret_cast<const double*>((uintptr_t)I.chunk_off);
         J.v_out = reinterpret_cast<double*>((uintptr_t)I.v_cur_off);
         J.pol_out = reinterpret_cast<int32_t*>((uintptr_t)I.pol_off);
-        first += b->nx;
+        first += nx;
         b->jobs.push_back(J);
       }
       b->inst[(size_t)t * N + rank] = I;
     }
+    if ((int64_t)(b->tasks.size() - b->task_off[(size_t)t]) != pl.n_tasks)
+      return bfail(b, SDPGPU_ERR_INTERNAL, "batch layout: period %d has %zu tasks, its plan says %lld", t + 1,
+                   b->tasks.size() - b->task_off[(size_t)t], (long long)pl.n_tasks);
   }
   b->chunk_elems = chunk_off;
   b->total_final = first;
@@ -337,6 +377,8 @@ int allocate(sdpgpu_batch* b) {
   }
   BHIP_TRY(b, hipMalloc((void**)&b->d_inst, b->inst.size() * sizeof(sdp::BatchInst)));
   BHIP_TRY(b, hipMemcpy(b->d_inst, b->inst.data(), b->inst.size() * sizeof(sdp::BatchInst), hipMemcpyHostToDevice));
+  BHIP_TRY(b, hipMalloc((void**)&b->d_tasks, std::max<size_t>(b->tasks.size(), 1) * sizeof(sdp::BatchTask)));
+  BHIP_TRY(b, hipMemcpy(b->d_tasks, b->tasks.data(), b->tasks.size() * sizeof(sdp::BatchTask), hipMemcpyHostToDevice));
   if (b->any_chunked) {
     BHIP_TRY(b, hipMalloc((void**)&b->d_keys, b->key_elems * sizeof(unsigned long long)));
     BHIP_TRY(b, hipMalloc((void**)&b->d_chunk_val, std::max<size_t>(b->chunk_elems, 1) * sizeof(double)));
@@ -373,8 +415,8 @@ int allocate(sdpgpu_batch* b) {
 }
 
 template <int R, int S>
-hipError_t launch_rs(sdpgpu_batch* b, const sdp::BatchLaunch& L, const BatchPlan& pl, const sdp::BatchInst* inst, bool future,
-                     bool keyed_in) {
+hipError_t launch_rs(sdpgpu_batch* b, const sdp::BatchLaunch& L, const BatchPlan& pl, const sdp::BatchInst* inst,
+                     const sdp::BatchTask* tasks, bool future, bool keyed_in) {
   const dim3 grid((unsigned)((L.n_tasks + 3) / 4));
 #define SDP_BATCH_GO(FU, KI)                                                                                         \
   do {                                                                                                               \
@@ -382,7 +424,7 @@ hipError_t launch_rs(sdpgpu_batch* b, const sdp::BatchLaunch& L, const BatchPlan
     hipError_t ea = lds_allow(sdp::window_f1_batch_kernel<R, S, FU, KI>, pl.smem, &mark);                            \
     if (ea != hipSuccess) return ea;                                                                                 \
     hipLaunchKernelGGL((sdp::window_f1_batch_kernel<R, S, FU, KI>), grid, dim3(256), pl.smem, b->stream, L, inst,    \
-                       b->d_values, b->d_policy, b->d_pmf, b->d_keys, b->d_chunk_val, b->d_chunk_idx);               \
+                       tasks, b->d_values, b->d_policy, b->d_pmf, b->d_keys, b->d_chunk_val, b->d_chunk_idx);        \
   } while (0)
   if (!future)
     SDP_BATCH_GO(false, false);
@@ -398,13 +440,8 @@ hipError_t launch_period(sdpgpu_batch* b, int t) {
   const BatchPlan& pl = b->plan[(size_t)t];
   sdp::BatchLaunch L{};
   L.step = b->d[0].step;
-  L.n_states = b->nx;
-  L.n_actions = b->A;
-  L.n_tiles = pl.n_tiles;
-  L.n_chunks = pl.n_chunks;
-  L.chunk_blocks = pl.chunk_blocks;
-  L.tasks_per_inst = pl.tasks_per_inst;
-  L.n_tasks = b->N * pl.tasks_per_inst;
+  L.n_tasks = (int32_t)pl.n_tasks;
+  L.chunked = pl.n_chunks > 1;
   L.span_max = pl.span_max;
   L.p_slots_max = pl.p_slots_max;
   L.maxdir = b->d[0].direction == SDPGPU_MAX;
@@ -414,15 +451,17 @@ hipError_t launch_period(sdpgpu_batch* b, int t) {
   // finalize pass at the end of the sweep)
   const bool keyed_in = future && b->plan[(size_t)t + 1].n_chunks > 1;
   const sdp::BatchInst* inst = b->d_inst + (size_t)t * b->N;
-  if (pl.R == 4 && pl.S == 1) return launch_rs<4, 1>(b, L, pl, inst, future, keyed_in);
-  if (pl.R == 4 && pl.S == 2) return launch_rs<4, 2>(b, L, pl, inst, future, keyed_in);
-  if (pl.R == 4 && pl.S == 4) return launch_rs<4, 4>(b, L, pl, inst, future, keyed_in);
-  if (pl.R == 4 && pl.S == 8) return launch_rs<4, 8>(b, L, pl, inst, future, keyed_in);
+  const sdp::BatchTask* tasks = b->d_tasks + b->task_off[(size_t)t];
+  if (pl.R == 4 && pl.S == 1) return launch_rs<4, 1>(b, L, pl, inst, tasks, future, keyed_in);
+  if (pl.R == 4 && pl.S == 2) return launch_rs<4, 2>(b, L, pl, inst, tasks, future, keyed_in);
+  if (pl.R == 4 && pl.S == 4) return launch_rs<4, 4>(b, L, pl, inst, tasks, future, keyed_in);
+  if (pl.R == 4 && pl.S == 8) return launch_rs<4, 8>(b, L, pl, inst, tasks, future, keyed_in);
   return hipErrorInvalidValue;
 }
 
-// what differs between instance k and instance 0 although the batch needs it shared (nullptr: nothing)
-const char* shape_mismatch(const sdpgpu_desc& a, const sdpgpu_desc& c, char* buf, size_t n) {
+// what differs between instance k and instance 0 although the batch needs it shared (nullptr: nothing); a ragged batch
+// leaves the inventory bounds and the order limit to the instance
+const char* shape_mismatch(const sdpgpu_desc& a, const sdpgpu_desc& c, bool ragged, char* buf, size_t n) {
 #define SDP_SAME_I(f) \
   if (a.f != c.f) { std::snprintf(buf, n, #f " %d differs from instance 0's %d", (int)c.f, (int)a.f); return buf; }
 #define SDP_SAME_D(f) \
@@ -430,9 +469,11 @@ const char* shape_mismatch(const sdpgpu_desc& a, const sdpgpu_desc& c, char* buf
   SDP_SAME_I(direction)
   SDP_SAME_I(periods)
   SDP_SAME_D(step)
-  SDP_SAME_D(min_inventory)
-  SDP_SAME_D(max_inventory)
-  SDP_SAME_D(max_order_quantity)
+  if (!ragged) {
+    SDP_SAME_D(min_inventory)
+    SDP_SAME_D(max_inventory)
+    SDP_SAME_D(max_order_quantity)
+  }
   SDP_SAME_I(device)
   SDP_SAME_I(store_all_values)
 #undef SDP_SAME_I
@@ -440,14 +481,7 @@ const char* shape_mismatch(const sdpgpu_desc& a, const sdpgpu_desc& c, char* buf
   return nullptr;
 }
 
-}  // namespace
-
-// =================================================================================================
-// C ABI
-// =================================================================================================
-extern "C" {
-
-int sdpgpu_batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out) {
+int batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out, bool ragged) {
   g_create_error.clear();
   if (!descs || !out) return bfail(nullptr, SDPGPU_ERR_ARG, "batch_create: null argument (descs, out)");
   *out = nullptr;
@@ -469,23 +503,49 @@ int sdpgpu_batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out)
       if (d.kernel != SDPGPU_KERNEL_AUTO && d.kernel != SDPGPU_KERNEL_WINDOW)
         return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "instance %d: kernel %d -- a batch runs the window kernel (SDPGPU_KERNEL_AUTO or _WINDOW)", k, d.kernel);
       char buf[160];
-      if (const char* why = shape_mismatch(descs[0], d, buf, sizeof buf))
-        return bfail(nullptr, SDPGPU_ERR_ARG, "instance %d: %s (the instances of a batch share one grid shape)", k, why);
+      if (const char* why = shape_mismatch(descs[0], d, ragged, buf, sizeof buf))
+        return bfail(nullptr, SDPGPU_ERR_ARG, "instance %d: %s (%s)", k, why,
+                     ragged ? "the instances of a ragged batch share direction, horizon, step, device and table storage"
+                            : "the instances of a batch share one grid shape");
       if (std::fmod(d.ini_inventory, d.step) != 0 || d.ini_inventory < d.min_inventory || d.ini_inventory > d.max_inventory)
         return bfail(nullptr, SDPGPU_ERR_ARG, "instance %d: ini_inventory %g is not a point of the grid [%g, %g]", k, d.ini_inventory, d.min_inventory, d.max_inventory);
     }
     const sdpgpu_desc& d = descs[0];
-    const int64_t nx = (int64_t)((d.max_inventory - d.min_inventory) / d.step) + 1;
-    const int32_t A = full_action_count(d);
-    if (nx >= 2147483647LL - 4096 || (int64_t)A + nx > 2000000000LL) return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "axis longer than 2^31");
-    if ((double)nx * d.periods * n > 4.0e9) return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "batch tables of %d x %d x %lld states are too large", n, d.periods, (long long)nx);
+    // states and actions per instance; the size refusals count the SUM of the instances' states
+    std::vector<int32_t> nxs((size_t)n), As((size_t)n);
+    double sum_nx = 0;
+    for (int32_t k = 0; k < n; ++k) {
+      const sdpgpu_desc& dk = descs[k];
+      const int64_t nx = (int64_t)((dk.max_inventory - dk.min_inventory) / dk.step) + 1;
+      const int32_t A = full_action_count(dk);
+      if (nx >= 2147483647LL - 4096 || (int64_t)A + nx > 2000000000LL) return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "axis longer than 2^31");
+      nxs[(size_t)k] = (int32_t)nx;
+      As[(size_t)k] = A;
+      sum_nx += (double)nx;
+    }
+    if (sum_nx * d.periods > 4.0e9) {
+      if (ragged)
+        return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "batch tables of %d periods x %.0f states (the sum over %d instances) are too large", d.periods, sum_nx, n);
+      return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "batch tables of %d x %d x %lld states are too large", n, d.periods, (long long)nxs[0]);
+    }
     sdpgpu_batch* b = new sdpgpu_batch();
     try {
       b->d.assign(descs, descs + n);
       b->N = n;
       b->T = d.periods;
-      b->nx = (int32_t)nx;
-      b->A = A;
+      b->ragged = ragged;
+      b->nxs.swap(nxs);
+      b->As.swap(As);
+      b->val_base.assign((size_t)n, 0);
+      b->pol_base.assign((size_t)n, 0);
+      size_t vb = 0, pb = 0;
+      for (int32_t k = 0; k < n; ++k) {
+        b->val_base[(size_t)k] = vb;
+        b->pol_base[(size_t)k] = pb;
+        vb += (size_t)b->nxs[(size_t)k] * (size_t)(d.store_all_values ? d.periods : 2);
+        pb += (size_t)b->nxs[(size_t)k] * (size_t)d.periods;
+      }
+      b->sum_nx = (int64_t)sum_nx;
       b->device = d.device;
       b->d0.assign((size_t)n * b->T, 0.0);
       b->pmf_p.resize((size_t)n * b->T);
@@ -506,6 +566,47 @@ int sdpgpu_batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out)
   });
 }
 
+}  // namespace
+
+// =================================================================================================
+// C ABI
+// =================================================================================================
+extern "C" {
+
+int sdpgpu_batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out) { return batch_create(descs, n, out, false); }
+
+int sdpgpu_batch_create_ragged(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out) { return batch_create(descs, n, out, true); }
+
+int64_t sdpgpu_batch_num_states(const sdpgpu_batch* b, int32_t instance) {
+  return b && instance >= 0 && instance < b->N ? (int64_t)b->nxs[(size_t)instance] : -1;
+}
+
+int32_t sdpgpu_batch_num_actions(const sdpgpu_batch* b, int32_t instance) {
+  return b && instance >= 0 && instance < b->N ? b->As[(size_t)instance] : -1;
+}
+
+int sdpgpu_batch_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_plan* out) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  if (!out) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_plan_period: out is null");
+  if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_plan_period: period %d outside 1 .. %d", period, b->T);
+  return guarded(b, "sdpgpu_batch_plan_period", [&]() -> int {
+    std::memset(out, 0, sizeof *out);
+    int rc = layout(b);  // (host arithmetic only; names the first pmf that is missing)
+    if (rc) return rc;
+    const BatchPlan& p = b->plan[(size_t)period - 1];
+    out->r = p.R;
+    out->s = p.S;
+    out->chunk_blocks = p.chunk_blocks;
+    out->chunked = p.n_chunks > 1;
+    out->max_chunks = p.n_chunks;
+    out->min_chunks = p.min_chunks;
+    out->tasks = p.n_tasks;
+    out->lds_bytes = (int64_t)p.smem;
+    return SDPGPU_OK;
+  });
+}
+
 void sdpgpu_batch_destroy(sdpgpu_batch* b) {
   if (!b) return;
   {
@@ -522,6 +623,7 @@ void sdpgpu_batch_destroy(sdpgpu_batch* b) {
     if (b->d_policy) (void)hipFree(b->d_policy);
     if (b->d_pmf) (void)hipFree(b->d_pmf);
     if (b->d_inst) (void)hipFree(b->d_inst);
+    if (b->d_tasks) (void)hipFree(b->d_tasks);
     if (b->d_keys) (void)hipFree(b->d_keys);
     if (b->d_chunk_val) (void)hipFree(b->d_chunk_val);
     if (b->d_chunk_idx) (void)hipFree(b->d_chunk_idx);
@@ -559,8 +661,9 @@ int sdpgpu_batch_set_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, const dou
         return bfail(b, SDPGPU_ERR_ARG, "demands of instance %d, period %d: spacing %g between points %d and %d, the batch kernel needs "
                      "spacing = step (%g)", instance, t + 1, demand[j] - demand[j - 1], j - 1, j, step);
     }
-    if (std::fabs(demand[0]) > 1.0e9 || n > 3000 || (int64_t)b->A + n > 3500)
-      return bfail(b, SDPGPU_ERR_UNSUPPORTED, "instance %d, period %d: %d actions + %d demand points exceed the window kernel's 3500", instance, t + 1, b->A, n);
+    const int32_t A = b->As[(size_t)instance];
+    if (std::fabs(demand[0]) > 1.0e9 || n > 3000 || (int64_t)A + n > 3500)
+      return bfail(b, SDPGPU_ERR_UNSUPPORTED, "instance %d, period %d: %d actions + %d demand points exceed the window kernel's 3500", instance, t + 1, A, n);
     const size_t k = (size_t)instance * b->T + t;
     b->pmf_p[k].assign(prob, prob + n);
     b->d0[k] = demand[0];
@@ -651,7 +754,8 @@ int sdpgpu_batch_synchronize(sdpgpu_batch* b) {
 static int read_check(sdpgpu_batch* b, const char* who, int32_t instance, int32_t period, const void* out, int64_t n, bool is_values) {
   if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, b->N - 1);
   if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, b->T);
-  if (!out || n < 0 || n > b->nx) return bfail(b, SDPGPU_ERR_ARG, "%s: bad output (n = %lld, the grid has %d states)", who, (long long)n, b->nx);
+  const int32_t nx = b->nxs[(size_t)instance];  // the instance's own count
+  if (!out || n < 0 || n > nx) return bfail(b, SDPGPU_ERR_ARG, "%s: bad output (n = %lld, the grid has %d states)", who, (long long)n, nx);
   if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
   if (is_values && !b->d[0].store_all_values && period > 2)
     return bfail(b, SDPGPU_ERR_STATE, "%s: V_%d was overwritten (store_all_values = 0 keeps two ping-pong tables: periods 1 and 2 survive)", who, period);
@@ -822,10 +926,7 @@ sdp::SimLaunch sim_launch_params(const sdpgpu_batch* b, int32_t n_paths, uint64_
   const sdpgpu_desc& d = b->d[0];
   L.step = d.step;
   L.inv_step = 1.0 / d.step;  // exact: step is a power of two (validate)
-  L.min_inventory = d.min_inventory;
-  L.max_inventory = d.max_inventory;
   L.T = b->T;
-  L.n_states = b->nx;
   L.n_inst = b->N;
   L.n_paths = n_paths;
   L.waves_per_inst = (n_paths + 63) / 64;
@@ -857,13 +958,13 @@ int sim_run(sdpgpu_batch* b, const char* who, int32_t n_paths, const double* dem
       return bfail(b, SDPGPU_ERR_ARG, "%s: instance_stride %lld is neither 0 (one shared set) nor >= n_paths * T = %lld", who, (long long)stride,
                    (long long)n_paths * T);
   }
-  const sdpgpu_desc& d0 = b->d[0];
   std::vector<int32_t> ini((size_t)N);
   for (int i = 0; i < N; ++i) {
-    const double x = ini_x ? ini_x[i] : b->d[(size_t)i].ini_inventory;
-    if (!(x >= d0.min_inventory && x <= d0.max_inventory) || std::fmod(x, d0.step) != 0)
-      return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d: ini_x %g is not a point of the grid [%g, %g]", who, i, x, d0.min_inventory, d0.max_inventory);
-    ini[(size_t)i] = (int32_t)((x - d0.min_inventory) / d0.step);
+    const sdpgpu_desc& di = b->d[(size_t)i];  // the instance's OWN grid
+    const double x = ini_x ? ini_x[i] : di.ini_inventory;
+    if (!(x >= di.min_inventory && x <= di.max_inventory) || std::fmod(x, di.step) != 0)
+      return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d: ini_x %g is not a point of the grid [%g, %g]", who, i, x, di.min_inventory, di.max_inventory);
+    ini[(size_t)i] = (int32_t)((x - di.min_inventory) / di.step);
   }
   if (sampled) {
     int rc = sim_needs_unit_step(b, who);
@@ -881,7 +982,8 @@ int sim_run(sdpgpu_batch* b, const char* who, int32_t n_paths, const double* dem
     std::vector<sdp::SimInst> inst((size_t)N);
     for (int i = 0; i < N; ++i) {
       const sdpgpu_desc& d = b->d[(size_t)i];
-      inst[(size_t)i] = sdp::SimInst{d.holding_cost, d.penalty_cost, d.fixed_order_cost, d.unit_order_cost};
+      inst[(size_t)i] = sdp::SimInst{d.holding_cost, d.penalty_cost, d.fixed_order_cost, d.unit_order_cost, d.min_inventory,
+                                     d.max_inventory, (int64_t)policy_row(b, i, 0), b->nxs[(size_t)i], 0};
     }
     BHIP_TRY(b, hipMalloc((void**)&b->d_sim_inst, inst.size() * sizeof(sdp::SimInst)));
     BHIP_TRY(b, hipMemcpy(b->d_sim_inst, inst.data(), inst.size() * sizeof(sdp::SimInst), hipMemcpyHostToDevice));

@@ -391,14 +391,15 @@ class CashLeadtimeRecursion(_GpuRecursionBase):
 
 
 class RecursionBatch:
-    """Many sdp.inventory.Recursion objects of ONE grid shape behind one solve: the body of a parameter sweep such as
+    """Many sdp.inventory.Recursion objects behind one solve: the body of a parameter sweep such as
     capacitated.CLSPTesting.main (CLSPTesting.java:58-118), which builds a Recursion per parameter set and asks each for
     getExpectedValue(initialState) and getAction(initialState).  `functors[i]` / `pmfs[i]` describe instance i (backorder
     family, same inventory bounds, order limit, step and horizon; costs, initial inventory and demand tiles are the
-    instance's own).  The first query runs period t of ALL instances in one kernel launch per period (SdpBatch); every
+    instance's own).  With `ragged=True` the inventory bounds and the order limit are the instance's own as well, as in
+    capacitated.fitss.ThreeLevelFitsSTest.main (ThreeLevelFitsSTest.java:67-77), and states are looked up on its own grid.  The first query runs period t of ALL instances in one kernel launch per period (SdpBatch); every
     instance's answers are those of its own Recursion, bit for bit.  There is no CPU fallback."""
 
-    def __init__(self, functors, pmfs, optDirection: OptDirection = OptDirection.MIN, device: int = -1):
+    def __init__(self, functors, pmfs, optDirection: OptDirection = OptDirection.MIN, device: int = -1, ragged: bool = False):
         from .batch import SdpBatch
         self.functors = list(functors)
         self.pmfs = pmfs  # shared by reference, never copied (Recursion.java:54)
@@ -409,7 +410,7 @@ class RecursionBatch:
         self.optDirection = optDirection
         self.T = len(pmfs[0])
         descs = [f.to_desc(self.T, optDirection) for f in self.functors]
-        self._batch = SdpBatch(descs, pmfs, device=device)
+        self._batch = SdpBatch(descs, pmfs, ragged=ragged, device=device)
         self._solved = False
         self._values: Dict[tuple, np.ndarray] = {}
         self._policy: Dict[tuple, np.ndarray] = {}
@@ -444,7 +445,7 @@ class RecursionBatch:
             raise IndexError(f"period {period} outside 1..{self.T}")
         x = state.getIniInventory()
         pos = (x - f.minInventory) / f.stepSize
-        if pos != int(pos) or not 0 <= pos < self._batch.num_states:
+        if pos != int(pos) or not 0 <= pos < self._batch.num_states_of(i):
             raise ValueError(f"state {x} is not a point of the batch's grid [{f.minInventory}, {f.maxInventory}]")
         if period == 1 and x == f.iniInventory:  # what a sweep asks of every instance: one gathered copy for all of them
             if self._initial is None:

@@ -280,7 +280,8 @@ class RiskSimulation:
 class SimulationBatch:
     """`new Simulation(distributions, sampleNum, recursion).simulateSDPGivenSamplNum(initialState)` for every instance of
     a sweep at once (CLSPTesting.java:120-124): `distributions_per_instance[i]` are instance i's T demand distributions
-    (None = draw from the instance's own pmf tiles), `recursion_batch` a RecursionBatch.  Sampling (latin hypercube,
+    (None = draw from the instance's own pmf tiles), `recursion_batch` a RecursionBatch of either kind (one grid shape, or
+    ragged: every path then moves on its instance's own grid).  Sampling (latin hypercube,
     seeded) and rollout happen on the device in one launch (SdpBatch.simulate_sampled); there is no host sampling."""
 
     def __init__(self, distributions_per_instance, sampleNum: int, recursion_batch, seed: int = 12345):

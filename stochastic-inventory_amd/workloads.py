@@ -300,6 +300,61 @@ def clsp_testing_sweep(patterns=None) -> List[Workload]:
     return out
 
 
+# capacitated.fitss.ThreeLevelFitsSTest.main (ThreeLevelFitsSTest.java:34-60): the mean demands of its ten demand patterns
+# (the first six periods of each, `newLength = 6`) and its cost grid; One- and TwoLevelFitsSTest sweep the same values
+FITSS_DEMANDS = (
+    (30, 30, 30, 30, 30, 30),
+    (6.6, 9.3, 11.1, 12.9, 16.8, 21.6),
+    (45.9, 48.6, 49.8, 49.8, 48.6, 45.9),
+    (36.3, 30, 23.7, 21, 23.7, 30),
+    (47.1, 30, 12.9, 6, 12.9, 30),
+    (62.7, 27.3, 9.9, 23.7, 1, 22.8),
+    (5, 15.3, 45.6, 140.1, 80.4, 146.7),
+    (14.1, 24.3, 70.8, 118.2, 49.2, 86.1),
+    (13.2, 34.8, 79.2, 43.2, 43.8, 59.4),
+    (14.7, 56.4, 19.2, 83.7, 135.9, 67.2),
+)
+FITSS_K = (500.0, 800.0, 200.0)
+FITSS_V = (0.0, 5.0, 10.0)
+FITSS_PAI = (15.0, 10.0, 5.0)
+FITSS_CAPACITY = (2.0, 3.0, 4.0)
+
+
+def fitss_sweep(levels: int = 3, patterns=None) -> List[Workload]:
+    """The instances of capacitated.fitss.ThreeLevelFitsSTest.main in its loop order (K, v, pai, demand pattern, capacity;
+    ThreeLevelFitsSTest.java:67-71): 3 x 3 x 3 x 10 x 3 = 810 F1 problems -- x in [-300, 800], T = 6, h = 1, Poisson demands
+    through GetPmf at the 0.999 quantile -- whose ORDER LIMIT is the instance's own: maxOrderQuantity =
+    (int)(Math.round(mean of meanDemand) * capacity) (:76-77), 27 distinct values from 26 to 288.  One grid of states, 27
+    numbers of actions: a ragged batch (SdpBatch(..., ragged=True)).  `levels` names the driver (1, 2, 3: One-, Two-,
+    ThreeLevelFitsSTest); the instances are the same, the drivers differ in the level rule they fit afterwards, which is not
+    part of the sweep.  `patterns`: a subset of the demand patterns, numbered 1..10 as the result file numbers them.  Every
+    workload carries `pattern` and `capacity`."""
+    from .pmf import GetPmf, PoissonDist
+    if levels not in (1, 2, 3):
+        raise ValueError(f"levels = {levels}: the reference has One-, Two- and ThreeLevelFitsSTest")
+    pats = tuple(range(1, len(FITSS_DEMANDS) + 1)) if patterns is None else tuple(patterns)
+    tiles = {}
+    out = []
+    for K in FITSS_K:
+        for v in FITSS_V:
+            for pai in FITSS_PAI:
+                for ip in pats:
+                    mean = FITSS_DEMANDS[ip - 1]
+                    if ip not in tiles:
+                        tiles[ip] = [np.asarray(t, dtype=np.float64)
+                                     for t in GetPmf([PoissonDist(m) for m in mean], 0.999, 1).getpmf()]
+                    for cap in FITSS_CAPACITY:
+                        # Math.round is floor(x + 0.5); the product is exact (an integer times 2, 3 or 4)
+                        q = int(math.floor(sum(mean) / len(mean) + 0.5) * cap)
+                        f = BackorderFunctor(fixedOrderingCost=K, variOrderingCost=v, holdingCost=1, penaltyCost=pai,
+                                             minInventory=-300, maxInventory=800, maxOrderQuantity=q, iniInventory=0)
+                        w = Workload(f"fitss{levels}_K{K:g}_v{v:g}_pai{pai:g}_p{ip}_cap{cap:g}", f, OptDirection.MIN, tiles[ip],
+                                     "ThreeLevelFitsSTest.main instance")
+                        w.pattern, w.capacity = ip, cap
+                        out.append(w)
+    return out
+
+
 def by_name(name: str, **kw) -> Workload:
     table = {"cfg1": cfg1_sS, "cfg2": cfg2_clsp, "cfg3": cfg3_cash, "cfg3t": cfg3_tenths, "cfg4": cfg4_leadtime,
              "cfg4p": cfg4_pipeline, "target": target_grid, "f5_spl": f5_single_product_leadtime, "staff": staff_testing,

@@ -1,0 +1,236 @@
+"""ThreeLevelFitsSTest's 810 instances (workloads.fitss_sweep): the sweep as 27 batches of one shape against ONE ragged batch.
+
+One process, one stream of its own, HIP events beside a synchronised host clock.
+
+  A   27 pre-created SdpBatches, one per order limit (today's only route; each is small enough to be chunked: key rows, a
+      key reset and a finalize pass per batch); timed: 27 x solve(sync=False) + one synchronize
+  B   one SdpBatch(..., ragged=True) of all 810: solve alone
+  C   B's solve + simulate_sampled(10000) + initial(): what the driver's loop body asks of every instance
+
+A sample is as many back-to-back sweeps as fill the window, divided by their number; samples alternate A, B, C, A, B, C, ...
+after a warm-up.  Before anything is timed the two routes are compared bit for bit (initial values and actions of all 810, the
+period-1 tables of one instance per shape).
+
+    python tools/fitss_sweep_rows.py [--samples 7] [--out profiles/batch_fitss_sweep.json]
+
+Under `rocprofv3 --kernel-trace --stats -- python tools/fitss_sweep_rows.py --trace-b` only B runs (three sweeps, nothing
+written).
+
+UNIFORM BATCHES MUST NOT PAY.  `--uniform FILE` times SdpBatch.solve of CLSPTesting's 540 instances (the batch of one shape)
+and writes its samples to FILE; it uses nothing newer than SdpBatch itself, so the same file runs from a checkout of the
+parent commit.  Run it from both trees in one session, alternating, then hand the files to the main run:
+`--uniform-parent P1.json,P2.json --uniform-new N1.json,N2.json`.  The verdict in the output: the new median lies within the
+parent's own min-to-max spread, or within 1 % of its median where that spread is tighter than 1 %.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np
+import torch
+
+import stochastic_inventory_amd as sia
+from stochastic_inventory_amd import workloads
+
+
+def summary(xs):
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "samples": list(xs)}
+
+
+def timed(stream, fn, sweeps):
+    """(host ms, device ms) per sweep of `sweeps` back-to-back calls of fn."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    stream.synchronize()
+    t0 = time.perf_counter()
+    e0.record(stream)
+    for _ in range(sweeps):
+        fn()
+    e1.record(stream)
+    stream.synchronize()
+    host = (time.perf_counter() - t0) * 1e3 / sweeps
+    return host, e0.elapsed_time(e1) / sweeps
+
+
+def descs_of(ws):
+    out = [w.desc() for w in ws]
+    for d in out:
+        d.device = 0
+    return out
+
+
+def uniform(args, stream):
+    ws = workloads.clsp_testing_sweep()
+    b = sia.SdpBatch(descs_of(ws), [w.pmf for w in ws])
+    b.set_stream(stream.cuda_stream)
+    b.solve(sync=True)
+    run = lambda: b.solve(sync=False)
+    sweeps = max(1, int(np.ceil(args.window * 1e3 / timed(stream, run, 3)[0])))
+    timed(stream, run, sweeps)  # warm-up
+    S = [timed(stream, run, sweeps) for _ in range(args.samples)]
+    st = b.stats()
+    res = {"workload": f"CLSPTesting.main, {len(ws)} instances of one shape, SdpBatch.solve", "tree": ROOT,
+           "device": torch.cuda.get_device_name(0), "sweeps_per_sample": sweeps,
+           "plan": {"r": st.window_r, "s": st.window_s, "chunks": st.window_chunks, "lds_bytes": int(st.lds_bytes)},
+           "ms_per_sweep_host": summary([x[0] for x in S]), "ms_per_sweep_device": summary([x[1] for x in S])}
+    b.close()
+    with open(args.uniform, "w") as f:
+        json.dump(res, f, indent=1)
+    print("uniform", ROOT, res["ms_per_sweep_host"])
+    return 0
+
+
+def uniform_verdict(parent_files, new_files):
+    def pool(files):
+        runs = [json.load(open(p)) for p in files]
+        return runs, [x for r in runs for x in r["ms_per_sweep_host"]["samples"]]
+    pr, p = pool(parent_files)
+    nr, n = pool(new_files)
+    pm, nm = statistics.median(p), statistics.median(n)
+    spread = (max(p) - min(p)) / pm
+    ok = (min(p) <= nm <= max(p)) if spread >= 0.01 else abs(nm - pm) <= 0.01 * pm
+    return {"workload": pr[0]["workload"], "order": "parent and new processes alternating in one session",
+            "parent_ms_per_sweep_host": summary(p), "new_ms_per_sweep_host": summary(n),
+            "parent_spread_relative": spread, "new_over_parent_median": nm / pm,
+            "rule": "new median within the parent's min..max, or within 1 % of its median where that spread is below 1 %",
+            "new_median_within_rule": bool(ok), "parent_plan": pr[0]["plan"], "new_plan": nr[0]["plan"]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=7)
+    ap.add_argument("--window", type=float, default=0.3, help="least length of a timed window, seconds")
+    ap.add_argument("--paths", type=int, default=10000, help="sample paths per instance of row C (Simulation's sampleNum)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_fitss_sweep.json"))
+    ap.add_argument("--trace-b", action="store_true", help="run B three times and leave (for a kernel trace)")
+    ap.add_argument("--uniform", default="", help="time CLSPTesting's uniform batch only and write the samples to this file")
+    ap.add_argument("--uniform-parent", default="", help="comma-separated --uniform files of the parent commit")
+    ap.add_argument("--uniform-new", default="", help="comma-separated --uniform files of this tree")
+    args = ap.parse_args()
+    if args.samples < 5:
+        raise SystemExit("at least 5 samples")
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: this tool measures, it has no CPU path")
+    torch.cuda.set_device(0)
+    stream = torch.cuda.Stream()
+    sptr = stream.cuda_stream
+    if args.uniform:
+        return uniform(args, stream)
+
+    ws = workloads.fitss_sweep()
+    n = len(ws)
+    descs, pmfs = descs_of(ws), [w.pmf for w in ws]
+    ragged = sia.SdpBatch(descs, pmfs, ragged=True)
+    ragged.set_stream(sptr)
+    ragged.solve(sync=True)
+    if args.trace_b:
+        for _ in range(3):
+            ragged.solve(sync=True)
+        ragged.close()
+        return 0
+    groups = {}
+    for i, w in enumerate(ws):
+        groups.setdefault(int(w.functor.maxOrderQuantity), []).append(i)
+    shaped = []
+    for q, idx in sorted(groups.items()):
+        g = sia.SdpBatch([descs[i] for i in idx], [pmfs[i] for i in idx])
+        g.set_stream(sptr)
+        g.solve(sync=True)
+        shaped.append((q, idx, g))
+
+    # ---- the two routes compared at the size that is timed -------------------------------------------------------------
+    rst = ragged.stats()
+    ini_v, ini_k = ragged.initial()
+    identical, cells_a, launches_a, others_a, chunks_a = True, 0, 0, 0, []
+    for q, idx, g in shaped:
+        gv, gk = g.initial()
+        identical &= bool(np.array_equal(ini_v[idx], gv) and np.array_equal(ini_k[idx], gk))
+        identical &= bool(np.array_equal(ragged.values(idx[0], 1), g.values(0, 1)) and np.array_equal(ragged.policy(idx[0], 1), g.policy(0, 1)))
+        st = g.stats()
+        cells_a += int(st.cells_evaluated)
+        launches_a += st.period_launches
+        others_a += st.finalize_launches
+        chunks_a.append(st.window_chunks)
+    if not identical:
+        raise SystemExit("the ragged batch and the batches by shape DIFFER: nothing is timed")
+    assert cells_a == int(rst.cells_evaluated)
+
+    def run_a():
+        for _, _, g in shaped:
+            g.solve(sync=False)
+
+    def run_b():
+        ragged.solve(sync=False)
+
+    def run_c():
+        ragged.solve(sync=False)
+        ragged.simulate_sampled(args.paths, 12345)
+        ragged.initial()
+
+    sweeps = {k: max(1, int(np.ceil(args.window * 1e3 / timed(stream, f, 2)[0]))) for k, f in (("A", run_a), ("B", run_b), ("C", run_c))}
+    rows = {"A": [], "B": [], "C": []}
+    for k, f in (("A", run_a), ("B", run_b), ("C", run_c)):  # warm-up at the timed length
+        timed(stream, f, sweeps[k])
+    for _ in range(args.samples):
+        rows["A"].append(timed(stream, run_a, sweeps["A"]))
+        rows["B"].append(timed(stream, run_b, sweeps["B"]))
+        rows["C"].append(timed(stream, run_c, sweeps["C"]))
+    sim_ms = ragged.simulate_ms()
+
+    # per-period launch times of the ragged batch (events between the launches: a run of its own)
+    prof = sia.SdpBatch(descs, pmfs, ragged=True)
+    prof.set_stream(sptr)
+    prof.set_profiling(True)
+    prof.solve(sync=True)
+    prof.solve(sync=True)
+    period_ms = [prof.period_ms(t) for t in range(1, prof.T + 1)]
+    plans = [prof.plan(t) for t in range(1, prof.T + 1)]
+    prof.close()
+
+    host = {k: [x[0] for x in v] for k, v in rows.items()}
+    cells = int(rst.cells_evaluated)
+    res = {
+        "workload": f"ThreeLevelFitsSTest.main, {n} instances of 1101 states, {len(groups)} order limits 26 .. 288, T = 6",
+        "device": torch.cuda.get_device_name(0),
+        "instances": n,
+        "cells_per_sweep": cells,
+        "bit_identical_A_and_B": identical,
+        "A_route": {"batches": len(shaped), "period_launches": launches_a, "other_launches": others_a,
+                    "chunks_min": min(chunks_a), "chunks_max": max(chunks_a)},
+        "B_plan": {"r": rst.window_r, "s": rst.window_s, "chunks": rst.window_chunks, "lds_bytes": int(rst.lds_bytes),
+                   "period_launches": rst.period_launches, "other_launches": rst.finalize_launches,
+                   "tasks_per_period": [int(p.tasks) for p in plans], "chunk_blocks": [p.chunk_blocks for p in plans]},
+        "sweeps_per_sample": sweeps,
+        "A_ms_per_sweep_host": summary(host["A"]), "A_ms_per_sweep_device": summary([x[1] for x in rows["A"]]),
+        "B_ms_per_sweep_host": summary(host["B"]), "B_ms_per_sweep_device": summary([x[1] for x in rows["B"]]),
+        "C_ms_per_sweep_host": summary(host["C"]), "C_ms_per_sweep_device": summary([x[1] for x in rows["C"]]),
+        "C_paths_per_instance": args.paths, "C_simulate_kernels_ms": sim_ms,
+        "A_over_B": statistics.median(host["A"]) / statistics.median(host["B"]),
+        "B_cells_per_s": cells / (statistics.median(host["B"]) * 1e-3),
+        "B_period_ms": period_ms,
+        "max_B_below_min_A": max(host["B"]) < min(host["A"]),
+    }
+    if args.uniform_parent and args.uniform_new:
+        res["uniform_batch_against_parent"] = uniform_verdict(args.uniform_parent.split(","), args.uniform_new.split(","))
+    for _, _, g in shaped:
+        g.close()
+    ragged.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({k: res[k] for k in ("instances", "A_route", "B_plan", "A_over_B", "B_cells_per_s", "max_B_below_min_A")}))
+    for k in "ABC":
+        print(k, "ms/sweep (host)", res[f"{k}_ms_per_sweep_host"])
+    print("B per-period ms", period_ms)
+    if "uniform_batch_against_parent" in res:
+        print("uniform", json.dumps(res["uniform_batch_against_parent"]))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
