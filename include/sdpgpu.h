@@ -779,6 +779,55 @@ double sdpgpu_batch_simulate_ms(sdpgpu_batch* b);
 #define SDPGPU_SAMPLE_TABLE_CAP 65536
 int sdpgpu_sample_table(const sdpgpu_dist_spec* spec, int32_t* k_lo_out, double* thresholds, int32_t capacity, int32_t* n_out);
 
+/* ---- (s, S) level rules of a batch: fit from the policy tables, roll out -------------------------------------------------
+ * What the capacitated.fitss drivers do after every solve (ThreeLevelFitsSTest.java:135-145; One- and TwoLevelFitsSTest
+ * alike): `recursion.getOptTable()`, fit a one-, two- or three-level (s, S) rule to it (sdp.inventory.FitsS.getSinglesS /
+ * getTwosS / getThreesS, FitsS.java:100-291), simulate the rule (capacitated.fitss.SimulateFitsS.simulateSinglesS / TwosS /
+ * ThreesS, SimulateFitsS.java:32-130) and record (simFinalValue - finalValue) / finalValue.  Additive to ABI 6.  The exact
+ * definition of the fit is DESIGN.md 4 ("Batched (s, S) level rules").
+ *
+ * The reference's opt table holds the states its memoised recursion visits.  For a batch instance (clamped grid, demand
+ * supports spaced `step`) they are ONE interval of grid indices per period: lo_1 = hi_1 = index(ini_inventory),
+ * lo_{t+1} = clamp(lo_t - d_max,t / step), hi_{t+1} = clamp(hi_t + (A - 1) - d_0,t / step), clamped to the instance's grid.
+ * sdpgpu_batch_reachable gives it for a 1-based period: host arithmetic, needs the instance's pmfs of the periods before
+ * (SDPGPU_ERR_STATE names the first one missing), not a device. */
+int sdpgpu_batch_reachable(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* lo, int32_t* hi);
+/* FitsS on rows [period, x, Q] (opt_table: n_rows x 3, the rows of a period ascending in x as Recursion.getOptTable gives
+ * them; FitsS(maxOrderQuantity, T)): out[t * 2 * levels ...] = s_1, S_1 (, s_2, S_2 (, s_3, S_3)) of period t + 1 for levels
+ * = 1 (getSinglesS), 2 (getTwosS), 3 (getThreesS), branch for branch -- period 1 is s = x_0 + 1, S = x_0 + Q_0 of the first
+ * row; levelIndex (FitsS.java:39-59); the "last row still at the limit" corrections; the copies of the upper bands.
+ * minSquare (:69-98) is the closed form of the problem the reference gives to CPLEX: the fp64 mean of the terms x_i + Q_i
+ * (i = the first row not at the limit, and every later row up to upIndex not at the limit), clamped to [lb, 10000].  Host
+ * arithmetic only, no device; a period without rows is SDPGPU_ERR_ARG (the reference indexes an empty array there).
+ * sdpgpu_fit_level_index and sdpgpu_fit_min_square are levelIndex and minSquare on the rows of ONE period (columns x, q of
+ * n rows; out_index holds up to n entries).  Errors through sdpgpu_last_error(NULL). */
+int sdpgpu_fit_ss(int32_t levels, int32_t T, double max_order_quantity, const double* opt_table, int64_t n_rows, double* out);
+int sdpgpu_fit_level_index(double max_order_quantity, const double* q, int32_t n, int32_t* out_index, int32_t* n_out);
+int sdpgpu_fit_min_square(double max_order_quantity, double lb, int32_t up_index, const double* x, const double* q, int32_t n,
+                          double* out);
+/* The fit of EVERY instance of a solved batch on the device: one kernel reads each (instance, period)'s reachable slice of
+ * the policy arena and writes its level row, one copy brings out[n x T x 2 * levels] back -- no policy table crosses to the
+ * host.  Bit for bit sdpgpu_fit_ss on the instance's read-back rows (the same statements compiled for the device; with
+ * step 1 every min-square term is an integer and the sum exact).  Needs step == 1 (SDPGPU_ERR_UNSUPPORTED otherwise);
+ * SDPGPU_ERR_STATE before a solve, SDPGPU_ERR_ARG for levels outside 1..3. */
+int sdpgpu_batch_fit_ss(sdpgpu_batch* b, int32_t levels, double* out);
+/* Roll a level rule of every instance along demand paths (SimulateFitsS.java:32-130): per path, x = ini; period index 0
+ * orders ss[0][1] - ini, uncapped as the reference has it (:43); every later period tests the bands as written -- one level:
+ * x >= s_1 ? 0 : min(maxQ, S_1 - x); two and three levels: x < s_1, s_1 <= x < s_2 (, s_2 <= x < s_3) order
+ * min(maxQ, S_k - x), 0.0 outside every band --, then `sum += immediateValue(x, Q, d)`, `x = stateTransition(x, Q, d)` with
+ * the statements of sdpgpu_batch_simulate.  The state is a double, not a grid index: a fitted S may be fractional.
+ * ss: n x T x 2 * levels (what sdpgpu_batch_fit_ss writes; any rule the caller made) -- then the call needs the pmfs and a
+ * device, not a solve -- or NULL = fit first, in the same call, the levels staying on the device (needs a solved batch and
+ * step == 1).  n_paths, demand, instance_stride, seed, ini_x, out_mean, out_sum, the samplers and the order of the mean's
+ * sum: exactly as sdpgpu_batch_simulate / _sampled.  The same (seed, position in the batch, n_paths) therefore rolls the
+ * rule along the SAME demand paths as sdpgpu_batch_simulate_sampled rolls the table policy: common random numbers for the
+ * gap between the two, which the reference's unseeded Math.random() cannot offer.  sdpgpu_batch_simulate_ms then covers
+ * the fit (when ss is NULL), the rollout and the means. */
+int sdpgpu_batch_simulate_ss(sdpgpu_batch* b, int32_t levels, const double* ss, int32_t n_paths, const double* demand,
+                             int64_t instance_stride, const double* ini_x, double* out_mean, double* out_sum);
+int sdpgpu_batch_simulate_ss_sampled(sdpgpu_batch* b, int32_t levels, const double* ss, int32_t n_paths, uint64_t seed,
+                                     const double* ini_x, double* out_mean, double* out_sum);
+
 /* ---- sampled simulation on a handle: demand paths drawn ON the device, rolled and reduced there ------------------------
  * What every driver does after its solve -- `new Simulation(distributions, sampleNum, recursion)
  * .simulateSDPGivenSamplNum(initialState)` (Simulation.java:53-74; CashSimulation.java:85-118 for the cash classes;

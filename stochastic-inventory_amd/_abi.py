@@ -323,6 +323,13 @@ EXPORTS = {
     "sdpgpu_batch_sample_demands": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint64, _DP, _DP]),
     "sdpgpu_batch_simulate_ms": (C.c_double, [_P]),
     "sdpgpu_sample_table": (C.c_int, [C.POINTER(SdpgpuDistSpec), _IP, _DP, C.c_int32, _IP]),
+    "sdpgpu_batch_reachable": (C.c_int, [_P, C.c_int32, C.c_int32, _IP, _IP]),
+    "sdpgpu_fit_ss": (C.c_int, [C.c_int32, C.c_int32, C.c_double, _DP, C.c_int64, _DP]),
+    "sdpgpu_fit_level_index": (C.c_int, [C.c_double, _DP, C.c_int32, _IP, _IP]),
+    "sdpgpu_fit_min_square": (C.c_int, [C.c_double, C.c_double, C.c_int32, _DP, _DP, C.c_int32, _DP]),
+    "sdpgpu_batch_fit_ss": (C.c_int, [_P, C.c_int32, _DP]),
+    "sdpgpu_batch_simulate_ss": (C.c_int, [_P, C.c_int32, _DP, C.c_int32, _DP, C.c_int64, _DP, _DP, _DP]),
+    "sdpgpu_batch_simulate_ss_sampled": (C.c_int, [_P, C.c_int32, _DP, C.c_int32, C.c_uint64, _DP, _DP, _DP]),
     "sdpgpu_set_sampler": (C.c_int, [_P, C.c_int32, C.POINTER(SdpgpuDistSpec)]),
     "sdpgpu_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_double,
                                           C.POINTER(SdpgpuSimResult), _DP, C.POINTER(C.c_uint8)]),

@@ -194,3 +194,54 @@ class SdpBatch:
 
     def simulate_ms(self) -> float:
         return float(self._lib.sdpgpu_batch_simulate_ms(self._b))
+
+    # ---- (s, S) level rules (sdpgpu_batch_reachable / _fit_ss / _simulate_ss*; FitsS.java, SimulateFitsS.java) ----
+    def reachable(self, i: int, period: int):
+        """(lo, hi): the grid indices of the states of `period` (1-based) the reference's memoised recursion visits from
+        instance i's initial state -- one interval.  Host arithmetic, no device."""
+        lo, hi = C.c_int32(), C.c_int32()
+        self._check(self._lib.sdpgpu_batch_reachable(self._b, i, period, C.byref(lo), C.byref(hi)))
+        return int(lo.value), int(hi.value)
+
+    def fit_ss(self, levels: int) -> np.ndarray:
+        """The one-, two- or three-level (s, S) rule of every instance, fitted ON the device from the solved policy tables
+        (FitsS.getSinglesS / getTwosS / getThreesS): [n, T, 2 * levels]."""
+        out = np.empty((self.n, self.T, 2 * max(int(levels), 0)), dtype=np.float64)
+        self._check(self._lib.sdpgpu_batch_fit_ss(self._b, int(levels), _dp(out) if out.size else None))
+        return out
+
+    def _rule(self, levels, ss):
+        if ss is None:
+            return None, None
+        arr = np.ascontiguousarray(ss, dtype=np.float64)
+        if arr.shape != (self.n, self.T, 2 * int(levels)):
+            raise ValueError(f"ss of shape {arr.shape}: expected [{self.n}, {self.T}, {2 * int(levels)}] for {levels} level(s)")
+        return arr, _dp(arr)
+
+    def simulate_ss(self, levels: int, demands, ss=None, ini_x=None, want_sums: bool = False):
+        """Roll a level rule of every instance along given demand paths (SimulateFitsS.simulateSinglesS / TwosS / ThreesS);
+        `demands` as for simulate(); ss: [n, T, 2 * levels], or None = fit on the device first (needs a solve)."""
+        dem = np.ascontiguousarray(demands, dtype=np.float64)
+        if dem.ndim == 2 and dem.shape[1] == self.T:
+            n_paths, stride = dem.shape[0], 0
+        elif dem.ndim == 3 and dem.shape[0] == self.n and dem.shape[2] == self.T:
+            n_paths, stride = dem.shape[1], dem.shape[1] * self.T
+        else:
+            raise ValueError(f"demands of shape {dem.shape}: expected [n_paths, {self.T}] or [{self.n}, n_paths, {self.T}]")
+        rule, rule_p = self._rule(levels, ss)
+        ini, ini_p = self._ini(ini_x)
+        mean = np.empty(self.n, dtype=np.float64)
+        sums = np.empty((self.n, n_paths), dtype=np.float64) if want_sums else None
+        self._check(self._lib.sdpgpu_batch_simulate_ss(self._b, int(levels), rule_p, n_paths, _dp(dem), stride, ini_p, _dp(mean),
+                                                       _dp(sums) if want_sums else None))
+        return self._sim_result(mean, sums, want_sums)
+
+    def simulate_ss_sampled(self, levels: int, n_paths: int, seed: int, ss=None, ini_x=None, want_sums: bool = False):
+        """Draw the demand paths of simulate_sampled(n_paths, seed) -- the same ones -- and roll a level rule along them."""
+        rule, rule_p = self._rule(levels, ss)
+        ini, ini_p = self._ini(ini_x)
+        mean = np.empty(self.n, dtype=np.float64)
+        sums = np.empty((self.n, int(n_paths)), dtype=np.float64) if want_sums and n_paths > 0 else None
+        self._check(self._lib.sdpgpu_batch_simulate_ss_sampled(self._b, int(levels), rule_p, int(n_paths), C.c_uint64(seed & (2**64 - 1)),
+                                                               ini_p, _dp(mean), _dp(sums) if sums is not None else None))
+        return self._sim_result(mean, sums, want_sums)

@@ -1,4 +1,4 @@
-// sdpgpu_batch.hip -- a BATCH of backorder-family (F1) instances (include/sdpgpu.h, sdpgpu_batch_*): the parameter sweeps of
+// sdpgpu_batch.hip -- a BATCH of backorder-family (F1) instances (include/sdpgpu.h, sdpgpu_batch_*, sdpgpu_fit_*): the parameter sweeps of
 // the reference's *Testing mains -- of one grid shape (capacitated.CLSPTesting.main: 540 instances of one grid;
 // sdpgpu_batch_create) or with inventory bounds and an order limit of their own (capacitated.fitss.ThreeLevelFitsSTest.main:
 // 810 instances with 27 order limits; sdpgpu_batch_create_ragged).  Period t of ALL instances runs in one launch of
@@ -8,6 +8,7 @@
 #include "sdpgpu_internal.hpp"
 #include "sdp_batch.hpp"
 #include "sdp_batch_sim.hpp"
+#include "sdp_fitss.hpp"
 
 namespace sdpgpu_detail {
 int validate(const sdpgpu_desc& d);                 // sdpgpu.hip
@@ -75,6 +76,10 @@ struct sdpgpu_batch {
   size_t sim_scratch_bytes = 0;
   hipEvent_t sim_ev0 = nullptr, sim_ev1 = nullptr;
   bool sim_timed = false;
+  // ---- (s, S) level rules (sdp_fitss.hpp) ----
+  sdp::FitPair* d_fit_pairs = nullptr;  // [i * T + t]: the reachable slice of every (instance, period)
+  double* d_fit = nullptr;              // the last device fit, N x T x 2*levels (sized for three levels)
+  sdp::SsInst* d_ss_inst = nullptr;
   std::string err;
 };
 
@@ -634,6 +639,9 @@ void sdpgpu_batch_destroy(sdpgpu_batch* b) {
     if (b->d_thr) (void)hipFree(b->d_thr);
     if (b->d_sim_inst) (void)hipFree(b->d_sim_inst);
     if (b->d_sim_scratch) (void)hipFree(b->d_sim_scratch);
+    if (b->d_fit_pairs) (void)hipFree(b->d_fit_pairs);
+    if (b->d_fit) (void)hipFree(b->d_fit);
+    if (b->d_ss_inst) (void)hipFree(b->d_ss_inst);
     if (b->sim_ev0) (void)hipEventDestroy(b->sim_ev0);
     if (b->sim_ev1) (void)hipEventDestroy(b->sim_ev1);
     if (b->stream && b->own_stream) (void)hipStreamDestroy(b->stream);
@@ -946,8 +954,10 @@ int sim_needs_unit_step(sdpgpu_batch* b, const char* who) {
   return SDPGPU_OK;
 }
 
-int sim_run(sdpgpu_batch* b, const char* who, int32_t n_paths, const double* demand, int64_t stride, bool sampled, uint64_t seed,
-            const double* ini_x, double* out_mean, double* out_sum) {
+// What every rollout of a batch takes -- of the table policy and of a level rule alike: the outputs, the path count, the
+// explicit demands, the start states (ini[i]: the inventory instance i starts from) and, when sampled, the unit step.
+int sim_check_args(sdpgpu_batch* b, const char* who, int32_t n_paths, const double* demand, int64_t stride, bool sampled, const double* ini_x,
+                   const double* out_mean, std::vector<double>* ini) {
   const int N = b->N, T = b->T;
   if (!out_mean) return bfail(b, SDPGPU_ERR_ARG, "%s: out_mean is null", who);
   if (n_paths <= 0) return bfail(b, SDPGPU_ERR_ARG, "%s: n_paths = %d (1 .. %d)", who, n_paths, kSimMaxPaths);
@@ -958,18 +968,25 @@ int sim_run(sdpgpu_batch* b, const char* who, int32_t n_paths, const double* dem
       return bfail(b, SDPGPU_ERR_ARG, "%s: instance_stride %lld is neither 0 (one shared set) nor >= n_paths * T = %lld", who, (long long)stride,
                    (long long)n_paths * T);
   }
-  std::vector<int32_t> ini((size_t)N);
+  ini->assign((size_t)N, 0.0);
   for (int i = 0; i < N; ++i) {
     const sdpgpu_desc& di = b->d[(size_t)i];  // the instance's OWN grid
     const double x = ini_x ? ini_x[i] : di.ini_inventory;
     if (!(x >= di.min_inventory && x <= di.max_inventory) || std::fmod(x, di.step) != 0)
       return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d: ini_x %g is not a point of the grid [%g, %g]", who, i, x, di.min_inventory, di.max_inventory);
-    ini[(size_t)i] = (int32_t)((x - di.min_inventory) / di.step);
+    (*ini)[(size_t)i] = x;
   }
-  if (sampled) {
-    int rc = sim_needs_unit_step(b, who);
-    if (rc) return rc;
-  }
+  return sampled ? sim_needs_unit_step(b, who) : SDPGPU_OK;
+}
+
+int sim_run(sdpgpu_batch* b, const char* who, int32_t n_paths, const double* demand, int64_t stride, bool sampled, uint64_t seed,
+            const double* ini_x, double* out_mean, double* out_sum) {
+  const int N = b->N, T = b->T;
+  std::vector<double> ini_inv;
+  int rc0 = sim_check_args(b, who, n_paths, demand, stride, sampled, ini_x, out_mean, &ini_inv);
+  if (rc0) return rc0;
+  std::vector<int32_t> ini((size_t)N);
+  for (int i = 0; i < N; ++i) ini[(size_t)i] = (int32_t)((ini_inv[(size_t)i] - b->d[(size_t)i].min_inventory) / b->d[(size_t)i].step);
   if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
   const int64_t wpi = (n_paths + 63) / 64;
   const int64_t waves = (int64_t)N * wpi;
@@ -1130,6 +1147,281 @@ double sdpgpu_batch_simulate_ms(sdpgpu_batch* b) {
   float ms = 0;
   if (hipEventElapsedTime(&ms, b->sim_ev0, b->sim_ev1) != hipSuccess) return -1.0;
   return ms;
+}
+
+}  // extern "C"
+
+// =================================================================================================
+// (s, S) level rules: fit from the policy tables, roll out (sdp_fitss.hpp)
+// =================================================================================================
+namespace {
+
+// rows [period, x, Q] of one period of an opt table, in table order
+struct FitTableRows {
+  const double* tab;
+  const int64_t* idx;
+  double x(int j) const { return tab[3 * idx[j] + 1]; }
+  double q(int j) const { return tab[3 * idx[j] + 2]; }
+};
+
+// two parallel columns (sdpgpu_fit_level_index, sdpgpu_fit_min_square)
+struct FitColumnRows {
+  const double* xs;
+  const double* qs;
+  double x(int j) const { return xs[j]; }
+  double q(int j) const { return qs[j]; }
+};
+
+template <int LEVELS>
+int fit_table(int32_t T, double maxq, const double* tab, int64_t n_rows, double* out) {
+  sdp::fit_first_period<LEVELS>(tab[1], tab[2], out);  // (optimalTable[0], whatever its period: FitsS.java:102-103)
+  std::vector<int64_t> idx;
+  for (int32_t t = 1; t < T; ++t) {
+    idx.clear();
+    for (int64_t k = 0; k < n_rows; ++k)
+      if (tab[3 * k] == (double)(t + 1)) idx.push_back(k);
+    if (idx.empty() || idx.size() > (size_t)INT32_MAX)
+      return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_ss: the table has %zu rows of period %d (the reference indexes an empty array there)", idx.size(), t + 1);
+    sdp::fit_period<LEVELS>(FitTableRows{tab, idx.data()}, (int)idx.size(), maxq, out + (size_t)t * 2 * LEVELS);
+  }
+  return SDPGPU_OK;
+}
+
+// lo / hi of the reachable interval of (instance, period); needs the instance's pmfs of the periods before
+int reachable_interval(sdpgpu_batch* b, const char* who, int32_t instance, int32_t period, int32_t* lo_out, int32_t* hi_out) {
+  const sdpgpu_desc& d = b->d[(size_t)instance];
+  const int64_t nx = b->nxs[(size_t)instance], A = b->As[(size_t)instance];
+  int64_t lo = (int64_t)((d.ini_inventory - d.min_inventory) / d.step), hi = lo;
+  auto clampidx = [&](int64_t v) { return v < 0 ? (int64_t)0 : (v > nx - 1 ? nx - 1 : v); };
+  for (int32_t t = 0; t + 1 < period; ++t) {
+    const size_t k = (size_t)instance * b->T + t;
+    if (!b->pmf_set[k]) return bfail(b, SDPGPU_ERR_STATE, "%s: pmf of instance %d, period %d not set", who, instance, t + 1);
+    const int64_t d0 = (int64_t)(b->d0[k] / d.step), D = (int64_t)b->pmf_p[k].size();
+    lo = clampidx(lo - (d0 + D - 1));
+    hi = clampidx(hi + (A - 1) - d0);
+  }
+  *lo_out = (int32_t)lo;
+  *hi_out = (int32_t)hi;
+  return SDPGPU_OK;
+}
+
+int fit_needs_unit_step(sdpgpu_batch* b, const char* who) {
+  if (b->d[0].step != 1.0)
+    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: step %g -- the fit's `s = x + 1` (FitsS.java:102) and the exact min-square sum need step == 1", who,
+                 b->d[0].step);
+  return SDPGPU_OK;
+}
+
+// the (instance, period) slices on the device, once
+int fit_upload_pairs(sdpgpu_batch* b, const char* who) {
+  if (b->d_fit_pairs) return SDPGPU_OK;
+  const int N = b->N, T = b->T;
+  std::vector<sdp::FitPair> pairs((size_t)N * T);
+  for (int i = 0; i < N; ++i)
+    for (int t = 0; t < T; ++t) {
+      int32_t lo = 0, hi = 0;
+      int rc = reachable_interval(b, who, i, t + 1, &lo, &hi);
+      if (rc) return rc;
+      pairs[(size_t)i * T + t] = sdp::FitPair{(int64_t)policy_row(b, i, t), b->d[(size_t)i].min_inventory, b->d[(size_t)i].max_order_quantity, lo, hi - lo + 1};
+    }
+  BHIP_TRY(b, hipMalloc((void**)&b->d_fit_pairs, pairs.size() * sizeof(sdp::FitPair)));
+  BHIP_TRY(b, hipMemcpy(b->d_fit_pairs, pairs.data(), pairs.size() * sizeof(sdp::FitPair), hipMemcpyHostToDevice));
+  return SDPGPU_OK;
+}
+
+// launch the fit of the whole batch into b->d_fit (n x T x 2*levels doubles, kept on the device)
+int fit_launch(sdpgpu_batch* b, const char* who, int32_t levels) {
+  int rc = fit_upload_pairs(b, who);
+  if (rc) return rc;
+  const int n_pairs = b->N * b->T;
+  if (!b->d_fit) BHIP_TRY(b, hipMalloc((void**)&b->d_fit, (size_t)n_pairs * 6 * sizeof(double)));  // (room for three levels)
+  const dim3 grid((unsigned)((n_pairs + 255) / 256));
+  const double step = b->d[0].step;
+  if (levels == 1)
+    hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<1>), grid, dim3(256), 0, b->stream, b->d_fit_pairs, n_pairs, b->T, step, b->d_policy, b->d_fit);
+  else if (levels == 2)
+    hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<2>), grid, dim3(256), 0, b->stream, b->d_fit_pairs, n_pairs, b->T, step, b->d_policy, b->d_fit);
+  else
+    hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<3>), grid, dim3(256), 0, b->stream, b->d_fit_pairs, n_pairs, b->T, step, b->d_policy, b->d_fit);
+  BHIP_TRY(b, hipGetLastError());
+  return SDPGPU_OK;
+}
+
+template <int LEVELS>
+void ss_sim_launch(sdpgpu_batch* b, bool sampled, dim3 grid, const sdp::SimLaunch& L, const double* d_ini, const double* d_ss, const double* d_dem,
+                   double* d_part, double* d_sum) {
+  if (sampled)
+    hipLaunchKernelGGL((sdp::batch_ss_sim_kernel<LEVELS, true>), grid, dim3(256), 0, b->stream, L, b->d_ss_inst, d_ini, d_ss, nullptr, b->d_samp,
+                       b->d_thr, d_part, d_sum);
+  else
+    hipLaunchKernelGGL((sdp::batch_ss_sim_kernel<LEVELS, false>), grid, dim3(256), 0, b->stream, L, b->d_ss_inst, d_ini, d_ss, d_dem, nullptr,
+                       nullptr, d_part, d_sum);
+}
+
+int ss_sim_run(sdpgpu_batch* b, const char* who, int32_t levels, const double* ss, int32_t n_paths, const double* demand, int64_t stride,
+               bool sampled, uint64_t seed, const double* ini_x, double* out_mean, double* out_sum) {
+  const int N = b->N, T = b->T;
+  if (levels < 1 || levels > 3) return bfail(b, SDPGPU_ERR_ARG, "%s: levels = %d (1, 2 or 3: simulateSinglesS, simulateTwosS, simulateThreesS)", who, levels);
+  std::vector<double> ini;
+  int rc = sim_check_args(b, who, n_paths, demand, stride, sampled, ini_x, out_mean, &ini);
+  if (rc) return rc;
+  if (!ss) {  // fit first, in this call
+    if ((rc = fit_needs_unit_step(b, who))) return rc;
+    if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s: ss = NULL fits the rule from the policy tables: before sdpgpu_batch_solve", who);
+  }
+  rc = layout(b);  // (every pmf set)
+  if (rc) return rc;
+  const int64_t wpi = (n_paths + 63) / 64;
+  const int64_t waves = (int64_t)N * wpi;
+  if (!grid_ok((waves + 3) / 4) || (double)N * n_paths > 2.0e9)
+    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: %d instances x %d paths are too many for one launch", who, N, n_paths);
+
+  DeviceScope dev;
+  BHIP_TRY(b, dev.enter(b->device));
+  rc = allocate(b);
+  if (rc) return rc;
+  if (!b->d_ss_inst) {
+    std::vector<sdp::SsInst> inst((size_t)N);
+    for (int i = 0; i < N; ++i) {
+      const sdpgpu_desc& d = b->d[(size_t)i];
+      inst[(size_t)i] = sdp::SsInst{d.holding_cost, d.penalty_cost, d.fixed_order_cost, d.unit_order_cost, d.min_inventory, d.max_inventory,
+                                    d.max_order_quantity};
+    }
+    BHIP_TRY(b, hipMalloc((void**)&b->d_ss_inst, inst.size() * sizeof(sdp::SsInst)));
+    BHIP_TRY(b, hipMemcpy(b->d_ss_inst, inst.data(), inst.size() * sizeof(sdp::SsInst), hipMemcpyHostToDevice));
+  }
+  if (!b->sim_ev0) {
+    BHIP_TRY(b, hipEventCreate(&b->sim_ev0));
+    BHIP_TRY(b, hipEventCreate(&b->sim_ev1));
+  }
+  if (sampled && (rc = sim_upload_samplers(b))) return rc;
+  // scratch: [ini N] [partials] [means] [sums] [rule] [demands]
+  const size_t ss_elems = ss ? (size_t)N * T * 2 * levels : 0;
+  const size_t o_ini = 0, o_part = (size_t)N * 8, o_mean = o_part + (size_t)waves * 8, o_sum = o_mean + (size_t)N * 8;
+  const size_t sum_bytes = out_sum ? (size_t)N * n_paths * 8 : 0;
+  const size_t o_ss = o_sum + sum_bytes, o_dem = o_ss + ss_elems * 8;
+  const size_t dem_elems = sampled ? 0 : (stride == 0 ? (size_t)n_paths * T : (size_t)(N - 1) * (size_t)stride + (size_t)n_paths * T);
+  rc = sim_scratch(b, o_dem + dem_elems * 8);
+  if (rc) return rc;
+  char* base = b->d_sim_scratch;
+  double* d_ini = reinterpret_cast<double*>(base + o_ini);
+  double* d_part = reinterpret_cast<double*>(base + o_part);
+  double* d_mean = reinterpret_cast<double*>(base + o_mean);
+  double* d_sum = out_sum ? reinterpret_cast<double*>(base + o_sum) : nullptr;
+  double* d_rule = reinterpret_cast<double*>(base + o_ss);
+  double* d_dem = sampled ? nullptr : reinterpret_cast<double*>(base + o_dem);
+  BHIP_TRY(b, hipMemcpyAsync(d_ini, ini.data(), (size_t)N * 8, hipMemcpyHostToDevice, b->stream));
+  if (ss) BHIP_TRY(b, hipMemcpyAsync(d_rule, ss, ss_elems * 8, hipMemcpyHostToDevice, b->stream));
+  if (!sampled) BHIP_TRY(b, hipMemcpyAsync(d_dem, demand, dem_elems * 8, hipMemcpyHostToDevice, b->stream));
+  const sdp::SimLaunch L = sim_launch_params(b, n_paths, seed, stride);
+  const dim3 grid((unsigned)((waves + 3) / 4));
+  BHIP_TRY(b, hipEventRecord(b->sim_ev0, b->stream));
+  if (!ss) {
+    rc = fit_launch(b, who, levels);
+    if (rc) return rc;
+    d_rule = b->d_fit;
+  }
+  if (levels == 1)
+    ss_sim_launch<1>(b, sampled, grid, L, d_ini, d_rule, d_dem, d_part, d_sum);
+  else if (levels == 2)
+    ss_sim_launch<2>(b, sampled, grid, L, d_ini, d_rule, d_dem, d_part, d_sum);
+  else
+    ss_sim_launch<3>(b, sampled, grid, L, d_ini, d_rule, d_dem, d_part, d_sum);
+  BHIP_TRY(b, hipGetLastError());
+  hipLaunchKernelGGL(sdp::batch_sim_mean_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, d_part, N, (int)wpi, n_paths, d_mean);
+  BHIP_TRY(b, hipGetLastError());
+  BHIP_TRY(b, hipEventRecord(b->sim_ev1, b->stream));
+  b->sim_timed = true;
+  BHIP_TRY(b, hipMemcpyAsync(out_mean, d_mean, (size_t)N * 8, hipMemcpyDeviceToHost, b->stream));
+  if (out_sum) BHIP_TRY(b, hipMemcpyAsync(out_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost, b->stream));
+  BHIP_TRY(b, hipStreamSynchronize(b->stream));
+  return SDPGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdpgpu_batch_reachable(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* lo, int32_t* hi) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  const char* who = "sdpgpu_batch_reachable";
+  if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, b->N - 1);
+  if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, b->T);
+  if (!lo || !hi) return bfail(b, SDPGPU_ERR_ARG, "%s: null output (lo, hi)", who);
+  return reachable_interval(b, who, instance, period, lo, hi);
+}
+
+int sdpgpu_fit_ss(int32_t levels, int32_t T, double max_order_quantity, const double* opt_table, int64_t n_rows, double* out) {
+  g_create_error.clear();
+  return guarded(nullptr, "sdpgpu_fit_ss", [&]() -> int {
+    if (levels < 1 || levels > 3) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_ss: levels = %d (1, 2 or 3: getSinglesS, getTwosS, getThreesS)", levels);
+    if (T < 1) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_ss: T = %d", T);
+    if (!opt_table || !out) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_ss: null argument (opt_table, out)");
+    if (n_rows < 1) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_ss: n_rows = %lld (the table holds at least the initial state's row)", (long long)n_rows);
+    if (levels == 1) return fit_table<1>(T, max_order_quantity, opt_table, n_rows, out);
+    if (levels == 2) return fit_table<2>(T, max_order_quantity, opt_table, n_rows, out);
+    return fit_table<3>(T, max_order_quantity, opt_table, n_rows, out);
+  });
+}
+
+int sdpgpu_fit_level_index(double max_order_quantity, const double* q, int32_t n, int32_t* out_index, int32_t* n_out) {
+  g_create_error.clear();
+  if (!q || !out_index || !n_out || n < 0) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_level_index: bad argument (q, out_index, n_out, n = %d)", n);
+  struct {
+    int32_t* out;
+    int32_t count;
+    void add(int j) { out[count++] = j; }
+  } sink{out_index, 0};
+  sdp::fit_level_walk(FitColumnRows{q, q}, n, max_order_quantity, sink);
+  *n_out = sink.count;
+  return SDPGPU_OK;
+}
+
+int sdpgpu_fit_min_square(double max_order_quantity, double lb, int32_t up_index, const double* x, const double* q, int32_t n, double* out) {
+  g_create_error.clear();
+  if (!x || !q || !out || n < 1) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_min_square: bad argument (x, q, out, n = %d)", n);
+  if (up_index < 0 || up_index >= n) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_min_square: up_index %d outside 0 .. %d", up_index, n - 1);
+  *out = sdp::fit_min_square(FitColumnRows{x, q}, n, max_order_quantity, lb, up_index);
+  return SDPGPU_OK;
+}
+
+int sdpgpu_batch_fit_ss(sdpgpu_batch* b, int32_t levels, double* out) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_fit_ss", [&]() -> int {
+    const char* who = "sdpgpu_batch_fit_ss";
+    if (levels < 1 || levels > 3) return bfail(b, SDPGPU_ERR_ARG, "%s: levels = %d (1, 2 or 3: getSinglesS, getTwosS, getThreesS)", who, levels);
+    if (!out) return bfail(b, SDPGPU_ERR_ARG, "%s: out is null", who);
+    int rc = fit_needs_unit_step(b, who);
+    if (rc) return rc;
+    if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+    DeviceScope dev;
+    BHIP_TRY(b, dev.enter(b->device));
+    rc = fit_launch(b, who, levels);
+    if (rc) return rc;
+    BHIP_TRY(b, hipMemcpyAsync(out, b->d_fit, (size_t)b->N * b->T * 2 * levels * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    return SDPGPU_OK;
+  });
+}
+
+int sdpgpu_batch_simulate_ss(sdpgpu_batch* b, int32_t levels, const double* ss, int32_t n_paths, const double* demand, int64_t instance_stride,
+                             const double* ini_x, double* out_mean, double* out_sum) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_simulate_ss", [&]() -> int {
+    return ss_sim_run(b, "sdpgpu_batch_simulate_ss", levels, ss, n_paths, demand, instance_stride, false, 0, ini_x, out_mean, out_sum);
+  });
+}
+
+int sdpgpu_batch_simulate_ss_sampled(sdpgpu_batch* b, int32_t levels, const double* ss, int32_t n_paths, uint64_t seed, const double* ini_x,
+                                     double* out_mean, double* out_sum) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_simulate_ss_sampled", [&]() -> int {
+    return ss_sim_run(b, "sdpgpu_batch_simulate_ss_sampled", levels, ss, n_paths, nullptr, 0, true, seed, ini_x, out_mean, out_sum);
+  });
 }
 
 }  // extern "C"

@@ -461,3 +461,21 @@ class RecursionBatch:
 
     def getAction(self, i: int, state) -> float:
         return self._lookup(i, state)[1] * self.functors[i].stepSize
+
+    def getOptTable(self, i: int) -> np.ndarray:
+        """Instance i's rows [period, inventory, quantity] in the comparator's order, reachable states only -- what
+        Recursion.getOptTable gives for a handle of the instance (Recursion.java:177-186).  The reachable states of a batch
+        instance are one interval of grid indices per period (SdpBatch.reachable)."""
+        self._solve()
+        f = self.functors[i]
+        rows = []
+        for period in range(1, self.T + 1):
+            lo, hi = self._batch.reachable(i, period)
+            if (i, period) not in self._policy:
+                self._values[(i, period)] = self._batch.values(i, period)
+                self._policy[(i, period)] = self._batch.policy(i, period)
+            idx = np.arange(lo, hi + 1)
+            x = f.minInventory + idx.astype(np.float64) * f.stepSize
+            q = self._policy[(i, period)][idx].astype(np.float64) * f.stepSize
+            rows.append(np.stack([np.full(len(idx), float(period)), x, q], axis=1))
+        return np.concatenate(rows, axis=0)

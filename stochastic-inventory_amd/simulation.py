@@ -314,3 +314,88 @@ class SimulationBatch:
             self.last_values = out[1]
             return out[0]
         return out
+
+    def _simulate_rule(self, levels: int, iniStates, optsS, want_sums: bool):
+        if optsS is None:
+            self.recursion._solve()  # the rule is fitted on the device from the solved tables
+        ini = None if iniStates is None else [s.getIniInventory() for s in iniStates]
+        out = self.recursion.batch.simulate_ss_sampled(levels, self.sampleNum, self.seed, ss=optsS, ini_x=ini, want_sums=want_sums)
+        if want_sums:
+            self.last_values = out[1]
+            return out[0]
+        return out
+
+    def simulateSinglesS(self, iniStates=None, optsS=None, want_sums: bool = False) -> np.ndarray:
+        """SimulateFitsS.simulateSinglesS (SimulateFitsS.java:32-54) for every instance: the n means of the one-level rule
+        optsS [n, T, 2] (None = FitsS.getSinglesS of every instance, fitted on the device), along the SAME demand paths as
+        simulateSDPGivenSamplNum (same seed: common random numbers)."""
+        return self._simulate_rule(1, iniStates, optsS, want_sums)
+
+    def simulateTwosS(self, iniStates=None, optsS=None, want_sums: bool = False) -> np.ndarray:
+        """SimulateFitsS.simulateTwosS (SimulateFitsS.java:63-91): optsS [n, T, 4] or None = getTwosS on the device."""
+        return self._simulate_rule(2, iniStates, optsS, want_sums)
+
+    def simulateThreesS(self, iniStates=None, optsS=None, want_sums: bool = False) -> np.ndarray:
+        """SimulateFitsS.simulateThreesS (SimulateFitsS.java:100-130): optsS [n, T, 6] or None = getThreesS on the device."""
+        return self._simulate_rule(3, iniStates, optsS, want_sums)
+
+
+class SimulateFitsS:
+    """capacitated.fitss.SimulateFitsS(distributions, sampleNum, recursion) for ONE backorder-family Recursion: the three
+    reference methods, signature (iniState, optsS, maxOrderQuantity).  Internally a batch of one built from the recursion's
+    functor and pmf; the rule is explicit, so nothing is solved a second time.  distributions: T demand distributions, or
+    None / None entries = the recursion's own pmf tiles.  Sampling is the seeded latin hypercube of the device
+    (SdpBatch.simulate_ss_sampled); `last_values` holds the path sums of the last call."""
+
+    def __init__(self, distributions: Sequence, sampleNum: int, recursion, seed: int = 12345):
+        from .functors import BackorderFunctor
+        if not isinstance(recursion.functor, BackorderFunctor):
+            raise TypeError("SimulateFitsS rolls the (s, S) rules of the backorder family (a Recursion over a BackorderFunctor)")
+        self.distributions = None if distributions is None else list(distributions)
+        if self.distributions is not None and len(self.distributions) != recursion.T:
+            raise ValueError(f"{len(self.distributions)} distributions, the horizon is {recursion.T}")
+        self.sampleNum = int(sampleNum)
+        self.recursion = recursion
+        self.seed = int(seed)
+        self.last_values = None
+        self._batch, self._batch_maxq = None, None
+
+    def _one(self, maxOrderQuantity):
+        """The batch of one; rebuilt when the caller's maxOrderQuantity is not the functor's (the rule's cap is an argument
+        in the reference, SimulateFitsS.java:32)."""
+        from .batch import SdpBatch
+        if self._batch is None or self._batch_maxq != float(maxOrderQuantity):
+            if self._batch is not None:
+                self._batch.close()
+            d = self.recursion.functor.to_desc(self.recursion.T, self.recursion.optDirection)
+            d.max_order_quantity = float(maxOrderQuantity)
+            self._batch = SdpBatch([d], [self.recursion.pmf], ragged=True, device=int(self.recursion.engine.desc.device))
+            self._batch_maxq = float(maxOrderQuantity)
+            if self.distributions is not None:
+                for t, dist in enumerate(self.distributions):
+                    if dist is not None:
+                        self._batch.set_sampler(0, t, dist)
+        return self._batch
+
+    def _simulate(self, levels: int, iniState, optsS, maxOrderQuantity) -> float:
+        rule = np.ascontiguousarray(optsS, dtype=np.float64)
+        if rule.shape != (self.recursion.T, 2 * levels):
+            raise ValueError(f"optsS of shape {rule.shape}: expected [{self.recursion.T}, {2 * levels}]")
+        mean, sums = self._one(maxOrderQuantity).simulate_ss_sampled(levels, self.sampleNum, self.seed, ss=rule[None],
+                                                                      ini_x=[iniState.getIniInventory()], want_sums=True)
+        self.last_values = sums[0]
+        return float(mean[0])
+
+    def simulateSinglesS(self, iniState, optsS, maxOrderQuantity) -> float:
+        return self._simulate(1, iniState, optsS, maxOrderQuantity)
+
+    def simulateTwosS(self, iniState, optsS, maxOrderQuantity) -> float:
+        return self._simulate(2, iniState, optsS, maxOrderQuantity)
+
+    def simulateThreesS(self, iniState, optsS, maxOrderQuantity) -> float:
+        return self._simulate(3, iniState, optsS, maxOrderQuantity)
+
+    def close(self):
+        if self._batch is not None:
+            self._batch.close()
+            self._batch = None

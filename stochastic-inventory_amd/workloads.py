@@ -326,8 +326,8 @@ def fitss_sweep(levels: int = 3, patterns=None) -> List[Workload]:
     through GetPmf at the 0.999 quantile -- whose ORDER LIMIT is the instance's own: maxOrderQuantity =
     (int)(Math.round(mean of meanDemand) * capacity) (:76-77), 27 distinct values from 26 to 288.  One grid of states, 27
     numbers of actions: a ragged batch (SdpBatch(..., ragged=True)).  `levels` names the driver (1, 2, 3: One-, Two-,
-    ThreeLevelFitsSTest); the instances are the same, the drivers differ in the level rule they fit afterwards, which is not
-    part of the sweep.  `patterns`: a subset of the demand patterns, numbered 1..10 as the result file numbers them.  Every
+    ThreeLevelFitsSTest); the instances are the same, the drivers differ in the level rule they fit afterwards
+    (SdpBatch.fit_ss / simulate_ss_sampled with that number of levels).  `patterns`: a subset of the demand patterns, numbered 1..10 as the result file numbers them.  Every
     workload carries `pattern` and `capacity`."""
     from .pmf import GetPmf, PoissonDist
     if levels not in (1, 2, 3):

@@ -6,8 +6,14 @@ One process, one stream of its own, HIP events beside a synchronised host clock.
       key reset and a finalize pass per batch); timed: 27 x solve(sync=False) + one synchronize
   B   one SdpBatch(..., ragged=True) of all 810: solve alone
   C   B's solve + simulate_sampled(10000) + initial(): what the driver's loop body asks of every instance
+  D   the WHOLE loop body of ThreeLevelFitsSTest.main (:120-145): B's solve + initial() + simulate_sampled(10000) (the table
+      policy) + simulate_ss_sampled(levels, 10000) with the rule fitted on the device + the 810 gaps
+      (simFinalValue - finalValue) / finalValue; the fit and rule-rollout kernels by HIP events (simulate_ms).  Beside it the
+      only route the batch offered before for the fit and the rule rollout: read the policy rows back (sdpgpu_batch_policy),
+      fit with the plain-Python twin of tests/fitss_twin.py and roll the rule out in numpy, path-vectorised, on demands from
+      sample_demands -- on every `--host-stride`-th instance, scaled to 810
 
-A sample is as many back-to-back sweeps as fill the window, divided by their number; samples alternate A, B, C, A, B, C, ...
+A sample is as many back-to-back sweeps as fill the window, divided by their number; samples alternate A, B, C, D, A, B, C, D, ...
 after a warm-up.  Before anything is timed the two routes are compared bit for bit (initial values and actions of all 810, the
 period-1 tables of one instance per shape).
 
@@ -55,6 +61,50 @@ def timed(stream, fn, sweeps):
     stream.synchronize()
     host = (time.perf_counter() - t0) * 1e3 / sweeps
     return host, e0.elapsed_time(e1) / sweeps
+
+
+def numpy_rule_rollout(levels, rule, dem, ini, max_q, K, v, h, pi, lo, hi):
+    """SimulateFitsS.simulateSinglesS / TwosS / ThreesS for ONE instance, all paths at once: rule [T, 2 * levels], dem [n, T]."""
+    x = np.full(dem.shape[0], float(ini))
+    total = np.zeros(dem.shape[0])
+    for t in range(dem.shape[1]):
+        o = rule[t]
+        if t == 0:
+            a = np.full_like(x, o[1] - ini)
+        elif levels == 1:
+            a = np.where(x >= o[0], 0.0, np.minimum(max_q, o[1] - x))
+        else:
+            a = np.zeros_like(x)
+            lower = -np.inf
+            for b in range(levels):
+                band = (x < o[0]) if b == 0 else ((lower <= x) & (x < o[2 * b]))
+                a = np.where(band, np.minimum(max_q, o[2 * b + 1] - x), a)
+                lower = o[2 * b]
+        level = (x + a) - dem[:, t]
+        total += ((np.where(a > 0, K, 0.0) + v * a) + h * np.maximum(level, 0.0)) + pi * np.maximum(-level, 0.0)
+        x = np.maximum(np.minimum(level, hi), lo)
+    return total
+
+
+def host_route(ragged, ws, idx, levels, paths, seed, tw):
+    """What the batch offered before for the fit and the rule rollout, on the instances `idx`: -> (seconds, rules, path sums)."""
+    t0 = time.perf_counter()
+    rules, sums = [], []
+    T = ragged.T
+    for i in idx:
+        f = ws[i].functor
+        rows = []
+        for period in range(1, T + 1):
+            lo, hi = ragged.reachable(i, period)
+            pol = ragged.policy(i, period)
+            k = np.arange(lo, hi + 1)
+            rows.append(np.stack([np.full(len(k), float(period)), f.minInventory + k.astype(np.float64), pol[k].astype(np.float64)], axis=1))
+        rule = tw.fit(levels, T, int(f.maxOrderQuantity), np.concatenate(rows))
+        dem, _ = ragged.sample_demands(i, paths, seed)
+        sums.append(numpy_rule_rollout(levels, rule, dem, f.iniInventory, float(int(f.maxOrderQuantity)), f.fixedOrderingCost,
+                                       f.variOrderingCost, f.holdingCost, f.penaltyCost, f.minInventory, f.maxInventory))
+        rules.append(rule)
+    return time.perf_counter() - t0, np.stack(rules), np.stack(sums)
 
 
 def descs_of(ws):
@@ -106,6 +156,8 @@ def main():
     ap.add_argument("--samples", type=int, default=7)
     ap.add_argument("--window", type=float, default=0.3, help="least length of a timed window, seconds")
     ap.add_argument("--paths", type=int, default=10000, help="sample paths per instance of row C (Simulation's sampleNum)")
+    ap.add_argument("--levels", type=int, default=3, help="row D: the driver (1, 2, 3: One-, Two-, ThreeLevelFitsSTest)")
+    ap.add_argument("--host-stride", type=int, default=30, help="row D's host route runs on every n-th instance and is scaled")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_fitss_sweep.json"))
     ap.add_argument("--trace-b", action="store_true", help="run B three times and leave (for a kernel trace)")
     ap.add_argument("--uniform", default="", help="time CLSPTesting's uniform batch only and write the samples to this file")
@@ -172,15 +224,44 @@ def main():
         ragged.simulate_sampled(args.paths, 12345)
         ragged.initial()
 
-    sweeps = {k: max(1, int(np.ceil(args.window * 1e3 / timed(stream, f, 2)[0]))) for k, f in (("A", run_a), ("B", run_b), ("C", run_c))}
-    rows = {"A": [], "B": [], "C": []}
-    for k, f in (("A", run_a), ("B", run_b), ("C", run_c)):  # warm-up at the timed length
+    gaps = {}
+
+    def run_d():
+        ragged.solve(sync=False)
+        final, _ = ragged.initial()
+        table_mean = ragged.simulate_sampled(args.paths, 12345)
+        rule_mean = ragged.simulate_ss_sampled(args.levels, args.paths, 12345)
+        gaps["rule"] = (rule_mean - final) / final
+        gaps["table"] = (table_mean - final) / final
+
+    runs = (("A", run_a), ("B", run_b), ("C", run_c), ("D", run_d))
+    sweeps = {k: max(1, int(np.ceil(args.window * 1e3 / timed(stream, f, 2)[0]))) for k, f in runs}
+    rows = {k: [] for k, _ in runs}
+    for k, f in runs:  # warm-up at the timed length
         timed(stream, f, sweeps[k])
     for _ in range(args.samples):
-        rows["A"].append(timed(stream, run_a, sweeps["A"]))
-        rows["B"].append(timed(stream, run_b, sweeps["B"]))
-        rows["C"].append(timed(stream, run_c, sweeps["C"]))
+        for k, f in runs:
+            rows[k].append(timed(stream, f, sweeps[k]))
+    run_c()
     sim_ms = ragged.simulate_ms()
+    fit_rule_ms = []
+    for _ in range(args.samples):
+        run_d()
+        fit_rule_ms.append(ragged.simulate_ms())
+
+    # row D's other side: policy rows to the host, the twin's fit, a numpy rollout -- on a subset, checked against the device
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fitss_twin as tw
+    sub = list(range(0, n, max(1, args.host_stride)))
+    dev_rules = ragged.fit_ss(args.levels)
+    _, dev_sums = ragged.simulate_ss_sampled(args.levels, args.paths, 12345, want_sums=True)
+    host_route(ragged, ws, sub[:2], args.levels, args.paths, 12345, tw)  # warm-up
+    host_s = []
+    for _ in range(args.samples):
+        sec, h_rules, h_sums = host_route(ragged, ws, sub, args.levels, args.paths, 12345, tw)
+        host_s.append(sec * 1e3 * n / len(sub))
+    rules_equal = bool(np.array_equal(h_rules, dev_rules[sub]))
+    sums_equal = bool(np.array_equal(h_sums, dev_sums[sub]))
 
     # per-period launch times of the ragged batch (events between the launches: a run of its own)
     prof = sia.SdpBatch(descs, pmfs, ragged=True)
@@ -210,6 +291,18 @@ def main():
         "B_ms_per_sweep_host": summary(host["B"]), "B_ms_per_sweep_device": summary([x[1] for x in rows["B"]]),
         "C_ms_per_sweep_host": summary(host["C"]), "C_ms_per_sweep_device": summary([x[1] for x in rows["C"]]),
         "C_paths_per_instance": args.paths, "C_simulate_kernels_ms": sim_ms,
+        "D_ms_per_sweep_host": summary(host["D"]), "D_ms_per_sweep_device": summary([x[1] for x in rows["D"]]),
+        "D_levels": args.levels, "D_paths_per_instance": args.paths,
+        "D_fit_and_rule_rollout_kernels_ms": summary(fit_rule_ms),
+        "D_minus_C_ms_host": statistics.median(host["D"]) - statistics.median(host["C"]),
+        "D_gap_rule": {"median": float(np.median(gaps["rule"])), "min": float(gaps["rule"].min()), "max": float(gaps["rule"].max())},
+        "D_gap_table_policy_same_paths": {"median": float(np.median(gaps["table"])), "min": float(gaps["table"].min()),
+                                          "max": float(gaps["table"].max())},
+        "D_host_route": {"what": "sdpgpu_batch_policy of the six periods, the plain-Python fit of tests/fitss_twin.py, sample_demands and a "
+                                 "path-vectorised numpy rollout, per instance; fit + rule rollout ONLY (no solve, no table rollout)",
+                         "instances_run": len(sub), "scaled_to": n, "ms_scaled": summary(host_s),
+                         "rules_equal_the_device_fit": rules_equal, "path_sums_equal_the_device_rollout": sums_equal},
+        "D_host_route_over_fit_and_rule_part_of_D": statistics.median(host_s) / max(statistics.median(host["D"]) - statistics.median(host["C"]), 1e-9),
         "A_over_B": statistics.median(host["A"]) / statistics.median(host["B"]),
         "B_cells_per_s": cells / (statistics.median(host["B"]) * 1e-3),
         "B_period_ms": period_ms,
@@ -224,9 +317,11 @@ def main():
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps({k: res[k] for k in ("instances", "A_route", "B_plan", "A_over_B", "B_cells_per_s", "max_B_below_min_A")}))
-    for k in "ABC":
+    for k in "ABCD":
         print(k, "ms/sweep (host)", res[f"{k}_ms_per_sweep_host"])
     print("B per-period ms", period_ms)
+    print("D fit + rule rollout kernels ms", res["D_fit_and_rule_rollout_kernels_ms"], "host route (scaled) ms", res["D_host_route"]["ms_scaled"],
+          "rules equal", rules_equal, "sums equal", sums_equal, "gap", res["D_gap_rule"])
     if "uniform_batch_against_parent" in res:
         print("uniform", json.dumps(res["uniform_batch_against_parent"]))
     return 0
