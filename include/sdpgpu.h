@@ -210,7 +210,9 @@ typedef struct sdpgpu_desc {
 
 typedef struct sdpgpu_stats {
   int64_t states_total;     /* sum over periods of grid states (whole grid, all ranks) */
-  int64_t cells_evaluated;  /* sum over periods and THIS rank's states of nA(s) * D_t */
+  int64_t cells_evaluated;  /* sum over periods and THIS rank's states of nA(s) * D_t: the cells of the grid DECIDED.  Where the
+                               F1 level kernel stops level blocks early (f1_level_steps_run below) not all of them are
+                               walked to their last demand step; fp64_ops_executed counts what ran. */
   int64_t cells_all_ranks;  /* the same over the whole grid */
   double  solve_ms;         /* HIP-event time of the last sdpgpu_solve on its stream */
   double  kernel_ms_sum;    /* sum of per-period kernel times when profiling is on, else 0 */
@@ -230,6 +232,15 @@ typedef struct sdpgpu_stats {
                                SDPGPU_GRAPH=1 (the first call runs eagerly, the second is captured while it is enqueued, later
                                calls replay; per-period profiling, user functors and the legacy NULL stream run eagerly).  Off
                                by default: replay measured 0.6-1.6 % SLOWER than the eager sweep on ROCm 7.2. */
+  int64_t f1_level_steps_planned; /* Additive to ABI 6.  Periods run by the F1 level kernel (window_f1_level_kernel): demand steps */
+  int64_t f1_level_steps_run;     /* of level blocks, summed over waves -- what the launches planned, and what their waves walked.
+                               run < planned where the cut-off stopped blocks no action of which could still win (MIN, built-in
+                               costs, K, v, h, pi >= 0, probabilities >= 0: every running sum is a lower bound of its cell;
+                               DESIGN.md).  run == planned with SDPGPU_F1_CUTOFF=0 or an instance the cut-off does not cover;
+                               both 0 when no period ran that kernel.  Values and policy are the same bits either way.
+                               NOTE: these two fields grew sizeof(sdpgpu_stats) by 16 bytes WITHIN ABI 6 (the version number is
+                               unchanged): sdpgpu_stats_get clears and writes the whole struct through the caller's pointer, so
+                               every caller compiled against an earlier ABI 6 header must be rebuilt against this one. */
 } sdpgpu_stats;
 
 typedef struct sdpgpu_handle sdpgpu_handle;
@@ -528,6 +539,10 @@ int sdpgpu_reachable(sdpgpu_handle* h, int32_t period, uint8_t* out, int64_t n);
 int sdpgpu_simulate(sdpgpu_handle* h, int64_t n_paths, const double* demand, const double* discount, double ini_x,
                     double ini_cash, double ini_preq, double* out_sum, uint8_t* out_valid);
 
+/* Host arithmetic, except: after a solve in which the F1 level kernel ran with its cut-off, the steps its waves walked are
+ * read from the device -- the call then waits for the handle's stream (hipStreamSynchronize) and copies a few bytes back, so
+ * a caller that polls the statistics between enqueued solves serialises on the stream.  (It also waits for the stream to read
+ * solve_ms and a user functor's cell counts.) */
 int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out);
 
 /* ABI 5: the launch plan of one period of THIS rank's slab, as the launcher would choose it now (descriptor, pmfs,

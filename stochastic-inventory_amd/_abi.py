@@ -106,6 +106,8 @@ class SdpgpuStats(C.Structure):
         ("lds_bytes", C.c_double),
         ("l1_bytes", C.c_double),
         ("graph_replays", C.c_int64),
+        ("f1_level_steps_planned", C.c_int64),
+        ("f1_level_steps_run", C.c_int64),
     ]
 
 

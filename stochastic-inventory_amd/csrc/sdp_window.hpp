@@ -140,6 +140,24 @@ __global__ __launch_bounds__(256) void window_f1_kernel(WinParams W, const doubl
 //     of one state both b and a are non-decreasing, so a lower row always holds lower actions; where a band boundary and
 //     an action-block boundary fall on the same action, the row skipped in between gets a NaN value, which the finalize
 //     never takes.  Rows above a state's last piece are never reached: the value it looks for is in one below.
+//
+// THE CUT-OFF (CUT; the host turns it on per period, f1_cutoff_on in sdpgpu_window.hip: MIN, the built-in costs, K, v, h,
+// pi >= 0, every probability >= 0, V_{t+1} >= 0).  Every addend of a cell is then >= 0, and under round-to-nearest
+// a + b >= a for b >= 0: the running sum of a cell never exceeds its final value.  A cell whose running sum is already
+// STRICTLY greater than a value some action of the same state has reached can neither win nor tie, and its remaining
+// steps change no value, no action index and no tie-break.  So
+//   * a state's slot does not start at the reduction identity but at U(i) = Q(i, 0), action 0: the exact value of the
+//     state's lowest action, the same operations in the same order (a pre-pass of window_f1_kernel with one action writes
+//     the row u_row).  Every piece then reports min(U(i), its own cells) under the strict <, a tie still goes to action 0,
+//     and the lowest chunk row whose value equals V_t still carries the lowest optimal action: chunk rows, key atomics and
+//     finalize_kernel are untouched;
+//   * every S steps from a scheduled step on (where the imm ring is in its canonical rotation) the wave tests its R S
+//     cells against their slots -- R S per-lane LDS reads and compares, about 0.7 of a step -- and when every real
+//     cell other than action 0 itself is beaten (one ballot, a scalar branch) it drops the rest of the level block and its
+//     epilogue.  A NaN compares false: such a block runs in full.
+// A stopped block skips (d_pad - stop) of its d_pad steps: 3 + 1/S + 1/(64 R) operations per cell and step, as above, over
+// the steps that ran (counted per wave into cut_count[0], the tests into cut_count[1]) plus one compare per cell and test.
+// With CUT off the kernel is the one above, instruction for instruction.
 // ---------------------------------------------------------------------------------------------
 struct LevelParams {
   int32_t band;       // levels per task (a multiple of S)
@@ -150,6 +168,7 @@ struct LevelParams {
   int32_t n_states;   // hi - lo
   int32_t y_hi;       // one past the last level: hi + A - 1
   int32_t n_chunks;   // chunk rows: ceil((A - 1) / band) + n_ablocks
+  int32_t cut_start;  // CUT: the step of a task's first cut-off test (a multiple of S, >= S)
 };
 
 template <int S>
@@ -166,12 +185,14 @@ __host__ __device__ inline int level_chunks(int n_actions, int band, int n_abloc
   return (n_actions - 1 + band - 1) / band + n_ablocks;
 }
 
-template <int R, int S, bool FUTURE, bool KEYED_IN>
+template <int R, int S, bool FUTURE, bool KEYED_IN, bool CUT>
 __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, LevelParams L, const double* __restrict__ v_next,
                                                               const unsigned long long* __restrict__ k_next,
                                                               double* __restrict__ out_val, int32_t* __restrict__ out_idx,
                                                               unsigned long long* __restrict__ k_cur,
-                                                              const double* __restrict__ pmf_p) {
+                                                              const double* __restrict__ pmf_p,
+                                                              const double* __restrict__ u_row,
+                                                              unsigned long long* __restrict__ cut_count) {
   constexpr int DB = LevelShape<S>::DB, ROW = LevelShape<S>::ROW, NA = 64 * R;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -191,9 +212,21 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
   double* s_row = reinterpret_cast<double*>(mine);
   double* s_val = s_row + DB * ROW;
   int* s_idx = reinterpret_cast<int*>(s_val + L.band + NA);
-  for (int q = lane; q < n_slot; q += 64) {
-    s_val[q] = ident;
-    s_idx[q] = 0;
+  if constexpr (CUT) {
+    // every slot starts at U(i) = Q(i, 0) with action 0 (see THE CUT-OFF above); a slot of no state of the slab -- the
+    // ends of the range, and the slots past n_slot that the last, ragged band's level blocks still address -- at a value
+    // every sum exceeds, so that it never holds a block back (it is never written out)
+    for (int q = lane; q < L.band + NA; q += 64) {
+      const int i = i_min + q;
+      const bool in = i >= L.lo && i - L.lo < L.n_states;
+      s_val[q] = in ? u_row[i] : -__builtin_huge_val();
+      s_idx[q] = 0;
+    }
+  } else {
+    for (int q = lane; q < n_slot; q += 64) {
+      s_val[q] = ident;
+      s_idx[q] = 0;
+    }
   }
   double c0[R];
   bool kreal[R];
@@ -207,6 +240,12 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
     else
       c0[r] = (a > 0 ? W.K : 0.0) + W.v * a;
   }
+  // CUT: the test schedule (wave-uniform, scalar registers).  A block's first test comes `dec` steps before the step its
+  // predecessor stopped at, then one every S steps; a block that passes its first test moves the next block's twice as
+  // far down, and after a block that ran to the end the next one is tested once, S steps before the end (a sum only grows,
+  // so a block that could have stopped earlier still passes there): where nothing ever stops, one test per block.
+  [[maybe_unused]] int cut_first = L.cut_start, cut_dec = S, cut_once = 0;
+  [[maybe_unused]] unsigned cut_steps = 0, cut_tests = 0;
 
   for (int y0 = yb; y0 < ye; y0 += S) {
     // Priority by progress, as in f1_cells: the four waves of a workgroup free its LDS only together, and a plan
@@ -224,7 +263,9 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
         imm[r][s] = c0[r] + ms;
       }
     }
-    for (int j0 = 0; j0 < L.d_pad; j0 += DB) {
+    [[maybe_unused]] int cut_at = cut_first, cut_fail = 0;
+    int stop_at = -1;  // CUT: the step the block stopped at
+    for (int j0 = 0; j0 < L.d_pad && stop_at < 0; j0 += DB) {
       const int nj = min(DB, L.d_pad - j0);
       // the table of steps j0 .. j0 + nj - 1: lane t forms row t (rows past nj repeat the last step and are not read)
       __builtin_amdgcn_wave_barrier();
@@ -254,6 +295,28 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
       for (int u = 0; u < NQ; ++u) nxt[u] = reinterpret_cast<const double2*>(s_row)[u];
 #pragma unroll 1
       for (int t0 = 0; t0 < nj; t0 += S) {
+        if constexpr (CUT) {
+          // (the imm ring is in its canonical rotation here; the slots are the ones the epilogue below updates)
+          if (j0 + t0 >= cut_at) {
+            const int sb = (y0 - yb) - lane + NA - 1;
+            bool beaten = true;
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+#pragma unroll
+              for (int r = 0; r < R; ++r) {
+                const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];  // not a padded action, not action 0
+                beaten = beaten && (!live || acc[r][s] > s_val[sb + s - 64 * r]);
+              }
+            }
+            ++cut_tests;
+            if (__builtin_amdgcn_ballot_w64(!beaten) == 0) {
+              stop_at = j0 + t0;
+              break;
+            }
+            ++cut_fail;
+            cut_at = cut_once ? INT32_MAX : j0 + t0 + S;
+          }
+        }
         const double* rows = s_row + t0 * ROW;
 #pragma unroll
         for (int t = 0; t < S; ++t) {
@@ -289,6 +352,18 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
           __builtin_amdgcn_sched_barrier(0);
         }
       }
+    }
+    if constexpr (CUT) {
+      cut_steps += (unsigned)(stop_at < 0 ? L.d_pad : stop_at);
+      if (stop_at >= 0) {  // no cell of the block can win or tie: nothing to put into the slots
+        cut_dec = cut_fail == 0 ? min(2 * cut_dec, 8 * S) : S;
+        cut_first = max(S, stop_at - cut_dec);
+        cut_once = 0;
+        continue;
+      }
+      cut_first = max(S, L.d_pad - S);
+      cut_dec = S;
+      cut_once = 1;
     }
     // into the per-state slots: cell (r, s) is state y0 + s - k, slot (y0 - yb) + s - lane - 64 r + NA - 1
     const int sb = (y0 - yb) - lane + NA - 1;
@@ -331,6 +406,12 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
       atomicMax(k_cur + i, f64_key(v));
     else
       atomicMin(k_cur + i, f64_key(v));
+  }
+  if constexpr (CUT) {  // what ran, for sdpgpu_stats: demand steps of level blocks, and cut-off tests
+    if (lane == 0) {
+      atomicAdd(cut_count, (unsigned long long)cut_steps);
+      atomicAdd(cut_count + 1, (unsigned long long)cut_tests);
+    }
   }
 }
 

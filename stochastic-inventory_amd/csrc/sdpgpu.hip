@@ -373,6 +373,10 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
   rc = ensure_device(h);
   if (rc) return rc;
   PeriodInfo& p = h->per[period - 1];
+  p.v_nonneg = false;  // (launch_window says otherwise)
+  p.lvl_steps_planned = 0;
+  p.lvl_cut = false;
+  p.pre_ops = 0;
   DevParams P = make_params(h, period);
   const double* v_next = period < h->T ? h->d_values + h->per[period].v_off : nullptr;
   double* v_cur = h->d_values + p.v_off;
@@ -654,6 +658,7 @@ int sdpgpu_create(const sdpgpu_desc* desc, sdpgpu_handle** out) {
     if (const char* e = std::getenv("SDPGPU_WIN_NCH")) h->win_nch = std::atoi(e);
     if (const char* e = std::getenv("SDPGPU_WIN_S")) h->win_s = std::atoi(e);
     if (const char* e = std::getenv("SDPGPU_WIN_LEVEL")) h->win_level = std::atoi(e) != 0;
+    if (const char* e = std::getenv("SDPGPU_F1_CUTOFF")) h->f1_cutoff = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_FUSE_COMBINE")) h->fuse_combine = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_CASH_SHIFT")) h->use_cash_shift = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_CASH_ROW")) h->use_cash_row = std::atoi(e) != 0;
@@ -799,6 +804,8 @@ void sdpgpu_destroy(sdpgpu_handle* h) {
   if (h->d_chunk_val) (void)hipFree(h->d_chunk_val);
   if (h->d_chunk_idx) (void)hipFree(h->d_chunk_idx);
   if (h->d_jobs) (void)hipFree(h->d_jobs);
+  if (h->d_f1_u) (void)hipFree(h->d_f1_u);
+  if (h->d_cut_count) (void)hipFree(h->d_cut_count);
   if (h->d_diag) (void)hipFree(h->d_diag);
   if (h->d_rowtab) (void)hipFree(h->d_rowtab);
   if (h->d_rowperm) (void)hipFree(h->d_rowperm);
@@ -1511,14 +1518,37 @@ int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out) {
   std::memset(out, 0, sizeof *out);
   if (layout(h)) return SDPGPU_ERR_STATE;
   bool modelled = true;
+  // the level kernel's own count of what it ran (periods with the cut-off): steps and tests per period
+  std::vector<unsigned long long> cut((size_t)h->T * 2, 0);
+  bool cut_read = false;
+  if (h->allocated && h->d_cut_count) {
+    bool any = false;
+    for (int t = 0; t < h->T; ++t) any = any || h->per[t].lvl_cut;
+    if (any) {
+      (void)ensure_device(h);
+      cut_read = hipStreamSynchronize(h->stream) == hipSuccess &&
+                 hipMemcpy(cut.data(), h->d_cut_count, cut.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+  }
   for (int t = 0; t < h->T; ++t) {
     const PeriodInfo& p = h->per[t];
     out->states_total += p.S;
     out->cells_evaluated += p.cells_rank;
     out->cells_all_ranks += p.cells_all;
     if (h->period_done[t]) out->periods_run++;
-    out->fp64_ops_executed += (double)p.cells_rank * p.ops_cell;
-    out->lds_bytes += (double)p.cells_rank * p.lds_cell;
+    // (a level period with the cut-off walks `run` of its planned steps, each at ops_cell operations per cell, makes its
+    // tests -- one compare per cell -- and pays the pre-pass; without it, or when the counters cannot be read, all of them)
+    double walked = 1.0, tests = 0.0;
+    out->f1_level_steps_planned += p.lvl_steps_planned;
+    if (p.lvl_cut && cut_read && p.lvl_steps_planned > 0) {
+      out->f1_level_steps_run += (int64_t)cut[(size_t)t * 2];
+      walked = (double)cut[(size_t)t * 2] / (double)p.lvl_steps_planned;
+      tests = (double)cut[(size_t)t * 2 + 1] / (double)p.lvl_steps_planned;
+    } else {
+      out->f1_level_steps_run += p.lvl_steps_planned;
+    }
+    out->fp64_ops_executed += (double)p.cells_rank * (p.ops_cell * walked + tests) + p.pre_ops;
+    out->lds_bytes += (double)p.cells_rank * p.lds_cell * walked;
     out->l1_bytes += (double)p.cells_rank * p.l1_cell;
     if (p.ops_cell == 0 && p.cells_rank > 0) modelled = false;
   }

@@ -88,6 +88,14 @@ struct PeriodInfo {
   // executed fp64 add/mul operations per cell of the kernel plan that ran this period (identical operations of
   // neighbouring cells are formed once, see sdp_window.hpp / sdp_cash.hpp); 0 = the kernel has no such model
   double ops_cell = 0;
+  // F1 window periods: every V_t of the row is >= 0 (a minimum or maximum of sums of non-negative terms, f1_terms_nonneg) --
+  // what the period below needs before it may stop level blocks early
+  bool v_nonneg = false;
+  // window_f1_level_kernel: demand steps of level blocks the launch planned (waves x blocks x d_pad; 0: another kernel), and
+  // whether it ran with the cut-off, i.e. counted the steps it ran and its tests on the device (sdpgpu_handle::d_cut_count)
+  int64_t lvl_steps_planned = 0;
+  bool lvl_cut = false;
+  double pre_ops = 0;  // fp64 operations of the cut-off's pre-pass (Q(i, 0) of every state), in total
   double lds_cell = 0, l1_cell = 0;  // bytes per cell through the LDS / the vector L1 of the kernel that ran the period (0: no model)
   mutable WinPlanCache win_plan;     // (a cache: filled through const handles by plan_window)
 };
@@ -146,6 +154,10 @@ struct sdpgpu_handle {
   bool use_cash_row = true;   // SDPGPU_CASH_ROW=0 turns the cash row kernel off (generic kernel instead)
   int win_prio_fair = 1;  // window kernel: s_setprio by progress (SDPGPU_WIN_PRIO=0 turns it off)
   int win_r = 0, win_nch = 0, win_s = 0;  // tuning overrides (SDPGPU_WIN_R / SDPGPU_WIN_NCH / SDPGPU_WIN_S), 0 = heuristic
+  int f1_cutoff = 1;   // SDPGPU_F1_CUTOFF=0: the level kernel never stops a level block early (A/B runs, tests)
+  double* d_f1_u = nullptr;  // the cut-off's row U(i) = Q(i, 0) of the period being run (window_f1_level_kernel)
+  size_t f1_u_elems = 0;
+  unsigned long long* d_cut_count = nullptr;  // [T][2]: steps run and tests made by the level kernel's waves, per period
   int win_level = -1;  // SDPGPU_WIN_LEVEL: 1 = the action-major level kernel wherever it can run, 0 = never, -1 = where it wins
   uint8_t* d_reach = nullptr;      // reachable masks, period t at reach_off[t-1]
   std::vector<size_t> reach_off;

@@ -27,6 +27,51 @@ bool window_eligible(const sdpgpu_handle* h, int period) {
 // ((5 + 4(S-1)) / S, see window_f1_kernel) but bigger, fewer tasks: small grids keep S low.
 static WinPlan plan_window_search(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, std::string* why);
 
+
+// Every addend of every F1 cell of the period is >= 0, so a cell's running sum is a lower bound of its final value (what the
+// level kernel's cut-off rests on, sdp_window.hpp).  What can enter a cell of the window kernels, and why each is covered:
+//   * c0(a) = (a > 0 ? K : 0) + v a with a = k step: K, v >= 0 and step > 0 (tested as !(x >= 0): a NaN says no);
+//   * M(m) = h max(l, 0) + pi max(-l, 0): h, pi >= 0, whatever the sign of the level l -- the grid bounds, d_0 and
+//     clamp_inventory only move l; user tables (m_tab / c_tab, the level shape) may hold any sign: not covered;
+//   * p_j: every probability of the period >= 0 (the zero padding of the window layout included);
+//   * V_{t+1}: the row the period below left, v_nonneg -- a minimum or maximum of such sums, from +0.0, by induction from
+//     period T; not trusted when the value arena is the caller's memory (sdpgpu_attach_values), which the library does not
+//     write alone;
+//   * nothing else: the backorder family's cell has no overhead, discount, salvage or price term (sdp_device.hpp: cell<FAM_BACKORDER>;
+//     PeriodInfo::overhead feeds the cash families only), and the window kernels read WinParams alone.
+static bool f1_terms_nonneg(const sdpgpu_handle* h, int period) {
+  if (h->custom || h->level_shape) return false;
+  const sdpgpu_desc& d = h->d;
+  if (!(d.fixed_order_cost >= 0 && d.unit_order_cost >= 0 && d.holding_cost >= 0 && d.penalty_cost >= 0 && d.step > 0)) return false;
+  for (double q : h->pmf_p[(size_t)period - 1])
+    if (!(q >= 0)) return false;
+  if (period < h->T && (h->values_external || !h->per[period].v_nonneg)) return false;
+  return true;
+}
+
+// The cut-off's pre-pass: window_f1_kernel<4, 8> with ONE action (one R-block, one chunk) over the slab, tiles of 512 states.
+struct CutPrePlan {
+  int d_pad = 0;
+  size_t smem = 0;
+  int64_t tiles = 0;
+};
+static CutPrePlan cut_pre_plan(const PeriodInfo& p, int64_t lo, int64_t hi) {
+  CutPrePlan c;
+  c.d_pad = (p.nD_win + 10) / 11 * 11;
+  c.smem = sdp::win_wg_lds(512 + 4 + c.d_pad + 8, p.nD_win);
+  c.tiles = (hi - lo + 511) / 512;
+  return c;
+}
+// THE gate of the cut-off (sdp_window.hpp), one predicate for the planner and the launcher: SDPGPU_F1_CUTOFF not 0, MIN,
+// every term >= 0, and a pre-pass that fits.  (For a period with a future it reads what the period below left, so it is
+// asked when that period has been launched; period T depends on the descriptor and the pmf alone.)
+static bool f1_cutoff_on(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi) {
+  if (!h->f1_cutoff || h->d.direction != SDPGPU_MIN || hi <= lo || hi - lo >= INT32_MAX) return false;
+  if (!f1_terms_nonneg(h, period)) return false;
+  const CutPrePlan c = cut_pre_plan(h->per[period - 1], lo, hi);
+  return c.smem <= kLdsPerCU && grid_ok((c.tiles + 3) / 4);
+}
+
 // The action-major level kernel (window_f1_level_kernel), where it can run and -- unless SDPGPU_WIN_LEVEL=1 asks for it
 // -- where it wins: a whole single-rank slab (no halo, no interior / boundary split), chunk rows allowed (every state's
 // actions meet across tasks), nothing forced about the state-major blocks, and a grid that fills the chip with tasks
@@ -46,8 +91,11 @@ static WinPlan plan_level(const sdpgpu_handle* h, int period, int64_t lo, int64_
   constexpr int R = 4, NA = 64 * R;
   const int nb = (A + NA - 1) / NA;
   // (period T has no future term: 2 + 1/S operations per cell on either kernel, and the action padding and the
-  // per-level-block overheads leave the level kernel behind -- measured 6.44 against 6.28 ms on the target grid)
-  if (h->win_level < 0 && !(period < h->T && n >= 262144 && (double)nb * NA <= 1.06 * A && D >= 16)) return pl;
+  // per-level-block overheads leave the level kernel behind -- measured 6.44 against 6.28 ms on the target grid.  Where the
+  // cut-off applies the level kernel walks fewer steps and wins: 4.43 ms, 0.69 of its steps walked, against the state-major
+  // kernel's 6.08 ms, per-launch events on the target grid, profiles/f1_cutoff_ab.txt.)
+  const bool last_cut = period == h->T && f1_cutoff_on(h, period, lo, hi);
+  if (h->win_level < 0 && !((period < h->T || last_cut) && n >= 262144 && (double)nb * NA <= 1.06 * A && D >= 16)) return pl;
   constexpr int S = 8;
   const int64_t ny = n + A - 1;
   int band_max = 0;
@@ -545,6 +593,7 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
   W.n_actions = h->n_actions_full;
   W.maxdir = P.maxdir;
   W.n_demand = p.nD_win;
+  p.v_nonneg = f1_terms_nonneg(h, period);  // (either kernel: the row this launch leaves)
   if (pl.level) {
     const unsigned long long* k_next = keyed_in ? h->d_keys + (size_t)period * h->key_stride : nullptr;
     sdp::LevelParams L{};
@@ -564,26 +613,108 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
     if (!grid_ok((pl.n_tasks + 3) / 4)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((pl.n_tasks + 3) / 4));
     bool launched = false;
-#define SDP_LVL_GO(RR, SS, FU, KI)                                                                                             \
+    // THE CUT-OFF (sdp_window.hpp): once per period, MIN only, every term >= 0, and SDPGPU_F1_CUTOFF=0 turns it off
+    const bool cut = f1_cutoff_on(h, period, lo, hi);
+    const CutPrePlan pre = cut_pre_plan(p, lo, hi);
+    const int pre_dpad = pre.d_pad;
+    const size_t pre_smem = pre.smem;
+    const int64_t pre_tiles = pre.tiles;
+    {
+      int64_t blocks = 0;
+      for (int64_t yb = lo; yb < L.y_hi; yb += pl.band) blocks += (std::min<int64_t>(yb + pl.band, L.y_hi) - yb + pl.S - 1) / pl.S;
+      p.lvl_steps_planned = blocks * pl.n_ablocks * pl.d_pad;
+    }
+    p.lvl_cut = cut;
+    const double* u_row = nullptr;
+    unsigned long long* cut_count = nullptr;
+    if (cut) {
+      const size_t need = (size_t)(hi - lo);
+      if (need > h->f1_u_elems) {
+        hipError_t e = hipStreamSynchronize(st);  // (earlier launches may still read the old row)
+        if (e != hipSuccess) return e;
+        if (h->d_f1_u) (void)hipFree(h->d_f1_u);
+        h->d_f1_u = nullptr;
+        h->f1_u_elems = 0;
+        e = hipMalloc((void**)&h->d_f1_u, need * sizeof(double));
+        if (e != hipSuccess) return e;
+        h->f1_u_elems = need;
+      }
+      if (!h->d_cut_count) {
+        hipError_t e = hipMalloc((void**)&h->d_cut_count, (size_t)h->T * 2 * sizeof(unsigned long long));
+        if (e != hipSuccess) return e;
+      }
+      cut_count = h->d_cut_count + (size_t)(period - 1) * 2;
+      hipError_t e = hipMemsetAsync(cut_count, 0, 2 * sizeof(unsigned long long), st);
+      if (e != hipSuccess) return e;
+      // U(i) = Q(i, 0): the state-major kernel with ONE action (its guards ignore the three padded actions of the R-block)
+      // and one chunk, into the row -- the same operations in the same order as the level kernel's action 0
+      sdp::WinParams Wp = W;
+      Wp.n_actions = 1;
+      Wp.d_pad = pre_dpad;
+      Wp.d_main = p.nD_win / 11 * 11;
+      Wp.n_chunks = 1;
+      Wp.chunk_blocks = 1;
+      Wp.n_tiles = (int32_t)pre_tiles;
+      Wp.n_tasks = (int32_t)pre_tiles;
+      Wp.tile_first = 0;
+      Wp.tile_gap_at = Wp.n_tiles;
+      Wp.tile_gap = 0;
+      Wp.partial_stride = 0;
+      Wp.pol_lo = Wp.pol_hi = 0;  // no action index is stored
+      double* u_out = h->d_f1_u - lo;
+      int32_t* no_idx = nullptr;
+      unsigned long long* no_keys = nullptr;
+      const dim3 pre_grid((unsigned)((pre_tiles + 3) / 4));
+#define SDP_PRE_GO(FU, KI)                                                                                                  \
+  do {                                                                                                                      \
+    static LdsMark mark;                                                                                                    \
+    hipError_t ea = lds_allow(sdp::window_f1_kernel<4, 8, FU, KI>, pre_smem, &mark);                                        \
+    if (ea != hipSuccess) return ea;                                                                                        \
+    hipLaunchKernelGGL((sdp::window_f1_kernel<4, 8, FU, KI>), pre_grid, dim3(256), pre_smem, st, Wp, v_next, k_next, u_out, \
+                       no_idx, no_keys, pmf_p, lo, hi);                                                                     \
+  } while (0)
+      if (!future)
+        SDP_PRE_GO(false, false);
+      else if (keyed_in)
+        SDP_PRE_GO(true, true);
+      else
+        SDP_PRE_GO(true, false);
+#undef SDP_PRE_GO
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      u_row = u_out;
+      // (four actions walked per state, at the state-major (4, 8) block's operations per cell)
+      p.pre_ops = (double)(hi - lo) * 4.0 * p.nD_win * (future ? 3.0 + 1.0 / 8 + 11.0 / 32 : 2.0 + 1.0 / 8);
+    }
+    L.cut_start = std::max(pl.S, p.nD_win / 2 / pl.S * pl.S);  // a task's first block: tests from D / 2 on
+#define SDP_LVL_GO(RR, SS, FU, KI, CU)                                                                                         \
   do {                                                                                                                         \
     static LdsMark mark;                                                                                                       \
-    hipError_t ea = lds_allow(sdp::window_f1_level_kernel<RR, SS, FU, KI>, pl.smem, &mark);                                    \
+    hipError_t ea = lds_allow(sdp::window_f1_level_kernel<RR, SS, FU, KI, CU>, pl.smem, &mark);                                \
     if (ea != hipSuccess) return ea;                                                                                           \
-    hipLaunchKernelGGL((sdp::window_f1_level_kernel<RR, SS, FU, KI>), grid, dim3(256), pl.smem, st, W, L, v_next, k_next,      \
-                       out_val, out_idx, k_cur, pmf_p);                                                                        \
+    hipLaunchKernelGGL((sdp::window_f1_level_kernel<RR, SS, FU, KI, CU>), grid, dim3(256), pl.smem, st, W, L, v_next, k_next,  \
+                       out_val, out_idx, k_cur, pmf_p, u_row, cut_count);                                                      \
+  } while (0)
+#define SDP_LVL_C(RR, SS, FU, KI)       \
+  do {                                  \
+    if (cut)                            \
+      SDP_LVL_GO(RR, SS, FU, KI, true); \
+    else                                \
+      SDP_LVL_GO(RR, SS, FU, KI, false);\
   } while (0)
 #define SDP_LVL_R(RR, SS)               \
   if (pl.R == RR && pl.S == SS) {       \
     if (!future)                        \
-      SDP_LVL_GO(RR, SS, false, false); \
+      SDP_LVL_C(RR, SS, false, false);  \
     else if (keyed_in)                  \
-      SDP_LVL_GO(RR, SS, true, true);   \
+      SDP_LVL_C(RR, SS, true, true);    \
     else                                \
-      SDP_LVL_GO(RR, SS, true, false);  \
+      SDP_LVL_C(RR, SS, true, false);   \
     launched = true;                    \
   }
     SDP_LVL_R(4, 8)
 #undef SDP_LVL_R
+#undef SDP_LVL_C
 #undef SDP_LVL_GO
     if (!launched) return hipErrorInvalidValue;
     hipError_t e = hipGetLastError();
