@@ -798,7 +798,10 @@ def _graph_cases():
             ("f1_ping_pong", lambda: workloads.cfg5_scaled(S=70000, T=4, A=40, D=30), 0),
             ("f2_leadtime", lambda: workloads.cfg4_leadtime(T=3, NX=120, A=40, D=30), 1), ("f2_pipeline", lambda: workloads.cfg4_pipeline(T=3, NX=90, A=24, D=30), 1),
             ("f3_dyadic_diag", _cfg3_small, 1), ("f3_tenths_pair", lambda: workloads.cfg3_tenths(T=3, NX=12, maxCash=60.0, A=9, D=12), 1),
-            ("f4_overdraft", cases.f4_overdraft, 1), ("f5_level_order", cases.f5_cash_leadtime, 1), ("f6_survival", cases.f6_survival, 1)]
+            ("f4_overdraft", cases.f4_overdraft, 1), ("f5_level_order", cases.f5_cash_leadtime, 1), ("f6_survival", cases.f6_survival, 1),
+            # the smallest grid the planner gives to the level kernel by itself (no switch is set here), 17 level blocks per task:
+            # pre-pass, counter memset and the kernel with the cut-off inside the capture
+            ("f1_level_cutoff", lambda: workloads.cfg5_scaled(S=262144, T=2, A=256, D=16), 1)]
 
 
 @pytest.mark.parametrize("name,make,store_all", _graph_cases(), ids=[c[0] for c in _graph_cases()])

@@ -10,6 +10,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import level_cut_twin
 from stochastic_inventory_amd import workloads
 from stochastic_inventory_amd.functors import BackorderFunctor
 from stochastic_inventory_amd.states import OptDirection
@@ -154,3 +155,49 @@ def test_cutoff_stats_fields_match_the_header(sia):
     with sia.SdpEngine(w.desc(), w.pmf, w.overhead()) as eng:
         st = eng.stats()
         assert st.f1_level_steps_planned == 0 and st.f1_level_steps_run == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Bands of several level blocks: what a task carries from one level block to the next (cut_first / cut_dec / cut_once, slots
+# that earlier blocks have lowered, the epilogue skipped for some blocks of a task and written for others, the -inf slots of a
+# ragged last band).  The device's step counter against the CPU twin's count (tests/level_cut_twin.py; its figures and the
+# conditions these grids meet are checked on the CPU by tests/test_level_cut_twin.py).
+# ---------------------------------------------------------------------------------------------------------------
+def _case_grid(c):
+    return _grid(c["S"], c["A"], c["D"], T=c["T"], lo=c["lo"], K=c["K"], v=c["v"], h=c["h"], pi=c["pi"])
+
+
+def _level_geometry(sia, w, monkeypatch, c):
+    """(band, action blocks, padded steps) of the level plan of `w`, from sdpgpu_plan_period."""
+    for k in _SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("SDPGPU_WIN_LEVEL", "1")
+    with sia.SdpEngine(w.desc(), w.pmf, w.overhead()) as eng:
+        return level_cut_twin.plan_geometry(eng.plan(1), c["S"], c["A"], c["D"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", level_cut_twin.MULTI_BLOCK_GRIDS, ids=lambda c: c["id"])
+def test_cutoff_bands_of_several_level_blocks(sia, oracle, monkeypatch, c):
+    """Grids whose plan gives every task four to six level blocks (asserted from the plan, so that a planner change cannot
+    return them to one): tables as in every test above, the planned steps are the host formula's -- level blocks of every
+    band x action blocks x padded steps -- and the steps run are EXACTLY the twin's.  A test that reads another slot, a
+    schedule that is not carried over as written or a slot outside the slab that holds a block back changes that count, mostly
+    without changing a table."""
+    w = _case_grid(c)
+    planned, run = _all_ways(sia, oracle, monkeypatch, w)
+    band, nb, d_pad = _level_geometry(sia, w, monkeypatch, c)
+    assert band // 8 == c["blocks"] and band >= 32
+    assert planned == c["T"] * level_cut_twin.planned_steps(c["S"], c["A"], band, nb, d_pad)
+    assert run == sum(c["run"]), f"{w.name}: the device ran {run} steps, the twin {sum(c['run'])}"
+    assert run <= 0.9 * planned
+
+
+@pytest.mark.gpu
+def test_cutoff_steps_are_the_twins_on_one_block_grids(sia, monkeypatch):
+    """The four grids of test_cutoff_fires_and_changes_nothing (tables: there): the device counts the twin's steps, 0.5842 /
+    0.6049 / 0.8942 / 0.7778 of the planned ones."""
+    for c in level_cut_twin.ONE_BLOCK_GRIDS:
+        _, planned, run = _solve(sia, _case_grid(c), monkeypatch, 1, None)
+        print(f"{c['id']}: steps planned {planned}, run {run} ({run / planned:.4f})")
+        assert run == sum(c["run"]), c["id"]
