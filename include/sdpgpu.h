@@ -128,6 +128,9 @@ typedef enum sdpgpu_direction { SDPGPU_MIN = 0, SDPGPU_MAX = 1 } sdpgpu_directio
 #define SDPGPU_KERNEL_SEPARABLE 3 /* OPT-IN, never chosen automatically.
                                      F1: Q(x,a) = c(a) + G(x+a), O((S+A)D + SA) per period.  REASSOCIATES the reference's
                                      sum: values agree to rounding (1e-9 relative), the arg-opt may differ on near-ties.
+                                     Weights that do not sum to 1 are honoured: the mode forms c(a) * P_t + G(x+a), P_t the
+                                     period's weights added in ascending order (the reference's sum carries c(a) * P_t);
+                                     P_t == 1.0 leaves c(a) + G(x+a) bit for bit (tests/separable_twin.py is its twin).
                                      F2 (lead time 1 or 2): V_t and the arg-min depend on (x + preQ[, q2]) only: one
                                      evaluation per level in the reference's operation order, O(A (nx+nq) D [nq]) for
                                      that table + one write per state.  EXACT: values and policy bit-identical to the

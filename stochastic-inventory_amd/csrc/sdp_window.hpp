@@ -711,12 +711,17 @@ __global__ __launch_bounds__(256) void window_combine_kernel(const double* __res
 // the arg-opt may differ where two actions tie to within that rounding.  Any demand grid (no unit-stride
 // requirement).  One workgroup = 64 states: phase 1 builds G over the tile's 64 + A - 1 levels in LDS,
 // phase 2 scans the actions.
+// The weights need not sum to 1 (the ABI takes any: zeroed points without renormalising, a negative weight): the reference's
+// sum_j p_j (c(a) + ...) carries c(a) * sum_j p_j, so phase 2 forms Q(x, a) = c(a) * P_t + G(x + a) with P_t the period's
+// weights added in ascending order from 0.0 on the host (SepParams::p_sum).  P_t == 1.0 multiplies exactly: the bits of
+// a normalised period are those of c(a) + G(x + a).  tests/separable_twin.py restates this kernel bit for bit.
 // ---------------------------------------------------------------------------------------------
 struct SepParams {
   double x_lo, step, h, pi, K, v;
   double next_x_lo, inv_step;
   double min_inventory, max_inventory;
   double d_min;          // smallest demand value of the period
+  double p_sum;          // the period's weights added in ascending order from 0.0 (1.0 for a normalised pmf)
   int32_t d_range;       // (d_max - d_min) / step
   int32_t clamp_inventory;
   int32_t next_last;
@@ -777,7 +782,7 @@ __global__ __launch_bounds__(256) void separable_f1_kernel(SepParams P, const do
   int bestk = 0;
   for (int k = as; k < P.n_actions; k += 4) {
     const double a = (double)k * P.step;
-    const double q = ((a > 0 ? P.K : 0.0) + P.v * a) + s_g[sx + k];
+    const double q = ((a > 0 ? P.K : 0.0) + P.v * a) * P.p_sum + s_g[sx + k];
     if (MAXDIR ? (q > best) : (q < best)) {
       best = q;
       bestk = k;

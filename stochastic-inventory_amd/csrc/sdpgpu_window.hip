@@ -872,6 +872,8 @@ hipError_t launch_separable(sdpgpu_handle* h, const DevParams& P, int period, co
     S.n_demand = p.nD;
     S.d_min = h->pmf_d[period - 1].front();  // demands are strictly ascending (checked at set_pmf)
     S.d_range = (int32_t)((h->pmf_d[period - 1].back() - S.d_min) / h->d.step);
+    S.p_sum = 0.0;  // the reference's sum carries c(a) * sum_j p_j: the weights need not sum to 1
+    for (double q : h->pmf_p[(size_t)period - 1]) S.p_sum += q;
     const bool future = period < h->T;
     if (future) {
       S.next_x_lo = h->per[period].g.x_lo;
