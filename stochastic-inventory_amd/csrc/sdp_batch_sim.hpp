@@ -4,10 +4,13 @@
 // from memory or DRAWN here (Sampling.generateLHSamples, Sampling.java:86-103, made reproducible).
 //
 //   * a wave's 64 paths belong to ONE instance (the paths of an instance are padded to whole waves), so the instance's
-//     record -- costs, inventory bounds, state count, the base of its policy rows --, its sampler records and its policy-row
-//     offsets are wave-uniform loads;
-//   * the rollout statements are cell<FAM_BACKORDER> of sdp_device.hpp word for word (simulate_kernel of sdp_gather.hpp with
-//     discount 1.0: `1.0 * imm` is `imm`), so a path's sum has the bits sdpgpu_simulate gives on a handle of the instance;
+//     record -- costs, inventory bounds, order limit, state count, the base of its policy rows --, its sampler records and
+//     its policy-row offsets are wave-uniform loads;
+//   * ONE kernel rolls the table policy and the (s, S) level rules (sdp_fitss.hpp): batch_sim_kernel is a template over a
+//     RULE -- a small struct that picks the period's order and says where the period starts from -- and everything else of
+//     a path (demand, f1_sim_period, sums, wave total) is written once.  f1_sim_period is cell<FAM_BACKORDER> of sdp_device.hpp
+//     (simulate_kernel of sdp_gather.hpp with discount 1.0: `1.0 * imm` is `imm`), so a path's sum under the table rule has
+//     the bits sdpgpu_simulate gives on a handle of the instance;
 //   * the sampler ("Batched simulation"): stratum j = sigma(p) of path p, a = 53 bits of Philox4x32-10 at counter
 //     (j, t, instance, 0) under the caller's seed, u = j / n + a / n, demand = k_lo + #{thresholds <= u} (or < u for an
 //     integer-valued distribution) by binary search in the host-made table of the (instance, period).  The tables are a few
@@ -21,36 +24,74 @@
 
 namespace sdp {
 
-// An instance's costs and its OWN grid (the instances of a ragged batch differ in it); wave-uniform in the rollout.
+// An instance's costs, its OWN grid (the instances of a ragged batch differ in it), its order limit and the base of its policy
+// rows; wave-uniform in the rollout.
 struct SimInst {
   double h, pi, K, v;
   double min_inventory, max_inventory;
-  int64_t pol_base;  // the instance's policy rows [T][n_states] in the batch's policy arena
+  double maxq;       // order limit (the level rules cap their orders at it)
+  int64_t pol_base;  // the instance's policy rows [T][n_states] in the batch's policy arena (the table rule)
   int32_t n_states, pad;
 };
 
 struct SimLaunch {
   double step, inv_step;
-  int32_t T, n_inst, n_paths;
+  int32_t T, n_inst;
   int32_t waves_per_inst;  // ceil(n_paths / 64)
-  int32_t half_bits;       // sigma: smallest h >= 1 with 4^h >= n_paths
   int64_t demand_stride;   // explicit demands: elements between the demand sets of two instances (0: one shared set)
-  uint32_t seed_lo, seed_hi;
+  SimStream R;             // n_paths, and the latin hypercube's seed and sigma width (first_path is not used: 0)
 };
 
 // demand of path p of (instance, t), and the uniform it came from
 __device__ __forceinline__ double sim_draw(const SimLaunch& L, const SimSampler& S, const double* __restrict__ thr, int inst, int t,
                                            uint32_t p, double* u_out) {
-  const double u = sim_uniform_lhs((uint32_t)L.n_paths, L.half_bits, L.seed_lo, L.seed_hi, inst, t, p);
+  const double u = sim_uniform_lhs(L.R.n_paths, L.R.half_bits, L.R.seed_lo, L.R.seed_hi, inst, t, p);
   *u_out = u;
   return sim_demand(S, thr, nullptr, u);
 }
 
-template <bool SAMPLED>
-__global__ __launch_bounds__(256) void batch_sim_kernel(SimLaunch L, const SimInst* __restrict__ inst, const int32_t* __restrict__ ini_idx,
-                                                        const int32_t* __restrict__ policy, const double* __restrict__ demand,
-                                                        const SimSampler* __restrict__ samp, const double* __restrict__ thr,
-                                                        double* __restrict__ partial, double* __restrict__ out_sum) {
+// One period of the backorder family from inventory x under order a and demand d: immediateValue and the clamped
+// stateTransition (decode_state / action_setup / cell of sdp_device.hpp; CLSP.java:255-272), one operation per statement.
+struct F1SimPeriod {
+  double imm, level;  // the period's cost, and the next inventory clamped into the instance's bounds
+};
+__device__ __forceinline__ F1SimPeriod f1_sim_period(const SimInst& I, double x, double a, double d) {
+  const double fixed = a > 0 ? I.K : 0.0;
+  const double var = I.v * a;
+  const double fv = fixed + var;
+  const double base = x + a;
+  const double level = base - d;
+  const double hold = I.h * fmax(level, 0.0);
+  const double pen = I.pi * fmax(-level, 0.0);
+  const double imm = fv + hold + pen;
+  double nx = level;
+  nx = nx > I.max_inventory ? I.max_inventory : nx;
+  nx = nx < I.min_inventory ? I.min_inventory : nx;
+  return F1SimPeriod{imm, nx};
+}
+
+// The table rule: the order is the policy row's entry at the state's grid index.  The state is SNAPPED to the grid every
+// period -- the index of the carried level truncated toward zero, the period then starts from min + idx * step --, as a
+// handle's rollout does.
+struct TableRule {
+  const int32_t* __restrict__ policy;
+  __device__ __forceinline__ const int32_t* rows(const SimLaunch&, const SimInst& I, int) const { return policy + I.pol_base; }
+  __device__ __forceinline__ double act(const SimLaunch& L, const SimInst& I, const int32_t* __restrict__ pol, int t, double* x) const {
+    int idx = (int)((*x - I.min_inventory) * L.inv_step);  // (inv_step is exact; of a start state: the host's division by step)
+    idx = idx < 0 ? 0 : (idx >= I.n_states ? I.n_states - 1 : idx);  // (a NaN demand must not leave the policy row)
+    *x = I.min_inventory + (double)idx * L.step;
+    return (double)pol[(int64_t)t * I.n_states + idx] * L.step;
+  }
+};
+
+// One demand path per lane under RULE (TableRule above, LevelRule<1 | 2 | 3> of sdp_fitss.hpp).  The body carries x -- the
+// start inventory, then each period's clamped level --; rule.rows gives what the rule reads of instance i, rule.act the
+// period's order, and may move x to the inventory the period is evaluated at.
+template <class RULE, bool SAMPLED>
+__global__ __launch_bounds__(256) void batch_sim_kernel(SimLaunch L, const SimInst* __restrict__ inst, const double* __restrict__ ini_x,
+                                                        RULE rule, const double* __restrict__ demand, const SimSampler* __restrict__ samp,
+                                                        const double* __restrict__ thr, double* __restrict__ partial,
+                                                        double* __restrict__ out_sum) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
@@ -58,11 +99,12 @@ __global__ __launch_bounds__(256) void batch_sim_kernel(SimLaunch L, const SimIn
   const int i = (int)(gw / L.waves_per_inst);              // (wave-uniform)
   const int w = (int)(gw - (int64_t)i * L.waves_per_inst);
   const int p = w * 64 + lane;
+  const int n_paths = (int)L.R.n_paths;
   const SimInst I = inst[i];
   double sum = 0.0;
-  if (p < L.n_paths) {
-    int idx = ini_idx[i];
-    const int32_t* __restrict__ pol = policy + I.pol_base;
+  if (p < n_paths) {
+    double x = ini_x[i];
+    const auto rows = rule.rows(L, I, i);
     const double* __restrict__ dem = SAMPLED ? nullptr : demand + (int64_t)i * L.demand_stride + (int64_t)p * L.T;
     for (int t = 0; t < L.T; ++t) {
       double d;
@@ -72,33 +114,15 @@ __global__ __launch_bounds__(256) void batch_sim_kernel(SimLaunch L, const SimIn
       } else {
         d = dem[t];
       }
-      // decode_state / action_setup / cell of the backorder family (sdp_device.hpp; CLSP.java:255-272)
-      const double x = I.min_inventory + (double)idx * L.step;
-      const int k = pol[(int64_t)t * I.n_states + idx];
-      const double a = (double)k * L.step;
-      const double fixed = a > 0 ? I.K : 0.0;
-      const double var = I.v * a;
-      const double fv = fixed + var;
-      const double base = x + a;
-      const double level = base - d;
-      const double hold = I.h * fmax(level, 0.0);
-      const double pen = I.pi * fmax(-level, 0.0);
-      const double imm = fv + hold + pen;
-      sum += imm;
-      if (t + 1 < L.T) {
-        double nx = level;
-        nx = nx > I.max_inventory ? I.max_inventory : nx;
-        nx = nx < I.min_inventory ? I.min_inventory : nx;
-        idx = (int)((nx - I.min_inventory) * L.inv_step);
-        idx = idx < 0 ? 0 : (idx >= I.n_states ? I.n_states - 1 : idx);  // (a NaN demand must not leave the policy row)
-      }
+      const double a = rule.act(L, I, rows, t, &x);
+      const F1SimPeriod s = f1_sim_period(I, x, a, d);
+      sum += s.imm;
+      x = s.level;
     }
-    if (out_sum) out_sum[(int64_t)i * L.n_paths + p] = sum;
+    if (out_sum) out_sum[(int64_t)i * n_paths + p] = sum;
   }
-  // wave total in a fixed order (lanes past n_paths hold 0.0); every lane ends with the same bits
-  double tot = sum;
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) tot += __shfl_xor(tot, s, 64);
+  // wave total in a fixed order (lanes past n_paths hold 0.0)
+  const double tot = sim_wave_sum(sum);
   if (lane == 0) partial[gw] = tot;
 }
 
@@ -117,7 +141,7 @@ __global__ __launch_bounds__(256) void batch_sim_draw_kernel(SimLaunch L, int in
                                                              const double* __restrict__ thr, double* __restrict__ out_demand,
                                                              double* __restrict__ out_u) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (p >= L.n_paths) return;
+  if (p >= (int64_t)L.R.n_paths) return;
   for (int t = 0; t < L.T; ++t) {
     double u;
     const double d = sim_draw(L, samp[(int64_t)inst * L.T + t], thr, inst, t, (uint32_t)p, &u);

@@ -13,10 +13,9 @@
 //     code (bit-for-bit equality is by construction, not by care);
 //   * minSquare (:69-98) is the closed form of the one-variable problem the reference hands to CPLEX: the mean of
 //     the terms x_i + Q_i, clamped to [lb, 10000].  With step 1 every term is an integer far below 2^53, the fp64 sum exact;
-//   * the rollout carries the state as a DOUBLE (a fitted S may be fractional), needs no policy row and gathers nothing per
-//     step; one path per lane, a wave's 64 paths belong to one instance, demands / sampler / wave butterfly / mean are those
-//     of batch_sim_kernel (sdp_batch_sim.hpp), so the same (seed, position, n) rolls the rule along the SAME demand paths
-//     as the table policy.
+//   * the rollout is batch_sim_kernel (sdp_batch_sim.hpp) under LevelRule below: the state stays the DOUBLE it is (a fitted S
+//     may be fractional), the rule needs no policy row and gathers nothing per step; everything else of a path is the table
+//     rollout's, so the same (seed, position, n) rolls the rule along the SAME demand paths as the table policy.
 //
 // Global memory is written with ordinary vector stores from plain C++ only.
 #pragma once
@@ -205,87 +204,28 @@ __global__ __launch_bounds__(256) void batch_fit_ss_kernel(const FitPair* __rest
 
 // ---- device: the rollout of a level rule ----
 
-struct SsInst {
-  double h, pi, K, v;
-  double min_inventory, max_inventory;
-  double maxq;
-};
-
 __device__ __forceinline__ double ss_capped(double maxq, double want) { return maxq <= want ? maxq : want; }  // Math.min
 
-// SimulateFitsS.simulateSinglesS / TwosS / ThreesS (SimulateFitsS.java:32-130) for every instance: ss[(i * T + t) * 2 * LEVELS ...].
-template <int LEVELS, bool SAMPLED>
-__global__ __launch_bounds__(256) void batch_ss_sim_kernel(SimLaunch L, const SsInst* __restrict__ inst, const double* __restrict__ ini_x,
-                                                           const double* __restrict__ ss, const double* __restrict__ demand,
-                                                           const SimSampler* __restrict__ samp, const double* __restrict__ thr,
-                                                           double* __restrict__ partial, double* __restrict__ out_sum) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
-  if (gw >= (int64_t)L.n_inst * L.waves_per_inst) return;  // no workgroup barrier below: a wave may leave on its own
-  const int i = (int)(gw / L.waves_per_inst);              // (wave-uniform)
-  const int w = (int)(gw - (int64_t)i * L.waves_per_inst);
-  const int p = w * 64 + lane;
-  const SsInst I = inst[i];
-  double sum = 0.0;
-  if (p < L.n_paths) {
-    const double ini = ini_x[i];
-    double x = ini;
-    const double* __restrict__ rule = ss + (int64_t)i * L.T * (2 * LEVELS);
-    const double* __restrict__ dem = SAMPLED ? nullptr : demand + (int64_t)i * L.demand_stride + (int64_t)p * L.T;
-    for (int t = 0; t < L.T; ++t) {
-      double d;
-      if constexpr (SAMPLED) {
-        double u;
-        d = sim_draw(L, samp[(int64_t)i * L.T + t], thr, i, t, (uint32_t)p, &u);
-      } else {
-        d = dem[t];
-      }
-      const double* __restrict__ o = rule + (int64_t)t * (2 * LEVELS);
-      double a;
-      if (t == 0) {
-        a = o[1] - ini;  // (not capped: SimulateFitsS.java:43)
-      } else if constexpr (LEVELS == 1) {
-        a = x >= o[0] ? 0.0 : ss_capped(I.maxq, o[1] - x);
-      } else if constexpr (LEVELS == 2) {
-        if (x < o[0])
-          a = ss_capped(I.maxq, o[1] - x);
-        else if (o[0] <= x && x < o[2])
-          a = ss_capped(I.maxq, o[3] - x);
-        else
-          a = 0.0;
-      } else {
-        if (x < o[0])
-          a = ss_capped(I.maxq, o[1] - x);
-        else if (o[0] <= x && x < o[2])
-          a = ss_capped(I.maxq, o[3] - x);
-        else if (o[2] <= x && x < o[4])
-          a = ss_capped(I.maxq, o[5] - x);
-        else
-          a = 0.0;
-      }
-      // immediateValue / stateTransition of the backorder family, the statements of batch_sim_kernel
-      const double fixed = a > 0 ? I.K : 0.0;
-      const double var = I.v * a;
-      const double fv = fixed + var;
-      const double base = x + a;
-      const double level = base - d;
-      const double hold = I.h * fmax(level, 0.0);
-      const double pen = I.pi * fmax(-level, 0.0);
-      const double imm = fv + hold + pen;
-      sum += imm;
-      double nx = level;
-      nx = nx > I.max_inventory ? I.max_inventory : nx;
-      nx = nx < I.min_inventory ? I.min_inventory : nx;
-      x = nx;
+// SimulateFitsS.simulateSinglesS / TwosS / ThreesS (SimulateFitsS.java:32-130): ss[(i * T + t) * 2 * LEVELS ...].  The period
+// starts from the carried level itself, NOT snapped to the grid.
+template <int LEVELS>
+struct LevelRule {
+  const double* __restrict__ ss;
+  __device__ __forceinline__ const double* rows(const SimLaunch& L, const SimInst&, int i) const { return ss + (int64_t)i * L.T * (2 * LEVELS); }
+  __device__ __forceinline__ double act(const SimLaunch&, const SimInst& I, const double* __restrict__ rule, int t, double* x_kept) const {
+    const double* __restrict__ o = rule + (int64_t)t * (2 * LEVELS);
+    const double x = *x_kept;
+    if (t == 0) return o[1] - x;  // (x is the start state; not capped: SimulateFitsS.java:43)
+    if constexpr (LEVELS == 1) {
+      return x >= o[0] ? 0.0 : ss_capped(I.maxq, o[1] - x);
+    } else {
+      if (x < o[0]) return ss_capped(I.maxq, o[1] - x);
+      if (o[0] <= x && x < o[2]) return ss_capped(I.maxq, o[3] - x);
+      if constexpr (LEVELS == 3)
+        if (o[2] <= x && x < o[4]) return ss_capped(I.maxq, o[5] - x);
+      return 0.0;
     }
-    if (out_sum) out_sum[(int64_t)i * L.n_paths + p] = sum;
   }
-  // wave total in a fixed order (lanes past n_paths hold 0.0); every lane ends with the same bits
-  double tot = sum;
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) tot += __shfl_xor(tot, s, 64);
-  if (lane == 0) partial[gw] = tot;
-}
+};
 
 }  // namespace sdp

@@ -1,7 +1,8 @@
 // sdp_sampler.hpp -- the device sampler of the simulation kernels ("Batched simulation" and "Sampled simulation on a
 // handle"): Philox4x32-10, the keyed bijection sigma of the latin hypercube's shuffle, the two streams of uniforms and the
-// demand of a uniform by binary search in a host-made threshold table.  Shared by batch_sim_kernel (sdp_batch_sim.hpp) and
-// sim_sampled_kernel (sdp_sim_sampled.hpp): device functions only, no kernels.
+// demand of a uniform by binary search in a host-made threshold table -- and the wave total every rollout ends with.  Shared
+// by batch_sim_kernel (sdp_batch_sim.hpp) and sim_sampled_kernel (sdp_sim_sampled.hpp): records and device functions only, no
+// kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,14 @@ struct SimSampler {
   // >= 0: the demand is the q-th VALUE of a table at this element offset of the value arena (a handle's pmf tile may have
   // gaps and a step other than 1: sdpgpu_simulate_sampled); -1: the demand is k_lo + q (specs, and every table of a batch)
   int64_t val_off;
+};
+
+// what identifies the stream of uniforms of one call (host: make_stream, sdpgpu_sim_host.hpp)
+struct SimStream {
+  uint64_t first_path;  // RANDOM mode: 64-bit index of the call's path 0
+  uint32_t n_paths;
+  uint32_t seed_lo, seed_hi;
+  int32_t half_bits;    // LHS mode: sigma's half width (smallest h >= 1 with 4^h >= n_paths)
 };
 
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11)
@@ -105,6 +114,13 @@ __device__ __forceinline__ double sim_demand(const SimSampler& S, const double* 
   }
   if (S.val_off >= 0) return val[S.val_off + (lo < S.m ? lo : S.m - 1)];
   return (double)(S.k_lo + lo);
+}
+
+// wave total by xor butterfly: every lane ends with the same bits
+__device__ __forceinline__ double sim_wave_sum(double v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+  return v;
 }
 
 }  // namespace sdp

@@ -22,27 +22,12 @@
 
 namespace sdp {
 
-// what identifies the stream of uniforms of one call
-struct SimStream {
-  uint64_t first_path;  // RANDOM mode: 64-bit index of the call's path 0
-  uint32_t n_paths;
-  uint32_t seed_lo, seed_hi;
-  int32_t half_bits;    // LHS mode: sigma's half width (smallest h >= 1 with 4^h >= n_paths)
-};
-
 template <bool RANDOM>
 __device__ __forceinline__ double sim_stream_uniform(const SimStream& R, int t, uint32_t p) {
   if constexpr (RANDOM)
     return sim_uniform_random(R.seed_lo, R.seed_hi, t, R.first_path + (uint64_t)p);
   else
     return sim_uniform_lhs(R.n_paths, R.half_bits, R.seed_lo, R.seed_hi, 0, t, p);
-}
-
-// wave total by xor butterfly: every lane ends with the same bits
-__device__ __forceinline__ double sim_wave_sum(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
 }
 
 // counts[0] paths with bit 0 of the flags (valid), counts[1] with bit 1 (a demand was lost): integer atomics, one per wave

@@ -5,7 +5,7 @@
 // window_f1_batch_kernel (sdp_batch.hpp); this file holds the validation, the host layout with its prefix-sum arenas, the
 // plan of a period, the task table, the launcher and the entry points.  Separate from sdpgpu_handle on purpose: a batch has no
 // slabs, no exchange, no user functors -- and the handle does not grow.
-#include "sdpgpu_internal.hpp"
+#include "sdpgpu_sim_host.hpp"
 #include "sdp_batch.hpp"
 #include "sdp_batch_sim.hpp"
 #include "sdp_fitss.hpp"
@@ -65,29 +65,22 @@ struct sdpgpu_batch {
   bool timed = false, periods_timed = false;
   int32_t period_launches = 0, finalize_launches = 0, periods_run = 0;
   // ---- simulation (sdp_batch_sim.hpp) ----
-  std::vector<char> samp_spec_set;             // [i * T + t]: 1 = a distribution spec, 0 = the pmf tile
-  std::vector<int32_t> samp_klo, samp_strict;  // of the spec tables
-  std::vector<std::vector<double>> samp_thr;
+  sdpgpu_detail::SamplerSpecs samp;  // [i * T + t]: a distribution spec, or none = the pmf tile
   bool samp_dirty = true;
   sdp::SimSampler* d_samp = nullptr;
   double* d_thr = nullptr;
-  sdp::SimInst* d_sim_inst = nullptr;
-  char* d_sim_scratch = nullptr;  // grow-only: start indices, wave partials, means, path sums, demands
+  sdp::SimInst* d_sim_inst = nullptr;  // [i], for the table rule and the level rules alike
+  char* d_sim_scratch = nullptr;  // grow-only: start states, wave partials, means, path sums, an explicit rule, demands
   size_t sim_scratch_bytes = 0;
   hipEvent_t sim_ev0 = nullptr, sim_ev1 = nullptr;
   bool sim_timed = false;
   // ---- (s, S) level rules (sdp_fitss.hpp) ----
   sdp::FitPair* d_fit_pairs = nullptr;  // [i * T + t]: the reachable slice of every (instance, period)
   double* d_fit = nullptr;              // the last device fit, N x T x 2*levels (sized for three levels)
-  sdp::SsInst* d_ss_inst = nullptr;
   std::string err;
 };
 
-namespace {
-
-using namespace sdpgpu_detail;
-
-int bfail(sdpgpu_batch* b, int code, const char* fmt, ...) {
+int sdpgpu_detail::bfail(sdpgpu_batch* b, int code, const char* fmt, ...) {
   char buf[640];
   va_list ap;
   va_start(ap, fmt);
@@ -100,43 +93,15 @@ int bfail(sdpgpu_batch* b, int code, const char* fmt, ...) {
   return code;
 }
 
+namespace {
+
+using namespace sdpgpu_detail;
+
 #define BHIP_TRY(b, expr)                                                                              \
   do {                                                                                                 \
     hipError_t e_ = (expr);                                                                            \
     if (e_ != hipSuccess) return bfail(b, SDPGPU_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
-
-// No C++ exception crosses the C ABI: the same barrier as the two-product entry points (sdpgpu_sparse.hip).
-template <class F>
-int guarded(sdpgpu_batch* b, const char* who, F&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return bfail(b, SDPGPU_ERR_ALLOC, "%s: host allocation failed (std::bad_alloc)", who);
-  } catch (const std::exception& e) {
-    return bfail(b, SDPGPU_ERR_INTERNAL, "%s: internal error: %s", who, e.what());
-  } catch (...) {
-    return bfail(b, SDPGPU_ERR_INTERNAL, "%s: internal error (unknown exception)", who);
-  }
-}
-
-// The batch's device for the length of a call; the caller's current device comes back at the end.
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t enter(int device) {
-    if (device < 0) return hipSuccess;
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess) return e;
-    if (prev == device) return hipSuccess;
-    e = hipSetDevice(device);
-    switched = e == hipSuccess;
-    return e;
-  }
-  ~DeviceScope() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-};
 
 inline int rup(int v, int r) { return (v + r - 1) / r * r; }
 
@@ -361,11 +326,7 @@ int allocate(sdpgpu_batch* b) {
   if (b->allocated) return SDPGPU_OK;
   int rc = layout(b);
   if (rc) return rc;
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev < 1)
-    return bfail(b, SDPGPU_ERR_DEVICE, "no HIP device available (%s); this library has no CPU path",
-                 e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+  if ((rc = no_device(b, nullptr))) return rc;
   if (!b->stream && !b->stream_given) {
     BHIP_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
     b->own_stream = true;
@@ -491,7 +452,7 @@ int batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out, bool r
   if (!descs || !out) return bfail(nullptr, SDPGPU_ERR_ARG, "batch_create: null argument (descs, out)");
   *out = nullptr;
   if (n < 1 || n > 1000000) return bfail(nullptr, SDPGPU_ERR_ARG, "batch_create: n = %d instances (1 .. 1000000)", n);
-  return guarded(nullptr, "sdpgpu_batch_create", [&]() -> int {
+  return guarded((sdpgpu_batch*)nullptr, "sdpgpu_batch_create", [&]() -> int {
     for (int32_t k = 0; k < n; ++k) {
       const sdpgpu_desc& d = descs[k];
       int rc = validate(d);
@@ -555,10 +516,7 @@ int batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out, bool r
       b->d0.assign((size_t)n * b->T, 0.0);
       b->pmf_p.resize((size_t)n * b->T);
       b->pmf_set.assign((size_t)n * b->T, 0);
-      b->samp_spec_set.assign((size_t)n * b->T, 0);
-      b->samp_klo.assign((size_t)n * b->T, 0);
-      b->samp_strict.assign((size_t)n * b->T, 0);
-      b->samp_thr.resize((size_t)n * b->T);
+      b->samp.resize((size_t)n * b->T);
       if (const char* e = std::getenv("SDPGPU_WIN_R")) b->win_r = std::atoi(e);
       if (const char* e = std::getenv("SDPGPU_WIN_NCH")) b->win_nch = std::atoi(e);
       if (const char* e = std::getenv("SDPGPU_WIN_S")) b->win_s = std::atoi(e);
@@ -641,7 +599,6 @@ void sdpgpu_batch_destroy(sdpgpu_batch* b) {
     if (b->d_sim_scratch) (void)hipFree(b->d_sim_scratch);
     if (b->d_fit_pairs) (void)hipFree(b->d_fit_pairs);
     if (b->d_fit) (void)hipFree(b->d_fit);
-    if (b->d_ss_inst) (void)hipFree(b->d_ss_inst);
     if (b->sim_ev0) (void)hipEventDestroy(b->sim_ev0);
     if (b->sim_ev1) (void)hipEventDestroy(b->sim_ev1);
     if (b->stream && b->own_stream) (void)hipStreamDestroy(b->stream);
@@ -870,11 +827,9 @@ double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period) {
 }  // extern "C"
 
 // =================================================================================================
-// Batched simulation (sdp_batch_sim.hpp)
+// Batched simulation (sdp_batch_sim.hpp): the samplers and what every rollout checks (the rollouts end the file)
 // =================================================================================================
 namespace {
-
-constexpr int32_t kSimMaxPaths = 1 << 24;
 
 // sampler records + threshold arena on the device (spec tables as set; tile tables = the running sum of the tile)
 int sim_upload_samplers(sdpgpu_batch* b) {
@@ -883,25 +838,17 @@ int sim_upload_samplers(sdpgpu_batch* b) {
   std::vector<sdp::SimSampler> rec(NT);
   std::vector<double> arena;
   for (size_t k = 0; k < NT; ++k) {
+    if (b->samp.has(k)) {
+      rec[k] = b->samp.append(k, &arena);
+      continue;
+    }
     sdp::SimSampler S{};
     S.off = (int64_t)arena.size();
     S.val_off = -1;  // demand = k_lo + q (validate: step 1 and a gapless tile)
-    if (b->samp_spec_set[k]) {
-      S.k_lo = b->samp_klo[k];
-      S.strict = b->samp_strict[k];
-      S.m = (int32_t)b->samp_thr[k].size();
-      arena.insert(arena.end(), b->samp_thr[k].begin(), b->samp_thr[k].end());
-    } else {
-      const std::vector<double>& p = b->pmf_p[k];
-      S.k_lo = (int32_t)b->d0[k];
-      S.strict = 0;
-      S.m = (int32_t)p.size();
-      double s = 0.0;
-      for (size_t j = 0; j < p.size(); ++j) {
-        s += p[j];
-        arena.push_back(j + 1 == p.size() ? HUGE_VAL : s);
-      }
-    }
+    S.k_lo = (int32_t)b->d0[k];
+    S.strict = 0;
+    S.m = (int32_t)b->pmf_p[k].size();
+    append_tile_thresholds(b->pmf_p[k], &arena);
     rec[k] = S;
   }
   if (b->d_samp) (void)hipFree(b->d_samp);
@@ -916,19 +863,6 @@ int sim_upload_samplers(sdpgpu_batch* b) {
   return SDPGPU_OK;
 }
 
-int sim_scratch(sdpgpu_batch* b, size_t bytes) {
-  if (bytes <= b->sim_scratch_bytes && b->d_sim_scratch) return SDPGPU_OK;
-  if (b->d_sim_scratch) {
-    BHIP_TRY(b, hipStreamSynchronize(b->stream));
-    (void)hipFree(b->d_sim_scratch);
-    b->d_sim_scratch = nullptr;
-    b->sim_scratch_bytes = 0;
-  }
-  BHIP_TRY(b, hipMalloc((void**)&b->d_sim_scratch, bytes));
-  b->sim_scratch_bytes = bytes;
-  return SDPGPU_OK;
-}
-
 sdp::SimLaunch sim_launch_params(const sdpgpu_batch* b, int32_t n_paths, uint64_t seed, int64_t stride) {
   sdp::SimLaunch L{};
   const sdpgpu_desc& d = b->d[0];
@@ -936,14 +870,9 @@ sdp::SimLaunch sim_launch_params(const sdpgpu_batch* b, int32_t n_paths, uint64_
   L.inv_step = 1.0 / d.step;  // exact: step is a power of two (validate)
   L.T = b->T;
   L.n_inst = b->N;
-  L.n_paths = n_paths;
   L.waves_per_inst = (n_paths + 63) / 64;
-  int h = 1;
-  while (((int64_t)1 << (2 * h)) < (int64_t)n_paths) ++h;
-  L.half_bits = h;
   L.demand_stride = stride;
-  L.seed_lo = (uint32_t)(seed & 0xffffffffu);
-  L.seed_hi = (uint32_t)(seed >> 32);
+  L.R = make_stream(n_paths, seed, 0);
   return L;
 }
 
@@ -960,8 +889,7 @@ int sim_check_args(sdpgpu_batch* b, const char* who, int32_t n_paths, const doub
                    const double* out_mean, std::vector<double>* ini) {
   const int N = b->N, T = b->T;
   if (!out_mean) return bfail(b, SDPGPU_ERR_ARG, "%s: out_mean is null", who);
-  if (n_paths <= 0) return bfail(b, SDPGPU_ERR_ARG, "%s: n_paths = %d (1 .. %d)", who, n_paths, kSimMaxPaths);
-  if (n_paths > kSimMaxPaths) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: n_paths = %d exceeds %d", who, n_paths, kSimMaxPaths);
+  if (const int rc = check_n_paths(b, who, n_paths)) return rc;
   if (!sampled) {
     if (!demand) return bfail(b, SDPGPU_ERR_ARG, "%s: demand is null", who);
     if (stride != 0 && stride < (int64_t)n_paths * T)
@@ -979,96 +907,9 @@ int sim_check_args(sdpgpu_batch* b, const char* who, int32_t n_paths, const doub
   return sampled ? sim_needs_unit_step(b, who) : SDPGPU_OK;
 }
 
-int sim_run(sdpgpu_batch* b, const char* who, int32_t n_paths, const double* demand, int64_t stride, bool sampled, uint64_t seed,
-            const double* ini_x, double* out_mean, double* out_sum) {
-  const int N = b->N, T = b->T;
-  std::vector<double> ini_inv;
-  int rc0 = sim_check_args(b, who, n_paths, demand, stride, sampled, ini_x, out_mean, &ini_inv);
-  if (rc0) return rc0;
-  std::vector<int32_t> ini((size_t)N);
-  for (int i = 0; i < N; ++i) ini[(size_t)i] = (int32_t)((ini_inv[(size_t)i] - b->d[(size_t)i].min_inventory) / b->d[(size_t)i].step);
-  if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
-  const int64_t wpi = (n_paths + 63) / 64;
-  const int64_t waves = (int64_t)N * wpi;
-  if (!grid_ok((waves + 3) / 4) || (double)N * n_paths > 2.0e9)
-    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: %d instances x %d paths are too many for one launch", who, N, n_paths);
-
-  DeviceScope dev;
-  BHIP_TRY(b, dev.enter(b->device));
-  if (!b->d_sim_inst) {
-    std::vector<sdp::SimInst> inst((size_t)N);
-    for (int i = 0; i < N; ++i) {
-      const sdpgpu_desc& d = b->d[(size_t)i];
-      inst[(size_t)i] = sdp::SimInst{d.holding_cost, d.penalty_cost, d.fixed_order_cost, d.unit_order_cost, d.min_inventory,
-                                     d.max_inventory, (int64_t)policy_row(b, i, 0), b->nxs[(size_t)i], 0};
-    }
-    BHIP_TRY(b, hipMalloc((void**)&b->d_sim_inst, inst.size() * sizeof(sdp::SimInst)));
-    BHIP_TRY(b, hipMemcpy(b->d_sim_inst, inst.data(), inst.size() * sizeof(sdp::SimInst), hipMemcpyHostToDevice));
-  }
-  if (!b->sim_ev0) {
-    BHIP_TRY(b, hipEventCreate(&b->sim_ev0));
-    BHIP_TRY(b, hipEventCreate(&b->sim_ev1));
-  }
-  if (sampled) {
-    int rc = sim_upload_samplers(b);
-    if (rc) return rc;
-  }
-  // scratch: [ini N x i32, padded to 8] [partials] [means] [sums] [demands]
-  auto up8 = [](size_t v) { return (v + 7) / 8 * 8; };
-  const size_t o_ini = 0, o_part = up8((size_t)N * 4), o_mean = o_part + (size_t)waves * 8, o_sum = o_mean + (size_t)N * 8;
-  const size_t sum_bytes = out_sum ? (size_t)N * n_paths * 8 : 0;
-  const size_t o_dem = o_sum + sum_bytes;
-  const size_t dem_elems = sampled ? 0 : (stride == 0 ? (size_t)n_paths * T : (size_t)(N - 1) * (size_t)stride + (size_t)n_paths * T);
-  int rc = sim_scratch(b, o_dem + dem_elems * 8);
-  if (rc) return rc;
-  char* base = b->d_sim_scratch;
-  int32_t* d_ini = reinterpret_cast<int32_t*>(base + o_ini);
-  double* d_part = reinterpret_cast<double*>(base + o_part);
-  double* d_mean = reinterpret_cast<double*>(base + o_mean);
-  double* d_sum = out_sum ? reinterpret_cast<double*>(base + o_sum) : nullptr;
-  double* d_dem = sampled ? nullptr : reinterpret_cast<double*>(base + o_dem);
-  BHIP_TRY(b, hipMemcpyAsync(d_ini, ini.data(), (size_t)N * 4, hipMemcpyHostToDevice, b->stream));
-  if (!sampled) BHIP_TRY(b, hipMemcpyAsync(d_dem, demand, dem_elems * 8, hipMemcpyHostToDevice, b->stream));
-  const sdp::SimLaunch L = sim_launch_params(b, n_paths, seed, stride);
-  const dim3 grid((unsigned)((waves + 3) / 4));
-  BHIP_TRY(b, hipEventRecord(b->sim_ev0, b->stream));
-  if (sampled)
-    hipLaunchKernelGGL((sdp::batch_sim_kernel<true>), grid, dim3(256), 0, b->stream, L, b->d_sim_inst, d_ini, b->d_policy, nullptr, b->d_samp,
-                       b->d_thr, d_part, d_sum);
-  else
-    hipLaunchKernelGGL((sdp::batch_sim_kernel<false>), grid, dim3(256), 0, b->stream, L, b->d_sim_inst, d_ini, b->d_policy, d_dem, nullptr,
-                       nullptr, d_part, d_sum);
-  BHIP_TRY(b, hipGetLastError());
-  hipLaunchKernelGGL(sdp::batch_sim_mean_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, d_part, N, (int)wpi, n_paths, d_mean);
-  BHIP_TRY(b, hipGetLastError());
-  BHIP_TRY(b, hipEventRecord(b->sim_ev1, b->stream));
-  b->sim_timed = true;
-  BHIP_TRY(b, hipMemcpyAsync(out_mean, d_mean, (size_t)N * 8, hipMemcpyDeviceToHost, b->stream));
-  if (out_sum) BHIP_TRY(b, hipMemcpyAsync(out_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost, b->stream));
-  BHIP_TRY(b, hipStreamSynchronize(b->stream));
-  return SDPGPU_OK;
-}
-
 }  // namespace
 
 extern "C" {
-
-int sdpgpu_batch_simulate(sdpgpu_batch* b, int32_t n_paths, const double* demand, int64_t instance_stride, const double* ini_x,
-                          double* out_mean, double* out_sum) {
-  if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  return guarded(b, "sdpgpu_batch_simulate", [&]() -> int {
-    return sim_run(b, "sdpgpu_batch_simulate", n_paths, demand, instance_stride, false, 0, ini_x, out_mean, out_sum);
-  });
-}
-
-int sdpgpu_batch_simulate_sampled(sdpgpu_batch* b, int32_t n_paths, uint64_t seed, const double* ini_x, double* out_mean, double* out_sum) {
-  if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  return guarded(b, "sdpgpu_batch_simulate_sampled", [&]() -> int {
-    return sim_run(b, "sdpgpu_batch_simulate_sampled", n_paths, nullptr, 0, true, seed, ini_x, out_mean, out_sum);
-  });
-}
 
 int sdpgpu_batch_set_sampler(sdpgpu_batch* b, int32_t instance, int32_t t, const sdpgpu_dist_spec* spec) {
   if (!b) return SDPGPU_ERR_ARG;
@@ -1080,20 +921,12 @@ int sdpgpu_batch_set_sampler(sdpgpu_batch* b, int32_t instance, int32_t t, const
     if (rc) return rc;
     const size_t k = (size_t)instance * b->T + t;
     if (!spec) {
-      b->samp_spec_set[k] = 0;
-      b->samp_thr[k].clear();
-      b->samp_dirty = true;
-      return SDPGPU_OK;
+      b->samp.clear(k);
+    } else {
+      std::string why;
+      rc = b->samp.set(k, *spec, &why);
+      if (rc) return bfail(b, rc, "batch_set_sampler: instance %d, period %d: spec: %s", instance, t + 1, why.c_str());
     }
-    std::vector<double> thr;
-    std::string why;
-    int32_t k_lo = 0, strict = 0;
-    rc = sample_table_build(*spec, &k_lo, &thr, &strict, &why);
-    if (rc) return bfail(b, rc, "batch_set_sampler: instance %d, period %d: spec: %s", instance, t + 1, why.c_str());
-    b->samp_thr[k].swap(thr);
-    b->samp_klo[k] = k_lo;
-    b->samp_strict[k] = strict;
-    b->samp_spec_set[k] = 1;
     b->samp_dirty = true;
     return SDPGPU_OK;
   });
@@ -1106,9 +939,9 @@ int sdpgpu_batch_sample_demands(sdpgpu_batch* b, int32_t instance, int32_t n_pat
     const char* who = "sdpgpu_batch_sample_demands";
     if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, b->N - 1);
     if (!out_demand) return bfail(b, SDPGPU_ERR_ARG, "%s: out_demand is null", who);
-    if (n_paths <= 0) return bfail(b, SDPGPU_ERR_ARG, "%s: n_paths = %d (1 .. %d)", who, n_paths, kSimMaxPaths);
-    if (n_paths > kSimMaxPaths) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: n_paths = %d exceeds %d", who, n_paths, kSimMaxPaths);
-    int rc = sim_needs_unit_step(b, who);
+    int rc = check_n_paths(b, who, n_paths);
+    if (rc) return rc;
+    rc = sim_needs_unit_step(b, who);
     if (rc) return rc;
     rc = layout(b);  // (every pmf set: the tile samplers read them)
     if (rc) return rc;
@@ -1119,10 +952,12 @@ int sdpgpu_batch_sample_demands(sdpgpu_batch* b, int32_t instance, int32_t n_pat
     rc = sim_upload_samplers(b);
     if (rc) return rc;
     const size_t elems = (size_t)n_paths * b->T;
-    rc = sim_scratch(b, elems * 8 * (out_u ? 2 : 1));
+    Carve c;
+    const size_t o_dem = c.take(elems * 8), o_u = c.take(out_u ? elems * 8 : 0);
+    rc = sim_scratch(b, c.at);
     if (rc) return rc;
-    double* d_dem = reinterpret_cast<double*>(b->d_sim_scratch);
-    double* d_u = out_u ? d_dem + elems : nullptr;
+    double* d_dem = reinterpret_cast<double*>(b->d_sim_scratch + o_dem);
+    double* d_u = out_u ? reinterpret_cast<double*>(b->d_sim_scratch + o_u) : nullptr;
     const sdp::SimLaunch L = sim_launch_params(b, n_paths, seed, 0);
     hipLaunchKernelGGL(sdp::batch_sim_draw_kernel, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, b->stream, L, (int)instance, b->d_samp,
                        b->d_thr, d_dem, d_u);
@@ -1152,7 +987,7 @@ double sdpgpu_batch_simulate_ms(sdpgpu_batch* b) {
 }  // extern "C"
 
 // =================================================================================================
-// (s, S) level rules: fit from the policy tables, roll out (sdp_fitss.hpp)
+// (s, S) level rules: fit from the policy tables (sdp_fitss.hpp)
 // =================================================================================================
 namespace {
 
@@ -1247,97 +1082,6 @@ int fit_launch(sdpgpu_batch* b, const char* who, int32_t levels) {
   return SDPGPU_OK;
 }
 
-template <int LEVELS>
-void ss_sim_launch(sdpgpu_batch* b, bool sampled, dim3 grid, const sdp::SimLaunch& L, const double* d_ini, const double* d_ss, const double* d_dem,
-                   double* d_part, double* d_sum) {
-  if (sampled)
-    hipLaunchKernelGGL((sdp::batch_ss_sim_kernel<LEVELS, true>), grid, dim3(256), 0, b->stream, L, b->d_ss_inst, d_ini, d_ss, nullptr, b->d_samp,
-                       b->d_thr, d_part, d_sum);
-  else
-    hipLaunchKernelGGL((sdp::batch_ss_sim_kernel<LEVELS, false>), grid, dim3(256), 0, b->stream, L, b->d_ss_inst, d_ini, d_ss, d_dem, nullptr,
-                       nullptr, d_part, d_sum);
-}
-
-int ss_sim_run(sdpgpu_batch* b, const char* who, int32_t levels, const double* ss, int32_t n_paths, const double* demand, int64_t stride,
-               bool sampled, uint64_t seed, const double* ini_x, double* out_mean, double* out_sum) {
-  const int N = b->N, T = b->T;
-  if (levels < 1 || levels > 3) return bfail(b, SDPGPU_ERR_ARG, "%s: levels = %d (1, 2 or 3: simulateSinglesS, simulateTwosS, simulateThreesS)", who, levels);
-  std::vector<double> ini;
-  int rc = sim_check_args(b, who, n_paths, demand, stride, sampled, ini_x, out_mean, &ini);
-  if (rc) return rc;
-  if (!ss) {  // fit first, in this call
-    if ((rc = fit_needs_unit_step(b, who))) return rc;
-    if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s: ss = NULL fits the rule from the policy tables: before sdpgpu_batch_solve", who);
-  }
-  rc = layout(b);  // (every pmf set)
-  if (rc) return rc;
-  const int64_t wpi = (n_paths + 63) / 64;
-  const int64_t waves = (int64_t)N * wpi;
-  if (!grid_ok((waves + 3) / 4) || (double)N * n_paths > 2.0e9)
-    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: %d instances x %d paths are too many for one launch", who, N, n_paths);
-
-  DeviceScope dev;
-  BHIP_TRY(b, dev.enter(b->device));
-  rc = allocate(b);
-  if (rc) return rc;
-  if (!b->d_ss_inst) {
-    std::vector<sdp::SsInst> inst((size_t)N);
-    for (int i = 0; i < N; ++i) {
-      const sdpgpu_desc& d = b->d[(size_t)i];
-      inst[(size_t)i] = sdp::SsInst{d.holding_cost, d.penalty_cost, d.fixed_order_cost, d.unit_order_cost, d.min_inventory, d.max_inventory,
-                                    d.max_order_quantity};
-    }
-    BHIP_TRY(b, hipMalloc((void**)&b->d_ss_inst, inst.size() * sizeof(sdp::SsInst)));
-    BHIP_TRY(b, hipMemcpy(b->d_ss_inst, inst.data(), inst.size() * sizeof(sdp::SsInst), hipMemcpyHostToDevice));
-  }
-  if (!b->sim_ev0) {
-    BHIP_TRY(b, hipEventCreate(&b->sim_ev0));
-    BHIP_TRY(b, hipEventCreate(&b->sim_ev1));
-  }
-  if (sampled && (rc = sim_upload_samplers(b))) return rc;
-  // scratch: [ini N] [partials] [means] [sums] [rule] [demands]
-  const size_t ss_elems = ss ? (size_t)N * T * 2 * levels : 0;
-  const size_t o_ini = 0, o_part = (size_t)N * 8, o_mean = o_part + (size_t)waves * 8, o_sum = o_mean + (size_t)N * 8;
-  const size_t sum_bytes = out_sum ? (size_t)N * n_paths * 8 : 0;
-  const size_t o_ss = o_sum + sum_bytes, o_dem = o_ss + ss_elems * 8;
-  const size_t dem_elems = sampled ? 0 : (stride == 0 ? (size_t)n_paths * T : (size_t)(N - 1) * (size_t)stride + (size_t)n_paths * T);
-  rc = sim_scratch(b, o_dem + dem_elems * 8);
-  if (rc) return rc;
-  char* base = b->d_sim_scratch;
-  double* d_ini = reinterpret_cast<double*>(base + o_ini);
-  double* d_part = reinterpret_cast<double*>(base + o_part);
-  double* d_mean = reinterpret_cast<double*>(base + o_mean);
-  double* d_sum = out_sum ? reinterpret_cast<double*>(base + o_sum) : nullptr;
-  double* d_rule = reinterpret_cast<double*>(base + o_ss);
-  double* d_dem = sampled ? nullptr : reinterpret_cast<double*>(base + o_dem);
-  BHIP_TRY(b, hipMemcpyAsync(d_ini, ini.data(), (size_t)N * 8, hipMemcpyHostToDevice, b->stream));
-  if (ss) BHIP_TRY(b, hipMemcpyAsync(d_rule, ss, ss_elems * 8, hipMemcpyHostToDevice, b->stream));
-  if (!sampled) BHIP_TRY(b, hipMemcpyAsync(d_dem, demand, dem_elems * 8, hipMemcpyHostToDevice, b->stream));
-  const sdp::SimLaunch L = sim_launch_params(b, n_paths, seed, stride);
-  const dim3 grid((unsigned)((waves + 3) / 4));
-  BHIP_TRY(b, hipEventRecord(b->sim_ev0, b->stream));
-  if (!ss) {
-    rc = fit_launch(b, who, levels);
-    if (rc) return rc;
-    d_rule = b->d_fit;
-  }
-  if (levels == 1)
-    ss_sim_launch<1>(b, sampled, grid, L, d_ini, d_rule, d_dem, d_part, d_sum);
-  else if (levels == 2)
-    ss_sim_launch<2>(b, sampled, grid, L, d_ini, d_rule, d_dem, d_part, d_sum);
-  else
-    ss_sim_launch<3>(b, sampled, grid, L, d_ini, d_rule, d_dem, d_part, d_sum);
-  BHIP_TRY(b, hipGetLastError());
-  hipLaunchKernelGGL(sdp::batch_sim_mean_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, d_part, N, (int)wpi, n_paths, d_mean);
-  BHIP_TRY(b, hipGetLastError());
-  BHIP_TRY(b, hipEventRecord(b->sim_ev1, b->stream));
-  b->sim_timed = true;
-  BHIP_TRY(b, hipMemcpyAsync(out_mean, d_mean, (size_t)N * 8, hipMemcpyDeviceToHost, b->stream));
-  if (out_sum) BHIP_TRY(b, hipMemcpyAsync(out_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost, b->stream));
-  BHIP_TRY(b, hipStreamSynchronize(b->stream));
-  return SDPGPU_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1354,7 +1098,7 @@ int sdpgpu_batch_reachable(sdpgpu_batch* b, int32_t instance, int32_t period, in
 
 int sdpgpu_fit_ss(int32_t levels, int32_t T, double max_order_quantity, const double* opt_table, int64_t n_rows, double* out) {
   g_create_error.clear();
-  return guarded(nullptr, "sdpgpu_fit_ss", [&]() -> int {
+  return guarded((sdpgpu_batch*)nullptr, "sdpgpu_fit_ss", [&]() -> int {
     if (levels < 1 || levels > 3) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_ss: levels = %d (1, 2 or 3: getSinglesS, getTwosS, getThreesS)", levels);
     if (T < 1) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_ss: T = %d", T);
     if (!opt_table || !out) return bfail(nullptr, SDPGPU_ERR_ARG, "sdpgpu_fit_ss: null argument (opt_table, out)");
@@ -1406,22 +1150,149 @@ int sdpgpu_batch_fit_ss(sdpgpu_batch* b, int32_t levels, double* out) {
   });
 }
 
-int sdpgpu_batch_simulate_ss(sdpgpu_batch* b, int32_t levels, const double* ss, int32_t n_paths, const double* demand, int64_t instance_stride,
-                             const double* ini_x, double* out_mean, double* out_sum) {
+}  // extern "C"
+
+// =================================================================================================
+// The rollouts: the table policy or a level rule along given or drawn demand paths (batch_sim_kernel, sdp_batch_sim.hpp)
+// =================================================================================================
+namespace {
+
+// What a call rolls: the solved policy tables, or a rule of `levels` (s, S) pairs -- the caller's `ss`, or with ss == NULL the
+// fit of the tables, made on the device inside the call.
+struct SimRule {
+  bool table;
+  int32_t levels;
+  const double* ss;
+};
+
+template <class RULE>
+void sim_launch(sdpgpu_batch* b, bool sampled, dim3 grid, const sdp::SimLaunch& L, const double* d_ini, RULE rule, const double* d_dem,
+                double* d_part, double* d_sum) {
+  if (sampled)
+    hipLaunchKernelGGL((sdp::batch_sim_kernel<RULE, true>), grid, dim3(256), 0, b->stream, L, b->d_sim_inst, d_ini, rule, nullptr, b->d_samp,
+                       b->d_thr, d_part, d_sum);
+  else
+    hipLaunchKernelGGL((sdp::batch_sim_kernel<RULE, false>), grid, dim3(256), 0, b->stream, L, b->d_sim_inst, d_ini, rule, d_dem, nullptr,
+                       nullptr, d_part, d_sum);
+}
+
+int sim_run(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, const double* demand, int64_t stride, bool sampled, uint64_t seed,
+            const double* ini_x, double* out_mean, double* out_sum) {
+  const int N = b->N, T = b->T;
+  const int32_t levels = rule.levels;
+  if (!rule.table && (levels < 1 || levels > 3))
+    return bfail(b, SDPGPU_ERR_ARG, "%s: levels = %d (1, 2 or 3: simulateSinglesS, simulateTwosS, simulateThreesS)", who, levels);
+  std::vector<double> ini;
+  int rc = sim_check_args(b, who, n_paths, demand, stride, sampled, ini_x, out_mean, &ini);
+  if (rc) return rc;
+  // The tables must exist for the table policy and for a fit; an explicit rule may be rolled on an unsolved batch, whose
+  // tables layout() and allocate() below then make (after a solve both return at once).
+  if (rule.table) {
+    if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+  } else if (!rule.ss) {  // fit first, in this call
+    if ((rc = fit_needs_unit_step(b, who))) return rc;
+    if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s: ss = NULL fits the rule from the policy tables: before sdpgpu_batch_solve", who);
+  }
+  rc = layout(b);  // (every pmf set)
+  if (rc) return rc;
+  const int64_t wpi = (n_paths + 63) / 64;
+  const int64_t waves = (int64_t)N * wpi;
+  if (!grid_ok((waves + 3) / 4) || (double)N * n_paths > 2.0e9)
+    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: %d instances x %d paths are too many for one launch", who, N, n_paths);
+
+  DeviceScope dev;
+  BHIP_TRY(b, dev.enter(b->device));
+  rc = allocate(b);
+  if (rc) return rc;
+  if (!b->d_sim_inst) {
+    std::vector<sdp::SimInst> inst((size_t)N);
+    for (int i = 0; i < N; ++i) {
+      const sdpgpu_desc& d = b->d[(size_t)i];
+      inst[(size_t)i] = sdp::SimInst{d.holding_cost, d.penalty_cost, d.fixed_order_cost, d.unit_order_cost, d.min_inventory, d.max_inventory,
+                                     d.max_order_quantity, (int64_t)policy_row(b, i, 0), b->nxs[(size_t)i], 0};
+    }
+    BHIP_TRY(b, hipMalloc((void**)&b->d_sim_inst, inst.size() * sizeof(sdp::SimInst)));
+    BHIP_TRY(b, hipMemcpy(b->d_sim_inst, inst.data(), inst.size() * sizeof(sdp::SimInst), hipMemcpyHostToDevice));
+  }
+  if (!b->sim_ev0) {
+    BHIP_TRY(b, hipEventCreate(&b->sim_ev0));
+    BHIP_TRY(b, hipEventCreate(&b->sim_ev1));
+  }
+  if (sampled && (rc = sim_upload_samplers(b))) return rc;
+  const size_t ss_elems = rule.ss ? (size_t)N * T * 2 * levels : 0;
+  const size_t sum_bytes = out_sum ? (size_t)N * n_paths * 8 : 0;
+  const size_t dem_elems = sampled ? 0 : (stride == 0 ? (size_t)n_paths * T : (size_t)(N - 1) * (size_t)stride + (size_t)n_paths * T);
+  Carve c;
+  const size_t o_ini = c.take((size_t)N * 8), o_part = c.take((size_t)waves * 8), o_mean = c.take((size_t)N * 8);
+  const size_t o_sum = c.take(sum_bytes), o_ss = c.take(ss_elems * 8), o_dem = c.take(dem_elems * 8);
+  rc = sim_scratch(b, c.at);
+  if (rc) return rc;
+  char* base = b->d_sim_scratch;
+  double* d_ini = reinterpret_cast<double*>(base + o_ini);
+  double* d_part = reinterpret_cast<double*>(base + o_part);
+  double* d_mean = reinterpret_cast<double*>(base + o_mean);
+  double* d_sum = out_sum ? reinterpret_cast<double*>(base + o_sum) : nullptr;
+  const double* d_rule = reinterpret_cast<double*>(base + o_ss);
+  double* d_dem = sampled ? nullptr : reinterpret_cast<double*>(base + o_dem);
+  BHIP_TRY(b, hipMemcpyAsync(d_ini, ini.data(), (size_t)N * 8, hipMemcpyHostToDevice, b->stream));
+  if (rule.ss) BHIP_TRY(b, hipMemcpyAsync(base + o_ss, rule.ss, ss_elems * 8, hipMemcpyHostToDevice, b->stream));
+  if (!sampled) BHIP_TRY(b, hipMemcpyAsync(d_dem, demand, dem_elems * 8, hipMemcpyHostToDevice, b->stream));
+  const sdp::SimLaunch L = sim_launch_params(b, n_paths, seed, stride);
+  const dim3 grid((unsigned)((waves + 3) / 4));
+  BHIP_TRY(b, hipEventRecord(b->sim_ev0, b->stream));
+  if (!rule.table && !rule.ss) {
+    rc = fit_launch(b, who, levels);
+    if (rc) return rc;
+    d_rule = b->d_fit;
+  }
+  if (rule.table)
+    sim_launch(b, sampled, grid, L, d_ini, sdp::TableRule{b->d_policy}, d_dem, d_part, d_sum);
+  else if (levels == 1)
+    sim_launch(b, sampled, grid, L, d_ini, sdp::LevelRule<1>{d_rule}, d_dem, d_part, d_sum);
+  else if (levels == 2)
+    sim_launch(b, sampled, grid, L, d_ini, sdp::LevelRule<2>{d_rule}, d_dem, d_part, d_sum);
+  else
+    sim_launch(b, sampled, grid, L, d_ini, sdp::LevelRule<3>{d_rule}, d_dem, d_part, d_sum);
+  BHIP_TRY(b, hipGetLastError());
+  hipLaunchKernelGGL(sdp::batch_sim_mean_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, d_part, N, (int)wpi, n_paths, d_mean);
+  BHIP_TRY(b, hipGetLastError());
+  BHIP_TRY(b, hipEventRecord(b->sim_ev1, b->stream));
+  b->sim_timed = true;
+  BHIP_TRY(b, hipMemcpyAsync(out_mean, d_mean, (size_t)N * 8, hipMemcpyDeviceToHost, b->stream));
+  if (out_sum) BHIP_TRY(b, hipMemcpyAsync(out_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost, b->stream));
+  BHIP_TRY(b, hipStreamSynchronize(b->stream));
+  return SDPGPU_OK;
+}
+
+// the four entry points differ in the rule and in where the demands come from
+int sim_entry(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, const double* demand, int64_t stride, bool sampled, uint64_t seed,
+              const double* ini_x, double* out_mean, double* out_sum) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
-  return guarded(b, "sdpgpu_batch_simulate_ss", [&]() -> int {
-    return ss_sim_run(b, "sdpgpu_batch_simulate_ss", levels, ss, n_paths, demand, instance_stride, false, 0, ini_x, out_mean, out_sum);
-  });
+  return guarded(b, who, [&]() -> int { return sim_run(b, who, rule, n_paths, demand, stride, sampled, seed, ini_x, out_mean, out_sum); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdpgpu_batch_simulate(sdpgpu_batch* b, int32_t n_paths, const double* demand, int64_t instance_stride, const double* ini_x,
+                          double* out_mean, double* out_sum) {
+  return sim_entry(b, "sdpgpu_batch_simulate", SimRule{true, 0, nullptr}, n_paths, demand, instance_stride, false, 0, ini_x, out_mean, out_sum);
+}
+
+int sdpgpu_batch_simulate_sampled(sdpgpu_batch* b, int32_t n_paths, uint64_t seed, const double* ini_x, double* out_mean, double* out_sum) {
+  return sim_entry(b, "sdpgpu_batch_simulate_sampled", SimRule{true, 0, nullptr}, n_paths, nullptr, 0, true, seed, ini_x, out_mean, out_sum);
+}
+
+int sdpgpu_batch_simulate_ss(sdpgpu_batch* b, int32_t levels, const double* ss, int32_t n_paths, const double* demand, int64_t instance_stride,
+                             const double* ini_x, double* out_mean, double* out_sum) {
+  return sim_entry(b, "sdpgpu_batch_simulate_ss", SimRule{false, levels, ss}, n_paths, demand, instance_stride, false, 0, ini_x, out_mean, out_sum);
 }
 
 int sdpgpu_batch_simulate_ss_sampled(sdpgpu_batch* b, int32_t levels, const double* ss, int32_t n_paths, uint64_t seed, const double* ini_x,
                                      double* out_mean, double* out_sum) {
-  if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  return guarded(b, "sdpgpu_batch_simulate_ss_sampled", [&]() -> int {
-    return ss_sim_run(b, "sdpgpu_batch_simulate_ss_sampled", levels, ss, n_paths, nullptr, 0, true, seed, ini_x, out_mean, out_sum);
-  });
+  return sim_entry(b, "sdpgpu_batch_simulate_ss_sampled", SimRule{false, levels, ss}, n_paths, nullptr, 0, true, seed, ini_x, out_mean, out_sum);
 }
 
 }  // extern "C"

@@ -8,7 +8,10 @@
 //   sdpgpu_staff.hip    STAFF family (workforce.StaffRecursion): level-dependent pmf tables, its period kernel
 //   sdpgpu_sparse.hip   reachable-set engine of the two-product lead-time family (own entry point)
 //   sdpgpu_pmf.hip      GetPmf.getpmf / CLSP.main's inline pmf (host arithmetic) behind the ABI
+//   sdpgpu_batch.hip    a batch of F1 instances (own entry points): batched solve, batched rollout of the table policy and of
+//                       (s, S) level rules (ONE kernel over a rule: sdp_batch_sim.hpp, sdp_fitss.hpp), the level-rule fit
 //   sdpgpu_simsample.hip  demand paths drawn on the device for a handle's policy simulation (sampler, fused rollout, reduction)
+//   sdpgpu_sim_host.hpp   host helpers of those two units: exception barrier, device scope, stream record, sampler specs, scratch
 //   sdpgpu_comm.hip     multi-GPU: RCCL communicators (loaded on first use), per-period all-gather, sharded sweeps
 #pragma once
 #include "../../include/sdpgpu.h"
@@ -21,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 #include <new>
 #include <mutex>
 #include <string>
@@ -33,6 +37,10 @@ struct FinalizeJob;
 struct QueryStates;
 struct SimPeriod;
 }  // namespace sdp
+
+namespace sdpgpu_detail {
+struct SamplerSpecs;  // sdpgpu_sim_host.hpp
+}
 
 using sdp::DevParams;
 using sdp::Grid;
@@ -218,11 +226,10 @@ struct sdpgpu_handle {
   int64_t graph_replays = 0;
   int flush_uploads = 0;  // job-list uploads of flush_pending since the counter was last reset (sdpgpu_solve's capture)
   // sdpgpu_set_sampler / sdpgpu_simulate_sampled / sdpgpu_sample_demands (sdpgpu_simsample.hip): per period index the spec's
-  // threshold table (empty vectors: every period draws from its pmf tile), and ONE device block for the period records,
-  // sampler records, threshold / value arenas, sums, flags and partials of a call
-  std::vector<char> samp_spec_set;
-  std::vector<int32_t> samp_klo, samp_strict;
-  std::vector<std::vector<double>> samp_thr;
+  // threshold table (null until the first sdpgpu_set_sampler: every period draws from its pmf tile; a shared_ptr because it
+  // destroys a type that only that unit completes), and ONE device block for the period records, sampler records, threshold /
+  // value arenas, sums, flags and partials of a call
+  std::shared_ptr<sdpgpu_detail::SamplerSpecs> samp;
   char* d_sim_scratch = nullptr;
   size_t sim_scratch_bytes = 0;
   hipEvent_t sim_ev0 = nullptr, sim_ev1 = nullptr;

@@ -1,47 +1,14 @@
 // sdpgpu_simsample.hip -- sdpgpu_set_sampler, sdpgpu_simulate_sampled, sdpgpu_sample_demands: demand paths drawn on the
 // device for a handle's policy simulation (kernels: sdp_sim_sampled.hpp; definition: DESIGN 4, "Sampled simulation on a
 // handle").  All validation comes before the first device call; the device scratch of these entry points is ONE block kept
-// on the handle (sim_scratch) and released by sdpgpu_destroy.
-#include "sdpgpu_internal.hpp"
+// on the handle (sim_scratch of sdpgpu_sim_host.hpp, which also holds what this unit shares with the batch's rollouts) and
+// released by sdpgpu_destroy.
+#include "sdpgpu_sim_host.hpp"
 #include "sdp_sim_sampled.hpp"
 
 using namespace sdpgpu_detail;
 
 namespace {
-
-constexpr int32_t kSimMaxPaths = 1 << 24;
-
-// No C++ exception crosses the C ABI.
-template <class F>
-int guarded(sdpgpu_handle* h, const char* who, F&& body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc&) {
-    return fail(h, SDPGPU_ERR_ALLOC, "%s: host allocation failed (std::bad_alloc)", who);
-  } catch (const std::exception& e) {
-    return fail(h, SDPGPU_ERR_INTERNAL, "%s: internal error: %s", who, e.what());
-  } catch (...) {
-    return fail(h, SDPGPU_ERR_INTERNAL, "%s: internal error (unknown exception)", who);
-  }
-}
-
-// The handle's device for the length of a call; the caller's current device comes back at the end.
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t enter(int device) {
-    if (device < 0) return hipSuccess;
-    hipError_t e = hipGetDevice(&prev);
-    if (e != hipSuccess) return e;
-    if (prev == device) return hipSuccess;
-    e = hipSetDevice(device);
-    switched = e == hipSuccess;
-    return e;
-  }
-  ~DeviceScope() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-};
 
 // the refusals sdpgpu_simulate has, in its order (the solve state is the caller's business)
 int refuse(sdpgpu_handle* h, const char* who) {
@@ -55,30 +22,17 @@ int refuse(sdpgpu_handle* h, const char* who) {
 }
 
 int check_stream_args(sdpgpu_handle* h, const char* who, int32_t n_paths, int32_t mode, uint64_t first_path) {
-  if (n_paths <= 0) return fail(h, SDPGPU_ERR_ARG, "%s: n_paths = %d (1 .. %d)", who, n_paths, kSimMaxPaths);
-  if (n_paths > kSimMaxPaths) return fail(h, SDPGPU_ERR_UNSUPPORTED, "%s: n_paths = %d exceeds %d", who, n_paths, kSimMaxPaths);
+  if (const int rc = check_n_paths(h, who, n_paths)) return rc;
   if (mode != SDPGPU_SAMPLE_LHS && mode != SDPGPU_SAMPLE_RANDOM)
     return fail(h, SDPGPU_ERR_ARG, "%s: mode = %d (SDPGPU_SAMPLE_LHS 0, SDPGPU_SAMPLE_RANDOM 1)", who, mode);
   if (mode == SDPGPU_SAMPLE_LHS && first_path != 0)
     return fail(h, SDPGPU_ERR_ARG, "%s: first_path = %llu -- a latin hypercube is one whole of n_paths strata, first_path must be 0", who,
                 (unsigned long long)first_path);
   for (int t = 0; t < h->T; ++t) {
-    const bool spec = !h->samp_spec_set.empty() && h->samp_spec_set[(size_t)t];
+    const bool spec = h->samp && h->samp->has((size_t)t);
     if (!spec && !h->pmf_set[(size_t)t]) return fail(h, SDPGPU_ERR_STATE, "%s: pmf of period %d not set and no sampler spec given", who, t + 1);
   }
   return SDPGPU_OK;
-}
-
-sdp::SimStream make_stream(int32_t n_paths, uint64_t seed, uint64_t first_path) {
-  sdp::SimStream R{};
-  R.first_path = first_path;
-  R.n_paths = (uint32_t)n_paths;
-  R.seed_lo = (uint32_t)(seed & 0xffffffffu);
-  R.seed_hi = (uint32_t)(seed >> 32);
-  int hb = 1;
-  while (((int64_t)1 << (2 * hb)) < (int64_t)n_paths) ++hb;
-  R.half_bits = hb;
-  return R;
 }
 
 // sampler records and their two arenas: spec tables as set (demand = k_lo + q); tile tables = the running fp64 sum of the
@@ -86,62 +40,20 @@ sdp::SimStream make_stream(int32_t n_paths, uint64_t seed, uint64_t first_path) 
 void build_samplers(const sdpgpu_handle* h, std::vector<sdp::SimSampler>* rec, std::vector<double>* thr, std::vector<double>* val) {
   rec->resize((size_t)h->T);
   for (int t = 0; t < h->T; ++t) {
+    if (h->samp && h->samp->has((size_t)t)) {
+      (*rec)[(size_t)t] = h->samp->append((size_t)t, thr);
+      continue;
+    }
     sdp::SimSampler S{};
     S.off = (int64_t)thr->size();
-    if (!h->samp_spec_set.empty() && h->samp_spec_set[(size_t)t]) {
-      S.k_lo = h->samp_klo[(size_t)t];
-      S.strict = h->samp_strict[(size_t)t];
-      S.m = (int32_t)h->samp_thr[(size_t)t].size();
-      S.val_off = -1;
-      thr->insert(thr->end(), h->samp_thr[(size_t)t].begin(), h->samp_thr[(size_t)t].end());
-    } else {
-      const std::vector<double>& p = h->pmf_p[(size_t)t];
-      const std::vector<double>& d = h->pmf_d[(size_t)t];
-      S.k_lo = 0;
-      S.strict = 0;
-      S.m = (int32_t)p.size();
-      S.val_off = (int64_t)val->size();
-      double s = 0.0;
-      for (size_t j = 0; j < p.size(); ++j) {
-        s += p[j];
-        thr->push_back(j + 1 == p.size() ? HUGE_VAL : s);
-      }
-      val->insert(val->end(), d.begin(), d.end());
-    }
+    S.k_lo = 0;
+    S.strict = 0;
+    S.m = (int32_t)h->pmf_p[(size_t)t].size();
+    S.val_off = (int64_t)val->size();
+    append_tile_thresholds(h->pmf_p[(size_t)t], thr);
+    val->insert(val->end(), h->pmf_d[(size_t)t].begin(), h->pmf_d[(size_t)t].end());
     (*rec)[(size_t)t] = S;
   }
-}
-
-int sim_scratch(sdpgpu_handle* h, size_t bytes) {
-  if (bytes <= h->sim_scratch_bytes && h->d_sim_scratch) return SDPGPU_OK;
-  if (h->d_sim_scratch) {
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(h->d_sim_scratch);
-    h->d_sim_scratch = nullptr;
-    h->sim_scratch_bytes = 0;
-  }
-  HIP_TRY(h, hipMalloc((void**)&h->d_sim_scratch, bytes));
-  h->sim_scratch_bytes = bytes;
-  return SDPGPU_OK;
-}
-
-// offsets of the scratch block, every part aligned to 16 bytes
-struct Carve {
-  size_t at = 0;
-  size_t take(size_t bytes) {
-    const size_t o = at;
-    at += (bytes + 15) / 16 * 16;
-    return o;
-  }
-};
-
-int no_device(sdpgpu_handle* h, const char* who) {
-  int ndev = 0;
-  const hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev < 1)
-    return fail(h, SDPGPU_ERR_DEVICE, "%s: no HIP device available (%s); this library has no CPU path", who,
-                e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-  return SDPGPU_OK;
 }
 
 template <bool RANDOM>
@@ -177,29 +89,20 @@ int sdpgpu_set_sampler(sdpgpu_handle* h, int32_t t, const sdpgpu_dist_spec* spec
   h->err.clear();
   return guarded(h, "sdpgpu_set_sampler", [&]() -> int {
     if (t < 0 || t >= h->T) return fail(h, SDPGPU_ERR_ARG, "set_sampler: period index %d outside 0 .. %d", t, h->T - 1);
-    if (h->samp_spec_set.empty()) {
-      h->samp_spec_set.assign((size_t)h->T, 0);
-      h->samp_klo.assign((size_t)h->T, 0);
-      h->samp_strict.assign((size_t)h->T, 0);
-      h->samp_thr.resize((size_t)h->T);
+    if (!h->samp) {  // (a NULL spec at any step creates them too: unlike a batch, whose tables all need step 1)
+      h->samp = std::make_shared<SamplerSpecs>();
+      h->samp->resize((size_t)h->T);
     }
     if (!spec) {  // back to the pmf tile (any step)
-      h->samp_spec_set[(size_t)t] = 0;
-      h->samp_thr[(size_t)t].clear();
+      h->samp->clear((size_t)t);
       return SDPGPU_OK;
     }
     if (h->d.step != 1.0)
       return fail(h, SDPGPU_ERR_UNSUPPORTED, "set_sampler: step %g -- a spec's demands are Math.round's integers (Simulation.java:64), it needs step == 1 "
                   "(the pmf tile samples at any step)", h->d.step);
-    std::vector<double> thr;
     std::string why;
-    int32_t k_lo = 0, strict = 0;
-    const int rc = sample_table_build(*spec, &k_lo, &thr, &strict, &why);
+    const int rc = h->samp->set((size_t)t, *spec, &why);
     if (rc) return fail(h, rc, "set_sampler: period %d: spec: %s", t + 1, why.c_str());
-    h->samp_thr[(size_t)t].swap(thr);
-    h->samp_klo[(size_t)t] = k_lo;
-    h->samp_strict[(size_t)t] = strict;
-    h->samp_spec_set[(size_t)t] = 1;
     return SDPGPU_OK;
   });
 }

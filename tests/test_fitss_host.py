@@ -438,3 +438,28 @@ def test_an_explicit_rule_without_a_device_is_a_device_error(sia, lib):
             assert rc == 3 and lib.sdpgpu_batch_last_error(b) != b""
     finally:
         lib.sdpgpu_batch_destroy(b)
+
+
+def test_an_unsolved_batch_rolls_an_explicit_rule_but_not_its_tables(sia, lib):
+    """The two rollouts share one instance record and one host path, not their refusals: on a batch with every pmf set and
+    nothing solved an explicit rule goes on to the device (here: the error that there is none), the table rollout stops at
+    the state error -- before and after the other call."""
+    has_gpu = False
+    try:
+        import torch
+        has_gpu = torch.cuda.is_available()
+    except ImportError:
+        pass
+    b = _batch(sia, lib)
+    err = lambda: lib.sdpgpu_batch_last_error(b).decode()
+    try:
+        dem, mean, ss = np.zeros((5, 3)), np.zeros(3), np.zeros((3, 3, 2))
+        for _ in range(2):
+            assert lib.sdpgpu_batch_simulate(b, 5, _dp(dem), 0, None, _dp(mean), None) == 2 and "before sdpgpu_batch_solve" in err()
+            rc = lib.sdpgpu_batch_simulate_ss(b, 1, _dp(ss), 5, _dp(dem), 0, None, _dp(mean), None)
+            if has_gpu:
+                assert rc == 0, err()
+            else:
+                assert rc == 3 and "no HIP device available" in err(), err()
+    finally:
+        lib.sdpgpu_batch_destroy(b)

@@ -1,5 +1,5 @@
 """The (s, S) level rules of a batch on the GPU (sdpgpu_batch_fit_ss: batch_fit_ss_kernel; sdpgpu_batch_simulate_ss*:
-batch_ss_sim_kernel; DESIGN 4 "Batched (s, S) level rules").  The bar is bit equality throughout: the device fit against
+batch_sim_kernel under LevelRule; DESIGN 4 "Batched (s, S) level rules").  The bar is bit equality throughout: the device fit against
 sdpgpu_fit_ss on the batch's own read-back rows and against the independent twin (tests/fitss_twin.py) on the oracle's
 tables; the rule rollout against the twin path for path; and, where the optimal policy IS one (s, S) rule, the rule rollout
 against the table rollout of the same seed.  Means are held to math.fsum of the path sums at the batched simulation's 1e-13."""
