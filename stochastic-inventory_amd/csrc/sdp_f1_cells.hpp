@@ -80,16 +80,30 @@ struct FinalizeJob {
 // V_{t+1}(clamp m).  CLSP.java:257-258: upper clamp, then lower clamp.  In the unclamped variant every real cell
 // is inside the next box by construction; the clamp then only keeps padded (p = 0) demand
 // steps, padded actions and tail lanes from reading outside the table.
+// In two halves -- the load of the stored word, and its decoding -- for a caller that issues the load long before it uses
+// the value (the level kernel's prefetch slot): decoding a key is arithmetic on the loaded word, and would wait for it.
 template <bool KEYED_IN>
-__device__ __forceinline__ double level_v(const WinParams& W, const double* __restrict__ v_next,
-                                          const unsigned long long* __restrict__ k_next, int m) {
+__device__ __forceinline__ unsigned long long level_v_word(const WinParams& W, const double* __restrict__ v_next,
+                                                           const unsigned long long* __restrict__ k_next, int m) {
   int idx = m + W.idx_off;
   idx = idx > W.next_last ? W.next_last : idx;
   idx = idx < 0 ? 0 : idx;
   if constexpr (KEYED_IN)
-    return f64_unkey(k_next[idx]);
+    return k_next[idx];
   else
-    return v_next[idx];
+    return (unsigned long long)__double_as_longlong(v_next[idx]);
+}
+template <bool KEYED_IN>
+__device__ __forceinline__ double level_v_decode(unsigned long long word) {
+  if constexpr (KEYED_IN)
+    return f64_unkey(word);
+  else
+    return __longlong_as_double((long long)word);
+}
+template <bool KEYED_IN>
+__device__ __forceinline__ double level_v(const WinParams& W, const double* __restrict__ v_next,
+                                          const unsigned long long* __restrict__ k_next, int m) {
+  return level_v_decode<KEYED_IN>(level_v_word<KEYED_IN>(W, v_next, k_next, m));
 }
 
 // W[m] for one m: the immediate-cost part that depends on the level, and the future value.

@@ -212,6 +212,28 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
   double* s_row = reinterpret_cast<double*>(mine);
   double* s_val = s_row + DB * ROW;
   int* s_idx = reinterpret_cast<int*>(s_val + L.band + NA);
+  // THE PREFETCH SLOT: what the build of ONE table reads from memory, loaded while the table before it is walked.  The
+  // table of block y and steps j .. j + DB - 1 needs V(clamp(y + s - j')) for s < S and DB steps j': the DB + S - 1
+  // consecutive entries w[q] = V(clamp(y - j - (DB - 1) + q)), of which row t, level s takes w[DB - 1 - t + s].  Lane t holds
+  // w[t] and w[64 + t] (as stored: a key is decoded where it is used, so that nothing waits for the load here) and its
+  // row's p_j; the tag (pf_y, pf_j) says whose they are.  A table whose tag does not match is built from direct loads.
+  // Period T (no future term) has only p_j to fetch, and holding it costs its CUT instantiation the third wave per SIMD
+  // (166 -> 189 VGPRs): it stays as it was.
+  constexpr bool PF = FUTURE;
+  static_assert(DB + S - 1 > 64 && DB + S - 1 <= 128, "two window entries per lane");
+  [[maybe_unused]] unsigned long long pf_w0 = 0, pf_w1 = 0;
+  [[maybe_unused]] double pf_p = 0.0;
+  [[maybe_unused]] int pf_y = INT32_MIN, pf_j = 0;
+  [[maybe_unused]] int pf_stop = INT32_MAX;  // CUT: the step the block before stopped at (a guess at where this one will)
+  [[maybe_unused]] auto prefetch = [&](int y, int j) {
+    const int m = y - j - (DB - 1);
+    pf_p = pmf_p[j + min(lane, min(DB, L.d_pad - j) - 1)];
+    pf_w0 = level_v_word<KEYED_IN>(W, v_next, k_next, m + lane);
+    pf_w1 = level_v_word<KEYED_IN>(W, v_next, k_next, m + 64 + min(lane, DB + S - 2 - 64));
+    pf_y = y;
+    pf_j = j;
+  };
+  if constexpr (PF) prefetch(yb, 0);  // (the slot fill below covers it)
   if constexpr (CUT) {
     // every slot starts at U(i) = Q(i, 0) with action 0 (see THE CUT-OFF above); a slot of no state of the slab -- the
     // ends of the range, and the slots past n_slot that the last, ragged band's level blocks still address -- at a value
@@ -269,15 +291,34 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
       const int nj = min(DB, L.d_pad - j0);
       // the table of steps j0 .. j0 + nj - 1: lane t forms row t (rows past nj repeat the last step and are not read)
       __builtin_amdgcn_wave_barrier();
+      const bool fetched = PF && pf_y == y0 && pf_j == j0;  // (wave-uniform)
+      if constexpr (PF) {
+        if (fetched) {
+          // the window goes through a strip at the start of the table region (the table before is dead, and the rows are
+          // written only after every lane has read its S entries)
+          s_row[lane] = level_v_decode<KEYED_IN>(pf_w0);
+          if (lane < DB + S - 1 - 64) s_row[64 + lane] = level_v_decode<KEYED_IN>(pf_w1);
+          __builtin_amdgcn_wave_barrier();
+        }
+      }
       if (lane < DB) {
-        const int j = j0 + min(lane, nj - 1);
-        const double p = pmf_p[j];  // (the array ends in kPmfPad zeros: d_pad < D + S stays inside)
+        const int tt = min(lane, nj - 1);
+        const int j = j0 + tt;
+        double p;
         double* row = s_row + lane * ROW;
         double vv[S];
-        if constexpr (FUTURE) {
+        if (fetched) {
+          p = pf_p;
 #pragma unroll
-          for (int s = 0; s < S; ++s) vv[s] = level_v<KEYED_IN>(W, v_next, k_next, y0 + s - j);
+          for (int s = 0; s < S; ++s) vv[s] = s_row[DB - 1 - tt + s];
+        } else {
+          p = pmf_p[j];  // (the array ends in kPmfPad zeros: d_pad < D + S stays inside)
+          if constexpr (FUTURE) {
+#pragma unroll
+            for (int s = 0; s < S; ++s) vv[s] = level_v<KEYED_IN>(W, v_next, k_next, y0 + s - j);
+          }
         }
+        __builtin_amdgcn_wave_barrier();
         row[0] = p;
         row[1] = window_entry<false, false>(W, nullptr, nullptr, y0 - j - 1).x;
         if constexpr (FUTURE) {
@@ -286,6 +327,14 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
         }
       }
       __builtin_amdgcn_wave_barrier();
+      // The inputs of the table expected next, in flight under this table's steps: the block's next table if there is one
+      // and (CUT) the block before got that far -- after a block that ran to the end, a full run -- else the first table
+      // of the task's next block.  A wrong guess costs that table its direct loads and touches nothing else.
+      if constexpr (PF) {
+        bool same = j0 + DB < L.d_pad;
+        if constexpr (CUT) same = same && j0 + DB < pf_stop;
+        if (same || y0 + S < ye) prefetch(same ? y0 : y0 + S, same ? j0 + DB : 0);
+      }
       // Each step reads the NEXT step's row (a broadcast ds_read_b128 per two doubles) before its own 100 fp64
       // instructions, which then cover the LDS latency; the row past the block's last step lies inside the wave's region
       // and is not used.
@@ -299,13 +348,27 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
           // (the imm ring is in its canonical rotation here; the slots are the ones the epilogue below updates)
           if (j0 + t0 >= cut_at) {
             const int sb = (y0 - yb) - lane + NA - 1;
+            // (`beaten` is a pure conjunction.  With a future term the R thresholds of a level are read together and the
+            // compares ANDed without a short cut -- S LDS round trips per test instead of R S; every slot index lies inside
+            // the wave's slots.  Period T keeps the short cut: the grouped reads cost it the third wave per SIMD, 198 VGPRs.)
             bool beaten = true;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
+              if constexpr (FUTURE) {
+                double th[R];
 #pragma unroll
-              for (int r = 0; r < R; ++r) {
-                const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];  // not a padded action, not action 0
-                beaten = beaten && (!live || acc[r][s] > s_val[sb + s - 64 * r]);
+                for (int r = 0; r < R; ++r) th[r] = s_val[sb + s - 64 * r];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                  const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];  // not a padded action, not action 0
+                  beaten = beaten & (!live | (acc[r][s] > th[r]));
+                }
+              } else {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                  const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];
+                  beaten = beaten && (!live || acc[r][s] > s_val[sb + s - 64 * r]);
+                }
               }
             }
             ++cut_tests;
@@ -355,6 +418,7 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
     }
     if constexpr (CUT) {
       cut_steps += (unsigned)(stop_at < 0 ? L.d_pad : stop_at);
+      if constexpr (PF) pf_stop = stop_at < 0 ? INT32_MAX : stop_at;
       if (stop_at >= 0) {  // no cell of the block can win or tie: nothing to put into the slots
         cut_dec = cut_fail == 0 ? min(2 * cut_dec, 8 * S) : S;
         cut_first = max(S, stop_at - cut_dec);
