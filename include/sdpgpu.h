@@ -620,6 +620,25 @@ typedef struct sdpgpu_multi_table {
 } sdpgpu_multi_table;
 void sdpgpu_multi_set_table(sdpgpu_multi_table* table);
 
+/* Which kernel forms the calling thread's last sdpgpu_multi*_solve launched: one bit per launch site of the reachable-set
+ * engine, OR-ed over the periods of that solve (0 after a solve that launched nothing).  The engine picks a form per period
+ * from the instance's shape (and the SDPGPU_MULTI_* environment switches); a test that means to exercise one reads here
+ * that it ran.  Host bookkeeping only: no kernel reads or writes it. */
+#define SDPGPU_MULTI_FORM_SORTED_FORWARD 0x0001u /* forward pass over hash-sorted candidates (expand / sort / scatter) */
+#define SDPGPU_MULTI_FORM_LATTICE_MARK 0x0002u   /* lattice_mark_kernel: the transition lambda per (state, action, pair) */
+#define SDPGPU_MULTI_FORM_FACT_MARK 0x0004u      /* backward_fact_kernel as the lattice's marking pass (LK = 3) */
+#define SDPGPU_MULTI_FORM_TRIPLES_MARK 0x0008u   /* XR family: marking through the distinct post-order triples */
+#define SDPGPU_MULTI_FORM_FACT_LAST 0x0010u      /* backward_fact_kernel, period T (no successor) */
+#define SDPGPU_MULTI_FORM_FACT_UID 0x0020u       /* backward_fact_kernel, LK = 0: successor ids stored per candidate */
+#define SDPGPU_MULTI_FORM_FACT_RANK 0x0040u      /* backward_fact_kernel, LK = 1: the lattice's rank word, then the value */
+#define SDPGPU_MULTI_FORM_FACT_DENSE 0x0080u     /* backward_fact_kernel, LK = 2: V_{t+1} laid out on the lattice */
+#define SDPGPU_MULTI_FORM_FACT_I32 0x0100u       /* a backward_fact_kernel (LK 1, 2 or 3) formed lattice indices in 32-bit words */
+#define SDPGPU_MULTI_FORM_FACT_I64 0x0200u       /* ... in 64-bit words */
+#define SDPGPU_MULTI_FORM_LEAD_WAVE 0x0400u      /* backward_lead_wave_kernel: lead-time family, a wave per state */
+#define SDPGPU_MULTI_FORM_BACKWARD 0x0800u       /* backward_kernel: a workgroup per state, the lambdas per cell */
+#define SDPGPU_MULTI_FORM_DENSE_SCATTER 0x1000u  /* dense_scatter_kernel: V_{t+1} scattered to its lattice points */
+uint32_t sdpgpu_multi_forms_used(void);
+
 /* sdp.cash.multiItem.CashRecursionMulti.getExpectedValue (CashRecursionMulti.java:82-116) over the lambdas of
  * cash.multiItem.MultiItemCash (MultiItemCash.java:66-118): two products, cash-limited orders
  * (variCost[0] * i + variCost[1] * j < cash + 0.1), no lead time, state (I1, I2, cash) truncated to ints by the

@@ -219,6 +219,21 @@ def multi_table_rows(t, arrs):
     return m[order]
 
 
+# SDPGPU_MULTI_FORM_* (include/sdpgpu.h): the bits of sdpgpu_multi_forms_used()
+MULTI_FORMS = {
+    "SORTED_FORWARD": 0x0001, "LATTICE_MARK": 0x0002, "FACT_MARK": 0x0004, "TRIPLES_MARK": 0x0008, "FACT_LAST": 0x0010,
+    "FACT_UID": 0x0020, "FACT_RANK": 0x0040, "FACT_DENSE": 0x0080, "FACT_I32": 0x0100, "FACT_I64": 0x0200,
+    "LEAD_WAVE": 0x0400, "BACKWARD": 0x0800, "DENSE_SCATTER": 0x1000,
+}
+
+
+def multi_form_names(mask: int):
+    """The names of the bits set in a forms mask, in bit order (an unknown bit shows as its hex value)."""
+    names = [n for n, b in MULTI_FORMS.items() if mask & b]
+    rest = mask & ~sum(MULTI_FORMS.values())
+    return names + ([hex(rest)] if rest else [])
+
+
 class SdpgpuDistSpec(C.Structure):
     """struct sdpgpu_dist_spec (include/sdpgpu.h)."""
 
@@ -300,6 +315,7 @@ EXPORTS = {
     "sdpgpu_multilead_solve": (C.c_int, [C.POINTER(SdpgpuMultilead), _DP, _IP, _IP, _LP, _LP, _DP]),
     "sdpgpu_multilead_last_error": (C.c_char_p, []),
     "sdpgpu_multi_set_table": (None, [C.POINTER(SdpgpuMultiTable)]),
+    "sdpgpu_multi_forms_used": (C.c_uint32, []),
     "sdpgpu_multicash_solve": (C.c_int, [C.POINTER(SdpgpuMulticash), _DP, _IP, _IP, _LP, _LP, _DP]),
     "sdpgpu_multixr_solve": (C.c_int, [C.POINTER(SdpgpuMulticash), C.c_double, _DP, _IP, _IP, _LP, _LP, _DP]),
     "sdpgpu_batch_create": (C.c_int, [C.POINTER(SdpgpuDesc), C.c_int32, C.POINTER(_P)]),

@@ -39,6 +39,7 @@ namespace {
 
 thread_local std::string g_ml_error;
 thread_local sdpgpu_multi_table* g_ml_table = nullptr;  // read-out request for the next solve of this thread
+thread_local uint32_t g_ml_forms = 0;  // SDPGPU_MULTI_FORM_* bits of the launch sites this thread's last solve went through
 
 struct MLParams {
   double price[2], vari[2], sal[2];
@@ -1312,6 +1313,7 @@ struct SparseProblem {
 
 int sparse_solve(const SparseProblem& sp, double* final_value, int32_t* q1, int32_t* q2, int64_t* states_per_period,
                  int64_t* cells, double* gpu_ms) {
+  g_ml_forms = 0;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
     g_ml_error = "no HIP device available; this library has no CPU path";
@@ -1427,6 +1429,7 @@ int sparse_solve(const SparseProblem& sp, double* final_value, int32_t* q1, int3
               const int64_t per_batch_s = std::max<int64_t>(1, ((int64_t)1 << 30) / NA);
               for (int64_t first = 0; first < n_states[t]; first += per_batch_s) {
                 const int64_t ns = std::min<int64_t>(per_batch_s, n_states[t] - first);
+                g_ml_forms |= SDPGPU_MULTI_FORM_TRIPLES_MARK;
                 hipLaunchKernelGGL(xr_triple_mark_kernel, dim3((unsigned)((ns * NA + 255) / 256)), dim3(256), 0, 0, P, B, w0,
                                    d_states[t] + first, ns, d_tw, d_oob);
                 ML_TRY(hipGetLastError());
@@ -1518,6 +1521,7 @@ int sparse_solve(const SparseProblem& sp, double* final_value, int32_t* q1, int3
       ML_TRY(hipGetLastError());                                                                                              \
     }                                                                                                                         \
   } while (0)
+            g_ml_forms |= SDPGPU_MULTI_FORM_FACT_MARK | (lat_i32 ? SDPGPU_MULTI_FORM_FACT_I32 : SDPGPU_MULTI_FORM_FACT_I64);
             if (P.model == 1) {
               if (lat_i32) ML_MARK(1, true); else ML_MARK(1, false);
             } else {
@@ -1531,6 +1535,7 @@ int sparse_solve(const SparseProblem& sp, double* final_value, int32_t* q1, int3
         const int64_t per_batch = std::max<int64_t>(1, ((int64_t)1 << 30) / NA);
         for (int64_t first = 0; !marked && first < n_states[t]; first += per_batch) {
           const int64_t ns = std::min<int64_t>(per_batch, n_states[t] - first);
+          g_ml_forms |= SDPGPU_MULTI_FORM_LATTICE_MARK;
           hipLaunchKernelGGL(lattice_mark_kernel, dim3((unsigned)((ns * NA + 255) / 256)), dim3(256), 0, 0, P, L,
                              d_states[t] + first, ns, dem_t, d_lat_words, d_oob);
           ML_TRY(hipGetLastError());
@@ -1588,6 +1593,7 @@ int sparse_solve(const SparseProblem& sp, double* final_value, int32_t* q1, int3
       ML_TRY(hipMalloc((void**)&d_rank, (size_t)nc * 4));
       ML_TRY(hipMalloc((void**)&d_uid[t], (size_t)nc * 4));
       const unsigned gsa = (unsigned)((n_states[t] * NA + 255) / 256);
+      g_ml_forms |= SDPGPU_MULTI_FORM_SORTED_FORWARD;
       hipLaunchKernelGGL(expand_kernel, dim3(gsa), dim3(256), 0, 0, P, d_states[t], n_states[t], dem_t, d_hash, d_order);
       ML_TRY(hipGetLastError());
       size_t tmp_bytes = 0;
@@ -1685,6 +1691,7 @@ int sparse_solve(const SparseProblem& sp, double* final_value, int32_t* q1, int3
             double cap_gb = 16.0;
             if (const char* e = std::getenv("SDPGPU_MULTI_DENSE_GB")) cap_gb = std::atof(e);
             if ((double)sp.lat.bits * 8.0 <= cap_gb * 1e9 && hipMalloc((void**)&d_vdense, (size_t)sp.lat.bits * 8) == hipSuccess) {
+              g_ml_forms |= SDPGPU_MULTI_FORM_DENSE_SCATTER;
               hipLaunchKernelGGL(dense_scatter_kernel, dim3((unsigned)((n_states[t + 1] + 255) / 256)), dim3(256), 0, 0, sp.lat,
                                  d_states[t + 1], n_states[t + 1], d_vnext, d_vdense);
               ML_TRY(hipGetLastError());
@@ -1715,6 +1722,11 @@ int sparse_solve(const SparseProblem& sp, double* final_value, int32_t* q1, int3
   } while (0)
           const int lk = d_vdense ? 2 : (d_lat_rank[t] ? 1 : 0);
           const bool w32 = lat_i32 && lk != 0;
+          if (P.is_last)
+            g_ml_forms |= SDPGPU_MULTI_FORM_FACT_LAST;
+          else
+            g_ml_forms |= (lk == 2 ? SDPGPU_MULTI_FORM_FACT_DENSE : lk == 1 ? SDPGPU_MULTI_FORM_FACT_RANK : SDPGPU_MULTI_FORM_FACT_UID) |
+                          (lk == 0 ? 0u : w32 ? SDPGPU_MULTI_FORM_FACT_I32 : SDPGPU_MULTI_FORM_FACT_I64);
           if (P.model == 1) {
             if (P.is_last) ML_FACT(1, true, 0, false);
             else if (lk == 2 && w32) ML_FACT(1, false, 2, true);
@@ -1743,6 +1755,7 @@ int sparse_solve(const SparseProblem& sp, double* final_value, int32_t* q1, int3
           ML_TRY(hipGetLastError());
         }
         const size_t smem_w = (size_t)nd * (4 * sizeof(DemandTerms) + 8);
+        g_ml_forms |= SDPGPU_MULTI_FORM_LEAD_WAVE;
         for (int64_t first = 0; first < n_states[t]; first += (int64_t)1 << 24) {  // 4M workgroups of four states
           const int64_t ns = std::min<int64_t>((int64_t)1 << 24, n_states[t] - first);
           if (P.is_last)
@@ -1757,6 +1770,7 @@ int sparse_solve(const SparseProblem& sp, double* final_value, int32_t* q1, int3
       // a dispatch carries at most 2^32 work-items: batches of 4M workgroups (2^30 lanes)
       for (int64_t first = 0; first < n_states[t]; first += (int64_t)1 << 22) {
         const int64_t nb = std::min<int64_t>((int64_t)1 << 22, n_states[t] - first);
+        g_ml_forms |= SDPGPU_MULTI_FORM_BACKWARD;
         hipLaunchKernelGGL(backward_kernel, dim3((unsigned)nb), dim3(256), smem, 0, P, d_states[t], first, n_states[t],
                            d_dem + sp.off[(size_t)t], d_prob + sp.off[(size_t)t], d_vnext, d_uid[t], d_vcur, d_act, d_cells,
                            sp.lat, d_lat_rank[t]);
@@ -1860,6 +1874,8 @@ extern "C" {
 const char* sdpgpu_multilead_last_error(void) { return g_ml_error.c_str(); }
 
 void sdpgpu_multi_set_table(sdpgpu_multi_table* table) { g_ml_table = table; }
+
+uint32_t sdpgpu_multi_forms_used(void) { return g_ml_forms; }
 
 static int multilead_body(const sdpgpu_multilead* k, double* final_value, int32_t* q1, int32_t* q2,
                           int64_t* states_per_period, int64_t* cells, double* gpu_ms) {

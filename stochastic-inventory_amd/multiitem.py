@@ -28,6 +28,8 @@ class MultiLeadResult:
     # rows {period, i1, i2, q1, q2, cash (R for the XR family), value, action 1, action 2} of every visited state in the
     # order of the reference's TreeMap keys -- what getCacheActions() / getOptTable() iterate; None unless asked for
     table: object = None
+    # SDPGPU_MULTI_FORM_* bits (_abi.MULTI_FORMS) of the kernel forms the solve launched (sdpgpu_multi_forms_used)
+    forms: int = 0
 
 
 def fill_multilead(k, *, T, q_bound, price, vari_cost, sal_value, ini_cash, ini_i1, ini_i2, r0, r1, r2, limit,
@@ -64,7 +66,8 @@ def _run(call, T: int, want_table: bool) -> MultiLeadResult:
         rc = call(C.byref(fv), C.byref(q1), C.byref(q2), states, C.byref(cells), C.byref(ms))
         if rc:
             raise SdpgpuError(rc, lib.sdpgpu_multilead_last_error().decode())
-        return MultiLeadResult(fv.value, q1.value, q2.value, list(states), cells.value, ms.value)
+        return MultiLeadResult(fv.value, q1.value, q2.value, list(states), cells.value, ms.value,
+                               forms=int(lib.sdpgpu_multi_forms_used()))
 
     res = once()
     if want_table:

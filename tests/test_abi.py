@@ -68,6 +68,24 @@ def test_two_product_struct_layouts_match_the_header(sia):
         assert out[1:] == [getattr(cls, f[0]).offset for f in cls._fields_], cname
 
 
+def test_two_product_form_bits_match_the_header(sia, lib):
+    """SDPGPU_MULTI_FORM_*: the Python names and values are the header's, every bit is distinct, and
+    sdpgpu_multi_forms_used reports none for a thread that has launched nothing."""
+    from stochastic_inventory_amd import _abi
+    header = open(os.path.join(ROOT, "include", "sdpgpu.h")).read()
+    declared = {n: int(v, 16) for n, v in re.findall(r"#define SDPGPU_MULTI_FORM_([A-Z0-9_]+)\s+(0x[0-9a-fA-F]+)u", header)}
+    assert declared == _abi.MULTI_FORMS and len(declared) == 13
+    assert all(b and b & (b - 1) == 0 for b in declared.values()) and len(set(declared.values())) == len(declared)
+    assert _abi.multi_form_names(0x0401) == ["SORTED_FORWARD", "LEAD_WAVE"] and _abi.multi_form_names(1 << 20) == ["0x100000"]
+    import threading
+    got = []
+    t = threading.Thread(target=lambda: got.append(lib.sdpgpu_multi_forms_used()))  # (the mask is per thread)
+    t.start()
+    t.join()
+    assert got == [0]
+    assert sia.MultiLeadResult(0.0, 0, 0, [1], 0, 0.0).forms == 0
+
+
 def test_create_rejects_bad_descriptors(sia, lib):
     d = sia.desc_defaults()
     d.family = 9

@@ -54,7 +54,7 @@ def test_kat3_to_kat6_three_point_demands(sia, name):
 
 
 @pytest.mark.parametrize("seed", list(range(1, 17)) + [101, 102, 103])
-def test_random_instances_match_the_oracle(sia, oracle, seed):
+def test_random_instances_match_the_oracle(sia, oracle, seed, monkeypatch):
     from stochastic_inventory_amd.multiitem import multilead_solve
     rng = np.random.default_rng(seed)
     T = int(rng.integers(2, 4)) if seed < 100 else 1 + seed % 100  # (101 .. 103: horizons 2 .. 4 with the smallest action boxes)
@@ -74,6 +74,18 @@ def test_random_instances_match_the_oracle(sia, oracle, seed):
     assert g.finalValue == fv
     assert (g.firstAction, g.secondAction) == (q1, q2)
     assert sum(g.statesPerPeriod) == states and g.cells == cells
+    # every visited state -- tuple, value, action pair -- under the wave-per-state kernel and the workgroup-per-state one
+    _, want = oracle.memo_table("multilead", **kw)
+    for wave in (None, "0"):
+        if wave is None:
+            monkeypatch.delenv("SDPGPU_MULTI_WAVE", raising=False)
+        else:
+            monkeypatch.setenv("SDPGPU_MULTI_WAVE", wave)
+        r = multilead_solve(table=True, **kw)
+        assert r.finalValue == fv and (r.firstAction, r.secondAction) == (q1, q2), wave
+        assert r.statesPerPeriod == [int((want[:, 0] == t + 1).sum()) for t in range(T)] and r.cells == cells, wave
+        assert r.table.shape == want.shape == (states, 9), wave
+        assert (r.table == want).all(), wave
 
 
 def test_kat1_whole_memo_matches_the_oracle(sia, oracle):
