@@ -250,7 +250,8 @@ def make_large_magnitude_cash_instance(seed, past_limit=False):
     scale = 5.0e8 / mult                          # the balance at which bound * mult reaches the limit
     base = float(rng.uniform(1.06, 1.6) if past_limit else rng.uniform(0.5, 0.93)) * scale
     # rows wide enough, and prices small enough, for most successors to land INSIDE the row (not on its clamped ends): a unit
-    # sold moves the balance by 5 .. 60 keys, the row has 1500 .. 5000 of them
+    # sold moves the balance by 5 .. 60 keys, the row has 1500 .. 5000 of them.  (Not in every instance: in seeds 4 and 5 every
+    # successor clamps to the last key of its row -- tests/test_scrambled_inputs.py measures it, tests/scrambled.py drops them.)
     nc = int(rng.integers(1500, 5000))
     family4 = bool(rng.integers(0, 4) == 0)
     if family4:

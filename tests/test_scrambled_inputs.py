@@ -1,0 +1,137 @@
+"""CPU side of the scrambled-successor tests (tests/scrambled.py): the condition that keeps the GPU tests from being vacuous,
+the contrast with the solved tables, and oracle.period against the host lambdas on arbitrary successor tables."""
+import sys
+
+import numpy as np
+import pytest
+
+import cases
+import scrambled
+from stochastic_inventory_amd.functors import SurvivalFunctor
+from stochastic_inventory_amd.states import OptDirection
+
+DBL_MAX = sys.float_info.max
+
+
+def _instances():
+    for group, (make, seeds) in scrambled.generators().items():
+        yield group, [(s, make(s)) for s in seeds]
+    yield "named", list(scrambled.named_cases().items())
+
+
+def test_kept_pairs_are_the_sensitive_ones(oracle):
+    """Per generator and seed list of the GPU tests: the share of states of period t whose value changes when every row of the
+    scrambled V_{t+1} slips by one cash key, on the oracle.  scrambled.KEPT is exactly the pairs at or above 0.5; at most one
+    third of a generator's tables is dropped, at least 8 remain, and the median over the kept ones is at least 0.75.
+
+    Measured (tables / dropped / median / min over the kept tables):
+        fuzz_f3              24 / 5 / 0.999 / 0.609      wide_cash            20 / 2 / 1.000 / 0.837
+        fuzz_f4              21 / 0 / 0.995 / 0.830      big_cash             14 / 4 / 0.997 / 0.973
+        fuzz_f5               9 / 0 / 1.000 / 0.531      big_cash_past_limit  14 / 4 / 0.997 / 0.973
+        fuzz_f6              22 / 3 / 0.812 / 0.581      big_f5               10 / 1 / 1.000 / 0.914
+        xr                   18 / 0 / 0.976 / 0.543      wide_survival        24 / 0 / 0.915 / 0.737
+        named                29 / 0 / 1.000 / 0.996
+    The tables that stay insensitive are those whose every successor clamps to the last key of the row (large-magnitude seeds
+    4 and 5, within and past the limit: sensitivity 0.000).  big_cash_past_limit runs seeds 0-7: seeds 0-3 alone leave 7."""
+    for group, instances in _instances():
+        for key, w in instances:
+            P = scrambled.reference(oracle, w)["P"]
+            for t in range(1, w.T + 1):
+                assert scrambled.row_length(P, t) == P.grids[t - 1].nc, f"{group} {w.name} t={t}"
+        m = scrambled.measure(oracle, instances)
+        keep = [(k, t) for k, t, s in m if s >= scrambled.THRESHOLD]
+        sens = [s for _, _, s in m if s >= scrambled.THRESHOLD]
+        print(f"{group}: tables {len(m)}, dropped {len(m) - len(keep)}, median {np.median(sens):.3f}, min {min(sens):.3f}")
+        assert keep == scrambled.KEPT[group], group
+        assert len(m) - len(keep) <= scrambled.MAX_DROPPED * len(m), group
+        assert len(keep) >= scrambled.MIN_KEPT, group
+        assert np.median(sens) >= scrambled.MIN_MEDIAN, group
+
+
+def test_solved_large_magnitude_tables_cannot_see_a_slipped_key(oracle):
+    """Why the scrambled tests exist: on the tables the recursion itself produces for make_large_magnitude_cash_instance(0..7),
+    a slip of one key in every gather changes at most 5 % of the states of any period (measured: none).  If a change of the
+    generator makes this fail, test_large_magnitude_cash_shortcuts_bit_exact has become sensitive by itself."""
+    import test_gpu_fuzz as fz
+    for seed in range(8):
+        w = fz.make_large_magnitude_cash_instance(seed)
+        ref = scrambled.reference(oracle, w)
+        for t in range(1, w.T):
+            assert scrambled.slip_sensitivity(ref["P"], t, ref["V"][t]) <= 0.05, f"{w.name} t={t}"
+
+
+def test_scramble_and_slip():
+    rng = np.random.default_rng(1)
+    for n, lo, hi in ((1, 0.0, 0.0), (7, -3.0, -3.0), (1000, -2.5e6, 4.0e6), (50000, 0.0, 1.0)):
+        v = scrambled.scramble(n, lo, hi, rng)
+        assert v.shape == (n,) and v.min() >= lo and v.max() < lo + max(hi - lo, 1.0)
+    v = np.arange(12.0)
+    assert np.array_equal(scrambled.slip(v, 4), [1, 2, 3, 3, 5, 6, 7, 7, 9, 10, 11, 11])
+    assert np.array_equal(v, np.arange(12.0))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# oracle.period on an arbitrary V_{t+1} against a literal loop over the host lambdas
+# ---------------------------------------------------------------------------------------------------------------
+def _survival_quantiser(long_division):
+    w = cases.f6_survival_gamma(T=3)
+    f = w.functor
+    w.functor = SurvivalFunctor(**{**f.__dict__, "cashRoundMult": 10.0, "cashRoundDiv": 10.0, "cashRoundIntDiv": long_division})
+    w.name = f"f6_survival_gamma_tenths_{'long' if long_division else 'double'}_division"
+    return w
+
+
+def _lambda_cases():
+    out = [make for make in cases.TINY if make().desc().family in (3, 4, 5, 6)]
+    out.append(lambda: cases.f6_survival(T=3))
+    out += [lambda: _survival_quantiser(False), lambda: _survival_quantiser(True)]
+    return out
+
+
+@pytest.mark.parametrize("make", _lambda_cases(), ids=lambda m: m().name)
+def test_oracle_period_equals_the_host_lambdas_on_scrambled_tables(sia, oracle, make):
+    """P.period(t, scrambled) against feasibleActions / immediateValue / stateTransition in the recursion's own order (first
+    best action wins; p * gamma * V for the cash families; the survival form of pyref.surv_recursion for F6: a bankrupt
+    successor is worth 0, and the period-T term is [final cash >= 0]), V_{t+1} looked up by state_index: values and action
+    indices bit for bit.  Every state of the small grids, 150 states drawn at random (and the two corner states) of the larger."""
+    import __graft_entry__ as g
+    g.build()
+    w = make()
+    f, T = w.functor, w.T
+    ref = scrambled.reference(oracle, w)
+    P = ref["P"]
+    survival = w.desc().family == 6
+    gamma = float(getattr(f, "discountFactor", 1.0))
+    rng = np.random.default_rng(11)
+    with sia.SdpEngine(w.desc(), w.pmf, w.overhead()) as eng:
+        for t in range(T, 0, -1):
+            if t == T:
+                v_next, want_v, want_a = None, ref["V"][T - 1], ref["pol"][T - 1]
+            else:
+                v_next, want_v, want_a = ref["scrambled"][t]
+            x, cash, preq = P.state_arrays(t)
+            pick = np.arange(len(x)) if len(x) <= 400 else np.unique(np.append(rng.integers(0, len(x), size=150), [0, len(x) - 1]))
+            for i in pick:
+                s = f.make_state(t, float(x[i]), float(cash[i]), float(preq[i]))
+                val, best = (DBL_MAX if w.direction == OptDirection.MIN else -DBL_MAX), 0
+                for k, action in enumerate(f.feasibleActions(s, T)):
+                    q = 0.0
+                    for d, p in np.asarray(w.pmf[t - 1]).tolist():
+                        imm = f.immediateValue(s, action, d, T)
+                        if survival:
+                            if t == T:
+                                q += p * (1 if s.getIniCash() + imm >= 0 else 0)
+                        else:
+                            q += p * imm
+                        if t < T:
+                            ns = f.stateTransition(s, action, d, T)
+                            if survival and ns.getIniCash() < 0:
+                                nv = 0.0
+                            else:
+                                j = eng.state_index(t + 1, *f.tuple_of(ns))
+                                assert 0 <= j < len(v_next), f"{w.name} t={t} state {i}: successor off the grid"
+                                nv = float(v_next[j])
+                            q += p * gamma * nv
+                    if (q < val) if w.direction == OptDirection.MIN else (q > val):
+                        val, best = q, k
+                assert best == want_a[i] and val == want_v[i], f"{w.name} t={t} state {i}: ({val}, {best}) != ({want_v[i]}, {want_a[i]})"
