@@ -865,6 +865,51 @@ int sdpgpu_batch_simulate_ss(sdpgpu_batch* b, int32_t levels, const double* ss, 
 int sdpgpu_batch_simulate_ss_sampled(sdpgpu_batch* b, int32_t levels, const double* ss, int32_t n_paths, uint64_t seed,
                                      const double* ini_x, double* out_mean, double* out_sum);
 
+/* ---- structure checks: G(y) rows, K- and CK-convexity ------------------------------------------------------------------
+ * The reference's own validation idiom: after a solve the drivers run sdp.inventory.CheckKConvexity on a row of values --
+ * ThreeLevelFitsSTest.main (:146-159) checkCK on V_1(x), x = 0 .. 100, the verdict being the last column of its CSV row;
+ * CLSPforDraw.main (:144-182) check on G(y), built by a second Recursion whose period 1 is special; WorkforcePlanning.main
+ * (:208-209) likewise.  Additive to ABI 6.
+ *
+ * A row is g[0 .. n): fp64 values at consecutive grid points (the reference's xLength, taken from the first and last abscissa,
+ * is n for the unit-spaced rows every caller builds).  Both checks evaluate, in fp64, left to right, without FMA,
+ *     t = g_mid - g_near;  t = (double)mult * t;  t = t / (double)div;  rhs0 = g_mid + t;  lhs = g_far + K
+ * and a triple PASSES iff lhs > rhs0 - 0.1; anything else -- equality, a NaN on either side -- is a violation, and the check
+ * ends at the FIRST one in loop order.
+ *   kind 0, check   (CheckKConvexity.java:39-68): a = 0 .. n-1, b = 0 .. a-1, c = 0 .. b-1; far, mid, near = g[a], g[b], g[c];
+ *                   mult = a - b, div = b - c; (i0, i1, i2) = (a, b, c).
+ *   kind 1, checkCK (:6-36): y = 0 .. n-1, z = 0 .. capacity-1, b = 1 .. capacity-1, skipping y - b <= 0 and y + z >= n;
+ *                   far, mid, near = g[y+z], g[y], g[y-b]; mult = z, div = b; (i0, i1, i2) = (y, z, b).
+ * holds = 1: no triple violates (rows without any triple hold), the indices are -1 and both doubles 0.0.  holds = 0:
+ * (i0, i1, i2) is the first violating triple, lhs and rhs the two numbers the reference prints there (rhs without the - 0.1). */
+typedef struct sdpgpu_convexity {
+  int32_t holds;
+  int32_t i0, i1, i2;
+  double lhs;
+  double rhs;
+} sdpgpu_convexity;
+/* One row on the host (no device; the plain loops): what the device entry point is held to, bit for bit.  kind outside
+ * {0, 1}, n < 0, a null pointer: SDPGPU_ERR_ARG through sdpgpu_batch_last_error(NULL). */
+int sdpgpu_check_convexity(int32_t kind, const double* g, int64_t n, double K, int32_t capacity, sdpgpu_convexity* out);
+/* G_period(y) of one instance of a solved batch, y over the instance's grid (CLSPforDraw.java:147-170, its period 1
+ * generalised to any period): the cost of STANDING at level y -- sum over the demand index j, ascending, of
+ * p_j * (((0.0 + v*y) + h*max(y - d_j, 0)) + pi*max(d_j - y, 0)), then for period < T  p_j * V_{period+1}(clamp(y - d_j)), the
+ * clamp as the family's (upper bound first).  The rows of ALL instances and periods are computed on the device at the first
+ * request after a solve and kept there; the call copies n <= num_states values of one row.  SDPGPU_ERR_STATE before a solve,
+ * and for a period whose V_{period+1} was overwritten (store_all_values = 0 keeps G_1 and G_T). */
+int sdpgpu_batch_gy(sdpgpu_batch* b, int32_t instance, int32_t period, double* out, int64_t n);
+/* CheckKConvexity on one row of EVERY instance of a solved batch, in one kernel launch: kind as above; source 0 = the value
+ * rows V_period (ThreeLevelFitsSTest.java:146-159), 1 = the rows G_period.  x_lo / x_hi (n each, or both NULL = every
+ * instance's whole grid): the window of inventory levels x_lo[i] .. x_hi[i] of instance i, both grid points of ITS grid with
+ * x_lo <= x_hi, else SDPGPU_ERR_ARG naming the instance (the driver's call is 0 and 100 for all).  K NULL: each instance's
+ * fixed_order_cost.  capacity NULL: (int)max_order_quantity of the instance, which needs step == 1 (for kind 1: SDPGPU_ERR_ARG
+ * otherwise, asking for explicit capacities; kind 0 reads no capacity).  A window of more than 8192 points is
+ * SDPGPU_ERR_UNSUPPORTED.  out: n structs, written only when the call succeeds.  Bit for bit sdpgpu_check_convexity on the
+ * read-back rows (one predicate function for host and device; a violating triple is reduced as a 64-bit integer key that sorts
+ * like the loop order, so the first one wins whatever the order of the workgroups).  SDPGPU_ERR_STATE before a solve. */
+int sdpgpu_batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t period, const double* x_lo,
+                                 const double* x_hi, const double* K, const int32_t* capacity, sdpgpu_convexity* out);
+
 /* ---- sampled simulation on a handle: demand paths drawn ON the device, rolled and reduced there ------------------------
  * What every driver does after its solve -- `new Simulation(distributions, sampleNum, recursion)
  * .simulateSDPGivenSamplNum(initialState)` (Simulation.java:53-74; CashSimulation.java:85-118 for the cash classes;

@@ -6,7 +6,7 @@ The directory name carries a hyphen (it is fixed by the build contract); import 
 """
 from . import _abi
 from ._abi import (FAMILY_BACKORDER, FAMILY_CASH, FAMILY_CASH_LEADTIME, FAMILY_LEADTIME, FAMILY_OVERDRAFT,
-                   FAMILY_STAFF, FAMILY_SURVIVAL, KERNEL_AUTO, KERNEL_GATHER, KERNEL_WINDOW, SdpgpuBatchPlan, SdpgpuBatchStats, SdpgpuDesc, SdpgpuError, SdpgpuStats, desc_defaults)
+                   FAMILY_STAFF, FAMILY_SURVIVAL, KERNEL_AUTO, KERNEL_GATHER, KERNEL_WINDOW, SdpgpuBatchPlan, SdpgpuBatchStats, SdpgpuConvexity, SdpgpuDesc, SdpgpuError, SdpgpuStats, desc_defaults)
 from .batch import SdpBatch
 from .engine import SdpEngine
 from .fitss import FitsS
@@ -18,6 +18,7 @@ from .pmf import BinomialDist, DiscreteDistribution, GammaDist, GetPmf, NormalDi
 from .recursion import CLSP, CashLeadtimeRecursion, CashRecursion, CashRecursionXR, LeadtimeRecursion, Recursion, RecursionBatch, RiskRecursion
 from .simulation import RiskSimulation, Sampling, SimulateFitsS, Simulation, SimulationBatch
 from .workforce import StaffFunctor, StaffRecursion, StaffState
+from .structure import CheckKConvexity
 from .states import CashLeadtimeState, CashState, CashStateXR, LeadtimeState, OptDirection, RiskState, State
 
 __all__ = [
@@ -28,6 +29,6 @@ __all__ = [
     "multilead_solve", "multicash_solve", "multixr_solve", "MultiLeadResult", "Actions", "CashRecursionMulti",
     "CashRecursionMultiLead", "CashRecursionMultiXR", "CashStateMulti", "CashStateMultiLead", "CashStateMultiXR",
     "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "SimulationBatch", "RiskSimulation", "Sampling",
-    "FitsS", "SimulateFitsS",
+    "FitsS", "SimulateFitsS", "CheckKConvexity", "SdpgpuConvexity",
     "State", "LeadtimeState", "CashState", "CashStateXR", "CashLeadtimeState", "RiskState", "OptDirection", "java_round",
 ]

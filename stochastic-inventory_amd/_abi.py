@@ -135,6 +135,12 @@ class SdpgpuBatchPlan(C.Structure):
                 ("max_chunks", C.c_int32), ("min_chunks", C.c_int32), ("tasks", C.c_int64), ("lds_bytes", C.c_int64)]
 
 
+class SdpgpuConvexity(C.Structure):
+    """struct sdpgpu_convexity (include/sdpgpu.h)."""
+
+    _fields_ = [("holds", C.c_int32), ("i0", C.c_int32), ("i1", C.c_int32), ("i2", C.c_int32), ("lhs", C.c_double), ("rhs", C.c_double)]
+
+
 def desc_defaults() -> SdpgpuDesc:
     """Python twin of sdpgpu_desc_init (usable without loading the library)."""
     d = SdpgpuDesc()
@@ -348,6 +354,9 @@ EXPORTS = {
     "sdpgpu_batch_fit_ss": (C.c_int, [_P, C.c_int32, _DP]),
     "sdpgpu_batch_simulate_ss": (C.c_int, [_P, C.c_int32, _DP, C.c_int32, _DP, C.c_int64, _DP, _DP, _DP]),
     "sdpgpu_batch_simulate_ss_sampled": (C.c_int, [_P, C.c_int32, _DP, C.c_int32, C.c_uint64, _DP, _DP, _DP]),
+    "sdpgpu_check_convexity": (C.c_int, [C.c_int32, _DP, C.c_int64, C.c_double, C.c_int32, C.POINTER(SdpgpuConvexity)]),
+    "sdpgpu_batch_gy": (C.c_int, [_P, C.c_int32, C.c_int32, _DP, C.c_int64]),
+    "sdpgpu_batch_check_convexity": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP, _IP, C.POINTER(SdpgpuConvexity)]),
     "sdpgpu_set_sampler": (C.c_int, [_P, C.c_int32, C.POINTER(SdpgpuDistSpec)]),
     "sdpgpu_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_double,
                                           C.POINTER(SdpgpuSimResult), _DP, C.POINTER(C.c_uint8)]),

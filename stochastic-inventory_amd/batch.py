@@ -13,7 +13,7 @@ from typing import Sequence
 import numpy as np
 
 from . import _abi
-from ._abi import SdpgpuBatchPlan, SdpgpuBatchStats, SdpgpuDesc, SdpgpuError
+from ._abi import SdpgpuBatchPlan, SdpgpuBatchStats, SdpgpuConvexity, SdpgpuDesc, SdpgpuError
 from .engine import _dp, _ip, split_pmf
 
 
@@ -245,3 +245,35 @@ class SdpBatch:
         self._check(self._lib.sdpgpu_batch_simulate_ss_sampled(self._b, int(levels), rule_p, int(n_paths), C.c_uint64(seed & (2**64 - 1)),
                                                                ini_p, _dp(mean), _dp(sums) if sums is not None else None))
         return self._sim_result(mean, sums, want_sums)
+
+    # ---- structure checks (sdpgpu_batch_gy / _check_convexity; CheckKConvexity.java, CLSPforDraw.java:147-170) ----
+    def gy(self, i: int, period: int) -> np.ndarray:
+        """G_period(y) of instance i over its grid: the cost of standing at level y (CLSPforDraw's second Recursion for any
+        period), computed for all instances on the device at the first request after a solve."""
+        out = np.empty(self.num_states_of(i), dtype=np.float64)
+        self._check(self._lib.sdpgpu_batch_gy(self._b, i, period, _dp(out), len(out)))
+        return out
+
+    def _per_instance(self, v, dtype):
+        """A scalar for all instances or one value each -> a contiguous [n] array (None stays None: the library's default)."""
+        return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (self.n,)))
+
+    def check_convexity(self, kind: int, source="values", period: int = 1, x_lo=None, x_hi=None, K=None, capacity=None) -> np.ndarray:
+        """CheckKConvexity.check (kind 0) or checkCK (kind 1) on one row of EVERY instance, in one kernel launch: the rows
+        V_period (source "values") or G_period ("gy"), over the inventory window x_lo .. x_hi (scalars or one per instance;
+        None = the whole grid), with K (None = each instance's fixed ordering cost) and capacity (None = its order limit).
+        Returns a structured array [n] with the fields holds, i0, i1, i2, lhs, rhs of sdpgpu_convexity."""
+        from .structure import CONVEXITY_DTYPE
+        src = {"values": 0, "gy": 1}.get(source, source)
+        if not isinstance(src, (int, np.integer)):
+            raise ValueError(f"source {source!r}: 'values' or 'gy'")
+        if (x_lo is None) != (x_hi is None):
+            raise ValueError("x_lo and x_hi are given together, or neither")
+        lo, hi = self._per_instance(x_lo, np.float64), self._per_instance(x_hi, np.float64)
+        k, cap = self._per_instance(K, np.float64), self._per_instance(capacity, np.int32)
+        out = np.zeros(self.n, dtype=CONVEXITY_DTYPE)
+        assert out.itemsize == C.sizeof(SdpgpuConvexity)
+        self._check(self._lib.sdpgpu_batch_check_convexity(
+            self._b, int(kind), int(src), int(period), _dp(lo) if lo is not None else None, _dp(hi) if hi is not None else None,
+            _dp(k) if k is not None else None, _ip(cap) if cap is not None else None, out.ctypes.data_as(C.POINTER(SdpgpuConvexity))))
+        return out

@@ -9,6 +9,7 @@
 #include "sdp_batch.hpp"
 #include "sdp_batch_sim.hpp"
 #include "sdp_fitss.hpp"
+#include "sdp_structure.hpp"
 
 namespace sdpgpu_detail {
 int validate(const sdpgpu_desc& d);                 // sdpgpu.hip
@@ -77,6 +78,10 @@ struct sdpgpu_batch {
   // ---- (s, S) level rules (sdp_fitss.hpp) ----
   sdp::FitPair* d_fit_pairs = nullptr;  // [i * T + t]: the reachable slice of every (instance, period)
   double* d_fit = nullptr;              // the last device fit, N x T x 2*levels (sized for three levels)
+  // ---- structure checks (sdp_structure.hpp) ----
+  double* d_gy = nullptr;               // the G rows, laid out as the policy rows; made on first request after a solve
+  sdp::GyPair* d_gy_pairs = nullptr;    // [i * T + t]
+  bool gy_valid = false;
   std::string err;
 };
 
@@ -599,6 +604,8 @@ void sdpgpu_batch_destroy(sdpgpu_batch* b) {
     if (b->d_sim_scratch) (void)hipFree(b->d_sim_scratch);
     if (b->d_fit_pairs) (void)hipFree(b->d_fit_pairs);
     if (b->d_fit) (void)hipFree(b->d_fit);
+    if (b->d_gy) (void)hipFree(b->d_gy);
+    if (b->d_gy_pairs) (void)hipFree(b->d_gy_pairs);
     if (b->sim_ev0) (void)hipEventDestroy(b->sim_ev0);
     if (b->sim_ev1) (void)hipEventDestroy(b->sim_ev1);
     if (b->stream && b->own_stream) (void)hipStreamDestroy(b->stream);
@@ -677,6 +684,7 @@ int sdpgpu_batch_solve(sdpgpu_batch* b, int32_t sync) {
     }
     b->period_launches = b->finalize_launches = b->periods_run = 0;
     b->periods_timed = false;
+    b->gy_valid = false;  // (the G rows are those of the tables about to be replaced)
     BHIP_TRY(b, hipEventRecord(b->ev0, b->stream));
     if (b->any_chunked) {  // key rows back to the reduction identity
       const int64_t nk = (int64_t)b->key_elems;
@@ -1293,6 +1301,204 @@ int sdpgpu_batch_simulate_ss(sdpgpu_batch* b, int32_t levels, const double* ss, 
 int sdpgpu_batch_simulate_ss_sampled(sdpgpu_batch* b, int32_t levels, const double* ss, int32_t n_paths, uint64_t seed, const double* ini_x,
                                      double* out_mean, double* out_sum) {
   return sim_entry(b, "sdpgpu_batch_simulate_ss_sampled", SimRule{false, levels, ss}, n_paths, nullptr, 0, true, seed, ini_x, out_mean, out_sum);
+}
+
+}  // extern "C"
+
+// =================================================================================================
+// Structure checks: the G rows of a solved batch, K- and CK-convexity of its rows (sdp_structure.hpp)
+// =================================================================================================
+namespace {
+
+static_assert(sizeof(sdp::ConvexityOut) == sizeof(sdpgpu_convexity) && offsetof(sdp::ConvexityOut, lhs) == offsetof(sdpgpu_convexity, lhs) &&
+                  offsetof(sdp::ConvexityOut, rhs) == offsetof(sdpgpu_convexity, rhs) && offsetof(sdp::ConvexityOut, i2) == offsetof(sdpgpu_convexity, i2),
+              "sdp::ConvexityOut is sdpgpu_convexity field for field");
+
+// G_period exists when V_{period+1} does: every period with store_all_values, else period 1 (V_2 survives) and period T
+bool gy_period_kept(const sdpgpu_batch* b, int32_t period) { return b->d[0].store_all_values || period == b->T || period == 1; }
+
+// the G rows of every (instance, period) on the device, once per solve
+int gy_fill(sdpgpu_batch* b) {
+  if (b->gy_valid) return SDPGPU_OK;
+  const int N = b->N, T = b->T;
+  if (!b->d_gy_pairs) {
+    std::vector<sdp::GyPair> pairs((size_t)N * T);
+    for (int i = 0; i < N; ++i)
+      for (int t = 0; t < T; ++t) {
+        const sdpgpu_desc& d = b->d[(size_t)i];
+        const size_t k = (size_t)i * T + t;
+        sdp::GyPair P{};
+        P.pmf_off = (int64_t)b->pmf_off[k];
+        P.v_next_off = t + 1 < T ? (int64_t)value_row(b, i, t + 1) : -1;
+        P.out_off = (int64_t)policy_row(b, i, t);
+        P.x_min = d.min_inventory;
+        P.x_max = d.max_inventory;
+        P.d0 = b->d0[k];
+        P.h = d.holding_cost;
+        P.pi = d.penalty_cost;
+        P.v = d.unit_order_cost;
+        P.nx = gy_period_kept(b, t + 1) ? b->nxs[(size_t)i] : 0;  // (a row whose V_{t+1} is gone is not made)
+        P.n_demand = (int32_t)b->pmf_p[k].size();
+        pairs[k] = P;
+      }
+    BHIP_TRY(b, hipMalloc((void**)&b->d_gy_pairs, pairs.size() * sizeof(sdp::GyPair)));
+    BHIP_TRY(b, hipMemcpy(b->d_gy_pairs, pairs.data(), pairs.size() * sizeof(sdp::GyPair), hipMemcpyHostToDevice));
+  }
+  if (!b->d_gy) BHIP_TRY(b, hipMalloc((void**)&b->d_gy, std::max<size_t>(b->policy_elems, 1) * sizeof(double)));
+  if (!grid_ok((int64_t)N * T)) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "G rows: %d instances x %d periods are too many for one launch", N, T);
+  const double step = b->d[0].step;
+  hipLaunchKernelGGL(sdp::gy_kernel, dim3((unsigned)(N * T)), dim3(256), 0, b->stream, b->d_gy_pairs, step, 1.0 / step, b->d_pmf, b->d_values,
+                     b->d_gy);
+  BHIP_TRY(b, hipGetLastError());
+  b->gy_valid = true;
+  return SDPGPU_OK;
+}
+
+int convexity_kind_check(sdpgpu_batch* b, const char* who, int32_t kind) {
+  if (kind != sdp::kConvexityCheck && kind != sdp::kConvexityCheckCK)
+    return bfail(b, SDPGPU_ERR_ARG, "%s: kind = %d (0: CheckKConvexity.check, 1: CheckKConvexity.checkCK)", who, kind);
+  return SDPGPU_OK;
+}
+
+int batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t period, const double* x_lo, const double* x_hi, const double* K,
+                          const int32_t* capacity, sdpgpu_convexity* out) {
+  const char* who = "sdpgpu_batch_check_convexity";
+  const int N = b->N;
+  int rc = convexity_kind_check(b, who, kind);
+  if (rc) return rc;
+  if (source != 0 && source != 1) return bfail(b, SDPGPU_ERR_ARG, "%s: source = %d (0: the value rows V_period, 1: the rows G_period)", who, source);
+  if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, b->T);
+  if (!out) return bfail(b, SDPGPU_ERR_ARG, "%s: out is null", who);
+  if ((x_lo == nullptr) != (x_hi == nullptr)) return bfail(b, SDPGPU_ERR_ARG, "%s: x_lo and x_hi are given together, or both NULL (the whole grid)", who);
+  const double step = b->d[0].step;
+  if (kind == sdp::kConvexityCheckCK && !capacity && step != 1.0)
+    return bfail(b, SDPGPU_ERR_ARG, "%s: capacity = NULL means (int)max_order_quantity grid points, which holds with step == 1 only (step %g): pass "
+                 "the capacities explicitly", who, step);
+  if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+  if (source == 0 && !b->d[0].store_all_values && period > 2)
+    return bfail(b, SDPGPU_ERR_STATE, "%s: V_%d was overwritten (store_all_values = 0 keeps two ping-pong tables: periods 1 and 2 survive)", who, period);
+  if (source == 1 && !gy_period_kept(b, period))
+    return bfail(b, SDPGPU_ERR_STATE, "%s: G_%d needs V_%d, which was overwritten (store_all_values = 0 keeps G_1 and G_%d)", who, period, period + 1, b->T);
+  // the rows: a window of every instance's row, its K, its capacity
+  std::vector<int64_t> row_off((size_t)N);
+  std::vector<sdp::ConvexityRow> rows((size_t)N);
+  std::vector<sdp::ConvexityTask> tasks;
+  int n_max = 1;
+  double triples = 0;
+  for (int i = 0; i < N; ++i) {
+    const sdpgpu_desc& d = b->d[(size_t)i];
+    const int64_t nx = b->nxs[(size_t)i];
+    int64_t lo = 0, hi = nx - 1;
+    if (x_lo) {
+      const double a = x_lo[i], c = x_hi[i];
+      if (!(a >= d.min_inventory && c <= d.max_inventory && a <= c) || std::fmod(a, step) != 0 || std::fmod(c, step) != 0)
+        return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d: the window [%g, %g] is not a run of points of its grid [%g, %g]", who, i, a, c,
+                     d.min_inventory, d.max_inventory);
+      lo = (int64_t)((a - d.min_inventory) / step);
+      hi = (int64_t)((c - d.min_inventory) / step);
+    }
+    const int64_t n = hi - lo + 1;
+    if (n > sdp::kConvexityMaxRow)
+      return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: instance %d: a row of %lld points exceeds the kernel's %d (a workgroup keeps the row in LDS): "
+                   "narrow the window", who, i, (long long)n, sdp::kConvexityMaxRow);
+    sdp::ConvexityRow R{};
+    row_off[(size_t)i] = (int64_t)(source == 0 ? value_row(b, i, period - 1) : policy_row(b, i, period - 1)) + lo;
+    R.K = K ? K[i] : d.fixed_order_cost;
+    R.n = (int32_t)n;
+    R.capacity = capacity ? capacity[i] : (int32_t)d.max_order_quantity;
+    R.kind = kind;
+    rows[(size_t)i] = R;
+    n_max = std::max(n_max, (int)n);
+    for (int o = 0; o < (int)n; ++o)
+      triples += (double)(kind == sdp::kConvexityCheck ? sdp::convexity_count<sdp::kConvexityCheck>((int)n, R.capacity, o)
+                                                        : sdp::convexity_count<sdp::kConvexityCheckCK>((int)n, R.capacity, o));
+  }
+  // tiles of about equal triple counts: enough of them to fill the device several times over, none below what pays for
+  // staging its row
+  const int64_t target = (int64_t)std::min(std::max(triples / 16384.0, 16384.0), 4194304.0);
+  for (int i = 0; i < N; ++i) sdp::convexity_tasks(i, kind, rows[(size_t)i].n, rows[(size_t)i].capacity, target, &tasks);
+  if (tasks.size() > (size_t)INT32_MAX / 2) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: too many tasks in one launch", who);
+
+  DeviceScope dev;
+  BHIP_TRY(b, dev.enter(b->device));
+  if (source == 1 && (rc = gy_fill(b))) return rc;
+  const double* base = source == 0 ? b->d_values : b->d_gy;
+  for (int i = 0; i < N; ++i) rows[(size_t)i].g = base + row_off[(size_t)i];
+  Carve c;
+  const size_t o_rows = c.take(rows.size() * sizeof(sdp::ConvexityRow)), o_tasks = c.take(std::max<size_t>(tasks.size(), 1) * sizeof(sdp::ConvexityTask));
+  const size_t o_keys = c.take((size_t)N * 8), o_out = c.take((size_t)N * sizeof(sdp::ConvexityOut));
+  rc = sim_scratch(b, c.at);
+  if (rc) return rc;
+  char* sb = b->d_sim_scratch;
+  sdp::ConvexityRow* d_rows = reinterpret_cast<sdp::ConvexityRow*>(sb + o_rows);
+  sdp::ConvexityTask* d_tasks = reinterpret_cast<sdp::ConvexityTask*>(sb + o_tasks);
+  unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(sb + o_keys);
+  sdp::ConvexityOut* d_out = reinterpret_cast<sdp::ConvexityOut*>(sb + o_out);
+  BHIP_TRY(b, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(sdp::ConvexityRow), hipMemcpyHostToDevice, b->stream));
+  if (!tasks.empty()) BHIP_TRY(b, hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(sdp::ConvexityTask), hipMemcpyHostToDevice, b->stream));
+  const dim3 per_row((unsigned)((N + 255) / 256));
+  hipLaunchKernelGGL(sdp::convexity_key_fill_kernel, per_row, dim3(256), 0, b->stream, d_keys, N);
+  BHIP_TRY(b, hipGetLastError());
+  if (!tasks.empty()) {
+    static LdsMark mark;
+    const size_t smem = sdp::convexity_lds(n_max);
+    BHIP_TRY(b, lds_allow(sdp::convexity_kernel, smem, &mark));
+    hipLaunchKernelGGL(sdp::convexity_kernel, dim3((unsigned)tasks.size()), dim3(256), smem, b->stream, d_rows, d_tasks, d_keys);
+    BHIP_TRY(b, hipGetLastError());
+  }
+  hipLaunchKernelGGL(sdp::convexity_finish_kernel, per_row, dim3(256), 0, b->stream, d_rows, d_keys, N, d_out);
+  BHIP_TRY(b, hipGetLastError());
+  std::vector<sdp::ConvexityOut> host((size_t)N);  // (out is written only once everything has succeeded)
+  BHIP_TRY(b, hipMemcpyAsync(host.data(), d_out, host.size() * sizeof(sdp::ConvexityOut), hipMemcpyDeviceToHost, b->stream));
+  BHIP_TRY(b, hipStreamSynchronize(b->stream));
+  std::memcpy(out, host.data(), host.size() * sizeof(sdp::ConvexityOut));
+  return SDPGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdpgpu_check_convexity(int32_t kind, const double* g, int64_t n, double K, int32_t capacity, sdpgpu_convexity* out) {
+  g_create_error.clear();
+  return guarded((sdpgpu_batch*)nullptr, "sdpgpu_check_convexity", [&]() -> int {
+    const char* who = "sdpgpu_check_convexity";
+    int rc = convexity_kind_check(nullptr, who, kind);
+    if (rc) return rc;
+    if (!out || n < 0 || (n > 0 && !g)) return bfail(nullptr, SDPGPU_ERR_ARG, "%s: bad argument (g, out, n = %lld)", who, (long long)n);
+    if (n >= (1 << 21)) return bfail(nullptr, SDPGPU_ERR_UNSUPPORTED, "%s: a row of %lld points (below %d)", who, (long long)n, 1 << 21);
+    sdp::ConvexityOut r;
+    sdp::convexity_host(kind, g, (int)n, K, capacity, &r);
+    std::memcpy(out, &r, sizeof r);
+    return SDPGPU_OK;
+  });
+}
+
+int sdpgpu_batch_gy(sdpgpu_batch* b, int32_t instance, int32_t period, double* out, int64_t n) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_gy", [&]() -> int {
+    const char* who = "sdpgpu_batch_gy";
+    int rc = read_check(b, who, instance, period, out, n, false);
+    if (rc) return rc;
+    if (!gy_period_kept(b, period))
+      return bfail(b, SDPGPU_ERR_STATE, "%s: G_%d needs V_%d, which was overwritten (store_all_values = 0 keeps G_1 and G_%d)", who, period, period + 1, b->T);
+    DeviceScope dev;
+    BHIP_TRY(b, dev.enter(b->device));
+    rc = gy_fill(b);
+    if (rc) return rc;
+    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipMemcpy(out, b->d_gy + policy_row(b, instance, period - 1), (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return SDPGPU_OK;
+  });
+}
+
+int sdpgpu_batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t period, const double* x_lo, const double* x_hi,
+                                 const double* K, const int32_t* capacity, sdpgpu_convexity* out) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  return guarded(b, "sdpgpu_batch_check_convexity",
+                 [&]() -> int { return batch_check_convexity(b, kind, source, period, x_lo, x_hi, K, capacity, out); });
 }
 
 }  // extern "C"

@@ -479,3 +479,18 @@ class RecursionBatch:
             q = self._policy[(i, period)][idx].astype(np.float64) * f.stepSize
             rows.append(np.stack([np.full(len(idx), float(period)), x, q], axis=1))
         return np.concatenate(rows, axis=0)
+
+    def _check_convexity(self, kind, source, period, x_lo, x_hi, fixOrderCost, capacity):
+        self._solve()
+        return self._batch.check_convexity(kind, source=source, period=period, x_lo=x_lo, x_hi=x_hi, K=fixOrderCost, capacity=capacity)
+
+    def checkKConvexity(self, source="values", period: int = 1, x_lo=None, x_hi=None, fixOrderCost=None):
+        """CheckKConvexity.check (CheckKConvexity.java:39-68) on V_period ("values") or G_period ("gy") of every instance
+        over the window x_lo .. x_hi, on the device in one launch: the reference's return value per instance."""
+        return [bool(h) for h in self._check_convexity(0, source, period, x_lo, x_hi, fixOrderCost, None)["holds"]]
+
+    def checkCK(self, source="values", period: int = 1, x_lo=None, x_hi=None, fixOrderCost=None, capacity=None):
+        """CheckKConvexity.checkCK (:6-36; ThreeLevelFitsSTest.java:146-159 is source "values", period 1, window 0 .. 100,
+        the instance's own fixedOrderingCost and maxOrderQuantity): "CK convexity holds" or "not CK convex" per instance."""
+        from .structure import CK_FAILS, CK_HOLDS
+        return [CK_HOLDS if h else CK_FAILS for h in self._check_convexity(1, source, period, x_lo, x_hi, fixOrderCost, capacity)["holds"]]

@@ -12,8 +12,15 @@ One process, one stream of its own, HIP events beside a synchronised host clock.
       only route the batch offered before for the fit and the rule rollout: read the policy rows back (sdpgpu_batch_policy),
       fit with the plain-Python twin of tests/fitss_twin.py and roll the rule out in numpy, path-vectorised, on demands from
       sample_demands -- on every `--host-stride`-th instance, scaled to 810
+  E   D + check_convexity(kind=1, source="values", period=1, x_lo=0, x_hi=100): the loop body through :159, the CSV row's
+      last column (CheckKConvexity.checkCK on V_1(x), x = 0 .. 100) included
 
-A sample is as many back-to-back sweeps as fill the window, divided by their number; samples alternate A, B, C, D, A, B, C, D, ...
+The same run times a heavy case of its own: CheckKConvexity.check over the WHOLE grid (1101 points, 2.2e8 triples a row), on
+G, for all six periods of all 810 instances -- six launches, by HIP events -- and beside it the host route: sdpgpu_batch_gy
+read-back plus sdpgpu_check_convexity in one thread, on every `--host-stride`-th instance, scaled to 810.  Its samples go to
+`--convexity-out` (profiles/batch_convexity.json).
+
+A sample is as many back-to-back sweeps as fill the window, divided by their number; samples alternate A, B, C, D, E, A, ...
 after a warm-up.  Before anything is timed the two routes are compared bit for bit (initial values and actions of all 810, the
 period-1 tables of one instance per shape).
 
@@ -159,6 +166,7 @@ def main():
     ap.add_argument("--levels", type=int, default=3, help="row D: the driver (1, 2, 3: One-, Two-, ThreeLevelFitsSTest)")
     ap.add_argument("--host-stride", type=int, default=30, help="row D's host route runs on every n-th instance and is scaled")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_fitss_sweep.json"))
+    ap.add_argument("--convexity-out", default=os.path.join(ROOT, "profiles", "batch_convexity.json"))
     ap.add_argument("--trace-b", action="store_true", help="run B three times and leave (for a kernel trace)")
     ap.add_argument("--uniform", default="", help="time CLSPTesting's uniform batch only and write the samples to this file")
     ap.add_argument("--uniform-parent", default="", help="comma-separated --uniform files of the parent commit")
@@ -234,7 +242,13 @@ def main():
         gaps["rule"] = (rule_mean - final) / final
         gaps["table"] = (table_mean - final) / final
 
-    runs = (("A", run_a), ("B", run_b), ("C", run_c), ("D", run_d))
+    verdict = {}
+
+    def run_e():
+        run_d()
+        verdict["ck"] = ragged.check_convexity(1, source="values", period=1, x_lo=0.0, x_hi=100.0)
+
+    runs = (("A", run_a), ("B", run_b), ("C", run_c), ("D", run_d), ("E", run_e))
     sweeps = {k: max(1, int(np.ceil(args.window * 1e3 / timed(stream, f, 2)[0]))) for k, f in runs}
     rows = {k: [] for k, _ in runs}
     for k, f in runs:  # warm-up at the timed length
@@ -262,6 +276,66 @@ def main():
         host_s.append(sec * 1e3 * n / len(sub))
     rules_equal = bool(np.array_equal(h_rules, dev_rules[sub]))
     sums_equal = bool(np.array_equal(h_sums, dev_sums[sub]))
+
+    # ---- the heavy case: check over the whole grid, on G, all periods of all instances ----------------------------------
+    from stochastic_inventory_amd.structure import check_row
+    T = ragged.T
+    heavy_res = {}
+
+    def heavy():
+        for t in range(1, T + 1):
+            heavy_res[t] = ragged.check_convexity(0, source="gy", period=t)
+
+    nx = ragged.num_states_of(0)
+    row_triples = nx * (nx - 1) * (nx - 2) // 6
+    timed(stream, heavy, 1)  # warm-up (the G rows are made here)
+    heavy_s = [timed(stream, heavy, 1) for _ in range(args.samples)]
+    heavy_holds = int(sum(int(heavy_res[t]["holds"].sum()) for t in heavy_res))
+    heavy_first = sorted({(int(r["i0"]), int(r["i1"]), int(r["i2"])) for t in heavy_res for r in heavy_res[t] if not r["holds"]})
+    # A check ends at its first violation, so only a row that HOLDS costs all its triples.  The rate comes from the same six
+    # launches with K = 1e12 for every instance: every row holds, every triple is evaluated.
+    full_res = {}
+
+    def full():
+        for t in range(1, T + 1):
+            full_res[t] = ragged.check_convexity(0, source="gy", period=t, K=1.0e12)
+
+    timed(stream, full, 1)
+    full_s = [timed(stream, full, 1) for _ in range(args.samples)]
+    full_holds = int(sum(int(full_res[t]["holds"].sum()) for t in full_res))
+    triples = n * T * row_triples
+    # the host route: the G rows back, one thread of sdpgpu_check_convexity; a sample = one instance's six rows, scaled
+    heavy_host, heavy_equal = [], True
+    for i in sub:
+        t0 = time.perf_counter()
+        own = [check_row(0, ragged.gy(i, t), ws[i].functor.fixedOrderingCost) for t in range(1, T + 1)]
+        heavy_host.append((time.perf_counter() - t0) * 1e3 * n)
+        for t, r in enumerate(own, start=1):
+            d = heavy_res[t][i]
+            heavy_equal &= (r.holds, r.i0, r.i1, r.i2) == (d["holds"], d["i0"], d["i1"], d["i2"]) and \
+                np.array_equal(np.array([r.lhs, r.rhs]).view(np.uint64), np.array([d["lhs"], d["rhs"]]).view(np.uint64))
+    heavy_dev = statistics.median(x[1] for x in heavy_s)
+    full_dev = statistics.median(x[1] for x in full_s)
+    conv = {
+        "workload": f"CheckKConvexity.check over the whole grid ({nx} points) on G_t, t = 1 .. {T}, of {n} instances: {T} launches",
+        "device": torch.cuda.get_device_name(0), "rows": n * T, "triples_per_row": row_triples,
+        "with_each_instances_K": {
+            "rows_that_hold": heavy_holds, "triples_of_the_rows_that_hold": heavy_holds * row_triples,
+            "distinct_first_violations": len(heavy_first), "first_violations_sample": heavy_first[:8],
+            "ms_device_events": summary([x[1] for x in heavy_s]), "ms_host_clock": summary([x[0] for x in heavy_s]),
+            "host_route": {"what": "sdpgpu_batch_gy read-back + sdpgpu_check_convexity, one thread; one sample = one instance's six rows x "
+                                   "the instance count", "instances_run": len(sub), "scaled_to": n, "ms_scaled": summary(heavy_host),
+                           "equal_the_device_results": bool(heavy_equal)},
+            "host_route_over_device": statistics.median(heavy_host) / heavy_dev},
+        "with_K_1e12_every_row_holds": {
+            "rows_that_hold": full_holds, "triples": triples, "ms_device_events": summary([x[1] for x in full_s]),
+            "ms_host_clock": summary([x[0] for x in full_s]),
+            "triples_per_s_device": triples / (full_dev * 1e-3) if full_holds == n * T else None},
+        "row_E_last_column": {"what": "checkCK on V_1(x), x = 0 .. 100, K and capacity of the instance (ThreeLevelFitsSTest.java:146-159)",
+                              "rows_that_hold": int(verdict["ck"]["holds"].sum()), "rows": n},
+    }
+    with open(args.convexity_out, "w") as f:
+        json.dump(conv, f, indent=1)
 
     # per-period launch times of the ragged batch (events between the launches: a run of its own)
     prof = sia.SdpBatch(descs, pmfs, ragged=True)
@@ -302,6 +376,9 @@ def main():
                                  "path-vectorised numpy rollout, per instance; fit + rule rollout ONLY (no solve, no table rollout)",
                          "instances_run": len(sub), "scaled_to": n, "ms_scaled": summary(host_s),
                          "rules_equal_the_device_fit": rules_equal, "path_sums_equal_the_device_rollout": sums_equal},
+        "E_ms_per_sweep_host": summary(host["E"]), "E_ms_per_sweep_device": summary([x[1] for x in rows["E"]]),
+        "E_minus_D_ms_host": statistics.median(host["E"]) - statistics.median(host["D"]),
+        "E_rows_that_hold": int(verdict["ck"]["holds"].sum()),
         "D_host_route_over_fit_and_rule_part_of_D": statistics.median(host_s) / max(statistics.median(host["D"]) - statistics.median(host["C"]), 1e-9),
         "A_over_B": statistics.median(host["A"]) / statistics.median(host["B"]),
         "B_cells_per_s": cells / (statistics.median(host["B"]) * 1e-3),
@@ -317,11 +394,14 @@ def main():
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps({k: res[k] for k in ("instances", "A_route", "B_plan", "A_over_B", "B_cells_per_s", "max_B_below_min_A")}))
-    for k in "ABCD":
+    for k in "ABCDE":
         print(k, "ms/sweep (host)", res[f"{k}_ms_per_sweep_host"])
     print("B per-period ms", period_ms)
     print("D fit + rule rollout kernels ms", res["D_fit_and_rule_rollout_kernels_ms"], "host route (scaled) ms", res["D_host_route"]["ms_scaled"],
           "rules equal", rules_equal, "sums equal", sums_equal, "gap", res["D_gap_rule"])
+    print("heavy case:", conv["workload"])
+    print(" each instance's K:", json.dumps(conv["with_each_instances_K"]))
+    print(" K = 1e12:", json.dumps(conv["with_K_1e12_every_row_holds"]))
     if "uniform_batch_against_parent" in res:
         print("uniform", json.dumps(res["uniform_batch_against_parent"]))
     return 0
