@@ -961,6 +961,38 @@ int sdpgpu_simulate_sampled(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, in
 int sdpgpu_sample_demands(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t mode, uint64_t first_path, double* out_demand,
                           double* out_u);
 
+/* ---- STAFF family: a hiring rule rolled out on a sampled tree --------------------------------------------------------
+ * What `new SimulatesS(T, dimissionRate).simulatesS(initialState, sS)` does (SimulatesS.java:33-87, the draws of
+ * Sampling.java:110-124 made reproducible), on the device in one call; the two calls per instance of WorkforceTesting.main
+ * (WorkforceTesting.java:112-165) are one call with n_rules = 2.  Definition: DESIGN 4, "Workforce rollout on a sampled tree".
+ *   tree     sample_nums[t] >= 1 children per node of depth t (t = 0 .. T-1), N = their product leaves, 1 <= N <= 2^24.  Leaf
+ *            p passes node n_t = p div stride_t (stride_t = product of sample_nums[s], s > t); child digit j = n_t mod
+ *            sample_nums[t], parent i = n_t div sample_nums[t]: the reference's `i * K + j` order (SimulatesS.java:45-50).
+ *   uniform  of (t, parent i, child j): the latin hypercube of SDPGPU_SAMPLE_LHS above with n = sample_nums[t], instance
+ *            position i, period index t, path j -- every node draws its own hypercube of its children.
+ *   rule     ss != NULL: n_rules (1 .. 64) level rules, ss[(r * T + t) * 2 + {0, 1}] = (s, S) of period t + 1, truncated toward
+ *            zero like Java's (int); the period hires S - x when x < s, else nobody, in every period (SimulatesS.java:55).  Needs
+ *            no solve; the staff number may leave every box of an unclamped handle.  ss == NULL (n_rules = 1): the handle's
+ *            computed policy table; a staff number outside the period's box ends the leaf with its valid flag clear.
+ *   turnover hireTo = x + hires; hireTo <= 0: 0 (SimulatesS.java:64-67); else from row min(hireTo, n_rows - 1) of the period's
+ *            level pmf, the row the recursion integrates over (StaffRecursion.java:92-95): thresholds = the running fp64 sum of
+ *            the row, the last one +infinity, turnover = #{thresholds <= u}.
+ *   step     the period's cost and the next staff number as the recursion forms them (one fp64 operation per statement, the
+ *            two-sided clamp when the handle clamps); a leaf's sum adds the periods' costs in order.
+ * results[r] (n_rules of them): n_paths = N, n_valid, n_lost = 0, mean and m2 of the rule's leaf sums in the fixed order of
+ * sdpgpu_simulate_sampled (NaN when n_valid < N), kernel_ms of the whole call.  m2 is the SPREAD OF THE LEAF SUMS, not a variance
+ * of the mean: leaves share prefixes of their paths, so m2 / (N (N - 1)) is no standard error.  The counters of the uniforms do
+ * not carry the rule: every rule sees the same uniforms, and a call with R rules returns what R calls with one rule each
+ * return, bit for bit.  Optional outputs: out_sum[r * N + p], out_valid[r * N + p] (1 = valid), out_demand[(r * N + p) * T + t]
+ * (the turnover drawn, -1 in the periods an ended leaf did not reach).
+ * Refusals, all before the first device call and naming the argument: not a STAFF handle SDPGPU_ERR_UNSUPPORTED; world_size
+ * != 1, a level pmf missing, the table rule before a solve SDPGPU_ERR_STATE; sample_nums[t] < 1 or more than 2^24 leaves,
+ * n_rules outside 1 .. 64, an ss entry not finite or outside int32, (int) S < (int) s - 1 (a negative hire), ini_x not an
+ * integer in 0 .. 1e9, ini_x outside period 1's box under the table rule, a negative probability in a level pmf
+ * SDPGPU_ERR_ARG. */
+int sdpgpu_staff_simulate(sdpgpu_handle* h, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
+                          int32_t n_rules, sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid, int32_t* out_demand);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -17,7 +17,7 @@ from .multiitem import (Actions, CashRecursionMulti, CashRecursionMultiLead, Cas
 from .pmf import BinomialDist, DiscreteDistribution, GammaDist, GetPmf, NormalDist, PoissonDist, UniformIntDist, staff_level_pmf
 from .recursion import CLSP, CashLeadtimeRecursion, CashRecursion, CashRecursionXR, LeadtimeRecursion, Recursion, RecursionBatch, RiskRecursion
 from .simulation import RiskSimulation, Sampling, SimulateFitsS, Simulation, SimulationBatch
-from .workforce import StaffFunctor, StaffRecursion, StaffState
+from .workforce import SimulatesS, StaffFunctor, StaffRecursion, StaffState
 from .structure import CheckKConvexity
 from .states import CashLeadtimeState, CashState, CashStateXR, LeadtimeState, OptDirection, RiskState, State
 
@@ -25,7 +25,7 @@ __all__ = [
     "SdpEngine", "SdpBatch", "SdpgpuBatchPlan", "SdpgpuBatchStats", "RecursionBatch", "SdpgpuDesc", "SdpgpuError", "SdpgpuStats", "desc_defaults",
     "BackorderFunctor", "LeadtimeFunctor", "CashFunctor", "CashXRFunctor", "OverdraftFunctor", "CashLeadtimeFunctor", "SurvivalFunctor", "CustomFunctor",
     "Recursion", "CLSP", "LeadtimeRecursion", "CashRecursion", "CashRecursionXR", "CashLeadtimeRecursion", "RiskRecursion",
-    "StaffRecursion", "StaffFunctor", "StaffState", "BinomialDist", "staff_level_pmf",
+    "StaffRecursion", "StaffFunctor", "StaffState", "SimulatesS", "BinomialDist", "staff_level_pmf",
     "multilead_solve", "multicash_solve", "multixr_solve", "MultiLeadResult", "Actions", "CashRecursionMulti",
     "CashRecursionMultiLead", "CashRecursionMultiXR", "CashStateMulti", "CashStateMultiLead", "CashStateMultiXR",
     "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "SimulationBatch", "RiskSimulation", "Sampling",

@@ -361,6 +361,8 @@ EXPORTS = {
     "sdpgpu_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_double,
                                           C.POINTER(SdpgpuSimResult), _DP, C.POINTER(C.c_uint8)]),
     "sdpgpu_sample_demands": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, _DP]),
+    "sdpgpu_staff_simulate": (C.c_int, [_P, _IP, C.c_uint64, C.c_double, _DP, C.c_int32, C.POINTER(SdpgpuSimResult), _DP,
+                                        C.POINTER(C.c_uint8), _IP]),
 }
 
 _lib = None

@@ -201,6 +201,7 @@ struct sdpgpu_handle {
   double* d_staff_val = nullptr;    // partial arg-min rows [group][slab]
   int32_t* d_staff_idx = nullptr;
   size_t staff_part_elems = 0;
+  bool staff_tables_nonneg = false;  // sdpgpu_staff_simulate has found no negative entry in the (by then frozen) level pmfs
   // sdpgpu_set_action_counts: per period the caller's action-list lengths of every grid state (empty: family rule)
   std::vector<std::vector<int32_t>> counts;
   std::vector<int32_t*> d_counts;

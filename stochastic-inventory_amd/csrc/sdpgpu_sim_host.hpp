@@ -149,6 +149,10 @@ int sim_scratch(Owner* o, size_t bytes) {
   return SDPGPU_OK;
 }
 
+// sdpgpu_simsample.hip: the fixed-order reduction of a rollout (sim_reduce_kernel, sim_dev2_kernel of sdp_sim_sampled.hpp) on
+// n device-resident sums and their W = ceil(n / 64) wave partials: d_res[0] = mean, d_res[1] = m2, both NaN when d_cnt[0] < n
+hipError_t launch_sim_moments(hipStream_t st, const double* d_sum, uint32_t n, double* d_part, const unsigned int* d_cnt, double* d_res);
+
 // offsets of the scratch block, every part aligned to 16 bytes
 struct Carve {
   size_t at = 0;

@@ -82,6 +82,22 @@ hipError_t launch_fused(sdpgpu_handle* h, dim3 grid, const sdp::SimPeriod* d_per
 
 }  // namespace
 
+namespace sdpgpu_detail {
+
+// mean = (wave partials in the fixed order) / n; m2 = a second pass over the sums in the same order (which reuses the partials)
+hipError_t launch_sim_moments(hipStream_t st, const double* d_sum, uint32_t n, double* d_part, const unsigned int* d_cnt, double* d_res) {
+  const uint32_t W = (n + 63u) / 64u;
+  hipLaunchKernelGGL(sdp::sim_reduce_kernel, dim3(1), dim3(1024), 0, st, d_part, W, (double)n, d_cnt, n, d_res);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sdp::sim_dev2_kernel, dim3((W + 3) / 4), dim3(256), 0, st, d_sum, n, d_res, d_part);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(sdp::sim_reduce_kernel, dim3(1), dim3(1024), 0, st, d_part, W, 0.0, d_cnt, n, d_res + 1);
+  return hipGetLastError();
+}
+
+}  // namespace sdpgpu_detail
+
 extern "C" {
 
 int sdpgpu_set_sampler(sdpgpu_handle* h, int32_t t, const sdpgpu_dist_spec* spec) {
@@ -237,13 +253,7 @@ int sdpgpu_simulate_sampled(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, in
                              ? launch_fused<true>(h, grid, d_per, d_samp, d_thr, d_val, d_disc, R, idx0, ini, (int)first_k, d_sum, d_flag, d_part, d_cnt)
                              : launch_fused<false>(h, grid, d_per, d_samp, d_thr, d_val, d_disc, R, idx0, ini, (int)first_k, d_sum, d_flag, d_part, d_cnt);
     HIP_TRY(h, e);
-    // mean = (partials in the fixed order) / n; m2 = a second pass over the sums in the same order
-    hipLaunchKernelGGL(sdp::sim_reduce_kernel, dim3(1), dim3(1024), 0, st, d_part, W, (double)n_paths, d_cnt, (uint32_t)n_paths, d_res);
-    HIP_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL(sdp::sim_dev2_kernel, grid, dim3(256), 0, st, d_sum, (uint32_t)n_paths, d_res, d_part);
-    HIP_TRY(h, hipGetLastError());
-    hipLaunchKernelGGL(sdp::sim_reduce_kernel, dim3(1), dim3(1024), 0, st, d_part, W, 0.0, d_cnt, (uint32_t)n_paths, d_res + 1);
-    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, launch_sim_moments(st, d_sum, (uint32_t)n_paths, d_part, d_cnt, d_res));
     HIP_TRY(h, hipEventRecord(h->sim_ev1, st));
     double res[2] = {0, 0};
     unsigned int cnt[2] = {0, 0};

@@ -365,6 +365,42 @@ class SdpEngine:
                                                     C.c_uint64(int(first_path) & (2**64 - 1)), _dp(dem), _dp(u)))
         return dem, u
 
+    def staff_simulate(self, sample_nums, seed: int, ini_x: int, ss=None, *, want_sums: bool = False, want_demands: bool = False):
+        """STAFF family: roll hiring rules out on a sampled tree (sdpgpu_staff_simulate; DESIGN 4, "Workforce rollout on a
+        sampled tree").  sample_nums[t] children per node of depth t; ss = None: the computed policy table (one rule), else
+        (s, S) levels of shape (T, 2) or (R, T, 2).  Returns the list of SdpgpuSimResult, one per rule; with want_sums also
+        (sums[R, N], valid[R, N]); with want_demands also the turnovers drawn, demands[R, N, T] (int32)."""
+        k = np.ascontiguousarray(sample_nums, dtype=np.int32)
+        if k.shape != (self.T,):
+            raise ValueError("sample_nums must have one entry per period")
+        levels, n_rules = None, 1
+        if ss is not None:
+            levels = np.ascontiguousarray(ss, dtype=np.float64)
+            if levels.ndim == 2:
+                levels = levels[None]
+            if levels.ndim != 3 or levels.shape[1:] != (self.T, 2):
+                raise ValueError(f"ss must have shape ({self.T}, 2) or (rules, {self.T}, 2)")
+            n_rules = levels.shape[0]
+        n = 1
+        for v in k.tolist():  # (the library refuses a bad tree; the buffers below only need a size)
+            n *= max(int(v), 1)
+        n = min(n, 1 << 24)
+        rows = min(max(n_rules, 1), 64)
+        res = (_abi.SdpgpuSimResult * max(n_rules, 1))()
+        sums = np.empty((rows, n), dtype=np.float64) if want_sums else None
+        valid = np.empty((rows, n), dtype=np.uint8) if want_sums else None
+        dem = np.empty((rows, n, self.T), dtype=np.int32) if want_demands else None
+        self._check(self._lib.sdpgpu_staff_simulate(
+            self._h, _ip(k), C.c_uint64(int(seed) & (2**64 - 1)), float(ini_x), None if levels is None else _dp(levels), n_rules, res,
+            None if sums is None else _dp(sums), None if valid is None else valid.ctypes.data_as(C.POINTER(C.c_uint8)),
+            None if dem is None else _ip(dem)))
+        out = [list(res)]
+        if want_sums:
+            out += [sums, valid.astype(bool)]
+        if want_demands:
+            out.append(dem)
+        return out[0] if len(out) == 1 else tuple(out)
+
     def stats(self) -> SdpgpuStats:
         st = SdpgpuStats()
         self._check(self._lib.sdpgpu_stats_get(self._h, C.byref(st)))

@@ -2,6 +2,7 @@
 
     workforce.StaffState        src/workforce/StaffState.java:4-35
     workforce.StaffRecursion    src/workforce/StaffRecursion.java:16-118, 262-279
+    workforce.SimulatesS        src/workforce/SimulatesS.java:14-94
 
 Same names, argument meaning and behaviour for the path the drivers solve -- `getExpectedValue(StaffState)`
 (WorkforcePlanning.java:104-112, WorkforceTesting.java:116-124): the turnover pmf of a period is picked by the
@@ -196,3 +197,49 @@ class StaffRecursion:
 
     def close(self):
         self._engine.close()
+
+
+class SimulatesS:
+    """workforce.SimulatesS(recursion, T, dimissionRate) -- SimulatesS.java:21-27: the rollout of an (s, S) hiring rule on a
+    sampled tree, on the device (SdpEngine.staff_simulate; DESIGN 4, "Workforce rollout on a sampled tree").
+
+    `dimissionRate` is kept for the signature and NOT used: the turnover of a period is drawn from the row of the recursion's own
+    table, pmfs[t][min(hireTo, rows - 1)] -- for the drivers' tables that row IS BinomialDist(hireTo, dimissionRate[t]).  The
+    reference resets its random stream per call (Sampling.resetStartStream); here the draws are a function of `seed`."""
+
+    def __init__(self, recursion: StaffRecursion, T: int, dimissionRate=None, seed: int = 12345):
+        if int(T) != recursion.T:
+            raise ValueError(f"T = {T}, the recursion has {recursion.T} periods")
+        self.recursion = recursion
+        self.T = int(T)
+        self.dimissionRate = dimissionRate
+        self.seed = int(seed)
+        self.stateTransition = recursion.getStateTransitionFunction()
+        self.immediateValue = recursion.getImmediateValueFunction()
+        self.last_results = None
+
+    def defaultSampleNums(self) -> List[int]:
+        """10 children in the first four periods, one from the fifth on (SimulatesS.java:33-41)."""
+        return [10 if t <= 3 else 1 for t in range(self.T)]
+
+    @staticmethod
+    def _ini(iniState) -> int:
+        return int(iniState.iniStaffNum) if isinstance(iniState, StaffState) else int(iniState)
+
+    def simulatesS(self, iniState, optimalsS, sampleNums=None):
+        """Mean of the leaf sums under the level rule optimalsS[t] = (s, S): a float for shape (T, 2), an array for (R, T, 2)
+        (R rules in one launch, on the same uniforms).  The SdpgpuSimResults stay in `last_results`."""
+        ss = np.asarray(optimalsS, dtype=np.float64)
+        k = self.defaultSampleNums() if sampleNums is None else sampleNums
+        res = self.recursion.engine.staff_simulate(k, self.seed, self._ini(iniState), ss)
+        self.last_results = res
+        means = np.array([r.mean for r in res])
+        return float(means[0]) if ss.ndim == 2 else means
+
+    def simulateTable(self, iniState, sampleNums=None) -> float:
+        """The same rollout under the recursion's own policy table (solved first if it has not been)."""
+        self.recursion._lookup(StaffState(1, self.recursion.functor.iniStaffNum))
+        k = self.defaultSampleNums() if sampleNums is None else sampleNums
+        res = self.recursion.engine.staff_simulate(k, self.seed, self._ini(iniState), None)
+        self.last_results = res
+        return float(res[0].mean)
