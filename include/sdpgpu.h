@@ -677,6 +677,20 @@ double sdpgpu_period_ms(sdpgpu_handle* h, int32_t period);
  * not counted yet (the period has not run) or not known per period. */
 int64_t sdpgpu_period_cells(sdpgpu_handle* h, int32_t period);
 
+/* Additive to ABI 6: the screen of the F1 level kernel (a level block whose predecessor stopped at the cut-off is first walked
+ * without the pmf's leading steps).  For period t of the last solve: out[0] = the step its screened blocks started
+ * at (0: the screen was off for the period -- another kernel, the cut-off's gate closed, a leading step that carries more than
+ * 2^-16 of the probability, a forced plan without SDPGPU_F1_SCREEN=1, or SDPGPU_F1_SCREEN=0), then its level blocks summed over
+ * waves: out[1] screened and stopped, out[2] screens that failed (each walked again from step 0), out[3] walked from step 0
+ * (out[1] + out[3] = the blocks of the launch); out[4] the demand steps its waves walked and out[5] those the launch planned
+ * (the period's share of sdpgpu_stats.f1_level_steps_run / _planned).  All 0 for a period the level kernel's cut-off did not
+ * run.  Waits for the handle's stream and copies a few bytes back, as sdpgpu_stats_get does. */
+int sdpgpu_f1_screen_get(sdpgpu_handle* h, int32_t period, int64_t out[6]);
+/* Host arithmetic, no device: the step the screen's rule gives for the pmf of period t -- the largest multiple of 8 (the
+ * level kernel's levels per block) whose leading steps, on the unit-stride layout of the demands, carry at most 2^-16 of the
+ * probability (SDPGPU_F1_SCREEN_LOG2=<e> at create time, a diagnostic: 2^-e); 0 below 8.  Whether a launch uses it is decided at the launch.  -1: bad arguments or no layout. */
+int32_t sdpgpu_f1_screen_start(sdpgpu_handle* h, int32_t period);
+
 /* ---- batched solve: many backorder-family instances, of ONE grid shape or each with its own ----------------------------
  * The reference's parameter sweeps -- capacitated.CLSPTesting.main (CLSPTesting.java:33-141: 10 demand patterns x 2 v x
  * 3 pi x 3 K x 3 coeVar = 540 instances of the grid x in [-500, 500], Q = 0..500, T = 8), LevelFitsS, CLSPforDraw -- build

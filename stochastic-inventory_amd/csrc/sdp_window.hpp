@@ -158,6 +158,29 @@ __global__ __launch_bounds__(256) void window_f1_kernel(WinParams W, const doubl
 // A stopped block skips (d_pad - stop) of its d_pad steps: 3 + 1/S + 1/(64 R) operations per cell and step, as above, over
 // the steps that ran (counted per wave into cut_count[0], the tests into cut_count[1]) plus one compare per cell and test.
 // With CUT off the kernel is the one above, instruction for instruction.
+//
+// THE SCREEN (CUT only; LevelParams::screen_start, a multiple of S, 0 = off; the host: f1_screen_start / f1_screen_on in
+// sdpgpu_window.hip).  The steps in front of the pmf's mass prove nothing about a block that loses; they are walked only
+// because a winner's value is summed from step 0.  Under the cut-off's gate every addend is >= 0, round-to-nearest addition
+// is monotone in both operands and fl(x + 0) = x: replace any addends of a cell by +0.0, in the reference's order, and by
+// induction over the steps the sum is <= the cell's fp64 value.  So the sum over the steps j >= screen_start alone, in
+// order from +0.0, is a lower bound of Q(i, k), and a cell whose bound is STRICTLY greater than its slot can neither win
+// nor tie -- the cut-off's own condition.  A level block is therefore either exact (walked from step 0, as above) or
+// SCREENED: the imm ring set up for step screen_start (its canonical rotation), the sums from +0.0, the product tables
+// from j0 = screen_start (tables and prefetch tags at screen_start + n DB), the tests on their schedule but not before
+// screen_start + S.  A screened block that stops is done, like any stopped block.  One that reaches d_pad has learned
+// nothing: the block is walked again as an exact block, by a second turn of the loop around the table loop (there is one
+// step loop).  A NaN sum compares false, so such a block fails its screen and is walked exactly.
+//   The mode (wave-uniform, scalar registers): a task's first block is exact; a block is screened only while the task's
+// last `need` blocks all stopped, in either mode; a failed screen doubles `need` (up to 8) and starts the count again
+// (the exact walk of the same block counts if it stops), a screen that stopped sets it back to 1.  Where nothing ever
+// stops, no block is screened and the steps are the cut-off's; a run of stopped blocks pays for few failed screens.
+//   The prefetch guess for the next block's first table starts at the step that block is expected to start at.
+//   cut_count[0] counts the steps walked (a failed screen: its own and the exact walk's), cut_count[2..4] the blocks
+// screened and stopped, the screens that failed and the exact walks.
+//   The host screens where the planner chose this kernel by itself.  Under a forced plan (SDPGPU_WIN_LEVEL=1) it does so
+// only with SDPGPU_F1_SCREEN=1: screen_start is 0 there otherwise and the kernel walks the cut-off's schedule step for
+// step, which the device tests of the cut-off count against a CPU twin.  SDPGPU_F1_SCREEN=0 turns it off everywhere.
 // ---------------------------------------------------------------------------------------------
 struct LevelParams {
   int32_t band;       // levels per task (a multiple of S)
@@ -169,6 +192,7 @@ struct LevelParams {
   int32_t y_hi;       // one past the last level: hi + A - 1
   int32_t n_chunks;   // chunk rows: ceil((A - 1) / band) + n_ablocks
   int32_t cut_start;  // CUT: the step of a task's first cut-off test (a multiple of S, >= S)
+  int32_t screen_start;  // CUT: the step a screened level block starts at (a multiple of S; 0: no block is screened)
 };
 
 template <int S>
@@ -268,6 +292,10 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
   // so a block that could have stopped earlier still passes there): where nothing ever stops, one test per block.
   [[maybe_unused]] int cut_first = L.cut_start, cut_dec = S, cut_once = 0;
   [[maybe_unused]] unsigned cut_steps = 0, cut_tests = 0;
+  // CUT: the screen's mode rule (wave-uniform, scalar registers; THE SCREEN above).  scr_run counts the stopped blocks since
+  // the last one that ran to the end or failed its screen; a block is screened when scr_run >= scr_need.
+  [[maybe_unused]] int scr_run = 0, scr_need = 1;
+  [[maybe_unused]] unsigned scr_hit = 0, scr_miss = 0, scr_exact = 0;
 
   for (int y0 = yb; y0 < ye; y0 += S) {
     // Priority by progress, as in f1_cells: the four waves of a workgroup free its LDS only together, and a plan
@@ -276,148 +304,178 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
     if (W.prio_fair) prio_by_progress((unsigned)(y0 - yb), (unsigned)(ye - yb));
     double acc[R][S];
     double imm[R][S];  // ring: at step j, cell s uses imm[r][(s - j) mod S] = c0[r] + M(y0 + s - j)
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const double ms = window_entry<false, false>(W, nullptr, nullptr, y0 + s).x;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        acc[r][s] = 0.0;
-        imm[r][s] = c0[r] + ms;
-      }
-    }
-    [[maybe_unused]] int cut_at = cut_first, cut_fail = 0;
+    [[maybe_unused]] int cut_fail = 0;
     int stop_at = -1;  // CUT: the step the block stopped at
-    for (int j0 = 0; j0 < L.d_pad && stop_at < 0; j0 += DB) {
-      const int nj = min(DB, L.d_pad - j0);
-      // the table of steps j0 .. j0 + nj - 1: lane t forms row t (rows past nj repeat the last step and are not read)
-      __builtin_amdgcn_wave_barrier();
-      const bool fetched = PF && pf_y == y0 && pf_j == j0;  // (wave-uniform)
-      if constexpr (PF) {
-        if (fetched) {
-          // the window goes through a strip at the start of the table region (the table before is dead, and the rows are
-          // written only after every lane has read its S entries)
-          s_row[lane] = level_v_decode<KEYED_IN>(pf_w0);
-          if (lane < DB + S - 1 - 64) s_row[64 + lane] = level_v_decode<KEYED_IN>(pf_w1);
-          __builtin_amdgcn_wave_barrier();
+    // CUT: the step this pass over the block starts at -- L.screen_start for a screened block, 0 for an exact one (and for
+    // the second pass over a block whose screen failed)
+    [[maybe_unused]] int scr_from = 0;
+    if constexpr (CUT) scr_from = scr_run >= scr_need ? L.screen_start : 0;
+    [[maybe_unused]] bool again = false;
+    do {
+      const int j_first = CUT ? scr_from : 0;
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const double ms = window_entry<false, false>(W, nullptr, nullptr, y0 + s - j_first).x;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          acc[r][s] = 0.0;
+          imm[r][s] = c0[r] + ms;
         }
       }
-      if (lane < DB) {
-        const int tt = min(lane, nj - 1);
-        const int j = j0 + tt;
-        double p;
-        double* row = s_row + lane * ROW;
-        double vv[S];
-        if (fetched) {
-          p = pf_p;
+      [[maybe_unused]] int cut_at = max(cut_first, j_first + S);
+      cut_fail = 0;
+      stop_at = -1;
+      // (PF) the step the task's next block is expected to start at: screened if this block stops, as the one before did
+      [[maybe_unused]] int pf_next = 0;
+      if constexpr (CUT && PF) pf_next = pf_stop != INT32_MAX && (j_first > 0 || scr_run + 1 >= scr_need) ? L.screen_start : 0;
+      for (int j0 = j_first; j0 < L.d_pad && stop_at < 0; j0 += DB) {
+        const int nj = min(DB, L.d_pad - j0);
+        // the table of steps j0 .. j0 + nj - 1: lane t forms row t (rows past nj repeat the last step and are not read)
+        __builtin_amdgcn_wave_barrier();
+        const bool fetched = PF && pf_y == y0 && pf_j == j0;  // (wave-uniform)
+        if constexpr (PF) {
+          if (fetched) {
+            // the window goes through a strip at the start of the table region (the table before is dead, and the rows are
+            // written only after every lane has read its S entries)
+            s_row[lane] = level_v_decode<KEYED_IN>(pf_w0);
+            if (lane < DB + S - 1 - 64) s_row[64 + lane] = level_v_decode<KEYED_IN>(pf_w1);
+            __builtin_amdgcn_wave_barrier();
+          }
+        }
+        if (lane < DB) {
+          const int tt = min(lane, nj - 1);
+          const int j = j0 + tt;
+          double p;
+          double* row = s_row + lane * ROW;
+          double vv[S];
+          if (fetched) {
+            p = pf_p;
 #pragma unroll
-          for (int s = 0; s < S; ++s) vv[s] = s_row[DB - 1 - tt + s];
-        } else {
-          p = pmf_p[j];  // (the array ends in kPmfPad zeros: d_pad < D + S stays inside)
+            for (int s = 0; s < S; ++s) vv[s] = s_row[DB - 1 - tt + s];
+          } else {
+            p = pmf_p[j];  // (the array ends in kPmfPad zeros: d_pad < D + S stays inside)
+            if constexpr (FUTURE) {
+#pragma unroll
+              for (int s = 0; s < S; ++s) vv[s] = level_v<KEYED_IN>(W, v_next, k_next, y0 + s - j);
+            }
+          }
+          __builtin_amdgcn_wave_barrier();
+          row[0] = p;
+          row[1] = window_entry<false, false>(W, nullptr, nullptr, y0 - j - 1).x;
           if constexpr (FUTURE) {
 #pragma unroll
-            for (int s = 0; s < S; ++s) vv[s] = level_v<KEYED_IN>(W, v_next, k_next, y0 + s - j);
+            for (int s = 0; s < S; ++s) row[2 + s] = p * vv[s];
           }
         }
         __builtin_amdgcn_wave_barrier();
-        row[0] = p;
-        row[1] = window_entry<false, false>(W, nullptr, nullptr, y0 - j - 1).x;
-        if constexpr (FUTURE) {
-#pragma unroll
-          for (int s = 0; s < S; ++s) row[2 + s] = p * vv[s];
+        // The inputs of the table expected next, in flight under this table's steps: the block's next table if there is one
+        // and (CUT) the block before got that far -- after a block that ran to the end, a full run -- else the first table
+        // of the task's next block.  A wrong guess costs that table its direct loads and touches nothing else.
+        if constexpr (PF) {
+          bool same = j0 + DB < L.d_pad;
+          if constexpr (CUT) same = same && j0 + DB < pf_stop;
+          if (same || y0 + S < ye) prefetch(same ? y0 : y0 + S, same ? j0 + DB : pf_next);
         }
-      }
-      __builtin_amdgcn_wave_barrier();
-      // The inputs of the table expected next, in flight under this table's steps: the block's next table if there is one
-      // and (CUT) the block before got that far -- after a block that ran to the end, a full run -- else the first table
-      // of the task's next block.  A wrong guess costs that table its direct loads and touches nothing else.
-      if constexpr (PF) {
-        bool same = j0 + DB < L.d_pad;
-        if constexpr (CUT) same = same && j0 + DB < pf_stop;
-        if (same || y0 + S < ye) prefetch(same ? y0 : y0 + S, same ? j0 + DB : 0);
-      }
-      // Each step reads the NEXT step's row (a broadcast ds_read_b128 per two doubles) before its own 100 fp64
-      // instructions, which then cover the LDS latency; the row past the block's last step lies inside the wave's region
-      // and is not used.
-      constexpr int NQ = FUTURE ? ROW / 2 : 1;
-      double2 nxt[NQ];
+        // Each step reads the NEXT step's row (a broadcast ds_read_b128 per two doubles) before its own 100 fp64
+        // instructions, which then cover the LDS latency; the row past the block's last step lies inside the wave's region
+        // and is not used.
+        constexpr int NQ = FUTURE ? ROW / 2 : 1;
+        double2 nxt[NQ];
 #pragma unroll
-      for (int u = 0; u < NQ; ++u) nxt[u] = reinterpret_cast<const double2*>(s_row)[u];
+        for (int u = 0; u < NQ; ++u) nxt[u] = reinterpret_cast<const double2*>(s_row)[u];
 #pragma unroll 1
-      for (int t0 = 0; t0 < nj; t0 += S) {
-        if constexpr (CUT) {
-          // (the imm ring is in its canonical rotation here; the slots are the ones the epilogue below updates)
-          if (j0 + t0 >= cut_at) {
-            const int sb = (y0 - yb) - lane + NA - 1;
-            // (`beaten` is a pure conjunction.  With a future term the R thresholds of a level are read together and the
-            // compares ANDed without a short cut -- S LDS round trips per test instead of R S; every slot index lies inside
-            // the wave's slots.  Period T keeps the short cut: the grouped reads cost it the third wave per SIMD, 198 VGPRs.)
-            bool beaten = true;
+        for (int t0 = 0; t0 < nj; t0 += S) {
+          if constexpr (CUT) {
+            // (the imm ring is in its canonical rotation here; the slots are the ones the epilogue below updates)
+            if (j0 + t0 >= cut_at) {
+              const int sb = (y0 - yb) - lane + NA - 1;
+              // (`beaten` is a pure conjunction.  With a future term the R thresholds of a level are read together and the
+              // compares ANDed without a short cut -- S LDS round trips per test instead of R S; every slot index lies inside
+              // the wave's slots.  Period T keeps the short cut: the grouped reads cost it the third wave per SIMD, 198 VGPRs.)
+              bool beaten = true;
 #pragma unroll
-            for (int s = 0; s < S; ++s) {
-              if constexpr (FUTURE) {
-                double th[R];
+              for (int s = 0; s < S; ++s) {
+                if constexpr (FUTURE) {
+                  double th[R];
 #pragma unroll
-                for (int r = 0; r < R; ++r) th[r] = s_val[sb + s - 64 * r];
+                  for (int r = 0; r < R; ++r) th[r] = s_val[sb + s - 64 * r];
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                  const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];  // not a padded action, not action 0
-                  beaten = beaten & (!live | (acc[r][s] > th[r]));
-                }
-              } else {
+                  for (int r = 0; r < R; ++r) {
+                    const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];  // not a padded action, not action 0
+                    beaten = beaten & (!live | (acc[r][s] > th[r]));
+                  }
+                } else {
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                  const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];
-                  beaten = beaten && (!live || acc[r][s] > s_val[sb + s - 64 * r]);
+                  for (int r = 0; r < R; ++r) {
+                    const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];
+                    beaten = beaten && (!live || acc[r][s] > s_val[sb + s - 64 * r]);
+                  }
                 }
               }
-            }
-            ++cut_tests;
-            if (__builtin_amdgcn_ballot_w64(!beaten) == 0) {
-              stop_at = j0 + t0;
-              break;
-            }
-            ++cut_fail;
-            cut_at = cut_once ? INT32_MAX : j0 + t0 + S;
-          }
-        }
-        const double* rows = s_row + t0 * ROW;
-#pragma unroll
-        for (int t = 0; t < S; ++t) {
-          double2 cur[NQ];
-#pragma unroll
-          for (int u = 0; u < NQ; ++u) {
-            cur[u] = nxt[u];
-            nxt[u] = reinterpret_cast<const double2*>(rows + (t + 1) * ROW)[u];
-          }
-          // (fences: left to itself the scheduler pulls the next step's products up to the reads and waits on them at once)
-          __builtin_amdgcn_sched_barrier(0);
-          const double2 pm = cur[0];
-          const double p = pm.x;
-          double pv[S];
-          if constexpr (FUTURE) {
-#pragma unroll
-            for (int s = 0; s < S; s += 2) {
-              pv[s] = cur[1 + s / 2].x;
-              if (s + 1 < S) pv[s + 1] = cur[1 + s / 2].y;
+              ++cut_tests;
+              if (__builtin_amdgcn_ballot_w64(!beaten) == 0) {
+                stop_at = j0 + t0;
+                break;
+              }
+              ++cut_fail;
+              cut_at = cut_once ? INT32_MAX : j0 + t0 + S;
             }
           }
+          const double* rows = s_row + t0 * ROW;
 #pragma unroll
-          for (int s = 0; s < S; ++s) {
+          for (int t = 0; t < S; ++t) {
+            double2 cur[NQ];
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-              acc[r][s] += p * imm[r][(s - t + S) % S];
-              if constexpr (FUTURE) acc[r][s] += pv[s];
+            for (int u = 0; u < NQ; ++u) {
+              cur[u] = nxt[u];
+              nxt[u] = reinterpret_cast<const double2*>(rows + (t + 1) * ROW)[u];
             }
-          }
-          // level 0 at step j + 1 takes the slot level S - 1 has just used
+            // (fences: left to itself the scheduler pulls the next step's products up to the reads and waits on them at once)
+            __builtin_amdgcn_sched_barrier(0);
+            const double2 pm = cur[0];
+            const double p = pm.x;
+            double pv[S];
+            if constexpr (FUTURE) {
 #pragma unroll
-          for (int r = 0; r < R; ++r) imm[r][(2 * S - 1 - t) % S] = c0[r] + pm.y;
-          __builtin_amdgcn_sched_barrier(0);
+              for (int s = 0; s < S; s += 2) {
+                pv[s] = cur[1 + s / 2].x;
+                if (s + 1 < S) pv[s + 1] = cur[1 + s / 2].y;
+              }
+            }
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+#pragma unroll
+              for (int r = 0; r < R; ++r) {
+                acc[r][s] += p * imm[r][(s - t + S) % S];
+                if constexpr (FUTURE) acc[r][s] += pv[s];
+              }
+            }
+            // level 0 at step j + 1 takes the slot level S - 1 has just used
+#pragma unroll
+            for (int r = 0; r < R; ++r) imm[r][(2 * S - 1 - t) % S] = c0[r] + pm.y;
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
       }
-    }
+      if constexpr (CUT) {
+        again = false;
+        cut_steps += (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);
+        if (j_first == 0) {
+          ++scr_exact;
+        } else if (stop_at >= 0) {
+          ++scr_hit;
+          scr_need = 1;
+        } else {  // the screen has failed: nothing is known about the block, walk it again from step 0
+          ++scr_miss;
+          scr_need = min(2 * scr_need, 8);
+          scr_run = 0;
+          scr_from = 0;
+          again = true;
+        }
+      }
+    } while (CUT && again);
     if constexpr (CUT) {
-      cut_steps += (unsigned)(stop_at < 0 ? L.d_pad : stop_at);
+      scr_run = stop_at >= 0 ? scr_run + 1 : 0;
       if constexpr (PF) pf_stop = stop_at < 0 ? INT32_MAX : stop_at;
       if (stop_at >= 0) {  // no cell of the block can win or tie: nothing to put into the slots
         cut_dec = cut_fail == 0 ? min(2 * cut_dec, 8 * S) : S;
@@ -475,6 +533,11 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
     if (lane == 0) {
       atomicAdd(cut_count, (unsigned long long)cut_steps);
       atomicAdd(cut_count + 1, (unsigned long long)cut_tests);
+      if (L.screen_start > 0) {
+        atomicAdd(cut_count + 2, (unsigned long long)scr_hit);
+        atomicAdd(cut_count + 3, (unsigned long long)scr_miss);
+      }
+      atomicAdd(cut_count + 4, (unsigned long long)scr_exact);
     }
   }
 }

@@ -376,6 +376,7 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
   p.v_nonneg = false;  // (launch_window says otherwise)
   p.lvl_steps_planned = 0;
   p.lvl_cut = false;
+  p.lvl_screen_start = 0;
   p.pre_ops = 0;
   DevParams P = make_params(h, period);
   const double* v_next = period < h->T ? h->d_values + h->per[period].v_off : nullptr;
@@ -659,6 +660,11 @@ int sdpgpu_create(const sdpgpu_desc* desc, sdpgpu_handle** out) {
     if (const char* e = std::getenv("SDPGPU_WIN_S")) h->win_s = std::atoi(e);
     if (const char* e = std::getenv("SDPGPU_WIN_LEVEL")) h->win_level = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_F1_CUTOFF")) h->f1_cutoff = std::atoi(e) != 0;
+    if (const char* e = std::getenv("SDPGPU_F1_SCREEN")) h->f1_screen = std::atoi(e) != 0;
+    if (const char* e = std::getenv("SDPGPU_F1_SCREEN_LOG2")) {
+      const int b = std::atoi(e);
+      if (b >= 1 && b <= 1000) h->f1_screen_mass = std::ldexp(1.0, -b);
+    }
     if (const char* e = std::getenv("SDPGPU_FUSE_COMBINE")) h->fuse_combine = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_CASH_SHIFT")) h->use_cash_shift = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_CASH_ROW")) h->use_cash_row = std::atoi(e) != 0;
@@ -1519,7 +1525,7 @@ int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out) {
   if (layout(h)) return SDPGPU_ERR_STATE;
   bool modelled = true;
   // the level kernel's own count of what it ran (periods with the cut-off): steps and tests per period
-  std::vector<unsigned long long> cut((size_t)h->T * 2, 0);
+  std::vector<unsigned long long> cut((size_t)h->T * kCutCounters, 0);
   bool cut_read = false;
   if (h->allocated && h->d_cut_count) {
     bool any = false;
@@ -1541,9 +1547,9 @@ int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out) {
     double walked = 1.0, tests = 0.0;
     out->f1_level_steps_planned += p.lvl_steps_planned;
     if (p.lvl_cut && cut_read && p.lvl_steps_planned > 0) {
-      out->f1_level_steps_run += (int64_t)cut[(size_t)t * 2];
-      walked = (double)cut[(size_t)t * 2] / (double)p.lvl_steps_planned;
-      tests = (double)cut[(size_t)t * 2 + 1] / (double)p.lvl_steps_planned;
+      out->f1_level_steps_run += (int64_t)cut[(size_t)t * kCutCounters];
+      walked = (double)cut[(size_t)t * kCutCounters] / (double)p.lvl_steps_planned;
+      tests = (double)cut[(size_t)t * kCutCounters + 1] / (double)p.lvl_steps_planned;
     } else {
       out->f1_level_steps_run += p.lvl_steps_planned;
     }
@@ -1612,6 +1618,34 @@ int64_t sdpgpu_period_cells(sdpgpu_handle* h, int32_t period) {
     return (int64_t)c;
   }
   return p.cells_counted ? p.cells_rank : -1;
+}
+
+int32_t sdpgpu_f1_screen_start(sdpgpu_handle* h, int32_t period) {
+  if (!h || period < 1 || period > h->T) return -1;
+  h->err.clear();
+  if (layout(h)) return -1;
+  return f1_screen_start(h, period, 8, h->f1_screen_mass);
+}
+
+int sdpgpu_f1_screen_get(sdpgpu_handle* h, int32_t period, int64_t out[6]) {
+  if (!h || !out) return SDPGPU_ERR_ARG;
+  h->err.clear();
+  if (period < 1 || period > h->T) return fail(h, SDPGPU_ERR_ARG, "period %d out of 1..%d", period, h->T);
+  for (int k = 0; k < 6; ++k) out[k] = 0;
+  const PeriodInfo& p = h->per[period - 1];
+  if (!(h->allocated && h->d_cut_count && p.lvl_cut)) return SDPGPU_OK;
+  int rc = ensure_device(h);
+  if (rc) return rc;
+  unsigned long long c[kCutCounters] = {};
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(c, h->d_cut_count + (size_t)(period - 1) * kCutCounters, sizeof c, hipMemcpyDeviceToHost));
+  out[0] = p.lvl_screen_start;
+  out[1] = (int64_t)c[2];
+  out[2] = (int64_t)c[3];
+  out[3] = (int64_t)c[4];
+  out[4] = (int64_t)c[0];
+  out[5] = p.lvl_steps_planned;
+  return SDPGPU_OK;
 }
 
 }  // extern "C"

@@ -47,6 +47,13 @@ using sdp::Grid;
 
 
 
+// THE SCREEN of the F1 level kernel (sdp_window.hpp): a screened level block skips the leading demand steps that carry at
+// most this share of the period's probability (screen_start, f1_screen_start in sdpgpu_window.hip).  Any bound is exact; a
+// larger one skips more steps and may fail more screens.  2^-16 was taken from the sweep of 2^-16, 2^-24, 2^-32 in
+// profiles/f1_screen_ab.txt (same failed screens, one more block of S steps skipped than 2^-24); SDPGPU_F1_SCREEN_LOG2=<e>
+// (diagnostic) uses 2^-e.
+constexpr double kF1ScreenMass = 0x1p-16;
+constexpr int kCutCounters = 5;  // per period: steps run, tests made, blocks screened and stopped, screens failed, exact walks
 constexpr size_t kPmfPad = 16;  // zero-probability tail: demand loop in blocks of R <= 8, one block of prefetch
 
 // register block / chunking of the F1 window kernel for one period (sdpgpu_window.hip)
@@ -103,6 +110,7 @@ struct PeriodInfo {
   // whether it ran with the cut-off, i.e. counted the steps it ran and its tests on the device (sdpgpu_handle::d_cut_count)
   int64_t lvl_steps_planned = 0;
   bool lvl_cut = false;
+  int32_t lvl_screen_start = 0;  // the step screened level blocks started at in the last launch (0: the screen was off)
   double pre_ops = 0;  // fp64 operations of the cut-off's pre-pass (Q(i, 0) of every state), in total
   double lds_cell = 0, l1_cell = 0;  // bytes per cell through the LDS / the vector L1 of the kernel that ran the period (0: no model)
   mutable WinPlanCache win_plan;     // (a cache: filled through const handles by plan_window)
@@ -165,7 +173,13 @@ struct sdpgpu_handle {
   int f1_cutoff = 1;   // SDPGPU_F1_CUTOFF=0: the level kernel never stops a level block early (A/B runs, tests)
   double* d_f1_u = nullptr;  // the cut-off's row U(i) = Q(i, 0) of the period being run (window_f1_level_kernel)
   size_t f1_u_elems = 0;
-  unsigned long long* d_cut_count = nullptr;  // [T][2]: steps run and tests made by the level kernel's waves, per period
+  // SDPGPU_F1_SCREEN: -1 = the screen where the planner chose the level kernel by itself (win_level < 0) and not under a
+  // forced plan, 1 = wherever the cut-off is on, 0 = never.  It never goes beyond the cut-off's gate (f1_cutoff_on).
+  int f1_screen = -1;
+  double f1_screen_mass = kF1ScreenMass;
+  // [T][kCutCounters], per period: steps run and tests made by the level kernel's waves, then its level blocks -- screened
+  // and stopped, screens that failed, walked exactly (sdpgpu_f1_screen_get)
+  unsigned long long* d_cut_count = nullptr;
   int win_level = -1;  // SDPGPU_WIN_LEVEL: 1 = the action-major level kernel wherever it can run, 0 = never, -1 = where it wins
   uint8_t* d_reach = nullptr;      // reachable masks, period t at reach_off[t-1]
   std::vector<size_t> reach_off;
@@ -376,6 +390,8 @@ int sample_table_build(const sdpgpu_dist_spec& spec, int32_t* k_lo, std::vector<
 bool window_eligible(const sdpgpu_handle* h, int period);
 // (why: receives the reason when no plan exists -- a forced plan that is infeasible, or a period too big for the LDS)
 WinPlan plan_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, std::string* why = nullptr);
+// the step screened level blocks start at under the mass bound `mass` (S: the level kernel's levels per block; 0: none)
+int f1_screen_start(const sdpgpu_handle* h, int period, int S, double mass);
 hipError_t flush_pending(sdpgpu_handle* h);
 // the two kernels of chunked periods, defined in this unit only (the batched solve launches them too): key rows to the
 // reduction identity of the direction; V_t and policy rows from keys + chunk rows (`total` states over `n_jobs` jobs)

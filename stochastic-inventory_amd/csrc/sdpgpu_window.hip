@@ -72,6 +72,33 @@ static bool f1_cutoff_on(const sdpgpu_handle* h, int period, int64_t lo, int64_t
   return c.smem <= kLdsPerCU && grid_ok((c.tiles + 3) / 4);
 }
 
+// THE SCREEN's first step (sdp_window.hpp), for a period whose cut-off is on: the largest multiple of S with
+// sum_{j < screen_start} p_j <= mass * sum_j p_j over the period's window-layout pmf (unit-stride steps from the lowest
+// demand, probability 0 in the gaps), and 0 -- no screen -- below S.  Whether the handle screens at all is f1_screen_on.
+int f1_screen_start(const sdpgpu_handle* h, int period, int S, double mass) {
+  const PeriodInfo& p = h->per[period - 1];
+  const std::vector<double>&dv = h->pmf_d[(size_t)period - 1], &pv = h->pmf_p[(size_t)period - 1];
+  if (p.nD_win <= 0 || dv.empty() || !(mass > 0)) return 0;
+  std::vector<double> w((size_t)p.nD_win, 0.0);
+  double total = 0;
+  for (size_t j = 0; j < dv.size(); ++j) {
+    const int64_t at = (int64_t)((dv[j] - dv[0]) / h->d.step);
+    if (at < 0 || at >= p.nD_win) return 0;
+    w[(size_t)at] = pv[j];
+  }
+  for (double q : w) total += q;
+  const double bound = mass * total;
+  double head = 0;
+  int n = 0;  // steps whose leading mass stays within the bound
+  while (n < p.nD_win && head + w[(size_t)n] <= bound) head += w[(size_t)n++];
+  const int start = n / S * S;
+  return start >= S && start < p.nD_win ? start : 0;
+}
+// The screen is on where the planner took the level kernel by itself; a forced plan (SDPGPU_WIN_LEVEL=1) keeps the pure
+// cut-off schedule, which its tests count step by step against a CPU twin, unless SDPGPU_F1_SCREEN=1 asks for the screen;
+// SDPGPU_F1_SCREEN=0 turns it off everywhere.
+static bool f1_screen_on(const sdpgpu_handle* h) { return h->f1_screen < 0 ? h->win_level < 0 : h->f1_screen != 0; }
+
 // The action-major level kernel (window_f1_level_kernel), where it can run and -- unless SDPGPU_WIN_LEVEL=1 asks for it
 // -- where it wins: a whole single-rank slab (no halo, no interior / boundary split), chunk rows allowed (every state's
 // actions meet across tasks), nothing forced about the state-major blocks, and a grid that fills the chip with tasks
@@ -640,11 +667,11 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
         h->f1_u_elems = need;
       }
       if (!h->d_cut_count) {
-        hipError_t e = hipMalloc((void**)&h->d_cut_count, (size_t)h->T * 2 * sizeof(unsigned long long));
+        hipError_t e = hipMalloc((void**)&h->d_cut_count, (size_t)h->T * kCutCounters * sizeof(unsigned long long));
         if (e != hipSuccess) return e;
       }
-      cut_count = h->d_cut_count + (size_t)(period - 1) * 2;
-      hipError_t e = hipMemsetAsync(cut_count, 0, 2 * sizeof(unsigned long long), st);
+      cut_count = h->d_cut_count + (size_t)(period - 1) * kCutCounters;
+      hipError_t e = hipMemsetAsync(cut_count, 0, kCutCounters * sizeof(unsigned long long), st);
       if (e != hipSuccess) return e;
       // U(i) = Q(i, 0): the state-major kernel with ONE action (its guards ignore the three padded actions of the R-block)
       // and one chunk, into the row -- the same operations in the same order as the level kernel's action 0
@@ -687,6 +714,9 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
       p.pre_ops = (double)(hi - lo) * 4.0 * p.nD_win * (future ? 3.0 + 1.0 / 8 + 11.0 / 32 : 2.0 + 1.0 / 8);
     }
     L.cut_start = std::max(pl.S, p.nD_win / 2 / pl.S * pl.S);  // a task's first block: tests from D / 2 on
+    // THE SCREEN (sdp_window.hpp): behind the cut-off's gate and nothing weaker
+    L.screen_start = cut && f1_screen_on(h) ? f1_screen_start(h, period, pl.S, h->f1_screen_mass) : 0;
+    p.lvl_screen_start = L.screen_start;
 #define SDP_LVL_GO(RR, SS, FU, KI, CU)                                                                                         \
   do {                                                                                                                         \
     static LdsMark mark;                                                                                                       \

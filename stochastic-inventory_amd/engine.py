@@ -409,6 +409,18 @@ class SdpEngine:
     def period_ms(self, period: int) -> float:
         return float(self._lib.sdpgpu_period_ms(self._h, period))
 
+    def f1_screen(self, period: int):
+        """The screen of the F1 level kernel in `period` of the last solve: (screen_start, level blocks screened and stopped,
+        screens failed, blocks walked from step 0, demand steps walked, demand steps planned); all 0 where the level kernel's
+        cut-off did not run."""
+        out = (C.c_int64 * 6)()
+        self._check(self._lib.sdpgpu_f1_screen_get(self._h, period, out))
+        return tuple(int(v) for v in out)
+
+    def f1_screen_start(self, period: int) -> int:
+        """Host arithmetic: the step the screen's rule gives for the pmf of `period` (0: no screen)."""
+        return int(self._lib.sdpgpu_f1_screen_start(self._h, period))
+
     def period_cells(self, period: int) -> int:
         """Cells of `period` on this rank's slab (-1: not counted)."""
         return int(self._lib.sdpgpu_period_cells(self._h, period))
