@@ -551,10 +551,15 @@ int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out);
 /* ABI 5: the launch plan of one period of THIS rank's slab, as the launcher would choose it now (descriptor, pmfs,
  * world size and the SDPGPU_WIN_* overrides read at create time).  Host arithmetic only: no device is touched, so a
  * caller (or a test without a GPU) can see what a period will cost in LDS before it runs.  Reported for the window
- * kernels of the backorder family (F1); other kernels return kernel = SDPGPU_KERNEL_GATHER and zeros.  A plan that
+ * kernels of the backorder family (F1) and for the row-window kernel of the lead-time family (F2: a period that would run
+ * it -- kernel AUTO or WINDOW, a unit-stride demand layout, no action counts of the caller's; r x s is the instantiation,
+ * chunk_blocks the register blocks a chunk's waves walk, tiles the row tiles of 64 s states that cover the slab -- the
+ * launcher and this call ask one function); other kernels return kernel = SDPGPU_KERNEL_GATHER and zeros.  A plan that
  * cannot run -- a forced register block that does not exist, a forced chunking that exceeds the 160 KiB of LDS of a
- * compute unit, chunk rows where ping-pong tables forbid them -- returns SDPGPU_ERR_ARG with the reason in
- * sdpgpu_last_error, which is also what sdpgpu_run_period then returns (before anything is launched). */
+ * compute unit, chunk rows where ping-pong tables forbid them, an F2 period whose row segments exceed that LDS under a
+ * forced block or kernel = WINDOW -- returns SDPGPU_ERR_ARG with the reason in sdpgpu_last_error, which is also what
+ * sdpgpu_run_period then returns (before anything is launched); under the automatic choice with nothing forced such a
+ * period runs on, and is reported as, the generic kernel. */
 typedef struct sdpgpu_plan {
   int32_t kernel;            /* SDPGPU_KERNEL_WINDOW or SDPGPU_KERNEL_GATHER */
   int32_t r, s;              /* register block: actions x adjacent states per lane */

@@ -1117,8 +1117,30 @@ int sdpgpu_plan_period(const sdpgpu_handle* hc, int32_t period, sdpgpu_plan* out
   const bool own_counts = !h->counts[(size_t)period - 1].empty();
   const bool f1_window = f1_like(h) && h->d.kernel != SDPGPU_KERNEL_GATHER && h->d.family == SDPGPU_FAMILY_BACKORDER && window_eligible(h, period) &&
                          (h->d.kernel == SDPGPU_KERNEL_WINDOW || (h->d.kernel == SDPGPU_KERNEL_AUTO && !own_counts));
-  if (!f1_window) return SDPGPU_OK;
   const PeriodInfo& p = h->per[period - 1];
+  // the lead-time family (F2) on the row-window kernel: run_period_impl's own condition, launch_row_window's own plan
+  const bool f2_window = h->d.family == SDPGPU_FAMILY_LEADTIME && window_eligible(h, period) &&
+                         (h->d.kernel == SDPGPU_KERNEL_WINDOW || (h->d.kernel == SDPGPU_KERNEL_AUTO && !own_counts));
+  if (f2_window) {
+    std::string why;
+    const RowPlan rp = plan_row_window(h, period, p.lo, p.hi, &why);
+    if (!rp.R) {
+      // (automatic kernel choice, nothing forced: such a period runs on the generic kernel, see run_period_impl)
+      if (h->d.kernel == SDPGPU_KERNEL_AUTO && !(h->win_r || h->win_s || h->win_nch)) return SDPGPU_OK;
+      return fail(h, SDPGPU_ERR_ARG, "period %d: %s", period, why.c_str());
+    }
+    out->kernel = SDPGPU_KERNEL_WINDOW;
+    out->r = rp.R;
+    out->s = rp.S;
+    out->chunks = rp.n_chunks;
+    out->chunk_blocks = rp.chunk_blocks;
+    out->tiles = rp.n_tiles;
+    out->tasks = rp.n_tiles * rp.n_chunks;
+    out->workgroups_per_cu = lds_workgroups(rp.smem);
+    out->lds_bytes = (int64_t)rp.smem;
+    return SDPGPU_OK;
+  }
+  if (!f1_window) return SDPGPU_OK;
   std::string why;
   const WinPlan pl = plan_window(h, period, p.lo, p.hi, &why);
   if (!pl.R) {

@@ -67,6 +67,17 @@ struct WinPlan {
   int tile_states() const { return 64 * S; }
 };
 
+// the launch of the F2 row-window kernel for one period and slab (plan_row_window, sdpgpu_window.hip): what launch_row_window
+// launches and sdpgpu_plan_period reports.  R = 0: no plan (the reason is in `why`).
+struct RowPlan {
+  int R = 0, S = 0;        // window_f2_kernel<R, S>: actions x adjacent states per lane
+  int d_pad = 0, span = 0; // demand steps padded to a multiple of 4; slots of a staged row segment
+  int waves = 0;           // waves of a workgroup that take action blocks
+  int chunk_blocks = 0, n_chunks = 0;     // R-blocks per chunk; chunks per tile (> 1: chunk rows + window_combine_kernel)
+  int tiles_per_row = 0, tile0 = 0, n_tiles = 0;  // row tiles of 64 S states: per inventory row, first of the slab, of the slab
+  size_t smem = 0;         // dynamic LDS per workgroup
+};
+
 // plan_window's answer for one period, kept per (slab, forced block): the search walks 8 block shapes x up to blocks_total
 // chunk counts on the issuing thread, and launch_window, run_period_impl's pre-check and sdpgpu_plan_period all ask for it
 // (at 30 us per period the second search sat on the critical path).  Dropped by layout().
@@ -390,6 +401,7 @@ int sample_table_build(const sdpgpu_dist_spec& spec, int32_t* k_lo, std::vector<
 bool window_eligible(const sdpgpu_handle* h, int period);
 // (why: receives the reason when no plan exists -- a forced plan that is infeasible, or a period too big for the LDS)
 WinPlan plan_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, std::string* why = nullptr);
+RowPlan plan_row_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, std::string* why = nullptr);
 // the step screened level blocks start at under the mass bound `mass` (S: the level kernel's levels per block; 0: none)
 int f1_screen_start(const sdpgpu_handle* h, int period, int S, double mass);
 hipError_t flush_pending(sdpgpu_handle* h);

@@ -374,12 +374,11 @@ hipError_t launch_row_r(const sdp::RowParams& W, size_t smem, bool future, const
   return hipGetLastError();
 }
 
-hipError_t launch_row_window(sdpgpu_handle* h, const DevParams& P, int period, const double* v_next, double* v_cur,
-                             int32_t* pol, const double* pmf_p, int64_t lo, int64_t hi, hipStream_t st) {
-  {
-    hipError_t ef = flush_pending(h);
-    if (ef != hipSuccess) return ef;
-  }
+// THE plan of the row-window kernel for period `period` on the slab [lo, hi): the register block R, the states per lane S,
+// the staged span, the waves that take blocks, the chunking and the run of row tiles -- host arithmetic only, one function
+// for launch_row_window and sdpgpu_plan_period, so that the plan reported is the plan launched.
+RowPlan plan_row_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, std::string* why) {
+  RowPlan pl;
   const PeriodInfo& p = h->per[period - 1];
   const int A = h->n_actions_full, D = p.nD_win;
   auto rup = [](int v, int r) { return (v + r - 1) / r * r; };
@@ -414,6 +413,67 @@ hipError_t launch_row_window(sdpgpu_handle* h, const DevParams& P, int period, c
   if (SL == 4 && R == 8) SL = 2;
   const int TSZ = 64 * SL;
   const bool future = period < h->T;
+  const int tiles_per_row = (int)((p.g.nx + TSZ - 1) / TSZ);
+  const int d_pad = rup(D, 4);  // the demand loop is unrolled by S (1, 2 or 4); padded steps carry p = 0
+  const int span = TSZ + d_pad + 2;  // (window_f2_kernel: two spare slots, even)
+  const int blocks_total = rup(A, R) / R;
+  // one R-block per wave: chunks of 4 R-blocks; every wave stages the R row segments of its own block in its own LDS
+  // region, so the budget (rows of `span` doubles) bounds the number of waves that take blocks, not the chunk
+  int waves = std::min(4, blocks_total);
+  // (the read-out scratch of a wave that stages rows lies inside its row region)
+  auto lds = [&](int wv) { return (size_t)span * 8 * (1 + (future ? wv * R : 0)) + (size_t)(future ? 4 - wv : 4) * TSZ * 12; };
+  // (two workgroups per compute unit stay resident up to half its 160 KiB each; a single wave's rows may take all of it)
+  while (waves > 1 && lds(waves) > kLdsPerCU / 2) --waves;
+  if (lds(waves) > kLdsPerCU) {
+    if (why) {
+      char buf[200];
+      std::snprintf(buf, sizeof buf, "row-window kernel: %d demand steps need %zu B of LDS per workgroup, over the %zu B of a compute unit",
+                    D, lds(waves), kLdsPerCU);
+      *why = buf;
+    }
+    return pl;
+  }
+  // the run of row tiles that covers [lo, hi) (none for an empty slab)
+  auto tile_of = [&](int64_t idx) { return (int32_t)((idx / p.g.nx) * tiles_per_row + (idx % p.g.nx) / TSZ); };
+  const int tile0 = hi > lo ? tile_of(lo) : 0;
+  const int n_tiles = hi > lo ? tile_of(hi - 1) - tile0 + 1 : 0;
+  // Blocks per chunk: a whole number of blocks per wave, as many as still leave about 6.5 rounds of workgroups on the chip
+  // (5000 at three per CU).  What a workgroup pays once -- M staged behind a barrier, the read-out behind another, a
+  // chunk row of (value, action) pairs for the combine pass -- is then shared by several blocks; with ONE chunk there are no
+  // chunk rows and no combine pass at all.  Measured (`profiles/r02_f2_chunk_sweep.txt`): configs[3], 800 tiles per period:
+  // 13 / 7 / 5 / 1 chunks -> 27.3 / 26.7 / 27.2 / 33.8 ms; its pipeline shape, 40,000 tiles: 13 / 4 / 1 -> 93.8 / 89.6 / 88.6 ms.
+  int bpc = waves;
+  for (int m = 2; (m - 1) * waves < blocks_total; ++m) {
+    const int cand_bpc = std::min(m * waves, rup(blocks_total, waves));
+    if ((int64_t)n_tiles * ((blocks_total + cand_bpc - 1) / cand_bpc) < 5000) break;
+    bpc = cand_bpc;
+  }
+  if (h->win_nch) bpc = std::max(1, (blocks_total + h->win_nch - 1) / h->win_nch);
+  pl.R = R;
+  pl.S = SL;
+  pl.d_pad = d_pad;
+  pl.span = span;
+  pl.waves = waves;
+  pl.chunk_blocks = bpc;
+  pl.n_chunks = (blocks_total + bpc - 1) / bpc;
+  pl.tiles_per_row = tiles_per_row;
+  pl.tile0 = tile0;
+  pl.n_tiles = n_tiles;
+  pl.smem = lds(waves);
+  return pl;
+}
+
+hipError_t launch_row_window(sdpgpu_handle* h, const DevParams& P, int period, const double* v_next, double* v_cur,
+                             int32_t* pol, const double* pmf_p, int64_t lo, int64_t hi, hipStream_t st) {
+  {
+    hipError_t ef = flush_pending(h);
+    if (ef != hipSuccess) return ef;
+  }
+  const PeriodInfo& p = h->per[period - 1];
+  const RowPlan pl = plan_row_window(h, period, lo, hi, &h->plan_error);
+  if (!pl.R) return hipErrorInvalidValue;
+  const int R = pl.R, SL = pl.S, A = h->n_actions_full;
+  const bool future = period < h->T;
   h->per[period - 1].ops_cell = future ? 4.0 + 1.0 / SL : 2.0 + 1.0 / SL;  // (c0 + M shared by SL cells, see window_f2_kernel)
   h->per[period - 1].lds_cell = 8.0 * ((future ? R : 0) + 1) / (double)(R * SL);  // M and one V entry per action, per SL states
   sdp::RowParams W{};
@@ -431,44 +491,14 @@ hipError_t launch_row_window(sdpgpu_handle* h, const DevParams& P, int period, c
   W.cur_nx = (int32_t)p.g.nx;
   W.nq1 = (int32_t)p.g.nq1;
   W.plane_stride = P.lead2 ? (int64_t)W.nq1 * W.next_nx : (int64_t)W.next_nx;
-  W.tiles_per_row = (int32_t)((p.g.nx + TSZ - 1) / TSZ);
+  W.tiles_per_row = pl.tiles_per_row;
   W.n_actions = A;
-  W.d_pad = rup(D, 4);  // the demand loop is unrolled by S (1, 2 or 4); padded steps carry p = 0
-  const int span = TSZ + W.d_pad + 2;  // (window_f2_kernel: two spare slots, even)
-  const int blocks_total = rup(A, R) / R;
-  // one R-block per wave: chunks of 4 R-blocks; every wave stages the R row segments of its own block in its own LDS
-  // region, so the budget (rows of `span` doubles) bounds the number of waves that take blocks, not the chunk
-  int waves = std::min(4, blocks_total);
-  // (the read-out scratch of a wave that stages rows lies inside its row region)
-  auto lds = [&](int wv) { return (size_t)span * 8 * (1 + (future ? wv * R : 0)) + (size_t)(future ? 4 - wv : 4) * TSZ * 12; };
-  // (two workgroups per compute unit stay resident up to half its 160 KiB each; a single wave's rows may take all of it)
-  while (waves > 1 && lds(waves) > kLdsPerCU / 2) --waves;
-  if (lds(waves) > kLdsPerCU) {
-    char buf[200];
-    std::snprintf(buf, sizeof buf, "row-window kernel: %d demand steps need %zu B of LDS per workgroup, over the %zu B of a compute unit",
-                  D, lds(waves), kLdsPerCU);
-    h->plan_error = buf;
-    return hipErrorInvalidValue;
-  }
-  // the run of row tiles that covers [lo, hi)
-  auto tile_of = [&](int64_t idx) { return (int32_t)((idx / p.g.nx) * W.tiles_per_row + (idx % p.g.nx) / TSZ); };
-  W.tile0 = tile_of(lo);
-  W.n_tiles = tile_of(hi - 1) - W.tile0 + 1;
-  // Blocks per chunk: a whole number of blocks per wave, as many as still leave about 6.5 rounds of workgroups on the chip
-  // (5000 at three per CU).  What a workgroup pays once -- M staged behind a barrier, the read-out behind another, a
-  // chunk row of (value, action) pairs for the combine pass -- is then shared by several blocks; with ONE chunk there are no
-  // chunk rows and no combine pass at all.  Measured (`profiles/r02_f2_chunk_sweep.txt`): configs[3], 800 tiles per period:
-  // 13 / 7 / 5 / 1 chunks -> 27.3 / 26.7 / 27.2 / 33.8 ms; its pipeline shape, 40,000 tiles: 13 / 4 / 1 -> 93.8 / 89.6 / 88.6 ms.
-  int bpc = waves;
-  for (int m = 2; (m - 1) * waves < blocks_total; ++m) {
-    const int cand_bpc = std::min(m * waves, rup(blocks_total, waves));
-    if ((int64_t)W.n_tiles * ((blocks_total + cand_bpc - 1) / cand_bpc) < 5000) break;
-    bpc = cand_bpc;
-  }
-  if (h->win_nch) bpc = std::max(1, (blocks_total + h->win_nch - 1) / h->win_nch);
-  W.waves_active = waves;
-  W.chunk_actions = bpc * R;
-  W.n_chunks = (blocks_total + bpc - 1) / bpc;
+  W.d_pad = pl.d_pad;
+  W.tile0 = pl.tile0;
+  W.n_tiles = pl.n_tiles;
+  W.waves_active = pl.waves;
+  W.chunk_actions = pl.chunk_blocks * R;
+  W.n_chunks = pl.n_chunks;
   double* out_val = v_cur;
   int32_t* out_idx = pol;
   if (W.n_chunks > 1) {
@@ -481,7 +511,7 @@ hipError_t launch_row_window(sdpgpu_handle* h, const DevParams& P, int period, c
     out_idx = h->d_part_idx[b] - lo;
   }
   hipError_t e = hipErrorInvalidValue;
-  size_t smem = lds(waves);
+  const size_t smem = pl.smem;
 #define SDP_ROW(RR, SS)                                                                                          \
   if (R == RR && SL == SS)                                                                                       \
     e = P.maxdir ? launch_row_r<RR, SS, true>(W, smem, future, v_next, out_val, out_idx, pmf_p, lo, hi, st)      \

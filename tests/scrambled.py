@@ -1,11 +1,14 @@
 """Scrambled successor tables: helpers of tests/test_scrambled_inputs.py (CPU) and tests/test_gpu_scrambled_successor.py /
-tests/test_gpu_survival_wide.py (GPU).  No test lives here.
+tests/test_gpu_survival_wide.py / tests/test_gpu_f2_scrambled_successor.py (GPU).  No test lives here.
 
 The value tables the recursion itself produces are almost constant along the cash axis for the cash families (V(x, cash) is an
 expected cash INCREMENT: it does not depend on the balance while the order constraint is slack; survival probabilities are
 plateaus of 0, gamma^k and 1), so a kernel that gathers V_{t+1} at a wrong cash key still gives the oracle's table.  Here a
 period is evaluated on a V_{t+1} of pairwise distinct values instead, and compared with the oracle's evaluation of the same
-period on the same table."""
+period on the same table.
+
+The lead-time family hides a different slip: a solved lead-time-1 table is a function of plane + index alone, so a gather that is
+one plane up and one index down reads the same value (slip_antidiagonal, KEPT_F2)."""
 import zlib
 
 import numpy as np
@@ -34,6 +37,24 @@ def slip(v, nc):
     out = rows.copy()
     out[:, :-1] = rows[:, 1:]
     return out.reshape(-1)
+
+
+def slip_antidiagonal(v, grid):
+    """The table whose entry (plane q, index i) is the entry (q + 1, i - 1) of `v`, the last plane and index 0 kept: what a
+    gather of the lead-time family reads whose plane base and row offset slip against each other (grid: the oracle's Grid of the
+    table's period, planes of nx inventory points).  A solved V_{t+1} of lead time 1 depends on q + i alone, so there the
+    slipped table is the table itself away from its edges."""
+    planes = np.asarray(v, dtype=np.float64).reshape(int(grid.nq), int(grid.nx))
+    out = planes.copy()
+    out[:-1, 1:] = planes[1:, :-1]
+    return out.reshape(-1)
+
+
+def antidiagonal_sensitivity(P, t, v_next, nthreads=8):
+    """Share of the states of period t (family 2) whose value changes when V_{t+1} = v_next is read one plane up, one index down."""
+    a = P.period(t, v_next, nthreads=nthreads)[0]
+    b = P.period(t, slip_antidiagonal(v_next, P.grids[t]), nthreads=nthreads)[0]
+    return float(np.mean(a != b))
 
 
 def row_length(P, period):
@@ -169,6 +190,32 @@ def parametrize_values(test_function, argname):
     raise KeyError(argname)
 
 
+def f2_named_cases():
+    """name -> workload: the named workloads of tests/test_gpu_parity.py's row-window tests, as those tests build them."""
+    import test_gpu_parity as tp
+    out = {f"lanes:{w.name}": w for w in (tp._f2_lane_workload(False), tp._f2_lane_workload(True))}
+    w = tp._f2_block_workload()
+    out[f"blocks:{w.name}"] = w
+    return out
+
+
+def f2_groups():
+    """group -> [(key, workload)]: the lead-time instances of the scrambled tests (keys as in KEPT_F2)."""
+    import test_gpu_f2_window_fuzz as wf
+    return {"window_fuzz": [(seed, wf.make_row_window_instance(seed)) for seed in range(wf.N_INSTANCES)],
+            "named": list(f2_named_cases().items())}
+
+
+def measure_f2(oracle, instances):
+    """[(key, t, sensitivity)] as measure(), for the anti-diagonal slip of the lead-time family."""
+    out = []
+    for key, w in instances:
+        ref = reference(oracle, w)
+        for t in range(1, w.T):
+            out.append((key, t, antidiagonal_sensitivity(ref["P"], t, ref["scrambled"][t][0])))
+    return out
+
+
 def measure(oracle, instances):
     """[(key, t, sensitivity)] for every period with a future of every (key, workload) in `instances`."""
     out = []
@@ -179,10 +226,10 @@ def measure(oracle, instances):
     return out
 
 
-def kept(group):
-    """{seed or case name: set of periods} of a group of KEPT."""
+def kept(group, table=None):
+    """{seed or case name: set of periods} of a group of KEPT (table: KEPT_F2 for the lead-time family)."""
     out = {}
-    for key, t in KEPT.get(group, ()):
+    for key, t in (KEPT if table is None else table).get(group, ()):
         out.setdefault(key, set()).add(t)
     return out
 
@@ -215,4 +262,15 @@ KEPT = {
               ("diag:cfg3_cash_24x700x70x30x3", 1), ("diag:cfg3_cash_24x700x70x30x3", 2), ("diag:f3_dyadic_wide", 1),
               ("diag:f3_dyadic_wide", 2), ("diag:f3_dyadic_wide_min", 1), ("diag:f3_dyadic_wide_min", 2),
               ("diag:f3_dyadic_big_fixed", 1), ("diag:f3_dyadic_big_fixed", 2)],
+}
+
+# The lead-time family (the row-window kernel): (seed, t) of test_gpu_f2_window_fuzz.make_row_window_instance, (case name, t) of
+# f2_named_cases(), at or above THRESHOLD under slip_antidiagonal; asserted by test_kept_f2_pairs_are_the_sensitive_ones
+KEPT_F2 = {
+    "window_fuzz": [(1, 1), (1, 2), (3, 1), (3, 2), (4, 1), (4, 2), (5, 1), (6, 1), (12, 1), (13, 1), (14, 1), (15, 1), (15, 2), (18, 1),
+                    (20, 1), (22, 1), (23, 1), (23, 2), (24, 1), (24, 2), (25, 1), (25, 2), (28, 1), (28, 2), (29, 1), (30, 1), (30, 2),
+                    (33, 1), (33, 2), (34, 1), (34, 2), (36, 1), (37, 1), (38, 1), (38, 2), (41, 1), (41, 2), (44, 1), (45, 1), (46, 1)],
+    "named": [("lanes:cfg4_leadtime_300x37q_37x30x3", 1), ("lanes:cfg4_leadtime_300x37q_37x30x3", 2),
+              ("lanes:cfg4_pipeline_300x10q1x10q2_10x22x3", 1), ("lanes:cfg4_pipeline_300x10q1x10q2_10x22x3", 2),
+              ("blocks:cfg4_leadtime_140x43q_43x120x2", 1)],
 }

@@ -251,15 +251,24 @@ def test_cfg4_shape_reduced(sia, oracle):
     eng.close()
 
 
+def _f2_lane_workload(pipeline):
+    from stochastic_inventory_amd import workloads
+    return workloads.cfg4_pipeline(T=3, NX=300, A=10, D=22) if pipeline else workloads.cfg4_leadtime(T=3, NX=300, A=37, D=30)
+
+
+def _f2_block_workload():
+    from stochastic_inventory_amd import workloads
+    return workloads.cfg4_leadtime(T=2, NX=140, A=43, D=120)
+
+
 @pytest.mark.parametrize("win_s", [None, "4", "2", "1"], ids=["planned", "S4", "S2", "S1"])
 @pytest.mark.parametrize("pipeline", [False, True], ids=["leadtime1", "pipeline"])
 def test_f2_row_window_states_per_lane(sia, oracle, monkeypatch, pipeline, win_s):
     """The F2 row-window kernel with one, two and four adjacent states per lane (wave-private row staging, 16-byte LDS reads
     of two demand steps for S >= 2) on rows wide enough for 256-state tiles, ragged at the end: every table against the oracle."""
-    from stochastic_inventory_amd import workloads
     if win_s:
         monkeypatch.setenv("SDPGPU_WIN_S", win_s)
-    w = workloads.cfg4_pipeline(T=3, NX=300, A=10, D=22) if pipeline else workloads.cfg4_leadtime(T=3, NX=300, A=37, D=30)
+    w = _f2_lane_workload(pipeline)
     eng, P, V, pol, cells = _solve_both(sia, oracle, w)
     assert eng.stats().cells_evaluated == cells and eng.stats().kernel_used == 2
     for period in range(1, w.T + 1):
@@ -347,10 +356,9 @@ def test_f2_row_window_block_plans(sia, oracle, monkeypatch, env):
     """The F2 row-window kernel's other plans: eight actions per lane with 120 demand points (the LDS budget then lets only
     three of a workgroup's four waves take action blocks), one or two chunks per tile (every wave walks several blocks and
     re-stages its rows between them), five actions per lane."""
-    from stochastic_inventory_amd import workloads
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    w = workloads.cfg4_leadtime(T=2, NX=140, A=43, D=120)
+    w = _f2_block_workload()
     eng, P, V, pol, cells = _solve_both(sia, oracle, w)
     assert eng.stats().cells_evaluated == cells and eng.stats().kernel_used == 2
     for period in range(1, w.T + 1):

@@ -138,17 +138,24 @@ def _f2_group(name):
         return [tf.make_instance(2, seed) for seed in range(40)]
     if name in ("step2", "step4"):
         return [tf.make_stepped_instance(2, 300 + seed, int(name[4:])) for seed in range(24)]
+    if name == "window":   # the row-window kernel's generator: rows, action counts and pmfs far wider than the groups above
+        import test_gpu_f2_window_fuzz as wf
+        return wf.instances()
     return [tf.make_shaped_instance(2, 40 + seed, shape) for shape in tf.SHAPES if not shape.startswith("pmf_") for seed in range(3)]
 
 
-@pytest.mark.parametrize("group", ["random", "step2", "step4", "shapes"])
+@pytest.mark.parametrize("group", ["random", "step2", "step4", "shapes", "window"])
 def test_f2_bit_exact_against_the_oracle(sia, oracle, group):
     ws = _f2_group(group)
     if group == "shapes":   # the instances without orders (one action, one pipeline plane) take part
         assert sum(1 for w in ws if w.functor.maxOrderQuantity == 0 and w.name.endswith("no_orders")) == 3
     lead2 = 0
     for w in ws:
-        V, pol, _ = oracle.Problem(w.desc(), w.pmf, w.overhead()).solve(nthreads=4)
+        if group == "window":
+            import test_gpu_f2_window_fuzz as wf
+            V, pol, _ = wf.solved(oracle, w)    # (solved once for every test of that generator)
+        else:
+            V, pol, _ = oracle.Problem(w.desc(), w.pmf, w.overhead()).solve(nthreads=4)
         gv, gp = _solve_separable(sia, w)
         _assert_tables(gv, gp, V, pol, w.name)
         lead2 += w.desc().lead_time == 2
