@@ -559,7 +559,14 @@ int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out);
  * compute unit, chunk rows where ping-pong tables forbid them, an F2 period whose row segments exceed that LDS under a
  * forced block or kernel = WINDOW -- returns SDPGPU_ERR_ARG with the reason in sdpgpu_last_error, which is also what
  * sdpgpu_run_period then returns (before anything is launched); under the automatic choice with nothing forced such a
- * period runs on, and is reported as, the generic kernel. */
+ * period runs on, and is reported as, the generic kernel.
+ * A handle of the STAFF family reports the form launch_staff would run (the launcher and this call ask one function; the
+ * SDPGPU_STAFF_* switches are read at create time): kernel = SDPGPU_KERNEL_GATHER, as sdpgpu_stats reports it; r = actions per
+ * register block (64: the lanes of a wave are 64 actions of one state, 1: the plain one-action-at-a-time kernel, else 4 or 8);
+ * s = adjacent states per lane (1, 2 for the pair kernel, 2 or 4 for the window kernel); chunks = action groups per state tile;
+ * chunk_blocks = trips of a group's action loop (actions per group / r); tiles = state tiles of this slab (64 s states, one
+ * state when r = 64), tasks = tiles x chunks = the launch's workgroups; lds_bytes = the window kernel's static LDS, 0 for every
+ * other form (which tells the window kernel from the pair kernel at s = 2); workgroups_per_cu = 0. */
 typedef struct sdpgpu_plan {
   int32_t kernel;            /* SDPGPU_KERNEL_WINDOW or SDPGPU_KERNEL_GATHER */
   int32_t r, s;              /* register block: actions x adjacent states per lane */

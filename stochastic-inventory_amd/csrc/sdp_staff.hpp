@@ -402,6 +402,12 @@ __global__ __launch_bounds__(64) void staff_pair_kernel(StaffParams P, const dou
 // runs WorkforceTesting.main's instance 3 % faster (3.86 against 3.75e12 cells/s, two runs each, same box) -- the launches of
 // that instance are short (0.2-1.4 ms, 28 tiles of states x action groups), which is what holds it, not the registers.
 // -DSDP_STAFF_WIN_ATTR= (empty) rebuilds the two-wave form.
+// Staging geometry of staff_window_kernel<R, S>, shared with the launcher's plan report (plan_staff): slots per residue class
+// of the level modulo S (the levels of a step, 64 S + R + S - 2, spread over S classes, plus an odd multiple-free padding), and
+// the kernel's static LDS, two such buffers of doubles.
+constexpr int staff_window_slots(int R, int S) { return (64 * S + R + S - 2 + S - 1) / S + 7; }
+constexpr size_t staff_window_lds_bytes(int R, int S) { return (size_t)2 * S * staff_window_slots(R, S) * sizeof(double); }
+
 #ifndef SDP_STAFF_WIN_ATTR
 #define SDP_STAFF_WIN_ATTR __attribute__((amdgpu_waves_per_eu(3, 3)))
 #endif
@@ -416,9 +422,11 @@ __global__ __launch_bounds__(64) SDP_STAFF_WIN_ATTR void staff_window_kernel(Sta
   constexpr int NLEV = TS + NW - 1;      // levels per step: Y0 .. Y0 + NLEV - 1
   constexpr int NPAIR = (NLEV + 1) / 2;  // ... loaded as pairs of adjacent levels
   constexpr int NPC = (NPAIR + 63) / 64;
-  constexpr int H = (NLEV + S - 1) / S + 7;  // slots per residue class (odd multiple-free padding)
+  constexpr int H = staff_window_slots(R, S);  // slots per residue class
+  static_assert(H == (NLEV + S - 1) / S + 7, "staff_window_slots is this kernel's staging geometry");
   static_assert(NW <= kStaffPadJ, "table padding behind the last row of realisations");
   __shared__ __attribute__((aligned(16))) double s_p[2][S * H];
+  static_assert(sizeof(s_p) == staff_window_lds_bytes(R, S), "the LDS the launch plan reports");
   const int lane = threadIdx.x;
   const int64_t tile = blockIdx.x / P.n_groups;
   const int group = (int)(blockIdx.x - tile * P.n_groups);

@@ -669,6 +669,7 @@ int sdpgpu_create(const sdpgpu_desc* desc, sdpgpu_handle** out) {
     if (const char* e = std::getenv("SDPGPU_CASH_SHIFT")) h->use_cash_shift = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_CASH_ROW")) h->use_cash_row = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_WIN_PRIO")) h->win_prio_fair = std::atoi(e) != 0;
+    if (desc->family == SDPGPU_FAMILY_STAFF) staff_read_switches(h);
   } catch (...) {
     delete h;
     return fail(nullptr, SDPGPU_ERR_ARG, "out of host memory");
@@ -1113,6 +1114,18 @@ int sdpgpu_plan_period(const sdpgpu_handle* hc, int32_t period, sdpgpu_plan* out
   int rc = layout(h);
   if (rc) return rc;
   out->kernel = SDPGPU_KERNEL_GATHER;
+  if (h->d.family == SDPGPU_FAMILY_STAFF) {  // launch_staff's own plan (kernel stays GATHER, as sdpgpu_stats reports it)
+    const PeriodInfo& ps = h->per[period - 1];
+    const StaffPlan sp = plan_staff(h, period, ps.lo, ps.hi);
+    out->r = sp.r;
+    out->s = sp.s;
+    out->chunks = sp.n_groups;
+    out->chunk_blocks = sp.group_actions / sp.r;
+    out->tiles = (int32_t)sp.tiles;
+    out->tasks = (int32_t)std::min<int64_t>(sp.tiles * sp.n_groups, 2147483647LL);  // (launch_staff refuses 2^26 workgroups and more)
+    out->lds_bytes = (int64_t)sp.lds;
+    return SDPGPU_OK;
+  }
   // (the launcher's own predicate: an AUTO handle with action counts of the caller's for this period runs the generic kernel)
   const bool own_counts = !h->counts[(size_t)period - 1].empty();
   const bool f1_window = f1_like(h) && h->d.kernel != SDPGPU_KERNEL_GATHER && h->d.family == SDPGPU_FAMILY_BACKORDER && window_eligible(h, period) &&

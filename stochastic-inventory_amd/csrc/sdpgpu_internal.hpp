@@ -78,6 +78,19 @@ struct RowPlan {
   size_t smem = 0;         // dynamic LDS per workgroup
 };
 
+// the launch of the staff family for one period and slab (plan_staff, sdpgpu_staff.hip): what launch_staff launches and
+// sdpgpu_plan_period reports
+enum StaffForm { STAFF_ACTION, STAFF_WINDOW, STAFF_PAIR, STAFF_PLAIN, STAFF_BLOCK };
+struct StaffPlan {
+  StaffForm form = STAFF_BLOCK;
+  int r = 4;              // actions per register block: 64 for staff_action_kernel (a wave's lanes), 1 for staff_period_kernel
+  int s = 1;              // adjacent states per lane: 2 for the pair kernel, 2 / 4 for the window kernel
+  int tile_states = 64;   // states per workgroup (1: lanes are actions)
+  int n_groups = 1, group_actions = 0;  // action groups per state tile; actions per group, a multiple of r
+  int64_t tiles = 0;      // state tiles of the slab; the launch has tiles * n_groups workgroups
+  size_t lds = 0;         // static LDS of the window form (sdp::staff_window_lds_bytes), 0 otherwise
+};
+
 // plan_window's answer for one period, kept per (slab, forced block): the search walks 8 block shapes x up to blocks_total
 // chunk counts on the issuing thread, and launch_window, run_period_impl's pre-check and sdpgpu_plan_period all ask for it
 // (at 30 us per period the second search sat on the critical path).  Dropped by layout().
@@ -226,6 +239,15 @@ struct sdpgpu_handle {
   double* d_staff_val = nullptr;    // partial arg-min rows [group][slab]
   int32_t* d_staff_idx = nullptr;
   size_t staff_part_elems = 0;
+  // kernel-form switches, read at create time (staff_read_switches): SDPGPU_STAFF_R (register block of staff_block_kernel, 4 | 8),
+  // _BLOCK=0 (staff_period_kernel, one action at a time), _PAIR (-1 unset: two states per lane where it pays, 0: never, 1: any
+  // other value, wherever it can run), _WIN (-1 unset: by the staff range's size, else the value given: 2 | 4 states per lane,
+  // anything else turns the window form off), _LANES (-1 unset: periods of at most 16 states, 0: never, 1: always lanes =
+  // actions), _UNI=0 (window kernel without the scalar-probability form)
+  int staff_r = 4;
+  bool staff_plain = false;
+  int staff_pair = -1, staff_win = -1, staff_lanes = -1;
+  bool staff_uni = true;
   bool staff_tables_nonneg = false;  // sdpgpu_staff_simulate has found no negative entry in the (by then frozen) level pmfs
   // sdpgpu_set_action_counts: per period the caller's action-list lengths of every grid state (empty: family rule)
   std::vector<std::vector<int32_t>> counts;
@@ -375,6 +397,8 @@ hipError_t launch_simulate(sdpgpu_handle* h, const sdp::SimPeriod* d_per, const 
 
 // ---- sdpgpu_staff.hip -----------------------------------------------------------------------------------
 int staff_upload(sdpgpu_handle* h);
+void staff_read_switches(sdpgpu_handle* h);  // the SDPGPU_STAFF_* switches, once per handle (sdpgpu_create)
+StaffPlan plan_staff(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi);
 hipError_t launch_staff(sdpgpu_handle* h, int period, const double* v_next, double* v_cur, int32_t* pol, int64_t lo,
                         int64_t hi, hipStream_t st);
 int64_t staff_cells(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi);

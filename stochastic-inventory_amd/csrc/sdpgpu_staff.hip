@@ -35,62 +35,60 @@ int staff_upload(sdpgpu_handle* h) {
   return SDPGPU_OK;
 }
 
-// action groups per state tile: enough waves to fill 1024 SIMDs a few times over, few enough to keep the partial
-// rows small
-static int staff_block() {  // register block of staff_block_kernel (SDPGPU_STAFF_R = 4 | 8)
-  static const int r = [] {
-    const char* e = std::getenv("SDPGPU_STAFF_R");
-    return e && std::atoi(e) == 8 ? 8 : 4;
-  }();
-  return r;
+// The SDPGPU_STAFF_* switches, once per handle: two engines of one process may run different forms.
+void staff_read_switches(sdpgpu_handle* h) {
+  if (const char* e = std::getenv("SDPGPU_STAFF_R")) h->staff_r = std::atoi(e) == 8 ? 8 : 4;
+  if (const char* e = std::getenv("SDPGPU_STAFF_BLOCK")) h->staff_plain = std::atoi(e) == 0;
+  if (const char* e = std::getenv("SDPGPU_STAFF_PAIR")) h->staff_pair = std::atoi(e) != 0;
+  if (const char* e = std::getenv("SDPGPU_STAFF_WIN")) {
+    const int v = std::atoi(e);
+    h->staff_win = v == 2 || v == 4 ? v : 0;
+  }
+  if (const char* e = std::getenv("SDPGPU_STAFF_LANES")) h->staff_lanes = std::atoi(e) != 0;
+  if (const char* e = std::getenv("SDPGPU_STAFF_UNI")) h->staff_uni = std::atoi(e) != 0;
 }
 
+// action groups per state tile: enough waves to fill 1024 SIMDs a few times over, few enough to keep the partial
+// rows small
 static void staff_groups(const sdpgpu_handle* h, int64_t states, int tile_states, int* n_groups, int* group_actions) {
   const int64_t tiles = std::max<int64_t>(1, (states + tile_states - 1) / tile_states);
   const int nA = h->n_actions_full;
   int64_t want = std::max<int64_t>(1, 16384 / tiles);
   want = std::min<int64_t>(want, nA);
-  const int R = staff_block();  // groups hold whole register blocks
+  const int R = h->staff_r;  // groups hold whole register blocks
   const int ga = (int)(((nA + want - 1) / want + R - 1) / R * R);
   *group_actions = ga;
   *n_groups = (nA + ga - 1) / ga;
 }
 
-hipError_t launch_staff(sdpgpu_handle* h, int period, const double* v_next, double* v_cur, int32_t* pol, int64_t lo,
-                        int64_t hi, hipStream_t st) {
-  if (hi <= lo) return hipSuccess;
-  const PeriodInfo& p = h->per[period - 1];
+// bounds of the next staff number: [minX, maxX] when clamped, else the next period's box
+static void staff_next_bounds(const sdpgpu_handle* h, int period, int32_t* next_x_lo, int32_t* nn_lo, int32_t* nn_hi) {
   const sdpgpu_desc& d = h->d;
-  sdp::StaffParams S{};
-  S.K = d.fixed_order_cost;
-  S.v = d.unit_order_cost;
-  S.salary = d.holding_cost;
-  S.pen = d.penalty_cost;
-  S.min_staff = (int32_t)p.overhead;
-  S.n_actions = h->n_actions_full;
-  S.n_rows = h->lvl_rows[period - 1];
-  S.uni_rows = !(std::getenv("SDPGPU_STAFF_UNI") && std::atoi(std::getenv("SDPGPU_STAFF_UNI")) == 0);
-  S.clamp = d.clamp_inventory;
-  S.min_x = (int32_t)d.min_inventory;
-  S.max_x = (int32_t)d.max_inventory;
-  S.x_lo = (int32_t)p.g.x_lo;
-  S.next_x_lo = period < h->T ? (int32_t)h->per[period].g.x_lo : 0;
+  *next_x_lo = period < h->T ? (int32_t)h->per[period].g.x_lo : 0;
   if (d.clamp_inventory) {
-    S.nn_lo = S.min_x;
-    S.nn_hi = S.max_x;
+    *nn_lo = (int32_t)d.min_inventory;
+    *nn_hi = (int32_t)d.max_inventory;
   } else {  // (never binding for a cell inside its row; keeps the reads of zero-probability steps inside the table)
-    S.nn_lo = S.next_x_lo;
-    S.nn_hi = period < h->T ? S.next_x_lo + (int32_t)h->per[period].g.nx - 1 : 0;
+    *nn_lo = *next_x_lo;
+    *nn_hi = period < h->T ? *next_x_lo + (int32_t)h->per[period].g.nx - 1 : 0;
   }
+}
+
+// Which kernel form serves the states [lo, hi) of a period, its state tiles and action groups: host arithmetic only, for
+// launch_staff and sdpgpu_plan_period, so that the plan reported is the plan launched.
+StaffPlan plan_staff(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi) {
+  StaffPlan pl;
+  const int32_t n_rows = h->lvl_rows[period - 1];
+  int32_t next_x_lo, nn_lo, nn_hi;
+  staff_next_bounds(h, period, &next_x_lo, &nn_lo, &nn_hi);
   // two adjacent states per lane (staff_pair_kernel) wherever the table and the next period's box have two entries
-  static const bool pair_off = std::getenv("SDPGPU_STAFF_PAIR") && std::atoi(std::getenv("SDPGPU_STAFF_PAIR")) == 0;
-  static const bool plain = std::getenv("SDPGPU_STAFF_BLOCK") && std::atoi(std::getenv("SDPGPU_STAFF_BLOCK")) == 0;
+  const bool pair_off = h->staff_pair == 0, plain = h->staff_plain;
   // (only where 128-state tiles x action blocks still make a few waves per SIMD: small staff ranges keep 64-state tiles)
   const bool roomy = ((hi - lo + 127) / 128) * (int64_t)((h->n_actions_full + 3) / 4) >= 4096;
   // (the pair kernel addresses the table and V_{t+1} by 32-bit byte offsets from scalar bases)
-  const bool small_tables = ((int64_t)S.n_rows + 2 * sdp::kStaffPadJ) * S.n_rows * 8 < 2147483647LL &&
+  const bool small_tables = ((int64_t)n_rows + 2 * sdp::kStaffPadJ) * n_rows * 8 < 2147483647LL &&
                             (period == h->T || (int64_t)h->per[period].g.nx * 8 < 2147483647LL);
-  const bool pair_ok = !pair_off && !plain && staff_block() == 4 && S.n_rows >= 2 && (period == h->T || S.nn_hi > S.nn_lo) && small_tables;
+  const bool pair_ok = !pair_off && !plain && h->staff_r == 4 && n_rows >= 2 && (period == h->T || nn_hi > nn_lo) && small_tables;
   // window form (staff_window_kernel: S adjacent states per lane, one probability per LEVEL instead of one per cell).  Which
   // form serves a period is its staff range's size -- measured per period on WorkforceTesting.main's instance (1, 1001, 2001,
   // ... 7001 states from period 1 to 8; tools/staff_variants.py): four states per lane from ~1500 numbers up (2001 states:
@@ -101,23 +99,64 @@ hipError_t launch_staff(sdpgpu_handle* h, int period, const double* v_next, doub
   int win_s = 0;
   if (pair_ok && hi - lo >= 1536) win_s = 4;
   else if (pair_ok && hi - lo >= 256) win_s = 2;
-  if (const char* e = std::getenv("SDPGPU_STAFF_WIN")) {
-    const int v = std::atoi(e);
-    win_s = (v == 2 || v == 4) && pair_ok ? v : 0;
-  }
+  if (h->staff_win >= 0) win_s = pair_ok ? h->staff_win : 0;
   // (without the window form: two adjacent states per lane only where 128-state tiles x action blocks still fill the chip)
-  const bool pair = win_s != 0 || (pair_ok && (roomy || std::getenv("SDPGPU_STAFF_PAIR")));
+  const bool pair = win_s != 0 || (pair_ok && (roomy || h->staff_pair >= 0));
   // a handful of states: lanes = actions (staff_action_kernel); SDPGPU_STAFF_LANES=0 never, =1 for any number of states
   bool by_action = hi - lo <= 16 && !plain;
-  if (const char* e = std::getenv("SDPGPU_STAFF_LANES")) by_action = std::atoi(e) != 0;
-  const int tile_states = by_action ? 1 : (win_s ? 64 * win_s : (pair ? 128 : 64));
+  if (h->staff_lanes >= 0) by_action = h->staff_lanes != 0;
+  pl.tile_states = by_action ? 1 : (win_s ? 64 * win_s : (pair ? 128 : 64));
   if (by_action) {
-    S.group_actions = 64;
-    S.n_groups = (h->n_actions_full + 63) / 64;
+    pl.form = STAFF_ACTION;
+    pl.r = 64;
+    pl.group_actions = 64;
+    pl.n_groups = (h->n_actions_full + 63) / 64;
   } else {
-    staff_groups(h, hi - lo, tile_states, &S.n_groups, &S.group_actions);
+    staff_groups(h, hi - lo, pl.tile_states, &pl.n_groups, &pl.group_actions);
+    if (win_s) {
+      pl.form = STAFF_WINDOW;
+      pl.r = 4;
+      pl.s = win_s;
+      pl.lds = win_s == 4 ? sdp::staff_window_lds_bytes(4, 4) : sdp::staff_window_lds_bytes(4, 2);
+    } else if (pair) {
+      pl.form = STAFF_PAIR;
+      pl.r = 4;
+      pl.s = 2;
+    } else if (plain) {  // one action at a time (kept as the cross-check of the register-blocked kernel)
+      pl.form = STAFF_PLAIN;
+      pl.r = 1;
+    } else {
+      pl.form = STAFF_BLOCK;
+      pl.r = h->staff_r;
+    }
   }
-  const int64_t tiles = (hi - lo + tile_states - 1) / tile_states;
+  pl.tiles = hi > lo ? (hi - lo + pl.tile_states - 1) / pl.tile_states : 0;
+  return pl;
+}
+
+hipError_t launch_staff(sdpgpu_handle* h, int period, const double* v_next, double* v_cur, int32_t* pol, int64_t lo,
+                        int64_t hi, hipStream_t st) {
+  if (hi <= lo) return hipSuccess;
+  const PeriodInfo& p = h->per[period - 1];
+  const sdpgpu_desc& d = h->d;
+  const StaffPlan pl = plan_staff(h, period, lo, hi);
+  sdp::StaffParams S{};
+  S.K = d.fixed_order_cost;
+  S.v = d.unit_order_cost;
+  S.salary = d.holding_cost;
+  S.pen = d.penalty_cost;
+  S.min_staff = (int32_t)p.overhead;
+  S.n_actions = h->n_actions_full;
+  S.n_rows = h->lvl_rows[period - 1];
+  S.uni_rows = h->staff_uni;
+  S.clamp = d.clamp_inventory;
+  S.min_x = (int32_t)d.min_inventory;
+  S.max_x = (int32_t)d.max_inventory;
+  S.x_lo = (int32_t)p.g.x_lo;
+  staff_next_bounds(h, period, &S.next_x_lo, &S.nn_lo, &S.nn_hi);
+  S.n_groups = pl.n_groups;
+  S.group_actions = pl.group_actions;
+  const int64_t tiles = pl.tiles;
   const int64_t blocks = tiles * S.n_groups;
   if (blocks * 64 >= 4294967296LL) return hipErrorInvalidValue;
   double* out_val = v_cur;
@@ -143,34 +182,34 @@ hipError_t launch_staff(sdpgpu_handle* h, int period, const double* v_next, doub
   }
   const double* pT = h->d_lvl_p[period - 1];
   const int32_t* len = h->d_lvl_len[period - 1];
-  if (by_action) {
+  if (pl.form == STAFF_ACTION) {
     if (period < h->T)
       hipLaunchKernelGGL((sdp::staff_action_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, st, S, pT, len, v_next, out_val,
                          out_idx, lo, hi);
     else
       hipLaunchKernelGGL((sdp::staff_action_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, st, S, pT, len, v_next, out_val,
                          out_idx, lo, hi);
-  } else if (win_s) {
+  } else if (pl.form == STAFF_WINDOW) {
 #define SDP_SW(SS, FU) \
   hipLaunchKernelGGL((sdp::staff_window_kernel<4, SS, FU>), dim3((unsigned)blocks), dim3(64), 0, st, S, pT, len, v_next, out_val, out_idx, lo, hi)
-    if (win_s == 4) { if (period < h->T) SDP_SW(4, true); else SDP_SW(4, false); }
+    if (pl.s == 4) { if (period < h->T) SDP_SW(4, true); else SDP_SW(4, false); }
     else { if (period < h->T) SDP_SW(2, true); else SDP_SW(2, false); }
 #undef SDP_SW
-  } else if (pair) {
+  } else if (pl.form == STAFF_PAIR) {
     if (period < h->T)
       hipLaunchKernelGGL((sdp::staff_pair_kernel<4, true>), dim3((unsigned)blocks), dim3(64), 0, st, S, pT, len, v_next,
                          out_val, out_idx, lo, hi);
     else
       hipLaunchKernelGGL((sdp::staff_pair_kernel<4, false>), dim3((unsigned)blocks), dim3(64), 0, st, S, pT, len, v_next,
                          out_val, out_idx, lo, hi);
-  } else if (plain) {  // one action at a time (kept as the cross-check of the register-blocked kernel)
+  } else if (pl.form == STAFF_PLAIN) {
     if (period < h->T)
       hipLaunchKernelGGL((sdp::staff_period_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, st, S, pT, len, v_next,
                          out_val, out_idx, lo, hi);
     else
       hipLaunchKernelGGL((sdp::staff_period_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, st, S, pT, len, v_next,
                          out_val, out_idx, lo, hi);
-  } else if (staff_block() == 8) {
+  } else if (pl.r == 8) {
     if (period < h->T)
       hipLaunchKernelGGL((sdp::staff_block_kernel<8, true>), dim3((unsigned)blocks), dim3(64), 0, st, S, pT, len, v_next,
                          out_val, out_idx, lo, hi);

@@ -147,7 +147,9 @@ def test_misuse_is_reported(sia):
         assert eng.footprint(1) is None
 
 
-def _random_case(seed):
+def _random_case(seed, ragged=False):
+    """ragged: every level's length is then drawn from 1 .. its length here on its own (a generator of its own: the instance
+    of a seed is otherwise the one it always was), the rows renormalised, NaN behind them in the caller's array."""
     rng = np.random.default_rng(seed)
     T = int(rng.integers(1, 5))
     clamp = bool(rng.integers(0, 2))
@@ -175,6 +177,16 @@ def _random_case(seed):
                                  salary=float(rng.integers(0, 40)) / 2, unitPenalty=float(rng.integers(0, 300)),
                                  minStaffNum=[int(v) for v in rng.integers(0, 60, size=T)], maxHireNum=max_hire,
                                  minX=min_x, maxX=max_x, clampStaff=clamp, iniStaffNum=ini)
+    if ragged:
+        rng2 = np.random.default_rng([seed, 1])
+        full = np.minimum(np.arange(rows) + 1, table.shape[2]) if row_len is None else row_len
+        row_len = rng2.integers(1, full + 1).astype(np.int32)
+        table = table.copy()
+        for y in range(rows):
+            n = row_len[y]
+            table[:, y, :n] /= table[:, y, :n].sum(axis=1, keepdims=True)
+            table[:, y, n:] = np.nan
+        return staff_cases.StaffCase(f"staff_fuzz_ragged_{seed}", f, table, row_len)
     return staff_cases.StaffCase(f"staff_fuzz_{seed}", f, table, row_len)
 
 
@@ -201,6 +213,34 @@ def test_random_instances(sia, staffref):
                 got_cells += eng.stats().cells_evaluated
         if world == 1:
             assert got_cells == cells, seed
+
+
+RAGGED_FORMS = [{}, {"SDPGPU_STAFF_PAIR": "1"}, {"SDPGPU_STAFF_PAIR": "1", "SDPGPU_STAFF_WIN": "4"},
+                {"SDPGPU_STAFF_PAIR": "1", "SDPGPU_STAFF_WIN": "2"}, {"SDPGPU_STAFF_LANES": "1"}, {"SDPGPU_STAFF_PAIR": "0"},
+                {"SDPGPU_STAFF_PAIR": "0", "SDPGPU_STAFF_R": "8"}, {"SDPGPU_STAFF_BLOCK": "0"}]
+
+
+def test_random_instances_with_ragged_rows(sia, staffref, monkeypatch):
+    """Neighbouring levels of unequal, non-monotone lengths (the named cases and the other seeds only have min(y + 1, cap)): the
+    block kernel's per-lane step count, the longer of a pair's two rows, the window kernel's wave-wide step count, under every
+    form.  Behind a row's length the caller's array holds NaN, which the reference's jagged rows do not have: a NaN in a table
+    is a read of it."""
+    for seed in range(400, 424):
+        c = _random_case(seed, ragged=True)
+        assert np.isnan(c.table).any() or (c.row_len == np.minimum(np.arange(len(c.row_len)) + 1, c.table.shape[2])).all()
+        V, pol, cells = c.oracle_problem(staffref).solve()
+        assert all(np.isfinite(v).all() for v in V), seed
+        for env in RAGGED_FORMS:
+            for k in ("SDPGPU_STAFF_R", "SDPGPU_STAFF_BLOCK", "SDPGPU_STAFF_PAIR", "SDPGPU_STAFF_WIN", "SDPGPU_STAFF_LANES"):
+                monkeypatch.delenv(k, raising=False)
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            with _engine(sia, c) as eng:
+                eng.solve(sync=True)
+                assert eng.stats().cells_evaluated == cells, (seed, env)
+                for period in range(1, c.T + 1):
+                    assert np.array_equal(eng.values(period), V[period - 1]), (seed, env, period)
+                    assert np.array_equal(eng.policy(period), pol[period - 1]), (seed, env, period)
 
 
 def test_two_states_per_lane_kernel_on_every_case(sia, staffref, monkeypatch):
