@@ -1019,6 +1019,45 @@ int sdpgpu_sample_demands(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int3
 int sdpgpu_staff_simulate(sdpgpu_handle* h, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
                           int32_t n_rules, sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid, int32_t* out_demand);
 
+/* ---- CASH family: (s, C, S) ordering rules rolled out along sampled demand paths -------------------------------------
+ * What CashSimulation.simulatesCS with (s, C1(x), C2(x), S) (CashSimulation.java:996-1042), simulatesCS with (s, C1(x), S)
+ * (:1050-1093) and simulatesMeanCS (:1101-1134) do after a solve, on the device; the four calls of CashConstraintTesting.main
+ * (CashConstraintTesting.java:187, 201, 216, 241) are one call with n_rules = 4.  Definition: DESIGN 4, "Cash rule rollout".
+ * Additive to ABI 6.
+ *   handle   family CASH with cash_formula 0 or 1.  Needs the pmf tiles (or a spec on every period without one) and a device,
+ *            NOT a solve: the rule replaces the policy table.
+ *   draws    n_paths, seed, mode, first_path as sdpgpu_simulate_sampled: sdpgpu_sample_demands returns the demands EVERY rule
+ *            of the call sees (the counters do not carry the rule).
+ *   rule r   form[r] one of the three below; rule[(r * T + t) * 4 + {0, 1, 2, 3}] = (s, c1, c2, S) of period index t; optional
+ *            dense threshold tables c1_tab, c2_tab [(r * T + t) * NX + ix], NX = the descriptor's inventory points
+ *            ((int)((max_inventory - min_inventory) / step) + 1), entry ix keyed by x = min_inventory + ix * step, NaN = key
+ *            absent, a NULL table = every key absent, entries of t = 0 not read.  A lookup at x hits only where x IS that
+ *            double (TreeMap.get(new State(period, x))).
+ *   period   t >= 1: m = max(0, (cash - min_cash_required - fix_order_cost) / vari_cost); form 0: m = (double)(int)m; m =
+ *            min(m, max_q).  Below s (x < s): forms 0, 1 read c1 from the table (absent: 0.0), form 0 reads c2 (absent:
+ *            10000.0), form 2 keeps the row's c1.  q = min(m, S - x) when x < s and cash > c1 (form 0: and cash < c2), else 0.
+ *            t = 0: q = x < s ? S - x : 0; form 1 then takes min(q, max(0, (cash - min_cash_required - fix_order_cost) /
+ *            vari_cost)).  A negative q is not refused.  The four scalars are the reference's ARGUMENTS; the descriptor's own
+ *            costs enter through the family's statements below.
+ *   step     sum += discount[t] * immediateValue(state, q, d); state = stateTransition(state, q, d): the CASH family's
+ *            statements with the order quantity as a double (per-period overhead, salvage in period T, penalty, both clamps,
+ *            the cash quantiser; one fp64 operation per statement, no contraction).  The state is the two doubles (x, cash):
+ *            the inventory may leave the grid, no path ever becomes invalid.  discount NULL = all 1.0.
+ * results[r] (n_rules of them): n_paths, n_valid = n_paths, n_lost = 0, mean and m2 of the rule's path sums in the fixed order
+ * of sdpgpu_simulate_sampled, kernel_ms of the whole call.  out_sum: NULL or [r * n_paths + p].  A call with R rules returns
+ * what R calls with one rule each return, bit for bit; RANDOM calls (0, a) then (a, b) give the sums of one call (0, a + b).
+ * Refusals, all before the first device call and naming the argument: not a CASH handle, cash_formula 2, a user functor,
+ * n_paths above 2^24 SDPGPU_ERR_UNSUPPORTED; world_size != 1, a period without tile or spec SDPGPU_ERR_STATE; n_paths < 1, a
+ * bad mode, LHS with first_path != 0, n_rules outside 1 .. 16, a form outside 0 .. 2, a rule entry, start value or scalar
+ * that is not finite, vari_cost <= 0, max_q < 0, a NULL form, rule or results, an infinite table entry SDPGPU_ERR_ARG. */
+#define SDPGPU_RULE_SC12S 0   /* (s, C1(x), C2(x), S) */
+#define SDPGPU_RULE_SC1S 1    /* (s, C1(x), S) */
+#define SDPGPU_RULE_SMEANCS 2 /* (s, C, S), C the row's own c1 */
+int sdpgpu_cash_rule_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t mode, uint64_t first_path,
+                              const double* discount, double ini_x, double ini_cash, int32_t n_rules, const int32_t* form,
+                              const double* rule, const double* c1_tab, const double* c2_tab, double min_cash_required,
+                              double max_q, double fix_order_cost, double vari_cost, sdpgpu_sim_result* results, double* out_sum);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -248,6 +248,7 @@ class SdpgpuDistSpec(C.Structure):
 
 DIST_POISSON, DIST_NORMAL, DIST_UNIFORM_INT, DIST_GAMMA = 1, 2, 3, 4
 SAMPLE_LHS, SAMPLE_RANDOM = 0, 1
+RULE_SC12S, RULE_SC1S, RULE_SMEANCS = 0, 1, 2  # SDPGPU_RULE_*: the forms of sdpgpu_cash_rule_simulate
 
 
 class SdpgpuSimResult(C.Structure):
@@ -365,6 +366,9 @@ EXPORTS = {
     "sdpgpu_sample_demands": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, _DP]),
     "sdpgpu_staff_simulate": (C.c_int, [_P, _IP, C.c_uint64, C.c_double, _DP, C.c_int32, C.POINTER(SdpgpuSimResult), _DP,
                                         C.POINTER(C.c_uint8), _IP]),
+    "sdpgpu_cash_rule_simulate": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_int32, _IP,
+                                            _DP, _DP, _DP, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(SdpgpuSimResult),
+                                            _DP]),
 }
 
 _lib = None

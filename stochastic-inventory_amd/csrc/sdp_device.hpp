@@ -174,6 +174,20 @@ __device__ __forceinline__ void action_setup(const DevParams& P, const StateT& s
   }
 }
 
+// action_setup<FAM_CASH> for an order quantity that arrives as a double (the (s, C, S) rule rollout, sdp_cash_rule_sim.hpp: the
+// quantity is cash / variCost and need not be a multiple of the step): the same statements with a = q.
+__device__ __forceinline__ void action_setup_q(const DevParams& P, const StateT& s, double q, ActionCtx& c) {
+  c.a = q;
+  c.fixed = c.a > 0 ? P.K : 0.0;
+  c.var = P.v * c.a;
+  c.fv = c.fixed + c.var;
+  c.before = 0;
+  c.interest = 0;
+  c.next_q_off = 0;
+  c.base = s.x + c.a;
+  c.deposit = (s.cash - c.fixed - c.var) * P.one_plus_deposit;
+}
+
 // Inventory index of a (clamped) next inventory value in the next period's grid.
 // (v_cvt_i32_f64: grids are < 2^31 points per axis, checked at create.)
 __device__ __forceinline__ int inv_index(const DevParams& P, double next_inv) {

@@ -11,7 +11,9 @@
 //   sdpgpu_batch.hip    a batch of F1 instances (own entry points): batched solve, batched rollout of the table policy and of
 //                       (s, S) level rules (ONE kernel over a rule: sdp_batch_sim.hpp, sdp_fitss.hpp), the level-rule fit
 //   sdpgpu_simsample.hip  demand paths drawn on the device for a handle's policy simulation (sampler, fused rollout, reduction)
-//   sdpgpu_sim_host.hpp   host helpers of those two units: exception barrier, device scope, stream record, sampler specs, scratch
+//   sdpgpu_staffsim.hip   STAFF family: a hiring rule rolled out on a sampled tree
+//   sdpgpu_cashrulesim.hip  CASH family: (s, C, S) ordering rules rolled out along sampled demand paths, the state kept as doubles
+//   sdpgpu_sim_host.hpp   host helpers of those units: exception barrier, device scope, stream record, sampler specs, scratch
 //   sdpgpu_comm.hip     multi-GPU: RCCL communicators (loaded on first use), per-period all-gather, sharded sweeps
 #pragma once
 #include "../../include/sdpgpu.h"

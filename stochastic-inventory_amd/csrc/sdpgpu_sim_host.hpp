@@ -153,6 +153,11 @@ int sim_scratch(Owner* o, size_t bytes) {
 // n device-resident sums and their W = ceil(n / 64) wave partials: d_res[0] = mean, d_res[1] = m2, both NaN when d_cnt[0] < n
 hipError_t launch_sim_moments(hipStream_t st, const double* d_sum, uint32_t n, double* d_part, const unsigned int* d_cnt, double* d_res);
 
+// sdpgpu_simsample.hip, shared with the cash rule rollout (sdpgpu_cashrulesim.hip): the refusals of a call's stream arguments
+// (n_paths, mode, first_path, a period without a tile or spec), and the handle's sampler records with their two arenas
+int check_stream_args(sdpgpu_handle* h, const char* who, int32_t n_paths, int32_t mode, uint64_t first_path);
+void build_samplers(const sdpgpu_handle* h, std::vector<sdp::SimSampler>* rec, std::vector<double>* thr, std::vector<double>* val);
+
 // offsets of the scratch block, every part aligned to 16 bytes
 struct Carve {
   size_t at = 0;

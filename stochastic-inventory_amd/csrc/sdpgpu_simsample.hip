@@ -21,6 +21,34 @@ int refuse(sdpgpu_handle* h, const char* who) {
   return SDPGPU_OK;
 }
 
+template <bool RANDOM>
+hipError_t launch_fused(sdpgpu_handle* h, dim3 grid, const sdp::SimPeriod* d_per, const sdp::SimSampler* d_samp, const double* d_thr,
+                        const double* d_val, const double* d_disc, const sdp::SimStream& R, int64_t idx0, const sdp::StateT& ini, int first_k,
+                        double* d_sum, uint8_t* d_flags, double* d_part, unsigned int* d_counts) {
+  const int T = h->T;
+#define SDP_SIMS(F)                                                                                                                  \
+  case F:                                                                                                                            \
+    hipLaunchKernelGGL((sdp::sim_sampled_kernel<F, RANDOM>), grid, dim3(256), 0, h->stream, d_per, T, h->d_policy, d_samp, d_thr, d_val, \
+                       d_disc, R, idx0, ini, first_k, d_sum, d_flags, d_part, d_counts);                                             \
+    break;
+  switch (h->d.family) {
+    SDP_SIMS(sdp::FAM_BACKORDER)
+    SDP_SIMS(sdp::FAM_LEADTIME)
+    SDP_SIMS(sdp::FAM_CASH)
+    SDP_SIMS(sdp::FAM_OVERDRAFT)
+    SDP_SIMS(sdp::FAM_CASH_LEADTIME)
+    SDP_SIMS(sdp::FAM_SURVIVAL)
+    default:
+      return hipErrorInvalidValue;
+  }
+#undef SDP_SIMS
+  return hipGetLastError();
+}
+
+}  // namespace
+
+namespace sdpgpu_detail {
+
 int check_stream_args(sdpgpu_handle* h, const char* who, int32_t n_paths, int32_t mode, uint64_t first_path) {
   if (const int rc = check_n_paths(h, who, n_paths)) return rc;
   if (mode != SDPGPU_SAMPLE_LHS && mode != SDPGPU_SAMPLE_RANDOM)
@@ -55,34 +83,6 @@ void build_samplers(const sdpgpu_handle* h, std::vector<sdp::SimSampler>* rec, s
     (*rec)[(size_t)t] = S;
   }
 }
-
-template <bool RANDOM>
-hipError_t launch_fused(sdpgpu_handle* h, dim3 grid, const sdp::SimPeriod* d_per, const sdp::SimSampler* d_samp, const double* d_thr,
-                        const double* d_val, const double* d_disc, const sdp::SimStream& R, int64_t idx0, const sdp::StateT& ini, int first_k,
-                        double* d_sum, uint8_t* d_flags, double* d_part, unsigned int* d_counts) {
-  const int T = h->T;
-#define SDP_SIMS(F)                                                                                                                  \
-  case F:                                                                                                                            \
-    hipLaunchKernelGGL((sdp::sim_sampled_kernel<F, RANDOM>), grid, dim3(256), 0, h->stream, d_per, T, h->d_policy, d_samp, d_thr, d_val, \
-                       d_disc, R, idx0, ini, first_k, d_sum, d_flags, d_part, d_counts);                                             \
-    break;
-  switch (h->d.family) {
-    SDP_SIMS(sdp::FAM_BACKORDER)
-    SDP_SIMS(sdp::FAM_LEADTIME)
-    SDP_SIMS(sdp::FAM_CASH)
-    SDP_SIMS(sdp::FAM_OVERDRAFT)
-    SDP_SIMS(sdp::FAM_CASH_LEADTIME)
-    SDP_SIMS(sdp::FAM_SURVIVAL)
-    default:
-      return hipErrorInvalidValue;
-  }
-#undef SDP_SIMS
-  return hipGetLastError();
-}
-
-}  // namespace
-
-namespace sdpgpu_detail {
 
 // mean = (wave partials in the fixed order) / n; m2 = a second pass over the sums in the same order (which reuses the partials)
 hipError_t launch_sim_moments(hipStream_t st, const double* d_sum, uint32_t n, double* d_part, const unsigned int* d_cnt, double* d_res) {

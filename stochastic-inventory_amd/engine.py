@@ -401,6 +401,53 @@ class SdpEngine:
             out.append(dem)
         return out[0] if len(out) == 1 else tuple(out)
 
+    def rule_table_points(self) -> int:
+        """NX of the threshold tables of cash_rule_simulate: the descriptor's inventory points, entry ix keyed by
+        min_inventory + ix * step."""
+        d = self.desc
+        return int((d.max_inventory - d.min_inventory) / d.step) + 1
+
+    def cash_rule_simulate(self, n_paths: int, seed: int, ini_x: float, ini_cash: float, forms, rules, *, min_cash_required: float,
+                           max_q: float, fix_order_cost: float, vari_cost: float, c1_tab=None, c2_tab=None, mode="lhs",
+                           first_path: int = 0, discount=None, want_sums: bool = False):
+        """CASH family: roll (s, C, S) ordering rules out along demand paths drawn on the device (sdpgpu_cash_rule_simulate;
+        DESIGN 4, "Cash rule rollout").  forms: one of _abi.RULE_SC12S / RULE_SC1S / RULE_SMEANCS per rule; rules: (s, c1, c2, S)
+        rows of shape (T, 4) or (R, T, 4); c1_tab / c2_tab: None or dense threshold tables (R, T, NX), NX = rule_table_points(),
+        NaN = key absent.  Needs no solve.  Returns the list of SdpgpuSimResult, one per rule; with want_sums also sums[R, n]."""
+        rows = np.ascontiguousarray(rules, dtype=np.float64)
+        if rows.ndim == 2:
+            rows = rows[None]
+        if rows.ndim != 3 or rows.shape[1:] != (self.T, 4):
+            raise ValueError(f"rules must have shape ({self.T}, 4) or (rules, {self.T}, 4)")
+        n_rules = rows.shape[0]
+        fm = np.ascontiguousarray(np.atleast_1d(forms), dtype=np.int32)
+        if fm.shape != (n_rules,):
+            raise ValueError(f"forms must have one entry per rule ({n_rules})")
+        nx = self.rule_table_points()
+        tabs = []
+        for name, tab in (("c1_tab", c1_tab), ("c2_tab", c2_tab)):
+            if tab is not None:
+                tab = np.ascontiguousarray(tab, dtype=np.float64)
+                if tab.ndim == 2:
+                    tab = tab[None]
+                if tab.shape != (n_rules, self.T, nx):
+                    raise ValueError(f"{name} must have shape ({n_rules}, {self.T}, {nx})")
+            tabs.append(tab)
+        disc = None
+        if discount is not None:
+            disc = np.ascontiguousarray(discount, dtype=np.float64)
+            if disc.shape != (self.T,):
+                raise ValueError("discount must have one entry per period")
+        n = min(max(int(n_paths), 0), 1 << 24)  # (the library refuses a bad count; the buffer below only needs a size)
+        res = (_abi.SdpgpuSimResult * max(n_rules, 1))()
+        sums = np.empty((min(max(n_rules, 1), 16), n), dtype=np.float64) if want_sums else None
+        self._check(self._lib.sdpgpu_cash_rule_simulate(
+            self._h, int(n_paths), C.c_uint64(int(seed) & (2**64 - 1)), self._sample_mode(mode), C.c_uint64(int(first_path) & (2**64 - 1)),
+            None if disc is None else _dp(disc), float(ini_x), float(ini_cash), n_rules, _ip(fm), _dp(rows),
+            None if tabs[0] is None else _dp(tabs[0]), None if tabs[1] is None else _dp(tabs[1]), float(min_cash_required), float(max_q),
+            float(fix_order_cost), float(vari_cost), res, None if sums is None else _dp(sums)))
+        return (list(res), sums) if want_sums else list(res)
+
     def stats(self) -> SdpgpuStats:
         st = SdpgpuStats()
         self._check(self._lib.sdpgpu_stats_get(self._h, C.byref(st)))

@@ -22,6 +22,7 @@ from typing import Sequence
 
 import numpy as np
 
+from . import _abi
 from .functors import java_round
 
 
@@ -204,6 +205,160 @@ class Simulation:
                 state = self.stateTransition(state, optQ, float(d))
             out[i] = total
         return out
+
+
+CASH_RULE_M = 10000.0  # `int M = 10000` (CashSimulation.java:1004): C2 of an inventory level without an entry
+
+
+def cash_rule_rows(form: int, optsCS) -> np.ndarray:
+    """The reference's optsCS as the (T, 4) rows (s, c1, c2, S) of sdpgpu_cash_rule_simulate: form 0 has the four columns
+    already (CashSimulation.java:1011-1028); the three columns [s, C, S] of forms 1 and 2 (:1064-1079, :1113-1120) become
+    (s, C, 0, S).  Four columns are taken as they are."""
+    rows = np.asarray(optsCS, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] not in (3, 4) or (form == _abi.RULE_SC12S and rows.shape[1] != 4):
+        raise ValueError(f"optsCS of shape {rows.shape}: [T, 4] for (s, C1, C2, S), [T, 3] for (s, C, S)")
+    if rows.shape[1] == 3:
+        rows = np.stack([rows[:, 0], rows[:, 1], np.zeros(len(rows)), rows[:, 2]], axis=1)
+    return np.ascontiguousarray(rows)
+
+
+def cash_rule_table_index(x: float, min_inventory: float, step: float, nx: int):
+    """Index of the table entry whose key IS the double x (key of entry ix: min_inventory + ix * step), or None -- the lookup
+    of DESIGN 4, "Cash rule rollout"."""
+    fi = float(np.rint((x - min_inventory) * (1.0 / step)))
+    if not (0.0 <= fi < nx):
+        return None
+    i = int(fi)
+    return i if min_inventory + i * step == x else None
+
+
+def pack_cash_rule_table(cache, T: int, min_inventory: float, step: float, nx: int) -> np.ndarray:
+    """A cacheC1Values / cacheC2Values map {(period, x): value} (period 1-based, as State.getPeriod(); a State key works too)
+    as the dense (T, NX) table: NaN where no key is present; a key off the grid or outside the horizon can never be hit and is
+    dropped."""
+    tab = np.full((T, nx), np.nan)
+    for key, v in (cache or {}).items():
+        period, x = (key.getPeriod(), key.getIniInventory()) if hasattr(key, "getPeriod") else key
+        ix = cash_rule_table_index(float(x), min_inventory, step, nx)
+        if ix is not None and 1 <= int(period) <= T and int(period) == period:
+            tab[int(period) - 1, ix] = float(v)
+    return tab
+
+
+def cash_rule_order(form: int, t: int, row, c1_row, c2_row, x: float, cash: float, minCashRequired: float, maxQ: float,
+                    fixOrderCost: float, variCost: float, grid) -> float:
+    """optQ of one period (CashSimulation.java:1009-1031, :1062-1082, :1111-1123).  row = (s, c1, c2, S); c1_row / c2_row:
+    the period's dense table rows or None; grid = (min_inventory, step, nx)."""
+    from .functors import _d2i
+    s, c1, c2, S = (float(v) for v in row)
+    m = max(0.0, (cash - minCashRequired - fixOrderCost) / variCost)
+    if t == 0:
+        q = S - x if x < s else 0.0
+        return min(q, m) if form == _abi.RULE_SC1S else q
+    if form == _abi.RULE_SC12S:
+        m = float(_d2i(m))
+    m = min(m, maxQ)
+    if not x < s:
+        return 0.0
+
+    def lookup(tab_row, absent):
+        ix = None if tab_row is None else cash_rule_table_index(x, *grid)
+        return absent if ix is None or tab_row[ix] != tab_row[ix] else float(tab_row[ix])
+
+    if form != _abi.RULE_SMEANCS:
+        c1 = lookup(c1_row, 0.0)
+    if form == _abi.RULE_SC12S:
+        c2 = lookup(c2_row, CASH_RULE_M)
+    orders = cash > c1 and (form != _abi.RULE_SC12S or cash < c2)
+    return min(m, S - x) if orders else 0.0
+
+
+class CashSimulation(Simulation):
+    """sdp.cash.CashSimulation(distributions, sampleNum, recursion, discountFactor): the SDP simulation of Simulation plus the
+    rollouts of an (s, C, S) ordering rule -- simulatesCS in its two forms and simulatesMeanCS (CashSimulation.java:996-1134),
+    the twelve extra columns of CashConstraintTesting.main.  sampler="device" (the default here): demand paths are drawn, every
+    rule rolled and the means reduced on the device in one call (SdpEngine.cash_rule_simulate; DESIGN 4, "Cash rule rollout"); a
+    rule needs no solve.  sampler="host": the same rules through the recursion's Python lambdas on host-sampled demands.
+    The rule is an argument (FindsCS is not mirrored)."""
+
+    def __init__(self, distributions: Sequence, sampleNum: int, recursion, discountFactor: float = 1.0, seed: int = 12345,
+                 sampler: str = "device"):
+        super().__init__(distributions, sampleNum, recursion, discountFactor, seed, sampler)
+        self.last_results = None
+
+    def _grid(self):
+        f = self.recursion.functor
+        return (float(f.minInventoryState), float(f.stepSize), self.recursion.engine.rule_table_points())
+
+    def _pack(self, rules):
+        """rules: (form, optsCS[, cacheC1Values[, cacheC2Values]]) each -> forms[R], rows[R, T, 4], c1_tab, c2_tab (None when no
+        rule brings that map)."""
+        T, grid = self.recursion.T, self._grid()
+        forms, rows, c1, c2 = [], [], [], []
+        for rule in rules:
+            form, opts = int(rule[0]), rule[1]
+            r = cash_rule_rows(form, opts)
+            if r.shape[0] != T:
+                raise ValueError(f"optsCS has {r.shape[0]} periods, the horizon is {T}")
+            forms.append(form)
+            rows.append(r)
+            c1.append(rule[2] if len(rule) > 2 else None)
+            c2.append(rule[3] if len(rule) > 3 else None)
+
+        def tabs(maps):
+            if all(m is None for m in maps):
+                return None
+            return np.stack([pack_cash_rule_table(m, T, *grid) for m in maps])
+
+        return np.asarray(forms, dtype=np.int32), np.stack(rows), tabs(c1), tabs(c2)
+
+    def simulateRulesOnDemands(self, iniState, rules, demands, minCashRequired, maxQ, fixOrderCost, variCost) -> np.ndarray:
+        """The reference's loops through the recursion's lambdas (sampler="host" and the cross-check of the device rollout):
+        path sums [R, n] of the rules along demands[n, T]."""
+        forms, rows, c1, c2 = self._pack(rules)
+        grid, disc = self._grid(), self._discount()
+        out = np.empty((len(forms), len(demands)))
+        for r, form in enumerate(forms.tolist()):
+            for i, path in enumerate(demands):
+                total, state = 0.0, iniState
+                for t, d in enumerate(path):
+                    q = cash_rule_order(form, t, rows[r, t], None if c1 is None else c1[r, t], None if c2 is None else c2[r, t],
+                                        state.getIniInventory(), state.getIniCash(), minCashRequired, maxQ, fixOrderCost, variCost, grid)
+                    total += disc[t] * self.immediateValue(state, q, float(d))
+                    state = self.stateTransition(state, q, float(d))
+                out[r, i] = total
+        return out
+
+    def simulateRules(self, iniState, rules, minCashRequired, maxQ, fixOrderCost, variCost) -> np.ndarray:
+        """Several rules along the SAME demand paths in one call: rules = [(form, optsCS[, cacheC1Values[, cacheC2Values]]),
+        ...], form one of _abi.RULE_SC12S / RULE_SC1S / RULE_SMEANCS.  Returns mean + iniCash per rule; last_values holds the
+        path sums [R, n], last_results the device's results."""
+        if self.sampler == "device":
+            forms, rows, c1, c2 = self._pack(rules)
+            res, sums = self.recursion.engine.cash_rule_simulate(
+                self.sampleNum, self.seed, iniState.getIniInventory(), iniState.getIniCash(), forms, rows, c1_tab=c1, c2_tab=c2,
+                min_cash_required=minCashRequired, max_q=maxQ, fix_order_cost=fixOrderCost, vari_cost=variCost, mode="lhs",
+                discount=self._discount(), want_sums=True)
+            self.last_results, self.last_values = res, sums
+            return np.array([r.mean + iniState.getIniCash() for r in res])
+        samples = self.sampling.generateLHSamples(self.distributions, self.sampleNum)
+        sums = self.simulateRulesOnDemands(iniState, rules, round_demands(samples), minCashRequired, maxQ, fixOrderCost, variCost)
+        self.last_results, self.last_values = None, sums
+        return np.array([math.fsum(s.tolist()) / len(s) + iniState.getIniCash() for s in sums])
+
+    def simulatesCS(self, iniState, optsCS, cacheC1Values, *rest) -> float:
+        """Both reference overloads: (iniState, optsCS, cacheC1Values, cacheC2Values, minCashRequired, maxQ, fixOrderCost,
+        variCost) is the (s, C1, C2, S) rule (CashSimulation.java:996-1042); without cacheC2Values -- (iniState, optsCS,
+        cacheC1Values, overheadCost, maxQ, fixOrderCost, variCost) -- the (s, C1, S) rule (:1050-1093)."""
+        if len(rest) == 5:
+            return float(self.simulateRules(iniState, [(_abi.RULE_SC12S, optsCS, cacheC1Values, rest[0])], *rest[1:])[0])
+        if len(rest) == 4:
+            return float(self.simulateRules(iniState, [(_abi.RULE_SC1S, optsCS, cacheC1Values)], *rest)[0])
+        raise TypeError("simulatesCS(iniState, optsCS, cacheC1Values, [cacheC2Values,] minCashRequired, maxQ, fixOrderCost, variCost)")
+
+    def simulatesMeanCS(self, iniState, optsCS, minCashRequired, maxQ, fixOrderCost, variCost) -> float:
+        """CashSimulation.java:1101-1134: the (s, C, S) rule with one C per period."""
+        return float(self.simulateRules(iniState, [(_abi.RULE_SMEANCS, optsCS)], minCashRequired, maxQ, fixOrderCost, variCost)[0])
 
 
 class RiskSimulation:
