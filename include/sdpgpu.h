@@ -1058,6 +1058,56 @@ int sdpgpu_cash_rule_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, 
                               const double* rule, const double* c1_tab, const double* c2_tab, double min_cash_required,
                               double max_q, double fix_order_cost, double vari_cost, sdpgpu_sim_result* results, double* out_sum);
 
+/* ---- CASH family, cash_formula 2: the (x, R) state of CashConstraintXR rolled out along demand paths -------------------
+ * What CashSimulationXR.simulateSDPGivenSamplNum (CashSimulationXR.java:91-113), the sampling loop of
+ * simulateSDPwithErrorConfidence (:115-147) and simulateAStar (:153-173) do after CashConstraintXR.main's solve, on the device.
+ * Definition: DESIGN 4, "(x, R) rollout".  Additive to ABI 6.  sdpgpu_simulate, sdpgpu_simulate_sampled, sdpgpu_sample_demands
+ * and sdpgpu_cash_rule_simulate keep refusing such a handle: this is the family's entry point of its own.
+ *   handle   family CASH with cash_formula 2, world_size 1, no user functor.
+ *   demands  demand == NULL: drawn on the device -- n_paths, seed, mode, first_path exactly as sdpgpu_simulate_sampled
+ *            (latin hypercube or plain random, instance position 0; RANDOM calls (0, a) then (a, b) continue one stream) from
+ *            the pmf tiles or the specs of sdpgpu_set_sampler.  demand != NULL (GIVEN): the caller's demand[p * T + t]; seed,
+ *            mode and first_path are not read.  The counters do not carry the rule: every rule of a call sees the same demands.
+ *   table    levels == NULL, n_rules 1: the handle's policy table, needs a solve.  Per period the statements of
+ *   rule     sdpgpu_simulate (optQ = getAction(state), immediateValue, stateTransition); a period-1 state (ini_x, ini_r) off
+ *            the grid takes its action from sdpgpu_eval_states.  Both clamps are in the transition: from a grid state no
+ *            path leaves the grid.  From a start whose INVENTORY is off the grid the period-1 successor is a grid state only
+ *            where the period sells out or fills the shelf; any other path ends there (the reference would re-enter its
+ *            recursion at a state no table holds): out_sum keeps period 1's term, n_valid < n_paths, mean and m2 are NaN, as
+ *            with sdpgpu_simulate_sampled; the action of such a start values a successor that is no grid state at 0.
+ *   level    levels[r * T + t] = a_t of rule r, n_rules 1 .. 16, needs NO solve and no layout.  The state is the two doubles
+ *   rule     (x, R), any finite start.  Period index t: y = R > vari_cost * a_t ? a_t : R / vari_cost (:162; a y below x is not
+ *            refused: the reference sells stock back at cost there); sum += discount[t] * immediateValue(state, y, d) -- the
+ *            statements of CashConstraintXR.java:78-91 with the level itself (action = y - x, fixed = y > x ? K : 0, initCash =
+ *            R - v * x, revenue = price * min(y, d), inventoryLevel = y - d: the level before demand is y, not x + (y - x)) --;
+ *            state = stateTransition(state, y, d) (:94-110: nextInv = max(0, y - d), nextCash = initCash + imm, both clamps, the
+ *            handle's cash quantiser, R' = nextCash + v * nextInv).  One fp64 operation per statement, no contraction.
+ *            vari_cost is the reference's constructor ARGUMENT variOrderCost; v, K and the other costs are the descriptor's.
+ *            recursion.getExpectedValue(state) of :161 is a memo side effect whose result is discarded: not mirrored.
+ * results[r] (n_rules of them): n_paths, n_valid = n_paths (but for the case above), n_lost = 0, mean and m2 of the rule's path
+ * sums in the fixed order of sdpgpu_simulate_sampled (no floating-point atomics), kernel_ms of the whole call.  out_sum: NULL or [r * n_paths + p];
+ * out_demand: NULL or [p * T + t], the demands every rule saw.  A call with R rules returns what R calls with one rule each
+ * return, bit for bit.  iniState.iniR (:110, :142, :170) is added by the caller.
+ * Refusals, all before the first device call and naming the argument: not a CASH handle with cash_formula 2, a user functor,
+ * n_paths above 2^24 SDPGPU_ERR_UNSUPPORTED; world_size != 1, a period without tile or spec while demand == NULL, the table rule
+ * before a solve SDPGPU_ERR_STATE; n_paths < 1, a bad mode, LHS with first_path != 0, n_rules outside 1 .. 16, n_rules != 1
+ * under the table rule, a level, start value, discount or given demand that is not finite, vari_cost <= 0 or not finite, NULL
+ * results SDPGPU_ERR_ARG. */
+int sdpgpu_xr_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t mode, uint64_t first_path, const double* demand,
+                       const double* discount, double ini_x, double ini_r, int32_t n_rules, const double* levels,
+                       double vari_cost, sdpgpu_sim_result* results, double* out_sum, double* out_demand);
+/* Chao's a* of every period: RecursionG.getOptY (RecursionG.java:80-153) over pmf tiles, host only and handle-free (as
+ * sdpgpu_fit_ss; errors through sdpgpu_last_error(NULL)).  Period index t's tile is elements tile_off[t] .. tile_off[t + 1] - 1 of
+ * tile_demand / tile_prob (tile_off[0] = 0).  The reference's two mutually recursive functions, literally: G (:96-123, the
+ * statement order of :105-107 and :116-118) and getAStar (:130-153: the scan y = 0; y < max_y; y += 1 from optYValue = -1000,
+ * a level taken only where it improves by MORE THAN 0.01); the memo of G is keyed by (period, y as a double).  The reference
+ * hard-codes max_y = 200.  aNStar of the constructor (an SSJ quantile, :66-70) is overwritten by the loop of :83-86 before
+ * anything reads it: it is not needed.  Math.pow(1 + depositeRate, T - n) is the host libm's pow: agreement with Java's is
+ * claimed only where the result is exact (deposit_rate 0, the driver's case).  T x max_y x |pmf| operations per memo entry's
+ * first visit; no device code.  SDPGPU_ERR_ARG: T < 1, max_y < 1, a NULL array, an empty tile, a value that is not finite. */
+int sdpgpu_xr_opt_levels(int32_t T, const int64_t* tile_off, const double* tile_demand, const double* tile_prob, double price,
+                         double vari_cost, double deposit_rate, double salvage, int32_t max_y, double* out_levels);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -15,8 +15,9 @@ from .functors import (BackorderFunctor, CashFunctor, CashXRFunctor, CashLeadtim
 from .multiitem import (Actions, CashRecursionMulti, CashRecursionMultiLead, CashRecursionMultiXR, CashStateMulti,
                         CashStateMultiLead, CashStateMultiXR, MultiLeadResult, multicash_solve, multilead_solve, multixr_solve)
 from .pmf import BinomialDist, DiscreteDistribution, GammaDist, GetPmf, NormalDist, PoissonDist, UniformIntDist, staff_level_pmf
-from .recursion import CLSP, CashLeadtimeRecursion, CashRecursion, CashRecursionXR, LeadtimeRecursion, Recursion, RecursionBatch, RiskRecursion
-from .simulation import CashSimulation, RiskSimulation, Sampling, SimulateFitsS, Simulation, SimulationBatch
+from .recursion import (CLSP, CashLeadtimeRecursion, CashRecursion, CashRecursionXR, LeadtimeRecursion, Recursion, RecursionBatch, RecursionG,
+                        RiskRecursion)
+from .simulation import CashSimulation, CashSimulationXR, RiskSimulation, Sampling, SimulateFitsS, Simulation, SimulationBatch
 from .workforce import SimulatesS, StaffFunctor, StaffRecursion, StaffState
 from .structure import CheckKConvexity
 from .states import CashLeadtimeState, CashState, CashStateXR, LeadtimeState, OptDirection, RiskState, State
@@ -28,7 +29,7 @@ __all__ = [
     "StaffRecursion", "StaffFunctor", "StaffState", "SimulatesS", "BinomialDist", "staff_level_pmf",
     "multilead_solve", "multicash_solve", "multixr_solve", "MultiLeadResult", "Actions", "CashRecursionMulti",
     "CashRecursionMultiLead", "CashRecursionMultiXR", "CashStateMulti", "CashStateMultiLead", "CashStateMultiXR",
-    "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "SimulationBatch", "RiskSimulation", "CashSimulation", "Sampling",
+    "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "SimulationBatch", "RiskSimulation", "CashSimulation", "CashSimulationXR", "RecursionG", "Sampling",
     "FitsS", "SimulateFitsS", "CheckKConvexity", "SdpgpuConvexity",
     "State", "LeadtimeState", "CashState", "CashStateXR", "CashLeadtimeState", "RiskState", "OptDirection", "java_round",
 ]

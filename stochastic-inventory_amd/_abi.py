@@ -369,6 +369,9 @@ EXPORTS = {
     "sdpgpu_cash_rule_simulate": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_int32, _IP,
                                             _DP, _DP, _DP, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(SdpgpuSimResult),
                                             _DP]),
+    "sdpgpu_xr_simulate": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, _DP, C.c_double, C.c_double, C.c_int32, _DP,
+                                     C.c_double, C.POINTER(SdpgpuSimResult), _DP, _DP]),
+    "sdpgpu_xr_opt_levels": (C.c_int, [C.c_int32, _LP, _DP, _DP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _DP]),
 }
 
 _lib = None

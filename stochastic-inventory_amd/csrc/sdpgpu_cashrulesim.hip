@@ -12,8 +12,13 @@ namespace {
 
 constexpr int32_t kCashRuleMaxRules = 16;
 
+}  // namespace
+
+namespace sdpgpu_detail {
+
 // the period's parameter block without a layout (the rollout reads no table, so it needs no pmf tile where a spec is set): the
-// family's scalars and the handle's overhead from make_params, the boxes from the descriptor as layout() forms them
+// family's scalars and the handle's overhead from make_params, the boxes from the descriptor as layout() forms them (shared with
+// the level rule of sdpgpu_xr_simulate, sdpgpu_xrsim.hip)
 DevParams rule_params(const sdpgpu_handle* h, int t, int64_t nx) {
   const sdpgpu_desc& d = h->d;
   DevParams P = make_params(h, t + 1);
@@ -29,7 +34,7 @@ DevParams rule_params(const sdpgpu_handle* h, int t, int64_t nx) {
   return P;
 }
 
-}  // namespace
+}  // namespace sdpgpu_detail
 
 extern "C" {
 

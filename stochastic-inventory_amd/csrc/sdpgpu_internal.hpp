@@ -13,6 +13,7 @@
 //   sdpgpu_simsample.hip  demand paths drawn on the device for a handle's policy simulation (sampler, fused rollout, reduction)
 //   sdpgpu_staffsim.hip   STAFF family: a hiring rule rolled out on a sampled tree
 //   sdpgpu_cashrulesim.hip  CASH family: (s, C, S) ordering rules rolled out along sampled demand paths, the state kept as doubles
+//   sdpgpu_xrsim.hip      CASH family, cash_formula 2: the policy table and Chao's a* levels rolled out on the (x, R) state; a* itself
 //   sdpgpu_sim_host.hpp   host helpers of those units: exception barrier, device scope, stream record, sampler specs, scratch
 //   sdpgpu_comm.hip     multi-GPU: RCCL communicators (loaded on first use), per-period all-gather, sharded sweeps
 #pragma once

@@ -158,6 +158,10 @@ hipError_t launch_sim_moments(hipStream_t st, const double* d_sum, uint32_t n, d
 int check_stream_args(sdpgpu_handle* h, const char* who, int32_t n_paths, int32_t mode, uint64_t first_path);
 void build_samplers(const sdpgpu_handle* h, std::vector<sdp::SimSampler>* rec, std::vector<double>* thr, std::vector<double>* val);
 
+// sdpgpu_cashrulesim.hip, shared with the (x, R) rollout (sdpgpu_xrsim.hip): the parameter block of period index t WITHOUT a
+// layout, for rollouts that carry the state as doubles and read no table (nx = the descriptor's inventory points)
+sdp::DevParams rule_params(const sdpgpu_handle* h, int t, int64_t nx);
+
 // offsets of the scratch block, every part aligned to 16 bytes
 struct Carve {
   size_t at = 0;

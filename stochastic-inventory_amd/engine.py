@@ -448,6 +448,52 @@ class SdpEngine:
             float(fix_order_cost), float(vari_cost), res, None if sums is None else _dp(sums)))
         return (list(res), sums) if want_sums else list(res)
 
+    def xr_simulate(self, n_paths: int = None, seed: int = 0, ini_x: float = 0.0, ini_r: float = 0.0, levels=None, *, vari_cost: float = None,
+                    demand=None, mode="lhs", first_path: int = 0, discount=None, want_sums: bool = False, want_demands: bool = False):
+        """CASH family with cash_formula 2: roll the policy table (levels=None; needs a solve) or Chao's a* levels -- shape
+        (T,) or (R, T), no solve needed -- out on the (x, R) state along demand paths (sdpgpu_xr_simulate; DESIGN 4, "(x, R)
+        rollout").  The demands are drawn on the device (mode "lhs" / "random", seed, first_path as simulate_sampled) or GIVEN
+        as demand[n, T].  vari_cost: the reference's variOrderCost (default: the descriptor's unit cost).  Returns the list of
+        SdpgpuSimResult, one per rule; with want_sums also sums[R, n]; with want_demands also the demands[n, T] every rule saw."""
+        lv, n_rules = None, 1
+        if levels is not None:
+            lv = np.ascontiguousarray(levels, dtype=np.float64)
+            if lv.ndim == 1:
+                lv = lv[None]
+            if lv.ndim != 2 or lv.shape[1] != self.T:
+                raise ValueError(f"levels must have shape ({self.T},) or (rules, {self.T})")
+            n_rules = lv.shape[0]
+        given = None
+        if demand is not None:
+            given = np.ascontiguousarray(demand, dtype=np.float64)
+            if given.ndim != 2 or given.shape[1] != self.T:
+                raise ValueError(f"demand must have shape (paths, {self.T})")
+            if n_paths is not None and int(n_paths) != given.shape[0]:
+                raise ValueError(f"n_paths = {n_paths}, demand has {given.shape[0]} paths")
+            n_paths = given.shape[0]
+        elif n_paths is None:
+            raise ValueError("n_paths is needed where no demand is given")
+        disc = None
+        if discount is not None:
+            disc = np.ascontiguousarray(discount, dtype=np.float64)
+            if disc.shape != (self.T,):
+                raise ValueError("discount must have one entry per period")
+        n = min(max(int(n_paths), 0), 1 << 24)  # (the library refuses a bad count; the buffers below only need a size)
+        res = (_abi.SdpgpuSimResult * max(n_rules, 1))()
+        sums = np.empty((min(max(n_rules, 1), 16), n), dtype=np.float64) if want_sums else None
+        dem = np.empty((n, self.T), dtype=np.float64) if want_demands else None
+        self._check(self._lib.sdpgpu_xr_simulate(
+            self._h, int(n_paths), C.c_uint64(int(seed) & (2**64 - 1)), self._sample_mode(mode), C.c_uint64(int(first_path) & (2**64 - 1)),
+            None if given is None else _dp(given), None if disc is None else _dp(disc), float(ini_x), float(ini_r), n_rules,
+            None if lv is None else _dp(lv), float(self.desc.unit_order_cost if vari_cost is None else vari_cost), res,
+            None if sums is None else _dp(sums), None if dem is None else _dp(dem)))
+        out = [list(res)]
+        if want_sums:
+            out.append(sums)
+        if want_demands:
+            out.append(dem)
+        return out[0] if len(out) == 1 else tuple(out)
+
     def stats(self) -> SdpgpuStats:
         st = SdpgpuStats()
         self._check(self._lib.sdpgpu_stats_get(self._h, C.byref(st)))

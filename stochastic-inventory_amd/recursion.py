@@ -319,6 +319,41 @@ class CashRecursionXR(CashRecursion):
         return {self.functor.make_state(int(r[0]), r[1], r[3]): float(r[4]) for r in self.getOptTable()}
 
 
+class RecursionG:
+    """sdp.cash.RecursionG(pmf, distributions, price, variCost, depositeRate, salvageValue) (RecursionG.java:47-72): Chao's
+    a* of every period by the two mutually recursive functions G and getAStar (:96-153), on the host (sdpgpu_xr_opt_levels;
+    no device and no engine).  `distributions` is kept for the signature only: the constructor's aNStar, an SSJ quantile of
+    the last one, is overwritten by getOptY's loop (:83-86) before anything reads it.  maxY is the reference's hard-coded 200
+    (:136)."""
+
+    def __init__(self, pmf, distributions, price: float, variCost: float, depositeRate: float, salvageValue: float):
+        self.pmf = [np.asarray(t, dtype=np.float64) for t in pmf]
+        self.distributions = distributions
+        self.price, self.variCost = float(price), float(variCost)
+        self.depositeRate, self.salvageValue = float(depositeRate), float(salvageValue)
+
+    def getOptY(self, maxY: int = 200) -> np.ndarray:
+        import ctypes as C
+
+        from . import _abi
+        lib = _abi.load()
+        T = len(self.pmf)
+        off = np.zeros(T + 1, dtype=np.int64)
+        for t, tile in enumerate(self.pmf):
+            if tile.ndim != 2 or tile.shape[1] != 2:
+                raise ValueError(f"pmf[{t}] of shape {tile.shape}: rows of [demand, probability]")
+            off[t + 1] = off[t] + len(tile)
+        dem = np.ascontiguousarray(np.concatenate([t[:, 0] for t in self.pmf])) if T else np.zeros(0)
+        prob = np.ascontiguousarray(np.concatenate([t[:, 1] for t in self.pmf])) if T else np.zeros(0)
+        out = np.zeros(max(T, 1), dtype=np.float64)
+        dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+        rc = lib.sdpgpu_xr_opt_levels(T, off.ctypes.data_as(C.POINTER(C.c_int64)), dp(dem), dp(prob), self.price, self.variCost,
+                                      self.depositeRate, self.salvageValue, int(maxY), dp(out))
+        if rc:
+            raise _abi.SdpgpuError(rc, lib.sdpgpu_last_error(None).decode())
+        return out[:T]
+
+
 class RiskRecursion(CashRecursion):
     """sdp.cash.RiskRecursion (RiskRecursion.java:31-46): the survival-probability recursion, MAX only, no
     discount; `getSurvProb` (:65-108) takes the place of getExpectedValue.  Rows of getOptTable are

@@ -361,6 +361,132 @@ class CashSimulation(Simulation):
         return float(self.simulateRules(iniState, [(_abi.RULE_SMEANCS, optsCS)], minCashRequired, maxQ, fixOrderCost, variCost)[0])
 
 
+class CashSimulationXR(Simulation):
+    """sdp.cash.CashSimulationXR(distributions, sampleNum, recursionXR, discountFactor, fixOrderCost, price, variOrderCost,
+    holdCost, salvageValue) (CashSimulationXR.java:48-62): the validation steps of cash.singleItem.CashConstraintXR.main on the
+    (x, R) state -- simulateSDPGivenSamplNum (:91-113), simulateSDPwithErrorConfidence (:115-147) and simulateAStar (:153-173),
+    the rollout of Chao's a* levels (RecursionG.getOptY).  sampler="device" (the default here): demand paths are drawn, rolled
+    and the means reduced on the device in one call (SdpEngine.xr_simulate; DESIGN 4, "(x, R) rollout"); the a* rollout needs
+    no solve.  sampler="host": the reference's loops through the recursion's Python lambdas on host-sampled demands.  Of the
+    five cost arguments only variOrderCost is read (:162), as in the reference."""
+
+    def __init__(self, distributions: Sequence, sampleNum: int, recursionXR, discountFactor: float = 1.0, fixOrderCost: float = 0.0,
+                 price: float = 0.0, variOrderCost: float = 1.0, holdCost: float = 0.0, salvageValue: float = 0.0, seed: int = 12345,
+                 sampler: str = "device"):
+        super().__init__(distributions, sampleNum, recursionXR, discountFactor, seed, sampler)
+        self.fixOrderCost, self.price, self.variOrderCost = float(fixOrderCost), float(price), float(variOrderCost)
+        self.holdCost, self.salvageValue = float(holdCost), float(salvageValue)
+        self.last_results = None
+        self.last_demands = None
+
+    @staticmethod
+    def _levels(optY) -> np.ndarray:
+        lv = np.asarray(optY, dtype=np.float64)
+        if lv.ndim not in (1, 2):
+            raise ValueError(f"optY of shape {lv.shape}: (T,) for one rule, (R, T) for several")
+        return lv
+
+    def simulateOnDemands(self, iniState, demands, optY=None) -> np.ndarray:
+        """The reference's loops through the recursion's lambdas (sampler="host" and the cross-check of the device rollout)
+        along demands[n, T]: optY None -- the policy table (getAction, :101-105), path sums [n]; optY of shape (T,) -- the a*
+        rule (:161-165), [n]; of shape (R, T) -- [R, n]."""
+        disc = self._discount()
+        if optY is None:
+            out = np.empty(len(demands))
+            for i, path in enumerate(demands):
+                total, state = 0.0, iniState
+                for t, d in enumerate(path):
+                    self.recursion.getExpectedValue(state)
+                    optQ = self.recursion.getAction(state)
+                    total += disc[t] * self.immediateValue(state, optQ, float(d))
+                    state = self.stateTransition(state, optQ, float(d))
+                out[i] = total
+            return out
+        lv = self._levels(optY)
+        rows = lv[None] if lv.ndim == 1 else lv
+        out = np.empty((len(rows), len(demands)))
+        c = self.variOrderCost
+        for r, row in enumerate(rows.tolist()):
+            for i, path in enumerate(demands):
+                total, state = 0.0, iniState
+                for t, d in enumerate(path):
+                    thisY = row[t] if state.getIniR() > c * row[t] else state.getIniR() / c  # :162
+                    total += disc[t] * self.immediateValue(state, thisY, float(d))
+                    state = self.stateTransition(state, thisY, float(d))
+                out[r, i] = total
+        return out[0] if lv.ndim == 1 else out
+
+    def _xr_call(self, iniState, n: int, mode: str, first_path: int = 0, levels=None):
+        rec = self.recursion
+        if levels is None:
+            rec.getExpectedValue(iniState)  # solves on first use, as :101 does
+        res, sums, dem = rec.engine.xr_simulate(n, self.seed, iniState.getIniInventory(), iniState.getIniR(), levels,
+                                                vari_cost=self.variOrderCost, mode=mode, first_path=first_path,
+                                                discount=self._discount(), want_sums=True, want_demands=True)
+        self.last_results, self.last_result, self.last_demands = res, res[0], dem
+        if res[0].n_valid != res[0].n_paths:
+            raise RuntimeError(f"{res[0].n_paths - res[0].n_valid} sample paths left the state grid after period 1 (a start whose inventory "
+                               "is no grid value); the reference would re-enter the recursion there")
+        return res, sums
+
+    @staticmethod
+    def _host_demands(samples) -> np.ndarray:
+        """`Math.round(Math.max(0, samples[i][t]))` (:103, :130, :163)."""
+        return round_demands(np.maximum(0.0, samples))
+
+    def simulateSDPGivenSamplNum(self, iniState) -> float:
+        """:91-113: mean of the table policy's totals over sampleNum LHS paths, + iniR."""
+        if self.sampler == "device":
+            res, sums = self._xr_call(iniState, self.sampleNum, "lhs")
+            self.last_values = sums[0]
+            return res[0].mean + iniState.getIniR()
+        samples = self.sampling.generateLHSamples(self.distributions, self.sampleNum)
+        sums = self.simulateOnDemands(iniState, self._host_demands(samples))
+        self.last_values = sums
+        return math.fsum(sums.tolist()) / len(sums) + iniState.getIniR()
+
+    def simulateSDPwithErrorConfidence(self, iniState, error: float, confidence: float, batch: int = 1000, maxRuns: int = 1000000):
+        """:115-147: plain-random paths until the normal confidence radius is below error * mean (at least 1000 runs);
+        returns [centre + iniR, radius]."""
+        from scipy import stats as _st
+        z = float(_st.norm.ppf(0.5 + confidence / 2.0))
+        center, radius = 0.0, math.inf
+        if self.sampler == "device":
+            n, mean, m2 = 0, 0.0, 0.0
+            chunks = []
+            while n < 1000 or (radius >= center * error and n < maxRuns):
+                res, sums = self._xr_call(iniState, batch, "random", first_path=n)
+                n, mean, m2 = merge_moments(n, mean, m2, res[0].n_paths, res[0].mean, res[0].m2)
+                chunks.append(sums[0])
+                center = mean
+                radius = z * math.sqrt(m2 / (n - 1)) / math.sqrt(n) if n > 1 else math.inf
+            self.last_values = np.concatenate(chunks)
+            return [center + iniState.getIniR(), radius]
+        vals = np.empty(0)
+        while len(vals) < 1000 or (radius >= center * error and len(vals) < maxRuns):
+            samples = self.sampling.generateRanSamples(self.distributions, batch)
+            vals = np.concatenate([vals, self.simulateOnDemands(iniState, self._host_demands(samples))])
+            center = float(vals.mean())
+            radius = z * float(vals.std(ddof=1)) / math.sqrt(len(vals))
+        self.last_values = vals
+        return [center + iniState.getIniR(), radius]
+
+    def simulateAStar(self, optY, iniState):
+        """:153-173: the a* rule y = R > variOrderCost * a_t ? a_t : R / variOrderCost over sampleNum LHS paths, + iniR.  optY
+        of shape (T,): a float; of shape (R, T): R rules on the SAME demand paths in one call, an array."""
+        lv = self._levels(optY)
+        if self.sampler == "device":
+            res, sums = self._xr_call(iniState, self.sampleNum, "lhs", levels=lv)
+            self.last_values = sums[0] if lv.ndim == 1 else sums
+            out = np.array([r.mean + iniState.getIniR() for r in res])
+        else:
+            samples = self.sampling.generateLHSamples(self.distributions, self.sampleNum)
+            sums = self.simulateOnDemands(iniState, self._host_demands(samples), lv)
+            self.last_values = sums
+            out = np.array([math.fsum(s.tolist()) / len(s) + iniState.getIniR() for s in np.atleast_2d(sums)])
+        return float(out[0]) if lv.ndim == 1 else out
+
+
 class RiskSimulation:
     """sdp.cash.RiskSimulation(distributions, sampleNum, recursion): `simulateLostSale` (RiskSimulation.java:206-241),
     the validation run of the survival-probability recursion -- roll the policy along LHS demand paths, count the
