@@ -42,7 +42,10 @@
  *                            simulators (Simulation.java:62-63).
  *   sdpgpu_simulate          the rollout loops of the simulators (Simulation.java:59-69,
  *                            CashSimulation.java:101-112): policy look-up + imm + transition.
- *   sdpgpu_reachable         the key set of `cacheActions`, i.e. the states the
+ *   sdpgpu_custom_simulate / the same loops, and the overdraft drivers' rule rollouts (CashSimulation.java:1142-1250:
+ *   _simulate_sampled /      simulatesCSDraft, simulatesSOD, simulatesSOD2), for a handle of USER lambdas
+ *   sdpgpu_custom_rule_simulate  (sdpgpu_create_custom), through the lambdas' own compiled text.
+ *   sdpgpu_reachable        the key set of `cacheActions`, i.e. the states the
  *                            memoised recursion would have visited; getOptTable
  *                            (Recursion.java:177-186) lists exactly those.
  *
@@ -323,7 +326,8 @@ void sdpgpu_destroy(sdpgpu_handle* h);
  * CASH_LEADTIME = (x, cash, preQ), SURVIVAL = (x, cash) under getSurvProb.  The grid fields of the descriptor
  * (step, inventory bounds and clamp flag, cash bounds and rounding, max_order_quantity = longest pipeline
  * quantity, ini_*) keep their meaning; the cost fields are ignored.  sdpgpu_simulate is not available (the
- * lambdas also exist on the host, where the reference's simulators call them).
+ * lambdas also exist on the host, where the reference's simulators call them); the device rollouts of such a handle are
+ * entry points of their own: sdpgpu_custom_simulate, sdpgpu_custom_simulate_sampled, sdpgpu_custom_rule_simulate (below).
  *
  * How the text is compiled: -O3, no contraction, no fast-math.  On a CLAMPED grid with finite constants the grid, the step and
  * params[] are baked into the generated source as exact literals (SDPGPU_CUSTOM_BAKE=0: read at run time, as before ABI 6), and
@@ -1107,6 +1111,63 @@ int sdpgpu_xr_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t
  * first visit; no device code.  SDPGPU_ERR_ARG: T < 1, max_y < 1, a NULL array, an empty tile, a value that is not finite. */
 int sdpgpu_xr_opt_levels(int32_t T, const int64_t* tile_off, const double* tile_demand, const double* tile_prob, double price,
                          double vari_cost, double deposit_rate, double salvage, int32_t max_y, double* out_levels);
+
+/* ---- User-functor handles (sdpgpu_create_custom): rollouts of the policy tables and of the overdraft drivers' rules ------
+ * What the validation half of the overdraft drivers does after a solve, on the device: simulateSDPGivenSamplNum and the
+ * sampling loop of simulateSDPwithErrorConfidence (CashOverdraftLimit.main:122-125), CashSimulation.simulatesSOD
+ * (CashSimulation.java:1180-1211; CashOverdraftTesting.main:142-149, CashOverdraft.main:154-163), simulatesCSDraft (:1142-1173;
+ * CashOverdraftLimitTesting.main:158) and simulatesSOD2 (:1218-1250).  Definition: DESIGN 4, "User-functor rollouts".  Additive
+ * to ABI 6.  sdpgpu_simulate, sdpgpu_simulate_sampled, sdpgpu_sample_demands, sdpgpu_cash_rule_simulate and sdpgpu_xr_simulate
+ * keep refusing a user-functor handle: these are its entry points.
+ *
+ * The rollout program -- two kernels around the handle's own text, the prelude and the helpers of the solve's program -- is
+ * compiled by hipRTC at the handle's FIRST rollout call, kept on the handle and released by sdpgpu_destroy.  Options: those of
+ * the solve's compile (shape, SDP_NP, the baked grid and constants) WITHOUT -fno-honor-nans.  The compile follows the argument
+ * checks and precedes the solve-state and device checks: a text around which the program does not compile is SDPGPU_ERR_ARG on
+ * a box without a GPU too.  SDPGPU_CUSTOM_DUMP=path writes the rollout object to path + ".sim".
+ *
+ * sdpgpu_custom_simulate / sdpgpu_custom_simulate_sampled: arguments, start state, off-grid start (its action is the
+ * one sdpgpu_eval_states gives wherever that call answers; a start with a successor that is no grid point, which sdpgpu_eval_states
+ * refuses, values that successor at 0 as the built-in families' rollouts do, and its path ends there), flags (bit 0: the path stayed on the grid), discount == NULL (sampled call only), NaN mean / m2 when
+ * n_valid < n_paths and kernel_ms mean what they mean for sdpgpu_simulate / sdpgpu_simulate_sampled.  Per period: state =
+ * decode(idx), action = policy[idx] * step, sum += discount[t] * immediate (one sdp_cell call under SDP_USER_CELL, else
+ * sdp_immediate and, except in period T, sdp_transition), idx = index of the successor.  A successor that is no grid point of the
+ * next period ends the path with its valid bit clear -- not an error.  The draws are exactly sdpgpu_simulate_sampled's (tiles or
+ * sdpgpu_set_sampler specs, instance position 0, LHS or RANDOM); out_demand (optional, [p * T + t]) returns them.  n_paths * T
+ * above 2^27 is SDPGPU_ERR_UNSUPPORTED (the demand buffer is resident).
+ *
+ * sdpgpu_custom_rule_simulate: handles of the (x, cash) state shape (descriptor family CASH or OVERDRAFT); needs NO solve.
+ *   rule r   rule[(r * T + t) * 4 + {0, 1, 2, 3}] = (s, C, S, S2) of period index t; form[r] one of the three below.
+ *            m = min(max(0, (cash - min_cash_required - fix_order_cost) / vari_cost), max_q).
+ *            SS      t = 0: q = S (the row's S itself);    t >= 1: q = x < s ? min(m, S - x) : 0
+ *            SCS     t = 0: q = S - s;                     t >= 1: q = (x < s && cash > C) ? min(m, S - x) : 0   (strict)
+ *            SCS1S2  t = 0: q = S - ini_x;                 t >= 1: q = x < s ? (cash <= C + 0.1 ? S - x : S2 - x) : 0; reads no scalar
+ *   step     sum += discount[t] * sdp_immediate(ctx{t + 1}, x, cash, 0, q, d); (x, cash) = sdp_transition(...), not in period T.
+ *            The state is the two doubles the user's transition returns: nothing is tested against a grid, n_valid = n_paths, a
+ *            negative q is not refused.  One fp64 operation per statement; min / max are the prelude's sdp_min / sdp_max.
+ *   draws    as above; up to 16 rules see the same demands (the counters do not carry the rule).  A call with R rules returns
+ *            what R one-rule calls return, bit for bit; RANDOM calls (0, a) then (a, b) give the sums of one call (0, a + b).
+ * results[r]: n_paths, n_valid, n_lost = 0, mean and m2 in the fixed order of sdpgpu_simulate_sampled, kernel_ms of the whole
+ * call; out_sum: NULL or [r * n_paths + p]; out_demand: NULL or [p * T + t].  iniState.iniCash is added by the caller.
+ *
+ * Refusals, all before the first device call and naming the argument: not a user-functor handle, state shape SURVIVAL, the rule
+ * call on a shape without a cash axis or with a pipeline quantity, n_paths above 2^24, n_paths * T above 2^27
+ * SDPGPU_ERR_UNSUPPORTED; world_size != 1, a period without tile or spec (drawn demands), the table calls before a solve
+ * SDPGPU_ERR_STATE; a NULL array that is required, n_paths < 1 (sdpgpu_custom_simulate: < 0), a bad mode, LHS with first_path != 0,
+ * n_rules outside 1 .. 16, a form outside 0 .. 2, a rule entry, start value or discount that is not finite, and -- where a form
+ * reads them -- a scalar that is not finite, vari_cost <= 0, max_q < 0 SDPGPU_ERR_ARG. */
+#define SDPGPU_ORULE_SS 0     /* simulatesSOD: (s, S) */
+#define SDPGPU_ORULE_SCS 1    /* simulatesCSDraft: (s, C, S) */
+#define SDPGPU_ORULE_SCS1S2 2 /* simulatesSOD2: (s, C, S1, S2) */
+int sdpgpu_custom_simulate(sdpgpu_handle* h, int64_t n_paths, const double* demand, const double* discount, double ini_x,
+                           double ini_cash, double ini_preq, double* out_sum, uint8_t* out_valid);
+int sdpgpu_custom_simulate_sampled(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t mode, uint64_t first_path,
+                                   const double* discount, double ini_x, double ini_cash, double ini_preq,
+                                   sdpgpu_sim_result* result, double* out_sum, uint8_t* out_valid, double* out_demand);
+int sdpgpu_custom_rule_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t mode, uint64_t first_path,
+                                const double* discount, double ini_x, double ini_cash, int32_t n_rules, const int32_t* form,
+                                const double* rule, double min_cash_required, double max_q, double fix_order_cost,
+                                double vari_cost, sdpgpu_sim_result* results, double* out_sum, double* out_demand);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

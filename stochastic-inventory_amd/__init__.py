@@ -9,7 +9,7 @@ from ._abi import (FAMILY_BACKORDER, FAMILY_CASH, FAMILY_CASH_LEADTIME, FAMILY_L
                    FAMILY_STAFF, FAMILY_SURVIVAL, KERNEL_AUTO, KERNEL_GATHER, KERNEL_WINDOW, SdpgpuBatchPlan, SdpgpuBatchStats, SdpgpuConvexity, SdpgpuDesc, SdpgpuError, SdpgpuStats, desc_defaults)
 from .batch import SdpBatch
 from .engine import SdpEngine
-from .fitss import FitsS
+from .fitss import FindsSOverDraft, FitsS
 from .functors import (BackorderFunctor, CashFunctor, CashXRFunctor, CashLeadtimeFunctor, CustomFunctor, LeadtimeFunctor, OverdraftFunctor,
                        SurvivalFunctor, java_round)
 from .multiitem import (Actions, CashRecursionMulti, CashRecursionMultiLead, CashRecursionMultiXR, CashStateMulti,
@@ -30,6 +30,6 @@ __all__ = [
     "multilead_solve", "multicash_solve", "multixr_solve", "MultiLeadResult", "Actions", "CashRecursionMulti",
     "CashRecursionMultiLead", "CashRecursionMultiXR", "CashStateMulti", "CashStateMultiLead", "CashStateMultiXR",
     "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "SimulationBatch", "RiskSimulation", "CashSimulation", "CashSimulationXR", "RecursionG", "Sampling",
-    "FitsS", "SimulateFitsS", "CheckKConvexity", "SdpgpuConvexity",
+    "FitsS", "FindsSOverDraft", "SimulateFitsS", "CheckKConvexity", "SdpgpuConvexity",
     "State", "LeadtimeState", "CashState", "CashStateXR", "CashLeadtimeState", "RiskState", "OptDirection", "java_round",
 ]

@@ -249,6 +249,7 @@ class SdpgpuDistSpec(C.Structure):
 DIST_POISSON, DIST_NORMAL, DIST_UNIFORM_INT, DIST_GAMMA = 1, 2, 3, 4
 SAMPLE_LHS, SAMPLE_RANDOM = 0, 1
 RULE_SC12S, RULE_SC1S, RULE_SMEANCS = 0, 1, 2  # SDPGPU_RULE_*: the forms of sdpgpu_cash_rule_simulate
+ORULE_SS, ORULE_SCS, ORULE_SCS1S2 = 0, 1, 2  # SDPGPU_ORULE_*: the forms of sdpgpu_custom_rule_simulate
 
 
 class SdpgpuSimResult(C.Structure):
@@ -371,6 +372,11 @@ EXPORTS = {
                                             _DP]),
     "sdpgpu_xr_simulate": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, _DP, C.c_double, C.c_double, C.c_int32, _DP,
                                      C.c_double, C.POINTER(SdpgpuSimResult), _DP, _DP]),
+    "sdpgpu_custom_simulate": (C.c_int, [_P, C.c_int64, _DP, _DP, C.c_double, C.c_double, C.c_double, _DP, C.POINTER(C.c_uint8)]),
+    "sdpgpu_custom_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_double,
+                                                 C.POINTER(SdpgpuSimResult), _DP, C.POINTER(C.c_uint8), _DP]),
+    "sdpgpu_custom_rule_simulate": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_int32, _IP,
+                                              _DP, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(SdpgpuSimResult), _DP, _DP]),
     "sdpgpu_xr_opt_levels": (C.c_int, [C.c_int32, _LP, _DP, _DP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _DP]),
 }
 

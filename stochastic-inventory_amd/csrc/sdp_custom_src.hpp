@@ -7,12 +7,14 @@
 // sdpgpu_create_custom) and this engine source is compiled around them: same loop, same accumulation
 // order, same strict-compare arg-opt as sdp_gather.hpp.
 //
-// Three pieces of text: kCustomPrelude (what the user's functions may use), the user's source, kCustomEngine.
+// The solve's program: kCustomPrelude (what the user's functions may use), the user's source, kCustomCommon, kCustomEngine.
+// The rollout program (sdpgpu_custom_simulate*, sdpgpu_custom_rule_simulate; sdpgpu_customsim.hip), compiled at a handle's first
+// rollout call: the same prelude, user text and kCustomCommon, then kCustomSim.
 #pragma once
 
 namespace sdp {
 
-// NOTE: struct CustomParams below (host) and `struct CParams` in kCustomEngine (device) must stay identical;
+// NOTE: struct CustomParams below (host) and `struct CParams` in kCustomCommon (device) must stay identical;
 // both sides static_assert the size.
 struct CustomGrid {
   double x_lo;
@@ -26,7 +28,7 @@ struct CustomParams {
   CustomGrid cur, next;
   const double* user;
 };
-static_assert(sizeof(CustomParams) == 168, "CustomParams layout is mirrored in kCustomEngine");
+static_assert(sizeof(CustomParams) == 168, "CustomParams layout is mirrored in kCustomCommon");
 
 static const char* const kCustomPrelude = R"SDPSRC(
 typedef long long sdp_i64;
@@ -50,7 +52,9 @@ __device__ inline double sdp_ldiv(double a, int b) { return (double)((int)a / b)
 #line 1 "user_functor"
 )SDPSRC";
 
-static const char* const kCustomEngine = R"SDPSRC(
+// what the solve's program (kCustomEngine) and the rollout program (kCustomSim) share: the parameter block, the SDP_* / C_* macros,
+// the level-shape lambdas, c_decode and c_next_index.  Both programs are prelude + user text + kCustomCommon + their own text.
+static const char* const kCustomCommon = R"SDPSRC(
 #line 1 "sdp_custom_engine"
 #ifndef SDP_NP
 #define SDP_NP 1  // number of user parameters (-DSDP_NP=n at compile time)
@@ -169,7 +173,9 @@ __device__ inline sdp_i64 c_next_index(const CParams& P, double nx, double ncash
   return ((sdp_i64)iq * C_NEXT_NX + ix) * C_NEXT_NC + ic;
 }
 
-__device__ inline bool c_better(bool maxdir, double v2, int k2, double v, int k) {
+)SDPSRC";
+
+static const char* const kCustomEngine = R"SDPSRC(__device__ inline bool c_better(bool maxdir, double v2, int k2, double v, int k) {
   return maxdir ? (v2 > v || (v2 == v && k2 < k)) : (v2 < v || (v2 == v && k2 < k));
 }
 
@@ -374,6 +380,218 @@ extern "C" __global__ __launch_bounds__(256) void sdp_custom_reach(
     }
   }
   if (bad) atomicOr(err, 1);
+}
+)SDPSRC";
+
+// NOTE: CustomSimPeriod / CustomRuleLaunch (host) and CSimPeriod / CRuleLaunch in kCustomSim (device) must stay identical; both
+// sides static_assert the size.
+struct CustomSimPeriod {
+  CustomParams P;
+  long long pol_off;  // element offset of the period's policy row (indexed by flat state index)
+  double disc;
+};
+static_assert(sizeof(CustomSimPeriod) == 184, "CustomSimPeriod layout is mirrored in kCustomSim");
+struct CustomRuleLaunch {
+  double ini_x, ini_cash, step;
+  double min_cash_required, max_q, fix_order_cost, vari_cost;  // the reference's arguments
+  int T, n_rules;
+  unsigned n_paths, pad;
+};
+static_assert(sizeof(CustomRuleLaunch) == 72, "CustomRuleLaunch layout is mirrored in kCustomSim");
+
+// Rollouts through the user's functions ("User-functor rollouts"; tests/custom_rule_twin.py is written from it):
+//   * sdp_custom_sim: one path per lane over the handle's policy tables -- the statements of sim_period_step (sdp_gather.hpp)
+//     with the user's functions in place of cell<FAM>: state from c_decode, action = pol[idx] * step, sum += disc[t] * imm,
+//     successor index from c_next_index.  A successor that is no grid point ends the path with its valid bit clear; the index
+//     read is the clamped one, and nothing is read after a path has ended;
+//   * sdp_custom_first: the action of an off-grid start, one lane (see there);
+//   * sdp_custom_rule_sim: one (rule, path) per lane, the rule index is blockIdx.y -- a workgroup's paths belong to ONE rule, so
+//     its form and its row of the period are wave-uniform loads.  The state is the two doubles (x, cash) the user's transition
+//     returns: nothing is tested against a grid.
+// The demands are read from a buffer the library's own sampler has filled (or the caller's); both kernels write their sums
+// with ordinary vector stores from plain C++ -- no LDS, no atomics: the wave partials of the fixed-order reduction are formed
+// by a precompiled pass over the sums (sdpgpu_customsim.hip).
+static const char* const kCustomSim = R"SDPSRC(
+#line 1 "sdp_custom_sim"
+struct CSimPeriod {
+  CParams P;
+  sdp_i64 pol_off;
+  double disc;
+};
+static_assert(sizeof(CSimPeriod) == 184, "CSimPeriod layout is mirrored in sdp_custom_src.hpp");
+struct CRuleLaunch {
+  double ini_x, ini_cash, step;
+  double min_cash_required, max_q, fix_order_cost, vari_cost;
+  int T, n_rules;
+  unsigned n_paths, pad;
+};
+static_assert(sizeof(CRuleLaunch) == 72, "CRuleLaunch layout is mirrored in sdp_custom_src.hpp");
+
+extern "C" __global__ __launch_bounds__(256) void sdp_custom_sim(
+    const CSimPeriod* __restrict__ per, int T, const int* __restrict__ pol, const double* __restrict__ user,
+    const double* __restrict__ demand, sdp_i64 n, sdp_i64 idx0, double ini_x, double ini_cash, double ini_preq, int first_k,
+    double* __restrict__ out_sum, unsigned char* __restrict__ out_valid) {
+  const sdp_i64 i = (sdp_i64)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+#ifdef SDP_BAKE
+  const double prm[SDP_NP] = SDP_B_PARAMS;
+#else
+  double prm[SDP_NP];
+#pragma unroll
+  for (int k = 0; k < SDP_NP; ++k) prm[k] = user[k];
+#endif
+  sdp_ctx U;
+  U.T = T;
+  U.params = prm;
+  double sum = 0.0;
+  sdp_i64 idx = idx0;
+  bool valid = true;
+  for (int t = 0; t < T && valid; ++t) {
+    const CParams& P = per[t].P;
+    U.period = t + 1;
+    U.step = C_STEP;
+    CState s;
+    int k;
+    if (t == 0 && idx0 < 0) {  // an off-grid start: its action comes from sdpgpu_eval_states
+      s.x = ini_x;
+      s.cash = ini_cash;
+      s.preq = ini_preq;
+      k = first_k;
+    } else {
+      c_decode(P, idx, s);
+      k = pol[per[t].pol_off + idx];
+    }
+    const double a = (double)k * C_STEP;
+    const double d = demand[i * T + t];
+    const bool last = t + 1 == T;
+#ifdef SDP_USER_CELL
+    double imm, nx, nc, nq;
+    sdp_cell(U, s.x, s.cash, s.preq, a, d, imm, nx, nc, nq);
+#else
+    const double imm = sdp_immediate(U, s.x, s.cash, s.preq, a, d);
+    double nx = 0, nc = 0, nq = 0;
+    if (!last) sdp_transition(U, s.x, s.cash, s.preq, a, d, nx, nc, nq);
+#endif
+    sum += per[t].disc * imm;
+    if (!last) {
+      bool bad = false;
+      idx = c_next_index(P, nx, nc, nq, bad);
+      if (bad) valid = false;
+    }
+  }
+  out_sum[i] = sum;
+  out_valid[i] = valid ? 1 : 0;
+}
+
+// The action of an OFF-GRID period-1 state (recursion.getAction after getExpectedValue, Simulation.java:62-63): the loop of
+// custom_period_body over every feasible action and the period's pmf, serially in the reference's order, by ONE lane; the arg-opt
+// is the strict compare in action order.  A successor that is no grid point of period 2 is valued at 0 -- what the built-in
+// families' rollouts and the oracle do with it; sdpgpu_eval_states refuses such a state, and gives this action wherever it
+// answers.  (A start off the grid is a single state: T x |actions| x |pmf| cells once per call.)
+extern "C" __global__ __launch_bounds__(64) void sdp_custom_first(
+    CParams P, const double* __restrict__ user, const double* __restrict__ v_next, const double* __restrict__ pmf_d,
+    const double* __restrict__ pmf_p, double x, double cash, double preq, int* __restrict__ out_k) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+#ifdef SDP_BAKE
+  const double prm[SDP_NP] = SDP_B_PARAMS;
+#else
+  double prm[SDP_NP];
+#pragma unroll
+  for (int k = 0; k < SDP_NP; ++k) prm[k] = user[k];
+#endif
+  sdp_ctx U;
+  U.period = P.period;
+  U.T = P.T;
+  U.step = C_STEP;
+  U.params = prm;
+  const int nA = sdp_feasible_count(U, x, cash, preq);
+  double best = SDP_MAXDIR ? -1.7976931348623157e308 : 1.7976931348623157e308;
+  int bestk = 0;
+  for (int k = 0; k < nA; ++k) {
+    const double a = (double)k * C_STEP;
+    double acc = 0.0;
+    for (int j = 0; j < P.n_demand; ++j) {
+      const double d = pmf_d[j], pr = pmf_p[j];
+#ifdef SDP_USER_CELL
+      double imm, nx, nc, nq;
+      sdp_cell(U, x, cash, preq, a, d, imm, nx, nc, nq);
+#else
+      const double imm = sdp_immediate(U, x, cash, preq, a, d);
+      double nx = 0, nc = 0, nq = 0;
+      if (!P.is_last) sdp_transition(U, x, cash, preq, a, d, nx, nc, nq);
+#endif
+      acc += pr * imm;
+      if (!P.is_last) {
+        bool bad = false;
+        const sdp_i64 ni = c_next_index(P, nx, nc, nq, bad);  // (clamped: a safe address either way)
+        const double vn = v_next[ni];
+        acc += (pr * P.gamma) * (bad ? 0.0 : vn);
+      }
+    }
+    if (SDP_MAXDIR ? (acc > best) : (acc < best)) {
+      best = acc;
+      bestk = k;
+    }
+  }
+  out_k[0] = bestk;
+}
+
+// the order of rule row (s, C, S, S2) in period index t at (x, cash): the overdraft drivers' three rollouts
+// (CashSimulation.java:1180-1211 simulatesSOD, :1142-1173 simulatesCSDraft, :1218-1250 simulatesSOD2)
+__device__ inline double c_rule_order(const CRuleLaunch& L, int form, int t, const double* __restrict__ row, double x, double cash) {
+  const double s = row[0], C = row[1], S = row[2], S2 = row[3];
+  if (form == 2) {
+    if (t == 0) return S - L.ini_x;
+    if (!(x < s)) return 0.0;
+    const double c01 = C + 0.1;
+    return cash <= c01 ? S - x : S2 - x;
+  }
+  if (t == 0) return form == 0 ? S : S - s;
+  double m = cash - L.min_cash_required;
+  m = m - L.fix_order_cost;
+  m = m / L.vari_cost;
+  m = sdp_max(0.0, m);
+  m = sdp_min(m, L.max_q);
+  const bool orders = form == 0 ? x < s : (x < s && cash > C);
+  if (!orders) return 0.0;
+  const double up = S - x;
+  return sdp_min(m, up);
+}
+
+extern "C" __global__ __launch_bounds__(256) void sdp_custom_rule_sim(
+    CRuleLaunch L, const double* __restrict__ user, const double* __restrict__ disc, const double* __restrict__ demand,
+    const int* __restrict__ form, const double* __restrict__ rule, double* __restrict__ out_sum) {
+  const int ri = blockIdx.y;  // (workgroup-uniform)
+  const unsigned p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= L.n_paths) return;
+#ifdef SDP_BAKE
+  const double prm[SDP_NP] = SDP_B_PARAMS;
+#else
+  double prm[SDP_NP];
+#pragma unroll
+  for (int k = 0; k < SDP_NP; ++k) prm[k] = user[k];
+#endif
+  sdp_ctx U;
+  U.T = L.T;
+  U.step = L.step;
+  U.params = prm;
+  const int fm = form[ri];
+  double x = L.ini_x, cash = L.ini_cash;
+  double sum = 0.0;
+  for (int t = 0; t < L.T; ++t) {
+    U.period = t + 1;
+    const double d = demand[(sdp_i64)p * L.T + t];
+    const double q = c_rule_order(L, fm, t, rule + ((sdp_i64)ri * L.T + t) * 4, x, cash);
+    const double imm = sdp_immediate(U, x, cash, 0.0, q, d);
+    sum += disc[t] * imm;
+    if (t + 1 < L.T) {
+      double nx = 0, nc = 0, nq = 0;
+      sdp_transition(U, x, cash, 0.0, q, d, nx, nc, nq);
+      x = nx;
+      cash = nc;
+    }
+  }
+  out_sum[(sdp_i64)ri * L.n_paths + p] = sum;
 }
 )SDPSRC";
 

@@ -694,7 +694,7 @@ int sdpgpu_create_custom(const sdpgpu_desc* desc, const char* functor_source, co
   if (desc->kernel != SDPGPU_KERNEL_AUTO && desc->kernel != SDPGPU_KERNEL_GATHER && !(level_shape && desc->kernel == SDPGPU_KERNEL_WINDOW))
     return fail(nullptr, SDPGPU_ERR_UNSUPPORTED, "a user functor runs on the generic kernel only (or, with SDP_SHAPE_LEVEL, on the window kernel)");
   // compile: prelude + the user's three device functions + the engine kernels, strict fp64 (no FMA)
-  std::string src = std::string(sdp::kCustomPrelude) + functor_source + "\n" + sdp::kCustomEngine;
+  std::string src = std::string(sdp::kCustomPrelude) + functor_source + "\n" + sdp::kCustomCommon + sdp::kCustomEngine;
   hiprtcProgram prog = nullptr;
   if (hiprtcCreateProgram(&prog, src.c_str(), "sdp_custom.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
     return fail(nullptr, SDPGPU_ERR_DEVICE, "hiprtcCreateProgram failed");
@@ -783,6 +783,11 @@ int sdpgpu_create_custom(const sdpgpu_desc* desc, const char* functor_source, co
   h->level_shape = level_shape;
   h->custom_code.swap(code);
   h->custom_params.assign(params, params + n_params);
+  // what the rollout program is compiled from at the handle's first rollout call (sdpgpu_customsim.hip): the same text and
+  // options, but NaNs honoured -- a rule rollout hands the lambdas off-grid doubles
+  h->custom_source = functor_source;
+  for (const char* o : opts)
+    if (std::strcmp(o, "-fno-honor-nans") != 0) h->custom_sim_opts.push_back(o);
   return SDPGPU_OK;
 }
 
@@ -832,6 +837,7 @@ void sdpgpu_destroy(sdpgpu_handle* h) {
   if (h->sim_ev0) (void)hipEventDestroy(h->sim_ev0);
   if (h->sim_ev1) (void)hipEventDestroy(h->sim_ev1);
   if (h->custom_mod) (void)hipModuleUnload(h->custom_mod);
+  if (h->custom_sim_mod) (void)hipModuleUnload(h->custom_sim_mod);
   comm_release(h);
   if (h->stream && h->own_stream) (void)hipStreamDestroy(h->stream);
   delete h;

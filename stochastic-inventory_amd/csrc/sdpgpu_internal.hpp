@@ -226,6 +226,14 @@ struct sdpgpu_handle {
   double* d_level_tabs = nullptr;             // per period: [m_tab (n_m)] [c_tab (n_a)]
   std::vector<size_t> level_tab_off;          // element offset of period t's m_tab
   std::vector<int32_t> level_m_min, level_m_n;
+  // the rollout program of a user functor (sdpgpu_customsim.hip; sdp_custom_src.hpp: kCustomSim): the user's text and the
+  // options of the engine compile WITHOUT -fno-honor-nans are kept from create; compiled at the first rollout call, loaded at
+  // the first one that reaches the device, released by sdpgpu_destroy
+  std::string custom_source;
+  std::vector<std::string> custom_sim_opts;
+  std::vector<char> custom_sim_code;
+  hipModule_t custom_sim_mod = nullptr;
+  hipFunction_t custom_sim = nullptr, custom_first = nullptr, custom_rule_sim = nullptr;
   double* d_custom_params = nullptr;
   unsigned long long* d_custom_cells = nullptr;  // [T]
   int* d_custom_err = nullptr;

@@ -153,6 +153,11 @@ int sim_scratch(Owner* o, size_t bytes) {
 // n device-resident sums and their W = ceil(n / 64) wave partials: d_res[0] = mean, d_res[1] = m2, both NaN when d_cnt[0] < n
 hipError_t launch_sim_moments(hipStream_t st, const double* d_sum, uint32_t n, double* d_part, const unsigned int* d_cnt, double* d_res);
 
+// sdpgpu_simsample.hip, shared with the user-functor rollouts (sdpgpu_customsim.hip): the draws of sdpgpu_sample_demands into a
+// device buffer, d_dem[p * T + t] (d_u: the uniforms, or null)
+hipError_t launch_sim_draw(hipStream_t st, int32_t mode, const sdp::SimStream& R, int T, const sdp::SimSampler* d_samp, const double* d_thr,
+                           const double* d_val, double* d_dem, double* d_u);
+
 // sdpgpu_simsample.hip, shared with the cash rule rollout (sdpgpu_cashrulesim.hip): the refusals of a call's stream arguments
 // (n_paths, mode, first_path, a period without a tile or spec), and the handle's sampler records with their two arenas
 int check_stream_args(sdpgpu_handle* h, const char* who, int32_t n_paths, int32_t mode, uint64_t first_path);

@@ -84,6 +84,17 @@ void build_samplers(const sdpgpu_handle* h, std::vector<sdp::SimSampler>* rec, s
   }
 }
 
+// the demands of a stream into a device buffer, out[p * T + t] (and the uniforms where d_u is given): sim_sampled_draw_kernel
+hipError_t launch_sim_draw(hipStream_t st, int32_t mode, const sdp::SimStream& R, int T, const sdp::SimSampler* d_samp, const double* d_thr,
+                           const double* d_val, double* d_dem, double* d_u) {
+  const dim3 grid((unsigned)((R.n_paths + 255u) / 256u));
+  if (mode == SDPGPU_SAMPLE_RANDOM)
+    hipLaunchKernelGGL((sdp::sim_sampled_draw_kernel<true>), grid, dim3(256), 0, st, R, T, d_samp, d_thr, d_val, d_dem, d_u);
+  else
+    hipLaunchKernelGGL((sdp::sim_sampled_draw_kernel<false>), grid, dim3(256), 0, st, R, T, d_samp, d_thr, d_val, d_dem, d_u);
+  return hipGetLastError();
+}
+
 // mean = (wave partials in the fixed order) / n; m2 = a second pass over the sums in the same order (which reuses the partials)
 hipError_t launch_sim_moments(hipStream_t st, const double* d_sum, uint32_t n, double* d_part, const unsigned int* d_cnt, double* d_res) {
   const uint32_t W = (n + 63u) / 64u;
@@ -154,17 +165,12 @@ int sdpgpu_sample_demands(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int3
     if (!thr.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice, h->stream));
     if (!val.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_val, val.data(), val.size() * 8, hipMemcpyHostToDevice, h->stream));
     const sdp::SimStream R = make_stream(n_paths, seed, first_path);
-    const dim3 grid((unsigned)((n_paths + 255) / 256));
     const sdp::SimSampler* d_samp = reinterpret_cast<const sdp::SimSampler*>(base + o_samp);
     const double* d_thr = reinterpret_cast<const double*>(base + o_thr);
     const double* d_val = reinterpret_cast<const double*>(base + o_val);
     double* d_dem = reinterpret_cast<double*>(base + o_dem);
     double* d_u = out_u ? reinterpret_cast<double*>(base + o_u) : nullptr;
-    if (mode == SDPGPU_SAMPLE_RANDOM)
-      hipLaunchKernelGGL((sdp::sim_sampled_draw_kernel<true>), grid, dim3(256), 0, h->stream, R, T, d_samp, d_thr, d_val, d_dem, d_u);
-    else
-      hipLaunchKernelGGL((sdp::sim_sampled_draw_kernel<false>), grid, dim3(256), 0, h->stream, R, T, d_samp, d_thr, d_val, d_dem, d_u);
-    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, launch_sim_draw(h->stream, mode, R, T, d_samp, d_thr, d_val, d_dem, d_u));
     HIP_TRY(h, hipMemcpyAsync(out_demand, d_dem, elems * 8, hipMemcpyDeviceToHost, h->stream));
     if (out_u) HIP_TRY(h, hipMemcpyAsync(out_u, d_u, elems * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));

@@ -494,6 +494,87 @@ class SdpEngine:
             out.append(dem)
         return out[0] if len(out) == 1 else tuple(out)
 
+    # -- user-functor handles: rollouts of their own ("User-functor rollouts") --------------------------------------
+    def _disc_or_none(self, discount):
+        if discount is None:
+            return None
+        disc = np.ascontiguousarray(discount, dtype=np.float64)
+        if disc.shape != (self.T,):
+            raise ValueError("discount must have one entry per period")
+        return disc
+
+    def custom_simulate(self, demand, discount, ini_x: float, ini_cash: float = 0.0, ini_preq: float = 0.0):
+        """simulate() for a handle made with custom_source: roll the policy tables through the user's compiled lambdas along
+        demand[n][T] with weights discount[T] -> (sums[n], valid[n]) (sdpgpu_custom_simulate)."""
+        dem = np.ascontiguousarray(demand, dtype=np.float64)
+        if dem.ndim != 2 or dem.shape[1] != self.T:
+            raise ValueError(f"demand must be [n_paths][{self.T}]")
+        disc = self._disc_or_none(discount)
+        n = dem.shape[0]
+        out = np.empty(n, dtype=np.float64)
+        valid = np.empty(n, dtype=np.uint8)
+        self._check(self._lib.sdpgpu_custom_simulate(self._h, n, _dp(dem), None if disc is None else _dp(disc), float(ini_x), float(ini_cash),
+                                                     float(ini_preq), _dp(out), valid.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self.last_sim_flags = valid
+        return out, (valid & 1).astype(bool)
+
+    def custom_simulate_sampled(self, n_paths: int, seed: int, ini_x: float, ini_cash: float = 0.0, ini_preq: float = 0.0, *, mode="lhs",
+                                first_path: int = 0, discount=None, want_sums: bool = False, want_demands: bool = False):
+        """simulate_sampled() for a handle made with custom_source (sdpgpu_custom_simulate_sampled): the draws of simulate_sampled,
+        the rollout through the user's compiled lambdas, the reduction on the device.  Returns the SdpgpuSimResult; with want_sums
+        also (sums[n], flags[n]); with want_demands also the demands[n, T] drawn (sample_demands refuses these handles)."""
+        disc = self._disc_or_none(discount)
+        n = min(max(int(n_paths), 0), 1 << 24)  # (the library refuses a bad count; the buffers below only need a size)
+        res = _abi.SdpgpuSimResult()
+        sums = np.empty(n, dtype=np.float64) if want_sums else None
+        flags = np.empty(n, dtype=np.uint8) if want_sums else None
+        dem = np.empty((n, self.T), dtype=np.float64) if want_demands else None
+        self._check(self._lib.sdpgpu_custom_simulate_sampled(
+            self._h, int(n_paths), C.c_uint64(int(seed) & (2**64 - 1)), self._sample_mode(mode), C.c_uint64(int(first_path) & (2**64 - 1)),
+            None if disc is None else _dp(disc), float(ini_x), float(ini_cash), float(ini_preq), C.byref(res),
+            None if sums is None else _dp(sums), None if flags is None else flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+            None if dem is None else _dp(dem)))
+        out = [res]
+        if want_sums:
+            self.last_sim_flags = flags
+            out += [sums, flags]
+        if want_demands:
+            out.append(dem)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def custom_rule_simulate(self, n_paths: int, seed: int, ini_x: float, ini_cash: float, forms, rules, *, min_cash_required: float = 0.0,
+                             max_q: float = 0.0, fix_order_cost: float = 0.0, vari_cost: float = 1.0, mode="lhs", first_path: int = 0,
+                             discount=None, want_sums: bool = False, want_demands: bool = False):
+        """A handle made with custom_source on the (x, cash) state shape: roll the overdraft drivers' ordering rules out through
+        the user's compiled lambdas along demand paths drawn on the device (sdpgpu_custom_rule_simulate).  forms: one of
+        _abi.ORULE_SS / ORULE_SCS / ORULE_SCS1S2 per rule; rules: (s, C, S, S2) rows of shape (T, 4) or (R, T, 4).  Needs no solve.
+        Returns the list of SdpgpuSimResult, one per rule; with want_sums also sums[R, n]; with want_demands the demands[n, T]."""
+        rows = np.ascontiguousarray(rules, dtype=np.float64)
+        if rows.ndim == 2:
+            rows = rows[None]
+        if rows.ndim != 3 or rows.shape[1:] != (self.T, 4):
+            raise ValueError(f"rules must have shape ({self.T}, 4) or (rules, {self.T}, 4)")
+        n_rules = rows.shape[0]
+        fm = np.ascontiguousarray(np.atleast_1d(forms), dtype=np.int32)
+        if fm.shape != (n_rules,):
+            raise ValueError(f"forms must have one entry per rule ({n_rules})")
+        disc = self._disc_or_none(discount)
+        n = min(max(int(n_paths), 0), 1 << 24)  # (the library refuses a bad count; the buffers below only need a size)
+        res = (_abi.SdpgpuSimResult * max(n_rules, 1))()
+        sums = np.empty((min(max(n_rules, 1), 16), n), dtype=np.float64) if want_sums else None
+        dem = np.empty((n, self.T), dtype=np.float64) if want_demands else None
+        self._check(self._lib.sdpgpu_custom_rule_simulate(
+            self._h, int(n_paths), C.c_uint64(int(seed) & (2**64 - 1)), self._sample_mode(mode), C.c_uint64(int(first_path) & (2**64 - 1)),
+            None if disc is None else _dp(disc), float(ini_x), float(ini_cash), n_rules, _ip(fm), _dp(rows), float(min_cash_required),
+            float(max_q), float(fix_order_cost), float(vari_cost), res, None if sums is None else _dp(sums),
+            None if dem is None else _dp(dem)))
+        out = [list(res)]
+        if want_sums:
+            out.append(sums)
+        if want_demands:
+            out.append(dem)
+        return out[0] if len(out) == 1 else tuple(out)
+
     def stats(self) -> SdpgpuStats:
         st = SdpgpuStats()
         self._check(self._lib.sdpgpu_stats_get(self._h, C.byref(st)))

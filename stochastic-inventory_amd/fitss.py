@@ -82,3 +82,70 @@ class FitsS:
     def getThreesS(self, optimalTable) -> np.ndarray:
         """FitsS.java:213-291: [T, 6] = (s1, S1, s2, S2, s3, S3) per period."""
         return self._fit(3, optimalTable)
+
+
+class FindsSOverDraft:
+    """cash.overdraft.FindsSOverDraft(T, iniCash) (FindsSOverDraft.java:20-103): the (s, S) and (s, C, S) rules the overdraft
+    drivers read off CashRecursion.getOptTable() -- rows [period, x, cash, Q], sorted as the reference's TreeMap sorts its keys --
+    before they roll them out (CashSimulation.simulatesSOD / simulatesCSDraft).  Host only, a few passes over the table.  The
+    reference's loops verbatim, including the read of row j + 1 where the LAST row of a period orders (an
+    ArrayIndexOutOfBoundsException there, an IndexError here) and the `cash + Q` on the left of getsCS's comparison (:86).
+    getsCS1S2 is not mirrored: its rule arrives as an array (CashSimulation.simulatesSOD2)."""
+
+    def __init__(self, T: int, iniCash: float):
+        self.T = int(T)
+        self.iniCash = float(iniCash)
+
+    @staticmethod
+    def _table(optimalTable) -> np.ndarray:
+        rows = np.asarray(optimalTable, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] < 4 or len(rows) == 0:
+            raise ValueError(f"optimalTable of shape {rows.shape}: rows [period, x, cash, Q]")
+        return rows
+
+    def getsS(self, optimalTable) -> np.ndarray:
+        """:35-55: s = the inventory of the row AFTER the last ordering row of the period, S = that row's x + Q."""
+        tab = self._table(optimalTable)
+        out = np.zeros((self.T, 2))
+        out[0, 0] = tab[0, 1]
+        out[0, 1] = tab[0, 1] + tab[0, 3]
+        for t in range(1, self.T):
+            rows = tab[tab[:, 0] == t + 1]
+            for j in range(len(rows) - 1, -1, -1):
+                if rows[j, 3] != 0:
+                    if j + 1 >= len(rows):
+                        raise IndexError(f"getsS: the last row of period {t + 1} orders; tOptTable[j + 1] does not exist")
+                    out[t, 0] = rows[j + 1, 1]
+                    out[t, 1] = rows[j, 1] + rows[j, 3]
+                    break
+        return out
+
+    def getsCS(self, optimalTable) -> np.ndarray:
+        """:62-103: s as getsS; S = x + Q of the ordering rows that pass `cash + Q > S so far`; C = the largest cash of a
+        non-ordering row below an ordering one (from -500)."""
+        tab = self._table(optimalTable)
+        out = np.zeros((self.T, 3))
+        minCashUsed = -500.0
+        out[0, 0] = tab[0, 1]
+        out[0, 1] = tab[0, 2]
+        out[0, 2] = tab[0, 1] + tab[0, 3]
+        for t in range(1, self.T):
+            rows = tab[tab[:, 0] == t + 1]
+            recordsTime = 0
+            out[t, 2] = 0.0
+            out[t, 1] = minCashUsed
+            mark_s = 0
+            for j in range(len(rows) - 1, -1, -1):
+                if rows[j, 3] != 0:
+                    if mark_s == 0:
+                        if j + 1 >= len(rows):
+                            raise IndexError(f"getsCS: the last row of period {t + 1} orders; tOptTable[j + 1] does not exist")
+                        out[t, 0] = rows[j + 1, 1]
+                        mark_s = 1
+                    if rows[j, 2] + rows[j, 3] > out[t, 2]:
+                        out[t, 2] = rows[j, 1] + rows[j, 3]
+                    recordsTime = 1
+                if rows[j, 3] == 0 and recordsTime == 1:
+                    if rows[j, 2] > out[t, 1]:
+                        out[t, 1] = rows[j, 2]
+        return out

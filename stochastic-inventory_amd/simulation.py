@@ -78,6 +78,12 @@ def _hand_samplers(recursion, distributions):
         recursion.engine.set_sampler(t, None if distributions is None else distributions[t])
 
 
+def _is_custom(recursion) -> bool:
+    """The recursion's functor is a CustomFunctor: its handle takes the user-functor rollouts."""
+    from .functors import CustomFunctor
+    return isinstance(recursion.functor, CustomFunctor)
+
+
 def merge_moments(na: int, mean_a: float, m2_a: float, nb: int, mean_b: float, m2_b: float):
     """(n, mean, M2) of the union of two samples from theirs (Chan, Golub, LeVeque: "Updating formulae and a pairwise algorithm
     for computing sample variances", 1979): M2 = sum of squared deviations from the mean."""
@@ -123,7 +129,9 @@ class Simulation:
         T = rec.T
         disc = np.array([math.pow(self.discountFactor, t) for t in range(T)], dtype=np.float64)
         x, cash, preq = rec.functor.tuple_of(iniState)
-        sums, valid = rec.engine.simulate(demands, disc, x, cash, preq)
+        # (a recursion over user lambdas rolls through their compiled text: SdpEngine.custom_simulate)
+        roll = rec.engine.custom_simulate if _is_custom(rec) else rec.engine.simulate
+        sums, valid = roll(demands, disc, x, cash, preq)
         if not valid.all():
             raise RuntimeError(f"{int((~valid).sum())} sample paths left the state grid (demand outside the PMF support "
                                "of an unclamped family); the reference would re-enter the recursion there")
@@ -137,8 +145,8 @@ class Simulation:
         rec = self.recursion
         rec.getExpectedValue(iniState)  # solves on first use, as Simulation.java:62 does
         x, cash, preq = rec.functor.tuple_of(iniState)
-        res, sums, _ = rec.engine.simulate_sampled(n, self.seed, x, cash, preq, mode=mode, first_path=first_path,
-                                                   discount=self._discount(), want_sums=True)
+        roll = rec.engine.custom_simulate_sampled if _is_custom(rec) else rec.engine.simulate_sampled
+        res, sums, _ = roll(n, self.seed, x, cash, preq, mode=mode, first_path=first_path, discount=self._discount(), want_sums=True)
         if res.n_valid != res.n_paths:
             raise RuntimeError(f"{res.n_paths - res.n_valid} sample paths left the state grid (demand outside the PMF support "
                                "of an unclamped family); the reference would re-enter the recursion there")
@@ -273,13 +281,50 @@ def cash_rule_order(form: int, t: int, row, c1_row, c2_row, x: float, cash: floa
     return min(m, S - x) if orders else 0.0
 
 
+def overdraft_rule_rows(form: int, opts, T: int) -> np.ndarray:
+    """The reference's arrays as the (T, 4) rows (s, C, S, S2) of sdpgpu_custom_rule_simulate: optsS [T, 2] = (s, S) of
+    simulatesSOD, optsCS [T, 3] = (s, C, S) of simulatesCSDraft, optsCS [T, 4] = (s, C, S1, S2) of simulatesSOD2.  Four columns
+    are taken as they are."""
+    rows = np.asarray(opts, dtype=np.float64)
+    want = {_abi.ORULE_SS: 2, _abi.ORULE_SCS: 3, _abi.ORULE_SCS1S2: 4}.get(form)
+    if want is None:
+        raise ValueError(f"form {form}: ORULE_SS 0, ORULE_SCS 1, ORULE_SCS1S2 2")
+    if rows.ndim != 2 or rows.shape[0] != T or rows.shape[1] not in (want, 4):
+        raise ValueError(f"rule of shape {rows.shape} for form {form}: [{T}, {want}] (or the four columns s, C, S, S2)")
+    z = np.zeros(T)
+    if rows.shape[1] == 2:
+        rows = np.stack([rows[:, 0], z, rows[:, 1], z], axis=1)
+    elif rows.shape[1] == 3:
+        rows = np.stack([rows[:, 0], rows[:, 1], rows[:, 2], z], axis=1)
+    return np.ascontiguousarray(rows)
+
+
+def overdraft_rule_order(form: int, t: int, row, x: float, cash: float, iniX: float, minCashRequired: float, maxQ: float, fixOrderCost: float,
+                         variCost: float) -> float:
+    """optQ of one period (CashSimulation.java:1152-1165, :1191-1202, :1228-1240); row = (s, C, S, S2)."""
+    s, c, S, S2 = (float(v) for v in row)
+    if form == _abi.ORULE_SCS1S2:
+        if t == 0:
+            return S - iniX
+        if not x < s:
+            return 0.0
+        return S - x if cash <= c + 0.1 else S2 - x
+    if t == 0:
+        return S if form == _abi.ORULE_SS else S - s
+    m = min(max(0.0, (cash - minCashRequired - fixOrderCost) / variCost), maxQ)
+    orders = x < s and (form == _abi.ORULE_SS or cash > c)
+    return min(m, S - x) if orders else 0.0
+
+
 class CashSimulation(Simulation):
     """sdp.cash.CashSimulation(distributions, sampleNum, recursion, discountFactor): the SDP simulation of Simulation plus the
     rollouts of an (s, C, S) ordering rule -- simulatesCS in its two forms and simulatesMeanCS (CashSimulation.java:996-1134),
     the twelve extra columns of CashConstraintTesting.main.  sampler="device" (the default here): demand paths are drawn, every
     rule rolled and the means reduced on the device in one call (SdpEngine.cash_rule_simulate; DESIGN 4, "Cash rule rollout"); a
     rule needs no solve.  sampler="host": the same rules through the recursion's Python lambdas on host-sampled demands.
-    The rule is an argument (FindsCS is not mirrored)."""
+    The rule is an argument (FindsCS is not mirrored).  Over a CustomFunctor recursion (user lambdas) the overdraft drivers' rules
+    -- simulatesSOD, simulatesCSDraft, simulatesSOD2, several at once: simulateOverdraftRules -- run through the compiled text
+    (SdpEngine.custom_rule_simulate; DESIGN 4, "User-functor rollouts"); fitss.FindsSOverDraft reads them off the table."""
 
     def __init__(self, distributions: Sequence, sampleNum: int, recursion, discountFactor: float = 1.0, seed: int = 12345,
                  sampler: str = "device"):
@@ -359,6 +404,57 @@ class CashSimulation(Simulation):
     def simulatesMeanCS(self, iniState, optsCS, minCashRequired, maxQ, fixOrderCost, variCost) -> float:
         """CashSimulation.java:1101-1134: the (s, C, S) rule with one C per period."""
         return float(self.simulateRules(iniState, [(_abi.RULE_SMEANCS, optsCS)], minCashRequired, maxQ, fixOrderCost, variCost)[0])
+
+    # ---- the overdraft drivers' rules over a CustomFunctor recursion (DESIGN 4, "User-functor rollouts") ----------------------
+    def simulateOverdraftRulesOnDemands(self, iniState, rules, demands, minCashRequired=0.0, maxQ=0.0, fixOrderCost=0.0,
+                                        variCost=1.0) -> np.ndarray:
+        """The reference's loops (CashSimulation.java:1142-1250) through the recursion's Python lambdas: path sums [R, n] of the
+        rules along demands[n, T] (sampler="host" and the cross-check of the device rollout)."""
+        T, disc = self.recursion.T, self._discount()
+        x0 = iniState.getIniInventory()
+        out = np.empty((len(rules), len(demands)))
+        for r, (form, opts) in enumerate(rules):
+            rows = overdraft_rule_rows(int(form), opts, T)
+            for i, path in enumerate(demands):
+                total, state = 0.0, iniState
+                for t, d in enumerate(path):
+                    q = overdraft_rule_order(int(form), t, rows[t], state.getIniInventory(), state.getIniCash(), x0, minCashRequired, maxQ,
+                                             fixOrderCost, variCost)
+                    total += disc[t] * self.immediateValue(state, q, float(d))
+                    if t + 1 < T:
+                        state = self.stateTransition(state, q, float(d))
+                out[r, i] = total
+        return out
+
+    def simulateOverdraftRules(self, iniState, rules, minCashRequired=0.0, maxQ=0.0, fixOrderCost=0.0, variCost=1.0) -> np.ndarray:
+        """Several overdraft rules along the SAME demand paths in one call: rules = [(form, opts), ...], form one of
+        _abi.ORULE_SS (opts [T, 2] = (s, S)), ORULE_SCS ([T, 3] = (s, C, S)), ORULE_SCS1S2 ([T, 4] = (s, C, S1, S2)).  Returns
+        mean + iniCash per rule; last_values holds the path sums [R, n], last_results the device's results."""
+        T = self.recursion.T
+        if self.sampler == "device":
+            forms = np.array([int(f) for f, _ in rules], dtype=np.int32)
+            rows = np.stack([overdraft_rule_rows(int(f), o, T) for f, o in rules])
+            res, sums = self.recursion.engine.custom_rule_simulate(
+                self.sampleNum, self.seed, iniState.getIniInventory(), iniState.getIniCash(), forms, rows, min_cash_required=minCashRequired,
+                max_q=maxQ, fix_order_cost=fixOrderCost, vari_cost=variCost, mode="lhs", discount=self._discount(), want_sums=True)
+            self.last_results, self.last_values = res, sums
+            return np.array([r.mean + iniState.getIniCash() for r in res])
+        samples = self.sampling.generateLHSamples(self.distributions, self.sampleNum)
+        sums = self.simulateOverdraftRulesOnDemands(iniState, rules, round_demands(samples), minCashRequired, maxQ, fixOrderCost, variCost)
+        self.last_results, self.last_values = None, sums
+        return np.array([math.fsum(s.tolist()) / len(s) + iniState.getIniCash() for s in sums])
+
+    def simulatesSOD(self, iniState, optsS, minCashRequired, maxQ, fixOrderCost, variCost) -> float:
+        """CashSimulation.java:1180-1211: the (s, S) rule under overdraft."""
+        return float(self.simulateOverdraftRules(iniState, [(_abi.ORULE_SS, optsS)], minCashRequired, maxQ, fixOrderCost, variCost)[0])
+
+    def simulatesCSDraft(self, iniState, optsCS, minCashRequired, maxQ, fixOrderCost, variCost) -> float:
+        """CashSimulation.java:1142-1173: the (s, C, S) rule under an overdraft limit."""
+        return float(self.simulateOverdraftRules(iniState, [(_abi.ORULE_SCS, optsCS)], minCashRequired, maxQ, fixOrderCost, variCost)[0])
+
+    def simulatesSOD2(self, iniState, optsCS) -> float:
+        """CashSimulation.java:1218-1250: the (s, C, S1, S2) rule; it reads no scalar."""
+        return float(self.simulateOverdraftRules(iniState, [(_abi.ORULE_SCS1S2, optsCS)])[0])
 
 
 class CashSimulationXR(Simulation):
