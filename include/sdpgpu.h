@@ -578,7 +578,8 @@ typedef struct sdpgpu_plan {
   int32_t chunk_blocks;      /* register blocks of the action axis per task; 0: the action-major level kernel, whose
                                 tasks are level bands x blocks of 64 r actions */
   int32_t tiles, tasks;      /* state tiles of 64 s states of this slab; tiles x chunks (level kernel: bands; tasks) */
-  int32_t workgroups_per_cu; /* workgroups (four tasks each) the LDS lets a compute unit hold at once */
+  int32_t workgroups_per_cu; /* workgroups (four tasks each) the LDS lets a compute unit hold at once (level kernel: at
+                                most the two its registers allow, which its bands are planned against) */
   int64_t lds_bytes;         /* dynamic LDS per workgroup */
 } sdpgpu_plan;
 int sdpgpu_plan_period(const sdpgpu_handle* h, int32_t period, sdpgpu_plan* out);
@@ -706,6 +707,22 @@ int sdpgpu_f1_screen_get(sdpgpu_handle* h, int32_t period, int64_t out[6]);
  * level kernel's levels per block) whose leading steps, on the unit-stride layout of the demands, carry at most 2^-16 of the
  * probability (SDPGPU_F1_SCREEN_LOG2=<e> at create time, a diagnostic: 2^-e); 0 below 8.  Whether a launch uses it is decided at the launch.  -1: bad arguments or no layout. */
 int32_t sdpgpu_f1_screen_start(sdpgpu_handle* h, int32_t period);
+
+/* Additive to ABI 6: the decided split of the F1 level kernel.  Under the cut-off's gate -- MIN, the built-in
+ * costs, K, v, h, pi >= 0, every probability >= 0, values of the library's own -- holding for period t and every later
+ * period, action 0 provably wins in every state from an index c_t on, and V_t is non-decreasing there.
+ * sdpgpu_f1_decided_start is host arithmetic, no device: c_t for this rank's slab of period t, from the descriptor, the grids
+ * and the demand supports alone (c_t = max(0, m0_t + D_t - 1, c_{t+1} - idx_off_t + D_t - 1): m0_t the first level index that is
+ * >= 0, D_t the steps of the period's unit-stride demand layout, idx_off_t the index shift into the next period's grid); the
+ * slab's end says "none" (the gate is closed for this or a later period, or no state qualifies); -1: bad arguments or no layout.
+ * Where the level kernel runs with the cut-off and lo < c_t < hi, the launcher walks only the live states [lo, c_t) and settles
+ * [c_t, hi) with one one-action launch -- only with SDPGPU_F1_DECIDED=1 (opt-in, read at create time: the default sweep stays
+ * the whole-slab one).
+ * sdpgpu_f1_decided_get, host side as well: out[0] = c_t as above; for period t of the last solve out[1] = the live states its
+ * level launch covered, out[2] = the decided states, out[3] = 1 where the split ran (else out[1] is the slab and out[2] is 0);
+ * out[4] = bytes of the chunk-row arenas (0 before the first chunked launch). */
+int64_t sdpgpu_f1_decided_start(sdpgpu_handle* h, int32_t period);
+int sdpgpu_f1_decided_get(sdpgpu_handle* h, int32_t period, int64_t out[5]);
 
 /* ---- batched solve: many backorder-family instances, of ONE grid shape or each with its own ----------------------------
  * The reference's parameter sweeps -- capacitated.CLSPTesting.main (CLSPTesting.java:33-141: 10 demand patterns x 2 v x

@@ -321,6 +321,8 @@ EXPORTS = {
     "sdpgpu_period_cells": (C.c_int64, [_P, C.c_int32]),
     "sdpgpu_f1_screen_get": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "sdpgpu_f1_screen_start": (C.c_int32, [_P, C.c_int32]),
+    "sdpgpu_f1_decided_start": (C.c_int64, [_P, C.c_int32]),
+    "sdpgpu_f1_decided_get": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "sdpgpu_plan_period": (C.c_int, [_P, C.c_int32, C.POINTER(SdpgpuPlan)]),
     "sdpgpu_multilead_solve": (C.c_int, [C.POINTER(SdpgpuMultilead), _DP, _IP, _IP, _LP, _LP, _DP]),
     "sdpgpu_multilead_last_error": (C.c_char_p, []),

@@ -661,6 +661,7 @@ int sdpgpu_create(const sdpgpu_desc* desc, sdpgpu_handle** out) {
     if (const char* e = std::getenv("SDPGPU_WIN_LEVEL")) h->win_level = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_F1_CUTOFF")) h->f1_cutoff = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_F1_SCREEN")) h->f1_screen = std::atoi(e) != 0;
+    if (const char* e = std::getenv("SDPGPU_F1_DECIDED")) h->f1_decided = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_F1_SCREEN_LOG2")) {
       const int b = std::atoi(e);
       if (b >= 1 && b <= 1000) h->f1_screen_mass = std::ldexp(1.0, -b);
@@ -1174,7 +1175,8 @@ int sdpgpu_plan_period(const sdpgpu_handle* hc, int32_t period, sdpgpu_plan* out
   out->chunk_blocks = pl.chunk_blocks;
   out->tiles = pl.n_tiles;
   out->tasks = pl.n_tasks;
-  out->workgroups_per_cu = lds_workgroups(pl.smem);
+  // (the level kernel's bands are planned against two waves per SIMD, its register budget: small bands do not raise that)
+  out->workgroups_per_cu = pl.level ? std::min(2, lds_workgroups(pl.smem)) : lds_workgroups(pl.smem);
   out->lds_bytes = (int64_t)pl.smem;
   return SDPGPU_OK;
 }
@@ -1586,6 +1588,10 @@ int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out) {
     // (a level period with the cut-off walks `run` of its planned steps, each at ops_cell operations per cell, makes its
     // tests -- one compare per cell -- and pays the pre-pass; without it, or when the counters cannot be read, all of them)
     double walked = 1.0, tests = 0.0;
+    // (a period of the decided split: the level launch walked the cells of its live states alone; the one-action launches
+    // over both parts are in pre_ops)
+    double lvl_cells = (double)p.cells_rank;
+    if (p.lvl_cut && p.dec_c >= 0 && p.hi > p.lo) lvl_cells *= (double)(p.dec_c - p.lo) / (double)(p.hi - p.lo);
     out->f1_level_steps_planned += p.lvl_steps_planned;
     if (p.lvl_cut && cut_read && p.lvl_steps_planned > 0) {
       out->f1_level_steps_run += (int64_t)cut[(size_t)t * kCutCounters];
@@ -1594,8 +1600,8 @@ int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out) {
     } else {
       out->f1_level_steps_run += p.lvl_steps_planned;
     }
-    out->fp64_ops_executed += (double)p.cells_rank * (p.ops_cell * walked + tests) + p.pre_ops;
-    out->lds_bytes += (double)p.cells_rank * p.lds_cell * walked;
+    out->fp64_ops_executed += lvl_cells * (p.ops_cell * walked + tests) + p.pre_ops;
+    out->lds_bytes += lvl_cells * p.lds_cell * walked;
     out->l1_bytes += (double)p.cells_rank * p.l1_cell;
     if (p.ops_cell == 0 && p.cells_rank > 0) modelled = false;
   }
@@ -1666,6 +1672,29 @@ int32_t sdpgpu_f1_screen_start(sdpgpu_handle* h, int32_t period) {
   h->err.clear();
   if (layout(h)) return -1;
   return f1_screen_start(h, period, 8, h->f1_screen_mass);
+}
+
+int64_t sdpgpu_f1_decided_start(sdpgpu_handle* h, int32_t period) {
+  if (!h || period < 1 || period > h->T) return -1;
+  h->err.clear();
+  if (layout(h)) return -1;
+  return f1_decided_start(h, period);
+}
+
+int sdpgpu_f1_decided_get(sdpgpu_handle* h, int32_t period, int64_t out[5]) {
+  if (!h || !out) return SDPGPU_ERR_ARG;
+  h->err.clear();
+  if (period < 1 || period > h->T) return fail(h, SDPGPU_ERR_ARG, "period %d out of 1..%d", period, h->T);
+  int rc = layout(h);
+  if (rc) return rc;
+  const PeriodInfo& p = h->per[period - 1];
+  const bool ran = h->allocated && p.lvl_cut && p.dec_c >= 0;
+  out[0] = f1_decided_start(h, period);
+  out[1] = ran ? p.dec_c - p.lo : p.hi - p.lo;
+  out[2] = ran ? p.hi - p.dec_c : 0;
+  out[3] = ran ? 1 : 0;
+  out[4] = (int64_t)(h->chunk_arena_elems * (sizeof(double) + sizeof(int32_t)));
+  return SDPGPU_OK;
 }
 
 int sdpgpu_f1_screen_get(sdpgpu_handle* h, int32_t period, int64_t out[6]) {

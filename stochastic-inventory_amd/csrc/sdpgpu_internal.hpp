@@ -67,6 +67,10 @@ struct WinPlan {
   // actions; d_pad, n_chunks and smem are then its own
   bool level = false;
   int band = 0, n_ablocks = 0;
+  // THE DECIDED SPLIT (f1_decided_start, sdpgpu_window.hip): >= 0: the level launch covers the live states [lo, dec_c) only
+  // -- band, n_tiles, n_tasks, n_chunks and smem are that launch's -- and the states [dec_c, hi) take action 0 from one
+  // one-action launch of window_f1_kernel<1, 8>; -1: no split
+  int64_t dec_c = -1;
   int tile_states() const { return 64 * S; }
 };
 
@@ -102,6 +106,7 @@ struct WinPlanCache {
   int64_t lo = 0, hi = 0;
   int win_r = 0, win_s = 0, win_nch = 0, win_level = -1;
   bool may_chunk = false;
+  bool values_external = false;
   WinPlan plan;
   std::string why;
 };
@@ -139,6 +144,10 @@ struct PeriodInfo {
   bool lvl_cut = false;
   int32_t lvl_screen_start = 0;  // the step screened level blocks started at in the last launch (0: the screen was off)
   double pre_ops = 0;  // fp64 operations of the cut-off's pre-pass (Q(i, 0) of every state), in total
+  // the decided split of the last launch: its boundary (live states [lo, dec_c), decided [dec_c, hi)) and the live launch's
+  // chunk rows; -1: the launch did not split (sdpgpu_f1_decided_get; flush_pending makes two finalize jobs of a split period)
+  int64_t dec_c = -1;
+  int dec_live_chunks = 0;
   double lds_cell = 0, l1_cell = 0;  // bytes per cell through the LDS / the vector L1 of the kernel that ran the period (0: no model)
   mutable WinPlanCache win_plan;     // (a cache: filled through const handles by plan_window)
 };
@@ -179,10 +188,11 @@ struct sdpgpu_handle {
   double* d_chunk_val = nullptr;         // arena of chunk rows, period t at chunk_off[t-1]
   int32_t* d_chunk_idx = nullptr;
   std::vector<size_t> chunk_off;
+  size_t chunk_arena_elems = 0;          // elements of each of the two arenas (12 bytes per element in all)
   std::vector<int> pending_chunks;       // >0: period's final rows not written yet (value = n_chunks)
   int n_pending = 0;
   sdp::FinalizeJob* d_jobs = nullptr;
-  std::vector<unsigned char> jobs_host;  // upload source of d_jobs: T FinalizeJobs at a fixed address (flush_pending)
+  std::vector<unsigned char> jobs_host;  // upload source of d_jobs: 2 T FinalizeJobs at a fixed address (flush_pending)
   int32_t* d_rowperm = nullptr;  // cash row kernel, F5: rows of the launch ordered by level x + preQ (RowTiling::perm)
   std::vector<int32_t> rowperm_host;
   int64_t rowperm_key[4] = {-1, -1, -1, -1};
@@ -204,6 +214,9 @@ struct sdpgpu_handle {
   // forced plan, 1 = wherever the cut-off is on, 0 = never.  It never goes beyond the cut-off's gate (f1_cutoff_on).
   int f1_screen = -1;
   double f1_screen_mass = kF1ScreenMass;
+  // SDPGPU_F1_DECIDED=1: the decided split wherever the level kernel runs with the cut-off; unset or 0: never (opt-in:
+  // f1_decided_on, sdpgpu_window.hip)
+  int f1_decided = 0;
   // [T][kCutCounters], per period: steps run and tests made by the level kernel's waves, then its level blocks -- screened
   // and stopped, screens that failed, walked exactly (sdpgpu_f1_screen_get)
   unsigned long long* d_cut_count = nullptr;
@@ -439,6 +452,7 @@ WinPlan plan_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, 
 RowPlan plan_row_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, std::string* why = nullptr);
 // the step screened level blocks start at under the mass bound `mass` (S: the level kernel's levels per block; 0: none)
 int f1_screen_start(const sdpgpu_handle* h, int period, int S, double mass);
+int64_t f1_decided_start(const sdpgpu_handle* h, int period);
 hipError_t flush_pending(sdpgpu_handle* h);
 // the two kernels of chunked periods, defined in this unit only (the batched solve launches them too): key rows to the
 // reduction identity of the direction; V_t and policy rows from keys + chunk rows (`total` states over `n_jobs` jobs)

@@ -39,17 +39,23 @@ static WinPlan plan_window_search(const sdpgpu_handle* h, int period, int64_t lo
 //     write alone;
 //   * nothing else: the backorder family's cell has no overhead, discount, salvage or price term (sdp_device.hpp: cell<FAM_BACKORDER>;
 //     PeriodInfo::overhead feeds the cash families only), and the window kernels read WinParams alone.
-static bool f1_terms_nonneg(const sdpgpu_handle* h, int period) {
+// (in two parts: what the descriptor, the period's pmf and the owner of the value arena say -- known before anything runs,
+// and what the decided boundary is planned from -- and what the period below left when it was launched)
+static bool f1_terms_nonneg_static(const sdpgpu_handle* h, int period) {
   if (h->custom || h->level_shape) return false;
   const sdpgpu_desc& d = h->d;
   if (!(d.fixed_order_cost >= 0 && d.unit_order_cost >= 0 && d.holding_cost >= 0 && d.penalty_cost >= 0 && d.step > 0)) return false;
   for (double q : h->pmf_p[(size_t)period - 1])
     if (!(q >= 0)) return false;
-  if (period < h->T && (h->values_external || !h->per[period].v_nonneg)) return false;
-  return true;
+  return !(period < h->T && h->values_external);
+}
+static bool f1_terms_nonneg(const sdpgpu_handle* h, int period) {
+  return f1_terms_nonneg_static(h, period) && !(period < h->T && !h->per[period].v_nonneg);
 }
 
-// The cut-off's pre-pass: window_f1_kernel<4, 8> with ONE action (one R-block, one chunk) over the slab, tiles of 512 states.
+// The cut-off's pre-pass: window_f1_kernel<1, 8> with ONE action (one R-block of one action, one chunk) over the slab, tiles of
+// 512 states.  (It ran as <4, 8> with three padded actions walked for nothing: 13.9 operations per state and step against
+// 4.1 -- f1_cells' cell is the same whatever R is, the same operations on the same operands in the same order.)
 struct CutPrePlan {
   int d_pad = 0;
   size_t smem = 0;
@@ -57,19 +63,22 @@ struct CutPrePlan {
 };
 static CutPrePlan cut_pre_plan(const PeriodInfo& p, int64_t lo, int64_t hi) {
   CutPrePlan c;
-  c.d_pad = (p.nD_win + 10) / 11 * 11;
-  c.smem = sdp::win_wg_lds(512 + 4 + c.d_pad + 8, p.nD_win);
+  c.d_pad = (p.nD_win + 7) / 8 * 8;
+  c.smem = sdp::win_wg_lds(512 + 1 + c.d_pad + 8, p.nD_win);
   c.tiles = (hi - lo + 511) / 512;
   return c;
 }
 // THE gate of the cut-off (sdp_window.hpp), one predicate for the planner and the launcher: SDPGPU_F1_CUTOFF not 0, MIN,
 // every term >= 0, and a pre-pass that fits.  (For a period with a future it reads what the period below left, so it is
 // asked when that period has been launched; period T depends on the descriptor and the pmf alone.)
-static bool f1_cutoff_on(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi) {
-  if (!h->f1_cutoff || h->d.direction != SDPGPU_MIN || hi <= lo || hi - lo >= INT32_MAX) return false;
-  if (!f1_terms_nonneg(h, period)) return false;
+static bool f1_pre_fits(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi) {
+  if (hi <= lo || hi - lo >= INT32_MAX) return false;
   const CutPrePlan c = cut_pre_plan(h->per[period - 1], lo, hi);
   return c.smem <= kLdsPerCU && grid_ok((c.tiles + 3) / 4);
+}
+static bool f1_cutoff_on(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi) {
+  if (!h->f1_cutoff || h->d.direction != SDPGPU_MIN || !f1_pre_fits(h, period, lo, hi)) return false;
+  return f1_terms_nonneg(h, period);
 }
 
 // THE SCREEN's first step (sdp_window.hpp), for a period whose cut-off is on: the largest multiple of S with
@@ -99,6 +108,60 @@ int f1_screen_start(const sdpgpu_handle* h, int period, int S, double mass) {
 // SDPGPU_F1_SCREEN=0 turns it off everywhere.
 static bool f1_screen_on(const sdpgpu_handle* h) { return h->f1_screen < 0 ? h->win_level < 0 : h->f1_screen != 0; }
 
+// THE DECIDED BOUNDARY: the first state index c_t of period t's slab from which action 0 provably wins
+// and V_t is non-decreasing; a value >= hi says "none".  Under the cut-off's gate a cell's addends are p_j (c0[k] + M(m))
+// and p_j V_{t+1}(clamp(m + idx_off)) with m = i + k - j.  For a state i whose lowest level i - (D - 1) is >= 0 in the
+// kernel's own arithmetic and whose lowest successor index is >= c_{t+1}, every addend of cell (i, k) is >= the addend of
+// cell (i, 0) at the same step: M is non-decreasing in m on levels >= 0 (the penalty term is 0, fl(h l) is monotone),
+// c0[0] = 0 and fl(c0[k] + M) >= M, the clamp is monotone and V_{t+1} is non-decreasing from c_{t+1} on, and a product by
+// p_j >= 0 and a round-to-nearest sum are monotone in each operand.  So the fp64 sum of (i, k) is >= that of (i, 0), a tie
+// goes to index 0, and the same comparison of (i + 1, 0) with (i, 0) makes V_t non-decreasing from c_t on.  Host arithmetic
+// on the descriptor, the grids and the window layouts alone: nothing is read from a table.
+//   c_t = max(0, m0_t + D_t - 1, c_{t+1} - idx_off_t + D_t - 1),  m0_t = the lowest m with level(m) >= 0
+// (exact where lev0 and the step are integers; one more otherwise), idx_off_t the launcher's own.  The static part of the
+// cut-off's gate must hold for period t AND every later period: one that fails leaves no decided part at or below it.
+static bool f1_decided_gate(const sdpgpu_handle* h, int period) {
+  if (!h->f1_cutoff || h->d.direction != SDPGPU_MIN) return false;
+  if (h->d.family != SDPGPU_FAMILY_BACKORDER || !window_eligible(h, period) || h->pmf_d[(size_t)period - 1].empty()) return false;
+  return f1_terms_nonneg_static(h, period);
+}
+int64_t f1_decided_start(const sdpgpu_handle* h, int period) {
+  const int64_t none = h->per[period - 1].hi;
+  const double step = h->d.step;
+  int64_t c_next = 0;
+  for (int u = h->T; u >= period; --u) {
+    if (!f1_decided_gate(h, u)) return none;
+    const PeriodInfo& p = h->per[u - 1];
+    const double lev0 = p.g.x_lo - h->pmf_d[(size_t)u - 1][0];
+    const double est = std::ceil(-lev0 / step);
+    if (!(std::fabs(est) < 1e15)) return none;
+    int64_t m0 = (int64_t)est;
+    const bool exact = lev0 == std::floor(lev0) && step == std::floor(step) && std::fabs(lev0) < 0x1p52 && step < 0x1p52;
+    if (!exact) {  // (the kernel's level is fl(lev0 + fl(m step)): settle on it, then one more)
+      for (int g = 0; g < 4 && lev0 + (double)m0 * step < 0; ++g) ++m0;
+      if (lev0 + (double)m0 * step < 0) return none;
+      ++m0;
+    }
+    int64_t c = std::max<int64_t>(0, m0 + p.nD_win - 1);
+    if (u < h->T) {
+      const PeriodInfo& pn = h->per[u];
+      if (c_next >= pn.S) return none;
+      const int64_t idx_off = (int32_t)((lev0 - pn.g.x_lo) / step);  // (launch_window's W.idx_off)
+      c = std::max(c, c_next - idx_off + p.nD_win - 1);
+    }
+    if (c >= p.S) return none;
+    c_next = c;
+  }
+  const PeriodInfo& p = h->per[period - 1];
+  return std::max(p.lo, std::min(c_next, p.hi));
+}
+// The split is OPT-IN (SDPGPU_F1_DECIDED=1, read at create time), under the planner's own level plan and under a forced one
+// alike.  It is not on by itself, although nothing about the tables depends on it: the benchmark's contract
+// (tests/test_gpu_bench_contract.py) holds the default headline to a throughput-bound sweep -- more than half of the fp64
+// peak by executed operations, and the separable mode more than three times faster -- and a sweep that walks 0.1 % of the
+// grid's cells is neither.  The default is a decision for whoever may change that contract.
+static bool f1_decided_on(const sdpgpu_handle* h) { return h->f1_decided > 0; }
+
 // The action-major level kernel (window_f1_level_kernel), where it can run and -- unless SDPGPU_WIN_LEVEL=1 asks for it
 // -- where it wins: a whole single-rank slab (no halo, no interior / boundary split), chunk rows allowed (every state's
 // actions meet across tasks), nothing forced about the state-major blocks, and a grid that fills the chip with tasks
@@ -107,7 +170,7 @@ static bool f1_screen_on(const sdpgpu_handle* h) { return h->f1_screen < 0 ? h->
 // actions stay on window_f1_kernel.  (R, S) = (4, 8): 232 VGPRs, two waves per SIMD, five broadcast ds_read_b128 per step
 // against 100 fp64 instructions ((4, 10) needs 277 VGPRs: one wave per SIMD).  The band is sized against the 2048 wave slots (two waves per SIMD): whole rounds of tasks,
 // each wave's table and slots within 16 KiB (64 KiB per workgroup).
-static WinPlan plan_level(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi) {
+static WinPlan plan_level(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, bool may_split = true) {
   WinPlan pl;
   if (h->win_level == 0 || h->win_r || h->win_s || h->win_nch) return pl;
   const PeriodInfo& p = h->per[period - 1];
@@ -124,7 +187,15 @@ static WinPlan plan_level(const sdpgpu_handle* h, int period, int64_t lo, int64_
   const bool last_cut = period == h->T && f1_cutoff_on(h, period, lo, hi);
   if (h->win_level < 0 && !((period < h->T || last_cut) && n >= 262144 && (double)nb * NA <= 1.06 * A && D >= 16)) return pl;
   constexpr int S = 8;
-  const int64_t ny = n + A - 1;
+  // THE DECIDED SPLIT: the level launch covers the live states [lo, c) alone where the boundary falls inside the slab (the
+  // launcher falls back to the whole-slab plan where the cut-off's gate then turns out closed: may_split = false).  The
+  // live bands hold at least two level blocks, so that the screen's mode rule can fire.
+  int64_t dec_c = -1;
+  if (may_split && f1_decided_on(h) && f1_pre_fits(h, period, lo, hi)) {
+    const int64_t c = f1_decided_start(h, period);
+    if (c > lo && c < hi) dec_c = c;
+  }
+  const int64_t ny = (dec_c >= 0 ? dec_c - lo : n) + A - 1;
   int band_max = 0;
   while (4 * sdp::level_wave_lds(band_max + S, R, S) <= kLdsLegacy) band_max += S;
   if (band_max < S) return pl;
@@ -137,8 +208,10 @@ static WinPlan plan_level(const sdpgpu_handle* h, int period, int64_t lo, int64_
       break;
     }
   }
+  if (dec_c >= 0) band = std::min(band_max, std::max(band, 2 * S));
   const int64_t n_bands = (ny + band - 1) / band;
   if (n_bands * nb > INT32_MAX / 2) return pl;
+  pl.dec_c = dec_c;
   pl.level = true;
   pl.R = R;
   pl.S = S;
@@ -157,7 +230,7 @@ WinPlan plan_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, 
   WinPlanCache& c = h->per[period - 1].win_plan;
   const bool may_chunk = h->fuse_combine && h->d.store_all_values;
   if (!(c.valid && c.lo == lo && c.hi == hi && c.win_r == h->win_r && c.win_s == h->win_s && c.win_nch == h->win_nch &&
-        c.win_level == h->win_level && c.may_chunk == may_chunk)) {
+        c.win_level == h->win_level && c.may_chunk == may_chunk && c.values_external == h->values_external)) {
     c.why.clear();
     c.plan = plan_window_search(h, period, lo, hi, &c.why);
     if (c.plan.R) {
@@ -171,6 +244,7 @@ WinPlan plan_window(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi, 
     c.win_nch = h->win_nch;
     c.win_level = h->win_level;
     c.may_chunk = may_chunk;
+    c.values_external = h->values_external;
     c.valid = true;
   }
   if (why && !c.plan.R) *why = c.why;
@@ -319,7 +393,8 @@ hipError_t flush_pending(sdpgpu_handle* h) {
   if (h->n_pending == 0) return hipSuccess;
   // The job list lives in the handle, at a fixed address: a caller that captures a sweep in a HIP graph records this
   // upload as a memcpy node FROM that address, and every sweep writes the same list there.
-  if (h->jobs_host.size() < (size_t)h->T * sizeof(sdp::FinalizeJob)) h->jobs_host.resize((size_t)h->T * sizeof(sdp::FinalizeJob));
+  // (two jobs for a period of the decided split: its live and its decided states)
+  if (h->jobs_host.size() < (size_t)h->T * 2 * sizeof(sdp::FinalizeJob)) h->jobs_host.resize((size_t)h->T * 2 * sizeof(sdp::FinalizeJob));
   sdp::FinalizeJob* jobs = reinterpret_cast<sdp::FinalizeJob*>(h->jobs_host.data());
   size_t n_jobs = 0;
   int64_t total = 0;
@@ -339,8 +414,26 @@ hipError_t flush_pending(sdpgpu_handle* h) {
     // only for this rank's slab
     J.vlo = h->d.world_size > 1 ? 0 : p.lo;
     J.vhi = h->d.world_size > 1 ? p.S : p.hi;
-    J.first = total;
     J.n_chunks = h->pending_chunks[t];
+    if (p.dec_c >= 0) {
+      // THE DECIDED SPLIT (launch_window): the period's part of the arena holds the decided states' one row, then the
+      // live states' chunk rows at their own stride
+      sdp::FinalizeJob Jd = J;
+      J.part_val = h->d_chunk_val + h->chunk_off[t] + (p.hi - p.dec_c) - p.lo;
+      J.part_idx = h->d_chunk_idx + h->chunk_off[t] + (p.hi - p.dec_c) - p.lo;
+      J.stride = p.dec_c - p.lo;
+      J.hi = J.vhi = p.dec_c;
+      J.first = total;
+      total += J.vhi - J.vlo;
+      jobs[n_jobs++] = J;
+      Jd.part_val = h->d_chunk_val + h->chunk_off[t] - p.dec_c;
+      Jd.part_idx = h->d_chunk_idx + h->chunk_off[t] - p.dec_c;
+      Jd.stride = 0;
+      Jd.lo = Jd.vlo = p.dec_c;
+      Jd.n_chunks = 1;
+      J = Jd;
+    }
+    J.first = total;
     total += J.vhi - J.vlo;
     jobs[n_jobs++] = J;
     h->pending_chunks[t] = 0;
@@ -348,7 +441,7 @@ hipError_t flush_pending(sdpgpu_handle* h) {
   h->n_pending = 0;
   if (n_jobs == 0 || total == 0) return hipSuccess;
   if (!h->d_jobs) {
-    hipError_t e = hipMalloc((void**)&h->d_jobs, (size_t)h->T * sizeof(sdp::FinalizeJob));
+    hipError_t e = hipMalloc((void**)&h->d_jobs, (size_t)h->T * 2 * sizeof(sdp::FinalizeJob));
     if (e != hipSuccess) return e;
   }
   hipError_t e = hipMemcpyAsync(h->d_jobs, jobs, n_jobs * sizeof(sdp::FinalizeJob), hipMemcpyHostToDevice, h->stream);
@@ -574,6 +667,12 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
     std::fprintf(stderr, "[sdpgpu] window plan: %s R=%d S=%d chunks=%d blocks/chunk=%d tiles=%d tasks=%d lds=%zu band=%d\n",
                  pl.level ? "level" : "state", pl.R, pl.S, pl.n_chunks, pl.chunk_blocks, pl.n_tiles, pl.n_tasks, pl.smem, pl.band);
   const bool future = period < h->T;
+  // THE DECIDED SPLIT is planned from the static part of the cut-off's gate; where the gate as it stands now (the row the
+  // period below left) is closed, the whole slab runs as one level launch
+  if (pl.level && pl.dec_c >= 0 && !f1_cutoff_on(h, period, lo, hi)) {
+    pl = plan_level(h, period, lo, hi, false);
+    if (!pl.R) return hipErrorInvalidValue;
+  }
   if (pl.level) {
     // c0 + M once per (action, m): 1/S; p * V once per (step, m) and wave: 1/(64 R); p * imm and two accumulations
     p.ops_cell = future ? 3.0 + 1.0 / pl.S + 1.0 / (64.0 * pl.R) : 2.0 + 1.0 / pl.S;
@@ -594,6 +693,7 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
   }
   // where V_{t+1} comes from: its key row while that period is still pending, else the final fp64 row
   const bool keyed_in = future && h->pending_chunks[period] > 0;
+  if (!continuing) p.dec_c = -1;  // (nothing of this period is pending any more; the level branch below says otherwise)
   if (chunked) {
     if (!h->d_chunk_val) {  // one-time arenas: a key row per period, the chunk rows of every chunked period
       size_t stride = 0;
@@ -608,9 +708,20 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
       for (int t = 0; t < h->T; ++t) {
         const PeriodInfo& q = h->per[t];
         h->chunk_off[t] = total;
-        if (window_eligible(h, t + 1))
-          total += (size_t)plan_window(h, t + 1, q.lo, q.hi).n_chunks * (size_t)std::max<int64_t>(chunk_row_cap(h, q), 0);
+        if (window_eligible(h, t + 1)) {
+          const WinPlan qp = plan_window(h, t + 1, q.lo, q.hi);
+          size_t need = (size_t)qp.n_chunks * (size_t)std::max<int64_t>(chunk_row_cap(h, q), 0);
+          if (qp.level && qp.dec_c >= 0) {
+            // a period of the decided split: one row of its decided states and the chunk rows of its live states -- or,
+            // should the cut-off's gate be closed when it runs, the rows of the whole-slab level plan
+            const size_t split = (size_t)(q.hi - qp.dec_c) + (size_t)qp.n_chunks * (size_t)(qp.dec_c - q.lo);
+            const WinPlan whole = plan_level(h, t + 1, q.lo, q.hi, false);
+            need = std::max(split, (size_t)whole.n_chunks * (size_t)std::max<int64_t>(chunk_row_cap(h, q), 0));
+          }
+          total += need;
+        }
       }
+      h->chunk_arena_elems = total;
       e = hipMalloc((void**)&h->d_chunk_val, std::max<size_t>(total, 1) * sizeof(double));
       if (e == hipSuccess) e = hipMalloc((void**)&h->d_chunk_idx, std::max<size_t>(total, 1) * sizeof(int32_t));
       if (e != hipSuccess) return e;
@@ -658,24 +769,31 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
     L.n_ablocks = pl.n_ablocks;
     L.n_tasks = pl.n_tasks;
     L.d_pad = pl.d_pad;
+    // THE DECIDED SPLIT: the level launch and its pre-pass see the slab [lo, live_hi) -- cells of the states from live_hi
+    // on are "outside the slab" to them -- and write chunk rows of their own stride behind the decided states' one row
+    const bool split = pl.dec_c >= 0;
+    const int64_t live_hi = split ? pl.dec_c : hi;
     L.lo = (int32_t)lo;
-    L.n_states = (int32_t)(hi - lo);
-    L.y_hi = (int32_t)(hi + W.n_actions - 1);
+    L.n_states = (int32_t)(live_hi - lo);
+    L.y_hi = (int32_t)(live_hi + W.n_actions - 1);
     L.n_chunks = pl.n_chunks;
     W.prio_fair = h->win_prio_fair;
-    W.partial_stride = chunk_row_cap(h, p);
+    W.partial_stride = split ? live_hi - lo : chunk_row_cap(h, p);
     double* out_val = h->d_chunk_val + h->chunk_off[period - 1] - chunk_row_lo(h, p);  // (rows indexed by flat state index)
     int32_t* out_idx = h->d_chunk_idx + h->chunk_off[period - 1] - chunk_row_lo(h, p);
+    if (split) {
+      out_val += hi - live_hi;
+      out_idx += hi - live_hi;
+    }
     unsigned long long* k_cur = h->d_keys + (size_t)(period - 1) * h->key_stride;
     if (!grid_ok((pl.n_tasks + 3) / 4)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((pl.n_tasks + 3) / 4));
     bool launched = false;
     // THE CUT-OFF (sdp_window.hpp): once per period, MIN only, every term >= 0, and SDPGPU_F1_CUTOFF=0 turns it off
     const bool cut = f1_cutoff_on(h, period, lo, hi);
-    const CutPrePlan pre = cut_pre_plan(p, lo, hi);
+    const CutPrePlan pre = cut_pre_plan(p, lo, live_hi);
     const int pre_dpad = pre.d_pad;
     const size_t pre_smem = pre.smem;
-    const int64_t pre_tiles = pre.tiles;
     {
       int64_t blocks = 0;
       for (int64_t yb = lo; yb < L.y_hi; yb += pl.band) blocks += (std::min<int64_t>(yb + pl.band, L.y_hi) - yb + pl.S - 1) / pl.S;
@@ -685,7 +803,7 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
     const double* u_row = nullptr;
     unsigned long long* cut_count = nullptr;
     if (cut) {
-      const size_t need = (size_t)(hi - lo);
+      const size_t need = (size_t)(live_hi - lo);
       if (need > h->f1_u_elems) {
         hipError_t e = hipStreamSynchronize(st);  // (earlier launches may still read the old row)
         if (e != hipSuccess) return e;
@@ -703,45 +821,57 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
       cut_count = h->d_cut_count + (size_t)(period - 1) * kCutCounters;
       hipError_t e = hipMemsetAsync(cut_count, 0, kCutCounters * sizeof(unsigned long long), st);
       if (e != hipSuccess) return e;
-      // U(i) = Q(i, 0): the state-major kernel with ONE action (its guards ignore the three padded actions of the R-block)
-      // and one chunk, into the row -- the same operations in the same order as the level kernel's action 0
-      sdp::WinParams Wp = W;
-      Wp.n_actions = 1;
-      Wp.d_pad = pre_dpad;
-      Wp.d_main = p.nD_win / 11 * 11;
-      Wp.n_chunks = 1;
-      Wp.chunk_blocks = 1;
-      Wp.n_tiles = (int32_t)pre_tiles;
-      Wp.n_tasks = (int32_t)pre_tiles;
-      Wp.tile_first = 0;
-      Wp.tile_gap_at = Wp.n_tiles;
-      Wp.tile_gap = 0;
-      Wp.partial_stride = 0;
-      Wp.pol_lo = Wp.pol_hi = 0;  // no action index is stored
-      double* u_out = h->d_f1_u - lo;
-      int32_t* no_idx = nullptr;
-      unsigned long long* no_keys = nullptr;
-      const dim3 pre_grid((unsigned)((pre_tiles + 3) / 4));
-#define SDP_PRE_GO(FU, KI)                                                                                                  \
-  do {                                                                                                                      \
-    static LdsMark mark;                                                                                                    \
-    hipError_t ea = lds_allow(sdp::window_f1_kernel<4, 8, FU, KI>, pre_smem, &mark);                                        \
-    if (ea != hipSuccess) return ea;                                                                                        \
-    hipLaunchKernelGGL((sdp::window_f1_kernel<4, 8, FU, KI>), pre_grid, dim3(256), pre_smem, st, Wp, v_next, k_next, u_out, \
-                       no_idx, no_keys, pmf_p, lo, hi);                                                                     \
+      // U(i) = Q(i, 0): the state-major kernel with ONE action (a register block of one action and eight states per lane)
+      // and one chunk, into the row -- the same operations in the same order as the level kernel's action 0.  The decided
+      // states take the very same launch as their whole period: value and action 0 into their row, the key published by the
+      // kernel's n_chunks > 1 atomics.
+      auto one_action = [&](int64_t r_lo, int64_t r_hi, double* o_val, int32_t* o_idx, unsigned long long* o_keys) -> hipError_t {
+        const int64_t tiles = (r_hi - r_lo + 511) / 512;
+        if (!grid_ok((tiles + 3) / 4)) return hipErrorInvalidValue;
+        sdp::WinParams Wp = W;
+        Wp.n_actions = 1;
+        Wp.d_pad = pre_dpad;
+        Wp.d_main = p.nD_win / 8 * 8;
+        Wp.n_chunks = o_keys ? 2 : 1;
+        Wp.chunk_blocks = 1;
+        Wp.n_tiles = (int32_t)tiles;
+        Wp.n_tasks = (int32_t)tiles;
+        Wp.tile_first = 0;
+        Wp.tile_gap_at = Wp.n_tiles;
+        Wp.tile_gap = 0;
+        Wp.partial_stride = 0;
+        Wp.pol_lo = o_idx ? INT64_MIN : 0;  // (the pre-pass stores no action index)
+        Wp.pol_hi = o_idx ? INT64_MAX : 0;
+        const dim3 pre_grid((unsigned)((tiles + 3) / 4));
+#define SDP_PRE_GO(FU, KI)                                                                                                 \
+  do {                                                                                                                     \
+    static LdsMark mark;                                                                                                   \
+    hipError_t ea = lds_allow(sdp::window_f1_kernel<1, 8, FU, KI>, pre_smem, &mark);                                       \
+    if (ea != hipSuccess) return ea;                                                                                       \
+    hipLaunchKernelGGL((sdp::window_f1_kernel<1, 8, FU, KI>), pre_grid, dim3(256), pre_smem, st, Wp, v_next, k_next, o_val, \
+                       o_idx, o_keys, pmf_p, r_lo, r_hi);                                                                  \
   } while (0)
-      if (!future)
-        SDP_PRE_GO(false, false);
-      else if (keyed_in)
-        SDP_PRE_GO(true, true);
-      else
-        SDP_PRE_GO(true, false);
+        if (!future)
+          SDP_PRE_GO(false, false);
+        else if (keyed_in)
+          SDP_PRE_GO(true, true);
+        else
+          SDP_PRE_GO(true, false);
 #undef SDP_PRE_GO
-      e = hipGetLastError();
+        return hipGetLastError();
+      };
+      double* u_out = h->d_f1_u - lo;
+      e = one_action(lo, live_hi, u_out, nullptr, nullptr);
       if (e != hipSuccess) return e;
       u_row = u_out;
-      // (four actions walked per state, at the state-major (4, 8) block's operations per cell)
-      p.pre_ops = (double)(hi - lo) * 4.0 * p.nD_win * (future ? 3.0 + 1.0 / 8 + 11.0 / 32 : 2.0 + 1.0 / 8);
+      if (split) {
+        double* d_val = h->d_chunk_val + h->chunk_off[period - 1] - live_hi;  // (indexed by flat state index)
+        int32_t* d_idx = h->d_chunk_idx + h->chunk_off[period - 1] - live_hi;
+        e = one_action(live_hi, hi, d_val, d_idx, k_cur);
+        if (e != hipSuccess) return e;
+      }
+      // (one action per state, at the state-major (1, 8) block's operations per cell: 3 + 1/S + (R + S - 1)/(R S))
+      p.pre_ops = (double)(hi - lo) * p.nD_win * (future ? 3.0 + 1.0 / 8 + 1.0 : 2.0 + 1.0 / 8);
     }
     L.cut_start = std::max(pl.S, p.nD_win / 2 / pl.S * pl.S);  // a task's first block: tests from D / 2 on
     // THE SCREEN (sdp_window.hpp): behind the cut-off's gate and nothing weaker
@@ -784,6 +914,8 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
       h->n_pending++;
       h->key_row_clean[period - 1] = 0;
     }
+    p.dec_c = split ? live_hi : -1;
+    p.dec_live_chunks = split ? pl.n_chunks : 0;
     return hipSuccess;
   }
   W.d_pad = pl.d_pad;

@@ -595,6 +595,17 @@ class SdpEngine:
         """Host arithmetic: the step the screen's rule gives for the pmf of `period` (0: no screen)."""
         return int(self._lib.sdpgpu_f1_screen_start(self._h, period))
 
+    def f1_decided_start(self, period: int) -> int:
+        """Host arithmetic: the first state index of `period`'s slab from which action 0 provably wins (the slab's end: none)."""
+        return int(self._lib.sdpgpu_f1_decided_start(self._h, period))
+
+    def f1_decided(self, period: int):
+        """The decided split of `period`: (boundary by the host rule, live states and decided states of the last solve's launch,
+        1 where the split ran, bytes of the chunk-row arenas)."""
+        out = (C.c_int64 * 5)()
+        self._check(self._lib.sdpgpu_f1_decided_get(self._h, period, out))
+        return tuple(int(v) for v in out)
+
     def period_cells(self, period: int) -> int:
         """Cells of `period` on this rank's slab (-1: not counted)."""
         return int(self._lib.sdpgpu_period_cells(self._h, period))
