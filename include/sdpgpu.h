@@ -1187,6 +1187,63 @@ int sdpgpu_custom_rule_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed
                                 double vari_cost, sdpgpu_sim_result* results, double* out_sum, double* out_demand);
 
 #if defined(__GNUC__)
+/* ---- two-product rollout: the computed policy of the three solves above along demand paths, on the device -----------------
+ * What `new CashSimulationMulti(...).simulateSDPGivenSamplNum[Multi](iniState)` (CashSimulationMulti.java:65-118) and
+ * `new CashSimulationMultiXR(...).simulateSDPGivenSamplNum(iniState)` (CashSimulationMultiXR.java:61-88) do after the solve:
+ * every path starts at the descriptor's period-1 state; for t = 0 .. T-1 the action pair of the current state is looked up
+ * (recursion.getAction: order-up-to levels for the XR family), sum += discount[t] * immediateValue(state, action, demand) and
+ * state = stateTransition(state, action, demand); after period T nothing is looked up.  The states lie on no grid, so the
+ * look-up is a probe of a hash table over the memo's (period, state tuple) keys, built once per policy object.  The lead-time
+ * family has no simulator in the reference; it gets the same loop over its own lambdas (MultiProductLeadtime.java:162-223).
+ * The exact construction is DESIGN.md 4 ("Two-product rollout").  Additive to ABI 6; errors through
+ * sdpgpu_multilead_last_error(); no C++ exception crosses these entry points. */
+typedef struct sdpgpu_multi_policy sdpgpu_multi_policy;
+
+/* The memo rows are those sdpgpu_multi_set_table received from a solve of the SAME descriptor
+   (the oracle's memo of it serves equally).  capacity_log2: 0 = the smallest power of two
+   >= 2 x rows, else any k with 2^k > rows.  Checked on the host before any device call: the descriptor as the solves check it;
+   memo non-NULL with 1 <= rows <= capacity and non-NULL columns; 2^capacity_log2 > rows; periods within 1 .. T; tuples finite;
+   action pairs inside the descriptor's box; exactly one period-1 row, equal to the descriptor's initial state
+   (SDPGPU_ERR_ARG naming the argument).  A state that appears twice with the same action pair is kept once; with different
+   pairs SDPGPU_ERR_ARG names the two rows.  xr: 0 = CashRecursionMulti, 1 = CashRecursionMultiXR (deposit_rate is read then). */
+int sdpgpu_multilead_policy_create(const sdpgpu_multilead* k, const sdpgpu_multi_table* memo,
+                                   int32_t capacity_log2, sdpgpu_multi_policy** out);
+int sdpgpu_multicash_policy_create(const sdpgpu_multicash* k, int32_t xr, double deposit_rate,
+                                   const sdpgpu_multi_table* memo, int32_t capacity_log2,
+                                   sdpgpu_multi_policy** out);
+void sdpgpu_multi_policy_destroy(sdpgpu_multi_policy* p);
+
+/* getAction for n states on the device: found[i] = 0 where the memo holds no such state. */
+int sdpgpu_multi_policy_lookup(sdpgpu_multi_policy* p, int64_t n, const int32_t* period,
+                               const double* i1, const double* i2, const double* q1,
+                               const double* q2, const double* cash,
+                               int32_t* a1, int32_t* a2, uint8_t* found);
+
+/* d1 / d2[path * T + t]: the demand pair of period t + 1, as the caller rounded it.
+   discount: NULL = all 1.0, else T weights (the reference's Math.pow(discountFactor, t)).
+   out_sum (NULL or n_paths): the path sums; out_valid (NULL or n_paths): bit 0 set when every look-up of the path hit.  A miss
+   (a demand outside the pmf support leads to a state the recursion never visited; the reference re-enters the recursion
+   there) ends the path and its sum is NaN.  result as sdpgpu_simulate_sampled fills it: mean and m2 in a fixed order (the same
+   bits on every call with the same arguments), both NaN when n_valid < n_paths -- the status is still SDPGPU_OK.  n_paths
+   1 .. 2^24 (above: SDPGPU_ERR_UNSUPPORTED). */
+int sdpgpu_multi_policy_simulate(sdpgpu_multi_policy* p, int32_t n_paths, const double* d1,
+                                 const double* d2, const double* discount,
+                                 sdpgpu_sim_result* result, double* out_sum, uint8_t* out_valid);
+/* The same with the demand pairs drawn on the device: one uniform per (path, period index t) from the streams of
+   sdpgpu_simulate_sampled (SDPGPU_SAMPLE_LHS / _RANDOM with instance position 0; mode and first_path rules as there) picks a
+   ROW of that period's joint tile -- thresholds = the running fp64 sum of the tile's probabilities in list order, the last one
+   +infinity, row q = #{c <= u}; multilead: the pairs in the engine's order i1 * n2 + i2 with p = p1 * p2.  Paths drawn this
+   way never leave the memo and their mean estimates V_1 without bias.  (The reference draws two independent columns per
+   period, generateLHSamplesMultiProd) */
+int sdpgpu_multi_policy_simulate_sampled(sdpgpu_multi_policy* p, int32_t n_paths, uint64_t seed,
+                                         int32_t mode, uint64_t first_path, const double* discount,
+                                         sdpgpu_sim_result* result, double* out_sum,
+                                         uint8_t* out_valid);
+/* Exactly what the sampled rollout draws: out_d1 / out_d2 / out_u [path * T + t]. */
+int sdpgpu_multi_policy_sample(sdpgpu_multi_policy* p, int32_t n_paths, uint64_t seed,
+                               int32_t mode, uint64_t first_path,
+                               double* out_d1, double* out_d2, double* out_u /* may be NULL */);
+
 #pragma GCC visibility pop
 #endif
 #ifdef __cplusplus

@@ -12,8 +12,9 @@ from .engine import SdpEngine
 from .fitss import FindsSOverDraft, FitsS
 from .functors import (BackorderFunctor, CashFunctor, CashXRFunctor, CashLeadtimeFunctor, CustomFunctor, LeadtimeFunctor, OverdraftFunctor,
                        SurvivalFunctor, java_round)
-from .multiitem import (Actions, CashRecursionMulti, CashRecursionMultiLead, CashRecursionMultiXR, CashStateMulti,
-                        CashStateMultiLead, CashStateMultiXR, MultiLeadResult, multicash_solve, multilead_solve, multixr_solve)
+from .multiitem import (Actions, CashRecursionMulti, CashRecursionMultiLead, CashRecursionMultiXR, CashSimulationMulti,
+                        CashSimulationMultiXR, CashStateMulti, CashStateMultiLead, CashStateMultiXR, MultiLeadResult, MultiPolicy,
+                        multicash_solve, multilead_solve, multixr_solve)
 from .pmf import BinomialDist, DiscreteDistribution, GammaDist, GetPmf, NormalDist, PoissonDist, UniformIntDist, staff_level_pmf
 from .recursion import (CLSP, CashLeadtimeRecursion, CashRecursion, CashRecursionXR, LeadtimeRecursion, Recursion, RecursionBatch, RecursionG,
                         RiskRecursion)
@@ -29,6 +30,7 @@ __all__ = [
     "StaffRecursion", "StaffFunctor", "StaffState", "SimulatesS", "BinomialDist", "staff_level_pmf",
     "multilead_solve", "multicash_solve", "multixr_solve", "MultiLeadResult", "Actions", "CashRecursionMulti",
     "CashRecursionMultiLead", "CashRecursionMultiXR", "CashStateMulti", "CashStateMultiLead", "CashStateMultiXR",
+    "MultiPolicy", "CashSimulationMulti", "CashSimulationMultiXR",
     "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "SimulationBatch", "RiskSimulation", "CashSimulation", "CashSimulationXR", "RecursionG", "Sampling",
     "FitsS", "FindsSOverDraft", "SimulateFitsS", "CheckKConvexity", "SdpgpuConvexity",
     "State", "LeadtimeState", "CashState", "CashStateXR", "CashLeadtimeState", "RiskState", "OptDirection", "java_round",

@@ -380,6 +380,15 @@ EXPORTS = {
     "sdpgpu_custom_rule_simulate": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_int32, _IP,
                                               _DP, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(SdpgpuSimResult), _DP, _DP]),
     "sdpgpu_xr_opt_levels": (C.c_int, [C.c_int32, _LP, _DP, _DP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _DP]),
+    "sdpgpu_multilead_policy_create": (C.c_int, [C.POINTER(SdpgpuMultilead), C.POINTER(SdpgpuMultiTable), C.c_int32, C.POINTER(_P)]),
+    "sdpgpu_multicash_policy_create": (C.c_int, [C.POINTER(SdpgpuMulticash), C.c_int32, C.c_double, C.POINTER(SdpgpuMultiTable), C.c_int32,
+                                                 C.POINTER(_P)]),
+    "sdpgpu_multi_policy_destroy": (None, [_P]),
+    "sdpgpu_multi_policy_lookup": (C.c_int, [_P, C.c_int64, _IP, _DP, _DP, _DP, _DP, _DP, _IP, _IP, C.POINTER(C.c_uint8)]),
+    "sdpgpu_multi_policy_simulate": (C.c_int, [_P, C.c_int32, _DP, _DP, _DP, C.POINTER(SdpgpuSimResult), _DP, C.POINTER(C.c_uint8)]),
+    "sdpgpu_multi_policy_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.POINTER(SdpgpuSimResult), _DP,
+                                                       C.POINTER(C.c_uint8)]),
+    "sdpgpu_multi_policy_sample": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, _DP, _DP]),
 }
 
 _lib = None

@@ -32,7 +32,8 @@ def sources():
     return [os.path.join(CSRC, f) for f in ("sdpgpu.hip", "sdpgpu_generic.hip", "sdpgpu_window.hip", "sdpgpu_cash.hip",
                                             "sdpgpu_staff.hip", "sdpgpu_sparse.hip", "sdpgpu_comm.hip", "sdpgpu_pmf.hip",
                                             "sdpgpu_batch.hip", "sdpgpu_simsample.hip", "sdpgpu_staffsim.hip",
-                                            "sdpgpu_cashrulesim.hip", "sdpgpu_xrsim.hip", "sdpgpu_customsim.hip")]
+                                            "sdpgpu_cashrulesim.hip", "sdpgpu_xrsim.hip", "sdpgpu_customsim.hip",
+                                            "sdpgpu_multisim.hip")]
 
 
 def deps():

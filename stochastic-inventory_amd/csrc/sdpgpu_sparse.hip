@@ -19,9 +19,8 @@
 // to the same value); it cannot merge different tuples, because representatives are cut by comparing
 // the full tuples.  This family is the one the reference records outputs for (KAT-1/KAT-2,
 // MultiProductLeadtime.java:30-50): tests/test_gpu_multilead.py reproduces them on the GPU.
-#include "../../include/sdpgpu.h"
+#include "sdp_multi_device.hpp"
 
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -37,108 +36,12 @@
 
 namespace {
 
+// the parameter block, the tuple, the model lambdas, the successor and the hash: sdp_multi_device.hpp (shared with the rollout)
+using namespace sdp_multi;
+
 thread_local std::string g_ml_error;
 thread_local sdpgpu_multi_table* g_ml_table = nullptr;  // read-out request for the next solve of this thread
 thread_local uint32_t g_ml_forms = 0;  // SDPGPU_MULTI_FORM_* bits of the launch sites this thread's last solve went through
-
-struct MLParams {
-  double price[2], vari[2], sal[2];
-  double r0, r1, r2, limit, interest_free;
-  double min_inventory, max_inventory, min_cash, max_cash, discount;
-  double overhead;  // of the period being processed
-  int32_t qb;       // actions (i, j), i, j in [0, qb)
-  int32_t nd;       // demand pairs, index = i1 * n2 + i2 (GetPmfMulti.java:157-172)
-  int32_t is_last;  // period == T: salvage applies, no transition
-  int32_t cash_int_cast;  // MultiProductLeadtime.java:219
-  int32_t model;          // 0: CashRecursionMultiLead + MultiProductLeadtime lambdas; 1: CashRecursionMulti + MultiItemCash;
-                          // 2: CashRecursionMultiXR + MultiItemCashXR (state (x1, x2, R), actions = order-up-to levels)
-  double one_minus_deposit;  // model 2: 1 - depositeRate
-};
-
-struct Tuple {
-  double i1, i2, q1, q2, cash;
-};
-
-__device__ __forceinline__ double jmax(double a, double b) { return fmax(a, b); }
-__device__ __forceinline__ double jmin(double a, double b) { return fmin(a, b); }
-
-// Piecewise overdraft interest, MultiProductLeadtime.java:186-194.
-__device__ __forceinline__ double ml_interest(const MLParams& P, double before) {
-  double interest;
-  if (before >= 0)
-    interest = -P.r0 * before;
-  else if (before >= -P.interest_free)
-    interest = 0;
-  else if (before >= -P.limit)
-    interest = P.r1 * (-before - P.interest_free);
-  else
-    interest = P.r2 * (-before - P.limit) + P.r1 * (P.limit - P.interest_free);
-  return interest;
-}
-
-// Demand-dependent pieces of one state, shared by all actions (MultiProductLeadtime.java:170-183).
-struct DemandTerms {
-  double revenue, sal_value, next_i1, next_i2;
-};
-
-__device__ __forceinline__ DemandTerms demand_terms(const MLParams& P, const Tuple& s, double d1, double d2) {
-  DemandTerms t;
-  const double end1 = jmax(0.0, s.i1 + s.q1 - d1);
-  const double end2 = jmax(0.0, s.i2 + s.q2 - d2);
-  const double revenue1 = P.price[0] * jmin(d1, s.i1 + s.q1);
-  const double revenue2 = P.price[1] * jmin(s.i2 + s.q2, d2);
-  t.revenue = revenue1 + revenue2;
-  t.sal_value = P.is_last ? (P.sal[0] * end1 + P.sal[1] * end2) : 0.0;
-  // the transition's own end inventories (:210-221): upper clamp on product 1 only, lower clamp on
-  // product 2 only, then (int) casts
-  double n1 = s.i1 + s.q1 - d1;
-  n1 = jmax(0.0, n1);
-  double n2 = s.i2 + s.q2 - d2;
-  n2 = jmax(0.0, n2);
-  n1 = n1 > P.max_inventory ? P.max_inventory : n1;
-  n2 = n2 < P.min_inventory ? P.min_inventory : n2;
-  t.next_i1 = (double)(int)n1;
-  t.next_i2 = (double)(int)n2;
-  return t;
-}
-
-// cashIncrement of (state, action, demand): MultiProductLeadtime.java:177-198 with the action-only part
-// (`bi` = cashBalanceBefore - interest) hoisted by the caller.
-__device__ __forceinline__ double cash_increment(const Tuple& s, double bi, const DemandTerms& t) {
-  const double after = bi + t.revenue + t.sal_value;
-  return after - s.cash;
-}
-
-__device__ __forceinline__ double next_cash(const MLParams& P, const Tuple& s, double inc) {
-  double c = s.cash + inc;
-  c = c > P.max_cash ? P.max_cash : c;
-  c = c < P.min_cash ? P.min_cash : c;
-  if (P.cash_int_cast) c = (double)(int)c;  // `nextCash = (int) nextCash` (:219)
-  return c;
-}
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long h, double v) {
-  v += 0.0;  // -0.0 -> +0.0 (the reference's equals() compares with ==)
-  unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  h ^= u + 0x9e3779b97f4a7c15ull + (h << 6) + (h >> 2);
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  return h;
-}
-
-__device__ __forceinline__ unsigned long long tuple_hash(const Tuple& t) {
-  unsigned long long h = 0x243f6a8885a308d3ull;
-  h = mix64(h, t.i1);
-  h = mix64(h, t.i2);
-  h = mix64(h, t.q1);
-  h = mix64(h, t.q2);
-  h = mix64(h, t.cash);
-  return h;
-}
-
-__device__ __forceinline__ bool tuple_eq(const Tuple& a, const Tuple& b) {
-  return a.i1 == b.i1 && a.i2 == b.i2 && a.q1 == b.q1 && a.q2 == b.q2 && a.cash == b.cash;
-}
 
 // ---- integer-lattice states (models 1 and 2) ---------------------------------------------------------------
 // After their (int) casts the successors of the two cash-constrained families live on an integer lattice
@@ -183,119 +86,6 @@ __device__ __forceinline__ int lattice_rank(const uint2* __restrict__ rank_info,
   const uint2 wp = rank_info[idx >> 5];
   const unsigned int below = wp.x & ((1u << (idx & 31)) - 1u);
   return (int)(wp.y + __popc(below));
-}
-
-// ---- model 1: sdp.cash.multiItem.CashRecursionMulti over the lambdas of cash.multiItem.MultiItemCash ----------
-// buildActionList (MultiItemCash.java:66-76): (i, j) is offered iff variCost[0] * i + variCost[1] * j < iniCash + 0.1
-__device__ __forceinline__ bool mc_feasible(const MLParams& P, const Tuple& s, int a1, int a2) {
-  return P.vari[0] * a1 + P.vari[1] * a2 < s.cash + 0.1;
-}
-
-// immediateValue (MultiItemCash.java:79-99)
-__device__ __forceinline__ double mc_immediate(const MLParams& P, const Tuple& s, int a1, int a2, double demand1,
-                                               double demand2) {
-  const double action1 = (double)a1, action2 = (double)a2;
-  const double endInventory1 = jmax(0.0, s.i1 + action1 - demand1);
-  const double endInventory2 = jmax(0.0, s.i2 + action2 - demand2);
-  const double revenue1 = P.price[0] * (s.i1 + action1 - endInventory1);
-  const double revenue2 = P.price[1] * (s.i2 + action2 - endInventory2);
-  const double revenue = revenue1 + revenue2;
-  const double orderingCost1 = P.vari[0] * action1;
-  const double orderingCost2 = P.vari[1] * action2;
-  const double orderingCosts = orderingCost1 + orderingCost2;
-  double salValue = 0;
-  if (P.is_last) salValue = P.sal[0] * endInventory1 + P.sal[1] * endInventory2;
-  return revenue - orderingCosts + salValue;
-}
-
-// stateTransition (MultiItemCash.java:103-118): upper clamp on product 1 only, lower clamp on product 2 only, (int) casts
-__device__ __forceinline__ Tuple mc_successor(const MLParams& P, const Tuple& s, int a1, int a2, double demand1,
-                                              double demand2) {
-  double endInventory1 = s.i1 + (double)a1 - demand1;
-  endInventory1 = jmax(0.0, endInventory1);
-  double endInventory2 = s.i2 + (double)a2 - demand2;
-  endInventory2 = jmax(0.0, endInventory2);
-  double nextCash = s.cash + mc_immediate(P, s, a1, a2, demand1, demand2);
-  nextCash = nextCash > P.max_cash ? P.max_cash : nextCash;
-  nextCash = nextCash < P.min_cash ? P.min_cash : nextCash;
-  endInventory1 = endInventory1 > P.max_inventory ? P.max_inventory : endInventory1;
-  endInventory2 = endInventory2 < P.min_inventory ? P.min_inventory : endInventory2;
-  Tuple n;
-  n.cash = (double)(int)nextCash;
-  n.i1 = (double)(int)endInventory1;
-  n.i2 = (double)(int)endInventory2;
-  n.q1 = 0.0;
-  n.q2 = 0.0;
-  return n;
-}
-
-// ---- model 2: sdp.cash.multiItem.CashRecursionMultiXR over the lambdas of cash.multiItem.MultiItemCashXR ------
-// The state is (x1, x2, R) with R = cash + variCost . x (kept in Tuple::cash); an action is a pair of order-up-to
-// levels (y1, y2) = ((int) x1 + i, (int) x2 + j), i, j in [0, Qbound) (MultiItemCashXR.java:92-105).
-// immediateValue (MultiItemCashXR.java:108-128)
-__device__ __forceinline__ double xr_immediate(const MLParams& P, const Tuple& s, double action1, double action2,
-                                               double demand1, double demand2) {
-  const double endInventory1 = jmax(0.0, action1 - demand1);
-  const double endInventory2 = jmax(0.0, action2 - demand2);
-  const double revenue1 = P.price[0] * (action1 - endInventory1);
-  const double revenue2 = P.price[1] * (action2 - endInventory2);
-  const double revenue = revenue1 + revenue2;
-  const double initialCash = s.cash - P.vari[0] * s.i1 - P.vari[1] * s.i2;
-  const double orderingCostY1 = P.vari[0] * action1;
-  const double orderingCostY2 = P.vari[1] * action2;
-  const double orderingCostsY = orderingCostY1 + orderingCostY2;
-  double salValue = 0;
-  if (P.is_last) salValue = P.sal[0] * endInventory1 + P.sal[1] * endInventory2;
-  return revenue + P.one_minus_deposit * (s.cash - orderingCostsY) + salValue - initialCash;
-}
-
-// stateTransition (MultiItemCashXR.java:132-148)
-__device__ __forceinline__ Tuple xr_successor(const MLParams& P, const Tuple& s, double action1, double action2,
-                                              double demand1, double demand2) {
-  double endInventory1 = action1 - demand1;
-  endInventory1 = jmax(0.0, endInventory1);
-  double endInventory2 = action2 - demand2;
-  endInventory2 = jmax(0.0, endInventory2);
-  const double initialCash = s.cash - P.vari[0] * s.i1 - P.vari[1] * s.i2;
-  double nextCash = initialCash + xr_immediate(P, s, action1, action2, demand1, demand2);
-  nextCash = nextCash > P.max_cash ? P.max_cash : nextCash;
-  nextCash = nextCash < P.min_cash ? P.min_cash : nextCash;
-  endInventory1 = endInventory1 > P.max_inventory ? P.max_inventory : endInventory1;
-  endInventory2 = endInventory2 < P.min_inventory ? P.min_inventory : endInventory2;
-  nextCash = (double)(int)nextCash;
-  endInventory1 = (double)(int)endInventory1;
-  endInventory2 = (double)(int)endInventory2;
-  Tuple n;
-  n.i1 = endInventory1;
-  n.i2 = endInventory2;
-  n.q1 = 0.0;
-  n.q2 = 0.0;
-  n.cash = (double)(int)nextCash + P.vari[0] * endInventory1 + P.vari[1] * endInventory2;  // nextR
-  return n;
-}
-
-// The successor of (state, action a, demand j).
-__device__ __forceinline__ Tuple successor(const MLParams& P, const Tuple& s, int a, const double2* dem, int j) {
-  const int a1 = a / P.qb, a2 = a - a1 * P.qb;
-  if (P.model == 1) {
-    // an action the state is not offered has no successors of its own: it stands in for (0, 0), which is always
-    // offered (0 < cash + 0.1 with cash >= min_cash >= 0), so the candidate list gains nothing new
-    const bool ok = mc_feasible(P, s, a1, a2);
-    return mc_successor(P, s, ok ? a1 : 0, ok ? a2 : 0, dem[j].x, dem[j].y);
-  }
-  if (P.model == 2)
-    return xr_successor(P, s, (double)((int)s.i1 + a1), (double)((int)s.i2 + a2), dem[j].x, dem[j].y);
-  const double oc = P.vari[0] * (double)a1 + P.vari[1] * (double)a2;
-  const double before = s.cash - oc - P.overhead;
-  const double bi = before - ml_interest(P, before);
-  const DemandTerms t = demand_terms(P, s, dem[j].x, dem[j].y);
-  Tuple n;
-  n.i1 = t.next_i1;
-  n.i2 = t.next_i2;
-  n.q1 = (double)a1;
-  n.q2 = (double)a2;
-  n.cash = next_cash(P, s, cash_increment(s, bi, t));
-  return n;
 }
 
 // ---- forward: candidates of one period ------------------------------------------------------------
@@ -1261,8 +1051,8 @@ __global__ __launch_bounds__(256) void backward_lead_wave_kernel(MLParams P, con
   } while (0)
 
 // No C++ exception crosses the C ABI: the entry points of this file build host vectors of up to ~1.8e7
-// tuples (the memo read-out) and a std::bad_alloc there must come back as a status code.  ML_GUARD wraps an entry point's
-// body; sparse_solve catches inside itself as well, so that its device buffers are released on that path too.
+// tuples (the memo read-out) and a std::bad_alloc there must come back as a status code.  ml_guard (sdp_multi_device.hpp) wraps an entry
+// point's body; sparse_solve catches inside itself as well, so that its device buffers are released on that path too.
 //   SDPGPU_TEST_THROW = bad_alloc | runtime | other : thrown at the top of the guarded region (tests, no device needed)
 //   SDPGPU_TEST_HOST_ALLOC_CAP = BYTES              : a host vector of the read-out larger than this throws bad_alloc
 void test_throw_hook() {
@@ -1280,33 +1070,9 @@ void checked_resize(V& v, size_t n) {
   v.resize(n);
 }
 
-template <class Body>
-int ml_guard(const char* who, Body&& body) {
-  try {
-    test_throw_hook();
-    return body();
-  } catch (const std::bad_alloc&) {
-    g_ml_error = std::string(who) + ": host allocation failed (std::bad_alloc)";
-    return SDPGPU_ERR_ALLOC;
-  } catch (const std::exception& e) {
-    g_ml_error = std::string(who) + ": internal error: " + e.what();
-    return SDPGPU_ERR_INTERNAL;
-  } catch (...) {
-    g_ml_error = std::string(who) + ": internal error (unknown exception)";
-    return SDPGPU_ERR_INTERNAL;
-  }
-}
-
 constexpr size_t kLdsPerCUSparse = 160 * 1024;  // (gfx950; sdpgpu_internal.hpp has the same figure for the grid kernels)
 
-struct SparseProblem {
-  int T = 0;
-  MLParams P{};
-  double overhead[16] = {0};
-  Tuple ini{};
-  std::vector<int> off;  // demand pairs of period t+1: [off[t], off[t+1])
-  std::vector<double2> dem;
-  std::vector<double> prob;
+struct SparseProblem : Problem {
   bool lattice_ok = false;  // models 1 / 2 with integer-lattice successors inside the box `lat`
   Lattice lat{};
 };
@@ -1877,14 +1643,13 @@ void sdpgpu_multi_set_table(sdpgpu_multi_table* table) { g_ml_table = table; }
 
 uint32_t sdpgpu_multi_forms_used(void) { return g_ml_forms; }
 
-static int multilead_body(const sdpgpu_multilead* k, double* final_value, int32_t* q1, int32_t* q2,
-                          int64_t* states_per_period, int64_t* cells, double* gpu_ms) {
+// the descriptor's checks and the problem it describes (the rollout's policy objects read the same: multilead_problem)
+static int multilead_fill(const sdpgpu_multilead* k, SparseProblem& sp) {
   if (!k || k->T < 1 || k->T > 16 || k->n1 < 1 || k->n1 > 16 || k->n2 < 1 || k->n2 > 16 || k->q_bound < 1 ||
       k->q_bound > 256) {
     g_ml_error = "multilead: bad descriptor";
     return SDPGPU_ERR_ARG;
   }
-  SparseProblem sp;
   sp.T = k->T;
   const int nd = k->n1 * k->n2;
   for (int t = 0; t <= k->T; ++t) sp.off.push_back(t * nd);
@@ -1909,6 +1674,13 @@ static int multilead_body(const sdpgpu_multilead* k, double* final_value, int32_
   P.model = 0;
   for (int t = 0; t < k->T; ++t) sp.overhead[t] = k->overhead[t];
   sp.ini = Tuple{k->ini_i1, k->ini_i2, 0.0, 0.0, k->ini_cash};  // MultiProductLeadtime.java:232
+  return SDPGPU_OK;
+}
+
+static int multilead_body(const sdpgpu_multilead* k, double* final_value, int32_t* q1, int32_t* q2,
+                          int64_t* states_per_period, int64_t* cells, double* gpu_ms) {
+  SparseProblem sp;
+  if (const int rc = multilead_fill(k, sp)) return rc;
   return sparse_solve(sp, final_value, q1, q2, states_per_period, cells, gpu_ms);
 }
 
@@ -1918,8 +1690,7 @@ int sdpgpu_multilead_solve(const sdpgpu_multilead* k, double* final_value, int32
   return ml_guard("multilead", [&] { return multilead_body(k, final_value, q1, q2, states_per_period, cells, gpu_ms); });
 }
 
-static int multicash_body(const sdpgpu_multicash* k, int model, double deposit_rate, double* final_value, int32_t* q1,
-                          int32_t* q2, int64_t* states_per_period, int64_t* cells, double* gpu_ms) {
+static int multicash_fill(const sdpgpu_multicash* k, int model, double deposit_rate, SparseProblem& sp) {
   if (!k || k->T < 1 || k->T > 16 || k->q_bound < 1 || k->q_bound > 256 || !k->pmf_off || !k->d1 || !k->d2 || !k->p) {
     g_ml_error = "multicash: bad descriptor";
     return SDPGPU_ERR_ARG;
@@ -1933,7 +1704,6 @@ static int multicash_body(const sdpgpu_multicash* k, int model, double deposit_r
     g_ml_error = "multicash: negative cash is not supported (MultiItemCash.java:51 has minCashState = 0)";
     return SDPGPU_ERR_UNSUPPORTED;
   }
-  SparseProblem sp;
   sp.T = k->T;
   for (int t = 0; t <= k->T; ++t) {
     if (k->pmf_off[t] < 0 || (t && k->pmf_off[t] <= k->pmf_off[t - 1]) || k->pmf_off[t] - (t ? k->pmf_off[t - 1] : 0) > 4096) {
@@ -1993,6 +1763,13 @@ static int multicash_body(const sdpgpu_multicash* k, int model, double deposit_r
   }
   // MultiItemCash.java:130; MultiItemCashXR.java:158 hands iniCash over as R
   sp.ini = Tuple{k->ini_i1, k->ini_i2, 0.0, 0.0, k->ini_cash};
+  return SDPGPU_OK;
+}
+
+static int multicash_body(const sdpgpu_multicash* k, int model, double deposit_rate, double* final_value, int32_t* q1,
+                          int32_t* q2, int64_t* states_per_period, int64_t* cells, double* gpu_ms) {
+  SparseProblem sp;
+  if (const int rc = multicash_fill(k, model, deposit_rate, sp)) return rc;
   int a1 = 0, a2 = 0;
   const int rc = sparse_solve(sp, final_value, &a1, &a2, states_per_period, cells, gpu_ms);
   if (rc == SDPGPU_OK) {  // model 2 answers with the order-up-to levels themselves (getAction(iniState)[0], [1])
@@ -2020,3 +1797,26 @@ int sdpgpu_multixr_solve(const sdpgpu_multicash* k, double deposit_rate, double*
 }
 
 }  // extern "C"
+
+// ---- what the rollout's translation unit reads of this one (sdp_multi_device.hpp) ----
+namespace sdp_multi {
+
+std::string& ml_error() { return g_ml_error; }
+
+void ml_test_throw_hook() { test_throw_hook(); }
+
+int multilead_problem(const sdpgpu_multilead* k, Problem* out) {
+  SparseProblem sp;
+  if (const int rc = multilead_fill(k, sp)) return rc;
+  *out = sp;  // (the engine's own fields -- the lattice box -- stay behind)
+  return SDPGPU_OK;
+}
+
+int multicash_problem(const sdpgpu_multicash* k, int model, double deposit_rate, Problem* out) {
+  SparseProblem sp;
+  if (const int rc = multicash_fill(k, model, deposit_rate, sp)) return rc;
+  *out = sp;
+  return SDPGPU_OK;
+}
+
+}  // namespace sdp_multi

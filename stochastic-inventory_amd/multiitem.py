@@ -132,6 +132,141 @@ def multixr_solve(depositeRate: float = 0.0, table: bool = False, **kw) -> Multi
 
 
 # ---------------------------------------------------------------------------------------------------------------
+# The computed policy on the device: a hash table over the memo's states and its rollouts (sdpgpu_multi_policy_*;
+# DESIGN 4, "Two-product rollout").
+# ---------------------------------------------------------------------------------------------------------------
+def _sample_mode(mode):
+    if mode in ("lhs", _abi.SAMPLE_LHS):
+        return _abi.SAMPLE_LHS
+    if mode in ("random", _abi.SAMPLE_RANDOM):
+        return _abi.SAMPLE_RANDOM
+    raise ValueError(f"mode {mode!r}: 'lhs' or 'random'")
+
+
+def _u64(v):
+    return C.c_uint64(int(v) & (2**64 - 1))
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def table_from_rows(rows):
+    """A sdpgpu_multi_table over memo rows {period, i1, i2, q1, q2, cash or R, value, a1, a2} (MultiLeadResult.table, or the
+    oracle's memo): -> (struct, the arrays it points to)."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 9)
+    t, arrs = _abi.make_multi_table(len(rows))
+    for c, name in enumerate(("period", "i1", "i2", "q1", "q2", "cash", "value", "a1", "a2")):
+        arrs[name][:] = rows[:, c]
+    t.rows = len(rows)
+    return t, arrs
+
+
+class MultiPolicy:
+    """The policy a two-product solve computed, on the device: `kind` is "multilead", "multicash" or "multixr", `rows` the
+    memo of a solve of the SAME keyword arguments (MultiLeadResult.table), `kw` those arguments.  lookup = getAction for many
+    states; simulate / simulate_sampled roll the policy along demand pairs from the period-1 state as CashSimulationMulti /
+    CashSimulationMultiXR do; sample returns what simulate_sampled draws.  close() releases the device memory."""
+
+    def __init__(self, kind: str, rows, capacity_log2: int = 0, depositeRate: float = 0.0, **kw):
+        self._lib = _abi.load()
+        self._h = C.c_void_p()
+        self.kind = kind
+        t, arrs = table_from_rows(rows)
+        if kind == "multilead":
+            k = fill_multilead(SdpgpuMultilead(), **kw)
+            rc = self._lib.sdpgpu_multilead_policy_create(C.byref(k), C.byref(t), int(capacity_log2), C.byref(self._h))
+        elif kind in ("multicash", "multixr"):
+            k = fill_multicash(SdpgpuMulticash(), **kw)
+            rc = self._lib.sdpgpu_multicash_policy_create(C.byref(k), 1 if kind == "multixr" else 0, float(depositeRate), C.byref(t),
+                                                          int(capacity_log2), C.byref(self._h))
+        else:
+            raise ValueError(f"kind {kind!r}: 'multilead', 'multicash' or 'multixr'")
+        self._check(rc)
+        self.T = int(k.T)
+        self.rows = int(t.rows)
+
+    def _check(self, rc):
+        if rc:
+            raise SdpgpuError(rc, self._lib.sdpgpu_multilead_last_error().decode())
+
+    def close(self):
+        if self._h:
+            self._lib.sdpgpu_multi_policy_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def lookup(self, period, i1, i2, q1, q2, cash):
+        """getAction of n states: (a1[n], a2[n], found[n]); found is False where the memo holds no such state."""
+        per = np.ascontiguousarray(period, dtype=np.int32)
+        cols = [np.ascontiguousarray(c, dtype=np.float64) for c in (i1, i2, q1, q2, cash)]
+        n = len(per)
+        if any(c.shape != (n,) for c in cols):
+            raise ValueError("period, i1, i2, q1, q2 and cash must have one entry per state")
+        a1, a2 = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        found = np.zeros(n, np.uint8)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self._lib.sdpgpu_multi_policy_lookup(self._h, n, ip(per), *(_dp(c) for c in cols), ip(a1), ip(a2),
+                                                         found.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return a1, a2, found.astype(bool)
+
+    def _disc(self, discount):
+        if discount is None:
+            return None
+        disc = np.ascontiguousarray(discount, dtype=np.float64)
+        if disc.shape != (self.T,):
+            raise ValueError("discount must have one entry per period")
+        return disc
+
+    def simulate(self, d1, d2, discount=None):
+        """Roll the policy along the demand pairs d1 / d2 [n, T] (as the caller rounded them): -> (SdpgpuSimResult, sums[n],
+        valid[n]).  A path whose look-up misses ends there: its sum is NaN, and mean and m2 of the result are NaN then."""
+        d1 = np.ascontiguousarray(d1, dtype=np.float64)
+        d2 = np.ascontiguousarray(d2, dtype=np.float64)
+        if d1.ndim != 2 or d1.shape[1] != self.T or d2.shape != d1.shape:
+            raise ValueError(f"d1 and d2 must both have shape (n_paths, {self.T})")
+        disc = self._disc(discount)
+        n = len(d1)
+        res = _abi.SdpgpuSimResult()
+        sums, valid = np.empty(n), np.zeros(n, np.uint8)
+        self._check(self._lib.sdpgpu_multi_policy_simulate(self._h, n, _dp(d1), _dp(d2), None if disc is None else _dp(disc), C.byref(res),
+                                                           _dp(sums), valid.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return res, sums, valid
+
+    def simulate_sampled(self, n_paths: int, seed: int, *, mode="lhs", first_path: int = 0, discount=None, want_sums: bool = False):
+        """Draw n_paths paths of demand pairs on the device (a row of each period's joint tile per uniform), roll and reduce
+        there: -> SdpgpuSimResult; with want_sums also (sums[n], valid[n])."""
+        disc = self._disc(discount)
+        n = int(n_paths)
+        res = _abi.SdpgpuSimResult()
+        sums = np.empty(max(n, 0)) if want_sums else None
+        valid = np.zeros(max(n, 0), np.uint8) if want_sums else None
+        self._check(self._lib.sdpgpu_multi_policy_simulate_sampled(
+            self._h, n, _u64(seed), _sample_mode(mode), _u64(first_path), None if disc is None else _dp(disc), C.byref(res),
+            None if sums is None else _dp(sums), None if valid is None else valid.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return (res, sums, valid) if want_sums else res
+
+    def sample(self, n_paths: int, seed: int, *, mode="lhs", first_path: int = 0):
+        """(d1[n, T], d2[n, T], u[n, T]): exactly what simulate_sampled draws."""
+        n = max(int(n_paths), 0)
+        d1, d2, u = (np.empty((n, self.T)) for _ in range(3))
+        self._check(self._lib.sdpgpu_multi_policy_sample(self._h, int(n_paths), _u64(seed), _sample_mode(mode), _u64(first_path), _dp(d1),
+                                                         _dp(d2), _dp(u)))
+        return d1, d2, u
+
+
+# ---------------------------------------------------------------------------------------------------------------
 # Mirror classes: the reference's names and methods over the solvers above.  As elsewhere the lambdas are accepted
 # and kept for the caller's own use (simulators), and a functor -- here simply the keyword arguments of the solver --
 # names the closed-form family the device evaluates.  The first getExpectedValue runs the solve and reads the whole
@@ -231,6 +366,7 @@ class _MultiRecursionBase:
             if ini[0] != 1:
                 raise ValueError("the first getExpectedValue must be asked for a period-1 state (it fixes the reachable set)")
             self._result = self._run(f, ini)
+            self._ini = ini
             t = self._result.table
             self._memo = {tuple(r[:6]): (float(r[6]), int(r[7]), int(r[8])) for r in t}
         return self._result
@@ -254,13 +390,24 @@ class _MultiRecursionBase:
     def result(self) -> MultiLeadResult:
         return self._result
 
+    _kind = None  # "multilead" / "multicash" / "multixr"
+
+    def policy(self, capacity_log2: int = 0) -> MultiPolicy:
+        """The computed policy on the device, from the memo the first getExpectedValue read back."""
+        if self._result is None:
+            raise RuntimeError("policy(): ask getExpectedValue for the period-1 state first (it runs the solve)")
+        return MultiPolicy(self._kind, self._result.table, capacity_log2, **self._solve_kw)
+
 
 class CashRecursionMultiLead(_MultiRecursionBase):
     """sdp.cash.multiItem.CashRecursionMultiLead (CashRecursionMultiLead.java:31-101) for the lambdas of
     MultiProductLeadtime.main; functor = the keyword arguments of multilead_solve (initial state and T come from the call)."""
 
+    _kind = "multilead"
+
     def _run(self, f, ini):
         kw = dict(f, ini_i1=ini[1], ini_i2=ini[2], ini_cash=ini[5])
+        self._solve_kw = dict(kw)
         return multilead_solve(table=True, **kw)
 
     def getAction(self, state: CashStateMultiLead) -> Actions:
@@ -272,8 +419,11 @@ class CashRecursionMulti(_MultiRecursionBase):
     """sdp.cash.multiItem.CashRecursionMulti (CashRecursionMulti.java:39-211) for the lambdas of MultiItemCash.main;
     functor = the keyword arguments of multicash_solve; `Pmf` = the per-period lists GetPmfMulti.getPmf(t) returns."""
 
+    _kind = "multicash"
+
     def _run(self, f, ini):
         kw = dict(f, ini_i1=ini[1], ini_i2=ini[2], ini_cash=ini[5], pmf=self.Pmf)
+        self._solve_kw = dict(kw)
         return multicash_solve(table=True, **kw)
 
     def getAction(self, state: CashStateMulti) -> Actions:
@@ -297,8 +447,11 @@ class CashRecursionMultiXR(_MultiRecursionBase):
     """sdp.cash.multiItem.CashRecursionMultiXR (CashRecursionMultiXR.java:39-148) for the lambdas of
     MultiItemCashXR.main; functor = the keyword arguments of multixr_solve (+ "depositeRate")."""
 
+    _kind = "multixr"
+
     def _run(self, f, ini):
         kw = dict(f, ini_i1=ini[1], ini_i2=ini[2], ini_cash=ini[5], pmf=self.Pmf)
+        self._solve_kw = dict(kw)  # (MultiPolicy takes depositeRate by that name)
         dep = kw.pop("depositeRate", 0.0)
         return multixr_solve(dep, table=True, **kw)
 
@@ -319,3 +472,50 @@ class CashRecursionMultiXR(_MultiRecursionBase):
                 alpha = variCost[0] * y1 / R
             rows.append([period, x1, x2, w, R, boolAlpha, alpha, float(y1), float(y2), variCost[0], variCost[1]])
         return np.array(rows)
+
+
+class _MultiSimulationBase:
+    """What the two simulators share: the sampled rollout of the recursion's policy on the device.  The reference draws two
+    independent latin-hypercube columns per period (Sampling.generateLHSamplesMultiProd); here ONE uniform per (path, period)
+    picks a row of the period's joint tile, so that every path stays inside the memo ("Two-product rollout").
+    `distributions`, stateTransition and immediateValue are kept for the caller; the device evaluates the closed forms the
+    recursion's functor names."""
+
+    def __init__(self, sampleNum, distributions, discountFactor, recursion, stateTransition=None, immediateValue=None, *, seed: int = 0):
+        self.sampleNum, self.distributions, self.discountFactor, self.recursion = int(sampleNum), distributions, discountFactor, recursion
+        self.stateTransition, self.immediateValue = stateTransition, immediateValue
+        self.seed = seed
+        self.last_result = None
+
+    def setSampleNum(self, n):
+        self.sampleNum = int(n)
+
+    def _simulate(self, iniState) -> float:
+        self.recursion.getExpectedValue(iniState)  # (the first call runs the solve)
+        if iniState._key() != self.recursion._ini:
+            raise ValueError("the policy's paths start at the period-1 state the recursion was solved from; simulate from that state")
+        T = len(self.recursion.result.statesPerPeriod)
+        with self.recursion.policy() as pol:
+            # Math.pow(discountFactor, t)
+            self.last_result = pol.simulate_sampled(self.sampleNum, self.seed, discount=[self.discountFactor ** t for t in range(T)])
+        return self.last_result.mean
+
+
+class CashSimulationMulti(_MultiSimulationBase):
+    """sdp.cash.multiItem.CashSimulationMulti (CashSimulationMulti.java:23-118) over a CashRecursionMulti."""
+
+    def simulateSDPGivenSamplNum(self, iniState: CashStateMulti) -> float:
+        """CashSimulationMulti.java:65-91: the mean of the path sums + iniState.iniCash."""
+        return self._simulate(iniState) + iniState.iniCash
+
+    def simulateSDPGivenSamplNumMulti(self, iniState: CashStateMulti) -> float:
+        """CashSimulationMulti.java:98-118 (the two-product Poisson driver's call): the same rollout."""
+        return self._simulate(iniState) + iniState.iniCash
+
+
+class CashSimulationMultiXR(_MultiSimulationBase):
+    """sdp.cash.multiItem.CashSimulationMultiXR (CashSimulationMultiXR.java:23-88) over a CashRecursionMultiXR."""
+
+    def simulateSDPGivenSamplNum(self, iniState: CashStateMultiXR) -> float:
+        """CashSimulationMultiXR.java:61-88: the mean of the path sums + iniState.iniR."""
+        return self._simulate(iniState) + iniState.iniR
