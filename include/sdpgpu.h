@@ -335,7 +335,8 @@ void sdpgpu_destroy(sdpgpu_handle* h);
  * off): a clamp the Java source spells `x > c ? c : x` against a non-zero constant then costs one v_min_f64 instead of a compare
  * and two selects.  For lambdas whose values are numbers the results are the same doubles either way
  * (tests/test_gpu_custom_functor.py runs the three modes against each other); what a lambda that does produce a NaN returns is
- * unspecified in the default mode.
+ * unspecified in the default mode.  With NaNs honoured, and on every grid that is not baked, it is Java's: the action is skipped
+ * (tests/test_gpu_custom_functor.py, test_nan_lambda_*).
  */
 int sdpgpu_create_custom(const sdpgpu_desc* desc, const char* functor_source, const double* params, int32_t n_params,
                          sdpgpu_handle** out);

@@ -250,6 +250,45 @@ def f6_survival_gamma(T=3):
     return Workload("f6_survival_gamma", f, OptDirection.MAX, _pmf([3, 5, 4][:T], 9))
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# Small-cost, LARGE-STATE instances for the user-text engine (tests/test_gpu_custom_scrambled.py): the generic loop picks its
+# launch form by the number of states of a launch (csrc/sdpgpu_generic.hip, launch_custom_period: SX = 64 from 64 * 2048 states,
+# SX = 16 from 16 * 1024, SX = 4 below), so these are wide in states and tiny in actions and demands.  Each has 3 periods, 4
+# demand points, 6 or 7 actions at most (below 16, no multiple of 4: under SX = 16 some action slots stay empty and the others
+# make one trip, under SX = 64 some slots make two trips and some one), a state count that is no multiple of 64 and a negative
+# minCashState (k_lo < 0).  Not in ALL / TINY: the parity tests of every kernel variant have no use for them.
+# ---------------------------------------------------------------------------------------------------------------
+def f3_custom_wide():
+    """(x, cash), CashConstraint's own quantum (tenths, `/ 10.0`): 10 x 15001 = 150010 states.  The cash bound on the order
+    binds below a balance of about 129 (1 .. 6 actions by state), nothing is exact (fractional prices, deposit rate, penalty)."""
+    f = CashFunctor(price=37.3, fixOrderCost=12.5, variCost=21.7, holdingCost=0.6, depositeRate=0.01, overheadRate=0.05,
+                    salvageValue=3.2, penaltyCost=0.3, discountFactor=0.97, maxOrderQuantity=5, minInventoryState=0,
+                    maxInventoryState=9, minCashState=-100, maxCashState=1400, cashRoundMult=10.0, cashRoundDiv=10.0,
+                    cashRoundIntDiv=False, cashFormula=0, iniInventory=0, iniCash=150, overheadCosts=[8.3, 5.1, 9.7])
+    return Workload("f3_custom_wide", f, OptDirection.MAX, discrete_pmf(3, [0, 2, 3, 6], [0.15, 0.35, 0.3, 0.2]))
+
+
+def f5_custom_wide():
+    """(x, cash, preQ), SingleProductLeadtime's hundredths: 8 x 2501 x 7 = 140056 states, index ((iq * 8 + ix) * 2501 + ic).  The
+    family's action list does not depend on the state (7 orders; 1 in the last period); the interest schedule does."""
+    f = CashLeadtimeFunctor(price=1.37, variCost=0.42, salvageValue=0.15, maxOrderQuantity=6, minInventoryState=0,
+                            maxInventoryState=7, minCashState=-5, maxCashState=20, cashRoundMult=100.0, cashRoundDiv=100.0,
+                            cashRoundIntDiv=False, r0=0.01, r2=0.1, r3=2.0, limit=3, interestFreeAmount=1, iniInventory=0,
+                            iniCash=2, iniPreQ=0, overheadCosts=[0.55, 0.35, 0.6])
+    return Workload("f5_custom_wide", f, OptDirection.MAX, discrete_pmf(3, [0, 1, 2, 4], [0.2, 0.3, 0.3, 0.2]))
+
+
+def f6_custom_wide():
+    """Survival probability over (x, cash) with integer cash: 12 x 5001 = 60012 states (between 16 * 1024 and 64 * 2048); orders
+    limited by cash / variCost (1 .. 6 actions below a balance of 200), successors with a negative balance are skipped."""
+    f = SurvivalFunctor(price=90, fixOrderCost=15, variCost=40, holdingCost=2.5, depositeRate=0.02, salvageValue=10,
+                        discountFactor=0.97, maxOrderQuantity=5, minInventoryState=0, maxInventoryState=11, minCashState=-300,
+                        maxCashState=4700, iniInventory=0, iniCash=260, overheadCosts=[55.0, 70.0, 40.0])
+    return Workload("f6_custom_wide", f, OptDirection.MAX, discrete_pmf(3, [0, 1, 3, 5], [0.2, 0.3, 0.3, 0.2]))
+
+
+CUSTOM_WIDE = [f3_custom_wide, f5_custom_wide, f6_custom_wide]
+
 ALL = [f1_small, f1_max, f1_gapped, f1_sparse_support, f1_unclamped, f1_edge_single, f2_unclamped, f2_clamped, f2_pipeline, f3_tenths, f3_row, f3_testing, f3_dyadic, f3_min_gamma,
        f3_xr, f3_xr_fractional, f3_grid_prices, f3_half_grid_prices, f4_overdraft, f5_cash_leadtime, f6_survival, f6_survival_gamma]
 TINY = [f1_small, f1_max, f1_gapped, f1_unclamped, f2_unclamped, f3_testing, f3_min_gamma, f3_xr, f3_xr_fractional, f4_overdraft]

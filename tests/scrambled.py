@@ -1,5 +1,5 @@
 """Scrambled successor tables: helpers of tests/test_scrambled_inputs.py (CPU) and tests/test_gpu_scrambled_successor.py /
-tests/test_gpu_survival_wide.py / tests/test_gpu_f2_scrambled_successor.py (GPU).  No test lives here.
+tests/test_gpu_survival_wide.py / tests/test_gpu_f2_scrambled_successor.py / tests/test_gpu_custom_scrambled.py (GPU).  No test lives here.
 
 The value tables the recursion itself produces are almost constant along the cash axis for the cash families (V(x, cash) is an
 expected cash INCREMENT: it does not depend on the balance while the order constraint is slack; survival probabilities are
@@ -99,8 +99,11 @@ def reference(oracle, w):
     return ref
 
 
-def run_scrambled(sia, oracle, w, kernel=0, poison=None, periods=None, rank=0, world=1):
+def run_scrambled(sia, oracle, w, kernel=0, poison=None, periods=None, rank=0, world=1, custom=None, slabs=None):
     """One instance on the GPU, every period below T on a scrambled V_{t+1}; returns stats().kernel_used.
+    custom: (text, params) -- the handle is a USER-TEXT handle (sdpgpu_create_custom) of a text that restates w's family
+    (tests/custom_sources.py; tests/test_custom_functor.py proves on the CPU that it does), nothing else changes: the reference
+    stays the built-in oracle.  slabs: a list that receives (t, lo, hi) of every period the handle ran.
     rank, world: the handle is that rank's slab of a sharded sweep (a table is padded to a multiple of `world` states: with one
     rank there is no padding); the whole V_{t+1} is written here, so no exchange is needed, and the slab's states are compared.
 
@@ -112,19 +115,23 @@ def run_scrambled(sia, oracle, w, kernel=0, poison=None, periods=None, rank=0, w
     periods: the t to compare (the pairs the sensitivity condition kept); the others still run, on their scrambled table.
 
     Not reached this way: with a caller's arena the F1 cut-off gate is off below T (values_external), and the keyed-input form
-    of the window kernels is never taken (the flush above).  Both have their own twins and tests."""
+    of the window kernels is never taken (the flush above).  Both have their own twins and tests.  For a user-text handle a
+    caller's arena turns nothing off: the generic loop has one form per launch size, chosen by the slab alone."""
     import torch
     ref = reference(oracle, w)
     d = w.desc()
     d.kernel = kernel
     d.rank, d.world_size = rank, world
     T = w.T
-    with sia.SdpEngine(d, w.pmf, w.overhead()) as eng:
+    kw = {} if custom is None else dict(custom_source=custom[0], custom_params=custom[1])
+    with sia.SdpEngine(d, w.pmf, w.overhead(), **kw) as eng:
         buf = torch.zeros(eng.values_bytes() // 8, dtype=torch.float64, device="cuda")
         eng.attach_values(buf.data_ptr(), buf.numel() * 8)
         eng.set_stream(torch.cuda.current_stream().cuda_stream)
         eng.run_period(T)
         _, lo, hi = eng.slab(T)
+        if slabs is not None:
+            slabs.append((T, lo, hi))
         assert np.array_equal(eng.policy(T), ref["pol"][T - 1][lo:hi]), f"{w.name} kernel {kernel} t={T}: policy"
         assert np.array_equal(eng.values(T)[lo:hi], ref["V"][T - 1][lo:hi]), f"{w.name} kernel {kernel} t={T}: values"
         for t in range(T - 1, 0, -1):
@@ -138,6 +145,8 @@ def run_scrambled(sia, oracle, w, kernel=0, poison=None, periods=None, rank=0, w
                 buf[off + S:off + padded] = poison
             eng.run_period(t)
             _, lo, hi = eng.slab(t)
+            if slabs is not None:
+                slabs.append((t, lo, hi))
             gv, ga = eng.values(t)[lo:hi], eng.policy(t)
             want_v, want_a = want_v[lo:hi], want_a[lo:hi]
             if periods is None or t in periods:
@@ -190,6 +199,12 @@ def parametrize_values(test_function, argname):
     raise KeyError(argname)
 
 
+def custom_wide_cases():
+    """name -> workload: the large-state instances of tests/test_gpu_custom_scrambled.py (cases.CUSTOM_WIDE)."""
+    import cases
+    return {w.name: w for w in (make() for make in cases.CUSTOM_WIDE)}
+
+
 def f2_named_cases():
     """name -> workload: the named workloads of tests/test_gpu_parity.py's row-window tests, as those tests build them."""
     import test_gpu_parity as tp
@@ -223,6 +238,20 @@ def measure(oracle, instances):
         ref = reference(oracle, w)
         for t in range(1, w.T):
             out.append((key, t, slip_sensitivity(ref["P"], t, ref["scrambled"][t][0])))
+    return out
+
+
+def kept_prefix(group, n=None):
+    """{seed: set of periods} of the first seeds of KEPT[group], in ascending order, that together cover at least n (default
+    MIN_KEPT) pairs."""
+    n = MIN_KEPT if n is None else n
+    out, pairs = {}, 0
+    for key, periods in sorted(kept(group).items()):
+        if pairs >= n:
+            break
+        out[key] = periods
+        pairs += len(periods)
+    assert pairs >= n, group
     return out
 
 
@@ -262,6 +291,9 @@ KEPT = {
               ("diag:cfg3_cash_24x700x70x30x3", 1), ("diag:cfg3_cash_24x700x70x30x3", 2), ("diag:f3_dyadic_wide", 1),
               ("diag:f3_dyadic_wide", 2), ("diag:f3_dyadic_wide_min", 1), ("diag:f3_dyadic_wide_min", 2),
               ("diag:f3_dyadic_big_fixed", 1), ("diag:f3_dyadic_big_fixed", 2)],
+    # cases.CUSTOM_WIDE: EVERY period with a future (test_custom_wide_pairs_are_all_sensitive)
+    "custom_wide": [("f3_custom_wide", 1), ("f3_custom_wide", 2), ("f5_custom_wide", 1), ("f5_custom_wide", 2),
+                    ("f6_custom_wide", 1), ("f6_custom_wide", 2)],
 }
 
 # The lead-time family (the row-window kernel): (seed, t) of test_gpu_f2_window_fuzz.make_row_window_instance, (case name, t) of

@@ -45,3 +45,81 @@ def test_create_custom_compiles_without_a_gpu_and_reports_compile_errors(sia):
     d.lead_time = 2
     d.family = 2
     assert lib.sdpgpu_create_custom(C.byref(d), cs.LEADTIME.encode(), prm, 7, C.byref(h)) == 4
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The built-in families restated as user text (tests/custom_sources.py): proved HERE, on the CPU, to be the families -- so that a
+# mismatch of a user-text handle on the GPU (tests/test_gpu_custom_functor.py, tests/test_gpu_custom_scrambled.py) is the engine's
+# ---------------------------------------------------------------------------------------------------------------
+def fuzz_text_instances(family):
+    """[(workload, text, params)]: the seeds test_gpu_fuzz.test_random_instances_bit_exact runs (40; 16 for F5) of the cash
+    families, and of families 1-2 the UNCLAMPED ones (lead time 2 is always clamped there) with the unclamped texts."""
+    import test_gpu_fuzz as fz
+    out = []
+    for seed in range(16 if family == 5 else 40):
+        w = fz.make_instance(family, seed)
+        if family in (1, 2):
+            if w.functor.clampInventory:
+                continue
+            out.append((w, cs.BACKORDER_UNCLAMPED if family == 1 else cs.LEADTIME_UNCLAMPED, _params_backorder(w.functor)))
+        else:
+            out.append((w,) + cs.cash_text(w))
+    return out
+
+
+def variant_counts():
+    """How often the loop variants occur among the cash-family instances of fuzz_text_instances (the ones the GPU parity test
+    compares): (not cashRoundIntDiv, MIN, cashFormula 0, cashFormula 1)."""
+    from stochastic_inventory_amd.states import OptDirection
+    ws = [w for family in (3, 4, 5, 6) for w, _, _ in fuzz_text_instances(family)]
+    return (sum(not w.functor.cashRoundIntDiv for w in ws), sum(w.direction == OptDirection.MIN for w in ws),
+            sum(w.desc().family == 3 and w.functor.cashFormula == 0 for w in ws),
+            sum(w.desc().family == 3 and w.functor.cashFormula == 1 for w in ws))
+
+
+def test_fuzz_seeds_cover_the_loop_variants():
+    """(by the generator: 53 / 11 / 24 / 16)"""
+    no_int_div, minimise, formula0, formula1 = variant_counts()
+    assert no_int_div >= 10 and minimise >= 3 and formula0 >= 5 and formula1 >= 5
+    assert sum(len(fuzz_text_instances(f)) for f in (3, 4, 5, 6)) == 40 + 40 + 16 + 40  # what the GPU parity test compares
+
+
+@pytest.mark.parametrize("family", [1, 2, 3, 4, 5, 6])
+def test_family_texts_restate_the_builtin_families(sia, oracle, family):
+    """Oracle with the text registered == built-in oracle: V, policy, cell count and the memoised recursion's root (value, action,
+    visited states), all exact; and sdpgpu_create_custom compiles the text for the instance's descriptor (hipRTC needs no
+    device).  The fused spelling of every cash text gives the same tables on the first seeds."""
+    lib = sia._abi.load()
+    instances = fuzz_text_instances(family)
+    assert len(instances) >= (4 if family in (1, 2) else 16)
+    for i, (w, text, prm) in enumerate(instances):
+        P = oracle.Problem(w.desc(), w.pmf, w.overhead())
+        V, pol, cells = P.solve(nthreads=4)
+        m = P.memo()
+        spellings = [text] + ([cs.cash_text(w, fused=True)[0]] if family >= 3 and i < 6 else [])
+        for source in spellings:
+            with oracle.custom_functor(source, prm):
+                V2, pol2, cells2 = P.solve(nthreads=4)
+                m2 = P.memo()
+            assert cells == cells2, w.name
+            assert m["value"] == m2["value"] and m["action"] == m2["action"] and m["n"] == m2["n"], w.name
+            for a, b in zip(V + pol, V2 + pol2):
+                assert np.array_equal(a, b), w.name
+            h = C.c_void_p()
+            d = w.desc()
+            arr = (C.c_double * len(prm))(*prm)
+            rc = lib.sdpgpu_create_custom(C.byref(d), source.encode(), arr, len(prm), C.byref(h))
+            assert rc == 0, f"{w.name}: {lib.sdpgpu_last_error(None).decode()}"
+            lib.sdpgpu_destroy(h)
+
+
+def test_nan_texts_compile(sia):
+    """The NaN texts of tests/test_gpu_custom_functor.py compile for a clamped and an unclamped descriptor."""
+    lib = sia._abi.load()
+    for w, text in ((cases.f1_small(), cs.BACKORDER_NAN), (cases.f1_unclamped(), cs.BACKORDER_NAN_UNCLAMPED)):
+        prm = _params_backorder(w.functor) + [3.0, -2.0, 1.0, 5.0, 2.0, 4.0]
+        h = C.c_void_p()
+        d = w.desc()
+        arr = (C.c_double * len(prm))(*prm)
+        assert lib.sdpgpu_create_custom(C.byref(d), text.encode(), arr, len(prm), C.byref(h)) == 0, lib.sdpgpu_last_error(None).decode()
+        lib.sdpgpu_destroy(h)

@@ -7,7 +7,7 @@ import pytest
 
 import cases
 import custom_sources as cs
-from test_custom_functor import _params_backorder
+from test_custom_functor import _params_backorder, fuzz_text_instances
 
 pytestmark = pytest.mark.gpu
 
@@ -146,15 +146,19 @@ def test_mirror_class_over_user_lambdas(sia, oracle):
 def test_compile_modes_give_the_same_tables(sia, oracle, env, monkeypatch):
     """The generated source with the grid and the user's constants baked in and NaN-free arithmetic assumed (the default on a
     clamped grid: `x > c ? c : x` against a non-zero constant becomes one v_min_f64), with NaNs honoured, and with everything
-    read at run time: the same tables, bit for bit, for a built-in family as text and for CashOverdraftLimit's lambdas."""
+    read at run time: the same tables, bit for bit, for a built-in family as text and for CashOverdraftLimit's lambdas -- and for one F5 and
+    one F6 instance as text: the folded three-axis index ((iq * NX + ix) * NC + ic) and the survival arm, baked against not baked."""
     w = cases.f1_clsp_main()
     shape, params, pmf = _overdraft_limit_case(sia)
     desc = shape.to_desc(len(pmf), sia.OptDirection.MAX)
+    more = [cases.f5_cash_leadtime(), cases.f6_survival_gamma()]
+    handles = [(w.desc(), w.pmf, None, cs.BACKORDER, _params_backorder(w.functor)), (desc, pmf, None, cs.OVERDRAFT_LIMIT, params)]
+    handles += [(m.desc(), m.pmf, m.overhead(), *cs.cash_text(m)) for m in more]
 
     def tables():
         out = []
-        for d, pm, src, prm in ((w.desc(), w.pmf, cs.BACKORDER, _params_backorder(w.functor)), (desc, pmf, cs.OVERDRAFT_LIMIT, params)):
-            e = sia.SdpEngine(d, pm, custom_source=src, custom_params=prm)
+        for d, pm, oh, src, prm in handles:
+            e = sia.SdpEngine(d, pm, oh, custom_source=src, custom_params=prm)
             e.solve()
             out.append([(e.values(t).copy(), e.policy(t).copy()) for t in range(1, len(pm) + 1)])
             e.close()
@@ -164,12 +168,16 @@ def test_compile_modes_give_the_same_tables(sia, oracle, env, monkeypatch):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     other = tables()
+    assert len(default) == len(other) == 4
     for a, b in zip(default, other):
+        assert len(a) == len(b) > 0
         for (va, pa), (vb, pb) in zip(a, b):
             assert np.array_equal(va, vb) and np.array_equal(pa, pb)
-    V, pol, _ = oracle.Problem(w.desc(), w.pmf).solve()
-    for t, (va, pa) in enumerate(default[0]):
-        assert np.array_equal(va, V[t]) and np.array_equal(pa, pol[t])
+    for got, m in zip([default[0]] + default[2:], [w] + more):
+        V, pol, _ = oracle.Problem(m.desc(), m.pmf, m.overhead()).solve()
+        assert len(got) == len(V)
+        for t, (va, pa) in enumerate(got):
+            assert np.array_equal(va, V[t]) and np.array_equal(pa, pol[t]), m.name
 
 
 def test_transition_that_leaves_the_grid_is_reported(sia):
@@ -184,23 +192,29 @@ def test_transition_that_leaves_the_grid_is_reported(sia):
 
 def test_random_instances_as_user_text(sia, oracle):
     """Seeded random backorder / lead-time instances (tests/test_gpu_fuzz.py) restated as user text: the hipRTC path
-    must give the oracle's tables whatever the parameters, the direction and the PMF support look like."""
+    must give the oracle's tables whatever the parameters, the direction and the PMF support look like.  Unclamped seeds run the
+    unclamped texts: per-period grids grown from the initial state, nothing baked, P.cur != P.next in c_next_index."""
     import test_gpu_fuzz as tf
-    done = 0
-    for family, src in ((1, cs.BACKORDER), (2, cs.LEADTIME)):
+    done = unclamped = 0
+    for family, src, loose in ((1, cs.BACKORDER, cs.BACKORDER_UNCLAMPED), (2, cs.LEADTIME, cs.LEADTIME_UNCLAMPED)):
         for seed in range(24):
             w = tf.make_instance(family, seed)
             f = w.functor
-            if not f.clampInventory or getattr(f, "leadTime", 1) != 1:
-                continue  # the two texts above clamp; the pipeline shape is built in
-            eng = sia.SdpEngine(w.desc(), w.pmf, custom_source=src, custom_params=_params_backorder(f))
+            if getattr(f, "leadTime", 1) != 1:
+                continue  # the pipeline shape is built in: sdpgpu_create_custom refuses lead time 2
+            if not f.clampInventory:
+                src_, unclamped = loose, unclamped + 1
+            else:
+                src_ = src
+            eng = sia.SdpEngine(w.desc(), w.pmf, custom_source=src_, custom_params=_params_backorder(f))
             eng.solve()
             V, pol, cells = oracle.Problem(w.desc(), w.pmf).solve()
             _tables_equal(eng, V, pol, w.name)
             assert eng.stats().cells_evaluated == cells
             eng.close()
             done += 1
-    assert done >= 20
+    # by the generator: 48 seeds, 11 of them lead time 2, 14 unclamped -- the old bound of 20 clamped instances plus those 14
+    assert unclamped == 14 and done == 37 and done >= 20 + 14
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -300,3 +314,119 @@ def test_level_shape_needs_the_backorder_family(sia):
     from stochastic_inventory_amd import workloads
     with pytest.raises(sia.SdpgpuError, match="SDP_SHAPE_LEVEL"):
         sia.SdpEngine(w.desc(), w.pmf, custom_source=workloads.CLSP_LAMBDAS_LEVEL_HIP, custom_params=[1, 1, 1, 1, 0, 0, 0])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The built-in CASH families as user text (tests/custom_sources.py: CASH, OVERDRAFT, CASH_LEADTIME, SURVIVAL).  tests/
+# test_custom_functor.py proves on the CPU that the texts restate the families; a mismatch here is the engine's
+# (csrc/sdp_custom_src.hpp: custom_period_body, c_next_index, c_decode, sdp_custom_reach)
+# ---------------------------------------------------------------------------------------------------------------
+FUZZ_CHUNK = 5  # instances per test case (one hipRTC compile each)
+
+
+def _fuzz_chunks():
+    return [pytest.param(family, first, id=f"f{family}-seeds-{first}-{min(first + FUZZ_CHUNK, 16 if family == 5 else 40) - 1}")
+            for family in (3, 4, 5, 6) for first in range(0, 16 if family == 5 else 40, FUZZ_CHUNK)]
+
+
+@pytest.mark.parametrize("family,first", _fuzz_chunks())
+def test_cash_family_fuzz_instances_as_user_text(sia, oracle, family, first):
+    """The seeds of test_gpu_fuzz.test_random_instances_bit_exact, families 3-6: user-text handle == built-in handle (automatic
+    kernel) == oracle, per period: values, policy and the reachable set; the cell counts of the three as well.  Among them
+    (counted on the CPU: tests/test_custom_functor.py::test_fuzz_seeds_cover_the_loop_variants) are
+    the `!SDP_CASH_INT_DIV` branch (tenths and halves in doubles), a cash shape under MIN, both F3 formulas, the three-axis index
+    of F5 and both arms of the survival loop with the `nc < 0` skip of sdp_custom_reach."""
+    for w, text, prm in fuzz_text_instances(family)[first:first + FUZZ_CHUNK]:
+        P = oracle.Problem(w.desc(), w.pmf, w.overhead())
+        V, pol, cells = P.solve(nthreads=4)
+        reach = P.reachable()
+        with sia.SdpEngine(w.desc(), w.pmf, w.overhead(), custom_source=text, custom_params=prm) as eng, \
+                sia.SdpEngine(w.desc(), w.pmf, w.overhead()) as builtin:
+            eng.solve()
+            builtin.solve()
+            assert eng.stats().kernel_used == 1, w.name
+            assert eng.stats().cells_evaluated == builtin.stats().cells_evaluated == cells, w.name
+            for t in range(1, w.T + 1):
+                gv, gp, gr = eng.values(t), eng.policy(t), eng.reachable(t)
+                assert np.array_equal(gp, builtin.policy(t)) and np.array_equal(gv, builtin.values(t)), f"{w.name} t={t}: built-in handle"
+                assert np.array_equal(gp, pol[t - 1]) and np.array_equal(gv, V[t - 1]), f"{w.name} t={t}: oracle"
+                assert np.array_equal(gr, builtin.reachable(t)) and np.array_equal(gr, reach[t - 1]), f"{w.name} t={t}: reachable"
+
+
+@pytest.mark.parametrize("make", [cases.f3_tenths, cases.f4_overdraft, cases.f5_cash_leadtime, cases.f6_survival_gamma],
+                         ids=lambda m: m.__name__)
+def test_cash_family_texts_off_grid_and_fused(sia, oracle, make):
+    """One instance per family: sdpgpu_eval_states on balances between the grid's keys (+0.37) against the built-in oracle's
+    eval_states, and the fused SDP_USER_CELL spelling of the text against the three-function spelling."""
+    w = make()
+    text, prm = cs.cash_text(w)
+    fused, _ = cs.cash_text(w, fused=True)
+    P = oracle.Problem(w.desc(), w.pmf, w.overhead())
+    V, pol, cells = P.solve(nthreads=4)
+    with sia.SdpEngine(w.desc(), w.pmf, w.overhead(), custom_source=text, custom_params=prm) as eng, \
+            sia.SdpEngine(w.desc(), w.pmf, w.overhead(), custom_source=fused, custom_params=prm) as one:
+        eng.solve()
+        one.solve()
+        _tables_equal(eng, V, pol, f"{w.name} as text")
+        for t in range(1, w.T + 1):
+            assert np.array_equal(one.values(t), eng.values(t)) and np.array_equal(one.policy(t), eng.policy(t)), f"{w.name} fused t={t}"
+        assert eng.stats().cells_evaluated == one.stats().cells_evaluated == cells
+        for period in sorted({1, 2, w.T}):
+            xs, cash, preq = P.state_arrays(period)
+            pick = np.arange(0, len(xs), 53)
+            kw = dict(cash=cash[pick] + 0.37)
+            if w.desc().family == 5:
+                kw["preq"] = preq[pick]
+            ov, oa = P.eval_states(period, V[period] if period < w.T else None, xs[pick], **kw)
+            for e in (eng, one):
+                gv, ga = e.eval_states(period, xs[pick], **kw)
+                assert np.array_equal(gv, ov) and np.array_equal(ga, oa), f"{w.name}: off-grid balances, period {period}"
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# A lambda that yields NaN, where include/sdpgpu.h promises Java's answer: with NaNs honoured (SDPGPU_CUSTOM_NNAN=0) and on every
+# grid that is not baked.  Java: every comparison with NaN is false, so the action is skipped; +-Double.MAX_VALUE and action 0
+# stay if nothing improves (Recursion.java:129-161).  The default baked mode is unspecified: nothing is asserted about it.
+# ---------------------------------------------------------------------------------------------------------------
+DBL_MAX = 1.7976931348623157e308
+
+
+def _nan_case(oracle, w):
+    """Parameters of cs.BACKORDER_NAN for workload w, from the grid of its LAST period: (a) order 1 * step everywhere, (b) a band
+    of four inventory levels a third of the way up, (c) one (state, order, demand) cell near the top."""
+    P = oracle.Problem(w.desc(), w.pmf)
+    xs = P.state_arrays(w.T)[0]
+    band = (float(xs[len(xs) // 3]), float(xs[len(xs) // 3 + 3]))
+    cell = (float(xs[-3]), 2.0 * w.functor.stepSize, float(np.asarray(w.pmf[-1])[1, 0]))
+    return P, _params_backorder(w.functor) + [1.0 * w.functor.stepSize, band[0], band[1], *cell], band
+
+
+def _run_nan(sia, oracle, w, text):
+    P, prm, band = _nan_case(oracle, w)
+    with oracle.custom_functor(text, prm):
+        V, pol, cells = P.solve()
+    xs = P.state_arrays(w.T)[0]
+    inside = (xs >= band[0]) & (xs <= band[1])
+    worst = -DBL_MAX if w.direction == sia.OptDirection.MAX else DBL_MAX
+    assert inside.sum() == 4 and np.all(V[-1][inside] == worst) and np.all(pol[-1][inside] == 0)  # (the oracle itself)
+    assert np.all(np.abs(V[-1][~inside]) < 1e6) and not any(np.isnan(v).any() for v in V)
+    with sia.SdpEngine(w.desc(), w.pmf, custom_source=text, custom_params=prm) as eng:
+        eng.solve()
+        assert eng.stats().kernel_used == 1 and eng.stats().cells_evaluated == cells
+        gv, gp = eng.values(w.T), eng.policy(w.T)
+        assert np.all(gv[inside] == worst) and np.all(gp[inside] == 0), f"{w.name}: the band of period T"
+        for t in range(1, w.T + 1):  # (what +-MAX_VALUE turns into in the earlier periods is whatever the oracle gets)
+            assert np.array_equal(eng.policy(t), pol[t - 1]), f"{w.name} t={t}: policy"
+            assert np.array_equal(eng.values(t), V[t - 1]), f"{w.name} t={t}: values"
+
+
+@pytest.mark.parametrize("make", [cases.f1_small, cases.f1_max], ids=["MIN", "MAX"])
+def test_nan_lambda_with_nans_honoured(sia, oracle, make, monkeypatch):
+    """SDPGPU_CUSTOM_NNAN=0 on a clamped (baked) grid, both directions: every table equals the oracle running the same text."""
+    monkeypatch.setenv("SDPGPU_CUSTOM_NNAN", "0")
+    _run_nan(sia, oracle, make(), cs.BACKORDER_NAN)
+
+
+def test_nan_lambda_on_a_grid_that_is_not_baked(sia, oracle):
+    """The unclamped text on an unclamped grid (per-period boxes: nothing is baked, NaNs are honoured by default)."""
+    _run_nan(sia, oracle, cases.f1_unclamped(), cs.BACKORDER_NAN_UNCLAMPED)

@@ -48,6 +48,62 @@ def test_kept_pairs_are_the_sensitive_ones(oracle):
         assert np.median(sens) >= scrambled.MIN_MEDIAN, group
 
 
+def test_custom_wide_pairs_are_all_sensitive(oracle):
+    """The three large-state instances of the user-text tests (cases.CUSTOM_WIDE): sensitivity is a CONDITION of those tests, so
+    here no table may be dropped -- every period with a future is in scrambled.KEPT["custom_wide"], at or above THRESHOLD on the
+    oracle alone, with the generators' median bound.  (Three named instances of three periods: six tables, so the generators'
+    MIN_KEPT of 8 tables per generator has no meaning here; nothing may be dropped instead of one third.)
+
+    Measured: f3_custom_wide 1.000 / 0.998, f5_custom_wide 1.000 / 1.000, f6_custom_wide 0.985 / 0.984."""
+    instances = list(scrambled.custom_wide_cases().items())
+    for key, w in instances:
+        P = scrambled.reference(oracle, w)["P"]
+        for t in range(1, w.T + 1):
+            assert scrambled.row_length(P, t) == P.grids[t - 1].nc, f"{w.name} t={t}"
+    m = scrambled.measure(oracle, instances)
+    for k, t, s in m:
+        print(f"{k} t={t}: {s:.3f}")
+    assert [(k, t) for k, t, s in m if s >= scrambled.THRESHOLD] == scrambled.KEPT["custom_wide"]
+    assert len(m) == len(scrambled.KEPT["custom_wide"]) == sum(w.T - 1 for _, w in instances)
+    assert np.median([s for _, _, s in m]) >= scrambled.MIN_MEDIAN
+
+
+def test_custom_wide_instances_have_the_shape_the_launch_forms_need(oracle):
+    """What makes cases.CUSTOM_WIDE exercise the three forms of the user-text period kernel, from the oracle's layout alone: the
+    thresholds tests/test_gpu_custom_scrambled.py quotes are the launcher's, the slab counts it runs fall in the bands it names,
+    and the instances are small in cost, ragged against every tile and state-dependent in their action lists."""
+    import os
+    import test_gpu_custom_scrambled as tcs
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "stochastic-inventory_amd", "csrc", "sdpgpu_generic.hip")) as f:
+        assert tcs.FORM_LINE in f.read()
+    seen = set()
+    for make in cases.CUSTOM_WIDE:
+        w = make()
+        d = w.desc()
+        ref = scrambled.reference(oracle, w)
+        P = ref["P"]
+        S = P.S[0]
+        assert 2 <= w.T <= 3 and all(len(t) <= 4 for t in w.pmf) and all(s == S for s in P.S)
+        assert S % 64 != 0 and P.grids[0].k_lo < 0 and d.min_cash < 0
+        most = int(d.max_order_quantity) + 1  # the longest action list
+        assert most < 16 and most % 4 != 0 and most - 1 <= 6
+        # feasible counts of period 1, state by state: cells / demand points
+        first = P.period(1, ref["V"][1], lo=0, hi=1)[2] // len(w.pmf[0])
+        whole = P.period(1, ref["V"][1], nthreads=8)[2] // len(w.pmf[0])
+        if d.family != 5:
+            assert first == 1 and S < whole < most * S, w.name  # 1 action at the lowest balance: the cash bound binds in part
+        else:  # (F5's list is the same in every state, SingleProductLeadtime.java:72-77; 1 action in the last period)
+            assert whole == most * S and P.period(w.T, None, nthreads=8)[2] == S * len(w.pmf[-1])
+        for world, form in tcs.WIDE_WORLDS[w.name].items():
+            padded = (S + world - 1) // world * world
+            assert tcs._form(padded // world) == form and tcs._form(S - (world - 1) * (padded // world)) == form, (w.name, world)
+            seen.add(form)
+    assert seen == {64, 16, 4}
+    assert set(tcs.WIDE_WORLDS["f3_custom_wide"].values()) == set(tcs.WIDE_WORLDS["f5_custom_wide"].values()) == {64, 16, 4}
+    assert tcs.SX16_FROM <= scrambled.reference(oracle, cases.f6_custom_wide())["P"].S[0] < tcs.SX64_FROM
+
+
 def test_solved_large_magnitude_tables_cannot_see_a_slipped_key(oracle):
     """Why the scrambled tests exist: on the tables the recursion itself produces for make_large_magnitude_cash_instance(0..7),
     a slip of one key in every gather changes at most 5 % of the states of any period (measured: none).  If a change of the
