@@ -142,7 +142,18 @@ typedef enum sdpgpu_direction { SDPGPU_MIN = 0, SDPGPU_MAX = 1 } sdpgpu_directio
                                      x + preQ only (SingleProductLeadtime.java:82-119), so every row of a level holds the same
                                      tables: one representative row per level through the cash row kernel, cell by cell in the
                                      reference's order, then one copy per state -- (nx + nq - 1) rows evaluated instead of
-                                     nx nq.  EXACT; one rank only. */
+                                     nx nq.  EXACT; one rank only.
+                                     STAFF (workforce): the lambdas read x and a through the hire-up-to level y = x + a only, so
+                                     Q_t(x, a) = c(a) P_t(y) + G_t(y), c(a) = (a > 0 ? fixCost : 0) + unitVariCost a,
+                                     G_t(y) = sum_{j < len(row)} p_row(j) w_t(y - j) + p_row(j) V_{t+1}(clamp(y - j)),
+                                     row = min(y, rows - 1), w_t(n) = salary n + (n > minStaff_t ? 0 : unitPenalty (minStaff_t - n)),
+                                     P_t(y) = the row's weights added in ascending j from 0.0: one serial sum per level and a
+                                     scan, sum_levels len + S A steps a period instead of S A D.  REASSOCIATES the reference's
+                                     sum: values within 1e-9 relative of the oracle's, the hire count may differ only where two
+                                     actions tie to that rounding; tables bit-identical to tests/staff_separable_twin.py; an
+                                     instance with fixCost = unitVariCost = salary = 0 is bit-identical to the oracle.  Rank
+                                     slabs: each rank builds the levels its slab reaches.  Every other `kernel` value on a
+                                     STAFF handle keeps the cell-by-cell kernels (reported as SDPGPU_KERNEL_GATHER). */
 
 /*
  * Problem descriptor: everything the reference's lambdas close over.  Field names
@@ -571,9 +582,12 @@ int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out);
  * s = adjacent states per lane (1, 2 for the pair kernel, 2 or 4 for the window kernel); chunks = action groups per state tile;
  * chunk_blocks = trips of a group's action loop (actions per group / r); tiles = state tiles of this slab (64 s states, one
  * state when r = 64), tasks = tiles x chunks = the launch's workgroups; lds_bytes = the window kernel's static LDS, 0 for every
- * other form (which tells the window kernel from the pair kernel at s = 2); workgroups_per_cu = 0. */
+ * other form (which tells the window kernel from the pair kernel at s = 2); workgroups_per_cu = 0.
+ * A STAFF handle with kernel = SDPGPU_KERNEL_SEPARABLE reports that mode's scan launch instead: kernel =
+ * SDPGPU_KERNEL_SEPARABLE, r = s = chunks = 1, chunk_blocks = 0, tiles = tasks = the workgroups of 64 states of this slab,
+ * lds_bytes = their static LDS (the G(y) launch before it has one lane per level and no LDS). */
 typedef struct sdpgpu_plan {
-  int32_t kernel;            /* SDPGPU_KERNEL_WINDOW or SDPGPU_KERNEL_GATHER */
+  int32_t kernel;            /* SDPGPU_KERNEL_WINDOW or SDPGPU_KERNEL_GATHER (STAFF in its opt-in mode: SDPGPU_KERNEL_SEPARABLE) */
   int32_t r, s;              /* register block: actions x adjacent states per lane */
   int32_t chunks;            /* tasks per state tile (1: no chunk rows, no key atomics, no finalize pass) */
   int32_t chunk_blocks;      /* register blocks of the action axis per task; 0: the action-major level kernel, whose

@@ -404,9 +404,13 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
   }
   if (h->d.family == SDPGPU_FAMILY_STAFF) {
     if (part == SDPGPU_PART_INTERIOR) return SDPGPU_OK;  // the footprint spans the whole table (turnover up to all staff)
-    hipError_t es = launch_staff(h, period, v_next, v_cur, pol, p.lo, p.hi, h->stream);
-    if (es != hipSuccess) return fail(h, SDPGPU_ERR_DEVICE, "period %d staff kernel: %s", period, hipGetErrorString(es));
-    p.kernel_used = SDPGPU_KERNEL_GATHER;
+    // OPT-IN separable mode (sdp_staff_sep.hpp): one G(y) row per period and a scan; every other `kernel` value is the
+    // cell-by-cell path
+    const bool sep = h->d.kernel == SDPGPU_KERNEL_SEPARABLE;
+    hipError_t es = sep ? launch_staff_separable(h, period, v_next, v_cur, pol, p.lo, p.hi, h->stream)
+                        : launch_staff(h, period, v_next, v_cur, pol, p.lo, p.hi, h->stream);
+    if (es != hipSuccess) return fail(h, SDPGPU_ERR_DEVICE, "period %d staff kernel%s: %s", period, sep ? " (separable mode)" : "", hipGetErrorString(es));
+    p.kernel_used = sep ? SDPGPU_KERNEL_SEPARABLE : SDPGPU_KERNEL_GATHER;
     if (h->profiling) {
       HIP_TRY(h, hipEventRecord(p.ev1, h->stream));
       p.timed = true;
@@ -480,7 +484,7 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
     return SDPGPU_OK;
   }
   if (h->d.kernel == SDPGPU_KERNEL_SEPARABLE) {
-    if (h->d.family != SDPGPU_FAMILY_BACKORDER) return fail(h, SDPGPU_ERR_UNSUPPORTED, "the separable mode exists for the backorder, lead-time and cash + lead-time families only");
+    if (h->d.family != SDPGPU_FAMILY_BACKORDER) return fail(h, SDPGPU_ERR_UNSUPPORTED, "the separable mode exists for the staff family and for the backorder, lead-time and cash + lead-time families only");
     if (h->n_actions_full > 6000) return fail(h, SDPGPU_ERR_UNSUPPORTED, "separable mode: action range exceeds the LDS tile");
     if (part == SDPGPU_PART_INTERIOR) return SDPGPU_OK;
     bool too_big = false;
@@ -826,6 +830,7 @@ void sdpgpu_destroy(sdpgpu_handle* h) {
   for (void* q : h->staff_owned) (void)hipFree(q);
   if (h->d_staff_val) (void)hipFree(h->d_staff_val);
   if (h->d_staff_idx) (void)hipFree(h->d_staff_idx);
+  if (h->d_staff_g) (void)hipFree(h->d_staff_g);
   for (int32_t* q : h->d_counts)
     if (q) (void)hipFree(q);
   if (h->d_sep_val) (void)hipFree(h->d_sep_val);
@@ -1123,6 +1128,17 @@ int sdpgpu_plan_period(const sdpgpu_handle* hc, int32_t period, sdpgpu_plan* out
   out->kernel = SDPGPU_KERNEL_GATHER;
   if (h->d.family == SDPGPU_FAMILY_STAFF) {  // launch_staff's own plan (kernel stays GATHER, as sdpgpu_stats reports it)
     const PeriodInfo& ps = h->per[period - 1];
+    if (h->d.kernel == SDPGPU_KERNEL_SEPARABLE) {  // launch_staff_separable's own plan: the 64-state workgroups of the min launch
+      const StaffSepPlan sp = plan_staff_separable(h, period, ps.lo, ps.hi);
+      out->kernel = SDPGPU_KERNEL_SEPARABLE;
+      out->r = 1;
+      out->s = 1;
+      out->chunks = 1;
+      out->chunk_blocks = 0;
+      out->tiles = out->tasks = (int32_t)std::min<int64_t>(sp.tiles, 2147483647LL);
+      out->lds_bytes = (int64_t)sp.lds;
+      return SDPGPU_OK;
+    }
     const StaffPlan sp = plan_staff(h, period, ps.lo, ps.hi);
     out->r = sp.r;
     out->s = sp.s;

@@ -98,6 +98,15 @@ struct StaffPlan {
   size_t lds = 0;         // static LDS of the window form (sdp::staff_window_lds_bytes), 0 otherwise
 };
 
+// the separable mode of the staff family (plan_staff_separable): two launches, the rows G and P over the slab's levels
+// (staff_g_kernel, one lane per level) and the scan of 64-state workgroups over them (staff_sep_min_kernel)
+struct StaffSepPlan {
+  int64_t levels = 0;     // hire-up-to levels the slab reaches: states + actions - 1
+  int64_t g_blocks = 0;   // workgroups of 64 levels of the G launch
+  int64_t tiles = 0;      // workgroups of 64 states of the min launch
+  size_t lds = 0;         // static LDS of the min launch (sdp::kStaffSepMinLds)
+};
+
 // plan_window's answer for one period, kept per (slab, forced block): the search walks 8 block shapes x up to blocks_total
 // chunk counts on the issuing thread, and launch_window, run_period_impl's pre-check and sdpgpu_plan_period all ask for it
 // (at 30 us per period the second search sat on the critical path).  Dropped by layout().
@@ -263,6 +272,8 @@ struct sdpgpu_handle {
   double* d_staff_val = nullptr;    // partial arg-min rows [group][slab]
   int32_t* d_staff_idx = nullptr;
   size_t staff_part_elems = 0;
+  double* d_staff_g = nullptr;      // separable mode: the rows G and P over the levels a slab reaches, [2][levels], grown on demand
+  size_t staff_g_elems = 0;
   // kernel-form switches, read at create time (staff_read_switches): SDPGPU_STAFF_R (register block of staff_block_kernel, 4 | 8),
   // _BLOCK=0 (staff_period_kernel, one action at a time), _PAIR (-1 unset: two states per lane where it pays, 0: never, 1: any
   // other value, wherever it can run), _WIN (-1 unset: by the staff range's size, else the value given: 2 | 4 states per lane,
@@ -423,6 +434,9 @@ hipError_t launch_simulate(sdpgpu_handle* h, const sdp::SimPeriod* d_per, const 
 int staff_upload(sdpgpu_handle* h);
 void staff_read_switches(sdpgpu_handle* h);  // the SDPGPU_STAFF_* switches, once per handle (sdpgpu_create)
 StaffPlan plan_staff(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi);
+StaffSepPlan plan_staff_separable(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi);
+hipError_t launch_staff_separable(sdpgpu_handle* h, int period, const double* v_next, double* v_cur, int32_t* pol, int64_t lo,
+                                  int64_t hi, hipStream_t st);
 hipError_t launch_staff(sdpgpu_handle* h, int period, const double* v_next, double* v_cur, int32_t* pol, int64_t lo,
                         int64_t hi, hipStream_t st);
 int64_t staff_cells(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi);

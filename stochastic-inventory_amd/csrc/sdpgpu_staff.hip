@@ -2,6 +2,7 @@
 // cell counts and the reachable intervals.  Kernels in sdp_staff.hpp.
 #include "sdpgpu_internal.hpp"
 #include "sdp_staff.hpp"
+#include "sdp_staff_sep.hpp"
 
 namespace sdpgpu_detail {
 
@@ -227,6 +228,75 @@ hipError_t launch_staff(sdpgpu_handle* h, int period, const double* v_next, doub
   if (e != hipSuccess || part_rows == 1) return e;
   hipLaunchKernelGGL(sdp::combine_staff_kernel, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, st, out_val,
                      out_idx, part_rows, S.part_stride, v_cur, pol, lo, hi);
+  return hipGetLastError();
+}
+
+// The separable mode's two launches for the states [lo, hi) of a period: host arithmetic only, for launch_staff_separable and
+// sdpgpu_plan_period.
+StaffSepPlan plan_staff_separable(const sdpgpu_handle* h, int period, int64_t lo, int64_t hi) {
+  (void)period;
+  StaffSepPlan pl;
+  if (hi <= lo) return pl;
+  pl.levels = (hi - lo) + (int64_t)h->n_actions_full - 1;
+  pl.g_blocks = (pl.levels + 63) / 64;
+  pl.tiles = (hi - lo + 63) / 64;
+  pl.lds = sdp::kStaffSepMinLds;
+  return pl;
+}
+
+// OPT-IN separable mode (sdp_staff_sep.hpp): the rows G and P over the levels this slab reaches, then the scan of the slab.
+// A rank builds the levels of its own slab only; both launches go to the handle's stream, the second behind the first.
+hipError_t launch_staff_separable(sdpgpu_handle* h, int period, const double* v_next, double* v_cur, int32_t* pol, int64_t lo,
+                                  int64_t hi, hipStream_t st) {
+  if (hi <= lo) return hipSuccess;
+  const PeriodInfo& p = h->per[period - 1];
+  const sdpgpu_desc& d = h->d;
+  const StaffSepPlan pl = plan_staff_separable(h, period, lo, hi);
+  // (levels and staff numbers are 32-bit in the kernels, the grids one-dimensional)
+  if (pl.levels >= 2147483647LL || (int64_t)p.g.x_lo + lo + pl.levels >= 2147483647LL || pl.tiles >= 2147483647LL) return hipErrorInvalidValue;
+  // (staff_g_kernel addresses the table and V_{t+1} by 32-bit byte offsets from scalar bases, as the pair kernel does)
+  if ((int64_t)h->lvl_rows[period - 1] * h->lvl_maxj[period - 1] * 8 >= 2147483647LL ||
+      (period < h->T && (int64_t)h->per[period].g.nx * 8 >= 2147483647LL))
+    return hipErrorInvalidValue;
+  sdp::StaffParams S{};
+  S.K = d.fixed_order_cost;
+  S.v = d.unit_order_cost;
+  S.salary = d.holding_cost;
+  S.pen = d.penalty_cost;
+  S.min_staff = (int32_t)p.overhead;
+  S.n_actions = h->n_actions_full;
+  S.n_rows = h->lvl_rows[period - 1];
+  S.clamp = d.clamp_inventory;
+  S.min_x = (int32_t)d.min_inventory;
+  S.max_x = (int32_t)d.max_inventory;
+  S.x_lo = (int32_t)p.g.x_lo;
+  staff_next_bounds(h, period, &S.next_x_lo, &S.nn_lo, &S.nn_hi);
+  S.n_groups = 1;
+  S.group_actions = S.n_actions;
+  const size_t need = 2 * (size_t)pl.levels;
+  if (need > h->staff_g_elems) {
+    if (h->d_staff_g) (void)hipFree(h->d_staff_g);
+    h->d_staff_g = nullptr;
+    h->staff_g_elems = 0;
+    hipError_t e = hipStreamSynchronize(st);  // an earlier period may still be reading the old rows
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_staff_g, need * sizeof(double));
+    if (e != hipSuccess) return e;
+    h->staff_g_elems = need;
+  }
+  double* g_row = h->d_staff_g;
+  double* p_row = h->d_staff_g + pl.levels;
+  const double* pT = h->d_lvl_p[period - 1];
+  const int32_t* len = h->d_lvl_len[period - 1];
+  const int y0 = (int)((int64_t)p.g.x_lo + lo);
+  if (period < h->T)
+    hipLaunchKernelGGL((sdp::staff_g_kernel<true>), dim3((unsigned)pl.g_blocks), dim3(64), 0, st, S, pT, len, v_next, g_row, p_row,
+                       y0, (int)pl.levels);
+  else
+    hipLaunchKernelGGL((sdp::staff_g_kernel<false>), dim3((unsigned)pl.g_blocks), dim3(64), 0, st, S, pT, len, v_next, g_row, p_row,
+                       y0, (int)pl.levels);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sdp::staff_sep_min_kernel, dim3((unsigned)pl.tiles), dim3(256), 0, st, S, g_row, p_row, v_cur, pol, lo, hi);
   return hipGetLastError();
 }
 

@@ -125,7 +125,10 @@ class StaffRecursion:
 
     def __init__(self, getFeasibleAction: Optional[Callable] = None, stateTransition: Optional[Callable] = None,
                  immediateValue: Optional[Callable] = None, pmf=None, T: Optional[int] = None, *,
-                 functor: Optional[StaffFunctor] = None, device: int = -1):
+                 functor: Optional[StaffFunctor] = None, device: int = -1, separable: bool = False):
+        """separable: opt into SDPGPU_KERNEL_SEPARABLE (one G(y) row per period instead of every (state, hire, turnover)
+        cell): values within 1e-9 relative of the cell-by-cell tables, the hire count may differ where two actions tie to
+        that rounding (include/sdpgpu.h)."""
         if functor is None:
             raise TypeError("a StaffFunctor descriptor is required: the GPU engine evaluates closed-form lambda families")
         if pmf is None:
@@ -141,6 +144,8 @@ class StaffRecursion:
         self.immediateValue = immediateValue or functor.immediateValue
         desc = functor.to_desc(self.T)
         desc.device = device
+        if separable:
+            desc.kernel = _abi.KERNEL_SEPARABLE
         self._engine = SdpEngine(desc, None, [float(m) for m in functor.minStaffNum], level_pmf=table,
                                  level_row_len=row_len)
         self._solved = False
