@@ -722,6 +722,22 @@ int sdpgpu_f1_screen_get(sdpgpu_handle* h, int32_t period, int64_t out[6]);
  * level kernel's levels per block) whose leading steps, on the unit-stride layout of the demands, carry at most 2^-16 of the
  * probability (SDPGPU_F1_SCREEN_LOG2=<e> at create time, a diagnostic: 2^-e); 0 below 8.  Whether a launch uses it is decided at the launch.  -1: bad arguments or no layout. */
 int32_t sdpgpu_f1_screen_start(sdpgpu_handle* h, int32_t period);
+/* Additive to ABI 6: the screen rows of the F1 level kernel.  A screened pass proves cells beaten, nothing else;
+ * under the cut-off's gate the sums of one lane and one level are non-decreasing in the action, so it walks RS of the block's R = 4
+ * action rows and holds each row's sum against the thresholds of all the rows it stands for.  SDPGPU_F1_SCREEN_ROWS=<1|2|4> at
+ * create time chooses RS (unset: 2; 4: every row, the kernel without the collapse; anything else: SDPGPU_ERR_ARG from
+ * sdpgpu_create, with a reason).  No table depends on it.  For period t of the last solve: out[0] = the demand steps its waves
+ * walked in screened passes, stopped or failed (part of sdpgpu_f1_screen_get's out[4]; 0 where the screen was off or the level
+ * kernel's cut-off did not run), out[1] = RS of the handle.  sdpgpu_stats.fp64_ops_executed prices those steps at the RS rows
+ * that ran.  Waits for the handle's stream, as sdpgpu_f1_screen_get does. */
+int sdpgpu_f1_screen_rows_get(sdpgpu_handle* h, int32_t period, int64_t out[2]);
+/* Host arithmetic, no handle: the executed fp64 operations per nominal cell that sdpgpu_stats_get charges a level period which
+ * counted its steps -- ops_cell for each of the (steps_run - steps_screened) exact steps; for a screened step the
+ * screen_rows * levels * (3 with a future term, 2 without) + screen_rows operations of a lane plus the table's levels / 64
+ * products, over its rows * levels nominal cells (screen_rows = rows: ops_cell); one compare per cell and test -- all in units of
+ * steps_planned.  -1: bad arguments. */
+double sdpgpu_f1_level_ops_model(double ops_cell, int32_t future, int32_t rows, int32_t levels, int32_t screen_rows,
+                                 int64_t steps_planned, int64_t steps_run, int64_t steps_screened, int64_t tests);
 
 /* Additive to ABI 6: the decided split of the F1 level kernel.  Under the cut-off's gate -- MIN, the built-in
  * costs, K, v, h, pi >= 0, every probability >= 0, values of the library's own -- holding for period t and every later

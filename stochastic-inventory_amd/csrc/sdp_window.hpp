@@ -177,10 +177,35 @@ __global__ __launch_bounds__(256) void window_f1_kernel(WinParams W, const doubl
 // stops, no block is screened and the steps are the cut-off's; a run of stopped blocks pays for few failed screens.
 //   The prefetch guess for the next block's first table starts at the step that block is expected to start at.
 //   cut_count[0] counts the steps walked (a failed screen: its own and the exact walk's), cut_count[2..4] the blocks
-// screened and stopped, the screens that failed and the exact walks.
+// screened and stopped, the screens that failed and the exact walks, cut_count[5] the steps walked in screened passes
+// (stopped or failed; part of cut_count[0]).
 //   The host screens where the planner chose this kernel by itself.  Under a forced plan (SDPGPU_WIN_LEVEL=1) it does so
 // only with SDPGPU_F1_SCREEN=1: screen_start is 0 there otherwise and the kernel walks the cut-off's schedule step for
 // step, which the device tests of the cut-off count against a CPU twin.  SDPGPU_F1_SCREEN=0 turns it off everywhere.
+//
+// THE SCREEN ROWS (RS, a divisor of R; the host: SDPGPU_F1_SCREEN_ROWS / kF1ScreenRows, sdpgpu_internal.hpp).  A screened
+// pass proves "beaten" and nothing else, and it does not need all R action rows of a lane for that.  At step j every cell
+// of level y0 + s has the same m = y0 + s - j whatever its action: for one lane and one level the R cells differ in ONE
+// operand, c0[r].  Under the cut-off's gate c0[k] = (a > 0 ? K : 0) + v a with K, v >= 0 and a = k step, step > 0, is
+// non-decreasing in k (fl(v a) and fl(K + .) are monotone), and fl(c0 + M), fl(p x) for p >= 0 and fl(acc + x) are monotone in
+// each operand under round-to-nearest: by induction over the steps, in the reference's order, acc[r'][s] >= acc[r][s]
+// whenever r' >= r -- termwise, in fp64 as executed, no error analysis.  So the sum of row r, started at the same step, is
+// a lower bound of the sums of the rows above it as well, and cell (r', s) is beaten as soon as a LOWER row's sum is strictly
+// greater than cell (r', s)'s OWN threshold.  (Against the lower row's threshold alone it would be wrong: in the ordering
+// region the states of the higher rows, 64 below, have far higher thresholds.)  The gate suffices because it already excludes
+// what would break the order of c0: a c_tab (user tables of the level shape) and custom costs; MAX; negative K or v.
+//   A screened pass of an RS < R instantiation therefore walks RS screen rows: row q stands for rows q G .. (q + 1) G - 1
+// (G = R / RS) and carries the c0 of the lowest live action among them (c0s: the base row; lane 0 of action block 0 skips
+// action 0; a lane whose base row is a padded action has nothing live in the group).  Ring set-up, step loop and the imm
+// hand-over run over RS rows -- the pass is ONE text, sdp_window_level_pass.hpp, included for R and for RS rows: the same
+// operations on the same operands in the same order -- and the test reads the R thresholds of a level as before, compares
+// each covered row's threshold with its screen row's sum and ANDs without a short cut (a NaN compares false and fails the
+// screen).  Where the thresholds U(i) do not fall with the state over the block -- everywhere but the ordering region near
+// level 0 -- that is the test of the row group's hardest cell and stops at the same step.  A screen that fails is walked
+// again exactly with all R rows; the exact pass, the epilogue, the product table, the prefetch slot, the test schedule, the
+// mode rule and stop_at know nothing of RS, and no table can change.  With RS = R the kernel is the one before, instruction
+// for instruction.  A screened step costs RS S 3 + RS fp64 operations per lane (period T: RS S 2 + RS) instead of
+// R S 3 + R: sdpgpu_stats prices cut_count[5] steps so (f1_level_ops_per_cell).
 // ---------------------------------------------------------------------------------------------
 struct LevelParams {
   int32_t band;       // levels per task (a multiple of S)
@@ -209,7 +234,7 @@ __host__ __device__ inline int level_chunks(int n_actions, int band, int n_abloc
   return (n_actions - 1 + band - 1) / band + n_ablocks;
 }
 
-template <int R, int S, bool FUTURE, bool KEYED_IN, bool CUT>
+template <int R, int S, bool FUTURE, bool KEYED_IN, bool CUT, int RS = R>
 __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, LevelParams L, const double* __restrict__ v_next,
                                                               const unsigned long long* __restrict__ k_next,
                                                               double* __restrict__ out_val, int32_t* __restrict__ out_idx,
@@ -218,6 +243,7 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
                                                               const double* __restrict__ u_row,
                                                               unsigned long long* __restrict__ cut_count) {
   constexpr int DB = LevelShape<S>::DB, ROW = LevelShape<S>::ROW, NA = 64 * R;
+  static_assert(RS >= 1 && R % RS == 0 && (CUT || RS == R), "screen rows divide R; only the cut-off screens");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -286,6 +312,13 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
     else
       c0[r] = (a > 0 ? W.K : 0.0) + W.v * a;
   }
+  // SCREEN ROWS: screen row q carries the c0 of the lowest live action of rows q G .. (q + 1) G - 1 -- its base row, except
+  // that lane 0 of action block 0 skips action 0 (a group whose base row is padded has nothing live: any finite c0 will do)
+  [[maybe_unused]] double c0s[RS];
+  if constexpr (RS < R) {
+#pragma unroll
+    for (int q = 0; q < RS; ++q) c0s[q] = q == 0 && kb + lane == 0 ? c0[1] : c0[q * (R / RS)];
+  }
   // CUT: the test schedule (wave-uniform, scalar registers).  A block's first test comes `dec` steps before the step its
   // predecessor stopped at, then one every S steps; a block that passes its first test moves the next block's twice as
   // far down, and after a block that ran to the end the next one is tested once, S steps before the end (a sum only grows,
@@ -295,7 +328,7 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
   // CUT: the screen's mode rule (wave-uniform, scalar registers; THE SCREEN above).  scr_run counts the stopped blocks since
   // the last one that ran to the end or failed its screen; a block is screened when scr_run >= scr_need.
   [[maybe_unused]] int scr_run = 0, scr_need = 1;
-  [[maybe_unused]] unsigned scr_hit = 0, scr_miss = 0, scr_exact = 0;
+  [[maybe_unused]] unsigned scr_hit = 0, scr_miss = 0, scr_exact = 0, scr_steps = 0;
 
   for (int y0 = yb; y0 < ye; y0 += S) {
     // Priority by progress, as in f1_cells: the four waves of a workgroup free its LDS only together, and a plan
@@ -303,7 +336,6 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
     // (the one left behind then runs alone, at 0.6 of the rate, while the slot of the finished one stays empty).
     if (W.prio_fair) prio_by_progress((unsigned)(y0 - yb), (unsigned)(ye - yb));
     double acc[R][S];
-    double imm[R][S];  // ring: at step j, cell s uses imm[r][(s - j) mod S] = c0[r] + M(y0 + s - j)
     [[maybe_unused]] int cut_fail = 0;
     int stop_at = -1;  // CUT: the step the block stopped at
     // CUT: the step this pass over the block starts at -- L.screen_start for a screened block, 0 for an exact one (and for
@@ -311,155 +343,48 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
     [[maybe_unused]] int scr_from = 0;
     if constexpr (CUT) scr_from = scr_run >= scr_need ? L.screen_start : 0;
     [[maybe_unused]] bool again = false;
-    do {
+    // ONE PASS over the block from step j_first is the text of sdp_window_level_pass.hpp.  A collapsed instantiation (RS < R)
+    // walks a screened pass here, over the RS screen rows, and leaves the loop below to the exact walks: the screen stopped
+    // the block (done), or it failed and the block is walked from step 0.  (In front of the loop and not a branch inside it:
+    // there the R S sums of the exact walk stay live through the screened pass, 279 VGPRs and one wave per SIMD.)
+    if constexpr (RS < R) {
+      if (scr_from > 0) {
+        const int j_first = scr_from;
+        double acs[RS][S];
+#define SDP_LEVEL_PASS_ROWS RS
+#define SDP_LEVEL_PASS_C0 c0s
+#define SDP_LEVEL_PASS_ACC acs
+#include "sdp_window_level_pass.hpp"
+#undef SDP_LEVEL_PASS_ROWS
+#undef SDP_LEVEL_PASS_C0
+#undef SDP_LEVEL_PASS_ACC
+        const unsigned walked = (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);
+        cut_steps += walked;
+        scr_steps += walked;
+        if (stop_at >= 0) {
+          ++scr_hit;
+          scr_need = 1;
+        } else {  // the screen has failed, as below
+          ++scr_miss;
+          scr_need = min(2 * scr_need, 8);
+          scr_run = 0;
+          scr_from = 0;
+        }
+      }
+    }
+    if (RS == R || stop_at < 0) do {
       const int j_first = CUT ? scr_from : 0;
-#pragma unroll
-      for (int s = 0; s < S; ++s) {
-        const double ms = window_entry<false, false>(W, nullptr, nullptr, y0 + s - j_first).x;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          acc[r][s] = 0.0;
-          imm[r][s] = c0[r] + ms;
-        }
-      }
-      [[maybe_unused]] int cut_at = max(cut_first, j_first + S);
-      cut_fail = 0;
-      stop_at = -1;
-      // (PF) the step the task's next block is expected to start at: screened if this block stops, as the one before did
-      [[maybe_unused]] int pf_next = 0;
-      if constexpr (CUT && PF) pf_next = pf_stop != INT32_MAX && (j_first > 0 || scr_run + 1 >= scr_need) ? L.screen_start : 0;
-      for (int j0 = j_first; j0 < L.d_pad && stop_at < 0; j0 += DB) {
-        const int nj = min(DB, L.d_pad - j0);
-        // the table of steps j0 .. j0 + nj - 1: lane t forms row t (rows past nj repeat the last step and are not read)
-        __builtin_amdgcn_wave_barrier();
-        const bool fetched = PF && pf_y == y0 && pf_j == j0;  // (wave-uniform)
-        if constexpr (PF) {
-          if (fetched) {
-            // the window goes through a strip at the start of the table region (the table before is dead, and the rows are
-            // written only after every lane has read its S entries)
-            s_row[lane] = level_v_decode<KEYED_IN>(pf_w0);
-            if (lane < DB + S - 1 - 64) s_row[64 + lane] = level_v_decode<KEYED_IN>(pf_w1);
-            __builtin_amdgcn_wave_barrier();
-          }
-        }
-        if (lane < DB) {
-          const int tt = min(lane, nj - 1);
-          const int j = j0 + tt;
-          double p;
-          double* row = s_row + lane * ROW;
-          double vv[S];
-          if (fetched) {
-            p = pf_p;
-#pragma unroll
-            for (int s = 0; s < S; ++s) vv[s] = s_row[DB - 1 - tt + s];
-          } else {
-            p = pmf_p[j];  // (the array ends in kPmfPad zeros: d_pad < D + S stays inside)
-            if constexpr (FUTURE) {
-#pragma unroll
-              for (int s = 0; s < S; ++s) vv[s] = level_v<KEYED_IN>(W, v_next, k_next, y0 + s - j);
-            }
-          }
-          __builtin_amdgcn_wave_barrier();
-          row[0] = p;
-          row[1] = window_entry<false, false>(W, nullptr, nullptr, y0 - j - 1).x;
-          if constexpr (FUTURE) {
-#pragma unroll
-            for (int s = 0; s < S; ++s) row[2 + s] = p * vv[s];
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-        // The inputs of the table expected next, in flight under this table's steps: the block's next table if there is one
-        // and (CUT) the block before got that far -- after a block that ran to the end, a full run -- else the first table
-        // of the task's next block.  A wrong guess costs that table its direct loads and touches nothing else.
-        if constexpr (PF) {
-          bool same = j0 + DB < L.d_pad;
-          if constexpr (CUT) same = same && j0 + DB < pf_stop;
-          if (same || y0 + S < ye) prefetch(same ? y0 : y0 + S, same ? j0 + DB : pf_next);
-        }
-        // Each step reads the NEXT step's row (a broadcast ds_read_b128 per two doubles) before its own 100 fp64
-        // instructions, which then cover the LDS latency; the row past the block's last step lies inside the wave's region
-        // and is not used.
-        constexpr int NQ = FUTURE ? ROW / 2 : 1;
-        double2 nxt[NQ];
-#pragma unroll
-        for (int u = 0; u < NQ; ++u) nxt[u] = reinterpret_cast<const double2*>(s_row)[u];
-#pragma unroll 1
-        for (int t0 = 0; t0 < nj; t0 += S) {
-          if constexpr (CUT) {
-            // (the imm ring is in its canonical rotation here; the slots are the ones the epilogue below updates)
-            if (j0 + t0 >= cut_at) {
-              const int sb = (y0 - yb) - lane + NA - 1;
-              // (`beaten` is a pure conjunction.  With a future term the R thresholds of a level are read together and the
-              // compares ANDed without a short cut -- S LDS round trips per test instead of R S; every slot index lies inside
-              // the wave's slots.  Period T keeps the short cut: the grouped reads cost it the third wave per SIMD, 198 VGPRs.)
-              bool beaten = true;
-#pragma unroll
-              for (int s = 0; s < S; ++s) {
-                if constexpr (FUTURE) {
-                  double th[R];
-#pragma unroll
-                  for (int r = 0; r < R; ++r) th[r] = s_val[sb + s - 64 * r];
-#pragma unroll
-                  for (int r = 0; r < R; ++r) {
-                    const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];  // not a padded action, not action 0
-                    beaten = beaten & (!live | (acc[r][s] > th[r]));
-                  }
-                } else {
-#pragma unroll
-                  for (int r = 0; r < R; ++r) {
-                    const bool live = r == 0 ? (kreal[0] && kb + lane != 0) : kreal[r];
-                    beaten = beaten && (!live || acc[r][s] > s_val[sb + s - 64 * r]);
-                  }
-                }
-              }
-              ++cut_tests;
-              if (__builtin_amdgcn_ballot_w64(!beaten) == 0) {
-                stop_at = j0 + t0;
-                break;
-              }
-              ++cut_fail;
-              cut_at = cut_once ? INT32_MAX : j0 + t0 + S;
-            }
-          }
-          const double* rows = s_row + t0 * ROW;
-#pragma unroll
-          for (int t = 0; t < S; ++t) {
-            double2 cur[NQ];
-#pragma unroll
-            for (int u = 0; u < NQ; ++u) {
-              cur[u] = nxt[u];
-              nxt[u] = reinterpret_cast<const double2*>(rows + (t + 1) * ROW)[u];
-            }
-            // (fences: left to itself the scheduler pulls the next step's products up to the reads and waits on them at once)
-            __builtin_amdgcn_sched_barrier(0);
-            const double2 pm = cur[0];
-            const double p = pm.x;
-            double pv[S];
-            if constexpr (FUTURE) {
-#pragma unroll
-              for (int s = 0; s < S; s += 2) {
-                pv[s] = cur[1 + s / 2].x;
-                if (s + 1 < S) pv[s + 1] = cur[1 + s / 2].y;
-              }
-            }
-#pragma unroll
-            for (int s = 0; s < S; ++s) {
-#pragma unroll
-              for (int r = 0; r < R; ++r) {
-                acc[r][s] += p * imm[r][(s - t + S) % S];
-                if constexpr (FUTURE) acc[r][s] += pv[s];
-              }
-            }
-            // level 0 at step j + 1 takes the slot level S - 1 has just used
-#pragma unroll
-            for (int r = 0; r < R; ++r) imm[r][(2 * S - 1 - t) % S] = c0[r] + pm.y;
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      }
+#define SDP_LEVEL_PASS_ROWS R
+#define SDP_LEVEL_PASS_C0 c0
+#define SDP_LEVEL_PASS_ACC acc
+#include "sdp_window_level_pass.hpp"
+#undef SDP_LEVEL_PASS_ROWS
+#undef SDP_LEVEL_PASS_C0
+#undef SDP_LEVEL_PASS_ACC
       if constexpr (CUT) {
         again = false;
         cut_steps += (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);
+        if (j_first > 0) scr_steps += (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);  // (RS = R: screened here)
         if (j_first == 0) {
           ++scr_exact;
         } else if (stop_at >= 0) {
@@ -536,6 +461,7 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
       if (L.screen_start > 0) {
         atomicAdd(cut_count + 2, (unsigned long long)scr_hit);
         atomicAdd(cut_count + 3, (unsigned long long)scr_miss);
+        atomicAdd(cut_count + 5, (unsigned long long)scr_steps);
       }
       atomicAdd(cut_count + 4, (unsigned long long)scr_exact);
     }

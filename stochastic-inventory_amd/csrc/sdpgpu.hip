@@ -666,6 +666,14 @@ int sdpgpu_create(const sdpgpu_desc* desc, sdpgpu_handle** out) {
     if (const char* e = std::getenv("SDPGPU_F1_CUTOFF")) h->f1_cutoff = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_F1_SCREEN")) h->f1_screen = std::atoi(e) != 0;
     if (const char* e = std::getenv("SDPGPU_F1_DECIDED")) h->f1_decided = std::atoi(e) != 0;
+    if (const char* e = std::getenv("SDPGPU_F1_SCREEN_ROWS")) {
+      const std::string rows(e);
+      if (rows != "1" && rows != "2" && rows != "4") {
+        delete h;
+        return fail(nullptr, SDPGPU_ERR_ARG, "SDPGPU_F1_SCREEN_ROWS=%s: the screen rows of the F1 level kernel are 1, 2 or 4", e);
+      }
+      h->f1_screen_rows = rows[0] - '0';
+    }
     if (const char* e = std::getenv("SDPGPU_F1_SCREEN_LOG2")) {
       const int b = std::atoi(e);
       if (b >= 1 && b <= 1000) h->f1_screen_mass = std::ldexp(1.0, -b);
@@ -1603,20 +1611,23 @@ int sdpgpu_stats_get(sdpgpu_handle* h, sdpgpu_stats* out) {
     if (h->period_done[t]) out->periods_run++;
     // (a level period with the cut-off walks `run` of its planned steps, each at ops_cell operations per cell, makes its
     // tests -- one compare per cell -- and pays the pre-pass; without it, or when the counters cannot be read, all of them)
-    double walked = 1.0, tests = 0.0;
+    double walked = 1.0, ops = p.ops_cell;
     // (a period of the decided split: the level launch walked the cells of its live states alone; the one-action launches
     // over both parts are in pre_ops)
     double lvl_cells = (double)p.cells_rank;
     if (p.lvl_cut && p.dec_c >= 0 && p.hi > p.lo) lvl_cells *= (double)(p.dec_c - p.lo) / (double)(p.hi - p.lo);
     out->f1_level_steps_planned += p.lvl_steps_planned;
     if (p.lvl_cut && cut_read && p.lvl_steps_planned > 0) {
-      out->f1_level_steps_run += (int64_t)cut[(size_t)t * kCutCounters];
-      walked = (double)cut[(size_t)t * kCutCounters] / (double)p.lvl_steps_planned;
-      tests = (double)cut[(size_t)t * kCutCounters + 1] / (double)p.lvl_steps_planned;
+      const unsigned long long* c = cut.data() + (size_t)t * kCutCounters;
+      out->f1_level_steps_run += (int64_t)c[0];
+      walked = (double)c[0] / (double)p.lvl_steps_planned;
+      // (exact steps at ops_cell, the steps of screened passes at the screen rows' count: f1_level_ops_per_cell)
+      ops = f1_level_ops_per_cell(p.ops_cell, p.lvl_future, p.lvl_r, p.lvl_s, h->f1_screen_rows, (double)p.lvl_steps_planned,
+                                  (double)c[0], (double)c[5], (double)c[1]);
     } else {
       out->f1_level_steps_run += p.lvl_steps_planned;
     }
-    out->fp64_ops_executed += lvl_cells * (p.ops_cell * walked + tests) + p.pre_ops;
+    out->fp64_ops_executed += lvl_cells * ops + p.pre_ops;
     out->lds_bytes += lvl_cells * p.lds_cell * walked;
     out->l1_bytes += (double)p.cells_rank * p.l1_cell;
     if (p.ops_cell == 0 && p.cells_rank > 0) modelled = false;
@@ -1732,6 +1743,32 @@ int sdpgpu_f1_screen_get(sdpgpu_handle* h, int32_t period, int64_t out[6]) {
   out[4] = (int64_t)c[0];
   out[5] = p.lvl_steps_planned;
   return SDPGPU_OK;
+}
+
+int sdpgpu_f1_screen_rows_get(sdpgpu_handle* h, int32_t period, int64_t out[2]) {
+  if (!h || !out) return SDPGPU_ERR_ARG;
+  h->err.clear();
+  if (period < 1 || period > h->T) return fail(h, SDPGPU_ERR_ARG, "period %d out of 1..%d", period, h->T);
+  out[0] = 0;
+  out[1] = h->f1_screen_rows;
+  const PeriodInfo& p = h->per[period - 1];
+  if (!(h->allocated && h->d_cut_count && p.lvl_cut)) return SDPGPU_OK;
+  int rc = ensure_device(h);
+  if (rc) return rc;
+  unsigned long long c = 0;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  HIP_TRY(h, hipMemcpy(&c, h->d_cut_count + (size_t)(period - 1) * kCutCounters + 5, sizeof c, hipMemcpyDeviceToHost));
+  out[0] = (int64_t)c;
+  return SDPGPU_OK;
+}
+
+double sdpgpu_f1_level_ops_model(double ops_cell, int32_t future, int32_t rows, int32_t levels, int32_t screen_rows,
+                                 int64_t steps_planned, int64_t steps_run, int64_t steps_screened, int64_t tests) {
+  if (!(ops_cell > 0) || rows < 1 || levels < 1 || screen_rows < 1 || rows % screen_rows || steps_planned < 1 ||
+      steps_screened < 0 || steps_run < steps_screened || tests < 0)
+    return -1;
+  return f1_level_ops_per_cell(ops_cell, future != 0, rows, levels, screen_rows, (double)steps_planned, (double)steps_run,
+                               (double)steps_screened, (double)tests);
 }
 
 }  // extern "C"

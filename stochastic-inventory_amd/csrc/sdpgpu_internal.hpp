@@ -56,7 +56,21 @@ using sdp::Grid;
 // profiles/f1_screen_ab.txt (same failed screens, one more block of S steps skipped than 2^-24); SDPGPU_F1_SCREEN_LOG2=<e>
 // (diagnostic) uses 2^-e.
 constexpr double kF1ScreenMass = 0x1p-16;
-constexpr int kCutCounters = 5;  // per period: steps run, tests made, blocks screened and stopped, screens failed, exact walks
+// per period: steps run, tests made, blocks screened and stopped, screens failed, exact walks, steps of screened passes
+constexpr int kCutCounters = 6;
+// THE SCREEN ROWS of the F1 level kernel (sdp_window.hpp): the action rows RS a screened pass walks, of the block's R = 4.
+// SDPGPU_F1_SCREEN_ROWS=<1|2|4> at create time; 4 is the kernel without the collapse, instruction for instruction.
+constexpr int kF1ScreenRows = 2;
+// Executed fp64 operations per nominal cell of a level period that counted its steps (sdpgpu_stats_get): an exact step costs
+// ops_cell per cell; a screened step walks RS of the R rows -- RS S (3 or 2) + RS operations per lane and the table's S / 64
+// products, spread over the R S nominal cells (RS = R: ops_cell itself) --; a test is one compare per cell.  `screened` of the
+// `steps` walked belong to screened passes; both are in units of `planned`.
+inline double f1_level_ops_per_cell(double ops_cell, bool future, int R, int S, int RS, double planned, double steps,
+                                    double screened, double tests) {
+  const double ops_scr = (RS * S * (future ? 3.0 : 2.0) + RS + (future ? S / 64.0 : 0.0)) / (double)(R * S);
+  const double ratio = RS == R ? 1.0 : ops_scr / ops_cell;
+  return ops_cell * (((steps - screened) + screened * ratio) / planned) + tests / planned;
+}
 constexpr size_t kPmfPad = 16;  // zero-probability tail: demand loop in blocks of R <= 8, one block of prefetch
 
 // register block / chunking of the F1 window kernel for one period (sdpgpu_window.hip)
@@ -152,6 +166,8 @@ struct PeriodInfo {
   int64_t lvl_steps_planned = 0;
   bool lvl_cut = false;
   int32_t lvl_screen_start = 0;  // the step screened level blocks started at in the last launch (0: the screen was off)
+  int32_t lvl_r = 0, lvl_s = 0;  // the level launch's register block (R action rows x S levels per lane)
+  bool lvl_future = false;       // the level launch had a future term
   double pre_ops = 0;  // fp64 operations of the cut-off's pre-pass (Q(i, 0) of every state), in total
   // the decided split of the last launch: its boundary (live states [lo, dec_c), decided [dec_c, hi)) and the live launch's
   // chunk rows; -1: the launch did not split (sdpgpu_f1_decided_get; flush_pending makes two finalize jobs of a split period)
@@ -223,11 +239,13 @@ struct sdpgpu_handle {
   // forced plan, 1 = wherever the cut-off is on, 0 = never.  It never goes beyond the cut-off's gate (f1_cutoff_on).
   int f1_screen = -1;
   double f1_screen_mass = kF1ScreenMass;
+  int f1_screen_rows = kF1ScreenRows;  // SDPGPU_F1_SCREEN_ROWS: action rows of a screened pass (1, 2 or 4 = all)
   // SDPGPU_F1_DECIDED=1: the decided split wherever the level kernel runs with the cut-off; unset or 0: never (opt-in:
   // f1_decided_on, sdpgpu_window.hip)
   int f1_decided = 0;
   // [T][kCutCounters], per period: steps run and tests made by the level kernel's waves, then its level blocks -- screened
-  // and stopped, screens that failed, walked exactly (sdpgpu_f1_screen_get)
+  // and stopped, screens that failed, walked exactly (sdpgpu_f1_screen_get) -- and the steps of its screened passes
+  // (sdpgpu_f1_screen_rows_get)
   unsigned long long* d_cut_count = nullptr;
   int win_level = -1;  // SDPGPU_WIN_LEVEL: 1 = the action-major level kernel wherever it can run, 0 = never, -1 = where it wins
   uint8_t* d_reach = nullptr;      // reachable masks, period t at reach_off[t-1]

@@ -877,20 +877,29 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
     // THE SCREEN (sdp_window.hpp): behind the cut-off's gate and nothing weaker
     L.screen_start = cut && f1_screen_on(h) ? f1_screen_start(h, period, pl.S, h->f1_screen_mass) : 0;
     p.lvl_screen_start = L.screen_start;
-#define SDP_LVL_GO(RR, SS, FU, KI, CU)                                                                                         \
+    p.lvl_r = pl.R;
+    p.lvl_s = pl.S;
+    p.lvl_future = future;
+    // THE SCREEN ROWS (sdp_window.hpp): behind the same gate -- only a launch that screens takes a collapsed instantiation
+    const int screen_rows = L.screen_start > 0 ? h->f1_screen_rows : pl.R;
+#define SDP_LVL_GO(RR, SS, FU, KI, CU, RS)                                                                                     \
   do {                                                                                                                         \
     static LdsMark mark;                                                                                                       \
-    hipError_t ea = lds_allow(sdp::window_f1_level_kernel<RR, SS, FU, KI, CU>, pl.smem, &mark);                                \
+    hipError_t ea = lds_allow(sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS>, pl.smem, &mark);                            \
     if (ea != hipSuccess) return ea;                                                                                           \
-    hipLaunchKernelGGL((sdp::window_f1_level_kernel<RR, SS, FU, KI, CU>), grid, dim3(256), pl.smem, st, W, L, v_next, k_next,  \
-                       out_val, out_idx, k_cur, pmf_p, u_row, cut_count);                                                      \
+    hipLaunchKernelGGL((sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS>), grid, dim3(256), pl.smem, st, W, L, v_next,      \
+                       k_next, out_val, out_idx, k_cur, pmf_p, u_row, cut_count);                                              \
   } while (0)
-#define SDP_LVL_C(RR, SS, FU, KI)       \
-  do {                                  \
-    if (cut)                            \
-      SDP_LVL_GO(RR, SS, FU, KI, true); \
-    else                                \
-      SDP_LVL_GO(RR, SS, FU, KI, false);\
+#define SDP_LVL_C(RR, SS, FU, KI)            \
+  do {                                       \
+    if (cut && screen_rows == 1)             \
+      SDP_LVL_GO(RR, SS, FU, KI, true, 1);   \
+    else if (cut && screen_rows == 2)        \
+      SDP_LVL_GO(RR, SS, FU, KI, true, 2);   \
+    else if (cut)                            \
+      SDP_LVL_GO(RR, SS, FU, KI, true, RR);  \
+    else                                     \
+      SDP_LVL_GO(RR, SS, FU, KI, false, RR); \
   } while (0)
 #define SDP_LVL_R(RR, SS)               \
   if (pl.R == RR && pl.S == SS) {       \

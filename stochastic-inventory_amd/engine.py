@@ -591,6 +591,13 @@ class SdpEngine:
         self._check(self._lib.sdpgpu_f1_screen_get(self._h, period, out))
         return tuple(int(v) for v in out)
 
+    def f1_screen_rows(self, period: int):
+        """The screen rows of the F1 level kernel in `period` of the last solve: (demand steps walked in screened passes, the
+        action rows RS such a pass walks -- SDPGPU_F1_SCREEN_ROWS, of the block's 4)."""
+        out = (C.c_int64 * 2)()
+        self._check(self._lib.sdpgpu_f1_screen_rows_get(self._h, period, out))
+        return tuple(int(v) for v in out)
+
     def f1_screen_start(self, period: int) -> int:
         """Host arithmetic: the step the screen's rule gives for the pmf of `period` (0: no screen)."""
         return int(self._lib.sdpgpu_f1_screen_start(self._h, period))

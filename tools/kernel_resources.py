@@ -49,7 +49,9 @@ def main():
         # (paired by the demangled name: a kernel whose parameter list changed has another mangled one)
         old = {v: k for k, v in demangle(sorted(n for n in a if flt in n)).items()}
         for n in sorted(names, key=names.get):
-            x, y = a[old[names[n]]], b[n]
+            # (a template parameter added at the end, with a default: the kernel without its last argument is the counterpart)
+            was = names[n] if names[n] in old else names[n].rsplit(", ", 1)[0] + ">"
+            x, y = a[old[was]], b[n]
             bad = y["private_segment_fixed_size"] or x["private_segment_fixed_size"] or any(x[k] != y[k] for k in ("v_mul_f64", "v_add_f64"))
             pair = lambda k: f"{x[k]}->{y[k]}"
             print(f"{names[n]:44s} {pair('vgpr_count'):>9s} {waves(x['vgpr_count'])}->{waves(y['vgpr_count']):<3d} {pair('sgpr_count'):>8s} "

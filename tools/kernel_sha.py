@@ -5,7 +5,7 @@ import hashlib
 import os
 
 COMMON = ["sdp_device.hpp", "sdpgpu_internal.hpp"]
-WINDOW = ["sdp_f1_cells.hpp", "sdp_window.hpp", "sdpgpu_window.hip"]   # F1 / F2 window kernels: target, cfg2, cfg4, cfg4p, cfg5
+WINDOW = ["sdp_f1_cells.hpp", "sdp_window.hpp", "sdp_window_level_pass.hpp", "sdpgpu_window.hip"]   # F1 / F2 window kernels: target, cfg2, cfg4, cfg4p, cfg5
 CASH = ["sdp_cash.hpp", "sdpgpu_cash.hip"]         # uniform-shift, diagonal and cash row kernels: cfg3, cfg3t, f5_spl
 STAFF = ["sdp_staff.hpp", "sdpgpu_staff.hip"]      # workforce.StaffRecursion's kernels
 SPARSE = ["sdpgpu_sparse.hip"]                     # the reachable-set engine of the two-product families
