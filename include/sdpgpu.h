@@ -846,6 +846,71 @@ typedef struct sdpgpu_batch_plan {
 } sdpgpu_batch_plan;
 int sdpgpu_batch_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_plan* out);
 
+/* ---- batched workforce solve: many STAFF instances of ONE shape, in the separable mode ------------------------------------
+ * workforce.WorkforceTesting.main (WorkforceTesting.java:36-41) solves 2 x 3 x 3 x 3 x 4 = 216 instances of one shape (T = 8,
+ * hires 0..1000, no clamp, iniStaffNum 0) over two turnover tables; they differ in fixCost, salary, unitPenalty and
+ * minStaffNum[t].  sdpgpu_batch_create accepts SDPGPU_FAMILY_STAFF descriptors: the family of instance 0 selects the kind of
+ * batch, and a batch holds one family.  Period t of ALL instances runs in TWO launches -- the rows G_t(y), P_t(y) of every
+ * instance, then the scan (the separable mode of a STAFF handle, SDPGPU_KERNEL_SEPARABLE) -- and every instance's tables are
+ * bit for bit those of its own separable handle.  Additive to ABI 6.
+ *
+ * Must agree between the n descriptors: family, periods, step (1), min_inventory, max_inventory, max_order_quantity,
+ * clamp_inventory (0 or 1), ini_inventory (the unclamped per-period staff ranges grow from it), device, store_all_values,
+ * world_size (1): a mismatch returns SDPGPU_ERR_ARG and names the instance and the field.  kernel must be
+ * SDPGPU_KERNEL_SEPARABLE on every instance: the batch runs the separable mode only, which is never chosen automatically --
+ * SDPGPU_KERNEL_AUTO or any other value returns SDPGPU_ERR_UNSUPPORTED; the exact cell-by-cell tables come from one handle per
+ * instance.  May differ per instance: fixed_order_cost, unit_order_cost, holding_cost (salary), penalty_cost, minStaffNum[t]
+ * (sdpgpu_batch_set_overhead; default: the descriptor's overhead_cost) and which level table each period uses.
+ * sdpgpu_batch_create_ragged refuses the family.  With clamp_inventory = 0 the staff range of a period depends on the longest
+ * rows of the tables before it: instances whose tables would give different ranges are refused at layout
+ * (SDPGPU_ERR_UNSUPPORTED).
+ *
+ * Level tables live in a POOL owned by the batch -- a handle stores pmfs[t] once per period and instance; the sweep's 216 x 8
+ * tables of 8 MB are two.  sdpgpu_batch_add_level_pmf takes pmfs[t] of StaffRecursion.java:23,92-95 exactly as
+ * sdpgpu_set_level_pmf does (prob[y * row_stride + j], row_len NULL = y + 1 entries in row y; whatever lies behind a row's
+ * length is never read) and returns the table's id; a table of 2 GiB or more is SDPGPU_ERR_UNSUPPORTED.
+ * sdpgpu_batch_use_level_pmf makes period index t (0-based) of `instance` integrate over table `table`; instance = -1: every
+ * instance, t = -1: every period.  sdpgpu_batch_set_overhead sets minStaffNum[t] of one instance (an integer value).  Tables
+ * and overheads are frozen once the device tables exist (SDPGPU_ERR_STATE).
+ *
+ * On a STAFF batch these entry points keep their meaning: sdpgpu_batch_destroy, _last_error, _num_actions, _num_states (the
+ * states of period T: the largest staff range, and every period's when clamped; -1 while an unclamped batch lacks a table it
+ * depends on), _set_stream, _set_profiling, _solve (2 T launches; SDPGPU_ERR_STATE names the first (instance, period) without
+ * a table, before any device call), _synchronize, _values and _policy (n is checked against the states of THAT period:
+ * sdpgpu_batch_grid), _initial (V_1(iniStaffNum) and its hire index), _stats_get (period_launches = 2 T, cells_evaluated = the
+ * sum of what the n separable handles report; finalize_launches, window_r, window_s, window_chunks and lds_bytes are 0),
+ * _period_ms.  Every other sdpgpu_batch_* call returns SDPGPU_ERR_UNSUPPORTED on a STAFF batch, naming the call and the
+ * family, before any device call (sdpgpu_batch_simulate_ms: -1); the three table calls and sdpgpu_batch_staff_plan_period
+ * return the same on a batch of the backorder family.
+ *
+ * sdpgpu_batch_grid: staff number of state index 0 and the number of states of one instance in one period (1-based) -- the
+ * unclamped ranges differ by period.  Host arithmetic; on a backorder batch x_lo = min_inventory of the instance.
+ *
+ * sdpgpu_batch_staff_plan_period: the two launches of one period (1-based), host arithmetic only, available once every
+ * (instance, period) has a table.  The instances are grouped per (period, table); a G task is one wave: 64 consecutive levels
+ * of a block of r instances of one group, which share the probabilities, the row weights P, the staff left and the addresses
+ * of a step, each with its own immediate cost, V_{t+1} and sum.  r comes from the group sizes alone: the instance block where
+ * some group of the period holds at least that many instances, else 1; a group's last block may be short. */
+typedef struct sdpgpu_batch_staff_plan {
+  int32_t tables;            /* distinct tables the period uses ... */
+  int32_t groups;            /* ... = groups of instances */
+  int32_t r;                 /* instances per G task */
+  int32_t u;                 /* steps a lane reads ahead per register set */
+  int32_t longest_row;       /* longest row of the period's tables: steps of the longest G task */
+  int32_t reserved;
+  int64_t blocks;            /* instance blocks: sum over the groups of ceil(size / r) */
+  int64_t g_tasks;           /* waves of the G launch: blocks x ceil(levels / 64) */
+  int64_t scan_workgroups;   /* workgroups of the scan launch: instances x ceil(states / 64) */
+  int64_t levels;            /* hire-up-to levels per instance: states + actions - 1 */
+  int64_t states;            /* states per instance */
+} sdpgpu_batch_staff_plan;
+int sdpgpu_batch_add_level_pmf(sdpgpu_batch* b, const double* prob, const int32_t* row_len, int32_t n_rows, int32_t row_stride,
+                               int32_t* out_table);
+int sdpgpu_batch_use_level_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, int32_t table);
+int sdpgpu_batch_set_overhead(sdpgpu_batch* b, int32_t instance, int32_t t, double min_staff);
+int sdpgpu_batch_grid(sdpgpu_batch* b, int32_t instance, int32_t period, double* x_lo, int64_t* nx);
+int sdpgpu_batch_staff_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_staff_plan* out);
+
 /* ---- batched simulation: roll the policies of ALL instances of a solved batch along demand paths, one launch ------------
  * What CLSPTesting.main does after every solve -- `new Simulation(distributions, 10000, recursion)
  * .simulateSDPGivenSamplNum(initialState)` (CLSPTesting.java:120-124; Simulation.java:53-74) -- for the whole batch.  Per path

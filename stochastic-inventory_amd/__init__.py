@@ -6,8 +6,8 @@ The directory name carries a hyphen (it is fixed by the build contract); import 
 """
 from . import _abi
 from ._abi import (FAMILY_BACKORDER, FAMILY_CASH, FAMILY_CASH_LEADTIME, FAMILY_LEADTIME, FAMILY_OVERDRAFT,
-                   FAMILY_STAFF, FAMILY_SURVIVAL, KERNEL_AUTO, KERNEL_GATHER, KERNEL_WINDOW, SdpgpuBatchPlan, SdpgpuBatchStats, SdpgpuConvexity, SdpgpuDesc, SdpgpuError, SdpgpuStats, desc_defaults)
-from .batch import SdpBatch
+                   FAMILY_STAFF, FAMILY_SURVIVAL, KERNEL_AUTO, KERNEL_GATHER, KERNEL_WINDOW, SdpgpuBatchPlan, SdpgpuBatchStaffPlan, SdpgpuBatchStats, SdpgpuConvexity, SdpgpuDesc, SdpgpuError, SdpgpuStats, desc_defaults)
+from .batch import SdpBatch, StaffBatch
 from .engine import SdpEngine
 from .fitss import FindsSOverDraft, FitsS
 from .functors import (BackorderFunctor, CashFunctor, CashXRFunctor, CashLeadtimeFunctor, CustomFunctor, LeadtimeFunctor, OverdraftFunctor,
@@ -19,7 +19,7 @@ from .pmf import BinomialDist, DiscreteDistribution, GammaDist, GetPmf, NormalDi
 from .recursion import (CLSP, CashLeadtimeRecursion, CashRecursion, CashRecursionXR, LeadtimeRecursion, Recursion, RecursionBatch, RecursionG,
                         RiskRecursion)
 from .simulation import CashSimulation, CashSimulationXR, RiskSimulation, Sampling, SimulateFitsS, Simulation, SimulationBatch
-from .workforce import SimulatesS, StaffFunctor, StaffRecursion, StaffState
+from .workforce import SimulatesS, StaffFunctor, StaffRecursion, StaffRecursionBatch, StaffState
 from .structure import CheckKConvexity
 from .states import CashLeadtimeState, CashState, CashStateXR, LeadtimeState, OptDirection, RiskState, State
 
@@ -27,7 +27,7 @@ __all__ = [
     "SdpEngine", "SdpBatch", "SdpgpuBatchPlan", "SdpgpuBatchStats", "RecursionBatch", "SdpgpuDesc", "SdpgpuError", "SdpgpuStats", "desc_defaults",
     "BackorderFunctor", "LeadtimeFunctor", "CashFunctor", "CashXRFunctor", "OverdraftFunctor", "CashLeadtimeFunctor", "SurvivalFunctor", "CustomFunctor",
     "Recursion", "CLSP", "LeadtimeRecursion", "CashRecursion", "CashRecursionXR", "CashLeadtimeRecursion", "RiskRecursion",
-    "StaffRecursion", "StaffFunctor", "StaffState", "SimulatesS", "BinomialDist", "staff_level_pmf",
+    "StaffRecursion", "StaffRecursionBatch", "StaffBatch", "SdpgpuBatchStaffPlan", "StaffFunctor", "StaffState", "SimulatesS", "BinomialDist", "staff_level_pmf",
     "multilead_solve", "multicash_solve", "multixr_solve", "MultiLeadResult", "Actions", "CashRecursionMulti",
     "CashRecursionMultiLead", "CashRecursionMultiXR", "CashStateMulti", "CashStateMultiLead", "CashStateMultiXR",
     "MultiPolicy", "CashSimulationMulti", "CashSimulationMultiXR",

@@ -135,6 +135,14 @@ class SdpgpuBatchPlan(C.Structure):
                 ("max_chunks", C.c_int32), ("min_chunks", C.c_int32), ("tasks", C.c_int64), ("lds_bytes", C.c_int64)]
 
 
+class SdpgpuBatchStaffPlan(C.Structure):
+    """struct sdpgpu_batch_staff_plan (include/sdpgpu.h)."""
+
+    _fields_ = [("tables", C.c_int32), ("groups", C.c_int32), ("r", C.c_int32), ("u", C.c_int32), ("longest_row", C.c_int32),
+                ("reserved", C.c_int32), ("blocks", C.c_int64), ("g_tasks", C.c_int64), ("scan_workgroups", C.c_int64),
+                ("levels", C.c_int64), ("states", C.c_int64)]
+
+
 class SdpgpuConvexity(C.Structure):
     """struct sdpgpu_convexity (include/sdpgpu.h)."""
 
@@ -350,6 +358,11 @@ EXPORTS = {
     "sdpgpu_batch_initial": (C.c_int, [_P, _DP, _IP]),
     "sdpgpu_batch_stats_get": (C.c_int, [_P, C.POINTER(SdpgpuBatchStats)]),
     "sdpgpu_batch_period_ms": (C.c_double, [_P, C.c_int32]),
+    "sdpgpu_batch_add_level_pmf": (C.c_int, [_P, _DP, _IP, C.c_int32, C.c_int32, _IP]),
+    "sdpgpu_batch_use_level_pmf": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32]),
+    "sdpgpu_batch_set_overhead": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double]),
+    "sdpgpu_batch_grid": (C.c_int, [_P, C.c_int32, C.c_int32, _DP, _LP]),
+    "sdpgpu_batch_staff_plan_period": (C.c_int, [_P, C.c_int32, C.POINTER(SdpgpuBatchStaffPlan)]),
     "sdpgpu_batch_simulate": (C.c_int, [_P, C.c_int32, _DP, C.c_int64, _DP, _DP, _DP]),
     "sdpgpu_batch_set_sampler": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(SdpgpuDistSpec)]),
     "sdpgpu_batch_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, _DP, _DP, _DP]),

@@ -4,6 +4,9 @@ one kernel launch -- the parameter sweeps of the reference's *Testing mains.  Th
 (ThreeLevelFitsSTest.java:67-77).
 
 `pmfs[i]` is instance i's `double[][][] pmf` (Recursion.java:38): pmfs[i][t][j] = [demand, prob].
+
+`StaffBatch` is the same object for N workforce (STAFF family) instances of one shape in the separable mode
+(WorkforceTesting.java:36-41): a pool of level tables, two launches per period for all instances.
 """
 from __future__ import annotations
 
@@ -13,7 +16,7 @@ from typing import Sequence
 import numpy as np
 
 from . import _abi
-from ._abi import SdpgpuBatchPlan, SdpgpuBatchStats, SdpgpuConvexity, SdpgpuDesc, SdpgpuError
+from ._abi import SdpgpuBatchPlan, SdpgpuBatchStaffPlan, SdpgpuBatchStats, SdpgpuConvexity, SdpgpuDesc, SdpgpuError
 from .engine import _dp, _ip, split_pmf
 
 
@@ -277,3 +280,138 @@ class SdpBatch:
             self._b, int(kind), int(src), int(period), _dp(lo) if lo is not None else None, _dp(hi) if hi is not None else None,
             _dp(k) if k is not None else None, _ip(cap) if cap is not None else None, out.ctypes.data_as(C.POINTER(SdpgpuConvexity))))
         return out
+
+
+class StaffBatch:
+    """N workforce (STAFF family) instances of ONE shape in the separable mode -- the sweep of WorkforceTesting.main
+    (WorkforceTesting.java:36-41): period t of all instances in two kernel launches, every instance's tables bit for bit
+    those of its own separable handle (SdpEngine with kernel = KERNEL_SEPARABLE).
+
+    descs      one STAFF descriptor per instance, kernel = KERNEL_SEPARABLE (StaffFunctor.to_desc)
+    tables     the pool of level tables: a list of (prob[rows, stride], row_len | None)
+    use        use[i][t] = id of the pool table period index t of instance i integrates over
+    min_staff  min_staff[i][t] = minStaffNum[t] of instance i"""
+
+    def __init__(self, descs: Sequence[SdpgpuDesc], tables, use, min_staff, device: int = -1):
+        self._lib = _abi.load()
+        self._b = C.c_void_p()
+        descs = list(descs)
+        if len(use) != len(descs) or len(min_staff) != len(descs):
+            raise ValueError(f"{len(descs)} descriptors but {len(use)} rows of table ids and {len(min_staff)} of minStaffNum")
+        arr = (SdpgpuDesc * max(len(descs), 1))()
+        for i, d in enumerate(descs):
+            C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(SdpgpuDesc))
+            if device >= 0:
+                arr[i].device = device
+        self.n = len(descs)
+        rc = self._lib.sdpgpu_batch_create(arr, self.n, C.byref(self._b))
+        if rc:
+            raise SdpgpuError(rc, self._lib.sdpgpu_batch_last_error(None).decode())
+        self.T = int(arr[0].periods)
+        try:
+            self.table_ids = []
+            for prob, row_len in tables:
+                prob = np.ascontiguousarray(prob, dtype=np.float64)
+                if prob.ndim != 2:
+                    raise ValueError(f"a level table is [rows, stride], got shape {prob.shape}")
+                lens = None if row_len is None else np.ascontiguousarray(row_len, dtype=np.int32)
+                if lens is not None and lens.shape != (prob.shape[0],):
+                    raise ValueError(f"row_len of shape {lens.shape} for a table of {prob.shape[0]} rows")
+                tid = C.c_int32(-1)
+                self._check(self._lib.sdpgpu_batch_add_level_pmf(self._b, _dp(prob), _ip(lens) if lens is not None else None,
+                                                                 prob.shape[0], prob.shape[1], C.byref(tid)))
+                self.table_ids.append(int(tid.value))
+            for i in range(self.n):
+                if len(use[i]) != self.T or len(min_staff[i]) != self.T:
+                    raise ValueError(f"instance {i}: {len(use[i])} table ids and {len(min_staff[i])} minStaffNum for {self.T} periods")
+                row = [int(k) for k in use[i]]
+                if len(set(row)) == 1:
+                    self._check(self._lib.sdpgpu_batch_use_level_pmf(self._b, i, -1, self.table_ids[row[0]]))
+                else:
+                    for t, k in enumerate(row):
+                        self._check(self._lib.sdpgpu_batch_use_level_pmf(self._b, i, t, self.table_ids[k]))
+                for t, m in enumerate(min_staff[i]):
+                    self._check(self._lib.sdpgpu_batch_set_overhead(self._b, i, t, float(m)))
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        if rc:
+            raise SdpgpuError(rc, self._lib.sdpgpu_batch_last_error(self._b).decode())
+
+    def close(self):
+        if getattr(self, "_b", None) is not None and self._b:
+            self._lib.sdpgpu_batch_destroy(self._b)
+            self._b = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return self.n
+
+    def set_stream(self, hip_stream: int):
+        self._check(self._lib.sdpgpu_batch_set_stream(self._b, C.c_void_p(hip_stream)))
+
+    def set_profiling(self, on: bool):
+        self._check(self._lib.sdpgpu_batch_set_profiling(self._b, 1 if on else 0))
+
+    def solve(self, sync: bool = True):
+        self._check(self._lib.sdpgpu_batch_solve(self._b, 1 if sync else 0))
+
+    def synchronize(self):
+        self._check(self._lib.sdpgpu_batch_synchronize(self._b))
+
+    def grid(self, i: int, period: int):
+        """(x_lo, nx): staff number of state index 0 and the number of states of instance i in `period` (1-based)."""
+        x_lo, nx = C.c_double(), C.c_int64()
+        self._check(self._lib.sdpgpu_batch_grid(self._b, i, period, C.byref(x_lo), C.byref(nx)))
+        return float(x_lo.value), int(nx.value)
+
+    def num_actions_of(self, i: int) -> int:
+        n = int(self._lib.sdpgpu_batch_num_actions(self._b, i))
+        if n < 0:
+            raise IndexError(f"instance {i} outside 0 .. {self.n - 1}")
+        return n
+
+    def plan(self, period: int) -> SdpgpuBatchStaffPlan:
+        """The two launches of one period (1-based) for the whole batch: host arithmetic, no device needed."""
+        pl = SdpgpuBatchStaffPlan()
+        self._check(self._lib.sdpgpu_batch_staff_plan_period(self._b, period, C.byref(pl)))
+        return pl
+
+    def values(self, i: int, period: int) -> np.ndarray:
+        out = np.empty(self.grid(i, period)[1], dtype=np.float64)
+        self._check(self._lib.sdpgpu_batch_values(self._b, i, period, _dp(out), len(out)))
+        return out
+
+    def policy(self, i: int, period: int) -> np.ndarray:
+        """Arg-min hire count of every state of the period."""
+        out = np.empty(self.grid(i, period)[1], dtype=np.int32)
+        self._check(self._lib.sdpgpu_batch_policy(self._b, i, period, _ip(out), len(out)))
+        return out
+
+    def initial(self):
+        """(values[n], hires[n]): V_1(iniStaffNum) and its hire count, all instances, one copy."""
+        val = np.empty(self.n, dtype=np.float64)
+        act = np.empty(self.n, dtype=np.int32)
+        self._check(self._lib.sdpgpu_batch_initial(self._b, _dp(val), _ip(act)))
+        return val, act
+
+    def stats(self) -> SdpgpuBatchStats:
+        st = SdpgpuBatchStats()
+        self._check(self._lib.sdpgpu_batch_stats_get(self._b, C.byref(st)))
+        return st
+
+    def period_ms(self, period: int) -> float:
+        return float(self._lib.sdpgpu_batch_period_ms(self._b, period))

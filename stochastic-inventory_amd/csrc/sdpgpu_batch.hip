@@ -5,6 +5,8 @@
 // window_f1_batch_kernel (sdp_batch.hpp); this file holds the validation, the host layout with its prefix-sum arenas, the
 // plan of a period, the task table, the launcher and the entry points.  Separate from sdpgpu_handle on purpose: a batch has no
 // slabs, no exchange, no user functors -- and the handle does not grow.
+// A batch whose instance 0 is of the STAFF family (the workforce sweep in the separable mode) lives in sdpgpu_staffbatch.hip:
+// sdpgpu_batch_create makes it there, and every entry point below forwards to it or refuses by name.
 #include "sdpgpu_sim_host.hpp"
 #include "sdp_batch.hpp"
 #include "sdp_batch_sim.hpp"
@@ -27,6 +29,9 @@ struct BatchPlan {
 struct sdpgpu_batch {
   std::vector<sdpgpu_desc> d;
   int32_t N = 0, T = 0;
+  // instance 0 of the STAFF family: the whole state of the batch lives in sdpgpu_staffbatch.hip, every entry point below forwards
+  // to it or refuses by name; N, T and err are the only other members in use
+  sdpgpu_detail::StaffBatch* staff = nullptr;
   bool ragged = false;             // sdpgpu_batch_create_ragged: bounds and order limit are the instance's own
   std::vector<int32_t> nxs, As;    // [i]: states and actions of instance i
   std::vector<size_t> val_base, pol_base;  // [i]: prefix sums -- instance i's value rows / policy (and key) rows
@@ -101,6 +106,18 @@ int sdpgpu_detail::bfail(sdpgpu_batch* b, int code, const char* fmt, ...) {
 namespace {
 
 using namespace sdpgpu_detail;
+
+// a call without a meaning on a STAFF batch (and the staff calls on a backorder batch): refused by name before anything else
+#define STAFF_REFUSE(b, who)                                                                                                        \
+  if ((b)->staff)                                                                                                                   \
+  return bfail(b, SDPGPU_ERR_UNSUPPORTED, who ": not available on a batch of the staff family (SDPGPU_FAMILY_STAFF), which solves, reads " \
+                                              "its tables and reports its plan (sdpgpu_batch_staff_plan_period)")
+#define STAFF_ONLY(b, who)                                                                                                          \
+  if (!(b)->staff)                                                                                                                  \
+  return bfail(b, SDPGPU_ERR_UNSUPPORTED, who ": the batch is of the backorder family (SDPGPU_FAMILY_BACKORDER); this call belongs to a " \
+                                              "batch of the staff family")
+#define STAFF_FORWARD(b, who, call) \
+  if ((b)->staff) return guarded(b, who, [&]() -> int { return call; })
 
 #define BHIP_TRY(b, expr)                                                                              \
   do {                                                                                                 \
@@ -458,6 +475,26 @@ int batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out, bool r
   *out = nullptr;
   if (n < 1 || n > 1000000) return bfail(nullptr, SDPGPU_ERR_ARG, "batch_create: n = %d instances (1 .. 1000000)", n);
   return guarded((sdpgpu_batch*)nullptr, "sdpgpu_batch_create", [&]() -> int {
+    if (!ragged && descs[0].family == SDPGPU_FAMILY_STAFF) {  // the family of instance 0 selects the kind of batch
+      StaffBatch* sb = nullptr;
+      std::string why;
+      const int rc = staff_batch_new(descs, n, &sb, &why);
+      g_create_error = why;
+      if (rc) return rc;
+      sdpgpu_batch* b = nullptr;
+      try {
+        b = new sdpgpu_batch();
+      } catch (...) {
+        staff_batch_delete(sb);
+        throw;
+      }
+      b->staff = sb;
+      b->N = n;
+      b->T = descs[0].periods;
+      b->device = descs[0].device;
+      *out = b;
+      return SDPGPU_OK;
+    }
     for (int32_t k = 0; k < n; ++k) {
       const sdpgpu_desc& d = descs[k];
       int rc = validate(d);
@@ -546,16 +583,19 @@ int sdpgpu_batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out)
 int sdpgpu_batch_create_ragged(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out) { return batch_create(descs, n, out, true); }
 
 int64_t sdpgpu_batch_num_states(const sdpgpu_batch* b, int32_t instance) {
+  if (b && b->staff) return staff_batch_num_states(b->staff, instance);
   return b && instance >= 0 && instance < b->N ? (int64_t)b->nxs[(size_t)instance] : -1;
 }
 
 int32_t sdpgpu_batch_num_actions(const sdpgpu_batch* b, int32_t instance) {
+  if (b && b->staff) return staff_batch_num_actions(b->staff, instance);
   return b && instance >= 0 && instance < b->N ? b->As[(size_t)instance] : -1;
 }
 
 int sdpgpu_batch_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_plan* out) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_REFUSE(b, "sdpgpu_batch_plan_period");
   if (!out) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_plan_period: out is null");
   if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_plan_period: period %d outside 1 .. %d", period, b->T);
   return guarded(b, "sdpgpu_batch_plan_period", [&]() -> int {
@@ -577,6 +617,11 @@ int sdpgpu_batch_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_plan*
 
 void sdpgpu_batch_destroy(sdpgpu_batch* b) {
   if (!b) return;
+  if (b->staff) {
+    staff_batch_delete(b->staff);
+    delete b;
+    return;
+  }
   {
     DeviceScope dev;
     if (b->allocated || b->d_values || b->d_pmf) {
@@ -618,6 +663,7 @@ const char* sdpgpu_batch_last_error(const sdpgpu_batch* b) { return b ? b->err.c
 int sdpgpu_batch_set_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, const double* demand, const double* prob, int32_t n) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_REFUSE(b, "sdpgpu_batch_set_pmf");
   return guarded(b, "sdpgpu_batch_set_pmf", [&]() -> int {
     if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "batch_set_pmf: instance %d outside 0 .. %d", instance, b->N - 1);
     if (t < 0 || t >= b->T) return bfail(b, SDPGPU_ERR_ARG, "batch_set_pmf: period index %d outside 0 .. %d", t, b->T - 1);
@@ -648,6 +694,7 @@ int sdpgpu_batch_set_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, const dou
 int sdpgpu_batch_set_stream(sdpgpu_batch* b, void* hip_stream) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_set_stream", staff_batch_set_stream(b->staff, &b->err, hip_stream));
   if (b->own_stream && b->stream) {
     DeviceScope dev;
     BHIP_TRY(b, dev.enter(b->device));
@@ -663,6 +710,7 @@ int sdpgpu_batch_set_stream(sdpgpu_batch* b, void* hip_stream) {
 int sdpgpu_batch_set_profiling(sdpgpu_batch* b, int32_t on) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  if (b->staff) return staff_batch_set_profiling(b->staff, on);
   b->profiling = on != 0;
   return SDPGPU_OK;
 }
@@ -670,6 +718,7 @@ int sdpgpu_batch_set_profiling(sdpgpu_batch* b, int32_t on) {
 int sdpgpu_batch_solve(sdpgpu_batch* b, int32_t sync) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_solve", staff_batch_solve(b->staff, &b->err, sync));
   return guarded(b, "sdpgpu_batch_solve", [&]() -> int {
     int rc = layout(b);  // (argument and state errors before the device is touched)
     if (rc) return rc;
@@ -717,6 +766,7 @@ int sdpgpu_batch_solve(sdpgpu_batch* b, int32_t sync) {
 int sdpgpu_batch_synchronize(sdpgpu_batch* b) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_synchronize", staff_batch_synchronize(b->staff, &b->err));
   if (!b->allocated) return SDPGPU_OK;
   DeviceScope dev;
   BHIP_TRY(b, dev.enter(b->device));
@@ -738,6 +788,7 @@ static int read_check(sdpgpu_batch* b, const char* who, int32_t instance, int32_
 int sdpgpu_batch_values(sdpgpu_batch* b, int32_t instance, int32_t period, double* out, int64_t n) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_values", staff_batch_values(b->staff, &b->err, instance, period, out, n));
   int rc = read_check(b, "sdpgpu_batch_values", instance, period, out, n, true);
   if (rc) return rc;
   DeviceScope dev;
@@ -750,6 +801,7 @@ int sdpgpu_batch_values(sdpgpu_batch* b, int32_t instance, int32_t period, doubl
 int sdpgpu_batch_policy(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* out, int64_t n) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_policy", staff_batch_policy(b->staff, &b->err, instance, period, out, n));
   int rc = read_check(b, "sdpgpu_batch_policy", instance, period, out, n, false);
   if (rc) return rc;
   DeviceScope dev;
@@ -762,6 +814,7 @@ int sdpgpu_batch_policy(sdpgpu_batch* b, int32_t instance, int32_t period, int32
 int sdpgpu_batch_initial(sdpgpu_batch* b, double* out_value, int32_t* out_action_index) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_initial", staff_batch_initial(b->staff, &b->err, out_value, out_action_index));
   if (!out_value || !out_action_index) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_initial: null output");
   if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "sdpgpu_batch_initial before sdpgpu_batch_solve");
   return guarded(b, "sdpgpu_batch_initial", [&]() -> int {
@@ -785,6 +838,7 @@ int sdpgpu_batch_initial(sdpgpu_batch* b, double* out_value, int32_t* out_action
 int sdpgpu_batch_stats_get(sdpgpu_batch* b, sdpgpu_batch_stats* out) {
   if (!b || !out) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_stats_get", staff_batch_stats(b->staff, &b->err, out));
   return guarded(b, "sdpgpu_batch_stats_get", [&]() -> int {
     std::memset(out, 0, sizeof *out);
     out->instances = b->N;
@@ -819,6 +873,7 @@ int sdpgpu_batch_stats_get(sdpgpu_batch* b, sdpgpu_batch_stats* out) {
 double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period) {
   if (!b) return -1.0;
   b->err.clear();
+  if (b->staff) return staff_batch_period_ms(b->staff, &b->err, period);
   if (period < 1 || period > b->T || !b->periods_timed) {
     (void)bfail(b, SDPGPU_ERR_STATE, "sdpgpu_batch_period_ms: period %d has no timing (sdpgpu_batch_set_profiling before the solve)", period);
     return -1.0;
@@ -830,6 +885,49 @@ double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period) {
   float ms = 0;
   if (hipEventElapsedTime(&ms, b->ev_period[(size_t)period], b->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
   return ms;
+}
+
+// ---- the staff batch's own calls (sdpgpu_staffbatch.hip) ----
+int sdpgpu_batch_add_level_pmf(sdpgpu_batch* b, const double* prob, const int32_t* row_len, int32_t n_rows, int32_t row_stride,
+                               int32_t* out_table) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  STAFF_ONLY(b, "sdpgpu_batch_add_level_pmf");
+  return guarded(b, "sdpgpu_batch_add_level_pmf",
+                 [&]() -> int { return staff_batch_add_table(b->staff, &b->err, prob, row_len, n_rows, row_stride, out_table); });
+}
+
+int sdpgpu_batch_use_level_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, int32_t table) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  STAFF_ONLY(b, "sdpgpu_batch_use_level_pmf");
+  return guarded(b, "sdpgpu_batch_use_level_pmf", [&]() -> int { return staff_batch_use_table(b->staff, &b->err, instance, t, table); });
+}
+
+int sdpgpu_batch_set_overhead(sdpgpu_batch* b, int32_t instance, int32_t t, double min_staff) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  STAFF_ONLY(b, "sdpgpu_batch_set_overhead");
+  return guarded(b, "sdpgpu_batch_set_overhead", [&]() -> int { return staff_batch_set_min_staff(b->staff, &b->err, instance, t, min_staff); });
+}
+
+int sdpgpu_batch_grid(sdpgpu_batch* b, int32_t instance, int32_t period, double* x_lo, int64_t* nx) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_grid", staff_batch_grid(b->staff, &b->err, instance, period, x_lo, nx));
+  if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: instance %d outside 0 .. %d", instance, b->N - 1);
+  if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: period %d outside 1 .. %d", period, b->T);
+  if (!x_lo || !nx) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: null output");
+  *x_lo = b->d[(size_t)instance].min_inventory;  // (one fixed grid for all periods)
+  *nx = b->nxs[(size_t)instance];
+  return SDPGPU_OK;
+}
+
+int sdpgpu_batch_staff_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_staff_plan* out) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  STAFF_ONLY(b, "sdpgpu_batch_staff_plan_period");
+  return guarded(b, "sdpgpu_batch_staff_plan_period", [&]() -> int { return staff_batch_plan(b->staff, &b->err, period, out); });
 }
 
 }  // extern "C"
@@ -922,6 +1020,7 @@ extern "C" {
 int sdpgpu_batch_set_sampler(sdpgpu_batch* b, int32_t instance, int32_t t, const sdpgpu_dist_spec* spec) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_REFUSE(b, "sdpgpu_batch_set_sampler");
   return guarded(b, "sdpgpu_batch_set_sampler", [&]() -> int {
     if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "batch_set_sampler: instance %d outside 0 .. %d", instance, b->N - 1);
     if (t < 0 || t >= b->T) return bfail(b, SDPGPU_ERR_ARG, "batch_set_sampler: period index %d outside 0 .. %d", t, b->T - 1);
@@ -943,6 +1042,7 @@ int sdpgpu_batch_set_sampler(sdpgpu_batch* b, int32_t instance, int32_t t, const
 int sdpgpu_batch_sample_demands(sdpgpu_batch* b, int32_t instance, int32_t n_paths, uint64_t seed, double* out_demand, double* out_u) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_REFUSE(b, "sdpgpu_batch_sample_demands");
   return guarded(b, "sdpgpu_batch_sample_demands", [&]() -> int {
     const char* who = "sdpgpu_batch_sample_demands";
     if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, b->N - 1);
@@ -980,6 +1080,10 @@ int sdpgpu_batch_sample_demands(sdpgpu_batch* b, int32_t instance, int32_t n_pat
 double sdpgpu_batch_simulate_ms(sdpgpu_batch* b) {
   if (!b) return -1.0;
   b->err.clear();
+  if (b->staff) {
+    (void)bfail(b, SDPGPU_ERR_UNSUPPORTED, "sdpgpu_batch_simulate_ms: not available on a batch of the staff family (SDPGPU_FAMILY_STAFF)");
+    return -1.0;
+  }
   if (!b->sim_timed) {
     (void)bfail(b, SDPGPU_ERR_STATE, "sdpgpu_batch_simulate_ms: no simulation has run");
     return -1.0;
@@ -1097,6 +1201,7 @@ extern "C" {
 int sdpgpu_batch_reachable(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* lo, int32_t* hi) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_REFUSE(b, "sdpgpu_batch_reachable");
   const char* who = "sdpgpu_batch_reachable";
   if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, b->N - 1);
   if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, b->T);
@@ -1141,6 +1246,7 @@ int sdpgpu_fit_min_square(double max_order_quantity, double lb, int32_t up_index
 int sdpgpu_batch_fit_ss(sdpgpu_batch* b, int32_t levels, double* out) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_REFUSE(b, "sdpgpu_batch_fit_ss");
   return guarded(b, "sdpgpu_batch_fit_ss", [&]() -> int {
     const char* who = "sdpgpu_batch_fit_ss";
     if (levels < 1 || levels > 3) return bfail(b, SDPGPU_ERR_ARG, "%s: levels = %d (1, 2 or 3: getSinglesS, getTwosS, getThreesS)", who, levels);
@@ -1277,6 +1383,9 @@ int sim_entry(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, c
               const double* ini_x, double* out_mean, double* out_sum) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  if (b->staff)
+    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: not available on a batch of the staff family (SDPGPU_FAMILY_STAFF): a hiring rule is rolled out per "
+                 "handle (sdpgpu_staff_simulate)", who);
   return guarded(b, who, [&]() -> int { return sim_run(b, who, rule, n_paths, demand, stride, sampled, seed, ini_x, out_mean, out_sum); });
 }
 
@@ -1477,6 +1586,7 @@ int sdpgpu_check_convexity(int32_t kind, const double* g, int64_t n, double K, i
 int sdpgpu_batch_gy(sdpgpu_batch* b, int32_t instance, int32_t period, double* out, int64_t n) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_REFUSE(b, "sdpgpu_batch_gy");
   return guarded(b, "sdpgpu_batch_gy", [&]() -> int {
     const char* who = "sdpgpu_batch_gy";
     int rc = read_check(b, who, instance, period, out, n, false);
@@ -1497,6 +1607,7 @@ int sdpgpu_batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, 
                                  const double* K, const int32_t* capacity, sdpgpu_convexity* out) {
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
+  STAFF_REFUSE(b, "sdpgpu_batch_check_convexity");
   return guarded(b, "sdpgpu_batch_check_convexity",
                  [&]() -> int { return batch_check_convexity(b, kind, source, period, x_lo, x_hi, K, capacity, out); });
 }

@@ -167,6 +167,31 @@ void build_samplers(const sdpgpu_handle* h, std::vector<sdp::SimSampler>* rec, s
 // layout, for rollouts that carry the state as doubles and read no table (nx = the descriptor's inventory points)
 sdp::DevParams rule_params(const sdpgpu_handle* h, int t, int64_t nx);
 
+// ---- sdpgpu_staffbatch.hip -------------------------------------------------------------------------------
+// A batch of STAFF instances in the separable mode (pool of level tables, groups per (period, table), two launches per period
+// for all instances: sdp_staff_batch.hpp): what the sdpgpu_batch_* entry points of sdpgpu_batch.hip forward to when instance 0
+// is of that family.  `err` is the batch's error sink (staff_batch_new: the create error).
+struct StaffBatch;
+int staff_batch_new(const sdpgpu_desc* descs, int32_t n, StaffBatch** out, std::string* why);
+void staff_batch_delete(StaffBatch* s);
+int staff_batch_add_table(StaffBatch* s, std::string* err, const double* prob, const int32_t* row_len, int32_t n_rows, int32_t row_stride,
+                          int32_t* out_table);
+int staff_batch_use_table(StaffBatch* s, std::string* err, int32_t instance, int32_t t, int32_t table);
+int staff_batch_set_min_staff(StaffBatch* s, std::string* err, int32_t instance, int32_t t, double min_staff);
+int staff_batch_grid(const StaffBatch* s, std::string* err, int32_t instance, int32_t period, double* x_lo, int64_t* nx);
+int64_t staff_batch_num_states(const StaffBatch* s, int32_t instance);
+int32_t staff_batch_num_actions(const StaffBatch* s, int32_t instance);
+int staff_batch_plan(StaffBatch* s, std::string* err, int32_t period, sdpgpu_batch_staff_plan* out);
+int staff_batch_set_stream(StaffBatch* s, std::string* err, void* hip_stream);
+int staff_batch_set_profiling(StaffBatch* s, int32_t on);
+int staff_batch_solve(StaffBatch* s, std::string* err, int32_t sync);
+int staff_batch_synchronize(StaffBatch* s, std::string* err);
+int staff_batch_values(StaffBatch* s, std::string* err, int32_t instance, int32_t period, double* out, int64_t n);
+int staff_batch_policy(StaffBatch* s, std::string* err, int32_t instance, int32_t period, int32_t* out, int64_t n);
+int staff_batch_initial(StaffBatch* s, std::string* err, double* out_value, int32_t* out_action_index);
+int staff_batch_stats(StaffBatch* s, std::string* err, sdpgpu_batch_stats* out);
+double staff_batch_period_ms(StaffBatch* s, std::string* err, int32_t period);
+
 // offsets of the scratch block, every part aligned to 16 bytes
 struct Carve {
   size_t at = 0;

@@ -1,0 +1,640 @@
+// sdpgpu_staffbatch.hip -- a BATCH of STAFF-family instances of one shape in the opt-in separable mode (include/sdpgpu.h,
+// "batched workforce solve"): the sweep of workforce.WorkforceTesting.main -- 216 instances of T = 8, hires 0..1000, no clamp,
+// two turnover tables.  Period t of ALL instances runs in two launches (sdp_staff_batch.hpp): the rows G and P of every
+// instance, then the scan.  This unit holds the pool of level tables, the validation, the host layout (per-period boxes,
+// groups of instances per (period, table), instance blocks), the plan, the launcher and what the entry points of
+// sdpgpu_batch.hip forward to on a batch whose instance 0 is of the STAFF family.  Errors go to the sink the caller names (the
+// batch's last error, or the create error).
+#include "sdpgpu_sim_host.hpp"
+#include "sdp_staff_batch.hpp"
+
+namespace sdpgpu_detail {
+
+int validate(const sdpgpu_desc& d);               // sdpgpu.hip
+int32_t full_action_count(const sdpgpu_desc& d);  // sdpgpu.hip
+
+namespace {
+
+int sfail(std::string* sink, int code, const char* fmt, ...) {
+  char buf[640];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  if (sink) *sink = buf;
+  return code;
+}
+
+#define SHIP_TRY(err, expr)                                                                              \
+  do {                                                                                                   \
+    hipError_t e_ = (expr);                                                                              \
+    if (e_ != hipSuccess) return sfail(err, SDPGPU_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+// launch of one period for the whole batch
+struct PeriodPlan {
+  int tables = 0;          // distinct tables = groups of instances
+  int R = 1, U = sdp::kStaffBatchU1;
+  int64_t blocks = 0;      // instance blocks: sum over groups of ceil(size / R)
+  int64_t g_blocks = 0;    // waves of 64 levels per block
+  int64_t tiles = 0;       // workgroups of 64 states per instance
+  int longest_row = 0;
+};
+
+struct Table {
+  std::vector<double> p;  // transposed: p[j * rows + y], zero behind a row's length
+  std::vector<int32_t> len;
+  int32_t rows = 0, maxj = 0;
+};
+
+}  // namespace
+
+struct StaffBatch {
+  std::vector<sdpgpu_desc> d;
+  int32_t N = 0, T = 0, A = 0;
+  std::vector<Table> pool;
+  std::vector<int32_t> use;        // [i * T + t]: pool id, -1 = none yet
+  std::vector<double> min_staff;   // [i * T + t]
+  std::vector<char> min_set;
+  bool laid_out = false, allocated = false, solved = false, profiling = false;
+  std::vector<int64_t> x_lo, nx, row_pre;  // [t]: the period's box (shared by the instances), prefix sums of nx
+  int64_t sum_nx = 0, nx_max = 0, lev_max = 0;
+  std::vector<PeriodPlan> plan;            // [t]
+  std::vector<sdp::StaffBatchInst> inst;   // [t * N + i]
+  std::vector<int32_t> blk;                // the periods' instance blocks, one after the other (R entries a block)
+  std::vector<size_t> blk_off;             // [t]
+  int64_t cells = 0;
+  // device
+  int device = -1;
+  hipStream_t stream = nullptr;
+  bool own_stream = false, stream_given = false;
+  std::vector<void*> owned;                // pool tables and row lengths
+  sdp::StaffBatchTable* d_tabs = nullptr;
+  sdp::StaffBatchInst* d_inst = nullptr;
+  int32_t* d_blk = nullptr;
+  double* d_values = nullptr;
+  int32_t* d_policy = nullptr;
+  double* d_gp = nullptr;                  // [N][2][lev_max]
+  char* d_ini_out = nullptr;               // N doubles, then N int32
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::vector<hipEvent_t> ev_period;       // [T + 1] when profiling
+  bool timed = false, periods_timed = false;
+  int32_t period_launches = 0, periods_run = 0;
+};
+
+namespace {
+
+size_t value_row(const StaffBatch* s, int i, int t) {
+  if (s->d[0].store_all_values) return (size_t)i * (size_t)s->sum_nx + (size_t)s->row_pre[(size_t)t];
+  return ((size_t)i * 2 + (size_t)(t & 1)) * (size_t)s->nx_max;  // two ping-pong tables per instance: V_1 and V_2 survive
+}
+size_t policy_row(const StaffBatch* s, int i, int t) { return (size_t)i * (size_t)s->sum_nx + (size_t)s->row_pre[(size_t)t]; }
+
+// The box of every period.  Clamped: [minX, maxX] throughout.  Unclamped: as a handle lays it out (layout, sdpgpu.hip) -- from
+// [ini, ini], lower end down by the longest row of the period's table less one (never below 0), upper end up by the hire limit.
+// The lower end reads instance i's tables of the periods before `upto`; -1 in *missing_t: all were there.
+void boxes_of(const StaffBatch* s, int i, int upto, std::vector<int64_t>* lo_out, std::vector<int64_t>* nx_out, int* missing_t) {
+  const sdpgpu_desc& d = s->d[0];
+  *missing_t = -1;
+  lo_out->assign((size_t)upto, 0);
+  nx_out->assign((size_t)upto, 0);
+  int64_t lo = (int64_t)d.min_inventory, hi = (int64_t)d.max_inventory;
+  if (!d.clamp_inventory) lo = hi = (int64_t)d.ini_inventory;
+  for (int t = 0; t < upto; ++t) {
+    (*lo_out)[(size_t)t] = lo;
+    (*nx_out)[(size_t)t] = hi - lo + 1;
+    if (d.clamp_inventory || t + 1 == upto) continue;
+    const int32_t id = s->use[(size_t)i * s->T + t];
+    if (id < 0) {
+      *missing_t = t;
+      return;
+    }
+    lo = std::max<int64_t>(0, lo - (s->pool[(size_t)id].maxj - 1));
+    hi += s->A - 1;
+  }
+}
+
+// sum over the states of a period and the actions of pmfs[t][min(x + a, rows - 1)].length (staff_cells, sdpgpu_staff.hip)
+int64_t cells_of(const Table& tb, int64_t x0, int64_t nx, int64_t nA) {
+  const int64_t rows = tb.rows;
+  std::vector<int64_t> pre((size_t)rows + 1, 0);
+  for (int64_t y = 0; y < rows; ++y) pre[(size_t)y + 1] = pre[(size_t)y] + tb.len[(size_t)y];
+  auto upto = [&](int64_t y) { return y <= rows ? pre[(size_t)y] : pre[(size_t)rows] + (y - rows) * (int64_t)tb.len[(size_t)rows - 1]; };
+  int64_t cells = 0;
+  for (int64_t i = 0; i < nx; ++i) cells += upto(x0 + i + nA) - upto(x0 + i);
+  return cells;
+}
+
+int layout(StaffBatch* s, std::string* err) {
+  if (s->laid_out) return SDPGPU_OK;
+  const int N = s->N, T = s->T;
+  const sdpgpu_desc& d0 = s->d[0];
+  for (int i = 0; i < N; ++i)
+    for (int t = 0; t < T; ++t)
+      if (s->use[(size_t)i * T + t] < 0)
+        return sfail(err, SDPGPU_ERR_STATE, "level table of instance %d, period %d not set (sdpgpu_batch_use_level_pmf)", i, t + 1);
+  for (int i = 0; i < N; ++i)
+    for (int t = 0; t < T; ++t) {
+      const size_t k = (size_t)i * T + t;
+      if (!s->min_set[k]) s->min_staff[k] = s->d[(size_t)i].overhead_cost;
+      const double m = s->min_staff[k];
+      if (m != std::floor(m) || std::fabs(m) > 1e9)
+        return sfail(err, SDPGPU_ERR_ARG, "minStaffNum of instance %d, period %d (sdpgpu_batch_set_overhead) must be an integer", i, t + 1);
+    }
+  int missing = -1;
+  boxes_of(s, 0, T, &s->x_lo, &s->nx, &missing);
+  if (!d0.clamp_inventory) {  // the boxes are common to the batch: every instance's tables must grow the same ones
+    std::vector<int64_t> lo, nx;
+    for (int i = 1; i < N; ++i) {
+      boxes_of(s, i, T, &lo, &nx, &missing);
+      for (int t = 0; t < T; ++t)
+        if (lo[(size_t)t] != s->x_lo[(size_t)t])
+          return sfail(err, SDPGPU_ERR_UNSUPPORTED, "instance %d: its level tables put the staff range of period %d at %lld .., instance 0's at %lld .. "
+                       "(clamp_inventory = 0: the longest rows of the tables of a period must leave the instances one staff range)",
+                       i, t + 1, (long long)lo[(size_t)t], (long long)s->x_lo[(size_t)t]);
+    }
+  }
+  s->row_pre.assign((size_t)T, 0);
+  s->sum_nx = s->nx_max = s->lev_max = 0;
+  for (int t = 0; t < T; ++t) {
+    const int64_t nx = s->nx[(size_t)t], levels = nx + s->A - 1;
+    // (levels and staff numbers are 32-bit in the kernels, V_{t+1} is addressed by 32-bit byte offsets)
+    if (nx >= 2147483647LL || levels >= 2147483647LL || s->x_lo[(size_t)t] + levels >= 2147483647LL)
+      return sfail(err, SDPGPU_ERR_UNSUPPORTED, "period %d: %lld states + %d actions reach 2^31 levels", t + 1, (long long)nx, s->A);
+    if (nx * 8 >= 2147483647LL)
+      return sfail(err, SDPGPU_ERR_UNSUPPORTED, "period %d: a value table of %lld states reaches 2 GiB (the G kernel uses 32-bit byte offsets)", t + 1, (long long)nx);
+    s->row_pre[(size_t)t] = (size_t)s->sum_nx;
+    s->sum_nx += nx;
+    s->nx_max = std::max(s->nx_max, nx);
+    s->lev_max = std::max(s->lev_max, levels);
+  }
+  if ((double)s->sum_nx * N > 4.0e9 || (double)s->lev_max * 2 * N > 4.0e9)
+    return sfail(err, SDPGPU_ERR_UNSUPPORTED, "batch tables of %d instances x %lld states (all periods) are too large", N, (long long)s->sum_nx);
+  s->plan.assign((size_t)T, PeriodPlan());
+  s->inst.assign((size_t)T * N, sdp::StaffBatchInst());
+  s->blk.clear();
+  s->blk_off.assign((size_t)T, 0);
+  s->cells = 0;
+  std::vector<int> order((size_t)N);
+  for (int t = 0; t < T; ++t) {
+    PeriodPlan& pl = s->plan[(size_t)t];
+    // groups: the instances of one table, in ascending table id and, inside a group, in the caller's order
+    for (int i = 0; i < N; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int c) { return s->use[(size_t)a * T + t] < s->use[(size_t)c * T + t]; });
+    int largest = 0;
+    for (int a = 0; a < N;) {
+      int e = a;
+      while (e < N && s->use[(size_t)order[(size_t)e] * T + t] == s->use[(size_t)order[(size_t)a] * T + t]) ++e;
+      pl.tables++;
+      largest = std::max(largest, e - a);
+      const Table& tb = s->pool[(size_t)s->use[(size_t)order[(size_t)a] * T + t]];
+      pl.longest_row = std::max(pl.longest_row, (int)tb.maxj);
+      s->cells += cells_of(tb, s->x_lo[(size_t)t], s->nx[(size_t)t], s->A) * (int64_t)(e - a);
+      a = e;
+    }
+    // R from the group sizes alone: the instance block where some group fills one, else single instances
+    pl.R = sdp::kStaffBatchR > 1 && largest >= sdp::kStaffBatchR ? sdp::kStaffBatchR : 1;
+    pl.U = pl.R > 1 ? sdp::kStaffBatchUR : sdp::kStaffBatchU1;
+    s->blk_off[(size_t)t] = s->blk.size();
+    for (int a = 0; a < N;) {
+      int e = a;
+      while (e < N && s->use[(size_t)order[(size_t)e] * T + t] == s->use[(size_t)order[(size_t)a] * T + t]) ++e;
+      for (int b0 = a; b0 < e; b0 += pl.R) {
+        for (int r = 0; r < pl.R; ++r) s->blk.push_back(order[(size_t)std::min(b0 + r, e - 1)]);  // (spare slots repeat the last instance)
+        pl.blocks++;
+      }
+      a = e;
+    }
+    const int64_t levels = s->nx[(size_t)t] + s->A - 1;
+    pl.g_blocks = (levels + 63) / 64;
+    pl.tiles = (s->nx[(size_t)t] + 63) / 64;
+    // (a dispatch carries at most 2^32 - 1 work-items)
+    if (pl.blocks * pl.g_blocks * 64 >= 4294967296LL || !grid_ok((int64_t)N * pl.tiles) || pl.blocks * pl.R >= 2147483647LL)
+      return sfail(err, SDPGPU_ERR_UNSUPPORTED, "period %d: %lld G tasks / %lld scan workgroups do not fit one launch", t + 1,
+                   (long long)(pl.blocks * pl.g_blocks), (long long)((int64_t)N * pl.tiles));
+    for (int i = 0; i < N; ++i) {
+      const sdpgpu_desc& d = s->d[(size_t)i];
+      sdp::StaffBatchInst I{};
+      I.K = d.fixed_order_cost;
+      I.v = d.unit_order_cost;
+      I.salary = d.holding_cost;
+      I.pen = d.penalty_cost;
+      I.min_staff = (int32_t)s->min_staff[(size_t)i * T + t];
+      I.table = s->use[(size_t)i * T + t];
+      I.v_cur_off = (int64_t)value_row(s, i, t);
+      I.v_next_off = t + 1 < T ? (int64_t)value_row(s, i, t + 1) : 0;
+      I.pol_off = (int64_t)policy_row(s, i, t);
+      s->inst[(size_t)t * N + i] = I;
+    }
+  }
+  s->laid_out = true;
+  return SDPGPU_OK;
+}
+
+int allocate(StaffBatch* s, std::string* err) {
+  if (s->allocated) return SDPGPU_OK;
+  int rc = layout(s, err);
+  if (rc) return rc;
+  int ndev = 0;
+  const hipError_t ec = hipGetDeviceCount(&ndev);
+  if (ec != hipSuccess || ndev < 1)
+    return sfail(err, SDPGPU_ERR_DEVICE, "no HIP device available (%s); this library has no CPU path", ec == hipSuccess ? "device count 0" : hipGetErrorString(ec));
+  if (!s->stream && !s->stream_given) {
+    SHIP_TRY(err, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    s->own_stream = true;
+  }
+  const int N = s->N, T = s->T;
+  std::vector<sdp::StaffBatchTable> tabs(s->pool.size());
+  for (size_t k = 0; k < s->pool.size(); ++k) {
+    const Table& tb = s->pool[k];
+    double* p = nullptr;
+    int32_t* len = nullptr;
+    SHIP_TRY(err, hipMalloc((void**)&p, tb.p.size() * sizeof(double)));
+    s->owned.push_back(p);
+    SHIP_TRY(err, hipMalloc((void**)&len, tb.len.size() * sizeof(int32_t)));
+    s->owned.push_back(len);
+    SHIP_TRY(err, hipMemcpy(p, tb.p.data(), tb.p.size() * sizeof(double), hipMemcpyHostToDevice));
+    SHIP_TRY(err, hipMemcpy(len, tb.len.data(), tb.len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    tabs[k] = sdp::StaffBatchTable{p, len, tb.rows, tb.maxj};
+  }
+  SHIP_TRY(err, hipMalloc((void**)&s->d_tabs, std::max<size_t>(tabs.size(), 1) * sizeof(sdp::StaffBatchTable)));
+  SHIP_TRY(err, hipMemcpy(s->d_tabs, tabs.data(), tabs.size() * sizeof(sdp::StaffBatchTable), hipMemcpyHostToDevice));
+  SHIP_TRY(err, hipMalloc((void**)&s->d_inst, s->inst.size() * sizeof(sdp::StaffBatchInst)));
+  SHIP_TRY(err, hipMemcpy(s->d_inst, s->inst.data(), s->inst.size() * sizeof(sdp::StaffBatchInst), hipMemcpyHostToDevice));
+  SHIP_TRY(err, hipMalloc((void**)&s->d_blk, std::max<size_t>(s->blk.size(), 1) * sizeof(int32_t)));
+  SHIP_TRY(err, hipMemcpy(s->d_blk, s->blk.data(), s->blk.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  const size_t v_elems = s->d[0].store_all_values ? (size_t)N * (size_t)s->sum_nx : (size_t)N * 2 * (size_t)s->nx_max;
+  SHIP_TRY(err, hipMalloc((void**)&s->d_values, v_elems * sizeof(double)));
+  SHIP_TRY(err, hipMalloc((void**)&s->d_policy, (size_t)N * (size_t)s->sum_nx * sizeof(int32_t)));
+  SHIP_TRY(err, hipMalloc((void**)&s->d_gp, (size_t)N * 2 * (size_t)s->lev_max * sizeof(double)));
+  SHIP_TRY(err, hipMalloc((void**)&s->d_ini_out, (size_t)N * 12));
+  SHIP_TRY(err, hipEventCreate(&s->ev0));
+  SHIP_TRY(err, hipEventCreate(&s->ev1));
+  (void)T;
+  s->allocated = true;
+  return SDPGPU_OK;
+}
+
+template <int R, int U>
+hipError_t launch_g(StaffBatch* s, const sdp::StaffBatchLaunch& L, const PeriodPlan& pl, int t) {
+  const dim3 grid((unsigned)(pl.blocks * pl.g_blocks));
+  const sdp::StaffBatchInst* inst = s->d_inst + (size_t)t * s->N;
+  const int32_t* blk = s->d_blk + s->blk_off[(size_t)t];
+  if (t + 1 < s->T)
+    hipLaunchKernelGGL((sdp::staff_batch_g_kernel<R, U, true>), grid, dim3(64), 0, s->stream, L, inst, s->d_tabs, blk, s->d_values, s->d_gp);
+  else
+    hipLaunchKernelGGL((sdp::staff_batch_g_kernel<R, U, false>), grid, dim3(64), 0, s->stream, L, inst, s->d_tabs, blk, s->d_values, s->d_gp);
+  return hipGetLastError();
+}
+
+hipError_t launch_period(StaffBatch* s, int t) {
+  const PeriodPlan& pl = s->plan[(size_t)t];
+  const sdpgpu_desc& d = s->d[0];
+  sdp::StaffBatchLaunch L{};
+  L.n_actions = s->A;
+  L.y0 = (int32_t)s->x_lo[(size_t)t];
+  L.n_states = (int32_t)s->nx[(size_t)t];
+  L.n_levels = L.n_states + s->A - 1;
+  // bounds of the next staff number: [minX, maxX] when clamped, else the next period's box (staff_next_bounds, sdpgpu_staff.hip)
+  L.next_x_lo = t + 1 < s->T ? (int32_t)s->x_lo[(size_t)t + 1] : 0;
+  if (d.clamp_inventory) {
+    L.nn_lo = (int32_t)d.min_inventory;
+    L.nn_hi = (int32_t)d.max_inventory;
+  } else {
+    L.nn_lo = L.next_x_lo;
+    L.nn_hi = t + 1 < s->T ? L.next_x_lo + (int32_t)s->nx[(size_t)t + 1] - 1 : 0;
+  }
+  L.g_blocks = (int32_t)pl.g_blocks;
+  L.tiles = (int32_t)pl.tiles;
+  L.lev_stride = s->lev_max;
+  hipError_t e = pl.R == 1 ? launch_g<1, sdp::kStaffBatchU1>(s, L, pl, t) : launch_g<sdp::kStaffBatchR, sdp::kStaffBatchUR>(s, L, pl, t);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sdp::staff_batch_min_kernel, dim3((unsigned)((int64_t)s->N * pl.tiles)), dim3(256), 0, s->stream, L,
+                     s->d_inst + (size_t)t * s->N, s->d_gp, s->d_values, s->d_policy);
+  return hipGetLastError();
+}
+
+// what differs between instance k and instance 0 although the batch needs it shared (nullptr: nothing)
+const char* shape_mismatch(const sdpgpu_desc& a, const sdpgpu_desc& c, char* buf, size_t n) {
+#define SDP_SAME_I(f) \
+  if (a.f != c.f) { std::snprintf(buf, n, #f " %d differs from instance 0's %d", (int)c.f, (int)a.f); return buf; }
+#define SDP_SAME_D(f) \
+  if (a.f != c.f) { std::snprintf(buf, n, #f " %g differs from instance 0's %g", (double)c.f, (double)a.f); return buf; }
+  SDP_SAME_I(periods)
+  SDP_SAME_D(step)
+  SDP_SAME_D(min_inventory)
+  SDP_SAME_D(max_inventory)
+  SDP_SAME_D(max_order_quantity)
+  SDP_SAME_I(clamp_inventory)
+  SDP_SAME_D(ini_inventory)
+  SDP_SAME_I(device)
+  SDP_SAME_I(store_all_values)
+#undef SDP_SAME_I
+#undef SDP_SAME_D
+  return nullptr;
+}
+
+int read_check(StaffBatch* s, std::string* err, const char* who, int32_t instance, int32_t period, const void* out, int64_t n, bool is_values) {
+  if (instance < 0 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, s->N - 1);
+  if (period < 1 || period > s->T) return sfail(err, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, s->T);
+  if (!s->solved) return sfail(err, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+  const int64_t nx = s->nx[(size_t)period - 1];  // the period's own count
+  if (!out || n < 0 || n > nx) return sfail(err, SDPGPU_ERR_ARG, "%s: bad output (n = %lld, period %d has %lld states)", who, (long long)n, period, (long long)nx);
+  if (is_values && !s->d[0].store_all_values && period > 2)
+    return sfail(err, SDPGPU_ERR_STATE, "%s: V_%d was overwritten (store_all_values = 0 keeps two ping-pong tables: periods 1 and 2 survive)", who, period);
+  return SDPGPU_OK;
+}
+
+}  // namespace
+
+int staff_batch_new(const sdpgpu_desc* descs, int32_t n, StaffBatch** out, std::string* why) {
+  for (int32_t k = 0; k < n; ++k) {
+    const sdpgpu_desc& d = descs[k];
+    g_create_error.clear();
+    int rc = validate(d);
+    if (rc) {
+      const std::string inner = g_create_error;
+      return sfail(why, rc, "instance %d: %s", k, inner.c_str());
+    }
+    if (d.family != SDPGPU_FAMILY_STAFF)
+      return sfail(why, SDPGPU_ERR_UNSUPPORTED, "instance %d: family %d -- instance 0 makes this a batch of the staff family (SDPGPU_FAMILY_STAFF); a batch holds one family", k, d.family);
+    if (d.world_size != 1)
+      return sfail(why, SDPGPU_ERR_UNSUPPORTED, "instance %d: world_size %d -- a batch runs on one device (split the instance list per rank on the host)", k, d.world_size);
+    if (d.kernel != SDPGPU_KERNEL_SEPARABLE)
+      return sfail(why, SDPGPU_ERR_UNSUPPORTED, "instance %d: kernel %d -- a staff batch runs the separable mode only (SDPGPU_KERNEL_SEPARABLE, never chosen "
+                   "automatically); the exact cell-by-cell tables come from one handle per instance", k, d.kernel);
+    char buf[160];
+    if (const char* mis = shape_mismatch(descs[0], d, buf, sizeof buf))
+      return sfail(why, SDPGPU_ERR_ARG, "instance %d: %s (the instances of a staff batch share one shape and iniStaffNum)", k, mis);
+  }
+  const sdpgpu_desc& d = descs[0];
+  const int32_t A = full_action_count(d);
+  StaffBatch* s = new StaffBatch();
+  try {
+    s->d.assign(descs, descs + n);
+    s->N = n;
+    s->T = d.periods;
+    s->A = A;
+    s->device = d.device;
+    s->use.assign((size_t)n * s->T, -1);
+    s->min_staff.assign((size_t)n * s->T, 0.0);
+    s->min_set.assign((size_t)n * s->T, 0);
+  } catch (...) {
+    delete s;
+    throw;
+  }
+  *out = s;
+  return SDPGPU_OK;
+}
+
+void staff_batch_delete(StaffBatch* s) {
+  if (!s) return;
+  {
+    DeviceScope dev;
+    if (s->allocated || s->d_tabs || !s->owned.empty()) {
+      (void)dev.enter(s->device);
+      if (s->stream) (void)hipStreamSynchronize(s->stream);
+    }
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    for (hipEvent_t e : s->ev_period)
+      if (e) (void)hipEventDestroy(e);
+    for (void* q : s->owned) (void)hipFree(q);
+    if (s->d_tabs) (void)hipFree(s->d_tabs);
+    if (s->d_inst) (void)hipFree(s->d_inst);
+    if (s->d_blk) (void)hipFree(s->d_blk);
+    if (s->d_values) (void)hipFree(s->d_values);
+    if (s->d_policy) (void)hipFree(s->d_policy);
+    if (s->d_gp) (void)hipFree(s->d_gp);
+    if (s->d_ini_out) (void)hipFree(s->d_ini_out);
+    if (s->stream && s->own_stream) (void)hipStreamDestroy(s->stream);
+  }
+  delete s;
+}
+
+int staff_batch_add_table(StaffBatch* s, std::string* err, const double* prob, const int32_t* row_len, int32_t n_rows, int32_t row_stride,
+                          int32_t* out_table) {
+  if (!prob || !out_table || n_rows < 1 || row_stride < 1)
+    return sfail(err, SDPGPU_ERR_ARG, "batch_add_level_pmf: bad argument (prob %s, out_table %s, rows=%d stride=%d)", prob ? "set" : "null",
+                 out_table ? "set" : "null", n_rows, row_stride);
+  if (s->allocated) return sfail(err, SDPGPU_ERR_STATE, "level tables are frozen once the device tables exist");
+  Table tb;
+  tb.len.resize((size_t)n_rows);
+  int32_t maxj = 1;
+  for (int32_t y = 0; y < n_rows; ++y) {
+    const int32_t n = row_len ? row_len[y] : y + 1;
+    if (n < 1 || n > y + 1 || n > row_stride)
+      return sfail(err, SDPGPU_ERR_ARG, "batch_add_level_pmf: row %d has %d entries (1 .. min(y + 1, row_stride) allowed)", y, n);
+    tb.len[(size_t)y] = n;
+    maxj = std::max(maxj, n);
+  }
+  if ((int64_t)n_rows * maxj * 8 >= 2147483647LL)
+    return sfail(err, SDPGPU_ERR_UNSUPPORTED, "batch_add_level_pmf: a table of %d x %d entries reaches 2 GiB (the G kernel uses 32-bit byte offsets)", n_rows, maxj);
+  tb.p.assign((size_t)n_rows * (size_t)maxj, 0.0);
+  for (int32_t y = 0; y < n_rows; ++y)
+    for (int32_t j = 0; j < tb.len[(size_t)y]; ++j) tb.p[(size_t)j * (size_t)n_rows + (size_t)y] = prob[(size_t)y * (size_t)row_stride + (size_t)j];
+  tb.rows = n_rows;
+  tb.maxj = maxj;
+  s->pool.push_back(std::move(tb));
+  *out_table = (int32_t)s->pool.size() - 1;
+  return SDPGPU_OK;
+}
+
+int staff_batch_use_table(StaffBatch* s, std::string* err, int32_t instance, int32_t t, int32_t table) {
+  if (instance < -1 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "batch_use_level_pmf: instance %d outside 0 .. %d (-1: every instance)", instance, s->N - 1);
+  if (t < -1 || t >= s->T) return sfail(err, SDPGPU_ERR_ARG, "batch_use_level_pmf: period index %d outside 0 .. %d (-1: every period)", t, s->T - 1);
+  if (table < 0 || table >= (int32_t)s->pool.size())
+    return sfail(err, SDPGPU_ERR_ARG, "batch_use_level_pmf: table %d is not in the pool (%d tables, sdpgpu_batch_add_level_pmf)", table, (int)s->pool.size());
+  if (s->allocated) return sfail(err, SDPGPU_ERR_STATE, "level tables are frozen once the device tables exist");
+  for (int i = instance < 0 ? 0 : instance; i < (instance < 0 ? s->N : instance + 1); ++i)
+    for (int u = t < 0 ? 0 : t; u < (t < 0 ? s->T : t + 1); ++u) s->use[(size_t)i * s->T + u] = table;
+  s->laid_out = false;
+  return SDPGPU_OK;
+}
+
+int staff_batch_set_min_staff(StaffBatch* s, std::string* err, int32_t instance, int32_t t, double min_staff) {
+  if (instance < 0 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "batch_set_overhead: instance %d outside 0 .. %d", instance, s->N - 1);
+  if (t < 0 || t >= s->T) return sfail(err, SDPGPU_ERR_ARG, "batch_set_overhead: period index %d outside 0 .. %d", t, s->T - 1);
+  if (!(min_staff == std::floor(min_staff)) || std::fabs(min_staff) > 1e9)
+    return sfail(err, SDPGPU_ERR_ARG, "batch_set_overhead: minStaffNum %g of instance %d, period %d must be an integer", min_staff, instance, t + 1);
+  if (s->allocated) return sfail(err, SDPGPU_ERR_STATE, "minStaffNum is frozen once the device tables exist");
+  s->min_staff[(size_t)instance * s->T + t] = min_staff;
+  s->min_set[(size_t)instance * s->T + t] = 1;
+  s->laid_out = false;
+  return SDPGPU_OK;
+}
+
+int staff_batch_grid(const StaffBatch* s, std::string* err, int32_t instance, int32_t period, double* x_lo, int64_t* nx) {
+  if (instance < 0 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: instance %d outside 0 .. %d", instance, s->N - 1);
+  if (period < 1 || period > s->T) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: period %d outside 1 .. %d", period, s->T);
+  if (!x_lo || !nx) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: null output");
+  std::vector<int64_t> lo, n;
+  int missing = -1;
+  boxes_of(s, instance, period, &lo, &n, &missing);
+  if (missing >= 0)
+    return sfail(err, SDPGPU_ERR_STATE, "sdpgpu_batch_grid: level table of instance %d, period %d not set (clamp_inventory = 0: the staff range of period %d "
+                 "grows from the tables before it)", instance, missing + 1, period);
+  *x_lo = (double)lo[(size_t)period - 1];
+  *nx = n[(size_t)period - 1];
+  return SDPGPU_OK;
+}
+
+int64_t staff_batch_num_states(const StaffBatch* s, int32_t instance) {
+  if (instance < 0 || instance >= s->N) return -1;
+  std::vector<int64_t> lo, n;
+  int missing = -1;
+  boxes_of(s, instance, s->T, &lo, &n, &missing);
+  return missing >= 0 ? -1 : n[(size_t)s->T - 1];
+}
+
+int32_t staff_batch_num_actions(const StaffBatch* s, int32_t instance) { return instance >= 0 && instance < s->N ? s->A : -1; }
+
+int staff_batch_plan(StaffBatch* s, std::string* err, int32_t period, sdpgpu_batch_staff_plan* out) {
+  if (!out) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_staff_plan_period: out is null");
+  if (period < 1 || period > s->T) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_staff_plan_period: period %d outside 1 .. %d", period, s->T);
+  std::memset(out, 0, sizeof *out);
+  int rc = layout(s, err);
+  if (rc) return rc;
+  const PeriodPlan& pl = s->plan[(size_t)period - 1];
+  out->tables = pl.tables;
+  out->groups = pl.tables;
+  out->r = pl.R;
+  out->u = pl.U;
+  out->longest_row = pl.longest_row;
+  out->blocks = pl.blocks;
+  out->g_tasks = pl.blocks * pl.g_blocks;
+  out->scan_workgroups = (int64_t)s->N * pl.tiles;
+  out->states = s->nx[(size_t)period - 1];
+  out->levels = out->states + s->A - 1;
+  return SDPGPU_OK;
+}
+
+int staff_batch_set_stream(StaffBatch* s, std::string* err, void* hip_stream) {
+  if (s->own_stream && s->stream) {
+    DeviceScope dev;
+    SHIP_TRY(err, dev.enter(s->device));
+    (void)hipStreamSynchronize(s->stream);
+    (void)hipStreamDestroy(s->stream);
+  }
+  s->stream = (hipStream_t)hip_stream;
+  s->own_stream = false;
+  s->stream_given = true;
+  return SDPGPU_OK;
+}
+
+int staff_batch_set_profiling(StaffBatch* s, int32_t on) {
+  s->profiling = on != 0;
+  return SDPGPU_OK;
+}
+
+int staff_batch_solve(StaffBatch* s, std::string* err, int32_t sync) {
+  int rc = layout(s, err);  // (argument and state errors before the device is touched)
+  if (rc) return rc;
+  DeviceScope dev;
+  SHIP_TRY(err, dev.enter(s->device));
+  rc = allocate(s, err);
+  if (rc) return rc;
+  const int T = s->T;
+  if (s->profiling && s->ev_period.empty()) {
+    s->ev_period.assign((size_t)T + 1, nullptr);
+    for (hipEvent_t& e : s->ev_period) SHIP_TRY(err, hipEventCreate(&e));
+  }
+  s->period_launches = s->periods_run = 0;
+  s->periods_timed = false;
+  SHIP_TRY(err, hipEventRecord(s->ev0, s->stream));
+  for (int t = T - 1; t >= 0; --t) {
+    if (s->profiling) SHIP_TRY(err, hipEventRecord(s->ev_period[(size_t)t + 1], s->stream));
+    const hipError_t e = launch_period(s, t);
+    if (e != hipSuccess) return sfail(err, SDPGPU_ERR_DEVICE, "staff batch period %d: %s", t + 1, hipGetErrorString(e));
+    s->period_launches += 2;
+    s->periods_run++;
+  }
+  if (s->profiling) SHIP_TRY(err, hipEventRecord(s->ev_period[0], s->stream));
+  SHIP_TRY(err, hipEventRecord(s->ev1, s->stream));
+  s->timed = true;
+  s->periods_timed = s->profiling;
+  s->solved = true;
+  if (sync) SHIP_TRY(err, hipStreamSynchronize(s->stream));
+  return SDPGPU_OK;
+}
+
+int staff_batch_synchronize(StaffBatch* s, std::string* err) {
+  if (!s->allocated) return SDPGPU_OK;
+  DeviceScope dev;
+  SHIP_TRY(err, dev.enter(s->device));
+  SHIP_TRY(err, hipStreamSynchronize(s->stream));
+  return SDPGPU_OK;
+}
+
+int staff_batch_values(StaffBatch* s, std::string* err, int32_t instance, int32_t period, double* out, int64_t n) {
+  int rc = read_check(s, err, "sdpgpu_batch_values", instance, period, out, n, true);
+  if (rc) return rc;
+  DeviceScope dev;
+  SHIP_TRY(err, dev.enter(s->device));
+  SHIP_TRY(err, hipStreamSynchronize(s->stream));
+  SHIP_TRY(err, hipMemcpy(out, s->d_values + value_row(s, instance, period - 1), (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  return SDPGPU_OK;
+}
+
+int staff_batch_policy(StaffBatch* s, std::string* err, int32_t instance, int32_t period, int32_t* out, int64_t n) {
+  int rc = read_check(s, err, "sdpgpu_batch_policy", instance, period, out, n, false);
+  if (rc) return rc;
+  DeviceScope dev;
+  SHIP_TRY(err, dev.enter(s->device));
+  SHIP_TRY(err, hipStreamSynchronize(s->stream));
+  SHIP_TRY(err, hipMemcpy(out, s->d_policy + policy_row(s, instance, period - 1), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return SDPGPU_OK;
+}
+
+int staff_batch_initial(StaffBatch* s, std::string* err, double* out_value, int32_t* out_action_index) {
+  if (!out_value || !out_action_index) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_initial: null output");
+  if (!s->solved) return sfail(err, SDPGPU_ERR_STATE, "sdpgpu_batch_initial before sdpgpu_batch_solve");
+  DeviceScope dev;
+  SHIP_TRY(err, dev.enter(s->device));
+  const int N = s->N;
+  const int ini_idx = (int)((int64_t)s->d[0].ini_inventory - s->x_lo[0]);  // (validated at create: inside period 1's box)
+  double* dv = reinterpret_cast<double*>(s->d_ini_out);
+  int32_t* di = reinterpret_cast<int32_t*>(s->d_ini_out + (size_t)N * 8);
+  hipLaunchKernelGGL(sdp::staff_batch_initial_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->d_inst, N, ini_idx,
+                     s->d_values, s->d_policy, dv, di);
+  SHIP_TRY(err, hipGetLastError());
+  std::vector<char> host((size_t)N * 12);
+  SHIP_TRY(err, hipMemcpyAsync(host.data(), s->d_ini_out, host.size(), hipMemcpyDeviceToHost, s->stream));
+  SHIP_TRY(err, hipStreamSynchronize(s->stream));
+  std::memcpy(out_value, host.data(), (size_t)N * 8);
+  std::memcpy(out_action_index, host.data() + (size_t)N * 8, (size_t)N * 4);
+  return SDPGPU_OK;
+}
+
+int staff_batch_stats(StaffBatch* s, std::string* err, sdpgpu_batch_stats* out) {
+  std::memset(out, 0, sizeof *out);
+  out->instances = s->N;
+  out->periods_run = s->periods_run;
+  out->period_launches = s->period_launches;
+  out->cells_evaluated = s->solved ? s->cells : 0;
+  if (s->timed) {
+    DeviceScope dev;
+    SHIP_TRY(err, dev.enter(s->device));
+    SHIP_TRY(err, hipEventSynchronize(s->ev1));
+    float ms = 0;
+    SHIP_TRY(err, hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    out->solve_ms = ms;
+  }
+  return SDPGPU_OK;
+}
+
+double staff_batch_period_ms(StaffBatch* s, std::string* err, int32_t period) {
+  if (period < 1 || period > s->T || !s->periods_timed) {
+    (void)sfail(err, SDPGPU_ERR_STATE, "sdpgpu_batch_period_ms: period %d has no timing (sdpgpu_batch_set_profiling before the solve)", period);
+    return -1.0;
+  }
+  DeviceScope dev;
+  if (dev.enter(s->device) != hipSuccess) return -1.0;
+  // period t was launched between the events t and t - 1 (the sweep runs t = T .. 1)
+  if (hipEventSynchronize(s->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, s->ev_period[(size_t)period], s->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
+  return ms;
+}
+
+}  // namespace sdpgpu_detail

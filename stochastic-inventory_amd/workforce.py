@@ -248,3 +248,152 @@ class SimulatesS:
         res = self.recursion.engine.staff_simulate(k, self.seed, self._ini(iniState), None)
         self.last_results = res
         return float(res[0].mean)
+
+
+def staff_reach_intervals(functor: StaffFunctor, lens_by_period) -> list:
+    """[(L, H)] per period: the staff numbers StaffRecursion.getExpectedValue visits from (1, iniStaffNum) -- one interval a
+    period, as the library computes it for a handle: from the levels y in [L, H + maxHire] the successors are the union of
+    [y - len(y) + 1, y].  lens_by_period[t] = the row lengths of period t's table."""
+    L = H = int(functor.iniStaffNum)
+    out = []
+    for lens in lens_by_period:
+        out.append((L, H))
+        rows = len(lens)
+        top = H + int(functor.maxHireNum)
+        y = np.arange(L, min(top, rows - 1) + 1, dtype=np.int64)
+        low = int((y - lens[y] + 1).min()) if len(y) else None
+        if top > rows - 1:
+            beyond = max(L, rows) - int(lens[rows - 1]) + 1
+            low = beyond if low is None else min(low, beyond)
+        L, H = low, top
+        if functor.clampStaff:
+            L, H = (min(max(v, functor.minX), functor.maxX) for v in (L, H))
+    return out
+
+
+class StaffRecursionBatch:
+    """Many workforce.StaffRecursion objects behind one solve: the body of WorkforceTesting.main's sweep
+    (WorkforceTesting.java:36-124), which builds a StaffRecursion per parameter set and asks each for
+    getExpectedValue(initialState).  `functors[i]` is instance i's StaffFunctor -- one shape for all: hire limit, bounds, clamp
+    and iniStaffNum; the costs and minStaffNum are the instance's own -- and `pmfs[i]` its table (T, rows, stride), or the
+    reference's nested list.  Per-period slices that ARE the same memory (same data pointer, shape and strides: a
+    zero-stride np.broadcast_to view over T, one array handed to many instances) become ONE table of the batch's pool.  The
+    first query runs period t of ALL instances in two kernel launches (StaffBatch, the separable mode); every instance's
+    answers are those of its own StaffRecursion(separable=True), bit for bit.  There is no CPU fallback."""
+
+    def __init__(self, functors, pmfs, T: Optional[int] = None, device: int = -1):
+        from .batch import StaffBatch
+        self.functors = list(functors)
+        if not self.functors:
+            raise ValueError("a batch needs at least one instance")
+        if len(self.functors) != len(pmfs):
+            raise ValueError(f"{len(self.functors)} functors but {len(pmfs)} pmfs")
+        self.pmfs = pmfs
+        tables, use, keys, self._keep = [], [], {}, []
+        self._lens = []  # [pool id]: row lengths
+        for i, pmf in enumerate(pmfs):
+            if isinstance(pmf, np.ndarray) and pmf.ndim == 3 and pmf.dtype == np.float64:
+                table, row_len = pmf, None  # (never copied: the sweep's views share two buffers)
+            else:
+                table, row_len = pack_level_pmf(pmf)
+            if T is None:
+                T = table.shape[0]
+            if table.shape[0] != int(T):
+                raise ValueError(f"pmf of instance {i} has {table.shape[0]} periods, T = {T}")
+            self._keep.append(table)
+            row = []
+            for t in range(int(T)):
+                sl = table[t]
+                key = (sl.__array_interface__["data"][0], sl.shape, sl.strides, None if row_len is None else row_len.tobytes())
+                if key not in keys:
+                    keys[key] = len(tables)
+                    tables.append((sl, row_len))
+                    self._lens.append(np.arange(sl.shape[0], dtype=np.int64) + 1 if row_len is None else np.asarray(row_len, dtype=np.int64))
+                row.append(keys[key])
+            use.append(row)
+        self.T = int(T)
+        self.use = use
+        descs = []
+        for f in self.functors:
+            d = f.to_desc(self.T)
+            d.kernel = _abi.KERNEL_SEPARABLE
+            descs.append(d)
+        self._batch = StaffBatch(descs, tables, use, [list(f.minStaffNum) for f in self.functors], device=device)
+        self._solved = False
+        self._tables = {}
+        self._initial = None
+        self._grid = {}
+
+    def __len__(self):
+        return len(self.functors)
+
+    @property
+    def batch(self):
+        return self._batch
+
+    @property
+    def num_tables(self) -> int:
+        """Tables of the batch's pool."""
+        return len(self._lens)
+
+    def close(self):
+        self._batch.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _solve(self):
+        if not self._solved:
+            self._batch.solve(sync=True)
+            self._solved = True
+
+    def _table(self, i: int, period: int):
+        if (i, period) not in self._tables:
+            self._tables[(i, period)] = (self._batch.values(i, period), self._batch.policy(i, period))
+        return self._tables[(i, period)]
+
+    def initial(self):
+        """(values[n], hires[n]) of (1, iniStaffNum) for all instances: what the sweep records, one gathered copy."""
+        self._solve()
+        if self._initial is None:
+            self._initial = self._batch.initial()
+        return self._initial
+
+    def _lookup(self, i: int, state: StaffState):
+        self._solve()
+        period = state.period
+        if period < 1 or period > self.T:
+            raise IndexError(f"period {period} outside 1..{self.T}")
+        if period == 1 and state.iniStaffNum == self.functors[i].iniStaffNum:
+            val, act = self.initial()
+            return float(val[i]), int(act[i])
+        if period not in self._grid:
+            self._grid[period] = self._batch.grid(i, period)
+        x_lo, nx = self._grid[period]
+        idx = state.iniStaffNum - int(x_lo)
+        if not 0 <= idx < nx:
+            raise KeyError(f"{state!r} lies outside the staff numbers the recursion can reach")
+        v, p = self._table(i, period)
+        return float(v[idx]), int(p[idx])
+
+    def getExpectedValue(self, i: int, state: StaffState) -> float:
+        return self._lookup(i, state)[0]
+
+    def getAction(self, i: int, state: StaffState) -> int:
+        return self._lookup(i, state)[1]
+
+    def getOptTable(self, i: int) -> np.ndarray:
+        """Instance i's rows {period, iniStaffNum, action} of the visited states in comparator order -- what
+        StaffRecursion.getOptTable gives for a handle of the instance."""
+        self._solve()
+        f = self.functors[i]
+        rows = []
+        for period, (L, H) in enumerate(staff_reach_intervals(f, [self._lens[k] for k in self.use[i]]), start=1):
+            x_lo = int(self._batch.grid(i, period)[0])
+            pol = self._table(i, period)[1]
+            x = np.arange(L, H + 1, dtype=np.int64)
+            rows.append(np.stack([np.full(len(x), float(period)), x.astype(np.float64), pol[x - x_lo].astype(np.float64)], axis=1))
+        return np.concatenate(rows, axis=0) if rows else np.zeros((0, 3))

@@ -179,6 +179,36 @@ def staff_testing(T: int = 8, maxHire: int = 1000, rate: float = 0.1) -> StaffWo
     return StaffWorkload(f"staff_testing0_{maxHire + 1}hires_x{T}", f, np.repeat(one, T, axis=0), "WorkforceTesting.main[0] via StaffRecursion")
 
 
+def workforce_testing_sweep(T: int = 8, maxHire: int = 1000) -> List[StaffWorkload]:
+    """WorkforceTesting.main's 216 instances in its loop order (WorkforceTesting.java:17-51): 2 turnover rates (the loop stops
+    at iRate < 2) x 3 fixCost x 3 salary x 3 unitPenalty x 4 minStaffNum rows; one shape (T = 8, hires 0..1000, no clamp,
+    iniStaffNum 0).  Each rate's table is built ONCE and every instance holds a zero-stride view of it over the periods:
+    copies would take 216 x 64 MB."""
+    from .pmf import staff_level_pmf
+    from .workforce import StaffFunctor
+    turnoverRates = [0.1, 0.5, 0.9]
+    fixCosts = [50, 1000, 2000]
+    salarys = [30, 100, 200]
+    unitPenaltys = [50, 250, 2200]
+    minStaffs = [[40, 40, 40, 40, 40, 40, 40, 40], [10, 20, 30, 40, 50, 60, 70, 80], [80, 70, 60, 50, 40, 30, 20, 10],
+                 [40, 50, 80, 60, 40, 50, 80, 60]]
+    m = len(turnoverRates)
+    out = []
+    for iRate in range(2):
+        one = staff_level_pmf([turnoverRates[iRate]], maxHire + 1)[0]
+        table = np.broadcast_to(one, (T,) + one.shape)
+        for iFix in range(m):
+            for iSalary in range(m):
+                for iPenalty in range(3):
+                    for iMinStaff in range(m + 1):
+                        f = StaffFunctor(fixCost=fixCosts[iFix], unitVariCost=20, salary=salarys[iSalary],
+                                         unitPenalty=unitPenaltys[iPenalty], minStaffNum=[minStaffs[iMinStaff][t % 8] for t in range(T)],
+                                         maxHireNum=maxHire, clampStaff=False, iniStaffNum=0)
+                        out.append(StaffWorkload(f"staff_testing{len(out)}_{maxHire + 1}hires_x{T}", f, table,
+                                                 f"WorkforceTesting.main[{len(out)}] via StaffRecursion"))
+    return out
+
+
 # capacitated.CLSP's three lambdas (CLSP.java:251-272) as the HIP device text a driver hands to sdpgpu_create_custom when its
 # lambdas are its own: params = {K, v, h, pi, minInventory, maxInventory, maxOrderQuantity}.  bench.py's `custom_clsp` entry
 # runs configs[1] through this text, i.e. through the reference's actual plugin API (arbitrary closures) instead of the
