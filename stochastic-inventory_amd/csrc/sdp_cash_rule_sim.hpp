@@ -89,13 +89,11 @@ __global__ __launch_bounds__(256) void cash_rule_sim_kernel(CashRuleLaunch L, Si
                                                             const double* __restrict__ c1_tab, const double* __restrict__ c2_tab,
                                                             double* __restrict__ out_sum, double* __restrict__ partial,
                                                             unsigned int* __restrict__ counts) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
-  if (gw >= (int64_t)L.n_rules * L.waves_per_rule) return;  // no workgroup barrier below: a wave may leave on its own
-  const int ri = (int)(gw / L.waves_per_rule);              // (wave-uniform)
-  const uint32_t w = (uint32_t)(gw - (int64_t)ri * L.waves_per_rule);
-  const uint32_t p = w * 64u + (uint32_t)lane;
+  SimWave wv;
+  if (wv.leaves(L.n_rules, L.waves_per_rule)) return;
+  wv.place(L.waves_per_rule);
+  const int ri = wv.ri;
+  const uint32_t p = wv.p;
   const bool live = p < R.n_paths;
   double sum = 0.0;
   if (live) {
@@ -129,12 +127,7 @@ __global__ __launch_bounds__(256) void cash_rule_sim_kernel(CashRuleLaunch L, Si
     }
     out_sum[(int64_t)ri * R.n_paths + p] = sum;
   }
-  const unsigned long long ml = __ballot(live);
-  const double tot = sim_wave_sum(sum);
-  if (lane == 0) {
-    partial[gw] = tot;
-    atomicAdd(&counts[2 * ri], (unsigned int)__popcll(ml));
-  }
+  sim_wave_finish(partial, counts, wv.gw, ri, live, sum);
 }
 
 }  // namespace sdp

@@ -1,8 +1,8 @@
 // sdp_sampler.hpp -- the device sampler of the simulation kernels ("Batched simulation" and "Sampled simulation on a
 // handle"): Philox4x32-10, the keyed bijection sigma of the latin hypercube's shuffle, the two streams of uniforms and the
-// demand of a uniform by binary search in a host-made threshold table -- and the wave total every rollout ends with.  Shared
-// by batch_sim_kernel (sdp_batch_sim.hpp) and sim_sampled_kernel (sdp_sim_sampled.hpp): records and device functions only, no
-// kernels.
+// demand of a uniform by binary search in a host-made threshold table -- and the wave total every rollout ends with, with the
+// wave prologue and epilogue of the rule kernels (sdp_cash_rule_sim.hpp, sdp_xr_sim.hpp, sdp_staff_sim.hpp).  Shared by every
+// simulation kernel: records and device functions only, no kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -121,6 +121,39 @@ __device__ __forceinline__ double sim_wave_sum(double v) {
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
   return v;
+}
+
+// Where a wave of a rule kernel stands (256-thread blocks; the waves of rule r are waves_per_rule * r ..).  A kernel opens with
+//   SimWave wv;  if (wv.leaves(n_rules, waves_per_rule)) return;  wv.place(waves_per_rule);
+// and has no workgroup barrier below that: a wave past the launch's last one may leave on its own.
+struct SimWave {
+  int lane;
+  int64_t gw;  // the wave's place in the launch
+  int ri;      // its rule (wave-uniform)
+  uint32_t p;  // the lane's path (or leaf) of that rule
+  __device__ __forceinline__ SimWave() {
+    lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    gw = (int64_t)blockIdx.x * 4 + wave;
+  }
+  __device__ __forceinline__ bool leaves(int n_rules, uint32_t waves_per_rule) const { return gw >= (int64_t)n_rules * waves_per_rule; }
+  __device__ __forceinline__ void place(uint32_t waves_per_rule) {
+    ri = (int)(gw / waves_per_rule);
+    const uint32_t w = (uint32_t)(gw - (int64_t)ri * waves_per_rule);
+    p = w * 64u + (uint32_t)lane;
+  }
+};
+
+// what a rule kernel's wave ends with: its total into partial[gw], its valid paths onto counts[2 * ri] (one integer atomic)
+template <class RI>
+__device__ __forceinline__ void sim_wave_finish(double* __restrict__ partial, unsigned int* __restrict__ counts, int64_t gw, RI ri, bool valid,
+                                                double sum) {
+  const unsigned long long mv = __ballot(valid);
+  const double tot = sim_wave_sum(sum);
+  if ((threadIdx.x & 63) == 0) {
+    partial[gw] = tot;
+    atomicAdd(&counts[2 * ri], (unsigned int)__popcll(mv));
+  }
 }
 
 }  // namespace sdp

@@ -99,13 +99,11 @@ __global__ __launch_bounds__(256) void staff_sim_kernel(StaffSimLaunch L, const 
                                                         double* __restrict__ out_sum, uint8_t* __restrict__ out_valid,
                                                         int32_t* __restrict__ out_demand, double* __restrict__ partial,
                                                         unsigned int* __restrict__ counts) {
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int64_t gw = (int64_t)blockIdx.x * 4 + wave;
-  if (gw >= (int64_t)L.n_rules * L.waves_per_rule) return;  // no workgroup barrier below: a wave may leave on its own
-  const int ri = (int)(gw / L.waves_per_rule);              // (wave-uniform)
-  const uint32_t w = (uint32_t)(gw - (int64_t)ri * L.waves_per_rule);
-  const uint32_t p = w * 64u + (uint32_t)lane;
+  SimWave wv;
+  if (wv.leaves(L.n_rules, L.waves_per_rule)) return;
+  wv.place(L.waves_per_rule);
+  const int ri = wv.ri;
+  const uint32_t p = wv.p;
   double sum = 0.0;
   bool valid = false;
   if (p < L.n_leaves) {
@@ -149,12 +147,7 @@ __global__ __launch_bounds__(256) void staff_sim_kernel(StaffSimLaunch L, const 
     out_sum[leaf] = sum;
     if (out_valid) out_valid[leaf] = valid ? 1 : 0;
   }
-  const unsigned long long mv = __ballot(valid);
-  const double tot = sim_wave_sum(sum);
-  if (lane == 0) {
-    partial[gw] = tot;
-    atomicAdd(&counts[2 * ri], (unsigned int)__popcll(mv));
-  }
+  sim_wave_finish(partial, counts, wv.gw, ri, valid, sum);
 }
 
 }  // namespace sdp

@@ -3,9 +3,9 @@
 // overdraft drivers' ordering rules (CashSimulation.java:1142-1250).  Definition: DESIGN 4, "User-functor rollouts"; device
 // text: kCustomSim of sdp_custom_src.hpp, compiled by hipRTC around the handle's own text at its first rollout call.  All
 // argument validation comes before the compile, the compile before the solve-state and device checks (hipRTC needs no GPU: a
-// text that does not compile is reported on a box without one).  The draws are sdpgpu_simulate_sampled's (check_stream_args,
-// build_samplers, make_stream, launch_sim_draw) into a device buffer the hipRTC kernel reads; the reduction is the
-// handle's (launch_sim_moments) from wave partials a small precompiled pass forms over the sums with sim_wave_sum.
+// text that does not compile is reported on a box without one).  The draws are sdpgpu_simulate_sampled's (launch_sim_draw) into a
+// device buffer the hipRTC kernel reads; the host frame is RolloutFrame (sdpgpu_sim_host.hpp), which reduces from wave partials
+// that a small precompiled pass forms over the sums.
 #include <hip/hiprtc.h>
 
 #include "sdpgpu_sim_host.hpp"
@@ -37,12 +37,7 @@ __global__ __launch_bounds__(256) void custom_partials_kernel(const double* __re
     v = sums[(int64_t)r * n + p];
     valid = flags ? (flags[p] & 1) != 0 : true;
   }
-  const unsigned long long mv = __ballot(valid);
-  const double tot = sdp::sim_wave_sum(v);
-  if (lane == 0) {
-    partial[(int64_t)r * W + w] = tot;
-    atomicAdd(&counts[2 * r], (unsigned int)__popcll(mv));
-  }
+  sdp::sim_wave_finish(partial, counts, (int64_t)r * W + w, r, valid, v);
 }
 
 int refuse(sdpgpu_handle* h, const char* who, bool rule) {
@@ -102,13 +97,6 @@ int load_sim(sdpgpu_handle* h) {
   return SDPGPU_OK;
 }
 
-int check_solved(sdpgpu_handle* h, const char* who) {
-  if (!h->allocated) return fail(h, SDPGPU_ERR_STATE, "%s: nothing has been solved", who);
-  for (int t = 0; t < h->T; ++t)
-    if (!h->policy_done[t]) return fail(h, SDPGPU_ERR_STATE, "%s: period %d has not been computed", who, t + 1);
-  return SDPGPU_OK;
-}
-
 int check_demand_cap(sdpgpu_handle* h, const char* who, int64_t n_paths) {
   if (n_paths * (int64_t)h->T > kCustomSimMaxDemands)
     return fail(h, SDPGPU_ERR_UNSUPPORTED, "%s: n_paths * T = %lld exceeds %lld (the demand buffer is resident)", who,
@@ -121,11 +109,9 @@ int table_rollout(sdpgpu_handle* h, const char* who, int64_t n_paths, const doub
                   const double* discount, double ini_x, double ini_cash, double ini_preq, sdpgpu_sim_result* result, double* out_sum,
                   uint8_t* out_valid, double* out_demand) {
   const int T = h->T;
-  std::vector<sdp::SimSampler> rec;
-  std::vector<double> thr, val;
-  if (!demand) build_samplers(h, &rec, &thr, &val);
-  std::vector<double> disc((size_t)T, 1.0);  // NULL = all 1.0: the bits of an explicit array of ones
-  if (discount) disc.assign(discount, discount + T);
+  HostSamplers samp;
+  if (!demand) build_samplers(h, &samp);
+  const std::vector<double> disc = discounts_or_ones(discount, T);
   int rc = compile_sim(h, who);
   if (rc) return rc;
   rc = check_solved(h, who);
@@ -163,78 +149,39 @@ int table_rollout(sdpgpu_handle* h, const char* who, int64_t n_paths, const doub
     per[(size_t)t].pol_off = (long long)h->per[t].pol_off - h->per[t].lo;
     per[(size_t)t].disc = disc[(size_t)t];
   }
-  const size_t nn = (size_t)n_paths, np = std::max<size_t>(h->custom_params.size(), 1);
-  const uint32_t n = (uint32_t)n_paths;
-  const uint32_t W = (n + 63u) / 64u;
-  Carve c;
-  const size_t o_per = c.take(per.size() * sizeof(sdp::CustomSimPeriod)), o_samp = c.take(rec.size() * sizeof(sdp::SimSampler));
-  const size_t o_thr = c.take(thr.size() * 8), o_val = c.take(val.size() * 8), o_user = c.take(np * 8);
-  const size_t o_cnt = c.take(2 * sizeof(unsigned int)), o_res = c.take(2 * 8), o_part = c.take((size_t)W * 8);
-  const size_t o_sum = c.take(nn * 8), o_flag = c.take(nn), o_dem = c.take(nn * T * 8);
-  rc = sim_scratch(h, c.at);
+  RolloutFrame<sdpgpu_handle> f(h, (uint32_t)n_paths, 1);
+  const size_t elems = (size_t)f.n * T;
+  const auto p_per = f.put(per.data(), per.size());
+  const auto p_samp = f.put_samplers(samp, true);
+  const auto p_user = f.put(h->custom_params.data(), h->custom_params.size(), 1);
+  const auto p_flag = f.take<uint8_t>(f.n);
+  const auto p_dem = f.put(demand, elems, elems);
+  rc = f.begin();
   if (rc) return rc;
-  if (!h->sim_ev0) {
-    HIP_TRY(h, hipEventCreate(&h->sim_ev0));
-    HIP_TRY(h, hipEventCreate(&h->sim_ev1));
-  }
-  char* base = h->d_sim_scratch;
   hipStream_t st = h->stream;
-  HIP_TRY(h, hipMemcpyAsync(base + o_per, per.data(), per.size() * sizeof(sdp::CustomSimPeriod), hipMemcpyHostToDevice, st));
-  if (!rec.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_samp, rec.data(), rec.size() * sizeof(sdp::SimSampler), hipMemcpyHostToDevice, st));
-  if (!thr.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice, st));
-  if (!val.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_val, val.data(), val.size() * 8, hipMemcpyHostToDevice, st));
-  if (!h->custom_params.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_user, h->custom_params.data(), h->custom_params.size() * 8, hipMemcpyHostToDevice, st));
-  if (demand) HIP_TRY(h, hipMemcpyAsync(base + o_dem, demand, nn * T * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(h, hipMemsetAsync(base + o_cnt, 0, 2 * sizeof(unsigned int), st));
-  const sdp::CustomSimPeriod* d_per = reinterpret_cast<const sdp::CustomSimPeriod*>(base + o_per);
-  const sdp::SimSampler* d_samp = reinterpret_cast<const sdp::SimSampler*>(base + o_samp);
-  const double* d_thr = reinterpret_cast<const double*>(base + o_thr);
-  const double* d_val = reinterpret_cast<const double*>(base + o_val);
-  const double* d_user = reinterpret_cast<const double*>(base + o_user);
-  unsigned int* d_cnt = reinterpret_cast<unsigned int*>(base + o_cnt);
-  double* d_res = reinterpret_cast<double*>(base + o_res);
-  double* d_part = reinterpret_cast<double*>(base + o_part);
-  double* d_sum = reinterpret_cast<double*>(base + o_sum);
-  uint8_t* d_flag = reinterpret_cast<uint8_t*>(base + o_flag);
-  double* d_dem = reinterpret_cast<double*>(base + o_dem);
-  HIP_TRY(h, hipEventRecord(h->sim_ev0, st));
-  if (!demand) HIP_TRY(h, launch_sim_draw(st, mode, make_stream((int32_t)n_paths, seed, first_path), T, d_samp, d_thr, d_val, d_dem, nullptr));
+  const sdp::CustomSimPeriod* d_per = f[p_per];
+  const double *d_user = f[p_user], *d_dem = f[p_dem];
+  double* d_sum = f.d_sum;
+  uint8_t* d_flag = f[p_flag];
+  rc = f.start();
+  if (rc) return rc;
+  if (!demand)
+    HIP_TRY(h, launch_sim_draw(st, mode, make_stream((int32_t)n_paths, seed, first_path), T, f[p_samp.rec], f[p_samp.thr], f[p_samp.val],
+                               f[p_dem], nullptr));
   {
     int Ti = T, fk = first_k;
     const int32_t* pol = h->d_policy;
-    const double* dem_c = d_dem;
     long long ln = (long long)n_paths;
-    void* args[] = {&d_per, &Ti, &pol, &d_user, &dem_c, &ln, &idx0, &ini_x, &ini_cash, &ini_preq, &fk, &d_sum, &d_flag};
+    void* args[] = {&d_per, &Ti, &pol, &d_user, &d_dem, &ln, &idx0, &ini_x, &ini_cash, &ini_preq, &fk, &d_sum, &d_flag};
     HIP_TRY(h, hipModuleLaunchKernel(h->custom_sim, (unsigned)((n_paths + 255) / 256), 1, 1, 256, 1, 1, 0, st, args, nullptr));
   }
   if (result) {
-    hipLaunchKernelGGL(custom_partials_kernel, dim3((W + 3) / 4, 1), dim3(256), 0, st, d_sum, d_flag, n, W, d_part, d_cnt);
+    hipLaunchKernelGGL(custom_partials_kernel, dim3((f.W + 3) / 4, 1), dim3(256), 0, st, d_sum, d_flag, f.n, f.W, f.d_part, f.d_cnt);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, launch_sim_moments(st, d_sum, n, d_part, d_cnt, d_res));
   }
-  HIP_TRY(h, hipEventRecord(h->sim_ev1, st));
-  double res[2] = {0, 0};
-  unsigned int cnt[2] = {0, 0};
-  if (result) {
-    HIP_TRY(h, hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
-  }
-  if (out_sum) HIP_TRY(h, hipMemcpyAsync(out_sum, d_sum, nn * 8, hipMemcpyDeviceToHost, st));
-  if (out_valid) HIP_TRY(h, hipMemcpyAsync(out_valid, d_flag, nn, hipMemcpyDeviceToHost, st));
-  if (out_demand) HIP_TRY(h, hipMemcpyAsync(out_demand, d_dem, nn * T * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(h, hipStreamSynchronize(st));
-  if (result) {
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->sim_ev0, h->sim_ev1));
-    result->n_paths = (int32_t)n_paths;
-    result->n_valid = (int32_t)cnt[0];
-    result->n_lost = 0;
-    result->reserved = 0;
-    result->mean = res[0];
-    result->m2 = res[1];
-    result->kernel_ms = ms;
-  }
-  return SDPGPU_OK;
+  f.download(out_valid, d_flag, f.n);
+  f.download(out_demand, d_dem, elems * 8);
+  return f.finish(result, out_sum);
 }
 
 }  // namespace
@@ -305,17 +252,11 @@ int sdpgpu_custom_rule_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed
         return fail(h, SDPGPU_ERR_ARG, "%s: form[%d] = %d (SDPGPU_ORULE_SS 0, SDPGPU_ORULE_SCS 1, SDPGPU_ORULE_SCS1S2 2)", who, r, form[r]);
       scalars_read = scalars_read || form[r] != SDPGPU_ORULE_SCS1S2;
     }
-    for (int r = 0; r < n_rules; ++r)
-      for (int t = 0; t < T; ++t)
-        for (int k = 0; k < 4; ++k) {
-          const double v = rule[((size_t)r * T + t) * 4 + k];
-          if (!std::isfinite(v)) return fail(h, SDPGPU_ERR_ARG, "%s: rule[%d][%d][%d] = %g is not finite", who, r, t, k, v);
-        }
+    rc = check_finite(h, who, "rule", rule, (size_t)n_rules * T * 4, {(size_t)T, 4});
+    if (rc) return rc;
     if (!std::isfinite(ini_x)) return fail(h, SDPGPU_ERR_ARG, "%s: ini_x = %g is not finite", who, ini_x);
     if (!std::isfinite(ini_cash)) return fail(h, SDPGPU_ERR_ARG, "%s: ini_cash = %g is not finite", who, ini_cash);
-    if (discount)
-      for (int t = 0; t < T; ++t)
-        if (!std::isfinite(discount[t])) return fail(h, SDPGPU_ERR_ARG, "%s: discount[%d] = %g is not finite", who, t, discount[t]);
+    if (discount && (rc = check_finite(h, who, "discount", discount, (size_t)T))) return rc;
     if (scalars_read) {
       if (!std::isfinite(min_cash_required)) return fail(h, SDPGPU_ERR_ARG, "%s: min_cash_required = %g is not finite", who, min_cash_required);
       if (!std::isfinite(fix_order_cost)) return fail(h, SDPGPU_ERR_ARG, "%s: fix_order_cost = %g is not finite", who, fix_order_cost);
@@ -326,11 +267,9 @@ int sdpgpu_custom_rule_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed
     if (rc) return rc;
     rc = check_demand_cap(h, who, n_paths);
     if (rc) return rc;
-    std::vector<sdp::SimSampler> rec;
-    std::vector<double> thr, val;
-    build_samplers(h, &rec, &thr, &val);
-    std::vector<double> disc((size_t)T, 1.0);  // NULL = all 1.0: the bits of an explicit array of ones
-    if (discount) disc.assign(discount, discount + T);
+    HostSamplers samp;
+    build_samplers(h, &samp);
+    const std::vector<double> disc = discounts_or_ones(discount, T);
     rc = compile_sim(h, who);
     if (rc) return rc;
 
@@ -341,7 +280,6 @@ int sdpgpu_custom_rule_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed
     rc = load_sim(h);
     if (rc) return rc;
     const uint32_t n = (uint32_t)n_paths;
-    const uint32_t W = (n + 63u) / 64u;
     sdp::CustomRuleLaunch L{};
     L.ini_x = ini_x;
     L.ini_cash = ini_cash;
@@ -354,73 +292,31 @@ int sdpgpu_custom_rule_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed
     L.n_rules = n_rules;
     L.n_paths = n;
 
-    const size_t nr = (size_t)n_rules, nn = (size_t)n, np = std::max<size_t>(h->custom_params.size(), 1);
-    Carve c;
-    const size_t o_samp = c.take(rec.size() * sizeof(sdp::SimSampler)), o_thr = c.take(thr.size() * 8), o_val = c.take(val.size() * 8);
-    const size_t o_user = c.take(np * 8), o_disc = c.take((size_t)T * 8);
-    const size_t o_form = c.take(nr * sizeof(int32_t)), o_rule = c.take(nr * T * 4 * 8);
-    const size_t o_cnt = c.take(2 * nr * sizeof(unsigned int)), o_res = c.take(2 * nr * 8), o_part = c.take(nr * W * 8);
-    const size_t o_sum = c.take(nr * nn * 8), o_dem = c.take(nn * T * 8);
-    rc = sim_scratch(h, c.at);
+    RolloutFrame<sdpgpu_handle> f(h, n, (size_t)n_rules);
+    const size_t elems = (size_t)n * T;
+    const auto p_samp = f.put_samplers(samp, true);
+    const auto p_user = f.put(h->custom_params.data(), h->custom_params.size(), 1);
+    const auto p_disc = f.put(disc.data(), disc.size());
+    const auto p_form = f.put(form, f.nr);
+    const auto p_rule = f.put(rule, f.nr * T * 4), p_dem = f.take<double>(elems);
+    rc = f.begin();
     if (rc) return rc;
-    if (!h->sim_ev0) {
-      HIP_TRY(h, hipEventCreate(&h->sim_ev0));
-      HIP_TRY(h, hipEventCreate(&h->sim_ev1));
-    }
-    char* base = h->d_sim_scratch;
     hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(base + o_samp, rec.data(), rec.size() * sizeof(sdp::SimSampler), hipMemcpyHostToDevice, st));
-    if (!thr.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice, st));
-    if (!val.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_val, val.data(), val.size() * 8, hipMemcpyHostToDevice, st));
-    if (!h->custom_params.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_user, h->custom_params.data(), h->custom_params.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(base + o_disc, disc.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(base + o_form, form, nr * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(base + o_rule, rule, nr * T * 4 * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemsetAsync(base + o_cnt, 0, 2 * nr * sizeof(unsigned int), st));
-    const sdp::SimSampler* d_samp = reinterpret_cast<const sdp::SimSampler*>(base + o_samp);
-    const double* d_thr = reinterpret_cast<const double*>(base + o_thr);
-    const double* d_val = reinterpret_cast<const double*>(base + o_val);
-    const double* d_user = reinterpret_cast<const double*>(base + o_user);
-    const double* d_disc = reinterpret_cast<const double*>(base + o_disc);
-    const int32_t* d_form = reinterpret_cast<const int32_t*>(base + o_form);
-    const double* d_rule = reinterpret_cast<const double*>(base + o_rule);
-    unsigned int* d_cnt = reinterpret_cast<unsigned int*>(base + o_cnt);
-    double* d_res = reinterpret_cast<double*>(base + o_res);
-    double* d_part = reinterpret_cast<double*>(base + o_part);
-    double* d_sum = reinterpret_cast<double*>(base + o_sum);
-    double* d_dem = reinterpret_cast<double*>(base + o_dem);
-    HIP_TRY(h, hipEventRecord(h->sim_ev0, st));
-    HIP_TRY(h, launch_sim_draw(st, mode, make_stream(n_paths, seed, first_path), T, d_samp, d_thr, d_val, d_dem, nullptr));
+    const double *d_user = f[p_user], *d_disc = f[p_disc], *d_rule = f[p_rule], *d_dem = f[p_dem];
+    const int32_t* d_form = f[p_form];
+    double* d_sum = f.d_sum;
+    rc = f.start();
+    if (rc) return rc;
+    HIP_TRY(h, launch_sim_draw(st, mode, make_stream(n_paths, seed, first_path), T, f[p_samp.rec], f[p_samp.thr], f[p_samp.val], f[p_dem], nullptr));
     {
-      const double* dem_c = d_dem;
-      void* args[] = {&L, &d_user, &d_disc, &dem_c, &d_form, &d_rule, &d_sum};
+      void* args[] = {&L, &d_user, &d_disc, &d_dem, &d_form, &d_rule, &d_sum};
       HIP_TRY(h, hipModuleLaunchKernel(h->custom_rule_sim, (n + 255u) / 256u, (unsigned)n_rules, 1, 256, 1, 1, 0, st, args, nullptr));
     }
     const uint8_t* no_flags = nullptr;
-    hipLaunchKernelGGL(custom_partials_kernel, dim3((W + 3) / 4, (unsigned)n_rules), dim3(256), 0, st, d_sum, no_flags, n, W, d_part, d_cnt);
+    hipLaunchKernelGGL(custom_partials_kernel, dim3((f.W + 3) / 4, (unsigned)n_rules), dim3(256), 0, st, d_sum, no_flags, n, f.W, f.d_part, f.d_cnt);
     HIP_TRY(h, hipGetLastError());
-    // per rule, as sdpgpu_simulate_sampled: mean = (partials in the fixed order) / n; m2 = a second pass over the sums
-    for (size_t r = 0; r < nr; ++r) HIP_TRY(h, launch_sim_moments(st, d_sum + r * nn, n, d_part + r * W, d_cnt + 2 * r, d_res + 2 * r));
-    HIP_TRY(h, hipEventRecord(h->sim_ev1, st));
-    std::vector<double> res(2 * nr, 0.0);
-    std::vector<unsigned int> cnt(2 * nr, 0u);
-    HIP_TRY(h, hipMemcpyAsync(res.data(), d_res, 2 * nr * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(cnt.data(), d_cnt, 2 * nr * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    if (out_sum) HIP_TRY(h, hipMemcpyAsync(out_sum, d_sum, nr * nn * 8, hipMemcpyDeviceToHost, st));
-    if (out_demand) HIP_TRY(h, hipMemcpyAsync(out_demand, d_dem, nn * T * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->sim_ev0, h->sim_ev1));
-    for (size_t r = 0; r < nr; ++r) {
-      results[r].n_paths = n_paths;
-      results[r].n_valid = (int32_t)cnt[2 * r];  // every path of a rule: nothing is tested against a grid
-      results[r].n_lost = 0;
-      results[r].reserved = 0;
-      results[r].mean = res[2 * r];
-      results[r].m2 = res[2 * r + 1];
-      results[r].kernel_ms = ms;
-    }
-    return SDPGPU_OK;
+    f.download(out_demand, d_dem, elems * 8);
+    return f.finish(results, out_sum);  // (n_valid: every path of a rule -- nothing is tested against a grid)
   });
 }
 

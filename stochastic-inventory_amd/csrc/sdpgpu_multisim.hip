@@ -4,8 +4,7 @@
 // "Two-product rollout").  The descriptor is read by the solver's own checks (multilead_problem / multicash_problem of
 // sdpgpu_sparse.hip), errors go through sdpgpu_multilead_last_error and every entry point sits behind ml_guard, as the three
 // solves do.  All validation comes before the first device call.  The path-count refusals, the stream record, the threshold
-// table of a tile, the scratch block with its carving and the fixed-order reduction are those of the other rollouts
-// (sdpgpu_sim_host.hpp; launch_sim_moments of sdpgpu_simsample.hip).
+// table of a tile and the host frame (RolloutFrame) are those of the other rollouts (sdpgpu_sim_host.hpp).
 #include <cstdarg>
 
 #include "sdpgpu_sim_host.hpp"
@@ -44,10 +43,16 @@ int mfail(int code, const char* fmt, ...) {
 
 }  // namespace
 
-// the error sink of the shared host helpers (check_n_paths, no_device, sim_scratch) for this owner
+// the error sink of the shared host helpers (check_n_paths, no_device, RolloutFrame) for this owner, and its timing events: the
+// pair its create made
 template <class... A>
 int sim_fail(sdpgpu_multi_policy*, int code, const char* fmt, A... a) {
   return mfail(code, fmt, a...);
+}
+inline hipError_t sim_events(sdpgpu_multi_policy* p, hipEvent_t* ev0, hipEvent_t* ev1) {
+  *ev0 = p->ev0;
+  *ev1 = p->ev1;
+  return hipSuccess;
 }
 
 namespace {
@@ -241,17 +246,15 @@ int simulate_body(const char* who, sdpgpu_multi_policy* p, int32_t n_paths, uint
     rc = check_n_paths(p, who, n_paths);
     if (rc) return rc;
     if (!d1 || !d2) return mfail(SDPGPU_ERR_ARG, "%s: null argument (d1, d2)", who);
-    for (size_t e = 0; e < (size_t)n_paths * T; ++e) {
-      if (!std::isfinite(d1[e])) return mfail(SDPGPU_ERR_ARG, "%s: d1[%zu][%zu] = %g is not finite", who, e / (size_t)T, e % (size_t)T, d1[e]);
-      if (!std::isfinite(d2[e])) return mfail(SDPGPU_ERR_ARG, "%s: d2[%zu][%zu] = %g is not finite", who, e / (size_t)T, e % (size_t)T, d2[e]);
-    }
+    // (element by element, d1 before d2)
+    const size_t elems = (size_t)n_paths * T, e1 = first_not_finite(d1, elems), e2 = first_not_finite(d2, elems);
+    if (e2 < e1) return not_finite(p, who, "d2", d2, e2, {(size_t)T});
+    if (e1 < elems) return not_finite(p, who, "d1", d1, e1, {(size_t)T});
   } else {
     rc = check_stream(p, who, n_paths, mode, first_path);
     if (rc) return rc;
   }
-  if (discount)
-    for (int t = 0; t < T; ++t)
-      if (!std::isfinite(discount[t])) return mfail(SDPGPU_ERR_ARG, "%s: discount[%d] = %g is not finite", who, t, discount[t]);
+  if (discount && (rc = check_finite(p, who, "discount", discount, (size_t)T))) return rc;
   const int source = given ? sdp_multi::MS_SOURCE_GIVEN : mode == SDPGPU_SAMPLE_RANDOM ? sdp_multi::MS_SOURCE_RANDOM : sdp_multi::MS_SOURCE_LHS;
   const sdp_multi::MultiSimLaunch L = make_launch(p, discount);
 
@@ -259,57 +262,26 @@ int simulate_body(const char* who, sdpgpu_multi_policy* p, int32_t n_paths, uint
   if (rc) return rc;
   DeviceScope dev;
   MS_TRY(dev.enter(p->device));
-  const uint32_t n = (uint32_t)n_paths, W = (n + 63u) / 64u;
-  const size_t elems = (size_t)n * T;
-  Carve c;
-  const size_t o_g1 = c.take(given ? elems * 8 : 0), o_g2 = c.take(given ? elems * 8 : 0);
-  const size_t o_cnt = c.take(2 * sizeof(unsigned int)), o_res = c.take(2 * 8), o_part = c.take((size_t)W * 8);
-  const size_t o_sum = c.take((size_t)n * 8), o_val = c.take(n);
-  rc = sim_scratch(p, c.at);
+  RolloutFrame<sdpgpu_multi_policy> f(p, (uint32_t)n_paths, 1);
+  const size_t elems = (size_t)f.n * T;
+  const auto p_g1 = f.put(given ? d1 : nullptr, elems), p_g2 = f.put(given ? d2 : nullptr, elems);
+  const auto p_valid = f.take<uint8_t>(f.n);
+  rc = f.begin();
   if (rc) return rc;
-  char* base = p->d_sim_scratch;
   hipStream_t st = p->stream;
-  if (given) {
-    MS_TRY(hipMemcpyAsync(base + o_g1, d1, elems * 8, hipMemcpyHostToDevice, st));
-    MS_TRY(hipMemcpyAsync(base + o_g2, d2, elems * 8, hipMemcpyHostToDevice, st));
-  }
-  MS_TRY(hipMemsetAsync(base + o_cnt, 0, 2 * sizeof(unsigned int), st));
-  const double* g1 = given ? reinterpret_cast<const double*>(base + o_g1) : nullptr;
-  const double* g2 = given ? reinterpret_cast<const double*>(base + o_g2) : nullptr;
-  unsigned int* d_cnt = reinterpret_cast<unsigned int*>(base + o_cnt);
-  double* d_res = reinterpret_cast<double*>(base + o_res);
-  double* d_part = reinterpret_cast<double*>(base + o_part);
-  double* d_sum = reinterpret_cast<double*>(base + o_sum);
-  uint8_t* d_valid = reinterpret_cast<uint8_t*>(base + o_val);
   const sdp::SimStream R = make_stream(n_paths, seed, given ? 0 : first_path);
   const sdp_multi::PolicyTable H = table_of(p);
-  const dim3 grid((W + 3u) / 4u);
-  MS_TRY(hipEventRecord(p->ev0, st));
+  const dim3 grid((f.W + 3u) / 4u);
+  rc = f.start();
+  if (rc) return rc;
   if (L.P.model == 1)
-    MS_TRY(launch_sim<1>(source, grid, st, L, R, H, p->d_thr, p->d_dem, g1, g2, d_sum, d_valid, d_part, d_cnt));
+    MS_TRY(launch_sim<1>(source, grid, st, L, R, H, p->d_thr, p->d_dem, f[p_g1], f[p_g2], f.d_sum, f[p_valid], f.d_part, f.d_cnt));
   else if (L.P.model == 2)
-    MS_TRY(launch_sim<2>(source, grid, st, L, R, H, p->d_thr, p->d_dem, g1, g2, d_sum, d_valid, d_part, d_cnt));
+    MS_TRY(launch_sim<2>(source, grid, st, L, R, H, p->d_thr, p->d_dem, f[p_g1], f[p_g2], f.d_sum, f[p_valid], f.d_part, f.d_cnt));
   else
-    MS_TRY(launch_sim<0>(source, grid, st, L, R, H, p->d_thr, p->d_dem, g1, g2, d_sum, d_valid, d_part, d_cnt));
-  MS_TRY(launch_sim_moments(st, d_sum, n, d_part, d_cnt, d_res));
-  MS_TRY(hipEventRecord(p->ev1, st));
-  double res[2] = {0, 0};
-  unsigned int cnt[2] = {0, 0};
-  MS_TRY(hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, st));
-  MS_TRY(hipMemcpyAsync(cnt, d_cnt, 2 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-  if (out_sum) MS_TRY(hipMemcpyAsync(out_sum, d_sum, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  if (out_valid) MS_TRY(hipMemcpyAsync(out_valid, d_valid, n, hipMemcpyDeviceToHost, st));
-  MS_TRY(hipStreamSynchronize(st));
-  float ms = 0;
-  MS_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-  result->n_paths = n_paths;
-  result->n_valid = (int32_t)cnt[0];
-  result->n_lost = 0;
-  result->reserved = 0;
-  result->mean = res[0];
-  result->m2 = res[1];
-  result->kernel_ms = ms;
-  return SDPGPU_OK;
+    MS_TRY(launch_sim<0>(source, grid, st, L, R, H, p->d_thr, p->d_dem, f[p_g1], f[p_g2], f.d_sum, f[p_valid], f.d_part, f.d_cnt));
+  f.download(out_valid, f[p_valid], f.n);
+  return f.finish(result, out_sum);
 }
 
 }  // namespace
@@ -360,27 +332,22 @@ int sdpgpu_multi_policy_lookup(sdpgpu_multi_policy* p, int64_t n, const int32_t*
     DeviceScope dev;
     MS_TRY(dev.enter(p->device));
     const size_t nn = (size_t)n;
-    Carve c;
-    size_t o_d[5];
-    for (int j = 0; j < 5; ++j) o_d[j] = c.take(nn * 8);
-    const size_t o_per = c.take(nn * 4), o_a1 = c.take(nn * 4), o_a2 = c.take(nn * 4), o_f = c.take(nn);
-    rc = sim_scratch(p, c.at);
-    if (rc) return rc;
-    char* base = p->d_sim_scratch;
-    hipStream_t st = p->stream;
+    RolloutFrame<sdpgpu_multi_policy> f(p, 0, 0);
     const double* src[5] = {i1, i2, q1, q2, cash};
-    for (int j = 0; j < 5; ++j) MS_TRY(hipMemcpyAsync(base + o_d[j], src[j], nn * 8, hipMemcpyHostToDevice, st));
-    MS_TRY(hipMemcpyAsync(base + o_per, period, nn * 4, hipMemcpyHostToDevice, st));
-    auto dp = [&](int j) { return reinterpret_cast<const double*>(base + o_d[j]); };
-    hipLaunchKernelGGL(sdp_multi::multi_lookup_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, table_of(p), n,
-                       reinterpret_cast<const int32_t*>(base + o_per), dp(0), dp(1), dp(2), dp(3), dp(4), reinterpret_cast<int32_t*>(base + o_a1),
-                       reinterpret_cast<int32_t*>(base + o_a2), reinterpret_cast<uint8_t*>(base + o_f));
+    Part<double> p_d[5];
+    for (int j = 0; j < 5; ++j) p_d[j] = f.put(src[j], nn);
+    const auto p_per = f.put(period, nn);
+    const auto p_a1 = f.take<int32_t>(nn), p_a2 = f.take<int32_t>(nn);
+    const auto p_f = f.take<uint8_t>(nn);
+    rc = f.begin();
+    if (rc) return rc;
+    hipLaunchKernelGGL(sdp_multi::multi_lookup_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, p->stream, table_of(p), n, f[p_per], f[p_d[0]],
+                       f[p_d[1]], f[p_d[2]], f[p_d[3]], f[p_d[4]], f[p_a1], f[p_a2], f[p_f]);
     MS_TRY(hipGetLastError());
-    MS_TRY(hipMemcpyAsync(a1, base + o_a1, nn * 4, hipMemcpyDeviceToHost, st));
-    MS_TRY(hipMemcpyAsync(a2, base + o_a2, nn * 4, hipMemcpyDeviceToHost, st));
-    MS_TRY(hipMemcpyAsync(found, base + o_f, nn, hipMemcpyDeviceToHost, st));
-    MS_TRY(hipStreamSynchronize(st));
-    return SDPGPU_OK;
+    f.download(a1, f[p_a1], nn * 4);
+    f.download(a2, f[p_a2], nn * 4);
+    f.download(found, f[p_f], nn);
+    return f.deliver();
   });
 }
 
@@ -416,27 +383,23 @@ int sdpgpu_multi_policy_sample(sdpgpu_multi_policy* p, int32_t n_paths, uint64_t
     DeviceScope dev;
     MS_TRY(dev.enter(p->device));
     const size_t elems = (size_t)n_paths * p->pb.T;
-    Carve c;
-    const size_t o_1 = c.take(elems * 8), o_2 = c.take(elems * 8), o_u = c.take(out_u ? elems * 8 : 0);
-    rc = sim_scratch(p, c.at);
+    RolloutFrame<sdpgpu_multi_policy> f(p, (uint32_t)n_paths, 0);
+    const auto p_1 = f.take<double>(elems), p_2 = f.take<double>(elems), p_u = f.take<double>(out_u ? elems : 0);
+    rc = f.begin();
     if (rc) return rc;
-    char* base = p->d_sim_scratch;
-    hipStream_t st = p->stream;
     const sdp::SimStream R = make_stream(n_paths, seed, first_path);
-    double* d_1 = reinterpret_cast<double*>(base + o_1);
-    double* d_2 = reinterpret_cast<double*>(base + o_2);
-    double* d_u = out_u ? reinterpret_cast<double*>(base + o_u) : nullptr;
     const dim3 grid(((unsigned)n_paths + 255u) / 256u);
     if (mode == SDPGPU_SAMPLE_RANDOM)
-      hipLaunchKernelGGL((sdp_multi::multi_sample_kernel<sdp_multi::MS_SOURCE_RANDOM>), grid, dim3(256), 0, st, L, R, p->d_thr, p->d_dem, d_1, d_2, d_u);
+      hipLaunchKernelGGL((sdp_multi::multi_sample_kernel<sdp_multi::MS_SOURCE_RANDOM>), grid, dim3(256), 0, p->stream, L, R, p->d_thr, p->d_dem, f[p_1],
+                         f[p_2], f[p_u]);
     else
-      hipLaunchKernelGGL((sdp_multi::multi_sample_kernel<sdp_multi::MS_SOURCE_LHS>), grid, dim3(256), 0, st, L, R, p->d_thr, p->d_dem, d_1, d_2, d_u);
+      hipLaunchKernelGGL((sdp_multi::multi_sample_kernel<sdp_multi::MS_SOURCE_LHS>), grid, dim3(256), 0, p->stream, L, R, p->d_thr, p->d_dem, f[p_1],
+                         f[p_2], f[p_u]);
     MS_TRY(hipGetLastError());
-    MS_TRY(hipMemcpyAsync(out_d1, d_1, elems * 8, hipMemcpyDeviceToHost, st));
-    MS_TRY(hipMemcpyAsync(out_d2, d_2, elems * 8, hipMemcpyDeviceToHost, st));
-    if (out_u) MS_TRY(hipMemcpyAsync(out_u, d_u, elems * 8, hipMemcpyDeviceToHost, st));
-    MS_TRY(hipStreamSynchronize(st));
-    return SDPGPU_OK;
+    f.download(out_d1, f[p_1], elems * 8);
+    f.download(out_d2, f[p_2], elems * 8);
+    f.download(out_u, f[p_u], elems * 8);
+    return f.deliver();
   });
 }
 

@@ -1,10 +1,18 @@
-// sdpgpu_sim_host.hpp -- what the host code of the two simulation translation units shares (sdpgpu_batch.hip: an sdpgpu_batch;
-// sdpgpu_simsample.hip: an sdpgpu_handle): the exception barrier, the device scope, the path-count refusals, the stream record,
-// the threshold table of a pmf tile, the sampler specs an owner keeps, and the grow-only scratch block with its carving.  The
-// templates take the OWNER (handle or batch) and report through its own error sink.  Internal, header only.
+// sdpgpu_sim_host.hpp -- what the host code of the simulation translation units shares.  By every rollout owner (sdpgpu_batch.hip:
+// an sdpgpu_batch; the handle rollouts sdpgpu_simsample.hip, sdpgpu_cashrulesim.hip, sdpgpu_xrsim.hip, sdpgpu_staffsim.hip,
+// sdpgpu_customsim.hip: an sdpgpu_handle; sdpgpu_multisim.hip: an sdpgpu_multi_policy): the exception barrier, the device scope,
+// the path-count refusals, the stream record, the threshold table of a pmf tile and the grow-only scratch block.  By the handle
+// and policy rollouts: RolloutFrame, the ONE host frame of a rollout call -- the carving of the scratch block with typed access
+// and uploads, the two timing events, the zeroed counters, the fixed-order reduction of every rule, the downloads and the
+// sdpgpu_sim_result records -- so that an entry point supplies its validation, its period records and its launch.  By the handle
+// rollouts: the sampler records with their arenas (HostSamplers), the discount weights, the flat finiteness check, the
+// descriptor's inventory points, the policy-table precondition and the parameter block without a layout.  By handle and batch:
+// the sampler specs an owner keeps.  The templates take the OWNER and report through its own error sink.  Internal, header only.
 #pragma once
 #include "sdpgpu_internal.hpp"
 #include "sdp_sampler.hpp"
+
+#include <initializer_list>
 
 struct sdpgpu_batch;
 
@@ -158,14 +166,67 @@ hipError_t launch_sim_moments(hipStream_t st, const double* d_sum, uint32_t n, d
 hipError_t launch_sim_draw(hipStream_t st, int32_t mode, const sdp::SimStream& R, int T, const sdp::SimSampler* d_samp, const double* d_thr,
                            const double* d_val, double* d_dem, double* d_u);
 
-// sdpgpu_simsample.hip, shared with the cash rule rollout (sdpgpu_cashrulesim.hip): the refusals of a call's stream arguments
-// (n_paths, mode, first_path, a period without a tile or spec), and the handle's sampler records with their two arenas
+// sdpgpu_simsample.hip: the refusals of a call's stream arguments (n_paths, mode, first_path, a period without a tile or spec),
+// and the handle's sampler records with their two arenas
 int check_stream_args(sdpgpu_handle* h, const char* who, int32_t n_paths, int32_t mode, uint64_t first_path);
-void build_samplers(const sdpgpu_handle* h, std::vector<sdp::SimSampler>* rec, std::vector<double>* thr, std::vector<double>* val);
+struct HostSamplers {
+  std::vector<sdp::SimSampler> rec;
+  std::vector<double> thr, val;
+};
+void build_samplers(const sdpgpu_handle* h, HostSamplers* s);
 
-// sdpgpu_cashrulesim.hip, shared with the (x, R) rollout (sdpgpu_xrsim.hip): the parameter block of period index t WITHOUT a
-// layout, for rollouts that carry the state as doubles and read no table (nx = the descriptor's inventory points)
+// sdpgpu_simsample.hip: the parameter block of period index t WITHOUT a layout, for rollouts that carry the state as doubles and
+// read no table (nx = the descriptor's inventory points: descriptor_nx)
 sdp::DevParams rule_params(const sdpgpu_handle* h, int t, int64_t nx);
+
+// the discount weights of a call
+inline std::vector<double> discounts_or_ones(const double* discount, int T) {
+  std::vector<double> disc((size_t)T, 1.0);  // NULL = all 1.0: the bits of an explicit array of ones
+  if (discount) disc.assign(discount, discount + T);
+  return disc;
+}
+
+// The finiteness refusal of a flat array: element e of `name`, whose trailing dimensions are `inner`, reported with its indices
+// ("rule[1][0][3] = inf is not finite").  first_not_finite: the element, or count when every one is finite.
+inline size_t first_not_finite(const double* a, size_t count) {
+  size_t e = 0;
+  while (e < count && std::isfinite(a[e])) ++e;
+  return e;
+}
+template <class Owner>
+int not_finite(Owner* o, const char* who, const char* name, const double* a, size_t e, std::initializer_list<size_t> inner) {
+  size_t below = 1;
+  for (const size_t d : inner) below *= d;
+  std::string idx = "[" + std::to_string(e / below) + "]";
+  for (const size_t d : inner) {
+    below /= d;
+    idx += "[" + std::to_string(e / below % d) + "]";
+  }
+  return sim_fail(o, SDPGPU_ERR_ARG, "%s: %s%s = %g is not finite", who, name, idx.c_str(), a[e]);
+}
+template <class Owner>
+int check_finite(Owner* o, const char* who, const char* name, const double* a, size_t count, std::initializer_list<size_t> inner = {}) {
+  const size_t e = first_not_finite(a, count);
+  return e == count ? SDPGPU_OK : not_finite(o, who, name, a, e, inner);
+}
+
+// NX of a rule's tables and parameter blocks: the descriptor's inventory points, as layout() counts them (below 2^31: validated
+// at create)
+inline int descriptor_nx(sdpgpu_handle* h, const char* who, int64_t* nx) {
+  const sdpgpu_desc& d = h->d;
+  *nx = (int64_t)((d.max_inventory - d.min_inventory) / d.step) + 1;
+  if (*nx < 1 || *nx >= 2147483647LL) return fail(h, SDPGPU_ERR_UNSUPPORTED, "%s: the descriptor's inventory axis has %lld points", who, (long long)*nx);
+  return SDPGPU_OK;
+}
+
+// the precondition of a rollout that reads the policy tables; every caller keeps its own wording (prefix, and what follows the
+// first sentence)
+inline int check_solved(sdpgpu_handle* h, const char* who, const char* prefix = "", const char* unsolved_tail = "") {
+  if (!h->allocated) return fail(h, SDPGPU_ERR_STATE, "%s: %snothing has been solved%s", who, prefix, unsolved_tail);
+  for (int t = 0; t < h->T; ++t)
+    if (!h->policy_done[(size_t)t]) return fail(h, SDPGPU_ERR_STATE, "%s: %speriod %d has not been computed", who, prefix, t + 1);
+  return SDPGPU_OK;
+}
 
 // ---- sdpgpu_staffbatch.hip -------------------------------------------------------------------------------
 // A batch of STAFF instances in the separable mode (pool of level tables, groups per (period, table), two launches per period
@@ -192,6 +253,7 @@ int staff_batch_initial(StaffBatch* s, std::string* err, double* out_value, int3
 int staff_batch_stats(StaffBatch* s, std::string* err, sdpgpu_batch_stats* out);
 double staff_batch_period_ms(StaffBatch* s, std::string* err, int32_t period);
 
+// ---- the host frame of a rollout --------------------------------------------------------------------------
 // offsets of the scratch block, every part aligned to 16 bytes
 struct Carve {
   size_t at = 0;
@@ -200,6 +262,163 @@ struct Carve {
     at += (bytes + 15) / 16 * 16;
     return o;
   }
+};
+
+// `count` elements of T at byte offset `off` of the scratch block
+template <class T>
+struct Part {
+  size_t off = 0, count = 0;
+};
+
+// the two timing events of an owner: a handle creates its pair at its first rollout (sdpgpu_destroy releases it), a policy
+// created its pair with its table (sim_events of sdpgpu_multisim.hip)
+inline hipError_t sim_events(sdpgpu_handle* h, hipEvent_t* ev0, hipEvent_t* ev1) {
+  hipError_t e = hipSuccess;
+  if (!h->sim_ev0 && (e = hipEventCreate(&h->sim_ev0)) != hipSuccess) return e;
+  if (!h->sim_ev1 && (e = hipEventCreate(&h->sim_ev1)) != hipSuccess) return e;
+  *ev0 = h->sim_ev0;
+  *ev1 = h->sim_ev1;
+  return hipSuccess;
+}
+
+#define SIM_TRY(o, expr)                                                                                \
+  do {                                                                                                  \
+    const hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess) return sim_fail(o, SDPGPU_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+// One call's use of the owner's scratch block and stream, in this order:
+//   take / put / put_samplers   reserve the caller's parts (put: with the host range that begin() uploads into it)
+//   begin()                     the block (sim_scratch), the events, the uploads, the counters zeroed
+//   f[part]                     the typed device pointer of a part (null for an empty part)
+//   start()                     ev0; the caller launches its kernels, which leave sums in d_sum, wave partials in d_part and
+//                               the valid paths of rule r in d_cnt[2 r] (d_cnt[2 r + 1]: a second counter of the caller's)
+//   download(host, dev, bytes)  one more output for finish / deliver to bring back (skipped when host is null)
+//   finish(results, out_sum)    mean and m2 of every rule (launch_sim_moments), ev1, the downloads, the synchronise, the results
+// The frame's own parts come FIRST in the block, so the counters (one integer atomic per wave) share their 128-byte line with the
+// results and the first partials only, never with the tail of a caller's read-only table: behind the sampler's value arena
+// they cost sdpgpu_simulate_sampled a fifth of its time at 100 000 paths (profiles/rollout_frame_rows.json).
+// n_rules == 0 is a call without sums (the draws alone, a look-up): no reduction parts, no events; it ends with deliver().  An
+// early return leaves the owner as it is: the block is grow-only and nothing is freed on an error.
+template <class Owner>
+class RolloutFrame {
+ public:
+  const uint32_t n, W;  // paths (or leaves) of a rule, and their waves: ceil(n / 64)
+  const size_t nr;      // rules
+  unsigned int* d_cnt = nullptr;
+  double *d_res = nullptr, *d_part = nullptr, *d_sum = nullptr;
+  std::vector<unsigned int> cnt;  // the counters as finish() downloaded them
+
+  RolloutFrame(Owner* owner, uint32_t n_paths, size_t n_rules) : n(n_paths), W((n_paths + 63u) / 64u), nr(n_rules), o(owner) {
+    p_cnt = take<unsigned int>(2 * nr);
+    p_res = take<double>(2 * nr);
+    p_part = take<double>(nr * W);
+    p_sum = take<double>(nr * n);
+  }
+
+  template <class T>
+  Part<T> take(size_t count) {
+    return Part<T>{c.take(count * sizeof(T)), count};
+  }
+  // a part of max(count, reserve) elements whose first `count` are the host range (none where host is null)
+  template <class T>
+  Part<T> put(const T* host, size_t count, size_t reserve = 0) {
+    if (!host) count = 0;
+    const Part<T> p = take<T>(std::max(count, reserve));
+    if (count) uploads.push_back(Upload{host, p.off, count * sizeof(T)});
+    return p;
+  }
+  struct SamplerParts {
+    Part<sdp::SimSampler> rec;
+    Part<double> thr, val;
+  };
+  // the two arenas of build_samplers and, for a kernel that does not carry them in its period records, the records
+  SamplerParts put_samplers(const HostSamplers& s, bool with_records) {
+    SamplerParts p;
+    p.rec = put(s.rec.data(), with_records ? s.rec.size() : 0);
+    p.thr = put(s.thr.data(), s.thr.size());
+    p.val = put(s.val.data(), s.val.size());
+    return p;
+  }
+
+  int begin() {
+    if (const int rc = sim_scratch(o, c.at)) return rc;
+    base = o->d_sim_scratch;
+    if (nr) SIM_TRY(o, sim_events(o, &ev0, &ev1));
+    for (const Upload& u : uploads) SIM_TRY(o, hipMemcpyAsync(base + u.off, u.host, u.bytes, hipMemcpyHostToDevice, o->stream));
+    d_cnt = (*this)[p_cnt];
+    d_res = (*this)[p_res];
+    d_part = (*this)[p_part];
+    d_sum = (*this)[p_sum];
+    if (nr) SIM_TRY(o, hipMemsetAsync(d_cnt, 0, 2 * nr * sizeof(unsigned int), o->stream));
+    return SDPGPU_OK;
+  }
+  template <class T>
+  T* operator[](Part<T> p) const {
+    return p.count ? reinterpret_cast<T*>(base + p.off) : nullptr;
+  }
+
+  int start() {
+    SIM_TRY(o, hipEventRecord(ev0, o->stream));
+    return SDPGPU_OK;
+  }
+  void download(void* host, const void* dev, size_t bytes) {
+    if (host) downloads.push_back(Download{host, dev, bytes});
+  }
+  // results == nullptr: no moments (the caller formed no partials), the outputs alone
+  int finish(sdpgpu_sim_result* results, double* out_sum) {
+    hipStream_t st = o->stream;
+    // per rule: mean = (partials in the fixed order) / n; m2 = a second pass over the sums
+    for (size_t r = 0; results && r < nr; ++r)
+      SIM_TRY(o, launch_sim_moments(st, d_sum + r * n, n, d_part + r * W, d_cnt + 2 * r, d_res + 2 * r));
+    SIM_TRY(o, hipEventRecord(ev1, st));
+    std::vector<double> res(2 * nr, 0.0);
+    cnt.assign(2 * nr, 0u);
+    if (results) {
+      SIM_TRY(o, hipMemcpyAsync(res.data(), d_res, 2 * nr * 8, hipMemcpyDeviceToHost, st));
+      SIM_TRY(o, hipMemcpyAsync(cnt.data(), d_cnt, 2 * nr * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    }
+    if (out_sum) SIM_TRY(o, hipMemcpyAsync(out_sum, d_sum, nr * n * 8, hipMemcpyDeviceToHost, st));
+    if (const int rc = deliver()) return rc;
+    if (!results) return SDPGPU_OK;
+    float ms = 0;
+    SIM_TRY(o, hipEventElapsedTime(&ms, ev0, ev1));
+    for (size_t r = 0; r < nr; ++r) {
+      results[r].n_paths = (int32_t)n;
+      results[r].n_valid = (int32_t)cnt[2 * r];
+      results[r].n_lost = 0;
+      results[r].reserved = 0;
+      results[r].mean = res[2 * r];
+      results[r].m2 = res[2 * r + 1];
+      results[r].kernel_ms = ms;
+    }
+    return SDPGPU_OK;
+  }
+  // the registered downloads and the synchronise
+  int deliver() {
+    for (const Download& d : downloads) SIM_TRY(o, hipMemcpyAsync(d.host, d.dev, d.bytes, hipMemcpyDeviceToHost, o->stream));
+    SIM_TRY(o, hipStreamSynchronize(o->stream));
+    return SDPGPU_OK;
+  }
+
+ private:
+  struct Upload {
+    const void* host;
+    size_t off, bytes;
+  };
+  struct Download {
+    void* host;
+    const void* dev;
+    size_t bytes;
+  };
+  Owner* o;
+  Carve c;
+  Part<unsigned int> p_cnt;
+  Part<double> p_res, p_part, p_sum;
+  std::vector<Upload> uploads;
+  std::vector<Download> downloads;
+  char* base = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
 }  // namespace sdpgpu_detail

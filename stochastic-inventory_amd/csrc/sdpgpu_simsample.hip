@@ -1,8 +1,8 @@
 // sdpgpu_simsample.hip -- sdpgpu_set_sampler, sdpgpu_simulate_sampled, sdpgpu_sample_demands: demand paths drawn on the
 // device for a handle's policy simulation (kernels: sdp_sim_sampled.hpp; definition: DESIGN 4, "Sampled simulation on a
-// handle").  All validation comes before the first device call; the device scratch of these entry points is ONE block kept
-// on the handle (sim_scratch of sdpgpu_sim_host.hpp, which also holds what this unit shares with the batch's rollouts) and
-// released by sdpgpu_destroy.
+// handle") -- and what every handle rollout takes from here: the stream refusals, the sampler records, the parameter block
+// without a layout, the draws and the fixed-order reduction.  All validation comes before the first device call; the host frame
+// is RolloutFrame (sdpgpu_sim_host.hpp), its scratch block is released by sdpgpu_destroy.
 #include "sdpgpu_sim_host.hpp"
 #include "sdp_sim_sampled.hpp"
 
@@ -65,23 +65,41 @@ int check_stream_args(sdpgpu_handle* h, const char* who, int32_t n_paths, int32_
 
 // sampler records and their two arenas: spec tables as set (demand = k_lo + q); tile tables = the running fp64 sum of the
 // tile's probabilities in ascending order, the last threshold +infinity, and the tile's demand VALUES (gaps, any step)
-void build_samplers(const sdpgpu_handle* h, std::vector<sdp::SimSampler>* rec, std::vector<double>* thr, std::vector<double>* val) {
-  rec->resize((size_t)h->T);
+void build_samplers(const sdpgpu_handle* h, HostSamplers* s) {
+  s->rec.resize((size_t)h->T);
   for (int t = 0; t < h->T; ++t) {
     if (h->samp && h->samp->has((size_t)t)) {
-      (*rec)[(size_t)t] = h->samp->append((size_t)t, thr);
+      s->rec[(size_t)t] = h->samp->append((size_t)t, &s->thr);
       continue;
     }
     sdp::SimSampler S{};
-    S.off = (int64_t)thr->size();
+    S.off = (int64_t)s->thr.size();
     S.k_lo = 0;
     S.strict = 0;
     S.m = (int32_t)h->pmf_p[(size_t)t].size();
-    S.val_off = (int64_t)val->size();
-    append_tile_thresholds(h->pmf_p[(size_t)t], thr);
-    val->insert(val->end(), h->pmf_d[(size_t)t].begin(), h->pmf_d[(size_t)t].end());
-    (*rec)[(size_t)t] = S;
+    S.val_off = (int64_t)s->val.size();
+    append_tile_thresholds(h->pmf_p[(size_t)t], &s->thr);
+    s->val.insert(s->val.end(), h->pmf_d[(size_t)t].begin(), h->pmf_d[(size_t)t].end());
+    s->rec[(size_t)t] = S;
   }
+}
+
+// the period's parameter block without a layout (the rollout reads no table, so it needs no pmf tile where a spec is set): the
+// family's scalars and the handle's overhead from make_params, the boxes from the descriptor as layout() forms them (the rule
+// rollouts of sdpgpu_cashrulesim.hip and sdpgpu_xrsim.hip)
+DevParams rule_params(const sdpgpu_handle* h, int t, int64_t nx) {
+  const sdpgpu_desc& d = h->d;
+  DevParams P = make_params(h, t + 1);
+  P.overhead = h->per[(size_t)t].overhead_set ? h->per[(size_t)t].overhead : d.overhead_cost;
+  Grid g{};
+  g.x_lo = d.min_inventory;
+  g.nx = nx;
+  g.k_lo = cash_key_of_bound(d, d.min_cash);
+  g.nc = cash_key_of_bound(d, d.max_cash) - g.k_lo + 1;
+  g.nq = g.nq1 = 1;
+  P.cur = P.next = g;
+  P.counts = nullptr;
+  return P;
 }
 
 // the demands of a stream into a device buffer, out[p * T + t] (and the uniforms where d_u is given): sim_sampled_draw_kernel
@@ -145,9 +163,8 @@ int sdpgpu_sample_demands(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int3
     if (!out_demand) return fail(h, SDPGPU_ERR_ARG, "%s: out_demand is null", who);
     rc = check_stream_args(h, who, n_paths, mode, first_path);
     if (rc) return rc;
-    std::vector<sdp::SimSampler> rec;
-    std::vector<double> thr, val;
-    build_samplers(h, &rec, &thr, &val);
+    HostSamplers samp;
+    build_samplers(h, &samp);
 
     rc = no_device(h, who);
     if (rc) return rc;
@@ -155,26 +172,15 @@ int sdpgpu_sample_demands(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int3
     HIP_TRY(h, dev.enter(h->device));
     const int T = h->T;
     const size_t elems = (size_t)n_paths * T;
-    Carve c;
-    const size_t o_samp = c.take(rec.size() * sizeof(sdp::SimSampler)), o_thr = c.take(thr.size() * 8), o_val = c.take(val.size() * 8);
-    const size_t o_dem = c.take(elems * 8), o_u = c.take(out_u ? elems * 8 : 0);
-    rc = sim_scratch(h, c.at);
+    RolloutFrame<sdpgpu_handle> f(h, (uint32_t)n_paths, 0);
+    const auto p_samp = f.put_samplers(samp, true);
+    const auto p_dem = f.take<double>(elems), p_u = f.take<double>(out_u ? elems : 0);
+    rc = f.begin();
     if (rc) return rc;
-    char* base = h->d_sim_scratch;
-    HIP_TRY(h, hipMemcpyAsync(base + o_samp, rec.data(), rec.size() * sizeof(sdp::SimSampler), hipMemcpyHostToDevice, h->stream));
-    if (!thr.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice, h->stream));
-    if (!val.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_val, val.data(), val.size() * 8, hipMemcpyHostToDevice, h->stream));
-    const sdp::SimStream R = make_stream(n_paths, seed, first_path);
-    const sdp::SimSampler* d_samp = reinterpret_cast<const sdp::SimSampler*>(base + o_samp);
-    const double* d_thr = reinterpret_cast<const double*>(base + o_thr);
-    const double* d_val = reinterpret_cast<const double*>(base + o_val);
-    double* d_dem = reinterpret_cast<double*>(base + o_dem);
-    double* d_u = out_u ? reinterpret_cast<double*>(base + o_u) : nullptr;
-    HIP_TRY(h, launch_sim_draw(h->stream, mode, R, T, d_samp, d_thr, d_val, d_dem, d_u));
-    HIP_TRY(h, hipMemcpyAsync(out_demand, d_dem, elems * 8, hipMemcpyDeviceToHost, h->stream));
-    if (out_u) HIP_TRY(h, hipMemcpyAsync(out_u, d_u, elems * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SDPGPU_OK;
+    HIP_TRY(h, launch_sim_draw(h->stream, mode, make_stream(n_paths, seed, first_path), T, f[p_samp.rec], f[p_samp.thr], f[p_samp.val], f[p_dem], f[p_u]));
+    f.download(out_demand, f[p_dem], elems * 8);
+    f.download(out_u, f[p_u], elems * 8);
+    return f.deliver();
   });
 }
 
@@ -190,15 +196,12 @@ int sdpgpu_simulate_sampled(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, in
     if (!result) return fail(h, SDPGPU_ERR_ARG, "%s: result is null", who);
     rc = check_stream_args(h, who, n_paths, mode, first_path);
     if (rc) return rc;
-    if (!h->allocated) return fail(h, SDPGPU_ERR_STATE, "%s: nothing has been solved", who);
-    for (int t = 0; t < h->T; ++t)
-      if (!h->policy_done[t]) return fail(h, SDPGPU_ERR_STATE, "%s: period %d has not been computed", who, t + 1);
+    rc = check_solved(h, who);
+    if (rc) return rc;
     const int T = h->T;
-    std::vector<sdp::SimSampler> rec;
-    std::vector<double> thr, val;
-    build_samplers(h, &rec, &thr, &val);
-    std::vector<double> disc((size_t)T, 1.0);  // NULL = all 1.0: the bits of an explicit array of ones
-    if (discount) disc.assign(discount, discount + T);
+    HostSamplers samp;
+    build_samplers(h, &samp);
+    const std::vector<double> disc = discounts_or_ones(discount, T);
 
     DeviceScope dev;
     HIP_TRY(h, dev.enter(h->device));
@@ -220,63 +223,26 @@ int sdpgpu_simulate_sampled(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, in
       per[(size_t)t].pol_off = (int64_t)h->per[t].pol_off - h->per[t].lo;
       per[(size_t)t].n_states = h->per[t].S;
     }
-    const size_t nn = (size_t)n_paths;
-    const uint32_t W = (uint32_t)((n_paths + 63) / 64);
-    Carve c;
-    const size_t o_per = c.take(per.size() * sizeof(sdp::SimPeriod)), o_samp = c.take(rec.size() * sizeof(sdp::SimSampler));
-    const size_t o_disc = c.take((size_t)T * 8), o_thr = c.take(thr.size() * 8), o_val = c.take(val.size() * 8);
-    const size_t o_cnt = c.take(2 * sizeof(unsigned int)), o_res = c.take(2 * 8), o_part = c.take((size_t)W * 8);
-    const size_t o_sum = c.take(nn * 8), o_flag = c.take(nn);
-    rc = sim_scratch(h, c.at);
+    RolloutFrame<sdpgpu_handle> f(h, (uint32_t)n_paths, 1);
+    const auto p_per = f.put(per.data(), per.size());
+    const auto p_samp = f.put_samplers(samp, true);
+    const auto p_disc = f.put(disc.data(), disc.size());
+    const auto p_flag = f.take<uint8_t>(f.n);
+    rc = f.begin();
     if (rc) return rc;
-    if (!h->sim_ev0) {
-      HIP_TRY(h, hipEventCreate(&h->sim_ev0));
-      HIP_TRY(h, hipEventCreate(&h->sim_ev1));
-    }
-    char* base = h->d_sim_scratch;
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(base + o_per, per.data(), per.size() * sizeof(sdp::SimPeriod), hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(base + o_samp, rec.data(), rec.size() * sizeof(sdp::SimSampler), hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemcpyAsync(base + o_disc, disc.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
-    if (!thr.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice, st));
-    if (!val.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_val, val.data(), val.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemsetAsync(base + o_cnt, 0, 2 * sizeof(unsigned int), st));
-    const sdp::SimPeriod* d_per = reinterpret_cast<const sdp::SimPeriod*>(base + o_per);
-    const sdp::SimSampler* d_samp = reinterpret_cast<const sdp::SimSampler*>(base + o_samp);
-    const double* d_disc = reinterpret_cast<const double*>(base + o_disc);
-    const double* d_thr = reinterpret_cast<const double*>(base + o_thr);
-    const double* d_val = reinterpret_cast<const double*>(base + o_val);
-    unsigned int* d_cnt = reinterpret_cast<unsigned int*>(base + o_cnt);
-    double* d_res = reinterpret_cast<double*>(base + o_res);
-    double* d_part = reinterpret_cast<double*>(base + o_part);
-    double* d_sum = reinterpret_cast<double*>(base + o_sum);
-    uint8_t* d_flag = reinterpret_cast<uint8_t*>(base + o_flag);
     const sdp::SimStream R = make_stream(n_paths, seed, first_path);
     const sdp::StateT ini{ini_x, ini_cash, ini_preq, ini_preq2};
-    const dim3 grid((W + 3) / 4);
-    HIP_TRY(h, hipEventRecord(h->sim_ev0, st));
+    const dim3 grid((f.W + 3) / 4);
+    rc = f.start();
+    if (rc) return rc;
     const hipError_t e = mode == SDPGPU_SAMPLE_RANDOM
-                             ? launch_fused<true>(h, grid, d_per, d_samp, d_thr, d_val, d_disc, R, idx0, ini, (int)first_k, d_sum, d_flag, d_part, d_cnt)
-                             : launch_fused<false>(h, grid, d_per, d_samp, d_thr, d_val, d_disc, R, idx0, ini, (int)first_k, d_sum, d_flag, d_part, d_cnt);
+                             ? launch_fused<true>(h, grid, f[p_per], f[p_samp.rec], f[p_samp.thr], f[p_samp.val], f[p_disc], R, idx0, ini, (int)first_k, f.d_sum, f[p_flag], f.d_part, f.d_cnt)
+                             : launch_fused<false>(h, grid, f[p_per], f[p_samp.rec], f[p_samp.thr], f[p_samp.val], f[p_disc], R, idx0, ini, (int)first_k, f.d_sum, f[p_flag], f.d_part, f.d_cnt);
     HIP_TRY(h, e);
-    HIP_TRY(h, launch_sim_moments(st, d_sum, (uint32_t)n_paths, d_part, d_cnt, d_res));
-    HIP_TRY(h, hipEventRecord(h->sim_ev1, st));
-    double res[2] = {0, 0};
-    unsigned int cnt[2] = {0, 0};
-    HIP_TRY(h, hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, st));
-    if (out_sum) HIP_TRY(h, hipMemcpyAsync(out_sum, d_sum, nn * 8, hipMemcpyDeviceToHost, st));
-    if (out_valid) HIP_TRY(h, hipMemcpyAsync(out_valid, d_flag, nn, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->sim_ev0, h->sim_ev1));
-    result->n_paths = n_paths;
-    result->n_valid = (int32_t)cnt[0];
-    result->n_lost = h->d.family == SDPGPU_FAMILY_SURVIVAL ? (int32_t)cnt[1] : 0;
-    result->reserved = 0;
-    result->mean = res[0];
-    result->m2 = res[1];
-    result->kernel_ms = ms;
+    f.download(out_valid, f[p_flag], f.n);
+    rc = f.finish(result, out_sum);
+    if (rc) return rc;
+    if (h->d.family == SDPGPU_FAMILY_SURVIVAL) result->n_lost = (int32_t)f.cnt[1];  // the survival loop's second counter
     return SDPGPU_OK;
   });
 }

@@ -1,8 +1,7 @@
 // sdpgpu_staffsim.hip -- sdpgpu_staff_simulate: the workforce drivers' rollout of a hiring rule on a sampled tree
 // (SimulatesS.java:33-87), for the (s, S) level rule and for the handle's policy table (kernel: sdp_staff_sim.hpp; definition:
-// DESIGN 4, "Workforce rollout on a sampled tree").  All validation comes before the first device call; the device scratch is
-// carved from the handle's simulation block (sim_scratch of sdpgpu_sim_host.hpp), the reduction is the handle's
-// (launch_sim_moments of sdpgpu_simsample.hip: sim_reduce_kernel, sim_dev2_kernel).
+// DESIGN 4, "Workforce rollout on a sampled tree").  All validation comes before the first device call; the host frame is
+// RolloutFrame (sdpgpu_sim_host.hpp).
 #include "sdpgpu_sim_host.hpp"
 #include "sdp_staff_sim.hpp"
 
@@ -74,9 +73,8 @@ int sdpgpu_staff_simulate(sdpgpu_handle* h, const int32_t* sample_nums, uint64_t
     if (!ss) {
       const double lo = h->per[0].g.x_lo, hi = lo + (double)(h->per[0].g.nx - 1);
       if (ini_x < lo || ini_x > hi) return fail(h, SDPGPU_ERR_ARG, "%s: ini_x = %g outside period 1's staff numbers %g .. %g", who, ini_x, lo, hi);
-      if (!h->allocated) return fail(h, SDPGPU_ERR_STATE, "%s: nothing has been solved (the table policy needs sdpgpu_solve; a level rule does not)", who);
-      for (int t = 0; t < T; ++t)
-        if (!h->policy_done[(size_t)t]) return fail(h, SDPGPU_ERR_STATE, "%s: period %d has not been computed", who, t + 1);
+      rc = check_solved(h, who, "", " (the table policy needs sdpgpu_solve; a level rule does not)");
+      if (rc) return rc;
     }
     if (!(h->allocated && h->staff_tables_nonneg)) {  // (looked at once: the tables are frozen once the device copies exist)
       rc = check_tables(h, who);
@@ -93,7 +91,6 @@ int sdpgpu_staff_simulate(sdpgpu_handle* h, const int32_t* sample_nums, uint64_t
     rc = flush_api(h);
     if (rc) return rc;
     const uint32_t n = (uint32_t)N;
-    const uint32_t W = (n + 63u) / 64u;
     std::vector<sdp::StaffSimPeriod> per((size_t)T);
     uint32_t stride = n;
     for (int t = 0; t < T; ++t) {
@@ -123,66 +120,31 @@ int sdpgpu_staff_simulate(sdpgpu_handle* h, const int32_t* sample_nums, uint64_t
     L.max_x = (int32_t)h->d.max_inventory;
     L.ini_x = (int32_t)ini_x;
     L.n_leaves = n;
-    L.waves_per_rule = W;
     L.seed_lo = (uint32_t)(seed & 0xffffffffu);
     L.seed_hi = (uint32_t)(seed >> 32);
 
-    const size_t nr = (size_t)n_rules, nn = (size_t)n;
-    Carve c;
-    const size_t o_per = c.take(per.size() * sizeof(sdp::StaffSimPeriod)), o_ss = c.take(levels.size() * sizeof(int32_t));
-    const size_t o_cnt = c.take(2 * nr * sizeof(unsigned int)), o_res = c.take(2 * nr * 8), o_part = c.take(nr * W * 8);
-    const size_t o_sum = c.take(nr * nn * 8), o_flag = c.take(out_valid ? nr * nn : 0);
-    const size_t o_dem = c.take(out_demand ? nr * nn * (size_t)T * sizeof(int32_t) : 0);
-    rc = sim_scratch(h, c.at);
+    RolloutFrame<sdpgpu_handle> f(h, n, (size_t)n_rules);
+    const size_t leaves = f.nr * n;
+    const auto p_per = f.put(per.data(), per.size());
+    const auto p_ss = f.put(levels.data(), levels.size());
+    const auto p_flag = f.take<uint8_t>(out_valid ? leaves : 0);
+    const auto p_dem = f.take<int32_t>(out_demand ? leaves * (size_t)T : 0);
+    rc = f.begin();
     if (rc) return rc;
-    if (!h->sim_ev0) {
-      HIP_TRY(h, hipEventCreate(&h->sim_ev0));
-      HIP_TRY(h, hipEventCreate(&h->sim_ev1));
-    }
-    char* base = h->d_sim_scratch;
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(base + o_per, per.data(), per.size() * sizeof(sdp::StaffSimPeriod), hipMemcpyHostToDevice, st));
-    if (ss) HIP_TRY(h, hipMemcpyAsync(base + o_ss, levels.data(), levels.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemsetAsync(base + o_cnt, 0, 2 * nr * sizeof(unsigned int), st));
-    const sdp::StaffSimPeriod* d_per = reinterpret_cast<const sdp::StaffSimPeriod*>(base + o_per);
-    unsigned int* d_cnt = reinterpret_cast<unsigned int*>(base + o_cnt);
-    double* d_res = reinterpret_cast<double*>(base + o_res);
-    double* d_part = reinterpret_cast<double*>(base + o_part);
-    double* d_sum = reinterpret_cast<double*>(base + o_sum);
-    uint8_t* d_flag = out_valid ? reinterpret_cast<uint8_t*>(base + o_flag) : nullptr;
-    int32_t* d_dem = out_demand ? reinterpret_cast<int32_t*>(base + o_dem) : nullptr;
-    const dim3 grid((unsigned)((nr * W + 3) / 4));  // (at most 64 x 2^18 waves)
-    HIP_TRY(h, hipEventRecord(h->sim_ev0, st));
+    L.waves_per_rule = f.W;
+    const dim3 grid((unsigned)((f.nr * f.W + 3) / 4));  // (at most 64 x 2^18 waves)
+    rc = f.start();
+    if (rc) return rc;
     if (ss)
-      hipLaunchKernelGGL((sdp::staff_sim_kernel<sdp::StaffLevelRule>), grid, dim3(256), 0, st, L, d_per,
-                         sdp::StaffLevelRule{reinterpret_cast<const int32_t*>(base + o_ss)}, d_sum, d_flag, d_dem, d_part, d_cnt);
+      hipLaunchKernelGGL((sdp::staff_sim_kernel<sdp::StaffLevelRule>), grid, dim3(256), 0, h->stream, L, f[p_per], sdp::StaffLevelRule{f[p_ss]},
+                         f.d_sum, f[p_flag], f[p_dem], f.d_part, f.d_cnt);
     else
-      hipLaunchKernelGGL((sdp::staff_sim_kernel<sdp::StaffTableRule>), grid, dim3(256), 0, st, L, d_per, sdp::StaffTableRule{h->d_policy}, d_sum,
-                         d_flag, d_dem, d_part, d_cnt);
+      hipLaunchKernelGGL((sdp::staff_sim_kernel<sdp::StaffTableRule>), grid, dim3(256), 0, h->stream, L, f[p_per], sdp::StaffTableRule{h->d_policy},
+                         f.d_sum, f[p_flag], f[p_dem], f.d_part, f.d_cnt);
     HIP_TRY(h, hipGetLastError());
-    // per rule, as sdpgpu_simulate_sampled: mean = (partials in the fixed order) / N; m2 = a second pass over the sums
-    for (size_t r = 0; r < nr; ++r) HIP_TRY(h, launch_sim_moments(st, d_sum + r * nn, n, d_part + r * W, d_cnt + 2 * r, d_res + 2 * r));
-    HIP_TRY(h, hipEventRecord(h->sim_ev1, st));
-    std::vector<double> res(2 * nr, 0.0);
-    std::vector<unsigned int> cnt(2 * nr, 0u);
-    HIP_TRY(h, hipMemcpyAsync(res.data(), d_res, 2 * nr * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(cnt.data(), d_cnt, 2 * nr * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    if (out_sum) HIP_TRY(h, hipMemcpyAsync(out_sum, d_sum, nr * nn * 8, hipMemcpyDeviceToHost, st));
-    if (out_valid) HIP_TRY(h, hipMemcpyAsync(out_valid, d_flag, nr * nn, hipMemcpyDeviceToHost, st));
-    if (out_demand) HIP_TRY(h, hipMemcpyAsync(out_demand, d_dem, nr * nn * (size_t)T * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->sim_ev0, h->sim_ev1));
-    for (size_t r = 0; r < nr; ++r) {
-      results[r].n_paths = (int32_t)n;
-      results[r].n_valid = (int32_t)cnt[2 * r];
-      results[r].n_lost = 0;
-      results[r].reserved = 0;
-      results[r].mean = res[2 * r];
-      results[r].m2 = res[2 * r + 1];
-      results[r].kernel_ms = ms;
-    }
-    return SDPGPU_OK;
+    f.download(out_valid, f[p_flag], leaves);
+    f.download(out_demand, f[p_dem], leaves * (size_t)T * sizeof(int32_t));
+    return f.finish(results, out_sum);
   });
 }
 

@@ -2,9 +2,7 @@
 // table (CashSimulationXR.java:91-147) and Chao's a* levels (:153-173) -- along demand paths (kernel: sdp_xr_sim.hpp;
 // definition: DESIGN 4, "(x, R) rollout"); and sdpgpu_xr_opt_levels: the a* levels themselves, RecursionG.getOptY
 // (RecursionG.java:80-153), on the host.  All validation comes before the first device call; the draws are
-// sdpgpu_simulate_sampled's (check_stream_args, build_samplers and make_stream of sdpgpu_sim_host.hpp), the device scratch is
-// carved from the handle's simulation block, the reduction is the handle's (launch_sim_moments of sdpgpu_simsample.hip:
-// sim_reduce_kernel, sim_dev2_kernel).
+// sdpgpu_simulate_sampled's, the host frame is RolloutFrame (sdpgpu_sim_host.hpp).
 #include <map>
 #include <utility>
 
@@ -145,43 +143,29 @@ int sdpgpu_xr_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t
     if (n_rules < 1 || n_rules > kXrMaxRules) return fail(h, SDPGPU_ERR_ARG, "%s: n_rules = %d (1 .. %d)", who, n_rules, kXrMaxRules);
     if (!levels && n_rules != 1) return fail(h, SDPGPU_ERR_ARG, "%s: n_rules = %d with levels null -- the table rule is one rule", who, n_rules);
     const int T = h->T;
-    if (levels)
-      for (int r = 0; r < n_rules; ++r)
-        for (int t = 0; t < T; ++t) {
-          const double v = levels[(size_t)r * T + t];
-          if (!std::isfinite(v)) return fail(h, SDPGPU_ERR_ARG, "%s: levels[%d][%d] = %g is not finite", who, r, t, v);
-        }
+    int rc = SDPGPU_OK;
+    if (levels && (rc = check_finite(h, who, "levels", levels, (size_t)n_rules * T, {(size_t)T}))) return rc;
     if (!std::isfinite(ini_x)) return fail(h, SDPGPU_ERR_ARG, "%s: ini_x = %g is not finite", who, ini_x);
     if (!std::isfinite(ini_r)) return fail(h, SDPGPU_ERR_ARG, "%s: ini_r = %g is not finite", who, ini_r);
     if (!std::isfinite(vari_cost) || vari_cost <= 0)
       return fail(h, SDPGPU_ERR_ARG, "%s: vari_cost = %g (finite, above 0: the level is R / vari_cost)", who, vari_cost);
-    if (discount)
-      for (int t = 0; t < T; ++t)
-        if (!std::isfinite(discount[t])) return fail(h, SDPGPU_ERR_ARG, "%s: discount[%d] = %g is not finite", who, t, discount[t]);
-    int rc;
+    if (discount && (rc = check_finite(h, who, "discount", discount, (size_t)T))) return rc;
     if (demand) {  // GIVEN: seed, mode and first_path are not read
       rc = check_n_paths(h, who, n_paths);
-      if (rc) return rc;
-      for (size_t e = 0; e < (size_t)n_paths * T; ++e)
-        if (!std::isfinite(demand[e])) return fail(h, SDPGPU_ERR_ARG, "%s: demand[%zu][%zu] = %g is not finite", who, e / (size_t)T, e % (size_t)T, demand[e]);
+      if (!rc) rc = check_finite(h, who, "demand", demand, (size_t)n_paths * T, {(size_t)T});
     } else {
       rc = check_stream_args(h, who, n_paths, mode, first_path);
-      if (rc) return rc;
     }
-    if (!levels) {
-      if (!h->allocated) return fail(h, SDPGPU_ERR_STATE, "%s: the table rule (levels null): nothing has been solved", who);
-      for (int t = 0; t < T; ++t)
-        if (!h->policy_done[t]) return fail(h, SDPGPU_ERR_STATE, "%s: the table rule (levels null): period %d has not been computed", who, t + 1);
-    }
+    if (!rc && !levels) rc = check_solved(h, who, "the table rule (levels null): ");
+    if (rc) return rc;
     const int source = demand ? sdp::XR_SOURCE_GIVEN : mode == SDPGPU_SAMPLE_RANDOM ? sdp::XR_SOURCE_RANDOM : sdp::XR_SOURCE_LHS;
-    std::vector<sdp::SimSampler> rec((size_t)T);
-    std::vector<double> thr, val;
-    if (!demand) build_samplers(h, &rec, &thr, &val);
-    std::vector<double> disc((size_t)T, 1.0);  // NULL = all 1.0: the bits of an explicit array of ones
-    if (discount) disc.assign(discount, discount + T);
-    // NX of the level rule's parameter blocks: the descriptor's inventory points, as layout() counts them
-    const int64_t nx = (int64_t)((d.max_inventory - d.min_inventory) / d.step) + 1;
-    if (nx < 1 || nx >= 2147483647LL) return fail(h, SDPGPU_ERR_UNSUPPORTED, "%s: the descriptor's inventory axis has %lld points", who, (long long)nx);
+    HostSamplers samp;
+    samp.rec.resize((size_t)T);
+    if (!demand) build_samplers(h, &samp);
+    const std::vector<double> disc = discounts_or_ones(discount, T);
+    int64_t nx = 0;  // NX of the level rule's parameter blocks
+    rc = descriptor_nx(h, who, &nx);
+    if (rc) return rc;
 
     rc = no_device(h, who);
     if (rc) return rc;
@@ -227,80 +211,36 @@ int sdpgpu_xr_simulate(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int32_t
         Q.S.pol_off = (int64_t)h->per[t].pol_off - h->per[t].lo;
         Q.S.n_states = h->per[t].S;
       }
-      Q.samp = rec[(size_t)t];
+      Q.samp = samp.rec[(size_t)t];
       Q.disc = disc[(size_t)t];
     }
-    const uint32_t n = (uint32_t)n_paths;
-    const uint32_t W = (n + 63u) / 64u;
+    RolloutFrame<sdpgpu_handle> f(h, (uint32_t)n_paths, (size_t)n_rules);
+    const size_t elems = (size_t)f.n * T;
+    const auto p_per = f.put(per.data(), per.size());
+    const auto p_samp = f.put_samplers(samp, false);
+    const auto p_lev = f.put(levels, f.nr * T), p_giv = f.put(demand, elems);
+    const auto p_dem = f.take<double>(out_demand ? elems : 0);
+    rc = f.begin();
+    if (rc) return rc;
     sdp::XrLaunch L{};
     L.ini_x = ini_x;
     L.ini_r = ini_r;
     L.vari_cost = vari_cost;
     L.T = T;
     L.n_rules = n_rules;
-    L.waves_per_rule = W;
-
-    const size_t nr = (size_t)n_rules, nn = (size_t)n, elems = nn * (size_t)T;
-    Carve c;
-    const size_t o_per = c.take(per.size() * sizeof(sdp::XrPeriod));
-    const size_t o_thr = c.take(thr.size() * 8), o_val = c.take(val.size() * 8);
-    const size_t o_lev = c.take(levels ? nr * T * 8 : 0), o_giv = c.take(demand ? elems * 8 : 0);
-    const size_t o_cnt = c.take(2 * nr * sizeof(unsigned int)), o_res = c.take(2 * nr * 8), o_part = c.take(nr * W * 8);
-    const size_t o_sum = c.take(nr * nn * 8), o_dem = c.take(out_demand ? elems * 8 : 0);
-    rc = sim_scratch(h, c.at);
-    if (rc) return rc;
-    if (!h->sim_ev0) {
-      HIP_TRY(h, hipEventCreate(&h->sim_ev0));
-      HIP_TRY(h, hipEventCreate(&h->sim_ev1));
-    }
-    char* base = h->d_sim_scratch;
-    hipStream_t st = h->stream;
-    HIP_TRY(h, hipMemcpyAsync(base + o_per, per.data(), per.size() * sizeof(sdp::XrPeriod), hipMemcpyHostToDevice, st));
-    if (!thr.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_thr, thr.data(), thr.size() * 8, hipMemcpyHostToDevice, st));
-    if (!val.empty()) HIP_TRY(h, hipMemcpyAsync(base + o_val, val.data(), val.size() * 8, hipMemcpyHostToDevice, st));
-    if (levels) HIP_TRY(h, hipMemcpyAsync(base + o_lev, levels, nr * T * 8, hipMemcpyHostToDevice, st));
-    if (demand) HIP_TRY(h, hipMemcpyAsync(base + o_giv, demand, elems * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipMemsetAsync(base + o_cnt, 0, 2 * nr * sizeof(unsigned int), st));
-    const sdp::XrPeriod* d_per = reinterpret_cast<const sdp::XrPeriod*>(base + o_per);
-    const double* d_thr = reinterpret_cast<const double*>(base + o_thr);
-    const double* d_val = reinterpret_cast<const double*>(base + o_val);
-    const double* d_giv = demand ? reinterpret_cast<const double*>(base + o_giv) : nullptr;
-    unsigned int* d_cnt = reinterpret_cast<unsigned int*>(base + o_cnt);
-    double* d_res = reinterpret_cast<double*>(base + o_res);
-    double* d_part = reinterpret_cast<double*>(base + o_part);
-    double* d_sum = reinterpret_cast<double*>(base + o_sum);
-    double* d_dem = out_demand ? reinterpret_cast<double*>(base + o_dem) : nullptr;
+    L.waves_per_rule = f.W;
     const sdp::SimStream R = make_stream(n_paths, seed, demand ? 0 : first_path);
-    const dim3 grid((unsigned)((nr * W + 3) / 4));  // (at most 16 x 2^18 waves)
-    HIP_TRY(h, hipEventRecord(h->sim_ev0, st));
-    if (levels) {
-      const sdp::XrLevelRule rule{reinterpret_cast<const double*>(base + o_lev)};
-      HIP_TRY(h, launch_xr(source, grid, st, L, R, d_per, d_thr, d_val, d_giv, rule, d_sum, d_dem, d_part, d_cnt));
-    } else {
-      HIP_TRY(h, launch_xr(source, grid, st, L, R, d_per, d_thr, d_val, d_giv, table, d_sum, d_dem, d_part, d_cnt));
-    }
-    // per rule, as sdpgpu_simulate_sampled: mean = (partials in the fixed order) / n; m2 = a second pass over the sums
-    for (size_t r = 0; r < nr; ++r) HIP_TRY(h, launch_sim_moments(st, d_sum + r * nn, n, d_part + r * W, d_cnt + 2 * r, d_res + 2 * r));
-    HIP_TRY(h, hipEventRecord(h->sim_ev1, st));
-    std::vector<double> res(2 * nr, 0.0);
-    std::vector<unsigned int> cnt(2 * nr, 0u);
-    HIP_TRY(h, hipMemcpyAsync(res.data(), d_res, 2 * nr * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipMemcpyAsync(cnt.data(), d_cnt, 2 * nr * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    if (out_sum) HIP_TRY(h, hipMemcpyAsync(out_sum, d_sum, nr * nn * 8, hipMemcpyDeviceToHost, st));
-    if (out_demand) HIP_TRY(h, hipMemcpyAsync(out_demand, d_dem, elems * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    float ms = 0;
-    HIP_TRY(h, hipEventElapsedTime(&ms, h->sim_ev0, h->sim_ev1));
-    for (size_t r = 0; r < nr; ++r) {
-      results[r].n_paths = n_paths;
-      results[r].n_valid = (int32_t)cnt[2 * r];  // every path, but for a table rule's start whose inventory is off the grid
-      results[r].n_lost = 0;
-      results[r].reserved = 0;
-      results[r].mean = res[2 * r];
-      results[r].m2 = res[2 * r + 1];
-      results[r].kernel_ms = ms;
-    }
-    return SDPGPU_OK;
+    const dim3 grid((unsigned)((f.nr * f.W + 3) / 4));  // (at most 16 x 2^18 waves)
+    rc = f.start();
+    if (rc) return rc;
+    if (levels)
+      HIP_TRY(h, launch_xr(source, grid, h->stream, L, R, f[p_per], f[p_samp.thr], f[p_samp.val], f[p_giv], sdp::XrLevelRule{f[p_lev]}, f.d_sum,
+                           f[p_dem], f.d_part, f.d_cnt));
+    else
+      HIP_TRY(h, launch_xr(source, grid, h->stream, L, R, f[p_per], f[p_samp.thr], f[p_samp.val], f[p_giv], table, f.d_sum, f[p_dem], f.d_part,
+                           f.d_cnt));
+    f.download(out_demand, f[p_dem], elems * 8);
+    return f.finish(results, out_sum);  // (n_valid: every path, but for a table rule's start whose inventory is off the grid)
   });
 }
 
