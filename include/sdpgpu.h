@@ -435,7 +435,11 @@ int64_t sdpgpu_state_index2(const sdpgpu_handle* h, int32_t period, double x, do
  * handle's stream unless `sync` != 0. */
 int sdpgpu_solve(sdpgpu_handle* h, int32_t sync);
 /* One period for this rank's slab, reading the FULL V_{period+1} table.  With world_size > 1
- * the caller all-gathers V_period (device pointer below) across ranks before the next call. */
+ * the caller all-gathers V_period (device pointer below) across ranks before the next call.
+ * With store_all_values = 0, V_period is written into table (period & 1): every other period of that parity stops existing
+ * (V_{period+2} inside a sweep; V_{period-2} of an earlier sweep when a period is run again), and whatever reads one of them
+ * -- sdpgpu_values, sdpgpu_eval_states, a rollout from a start off the grid, sdpgpu_run_period of the period below -- answers
+ * SDPGPU_ERR_STATE until it has been run again. */
 int sdpgpu_run_period(sdpgpu_handle* h, int32_t period);
 /* The same in two halves, so that a sharded caller can overlap the all-gather of V_{period+1} with
  * compute: INTERIOR = the states all of whose cells read only THIS rank's slab of V_{period+1} (it may

@@ -362,6 +362,25 @@ void graph_drop(sdpgpu_handle* h) {
   if (h->graph_state > 0) h->graph_state = 0;
 }
 
+// `period` is complete: its table and its policy exist.  With two ping-pong tables V_period was written into table
+// (period & 1) over whatever that table held, so no OTHER period of the same parity exists any more: V_{period+2} inside a
+// sweep, and V_{period-2}, V_{period-4} .. of an earlier sweep when a period is run again (sdpgpu_run_period after a solve, a
+// second sweep stepped by hand).  Their readers -- values, eval_states, an off-grid rollout start, run_period -- answer
+// SDPGPU_ERR_STATE until the period has been run again.
+static void mark_period_done(sdpgpu_handle* h, int period) {
+  if (!h->d.store_all_values)
+    for (int q = 2 - (period & 1); q <= h->T; q += 2) h->period_done[q - 1] = 0;
+  h->period_done[period - 1] = 1;
+  h->policy_done[period - 1] = 1;
+}
+
+// what a complete sweep T..1 leaves: every table with store_all_values, V_1 and V_2 on ping-pong tables (a replayed graph ran the
+// sweep without passing through run_period_impl)
+static void mark_sweep_done(sdpgpu_handle* h) {
+  std::fill(h->period_done.begin(), h->period_done.end(), 0);
+  for (int period = h->T; period >= 1; --period) mark_period_done(h, period);
+}
+
 int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, int64_t range_hi) {
   int rc = allocate(h);
   if (rc) return rc;
@@ -417,9 +436,7 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
     } else {
       p.timed = false;
     }
-    h->period_done[period - 1] = 1;
-    h->policy_done[period - 1] = 1;
-    if (!h->d.store_all_values && period + 2 <= h->T) h->period_done[period + 1] = 0;
+    mark_period_done(h, period);
     return SDPGPU_OK;
   }
   // user lambdas of the level shape run on the F1 window kernel wherever the built-in family would (tables in place of the
@@ -439,9 +456,7 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
     } else {
       p.timed = false;
     }
-    h->period_done[period - 1] = 1;
-    h->policy_done[period - 1] = 1;
-    if (!h->d.store_all_values && period + 2 <= h->T) h->period_done[period + 1] = 0;
+    mark_period_done(h, period);
     return SDPGPU_OK;
   }
   const bool own_counts = !h->counts[(size_t)period - 1].empty();  // the specialised kernels assume the family's action rule
@@ -456,9 +471,7 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
       HIP_TRY(h, hipEventRecord(p.ev1, h->stream));
       p.timed = true;
     }
-    h->period_done[period - 1] = 1;
-    h->policy_done[period - 1] = 1;
-    if (!h->d.store_all_values && period + 2 <= h->T) h->period_done[period + 1] = 0;
+    mark_period_done(h, period);
     return SDPGPU_OK;
   }
   if (h->d.kernel == SDPGPU_KERNEL_SEPARABLE && h->d.family == SDPGPU_FAMILY_CASH_LEADTIME) {
@@ -478,9 +491,7 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
       HIP_TRY(h, hipEventRecord(p.ev1, h->stream));
       p.timed = true;
     }
-    h->period_done[period - 1] = 1;
-    h->policy_done[period - 1] = 1;
-    if (!h->d.store_all_values && period + 2 <= h->T) h->period_done[period + 1] = 0;
+    mark_period_done(h, period);
     return SDPGPU_OK;
   }
   if (h->d.kernel == SDPGPU_KERNEL_SEPARABLE) {
@@ -496,9 +507,7 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
       HIP_TRY(h, hipEventRecord(p.ev1, h->stream));
       p.timed = true;
     }
-    h->period_done[period - 1] = 1;
-    h->policy_done[period - 1] = 1;
-    if (!h->d.store_all_values && period + 2 <= h->T) h->period_done[period + 1] = 0;
+    mark_period_done(h, period);
     return SDPGPU_OK;
   }
   bool use_window = false;
@@ -567,9 +576,7 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
     p.timed = false;
   }
   if (part == SDPGPU_PART_INTERIOR) return SDPGPU_OK;  // the period is complete only after its boundary part
-  h->period_done[period - 1] = 1;
-  h->policy_done[period - 1] = 1;
-  if (!h->d.store_all_values && period + 2 <= h->T) h->period_done[period + 1] = 0;  // V_{t+2} was overwritten
+  mark_period_done(h, period);
   return SDPGPU_OK;
 }
 
@@ -1281,6 +1288,7 @@ int sdpgpu_solve(sdpgpu_handle* h, int32_t sync) {
       hipError_t e = hipGraphLaunch(h->sweep_exec, h->stream);
       if (e == hipSuccess) {
         h->graph_replays++;
+        mark_sweep_done(h);  // (as the captured sweep left them: a replay rewrites every table the flags speak of)
         done = true;
       } else {
         (void)hipGetLastError();
@@ -1329,6 +1337,7 @@ int sdpgpu_solve(sdpgpu_handle* h, int32_t sync) {
           std::fill(h->pending_chunks.begin(), h->pending_chunks.end(), 0);
           h->n_pending = 0;
           std::fill(h->key_row_clean.begin(), h->key_row_clean.end(), 0);
+          std::fill(h->period_done.begin(), h->period_done.end(), 0);
           h->err.clear();
         }
       } else {
