@@ -706,6 +706,82 @@ int sdpgpu_multicash_solve(const sdpgpu_multicash* k, double* final_value, int32
  * depositeRate; final_value = iniCash + V_1(iniState) (:160), (y1, y2) = getAction(iniState). */
 int sdpgpu_multixr_solve(const sdpgpu_multicash* k, double deposit_rate, double* final_value, int32_t* y1, int32_t* y2,
                          int64_t* states_per_period, int64_t* cells, double* gpu_ms);
+
+/* ---- sdp.cash.multiItem.CashRecursionV: the two functional equations V(x1, x2, w) and Pi(y1, y2, R) ---------------------
+ * Replaces `new CashRecursionV(...).getExpectedValueV(iniState)` / getAction / getYStar / getAlpha
+ * (src/sdp/cash/multiItem/CashRecursionV.java:83-194) for the lambdas of cash.multiItem.MultiItemYR.main
+ * (MultiItemYR.java:104-158) and MultiItemYRTesting.main (its two order bounds, MultiItemYRTesting.java:100-101, and its
+ * rounding, :163-165):
+ *   Pi_t(y1, y2, R) = sum over the pmf list, in list order, of p_j * V_{t+1}(successor_j)           (CashRecursionV.java:83-97)
+ *     successor (MultiItemYR.java:138-158): e_i = max(0, y_i - d_i); w' = (p1 min(y1, d1) + p2 min(y2, d2)) +
+ *     (1 + depositeRate) * ((R - c1 y1) - c2 y2); e1, e2, w' rounded (below); w' clamped to [min_cash, max_cash], e1 clamped
+ *     ABOVE only to max_inventory, e2 clamped BELOW only to min_inventory; (t + 1, e1, e2, w').  discountFactor is never used.
+ *   V_t(x1, x2, w), t <= T (:100-131): R = (w + c1 x1) + c2 x2; the levels i in [(int) x1, (int) x1 + Q1), j in [(int) x2,
+ *     (int) x2 + Q2) with c1 i + c2 j < R + 0.1, row-major, accepted when Pi > val + 0.01 from val = -Double.MAX_VALUE and
+ *     best = (x1, x2); then getYStar(t, R).  V_{T+1} = w + sal1 x1 + sal2 x2 (MultiItemYR.java:132-135).
+ *   y*(t, R) (:149-173): the UNSHIFTED box [0, Q1) x [0, Q2), every entry, `> val + 0.1`, default (0, 0); alpha(t, R)
+ *     (:176-194) is computed iff c1 y1* + c2 y2* >= R + 0.1: the 100 values of `for (alpha = 0; alpha <= 1; alpha += 0.01)`
+ *     (fp64 accumulation: the 101st is 1.0000000000000007), y1 = (alpha R) / c1, y2 = ((1 - alpha) R) / c2, `> best + 0.1`,
+ *     default 0.
+ * Rounding: SDPGPU_MULTIV_TRUNC10 is `Math.round(v * 10) / 10` (long / int: truncates toward zero, MultiItemYR.java:149-151),
+ * SDPGPU_MULTIV_ROUND is `Math.round(v)` (MultiItemYRTesting.java:163-165); both leave integers, so the V states of periods
+ * 2 .. T live on an integer lattice.  V is a pure function of the state, and the engine solves a SUPERSET of the reference's
+ * memo: it evaluates the alpha line of every (t, R), the reference only where y* is not affordable.  Every state, (t, R) row
+ * and value of the reference is in the tables, bit for bit; the counts below are the engine's own. */
+#define SDPGPU_MULTIV_TRUNC10 0
+#define SDPGPU_MULTIV_ROUND 1
+typedef struct sdpgpu_multiv {
+  int32_t T;          /* horizon, 1 .. 16 */
+  int32_t q_bound[2]; /* Q1, Q2 (MultiItemYR.java:89 has one Qbound for both), 1 .. 1024 each */
+  int32_t rounding;   /* SDPGPU_MULTIV_TRUNC10 / _ROUND */
+  double price[2], vari_cost[2], sal_price[2];
+  double deposit_rate;
+  double ini_cash, ini_i1, ini_i2; /* the period-1 state (x1, x2, w); integer inventories */
+  double min_inventory, max_inventory, min_cash, max_cash; /* integers; 0 <= min_cash */
+  const int32_t* pmf_off; /* T + 1 offsets into d1 / d2 / p, as sdpgpu_multicash */
+  const double* d1;
+  const double* d2;
+  const double* p;
+} sdpgpu_multiv;
+
+typedef struct sdpgpu_multiv_result {
+  double value;        /* V_1(iniState), MultiItemYR.java:172 */
+  double y1, y2;       /* getAction(iniState), :174 */
+  double ystar1, ystar2; /* getYStar(1, iniCash), :179-180 */
+  int32_t constrained; /* 1: the reference computed alpha(1, iniCash) */
+  int32_t forms;       /* SDPGPU_MULTIV_FORM_* bits of the Pi kernel forms that ran */
+  double alpha;        /* alpha(1, iniCash); defined only when constrained */
+  int64_t cells;       /* (Pi entry, demand pair) evaluations of the backward pass */
+  double gpu_ms;       /* device time of the forward and the backward pass */
+} sdpgpu_multiv_result;
+#define SDPGPU_MULTIV_FORM_SIDE 0x1u    /* integer levels: e_i and revenue_i read from the per-product side tables */
+#define SDPGPU_MULTIV_FORM_GENERIC 0x2u /* the alpha line's fractional levels: the transition evaluated per cell */
+
+/* The (t, R) rows of CashRecursionV's cacheYStar / cacheAlpha: register before a solve (per thread; NULL clears), filled by
+ * the next sdpgpu_multiv_solve of the thread with one row per distinct R of every period, in (period, R) order.  `alpha` is
+ * defined only where `constrained` is 1, which is exactly where the reference computed it.  `rows` receives the number of
+ * rows; nothing is written when it exceeds `capacity`. */
+typedef struct sdpgpu_multiv_rtable {
+  int64_t capacity;
+  int64_t rows;
+  int32_t* period;
+  double* R;
+  int32_t* y1;
+  int32_t* y2;
+  int32_t* constrained;
+  double* alpha;
+} sdpgpu_multiv_rtable;
+void sdpgpu_multiv_set_rtable(sdpgpu_multiv_rtable* table);
+
+/* states / distinct R / Pi entries of periods 1 .. T (T entries each, may be NULL).  The V states come out through
+ * sdpgpu_multi_set_table (periods 1 .. T; `cash` = w, q1 = q2 = 0, a1 / a2 = the chosen levels).  V_{t+1} is laid out DENSE on
+ * the lattice (x1, x2, w) of the bounds; a lattice of more than 2^27 points is refused (SDPGPU_ERR_UNSUPPORTED, naming the
+ * bounds), as are, all before any device call and naming the field (SDPGPU_ERR_ARG): min_cash < 0 or ini_cash < 0 (an empty
+ * action list would return -Double.MAX_VALUE), non-integer initial inventories or bounds, vari_cost <= 0, q_bound < 1, T out of
+ * range, a negative or non-finite demand.  A period whose Pi table (distinct R x levels) exceeds 2^28 entries ends the solve
+ * with SDPGPU_ERR_UNSUPPORTED.  Errors through sdpgpu_multilead_last_error(). */
+int sdpgpu_multiv_solve(const sdpgpu_multiv* k, sdpgpu_multiv_result* out, int64_t* states_per_period,
+                        int64_t* r_per_period, int64_t* entries_per_period);
 /* Kernel time of period t of the last solve (ms), needs sdpgpu_set_profiling(h, 1). */
 double sdpgpu_period_ms(sdpgpu_handle* h, int32_t period);
 /* ABI 6: (state, action, demand) cells of period t on this rank's slab, as sdpgpu_stats.cells_evaluated sums them over the periods

@@ -14,7 +14,8 @@ from .functors import (BackorderFunctor, CashFunctor, CashXRFunctor, CashLeadtim
                        SurvivalFunctor, java_round)
 from .multiitem import (Actions, CashRecursionMulti, CashRecursionMultiLead, CashRecursionMultiXR, CashSimulationMulti,
                         CashSimulationMultiXR, CashStateMulti, CashStateMultiLead, CashStateMultiXR, MultiLeadResult, MultiPolicy,
-                        multicash_solve, multilead_solve, multixr_solve)
+                        multicash_solve, multilead_solve, multixr_solve,
+                        CashRecursionV, CashStateMultiYR, CashStateR, MultiVResult, multiv_alpha_list, multiv_solve)
 from .pmf import BinomialDist, DiscreteDistribution, GammaDist, GetPmf, NormalDist, PoissonDist, UniformIntDist, staff_level_pmf
 from .recursion import (CLSP, CashLeadtimeRecursion, CashRecursion, CashRecursionXR, LeadtimeRecursion, Recursion, RecursionBatch, RecursionG,
                         RiskRecursion)
@@ -31,6 +32,7 @@ __all__ = [
     "multilead_solve", "multicash_solve", "multixr_solve", "MultiLeadResult", "Actions", "CashRecursionMulti",
     "CashRecursionMultiLead", "CashRecursionMultiXR", "CashStateMulti", "CashStateMultiLead", "CashStateMultiXR",
     "MultiPolicy", "CashSimulationMulti", "CashSimulationMultiXR",
+    "multiv_solve", "multiv_alpha_list", "MultiVResult", "CashRecursionV", "CashStateMultiYR", "CashStateR",
     "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "SimulationBatch", "RiskSimulation", "CashSimulation", "CashSimulationXR", "RecursionG", "Sampling",
     "FitsS", "FindsSOverDraft", "SimulateFitsS", "CheckKConvexity", "SdpgpuConvexity",
     "State", "LeadtimeState", "CashState", "CashStateXR", "CashLeadtimeState", "RiskState", "OptDirection", "java_round",

@@ -201,6 +201,52 @@ class SdpgpuMulticash(C.Structure):
     ]
 
 
+class SdpgpuMultiv(C.Structure):
+    """struct sdpgpu_multiv (include/sdpgpu.h)."""
+
+    _fields_ = [
+        ("T", C.c_int32), ("q_bound", C.c_int32 * 2), ("rounding", C.c_int32),
+        ("price", C.c_double * 2), ("vari_cost", C.c_double * 2), ("sal_price", C.c_double * 2),
+        ("deposit_rate", C.c_double),
+        ("ini_cash", C.c_double), ("ini_i1", C.c_double), ("ini_i2", C.c_double),
+        ("min_inventory", C.c_double), ("max_inventory", C.c_double), ("min_cash", C.c_double), ("max_cash", C.c_double),
+        ("pmf_off", C.POINTER(C.c_int32)), ("d1", C.POINTER(C.c_double)), ("d2", C.POINTER(C.c_double)),
+        ("p", C.POINTER(C.c_double)),
+    ]
+
+
+class SdpgpuMultivResult(C.Structure):
+    """struct sdpgpu_multiv_result (include/sdpgpu.h)."""
+
+    _fields_ = [("value", C.c_double), ("y1", C.c_double), ("y2", C.c_double), ("ystar1", C.c_double), ("ystar2", C.c_double),
+                ("constrained", C.c_int32), ("forms", C.c_int32), ("alpha", C.c_double), ("cells", C.c_int64),
+                ("gpu_ms", C.c_double)]
+
+
+class SdpgpuMultivRtable(C.Structure):
+    """struct sdpgpu_multiv_rtable (include/sdpgpu.h)."""
+
+    _fields_ = [("capacity", C.c_int64), ("rows", C.c_int64), ("period", C.POINTER(C.c_int32)), ("R", C.POINTER(C.c_double)),
+                ("y1", C.POINTER(C.c_int32)), ("y2", C.POINTER(C.c_int32)), ("constrained", C.POINTER(C.c_int32)),
+                ("alpha", C.POINTER(C.c_double))]
+
+
+MULTIV_TRUNC10, MULTIV_ROUND = 0, 1  # SDPGPU_MULTIV_*: the rounding of the transition
+MULTIV_FORMS = {"SIDE": 0x1, "GENERIC": 0x2}  # SDPGPU_MULTIV_FORM_*
+
+
+def make_multiv_rtable(capacity: int):
+    """-> (struct, dict of numpy arrays it points to)."""
+    import numpy as np
+    arrs = {n: np.zeros(capacity, np.int32) for n in ("period", "y1", "y2", "constrained")}
+    arrs["R"], arrs["alpha"] = np.zeros(capacity), np.zeros(capacity)
+    t = SdpgpuMultivRtable()
+    t.capacity, t.rows = capacity, 0
+    for n, a in arrs.items():
+        setattr(t, n, a.ctypes.data_as(C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double)))
+    return t, arrs
+
+
 class SdpgpuMultiTable(C.Structure):
     """struct sdpgpu_multi_table (include/sdpgpu.h)."""
 
@@ -341,6 +387,8 @@ EXPORTS = {
     "sdpgpu_multi_forms_used": (C.c_uint32, []),
     "sdpgpu_multicash_solve": (C.c_int, [C.POINTER(SdpgpuMulticash), _DP, _IP, _IP, _LP, _LP, _DP]),
     "sdpgpu_multixr_solve": (C.c_int, [C.POINTER(SdpgpuMulticash), C.c_double, _DP, _IP, _IP, _LP, _LP, _DP]),
+    "sdpgpu_multiv_set_rtable": (None, [C.POINTER(SdpgpuMultivRtable)]),
+    "sdpgpu_multiv_solve": (C.c_int, [C.POINTER(SdpgpuMultiv), C.POINTER(SdpgpuMultivResult), _LP, _LP, _LP]),
     "sdpgpu_batch_create": (C.c_int, [C.POINTER(SdpgpuDesc), C.c_int32, C.POINTER(_P)]),
     "sdpgpu_batch_create_ragged": (C.c_int, [C.POINTER(SdpgpuDesc), C.c_int32, C.POINTER(_P)]),
     "sdpgpu_batch_num_states": (C.c_int64, [_P, C.c_int32]),

@@ -249,6 +249,7 @@ int multicash_problem(const sdpgpu_multicash* k, int model, double deposit_rate,
 
 std::string& ml_error();    // sdpgpu_sparse.hip: the calling thread's text behind sdpgpu_multilead_last_error()
 void ml_test_throw_hook();  // sdpgpu_sparse.hip: SDPGPU_TEST_THROW (tests of the barrier, no device needed)
+sdpgpu_multi_table* ml_table();  // sdpgpu_sparse.hip: the calling thread's sdpgpu_multi_set_table request (sdpgpu_multiv.hip fills it too)
 
 // No C++ exception crosses the C ABI: ml_guard wraps the body of every two-product entry point.
 template <class Body>

@@ -1805,6 +1805,8 @@ std::string& ml_error() { return g_ml_error; }
 
 void ml_test_throw_hook() { test_throw_hook(); }
 
+sdpgpu_multi_table* ml_table() { return g_ml_table; }
+
 int multilead_problem(const sdpgpu_multilead* k, Problem* out) {
   SparseProblem sp;
   if (const int rc = multilead_fill(k, sp)) return rc;

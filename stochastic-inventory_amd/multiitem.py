@@ -519,3 +519,250 @@ class CashSimulationMultiXR(_MultiSimulationBase):
     def simulateSDPGivenSamplNum(self, iniState: CashStateMultiXR) -> float:
         """CashSimulationMultiXR.java:61-88: the mean of the path sums + iniState.iniR."""
         return self._simulate(iniState) + iniState.iniR
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# sdp.cash.multiItem.CashRecursionV: the two functional equations V(x1, x2, w) and Pi(y1, y2, R) (sdpgpu_multiv_solve;
+# DESIGN 4, "V / Pi recursion").
+# ---------------------------------------------------------------------------------------------------------------
+@dataclass
+class MultiVResult:
+    value: float               # getExpectedValueV(iniState), MultiItemYR.java:172
+    action: List[float]        # getAction(iniState), :174
+    yStar: List[float]         # getYStar(1, iniCash), :179-180
+    constrained: bool          # the reference computed alpha(1, iniCash)
+    alpha: float               # ... and this is it (defined only then)
+    statesPerPeriod: List[int]
+    rPerPeriod: List[int]      # distinct R
+    entriesPerPeriod: List[int]  # Pi entries: flagged cells of the (R, y1, y2) table + the alpha line of every R
+    cells: int
+    gpu_ms: float
+    forms: int = 0             # SDPGPU_MULTIV_FORM_* bits (_abi.MULTIV_FORMS)
+    # rows {period, x1, x2, 0, 0, w, V, y1, y2} in the key order of cacheActions; None unless asked for
+    table: object = None
+    # rows {period, R, y1*, y2*, constrained, alpha} in the key order of cacheYStar; alpha is defined where constrained is 1
+    rtable: object = None
+
+
+def multiv_alpha_list() -> List[float]:
+    """The values `for (alpha = 0; alpha <= 1; alpha = alpha + 0.01)` visits (CashRecursionV.java:180): 100 of them, the
+    last 0.9900000000000007 (the 101st would be 1.0000000000000007)."""
+    out, alpha = [], 0.0
+    while alpha <= 1:
+        out.append(alpha)
+        alpha = alpha + 0.01
+    return out
+
+
+def _rounding_mode(rounding):
+    if rounding in ("trunc10", _abi.MULTIV_TRUNC10):
+        return _abi.MULTIV_TRUNC10
+    if rounding in ("round", _abi.MULTIV_ROUND):
+        return _abi.MULTIV_ROUND
+    raise ValueError(f"rounding {rounding!r}: 'trunc10' (MultiItemYR) or 'round' (MultiItemYRTesting)")
+
+
+def fill_multiv(k, *, T, q_bound, rounding, price, vari_cost, sal_price, ini_cash, ini_i1, ini_i2, min_inventory, max_inventory,
+                min_cash, max_cash, pmf, deposit_rate=0.0):
+    """pmf[t] = rows {d1, d2, probability} as for fill_multicash; q_bound = Qbound or (Qbound1, Qbound2)."""
+    qb = (q_bound, q_bound) if np.isscalar(q_bound) else tuple(q_bound)
+    k.T, k.rounding = T, _rounding_mode(rounding)
+    k.q_bound[0], k.q_bound[1] = int(qb[0]), int(qb[1])
+    for name, val in (("price", price), ("vari_cost", vari_cost), ("sal_price", sal_price)):
+        getattr(k, name)[0], getattr(k, name)[1] = val
+    for name, val in (("deposit_rate", deposit_rate), ("ini_cash", ini_cash), ("ini_i1", ini_i1), ("ini_i2", ini_i2),
+                      ("min_inventory", min_inventory), ("max_inventory", max_inventory), ("min_cash", min_cash),
+                      ("max_cash", max_cash)):
+        setattr(k, name, float(val))
+    if len(pmf) != T:
+        raise ValueError(f"pmf has {len(pmf)} periods, T = {T}")
+    tiles = [np.asarray(t, dtype=np.float64).reshape(-1, 3) for t in pmf]
+    off = np.concatenate([[0], np.cumsum([len(t) for t in tiles])]).astype(np.int32)
+    allp = np.concatenate(tiles, axis=0)
+    d1, d2, p = (np.ascontiguousarray(allp[:, c]) for c in range(3))
+    k._keep = (off, d1, d2, p)
+    k.pmf_off = off.ctypes.data_as(C.POINTER(C.c_int32))
+    k.d1, k.d2, k.p = (a.ctypes.data_as(C.POINTER(C.c_double)) for a in (d1, d2, p))
+    return k
+
+
+def multiv_solve(table: bool = False, **kw) -> MultiVResult:
+    """`sdp.cash.multiItem.CashRecursionV` as `cash.multiItem.MultiItemYR.main` sets it up (MultiItemYR.java:104-181;
+    rounding='round' and a pair of bounds: MultiItemYRTesting.main): one call = getExpectedValueV(iniState) +
+    getAction(iniState) + getYStar(1, iniCash).  table=True also returns the V states and the (t, R) rows (a second run
+    with tables large enough for them)."""
+    lib = _abi.load()
+    k = fill_multiv(_abi.SdpgpuMultiv(), **kw)
+    T = int(k.T)
+
+    def once():
+        out = _abi.SdpgpuMultivResult()
+        states, rs, entries = ((C.c_int64 * max(T, 1))() for _ in range(3))
+        rc = lib.sdpgpu_multiv_solve(C.byref(k), C.byref(out), states, rs, entries)
+        if rc:
+            raise SdpgpuError(rc, lib.sdpgpu_multilead_last_error().decode())
+        return MultiVResult(out.value, [out.y1, out.y2], [out.ystar1, out.ystar2], bool(out.constrained), out.alpha,
+                            list(states)[:T], list(rs)[:T], list(entries)[:T], out.cells, out.gpu_ms, forms=int(out.forms))
+
+    res = once()
+    if table:
+        vt, varrs = _abi.make_multi_table(sum(res.statesPerPeriod))
+        rt, rarrs = _abi.make_multiv_rtable(sum(res.rPerPeriod))
+        lib.sdpgpu_multi_set_table(C.byref(vt))
+        lib.sdpgpu_multiv_set_rtable(C.byref(rt))
+        try:
+            res = once()
+        finally:
+            lib.sdpgpu_multi_set_table(None)
+            lib.sdpgpu_multiv_set_rtable(None)
+        res.table = _abi.multi_table_rows(vt, varrs)
+        n = int(rt.rows)
+        res.rtable = np.stack([rarrs[c][:n].astype(np.float64) for c in ("period", "R", "y1", "y2", "constrained", "alpha")], axis=1)
+    return res
+
+
+class CashStateMultiYR:
+    """sdp.cash.multiItem.CashStateMultiYR (CashStateMultiYR.java:14-40): (period, y1, y2, R)."""
+
+    def __init__(self, period: int, iniInventory1: float, iniInventory2: float, R: float):
+        self.period, self.iniInventory1, self.iniInventory2, self.iniR = int(period), float(iniInventory1), float(iniInventory2), float(R)
+
+    def getPeriod(self): return self.period
+    def getIniInventory1(self): return self.iniInventory1
+    def getIniInventory2(self): return self.iniInventory2
+    def getIniR(self): return self.iniR
+
+
+class CashStateR:
+    """sdp.cash.multiItem.CashStateR (CashStateR.java:13-30): (period, R)."""
+
+    def __init__(self, period: int, R: float):
+        self.period, self.iniR = int(period), float(R)
+
+    def getPeriod(self): return self.period
+    def getIniR(self): return self.iniR
+
+
+def opt_table(rrows, variCost):
+    """CashRecursionV.getOptTable (CashRecursionV.java:251-272) from the (t, R) rows {period, R, y1*, y2*, constrained, alpha}:
+    rows {period, R, c1, c2, y1*, y2*, cashConstrained, alpha}, alpha = 10000 where y* is affordable."""
+    c1, c2 = variCost
+    out = []
+    for period, R, y1, y2, cons, a in np.asarray(rrows, dtype=np.float64).reshape(-1, 6):
+        cashConstrained, alpha = 0.0, 10000.0
+        if c1 * y1 + c2 * y2 >= R + 0.1:
+            cashConstrained = 1.0
+            alpha = a if cons else float("nan")  # (cacheAlpha.get; the two conditions are the same statement)
+        out.append([period, R, c1, c2, y1, y2, cashConstrained, alpha])
+    return np.array(out).reshape(-1, 8)
+
+
+def opt_table_detail(vrows, rrows, variCost):
+    """CashRecursionV.getOptTableDetail (CashRecursionV.java:279-325) from the V-state rows {period, x1, x2, ., ., w, V, y1, y2}
+    and the (t, R) rows: rows {period, x1, x2, w, c1, c2, R, y1*, y2*, cashConstrained, alpha, yHead1, yHead2} with the
+    reference's five cases and tolerances as written.  Case 2 reads cacheAlpha; where the reference never computed it (y* costs
+    within 0.1 of R: its `cacheAlpha.get` would throw a NullPointerException) alpha and the yHeads are NaN."""
+    c1, c2 = variCost
+    rr = np.asarray(rrows, dtype=np.float64).reshape(-1, 6)
+    ystar = {(int(r[0]), float(r[1]) + 0.0): r for r in rr}
+    out = []
+    for row in sorted(np.asarray(vrows, dtype=np.float64).reshape(-1, 9).tolist(), key=lambda r: (r[0], r[1], r[2], r[5])):
+        period, x1, x2, w = int(row[0]), row[1], row[2], row[5]
+        R = w + c1 * x1 + c2 * x2  # CashStateMulti.getIniR
+        rrow = ystar[(period, R + 0.0)]
+        ys = (rrow[2], rrow[3])
+        cashConstrained, alpha = 0.0, 10000.0
+        yHeads = [0.0, 0.0]
+        if x1 < ys[0] + 0.1 and x2 < ys[1] and c1 * ys[0] + c2 * ys[1] < R + 0.1:
+            yHeads = [ys[0], ys[1]]
+            cashConstrained = 1.0
+        elif x1 > ys[0] - 0.1 and x2 > ys[1] - 0.1:
+            yHeads = [x1, x2]
+            cashConstrained = 5.0
+        elif x1 > ys[0] - 0.1 and x2 < ys[1] + 0.1:
+            yHeads = [x1, min(ys[1], (R - x1 * c1) / c2)]
+            cashConstrained = 4.0
+        elif x1 < ys[0] + 0.1 and x2 > ys[1] - 0.1:
+            yHeads = [min(ys[0], (R - x2 * c2) / c1), x2]
+            cashConstrained = 3.0
+        elif x1 < ys[0] + 0.1 and x2 < ys[1] + 0.1 and c1 * ys[0] + c2 * ys[1] > R - 0.1:
+            alpha = rrow[5] if rrow[4] else float("nan")
+            yHeads = [alpha * R / c1, (1 - alpha) * R / c2]
+            cashConstrained = 2.0
+        out.append([period, x1, x2, w, c1, c2, R, ys[0], ys[1], cashConstrained, alpha, yHeads[0], yHeads[1]])
+    return np.array(out).reshape(-1, 13)
+
+
+class CashRecursionV:
+    """sdp.cash.multiItem.CashRecursionV (CashRecursionV.java:28-325) for the lambdas of MultiItemYR.main / MultiItemYRTesting.main;
+    functor = the keyword arguments of multiv_solve (initial state, T and pmf come from the calls).  The lambdas are accepted
+    and kept for the caller.  discountFactor is kept too and, as in the reference, never used.  The first getExpectedValueV
+    runs the solve and reads both tables back; they hold a superset of the reference's memo (the engine evaluates the alpha line
+    of every (t, R)), so getOptTable / getOptTableDetail may show rows the reference's run would not have visited."""
+
+    def __init__(self, discountFactor, Pmf, buildActionListV=None, buildActionListPai=None, stateTransition=None,
+                 boundFinalCash=None, T=None, variCost=None, *, functor=None):
+        if functor is None:
+            raise TypeError("functor: the parameters of the driver's lambdas (the keyword arguments of multiv_solve)")
+        self.discountFactor, self.Pmf, self.T = discountFactor, Pmf, T
+        self.buildActionListV, self.buildActionListPai = buildActionListV, buildActionListPai
+        self.stateTransition, self.boundFinalCash = stateTransition, boundFinalCash
+        self.functor = dict(functor)
+        if T is not None:
+            self.functor["T"] = int(T)
+        self.variCost = list(variCost) if variCost is not None else list(self.functor["vari_cost"])
+        self._result = None
+
+    def _solve(self, state):
+        if self._result is None:
+            if state.getPeriod() != 1:
+                raise ValueError("the first getExpectedValueV must be asked for a period-1 state (it fixes the reachable set)")
+            kw = dict(self.functor, ini_i1=state.iniInventory1, ini_i2=state.iniInventory2, ini_cash=state.iniCash, pmf=self.Pmf)
+            self._result = multiv_solve(table=True, **kw)
+            self._memo = {(int(r[0]), r[1], r[2], r[5] + 0.0): (float(r[6]), [float(r[7]), float(r[8])]) for r in self._result.table.tolist()}
+            self._rows = {(int(r[0]), r[1] + 0.0): r for r in self._result.rtable.tolist()}
+        return self._result
+
+    @property
+    def result(self) -> MultiVResult:
+        return self._result
+
+    def _lookup(self, state):
+        self._solve(state)
+        k = (state.getPeriod(), state.iniInventory1, state.iniInventory2, state.iniCash + 0.0)
+        if k not in self._memo:
+            raise KeyError(f"state {k} was not visited from the initial state")
+        return self._memo[k]
+
+    def getExpectedValueV(self, state: CashStateMulti) -> float:
+        return self._lookup(state)[0]
+
+    def getAction(self, state: CashStateMulti):
+        """the optimal levels {y1, y2} of (x1, x2, w) (CashRecursionV.java:139-141)."""
+        return list(self._lookup(state)[1])
+
+    def _row(self, stateR: CashStateR):
+        if self._result is None:
+            raise RuntimeError("ask getExpectedValueV for the period-1 state first (it runs the solve)")
+        k = (stateR.getPeriod(), stateR.getIniR() + 0.0)
+        if k not in self._rows:
+            raise KeyError(f"(period, R) = {k} is not an R of a visited state (a new solve would be needed)")
+        return self._rows[k]
+
+    def getYStar(self, stateR: CashStateR):
+        """y1*, y2* of (t, R) (CashRecursionV.java:149-173)."""
+        r = self._row(stateR)
+        return [r[2], r[3]]
+
+    def getAlpha(self, stateR: CashStateR) -> float:
+        """alpha(t, R) (CashRecursionV.java:176-194), where the reference's solve computed it (y* not affordable)."""
+        r = self._row(stateR)
+        if not r[4]:
+            raise KeyError(f"alpha{(stateR.getPeriod(), stateR.getIniR())}: y* is affordable there, the reference's memo holds no alpha")
+        return r[5]
+
+    def getOptTable(self):
+        return opt_table(self._result.rtable, self.variCost)
+
+    def getOptTableDetail(self):
+        return opt_table_detail(self._result.table, self._result.rtable, self.variCost)

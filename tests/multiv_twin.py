@@ -1,0 +1,238 @@
+"""A literal, memoised restatement of sdp.cash.multiItem.CashRecursionV (CashRecursionV.java:83-194) over the lambdas of
+cash.multiItem.MultiItemYR.main (MultiItemYR.java:104-158; the rounding and the two order bounds of MultiItemYRTesting.main,
+MultiItemYRTesting.java:100-101, 163-165).  Written from the Java, statement for statement, not from the kernels: the five
+maps are the reference's five caches, filled in the reference's call order, so what they hold after `drive()` is the
+reference's memo.  The counters record which corners an instance reaches (clamps that fire, candidates that beat `val` by
+less than the scan's threshold), so that a parity test can show it did not pass vacuously.  Also the instances the tests share.
+"""
+import math
+
+import numpy as np
+
+DBL_MAX = 1.7976931348623157e308
+
+
+def java_round(x):
+    """java.lang.Math.round(double): nearest long, ties toward +infinity (as stochastic_inventory_amd.java_round)."""
+    f = math.floor(x)
+    return int(f + 1) if (x - f) >= 0.5 else int(f)
+
+
+def long_div(a, b):
+    """Java long / int: truncates toward zero."""
+    q = abs(a) // b
+    return q if a >= 0 else -q
+
+
+class Twin:
+    def __init__(self, *, T, q_bound, rounding, price, vari_cost, sal_price, min_inventory, max_inventory, min_cash, max_cash,
+                 pmf, deposit_rate=0.0, **_ini):
+        self.T = T
+        self.Q1, self.Q2 = (q_bound, q_bound) if np.isscalar(q_bound) else q_bound
+        self.rounding = rounding
+        self.p1, self.p2 = price
+        self.v1, self.v2 = vari_cost
+        self.variCost = list(vari_cost)
+        self.salPrice = list(sal_price)
+        self.depositeRate = deposit_rate
+        self.minInventoryState, self.maxInventoryState = min_inventory, max_inventory
+        self.minCashState, self.maxCashState = min_cash, max_cash
+        self.pmf = [np.asarray(t, dtype=np.float64).reshape(-1, 3).tolist() for t in pmf]
+        self.cacheActions, self.cacheYStar, self.cacheAlpha, self.cacheValuesV, self.cacheValuesPai = {}, {}, {}, {}, {}
+        self.count = dict(w_hi=0, w_lo=0, e1_hi=0, e2_lo=0, v_near=0, ystar_near=0, alpha_near=0)
+
+    # ---- the lambdas ----
+    def buildActionListPai(self):  # MultiItemYR.java:104-113
+        return [(float(i), float(j)) for i in range(self.Q1) for j in range(self.Q2)]
+
+    def buildActionListV(self, s):  # :116-129
+        _, x1, x2, w = s
+        miny1, miny2 = int(x1), int(x2)
+        iniR = w + self.v1 * x1 + self.v2 * x2
+        actions = []
+        for i in range(miny1, miny1 + self.Q1):
+            for j in range(miny2, miny2 + self.Q2):
+                if self.v1 * float(i) + self.v2 * float(j) < iniR + 0.1:
+                    actions.append((float(i), float(j)))
+        return actions
+
+    def boundFinalCash(self, s):  # :132-135
+        _, x1, x2, w = s
+        return w + self.salPrice[0] * x1 + self.salPrice[1] * x2
+
+    def _round(self, v):
+        if self.rounding == "round":
+            return float(java_round(v))  # MultiItemYRTesting.java:163-165
+        return float(long_div(java_round(v * 10), 10))  # MultiItemYR.java:149-151
+
+    def stateTransition(self, s, d):  # :138-158
+        t, y1, y2, R = s
+        endInventory1 = y1 - d[0]
+        endInventory1 = max(0.0, endInventory1)
+        endInventory2 = y2 - d[1]
+        endInventory2 = max(0.0, endInventory2)
+        revenue1 = self.p1 * min(y1, d[0])
+        revenue2 = self.p2 * min(y2, d[1])
+        nextW = revenue1 + revenue2 + (1 + self.depositeRate) * (R - self.v1 * y1 - self.v2 * y2)
+        endInventory1 = self._round(endInventory1)
+        endInventory2 = self._round(endInventory2)
+        nextW = self._round(nextW)
+        if nextW > self.maxCashState:
+            nextW = float(self.maxCashState)
+            self.count["w_hi"] += 1
+        if nextW < self.minCashState:
+            nextW = float(self.minCashState)
+            self.count["w_lo"] += 1
+        if endInventory1 > self.maxInventoryState:
+            endInventory1 = float(self.maxInventoryState)
+            self.count["e1_hi"] += 1
+        if endInventory2 < self.minInventoryState:
+            endInventory2 = float(self.minInventoryState)
+            self.count["e2_lo"] += 1
+        return (t + 1, endInventory1 + 0.0, endInventory2 + 0.0, nextW + 0.0)
+
+    # ---- the recursion ----
+    def getExpectedValuePai(self, s):  # CashRecursionV.java:83-97
+        if s in self.cacheValuesPai:
+            return self.cacheValuesPai[s]
+        dAndP = self.pmf[s[0] - 1]
+        expectValue = 0.0
+        for j in range(len(dAndP)):
+            newState = self.stateTransition(s, (dAndP[j][0], dAndP[j][1]))
+            expectValue += dAndP[j][2] * self.getExpectedValueV(newState)
+        self.cacheValuesPai[s] = expectValue
+        return expectValue
+
+    def getExpectedValueV(self, s):  # :100-131
+        if s in self.cacheValuesV:
+            return self.cacheValuesV[s]
+        t, x1, x2, w = s
+        yHeads = self.buildActionListV(s)
+        val = -DBL_MAX
+        bestYs = (x1, x2)
+        if t <= self.T:
+            iniR = w + self.variCost[0] * x1 + self.variCost[1] * x2
+            for thisActions in yHeads:
+                thisActionsValue = self.getExpectedValuePai((t, thisActions[0], thisActions[1], iniR + 0.0))
+                if thisActionsValue > val + 0.01:
+                    val = thisActionsValue
+                    bestYs = thisActions
+                elif thisActionsValue > val:
+                    self.count["v_near"] += 1
+            self.getYStar((t, iniR + 0.0))
+            self.cacheActions.setdefault(s, bestYs)
+        else:
+            val = self.boundFinalCash(s)
+        self.cacheValuesV[s] = val
+        return val
+
+    def getAction(self, s):
+        return self.cacheActions.get(s)
+
+    def getYStar(self, s):  # :149-173
+        if s in self.cacheYStar:
+            return self.cacheYStar[s]
+        t, R = s
+        val = -DBL_MAX
+        bestYs = (0.0, 0.0)
+        for thisActions in self.buildActionListPai():
+            thisActionsValue = self.getExpectedValuePai((t, thisActions[0], thisActions[1], R))
+            if thisActionsValue > val + 0.1:
+                val = thisActionsValue
+                bestYs = thisActions
+            elif thisActionsValue > val:
+                self.count["ystar_near"] += 1
+        if self.variCost[0] * bestYs[0] + self.variCost[1] * bestYs[1] >= R + 0.1:
+            self.getAlpha(s)
+        self.cacheYStar[s] = bestYs
+        return bestYs
+
+    def getAlpha(self, s):  # :176-194
+        if s in self.cacheAlpha:
+            return self.cacheAlpha[s]
+        t, R = s
+        bestAlpha = 0.0
+        bestValue = -DBL_MAX
+        alpha = 0.0
+        while alpha <= 1:
+            y1 = alpha * R / self.variCost[0]
+            y2 = (1 - alpha) * R / self.variCost[1]
+            expectValue = self.getExpectedValuePai((t, y1 + 0.0, y2 + 0.0, R))
+            if expectValue > bestValue + 0.1:
+                bestValue = expectValue
+                bestAlpha = alpha
+            elif expectValue > bestValue:
+                self.count["alpha_near"] += 1
+            alpha = alpha + 0.01
+        self.cacheAlpha[s] = bestAlpha
+        return bestAlpha
+
+
+def drive(kw):
+    """MultiItemYR.java:170-181: V_1(ini), getAction(ini), getYStar(1, iniCash) -> (twin, value, action, y*)."""
+    tw = Twin(**kw)
+    ini = (1, float(kw["ini_i1"]), float(kw["ini_i2"]), float(kw["ini_cash"]) + 0.0)
+    value = tw.getExpectedValueV(ini)
+    action = tw.getAction(ini)
+    ystar = tw.getYStar((1, float(kw["ini_cash"]) + 0.0))
+    return tw, value, action, ystar
+
+
+def per_period(keys, T, first=1):
+    out = [0] * (T + 2)
+    for k in keys:
+        out[k[0]] += 1
+    return out[first:T + 1]
+
+
+# ---- the instances ----------------------------------------------------------------------------------------------------------
+def product_pmf(v1, p1, v2, p2):
+    return np.array([[float(a), float(b), pa * pb] for a, pa in zip(v1, p1) for b, pb in zip(v2, p2)])
+
+
+def instance_d(rounding):
+    a = product_pmf([0, 1, 3], [.2, .5, .3], [0, 2], [.6, .4])
+    b = product_pmf([1, 2], [.5, .5], [0, 1, 4], [.3, .3, .4])
+    return dict(T=3, q_bound=(4, 3), rounding=rounding, price=[2, 3.5], vari_cost=[1, 1.5], sal_price=[0.5, 0.75], deposit_rate=0.05,
+                ini_cash=3, ini_i1=0, ini_i2=0, min_inventory=1, max_inventory=4, min_cash=0, max_cash=14, pmf=[a, b, a])
+
+
+def random_instance(seed):
+    """T 1..3, Q1 != Q2 in 1..4, 1-3 demand points per product with n1 != n2, costs in halves, dep in {0, 0.05}, either
+    rounding, initial inventories sometimes > 0 (the V box then sits off the y* box)."""
+    rng = np.random.default_rng(7000 + seed)
+    T = int(rng.integers(1, 4))
+    Q1 = int(rng.integers(1, 5))
+    Q2 = int(rng.choice([q for q in range(1, 5) if q != Q1]))
+    pmf = []
+    for _ in range(T):
+        n1 = int(rng.integers(1, 4))
+        n2 = int(rng.choice([n for n in range(1, 4) if n != n1]))
+        v1 = np.sort(rng.choice(np.arange(0, 6), size=n1, replace=False))
+        v2 = np.sort(rng.choice(np.arange(0, 6), size=n2, replace=False))
+        p = rng.random((n1, n2)) + 0.05
+        p /= p.sum()
+        pmf.append(np.array([[float(a), float(b), float(p[i, j])] for i, a in enumerate(v1) for j, b in enumerate(v2)]))
+    return dict(T=T, q_bound=(Q1, Q2), rounding=str(rng.choice(["trunc10", "round"])),
+                price=[float(rng.integers(4, 16)) / 2, float(rng.integers(4, 24)) / 2],
+                vari_cost=[float(rng.integers(1, 5)) / 2, float(rng.integers(1, 7)) / 2],
+                sal_price=[float(rng.integers(0, 3)) / 2, float(rng.integers(0, 3)) / 4], deposit_rate=float(rng.choice([0.0, 0.05])),
+                ini_cash=float(rng.integers(0, 12)), ini_i1=float(rng.choice([0, 0, 1, 2])), ini_i2=float(rng.choice([0, 0, 1, 3])),
+                min_inventory=float(rng.integers(0, 2)), max_inventory=float(rng.integers(2, 7)), min_cash=0,
+                max_cash=float(rng.integers(10, 60)), pmf=pmf)
+
+
+def edge_instances():
+    base = dict(rounding="trunc10", price=[4, 6], vari_cost=[1, 1.5], sal_price=[0.5, 0.5], deposit_rate=0.0, ini_cash=4, ini_i1=0,
+                ini_i2=0, min_inventory=0, max_inventory=6, min_cash=0, max_cash=40)
+    two = product_pmf([0, 2], [.5, .5], [1, 2, 3], [.3, .3, .4])
+    wide = product_pmf(range(9), [1 / 9] * 9, range(8), [1 / 8] * 8)
+    return {
+        "T1": dict(base, T=1, q_bound=(3, 2), pmf=[two]),
+        "Q11": dict(base, T=2, q_bound=(1, 1), pmf=[two, two], rounding="round"),
+        "one_pair": dict(base, T=2, q_bound=(3, 2), pmf=[product_pmf([1], [1.0], [2], [1.0])] * 2),
+        "pairs72": dict(base, T=2, q_bound=(2, 2), pmf=[wide, wide], ini_cash=6),
+        "yr_small": dict(T=2, q_bound=(6, 5), rounding="trunc10", price=[5, 10], vari_cost=[1, 2], sal_price=[.5, 1], deposit_rate=0.0,
+                         ini_cash=10, ini_i1=0, ini_i2=0, min_inventory=0, max_inventory=200, min_cash=0, max_cash=10000,
+                         pmf=[product_pmf([2, 4, 5], [.25, .5, .25], [1, 3], [.6, .4])] * 2),
+    }
