@@ -3,7 +3,9 @@ cash.multiItem.MultiItemYR.main (MultiItemYR.java:104-158; the rounding and the 
 MultiItemYRTesting.java:100-101, 163-165).  Written from the Java, statement for statement, not from the kernels: the five
 maps are the reference's five caches, filled in the reference's call order, so what they hold after `drive()` is the
 reference's memo.  The counters record which corners an instance reaches (clamps that fire, candidates that beat `val` by
-less than the scan's threshold), so that a parity test can show it did not pass vacuously.  Also the instances the tests share.
+less than the scan's threshold, arguments of Math.round that sit half way), so that a parity test can show it did not pass
+vacuously.  `Closure` is the set the ENGINE solves (the alpha line of every (t, R)), restated from the header's contract with
+the same lambdas.  Also the instances the tests share.
 """
 import math
 
@@ -39,7 +41,7 @@ class Twin:
         self.minCashState, self.maxCashState = min_cash, max_cash
         self.pmf = [np.asarray(t, dtype=np.float64).reshape(-1, 3).tolist() for t in pmf]
         self.cacheActions, self.cacheYStar, self.cacheAlpha, self.cacheValuesV, self.cacheValuesPai = {}, {}, {}, {}, {}
-        self.count = dict(w_hi=0, w_lo=0, e1_hi=0, e2_lo=0, v_near=0, ystar_near=0, alpha_near=0)
+        self.count = dict(w_hi=0, w_lo=0, e1_hi=0, e2_lo=0, v_near=0, ystar_near=0, alpha_near=0, tie=0, tie_inv=0, inv_up=0)
 
     # ---- the lambdas ----
     def buildActionListPai(self):  # MultiItemYR.java:104-113
@@ -60,10 +62,20 @@ class Twin:
         _, x1, x2, w = s
         return w + self.salPrice[0] * x1 + self.salPrice[1] * x2
 
-    def _round(self, v):
+    def _round(self, v, inventory=False):
+        """`tie`: the argument of Math.round sat exactly half way (`tie_inv`: of those, the end inventories); `inv_up`: an end
+        inventory came out above its integer part, so rounding it is not truncating it."""
+        arg = v if self.rounding == "round" else v * 10
+        if arg - math.floor(arg) == 0.5:
+            self.count["tie"] += 1
+            self.count["tie_inv"] += int(inventory)
         if self.rounding == "round":
-            return float(java_round(v))  # MultiItemYRTesting.java:163-165
-        return float(long_div(java_round(v * 10), 10))  # MultiItemYR.java:149-151
+            out = float(java_round(v))  # MultiItemYRTesting.java:163-165
+        else:
+            out = float(long_div(java_round(v * 10), 10))  # MultiItemYR.java:149-151
+        if inventory and out > math.floor(v):
+            self.count["inv_up"] += 1
+        return out
 
     def stateTransition(self, s, d):  # :138-158
         t, y1, y2, R = s
@@ -74,8 +86,8 @@ class Twin:
         revenue1 = self.p1 * min(y1, d[0])
         revenue2 = self.p2 * min(y2, d[1])
         nextW = revenue1 + revenue2 + (1 + self.depositeRate) * (R - self.v1 * y1 - self.v2 * y2)
-        endInventory1 = self._round(endInventory1)
-        endInventory2 = self._round(endInventory2)
+        endInventory1 = self._round(endInventory1, inventory=True)
+        endInventory2 = self._round(endInventory2, inventory=True)
         nextW = self._round(nextW)
         if nextW > self.maxCashState:
             nextW = float(self.maxCashState)
@@ -178,6 +190,55 @@ def drive(kw):
     return tw, value, action, ystar
 
 
+class Closure:
+    """What sdpgpu_multiv_solve solves, from the header's contract (include/sdpgpu.h, "CashRecursionV": the engine evaluates
+    the alpha line of EVERY (t, R), the reference only where y* is not affordable), with the twin's lambdas and nothing else:
+      S_1 = {ini};  R_t = the distinct `iniR + 0.0` of S_t (period 1 also holds the driver's (1, iniCash));
+      E_t = per R, buildActionListV of the states that carry it + buildActionListPai, as (R, y1, y2);
+      S_{t+1} = stateTransition over the pmf list from every entry of E_t and from the 100 points of getAlpha's loop for every R.
+    S[t], R[t], E[t] for t = 1 .. T, and S[T + 1] (the terminal states).  A Twin of its own does the transitions, so no
+    counter or cache of another Twin moves."""
+
+    def __init__(self, kw):
+        tw = Twin(**kw)
+        T = kw["T"]
+        ini = (1, float(kw["ini_i1"]), float(kw["ini_i2"]), float(kw["ini_cash"]) + 0.0)
+        self.S, self.R, self.E = {1: {ini}}, {}, {}
+        for t in range(1, T + 1):
+            byR = {}
+            for s in self.S[t]:
+                iniR = s[3] + tw.variCost[0] * s[1] + tw.variCost[1] * s[2]  # CashRecursionV.java:108
+                byR.setdefault(iniR + 0.0, set()).update(tw.buildActionListV(s))
+            if t == 1:
+                byR.setdefault(ini[3], set())  # MultiItemYR.java:179-180
+            for acts in byR.values():
+                acts.update(tw.buildActionListPai())
+            self.R[t] = set(byR)
+            self.E[t] = {(R, y1, y2) for R, acts in byR.items() for (y1, y2) in acts}
+            dAndP = tw.pmf[t - 1]  # rows {d1, d2, p}: stateTransition reads the first two
+            nxt = {tw.stateTransition((t, y1, y2, R), d) for R, y1, y2 in self.E[t] for d in dAndP}
+            for R in byR:
+                alpha = 0.0
+                while alpha <= 1:  # CashRecursionV.java:180-184
+                    y1 = alpha * R / tw.variCost[0]
+                    y2 = (1 - alpha) * R / tw.variCost[1]
+                    nxt.update(tw.stateTransition((t, y1 + 0.0, y2 + 0.0, R), d) for d in dAndP)
+                    alpha = alpha + 0.01
+            self.S[t + 1] = nxt
+
+    def covers(self, tw):
+        """every key of the Twin's five caches is in the closure (the engine's memo is a superset of the reference's)"""
+        T = tw.T
+        return (all(k in self.S[k[0]] for k in tw.cacheValuesV) and all(k in self.S[k[0]] for k in tw.cacheActions)
+                and all(k[1] in self.R[k[0]] for k in tw.cacheYStar) and all(k[1] in self.R[k[0]] for k in tw.cacheAlpha)
+                and all(k[0] <= T for k in tw.cacheYStar))
+
+    def extra(self, tw):
+        """(V states, (t, R) rows) of periods 1 .. T that the Twin's memo does not hold"""
+        return (sorted(s for t in range(1, tw.T + 1) for s in self.S[t] if s not in tw.cacheActions),
+                sorted((t, R) for t in range(1, tw.T + 1) for R in self.R[t] if (t, R) not in tw.cacheYStar))
+
+
 def per_period(keys, T, first=1):
     out = [0] * (T + 2)
     for k in keys:
@@ -235,4 +296,73 @@ def edge_instances():
         "yr_small": dict(T=2, q_bound=(6, 5), rounding="trunc10", price=[5, 10], vari_cost=[1, 2], sal_price=[.5, 1], deposit_rate=0.0,
                          ini_cash=10, ini_i1=0, ini_i2=0, min_inventory=0, max_inventory=200, min_cash=0, max_cash=10000,
                          pmf=[product_pmf([2, 4, 5], [.25, .5, .25], [1, 3], [.6, .4])] * 2),
+        **hard_edges(),
     }
+
+
+HARD_EDGES = ("w0_offset", "one_cash_plane", "no_stock_kept", "blocks_257", "T5_tiny", "rounding_ties", "rounding_ties_trunc10")
+
+
+def hard_edges():
+    """Off the inputs on which the engine's arithmetic is the identity: a cash lattice that does not start at 0, one cash plane,
+    no stock of product 1 kept, more than 256 states AND more than 256 distinct R in a period, four hand-overs of V_{t+1}, and
+    end inventories that sit half way between two lattice points in either rounding."""
+    hard = dict(rounding="trunc10", price=[5.1, 9.7], vari_cost=[1.3, 1.9], sal_price=[0.5, 1], deposit_rate=0.03, ini_i1=0, ini_i2=0,
+                min_inventory=0)
+    frac = product_pmf([0.5, 2, 3.25], [.25, .5, .25], [1, 2.45], [.6, .4])
+    idle = product_pmf([0, 2, 3.25], [.25, .5, .25], [0, 2.45], [.6, .4])  # no demand at all: cash spent on stock is not earned back
+    return {
+        "w0_offset": dict(hard, T=3, q_bound=(3, 2), ini_cash=5.35, max_inventory=4, min_cash=3, max_cash=9, pmf=[idle] * 3),
+        "one_cash_plane": dict(hard, T=3, q_bound=(3, 2), ini_cash=6.35, max_inventory=4, min_cash=4, max_cash=4, pmf=[idle] * 3),
+        "no_stock_kept": dict(hard, T=3, q_bound=(3, 3), ini_cash=7.35, ini_i1=1, min_inventory=2, max_inventory=0, min_cash=1,
+                              max_cash=12, pmf=[frac] * 3),
+        "blocks_257": dict(hard, T=3, q_bound=(4, 3), ini_cash=14.35, max_inventory=30, min_cash=3, max_cash=400, pmf=[frac] * 3),
+        "T5_tiny": dict(hard, T=5, q_bound=(2, 1), ini_cash=4.35, max_inventory=2, min_cash=2, max_cash=8, pmf=[frac] * 5),
+        "rounding_ties": dict(hard, T=3, q_bound=(3, 3), rounding="round", ini_cash=6.35, max_inventory=5, min_cash=1, max_cash=12,
+                              pmf=[product_pmf([0.5, 2], [.5, .5], [1.5, 3], [.6, .4])] * 3),
+        "rounding_ties_trunc10": dict(hard, T=3, q_bound=(4, 2), ini_cash=6.35, max_inventory=5, min_cash=1, max_cash=12,
+                                      pmf=[product_pmf([2.25, 1.05], [.5, .5], [0, 2], [.6, .4])] * 3),
+    }
+
+
+HARD_SEEDS = 24
+_D1 = (0, 0.5, 1, 1.5, 2, 2.25, 3, 4.05)
+_D2 = (0, 0.5, 1, 1.45, 2, 3.5)
+_PRICE = (5.1, 9.7, 4.3, 7.9, 6.7, 3.3)
+_COST = (1.3, 0.7, 1.9, 1.1, 2.3, 0.9)
+_SAL = (0.3, 0.7, 0.1, 1.1, 0.9)
+
+
+def hard_instance(seed):
+    """Beside random_instance, off its easy inputs: T 2..5 (T >= 4 keeps q_bound at 1..2 and max_cash small), q_bound 1..4 per
+    product (equal allowed), prices / costs / salvage from non-dyadic decimals, dep in {0, 0.03}, either rounding; demand LISTS
+    that are no products -- nd in {1, 2, 3, 5, 7} pairs drawn independently, unsorted, from values with fractions, in some seeds
+    one pair repeated and one with probability exactly 0; min_cash 0..5 and max_cash = min_cash + k, k in 0..40 (k = 0: one
+    cash plane); ini_cash fractional in some seeds; min_inventory 0..3, max_inventory 0..4, initial inventories 0..3 (some start
+    above max_inventory)."""
+    rng = np.random.default_rng(9100 + seed)
+    T = 2 + seed % 4
+    small = T >= 4
+    tight = seed % 3 == 2  # little cash against dear products: y* is not affordable somewhere and alpha is computed
+    Q1, Q2 = (int(rng.integers(2 if tight else 1, 3 if small else 5)) for _ in range(2))
+    pmf = []
+    for t in range(T):
+        nd = int((1, 2, 3, 5, 7)[(seed + 2 * t) % 5]) if t < 2 else int(rng.choice([1, 2, 3, 5, 7]))
+        pairs = [[float(rng.choice(_D1)), float(rng.choice(_D2))] for _ in range(nd)]
+        p = rng.random(nd) + 0.05
+        if seed % 3 == 0 and nd >= 3:
+            pairs[2] = list(pairs[0])  # a repeated pair
+        if seed % 4 == 1 and nd >= 2:
+            p[1] = 0.0  # a pair of probability exactly 0 (its successors are still visited)
+        p /= p.sum()
+        pmf.append(np.array([[a, b, float(q)] for (a, b), q in zip(pairs, p)]))
+    min_cash = 0 if tight else int(rng.integers(0, 6))
+    k = 0 if seed % 8 == 5 else int(rng.integers(0, 9 if small else 41))
+    ini_cash = min_cash + (2.35 if seed % 3 == 1 else 0.6 if seed % 6 == 2 else float(rng.integers(0, 3 if tight else 9)))
+    c1, c2 = (float(v) for v in rng.choice(_COST[2:5] if tight else _COST, size=2, replace=False))
+    return dict(T=T, q_bound=(Q1, Q2), rounding=("trunc10", "round")[(seed // 2) % 2],
+                price=[float(rng.choice(_PRICE)), float(rng.choice(_PRICE))], vari_cost=[c1, c2],
+                sal_price=[float(rng.choice(_SAL)), float(rng.choice(_SAL))], deposit_rate=float(rng.choice([0.0, 0.03])),
+                ini_cash=ini_cash, ini_i1=float(rng.integers(0, 4)), ini_i2=float(rng.integers(0, 4)),
+                min_inventory=float(rng.integers(0, 4)), max_inventory=float(rng.integers(0, 5)), min_cash=float(min_cash),
+                max_cash=float(min_cash + k), pmf=pmf)

@@ -1,6 +1,7 @@
 """sdpgpu_multiv_solve / multiitem.CashRecursionV without a GPU: the struct layouts against the header, every refusal (it
 names its field and comes before any device call), the alpha list, the host getOptTable / getOptTableDetail on a hand-made
-table, and the coverage of the twin's instance D (so that tests/test_gpu_multiv.py cannot pass vacuously)."""
+table, and the coverage of the twin's instance D, of the 24 hard seeds and of the named edges (so that
+tests/test_gpu_multiv.py cannot pass vacuously)."""
 import ctypes as C
 import os
 import subprocess
@@ -196,6 +197,82 @@ def test_instance_d_reaches_every_corner(rounding, v1, states, terminal, nR, alp
     # every alpha in the memo belongs to a y* that is not affordable, and the other way round
     for (t, R), ys in tw.cacheYStar.items():
         assert ((t, R) in tw.cacheAlpha) == (kw["vari_cost"][0] * ys[0] + kw["vari_cost"][1] * ys[1] >= R + 0.1)
+
+
+def test_the_tie_counters_see_a_half(sia):
+    tw = mt.Twin(**mt.instance_d("round"))
+    assert tw.stateTransition((1, 2.0, 3.0, 20.0), (0.5, 1.5))[1:3] == (2.0, 2.0) and tw.count["tie"] == tw.count["tie_inv"] == 2
+    tw = mt.Twin(**mt.instance_d("trunc10"))
+    assert tw.stateTransition((1, 3.0, 3.0, 20.0), (2.25, 1.0))[1:3] == (0.0, 2.0) and tw.count["tie"] == tw.count["tie_inv"] == 1
+    assert mt.java_round(7.5) == 8 and (3 - 2.25) * 10 == 7.5 and tw.count["inv_up"] == 0  # 8 / 10 = 0: this tie decides nothing
+    assert (2 - 1.05) * 10 == 9.5  # this one does: Math.round gives 10, the end inventory is 1 and its integer part 0
+    assert tw.stateTransition((1, 2.0, 3.0, 20.0), (1.05, 1.0))[1] == 1.0 and tw.count["inv_up"] == 1 and tw.count["tie"] == 2
+
+
+def test_the_hard_instances_and_edges_are_not_vacuous(sia, lib):
+    """What tests/test_gpu_multiv.py runs off the easy inputs, with the twin alone: conditions on the inputs, no measurement."""
+    seeds = {s: mt.hard_instance(s) for s in range(mt.HARD_SEEDS)}
+    edges = {n: mt.edge_instances()[n] for n in mt.HARD_EDGES}
+    assert len(seeds) == 24
+    reached = {k: 0 for k in ("w_hi", "w_lo", "e1_hi", "e2_lo", "v_near", "ystar_near", "alpha_near", "tie", "inv_up")}
+    alphas = close = strictly_larger = 0
+    twins = {}
+    for name, kw in list(seeds.items()) + list(edges.items()):
+        tw, value, action, ystar = mt.drive(kw)
+        twins[name] = tw
+        count = dict(tw.count)
+        cl = mt.Closure(kw)
+        assert tw.count == count  # the closure moved no counter of the twin
+        T = kw["T"]
+        # the closure is a superset of the reference's memo, period by period
+        assert cl.covers(tw), name
+        sizes = [len(cl.S[t]) for t in range(1, T + 1)]
+        assert all(a >= b for a, b in zip(sizes, mt.per_period(tw.cacheActions, T))) and sizes[0] == 1, name
+        assert all(a >= b for a, b in zip([len(cl.R[t]) for t in range(1, T + 1)], mt.per_period(tw.cacheYStar, T))), name
+        assert len(cl.S[T + 1]) >= sum(1 for k in tw.cacheValuesV if k[0] == T + 1), name
+        assert all((R, y1, y2) in cl.E[t] or (t, R) in tw.cacheAlpha for (t, y1, y2, R) in tw.cacheValuesPai), name
+        extra = cl.extra(tw)
+        strictly_larger += bool(extra[0] and extra[1])
+        # every descriptor is one the library accepts (without a device: it gets as far as asking for one)
+        rc, err = _solve(sia, lib, kw)
+        assert rc == (OK if _has_gpu() else ERR_DEVICE), (name, rc, err)
+        if name in edges:
+            continue
+        for k in reached:
+            reached[k] += tw.count[k] > 0
+        alphas += len(tw.cacheAlpha) > 0
+        close += any(b - a < 1e-9 for t in range(1, T + 1) for a, b in zip(sorted(cl.R[t]), sorted(cl.R[t])[1:]))
+    assert all(n >= 3 for n in reached.values()), reached
+    assert alphas >= 3 and close >= 1 and strictly_larger >= 1, (alphas, close, strictly_larger)
+    kws = list(seeds.values())
+    assert {len(p) for kw in kws for p in kw["pmf"]} == {1, 2, 3, 5, 7}
+    assert {kw["T"] for kw in kws} == {2, 3, 4, 5} and {kw["rounding"] for kw in kws} == {"trunc10", "round"}
+    assert all(kw["T"] < 4 or (max(kw["q_bound"]) <= 2 and kw["max_cash"] - kw["min_cash"] <= 12) for kw in kws)
+    assert any(kw["min_cash"] == kw["max_cash"] for kw in kws) and {kw["min_cash"] for kw in kws} >= {0, 5}
+    assert any(p[2] == 0.0 for kw in kws for t in kw["pmf"] for p in t.tolist())
+    assert all(abs(sum(p[2] for p in t.tolist()) - 1) < 1e-12 for kw in kws for t in kw["pmf"])
+    assert any(len({(p[0], p[1]) for p in t.tolist()}) < len(t) for kw in kws for t in kw["pmf"])
+    assert any(t[:, 0].tolist() != sorted(t[:, 0].tolist()) for kw in kws for t in kw["pmf"])
+    assert any(kw["ini_cash"] != int(kw["ini_cash"]) for kw in kws) and any(kw["ini_i1"] > kw["max_inventory"] for kw in kws)
+    assert any(kw["max_inventory"] == 0 for kw in kws) and any(d != int(d) for kw in kws for t in kw["pmf"] for d in t[:, :2].ravel())
+    assert all(c * 4 != int(c * 4) for kw in kws for c in kw["price"] + kw["vari_cost"] + kw["sal_price"])  # no halves, no quarters
+    # the named edges are what their names say
+    tw = twins
+    assert (edges["w0_offset"]["min_cash"], edges["w0_offset"]["max_cash"]) == (3, 9)
+    assert tw["w0_offset"].count["w_lo"] > 0 and tw["w0_offset"].count["w_hi"] > 0
+    assert edges["one_cash_plane"]["min_cash"] == edges["one_cash_plane"]["max_cash"]
+    assert (edges["no_stock_kept"]["max_inventory"], edges["no_stock_kept"]["min_inventory"]) == (0, 2)
+    assert tw["no_stock_kept"].count["e1_hi"] > 0 and tw["no_stock_kept"].count["e2_lo"] > 0
+    assert edges["T5_tiny"]["T"] == 5 and edges["T5_tiny"]["q_bound"] == (2, 1) and edges["T5_tiny"]["max_cash"] <= 12
+    assert edges["rounding_ties"]["rounding"] == "round" and edges["rounding_ties_trunc10"]["rounding"] == "trunc10"
+    assert all(tw[n].count["tie_inv"] > 0 and tw[n].count["inv_up"] > 0 for n in ("rounding_ties", "rounding_ties_trunc10"))
+
+
+def test_blocks_257_crosses_a_block_on_both_axes():
+    """The figures the issue gives for the twin alone; the engine's closure is larger still (tests/test_gpu_multiv.py)."""
+    kw = mt.edge_instances()["blocks_257"]
+    tw, value, action, ystar = mt.drive(kw)
+    assert mt.per_period(tw.cacheActions, 3) == [1, 29, 279] and mt.per_period(tw.cacheYStar, 3) == [1, 29, 257]
 
 
 def test_the_named_edge_is_what_the_issue_says():
