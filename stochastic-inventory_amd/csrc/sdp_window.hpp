@@ -206,6 +206,15 @@ __global__ __launch_bounds__(256) void window_f1_kernel(WinParams W, const doubl
 // mode rule and stop_at know nothing of RS, and no table can change.  With RS = R the kernel is the one before, instruction
 // for instruction.  A screened step costs RS S 3 + RS fp64 operations per lane (period T: RS S 2 + RS) instead of
 // R S 3 + R: sdpgpu_stats prices cut_count[5] steps so (f1_level_ops_per_cell).
+//
+// THE STEP GROUPS (SG; the host: SDPGPU_F1_STEP_GROUP / kF1StepGroup, sdpgpu_internal.hpp).  A cell's step is three fp64
+// instructions, each waiting on the one before: t = p imm, t' = acc + t, acc = t' + p V.  Written cell after cell, two of
+// every three instructions of a collapsed pass follow their own operand directly, and a wave that runs alone on its SIMD --
+// while the other builds a table, tests or waits for LDS -- issues at the rate of that chain.  With SG > 1 a step takes its
+// RW S cells (level-major: the rows of a level together) in groups of SG: the group's SG products, then its SG `acc +=`,
+// then its SG `+= p V`, fenced so that the order holds; dependent instructions are SG apart.  Per cell these are the same
+// operations on the same operands in the same order, and no sum meets another before the test or the epilogue: tables,
+// counters, tests and stop steps know nothing of SG.  With SG = 1 the kernel is the one before, instruction for instruction.
 // ---------------------------------------------------------------------------------------------
 struct LevelParams {
   int32_t band;       // levels per task (a multiple of S)
@@ -234,7 +243,7 @@ __host__ __device__ inline int level_chunks(int n_actions, int band, int n_abloc
   return (n_actions - 1 + band - 1) / band + n_ablocks;
 }
 
-template <int R, int S, bool FUTURE, bool KEYED_IN, bool CUT, int RS = R>
+template <int R, int S, bool FUTURE, bool KEYED_IN, bool CUT, int RS = R, int SG = 1>
 __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, LevelParams L, const double* __restrict__ v_next,
                                                               const unsigned long long* __restrict__ k_next,
                                                               double* __restrict__ out_val, int32_t* __restrict__ out_idx,
@@ -244,6 +253,7 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
                                                               unsigned long long* __restrict__ cut_count) {
   constexpr int DB = LevelShape<S>::DB, ROW = LevelShape<S>::ROW, NA = 64 * R;
   static_assert(RS >= 1 && R % RS == 0 && (CUT || RS == R), "screen rows divide R; only the cut-off screens");
+  static_assert(SG >= 1 && (RS * S) % SG == 0, "a step's cells, RW S of them in either pass, fall into whole groups of SG");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

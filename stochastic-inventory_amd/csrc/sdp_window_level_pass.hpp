@@ -7,6 +7,7 @@
 // same order.  (Two inclusions and not a lambda or a function called twice: wrapped in a closure the very same statements
 // take 263 instead of 209 VGPRs, one wave per SIMD -- profiles/f1_screen_rows_resources.txt.)  Only the cut-off's test knows
 // about the collapse: it reads the R thresholds of a level and holds each against the sum of the row that stands for it.
+// The kernel's SG (THE STEP GROUPS, sdp_window.hpp) orders the instructions of a step, in either pass, and nothing else.
     {
       constexpr int RW = SDP_LEVEL_PASS_ROWS, G = R / RW;
       static_assert(RW >= 1 && R % RW == 0, "screen rows divide R");
@@ -140,12 +141,32 @@
                 if (s + 1 < S) pv[s + 1] = cur[1 + s / 2].y;
               }
             }
+            if constexpr (SG == 1) {
 #pragma unroll
-            for (int s = 0; s < S; ++s) {
+              for (int s = 0; s < S; ++s) {
 #pragma unroll
-              for (int r = 0; r < RW; ++r) {
-                SDP_LEVEL_PASS_ACC[r][s] += p * imm[r][(s - t + S) % S];
-                if constexpr (FUTURE) SDP_LEVEL_PASS_ACC[r][s] += pv[s];
+                for (int r = 0; r < RW; ++r) {
+                  SDP_LEVEL_PASS_ACC[r][s] += p * imm[r][(s - t + S) % S];
+                  if constexpr (FUTURE) SDP_LEVEL_PASS_ACC[r][s] += pv[s];
+                }
+              }
+            } else {
+              // THE STEP GROUPS: cell c = s RW + r, SG cells at a time -- products, sums, future terms, each kind fenced off,
+              // so that an instruction's operand was issued SG instructions before it (per cell: the text above)
+#pragma unroll
+              for (int cb = 0; cb < RW * S; cb += SG) {
+                double prod[SG];
+#pragma unroll
+                for (int g = 0; g < SG; ++g) prod[g] = p * imm[(cb + g) % RW][((cb + g) / RW - t + S) % S];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int g = 0; g < SG; ++g) SDP_LEVEL_PASS_ACC[(cb + g) % RW][(cb + g) / RW] += prod[g];
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (FUTURE) {
+#pragma unroll
+                  for (int g = 0; g < SG; ++g) SDP_LEVEL_PASS_ACC[(cb + g) % RW][(cb + g) / RW] += pv[(cb + g) / RW];
+                  __builtin_amdgcn_sched_barrier(0);
+                }
               }
             }
             // level 0 at step j + 1 takes the slot level S - 1 has just used

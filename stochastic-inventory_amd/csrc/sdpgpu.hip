@@ -681,6 +681,14 @@ int sdpgpu_create(const sdpgpu_desc* desc, sdpgpu_handle** out) {
       }
       h->f1_screen_rows = rows[0] - '0';
     }
+    if (const char* e = std::getenv("SDPGPU_F1_STEP_GROUP")) {
+      const std::string group(e);
+      if (group != "1" && group != "2" && group != "4") {
+        delete h;
+        return fail(nullptr, SDPGPU_ERR_ARG, "SDPGPU_F1_STEP_GROUP=%s: the step groups of the F1 level kernel are 1, 2 or 4 cells", e);
+      }
+      h->f1_step_group = group[0] - '0';
+    }
     if (const char* e = std::getenv("SDPGPU_F1_SCREEN_LOG2")) {
       const int b = std::atoi(e);
       if (b >= 1 && b <= 1000) h->f1_screen_mass = std::ldexp(1.0, -b);

@@ -61,6 +61,12 @@ constexpr int kCutCounters = 6;
 // THE SCREEN ROWS of the F1 level kernel (sdp_window.hpp): the action rows RS a screened pass walks, of the block's R = 4.
 // SDPGPU_F1_SCREEN_ROWS=<1|2|4> at create time; 4 is the kernel without the collapse, instruction for instruction.
 constexpr int kF1ScreenRows = 2;
+// THE STEP GROUPS of the F1 level kernel (sdp_window.hpp): the cells SG a step of a pass takes together -- their products,
+// then their `acc +=`, then their `+= p V` -- so that no fp64 instruction waits on the one directly before it.  Per cell the
+// same operations on the same operands in the same order: no table, counter or stop step depends on SG.
+// SDPGPU_F1_STEP_GROUP=<1|2|4> at create time; 1 is the kernel without the groups, instruction for instruction.  The default
+// is the fastest SG under which the bench contract holds on the full line with 3 % to spare (profiles/f1_step_groups_ab.txt).
+constexpr int kF1StepGroup = 4;
 // Executed fp64 operations per nominal cell of a level period that counted its steps (sdpgpu_stats_get): an exact step costs
 // ops_cell per cell; a screened step walks RS of the R rows -- RS S (3 or 2) + RS operations per lane and the table's S / 64
 // products, spread over the R S nominal cells (RS = R: ops_cell itself) --; a test is one compare per cell.  `screened` of the
@@ -240,6 +246,7 @@ struct sdpgpu_handle {
   int f1_screen = -1;
   double f1_screen_mass = kF1ScreenMass;
   int f1_screen_rows = kF1ScreenRows;  // SDPGPU_F1_SCREEN_ROWS: action rows of a screened pass (1, 2 or 4 = all)
+  int f1_step_group = kF1StepGroup;    // SDPGPU_F1_STEP_GROUP: cells a step of the level kernel takes together (1, 2 or 4)
   // SDPGPU_F1_DECIDED=1: the decided split wherever the level kernel runs with the cut-off; unset or 0: never (opt-in:
   // f1_decided_on, sdpgpu_window.hip)
   int f1_decided = 0;

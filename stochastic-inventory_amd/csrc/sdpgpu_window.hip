@@ -882,24 +882,35 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
     p.lvl_future = future;
     // THE SCREEN ROWS (sdp_window.hpp): behind the same gate -- only a launch that screens takes a collapsed instantiation
     const int screen_rows = L.screen_start > 0 ? h->f1_screen_rows : pl.R;
-#define SDP_LVL_GO(RR, SS, FU, KI, CU, RS)                                                                                     \
+    // THE STEP GROUPS (sdp_window.hpp): the order of a step's instructions and nothing else -- every launch form takes them
+    const int step_group = h->f1_step_group;
+#define SDP_LVL_GO(RR, SS, FU, KI, CU, RS, SG)                                                                                 \
   do {                                                                                                                         \
     static LdsMark mark;                                                                                                       \
-    hipError_t ea = lds_allow(sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS>, pl.smem, &mark);                            \
+    hipError_t ea = lds_allow(sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS, SG>, pl.smem, &mark);                        \
     if (ea != hipSuccess) return ea;                                                                                           \
-    hipLaunchKernelGGL((sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS>), grid, dim3(256), pl.smem, st, W, L, v_next,      \
+    hipLaunchKernelGGL((sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS, SG>), grid, dim3(256), pl.smem, st, W, L, v_next,  \
                        k_next, out_val, out_idx, k_cur, pmf_p, u_row, cut_count);                                              \
+  } while (0)
+#define SDP_LVL_G(RR, SS, FU, KI, CU, RS)      \
+  do {                                         \
+    if (step_group == 4)                       \
+      SDP_LVL_GO(RR, SS, FU, KI, CU, RS, 4);   \
+    else if (step_group == 2)                  \
+      SDP_LVL_GO(RR, SS, FU, KI, CU, RS, 2);   \
+    else                                       \
+      SDP_LVL_GO(RR, SS, FU, KI, CU, RS, 1);   \
   } while (0)
 #define SDP_LVL_C(RR, SS, FU, KI)            \
   do {                                       \
     if (cut && screen_rows == 1)             \
-      SDP_LVL_GO(RR, SS, FU, KI, true, 1);   \
+      SDP_LVL_G(RR, SS, FU, KI, true, 1);    \
     else if (cut && screen_rows == 2)        \
-      SDP_LVL_GO(RR, SS, FU, KI, true, 2);   \
+      SDP_LVL_G(RR, SS, FU, KI, true, 2);    \
     else if (cut)                            \
-      SDP_LVL_GO(RR, SS, FU, KI, true, RR);  \
+      SDP_LVL_G(RR, SS, FU, KI, true, RR);   \
     else                                     \
-      SDP_LVL_GO(RR, SS, FU, KI, false, RR); \
+      SDP_LVL_G(RR, SS, FU, KI, false, RR);  \
   } while (0)
 #define SDP_LVL_R(RR, SS)               \
   if (pl.R == RR && pl.S == SS) {       \
@@ -914,6 +925,7 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
     SDP_LVL_R(4, 8)
 #undef SDP_LVL_R
 #undef SDP_LVL_C
+#undef SDP_LVL_G
 #undef SDP_LVL_GO
     if (!launched) return hipErrorInvalidValue;
     hipError_t e = hipGetLastError();
