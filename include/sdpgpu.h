@@ -959,9 +959,10 @@ int sdpgpu_batch_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_plan*
  * a table, before any device call), _synchronize, _values and _policy (n is checked against the states of THAT period:
  * sdpgpu_batch_grid), _initial (V_1(iniStaffNum) and its hire index), _stats_get (period_launches = 2 T, cells_evaluated = the
  * sum of what the n separable handles report; finalize_launches, window_r, window_s, window_chunks and lds_bytes are 0),
- * _period_ms.  Every other sdpgpu_batch_* call returns SDPGPU_ERR_UNSUPPORTED on a STAFF batch, naming the call and the
- * family, before any device call (sdpgpu_batch_simulate_ms: -1); the three table calls and sdpgpu_batch_staff_plan_period
- * return the same on a batch of the backorder family.
+ * _period_ms.  Every other sdpgpu_batch_* call but the three of "batched workforce fit and rollout" below returns
+ * SDPGPU_ERR_UNSUPPORTED on a STAFF batch, naming the call and the family, before any device call
+ * (sdpgpu_batch_simulate_ms: -1); the three table calls and sdpgpu_batch_staff_plan_period return the same on a batch of the
+ * backorder family.
  *
  * sdpgpu_batch_grid: staff number of state index 0 and the number of states of one instance in one period (1-based) -- the
  * unclamped ranges differ by period.  Host arithmetic; on a backorder batch x_lo = min_inventory of the instance.
@@ -1215,6 +1216,47 @@ int sdpgpu_sample_demands(sdpgpu_handle* h, int32_t n_paths, uint64_t seed, int3
  * SDPGPU_ERR_ARG. */
 int sdpgpu_staff_simulate(sdpgpu_handle* h, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
                           int32_t n_rules, sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid, int32_t* out_demand);
+
+/* ---- batched workforce fit and rollout: the rest of WorkforceTesting.main's loop body for the whole sweep --------------
+ * After the solve every instance of the sweep runs `getOptTable()`, `new FitsS(Integer.MAX_VALUE, T).getSinglesS(optTable)`
+ * and two `SimulatesS.simulatesS(initialState, sS)` (WorkforceTesting.java:112-165).  The three calls below do that for ALL
+ * instances of a STAFF batch (sdpgpu_batch_create above) without a handle per instance and without a policy table on the host.  Definition: DESIGN 4,
+ * "Workforce batch: fit and rollout".  Additive to ABI 6; on a batch of the backorder family each returns
+ * SDPGPU_ERR_UNSUPPORTED, naming the call and the family.
+ *
+ * sdpgpu_batch_staff_reachable: the ONE interval [*lo, *hi] of staff numbers StaffRecursion.getExpectedValue visits in `period`
+ * (1-based) from (1, iniStaffNum) -- the rows of getOptTable for that period, what sdpgpu_reachable marks on a handle of the
+ * instance.  From the levels y in [L, H + maxHire] the successors are the union of [y - len(y) + 1, y]; the clamp maps an
+ * interval to an interval.  Host arithmetic only; reads the instance's tables of the periods before `period`:
+ * SDPGPU_ERR_STATE names the first (instance, period) without one.
+ *
+ * sdpgpu_batch_staff_fit_ss: `FitsS(max_order_quantity, T).getSinglesS` on every instance's getOptTable rows, on the device --
+ * one launch over the (instance, period) slices of the policy arena the intervals above cut out, one copy back:
+ * out[(i * T + t) * 2 + {0, 1}] = (s, S) of period t + 1, bit for bit sdpgpu_fit_ss(1, T, max_order_quantity, rows of instance i).
+ * max_order_quantity is the CALLER's value, not the hire limit (the drivers pass Integer.MAX_VALUE).  SDPGPU_ERR_STATE before
+ * sdpgpu_batch_solve; SDPGPU_ERR_ARG for a limit that is not finite or is negative.
+ *
+ * sdpgpu_batch_staff_simulate: sdpgpu_staff_simulate (above) for every instance in ONE rollout launch, then the fixed-order
+ * reduction of every (instance, rule).  Tree, uniforms, turnover walk, period step, clamp, valid flag and the order of the
+ * mean's sum are those of sdpgpu_staff_simulate word for word -- the kernels share the period step.
+ *   rule     ss != NULL: n_rules (1 .. 64) level rules PER INSTANCE, ss[((i * n_rules + r) * T + t) * 2 + {0, 1}], truncated
+ *            toward zero; needs no solve.  ss == NULL (n_rules = 1): every instance's own policy table; needs a solved batch.
+ *   outputs  results[i * n_rules + r]; optional out_sum[(i * n_rules + r) * N + p], out_valid likewise,
+ *            out_demand[((i * n_rules + r) * N + p) * T + t].
+ * The uniforms' counters carry neither the rule nor the instance: all instances see common random numbers, and instance i,
+ * rule r returns bit for bit -- leaf sums, flags, draws, n_valid, mean, m2 -- what sdpgpu_staff_simulate returns on a handle of
+ * instance i with the same seed, sample_nums and ini_x.  Every result carries the kernel_ms of the whole call
+ * (sdpgpu_batch_simulate_ms stays -1 on a STAFF batch).
+ * Refusals, all before the first device call and naming the argument: a level table missing, the table rule before a solve
+ * SDPGPU_ERR_STATE; sample_nums[t] < 1 or more than 2^24 leaves per rule, n x n_rules x N above 2^28 (2 GiB of leaf sums),
+ * n_rules outside 1 .. 64, n_rules != 1 with ss == NULL, an ss entry not finite or outside int32, (int) S < (int) s - 1, ini_x
+ * not an integer in 0 .. 1e9, ini_x outside period 1's box under the table rule, a negative or NaN probability in a pool table
+ * in use (named by its id; every table is looked at once) SDPGPU_ERR_ARG. */
+int sdpgpu_batch_staff_reachable(sdpgpu_batch* b, int32_t instance, int32_t period, int64_t* lo, int64_t* hi);
+int sdpgpu_batch_staff_fit_ss(sdpgpu_batch* b, double max_order_quantity, double* out);
+int sdpgpu_batch_staff_simulate(sdpgpu_batch* b, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
+                                int32_t n_rules, sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid,
+                                int32_t* out_demand);
 
 /* ---- CASH family: (s, C, S) ordering rules rolled out along sampled demand paths -------------------------------------
  * What CashSimulation.simulatesCS with (s, C1(x), C2(x), S) (CashSimulation.java:996-1042), simulatesCS with (s, C1(x), S)

@@ -411,6 +411,10 @@ EXPORTS = {
     "sdpgpu_batch_set_overhead": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double]),
     "sdpgpu_batch_grid": (C.c_int, [_P, C.c_int32, C.c_int32, _DP, _LP]),
     "sdpgpu_batch_staff_plan_period": (C.c_int, [_P, C.c_int32, C.POINTER(SdpgpuBatchStaffPlan)]),
+    "sdpgpu_batch_staff_reachable": (C.c_int, [_P, C.c_int32, C.c_int32, _LP, _LP]),
+    "sdpgpu_batch_staff_fit_ss": (C.c_int, [_P, C.c_double, _DP]),
+    "sdpgpu_batch_staff_simulate": (C.c_int, [_P, _IP, C.c_uint64, C.c_double, _DP, C.c_int32, C.POINTER(SdpgpuSimResult), _DP,
+                                              C.POINTER(C.c_uint8), _IP]),
     "sdpgpu_batch_simulate": (C.c_int, [_P, C.c_int32, _DP, C.c_int64, _DP, _DP, _DP]),
     "sdpgpu_batch_set_sampler": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(SdpgpuDistSpec)]),
     "sdpgpu_batch_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, _DP, _DP, _DP]),

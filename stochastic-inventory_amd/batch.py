@@ -401,6 +401,61 @@ class StaffBatch:
         self._check(self._lib.sdpgpu_batch_policy(self._b, i, period, _ip(out), len(out)))
         return out
 
+    # ---- fit and rollout of every instance (sdpgpu_batch_staff_reachable / _fit_ss / _simulate; WorkforceTesting.java:112-165) ----
+    def reachable(self, i: int, period: int):
+        """(L, H): the staff numbers of `period` (1-based) StaffRecursion.getExpectedValue visits from (1, iniStaffNum) of
+        instance i -- one interval, the rows of getOptTable.  Host arithmetic, no device."""
+        lo, hi = C.c_int64(), C.c_int64()
+        self._check(self._lib.sdpgpu_batch_staff_reachable(self._b, i, period, C.byref(lo), C.byref(hi)))
+        return int(lo.value), int(hi.value)
+
+    def fit_ss(self, max_order_quantity: float) -> np.ndarray:
+        """FitsS(max_order_quantity, T).getSinglesS of every instance, fitted ON the device from the solved policy tables:
+        [n, T, 2] = (s, S) per period.  The limit is the caller's (the drivers pass Integer.MAX_VALUE), not the hire limit."""
+        out = np.empty((self.n, self.T, 2), dtype=np.float64)
+        self._check(self._lib.sdpgpu_batch_staff_fit_ss(self._b, float(max_order_quantity), _dp(out)))
+        return out
+
+    def staff_simulate(self, sample_nums, seed: int, ini_x: int, ss=None, want_sums: bool = False, want_demands: bool = False):
+        """SdpEngine.staff_simulate for every instance in one rollout launch (sdpgpu_batch_staff_simulate; DESIGN 4, "Workforce
+        batch: fit and rollout").  ss = None: every instance's own policy table (one rule), else (s, S) levels of shape
+        (n, T, 2) or (n, R, T, 2).  Returns the SdpgpuSimResults as a nested list [n][R]; with want_sums also
+        (sums[n, R, N], valid[n, R, N]); with want_demands also the turnovers drawn, demands[n, R, N, T] (int32)."""
+        k = np.ascontiguousarray(sample_nums, dtype=np.int32)
+        if k.shape != (self.T,):
+            raise ValueError("sample_nums must have one entry per period")
+        levels, n_rules = None, 1
+        if ss is not None:
+            levels = np.asarray(ss, dtype=np.float64)
+            if levels.ndim == 3:
+                levels = levels[:, None]
+            if levels.ndim != 4 or levels.shape[0] != self.n or levels.shape[2:] != (self.T, 2):
+                raise ValueError(f"ss must have shape ({self.n}, {self.T}, 2) or ({self.n}, rules, {self.T}, 2)")
+            levels = np.ascontiguousarray(levels)
+            n_rules = levels.shape[1]
+        n = 1
+        for v in k.tolist():  # (the library refuses a bad tree; the buffers below only need a size)
+            n *= max(int(v), 1)
+        n = min(n, 1 << 24)
+        rows = min(max(n_rules, 1), 64)
+        if self.n * rows * n > 1 << 28:  # (refused by the library: no buffers for it)
+            n = 1
+        res = (_abi.SdpgpuSimResult * (self.n * max(n_rules, 1)))()
+        sums = np.empty((self.n, rows, n), dtype=np.float64) if want_sums else None
+        valid = np.empty((self.n, rows, n), dtype=np.uint8) if want_sums else None
+        dem = np.empty((self.n, rows, n, self.T), dtype=np.int32) if want_demands else None
+        self._check(self._lib.sdpgpu_batch_staff_simulate(
+            self._b, _ip(k), C.c_uint64(int(seed) & (2**64 - 1)), float(ini_x), None if levels is None else _dp(levels), n_rules, res,
+            None if sums is None else _dp(sums), None if valid is None else valid.ctypes.data_as(C.POINTER(C.c_uint8)),
+            None if dem is None else _ip(dem)))
+        flat = list(res)
+        out = [[flat[i * n_rules:(i + 1) * n_rules] for i in range(self.n)]]
+        if want_sums:
+            out += [sums, valid.astype(bool)]
+        if want_demands:
+            out.append(dem)
+        return out[0] if len(out) == 1 else tuple(out)
+
     def initial(self):
         """(values[n], hires[n]): V_1(iniStaffNum) and its hire count, all instances, one copy."""
         val = np.empty(self.n, dtype=np.float64)

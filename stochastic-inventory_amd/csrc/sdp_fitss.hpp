@@ -20,6 +20,7 @@
 // Global memory is written with ordinary vector stores from plain C++ only.
 #pragma once
 #include "sdp_batch_sim.hpp"
+#include "sdp_fit_pair.hpp"
 
 namespace sdp {
 
@@ -168,14 +169,6 @@ __host__ __device__ __forceinline__ void fit_first_period(double x0, double q0, 
 }
 
 // ---- device: the fit of every (instance, period) of a solved batch ----
-
-// the reachable slice of one (instance, period): rows lo .. lo + n - 1 of its policy row
-struct FitPair {
-  int64_t pol_off;  // of the (instance, period)'s policy row in the batch's arena
-  double x_min;     // inventory of the row's state 0
-  double maxq;      // the instance's order limit
-  int32_t lo, n;    // the reachable states lo .. lo + n - 1
-};
 
 struct FitSliceRows {
   const int32_t* __restrict__ pol;  // the policy row

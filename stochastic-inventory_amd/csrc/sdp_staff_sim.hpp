@@ -15,7 +15,8 @@
 //     transposed table, four reads a trip, that stops at the first threshold above u (the sums of non-negative terms never
 //     decrease; the host refuses a table with a negative entry).  Its mean length is hireTo x rate;
 //   * the period's cost and the next staff number are the statements of staff_period_kernel (sdp_staff.hpp), one fp64
-//     operation each;
+//     operation each.  A leaf's whole period -- rule, hireTo, uniform, turnover, cost, clamp -- is ONE device function,
+//     staff_sim_step, which the batch's kernel (sdp_staff_batch_sim.hpp) calls as well: there is no second copy of it;
 //   * a RULE is a small struct that picks the period's hires (the idiom of batch_sim_kernel<RULE, SAMPLED>).  A wave's 64 leaves
 //     belong to ONE rule (the leaves of a rule are padded to whole waves): the rule's levels and the period records are
 //     wave-uniform loads;
@@ -40,8 +41,13 @@ struct StaffSimPeriod {
   int32_t pad;
 };
 
+// fixCost, unitVariCost, salary, unitPenalty of one instance
+struct StaffSimCosts {
+  double K, v, salary, pen;
+};
+
 struct StaffSimLaunch {
-  double K, v, salary, pen;  // fixCost, unitVariCost, salary, unitPenalty
+  StaffSimCosts c;           // the handle's costs (a batch reads every instance's own: sdp_staff_batch_sim.hpp)
   int32_t T, n_rules;
   int32_t clamp, min_x, max_x;
   int32_t ini_x;
@@ -93,6 +99,42 @@ __device__ __forceinline__ int staff_sim_turnover(const StaffSimPeriod& P, int y
   return k;
 }
 
+// One period of a leaf, the ONE statement of it for the handle's kernel and the batch's (sdp_staff_batch_sim.hpp): rule -> hireTo
+// -> the uniform of (t, parent, child) -> turnover -> the cost statements of staff_period_kernel, one fp64 operation each -> the
+// clamp.  C: the costs of the instance the leaf belongs to; L: the tree's seed, the clamp; P: the period's table, box, minStaffNum
+// and tree level.  false: the rule ended the leaf (nothing is changed).
+template <class RULE>
+__device__ __forceinline__ bool staff_sim_step(const StaffSimCosts& C, const StaffSimLaunch& L, const StaffSimPeriod& P, const RULE& rule,
+                                               int ri, int t, uint32_t p, int* x_io, double* sum_io, int* demand_out) {
+  const int x = *x_io;
+  int a;
+  if (!rule.hires(L, P, ri, t, x, &a)) return false;
+  const int hireTo = x + a;
+  int demand = 0;
+  if (hireTo > 0) {  // (SimulatesS.java:64-67: nobody to leave)
+    const uint32_t node = p / P.stride;
+    const uint32_t parent = node / P.K, child = node - parent * P.K;
+    const double u = sim_uniform_lhs(P.K, P.half_bits, L.seed_lo, L.seed_hi, (int)parent, t, child);
+    demand = staff_sim_turnover(P, hireTo, u);
+  }
+  const double fixHire = a > 0 ? C.K : 0.0;
+  const double variHire = C.v * (double)a;
+  const double fv = fixHire + variHire;
+  const int n = hireTo - demand;  // nextStaffNum
+  const double salaryCost = C.salary * (double)n;
+  const double penalty = n > P.min_staff ? 0.0 : C.pen * (double)(P.min_staff - n);
+  const double imm = fv + salaryCost + penalty;
+  *sum_io = t == 0 ? imm : *sum_io + imm;
+  int nn = n;
+  if (L.clamp) {
+    nn = nn > L.max_x ? L.max_x : nn;
+    nn = nn < L.min_x ? L.min_x : nn;
+  }
+  *x_io = nn;
+  *demand_out = demand;
+  return true;
+}
+
 // counts[2 * rule]: valid leaves of the rule (integer atomics, one per wave)
 template <class RULE>
 __global__ __launch_bounds__(256) void staff_sim_kernel(StaffSimLaunch L, const StaffSimPeriod* __restrict__ per, RULE rule,
@@ -113,33 +155,11 @@ __global__ __launch_bounds__(256) void staff_sim_kernel(StaffSimLaunch L, const 
     int t = 0;
     for (; t < L.T; ++t) {
       const StaffSimPeriod P = per[t];
-      int a;
-      if (!rule.hires(L, P, ri, t, x, &a)) {
+      int demand;
+      if (!staff_sim_step(L.c, L, P, rule, ri, t, p, &x, &sum, &demand)) {
         valid = false;
         break;
       }
-      const int hireTo = x + a;
-      int demand = 0;
-      if (hireTo > 0) {  // (SimulatesS.java:64-67: nobody to leave)
-        const uint32_t node = p / P.stride;
-        const uint32_t parent = node / P.K, child = node - parent * P.K;
-        const double u = sim_uniform_lhs(P.K, P.half_bits, L.seed_lo, L.seed_hi, (int)parent, t, child);
-        demand = staff_sim_turnover(P, hireTo, u);
-      }
-      const double fixHire = a > 0 ? L.K : 0.0;
-      const double variHire = L.v * (double)a;
-      const double fv = fixHire + variHire;
-      const int n = hireTo - demand;  // nextStaffNum
-      const double salaryCost = L.salary * (double)n;
-      const double penalty = n > P.min_staff ? 0.0 : L.pen * (double)(P.min_staff - n);
-      const double imm = fv + salaryCost + penalty;
-      sum = t == 0 ? imm : sum + imm;
-      int nn = n;
-      if (L.clamp) {
-        nn = nn > L.max_x ? L.max_x : nn;
-        nn = nn < L.min_x ? L.min_x : nn;
-      }
-      x = nn;
       if (out_demand) out_demand[leaf * L.T + t] = demand;
     }
     if (out_demand)

@@ -930,6 +930,30 @@ int sdpgpu_batch_staff_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch
   return guarded(b, "sdpgpu_batch_staff_plan_period", [&]() -> int { return staff_batch_plan(b->staff, &b->err, period, out); });
 }
 
+int sdpgpu_batch_staff_reachable(sdpgpu_batch* b, int32_t instance, int32_t period, int64_t* lo, int64_t* hi) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  STAFF_ONLY(b, "sdpgpu_batch_staff_reachable");
+  return guarded(b, "sdpgpu_batch_staff_reachable", [&]() -> int { return staff_batch_reachable(b->staff, &b->err, instance, period, lo, hi); });
+}
+
+int sdpgpu_batch_staff_fit_ss(sdpgpu_batch* b, double max_order_quantity, double* out) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  STAFF_ONLY(b, "sdpgpu_batch_staff_fit_ss");
+  return guarded(b, "sdpgpu_batch_staff_fit_ss", [&]() -> int { return staff_batch_fit_ss(b->staff, &b->err, max_order_quantity, out); });
+}
+
+int sdpgpu_batch_staff_simulate(sdpgpu_batch* b, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss, int32_t n_rules,
+                                sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid, int32_t* out_demand) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->err.clear();
+  STAFF_ONLY(b, "sdpgpu_batch_staff_simulate");
+  return guarded(b, "sdpgpu_batch_staff_simulate", [&]() -> int {
+    return staff_batch_simulate(b->staff, &b->err, sample_nums, seed, ini_x, ss, n_rules, results, out_sum, out_valid, out_demand);
+  });
+}
+
 }  // extern "C"
 
 // =================================================================================================
@@ -1196,6 +1220,12 @@ int fit_launch(sdpgpu_batch* b, const char* who, int32_t levels) {
 
 }  // namespace
 
+hipError_t sdpgpu_detail::launch_fit_singles(hipStream_t st, const sdp::FitPair* d_pairs, int n_pairs, int T, const int32_t* d_policy, double* d_out) {
+  hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<1>), dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, d_pairs, n_pairs, T, 1.0, d_policy,
+                     d_out);
+  return hipGetLastError();
+}
+
 extern "C" {
 
 int sdpgpu_batch_reachable(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* lo, int32_t* hi) {
@@ -1384,8 +1414,8 @@ int sim_entry(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, c
   if (!b) return SDPGPU_ERR_ARG;
   b->err.clear();
   if (b->staff)
-    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: not available on a batch of the staff family (SDPGPU_FAMILY_STAFF): a hiring rule is rolled out per "
-                 "handle (sdpgpu_staff_simulate)", who);
+    return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: not available on a batch of the staff family (SDPGPU_FAMILY_STAFF): a hiring rule is rolled out on a "
+                 "sampled tree (sdpgpu_batch_staff_simulate)", who);
   return guarded(b, who, [&]() -> int { return sim_run(b, who, rule, n_paths, demand, stride, sampled, seed, ini_x, out_mean, out_sum); });
 }
 

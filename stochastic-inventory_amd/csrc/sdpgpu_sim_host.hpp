@@ -1,7 +1,8 @@
 // sdpgpu_sim_host.hpp -- what the host code of the simulation translation units shares.  By every rollout owner (sdpgpu_batch.hip:
 // an sdpgpu_batch; the handle rollouts sdpgpu_simsample.hip, sdpgpu_cashrulesim.hip, sdpgpu_xrsim.hip, sdpgpu_staffsim.hip,
-// sdpgpu_customsim.hip: an sdpgpu_handle; sdpgpu_multisim.hip: an sdpgpu_multi_policy): the exception barrier, the device scope,
-// the path-count refusals, the stream record, the threshold table of a pmf tile and the grow-only scratch block.  By the handle
+// sdpgpu_customsim.hip: an sdpgpu_handle; sdpgpu_multisim.hip: an sdpgpu_multi_policy; sdpgpu_staffbatch.hip: a StaffBatch, whose
+// pairs (instance, rule) are the frame's rules): the exception barrier, the device scope, the path-count refusals, the stream
+// record, the threshold table of a pmf tile and the grow-only scratch block.  By the handle, staff-batch
 // and policy rollouts: RolloutFrame, the ONE host frame of a rollout call -- the carving of the scratch block with typed access
 // and uploads, the two timing events, the zeroed counters, the fixed-order reduction of every rule, the downloads and the
 // sdpgpu_sim_result records -- so that an entry point supplies its validation, its period records and its launch.  By the handle
@@ -15,6 +16,9 @@
 #include <initializer_list>
 
 struct sdpgpu_batch;
+namespace sdp {
+struct FitPair;  // sdp_fit_pair.hpp
+}
 
 namespace sdpgpu_detail {
 
@@ -252,6 +256,15 @@ int staff_batch_policy(StaffBatch* s, std::string* err, int32_t instance, int32_
 int staff_batch_initial(StaffBatch* s, std::string* err, double* out_value, int32_t* out_action_index);
 int staff_batch_stats(StaffBatch* s, std::string* err, sdpgpu_batch_stats* out);
 double staff_batch_period_ms(StaffBatch* s, std::string* err, int32_t period);
+// steps 2-5 of WorkforceTesting.main's loop body for the whole batch ("Workforce batch: fit and rollout")
+int staff_batch_reachable(StaffBatch* s, std::string* err, int32_t instance, int32_t period, int64_t* lo, int64_t* hi);
+int staff_batch_fit_ss(StaffBatch* s, std::string* err, double max_order_quantity, double* out);
+int staff_batch_simulate(StaffBatch* s, std::string* err, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
+                         int32_t n_rules, sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid, int32_t* out_demand);
+
+// sdpgpu_batch.hip: one launch of batch_fit_ss_kernel<1> (sdp_fitss.hpp) at step 1 over the slices pairs[i * T + t] of a policy
+// arena, out[(i * T + t) * 2 + {0, 1}] -- for the staff batch, whose unit fills the slices and owns the buffers
+hipError_t launch_fit_singles(hipStream_t st, const sdp::FitPair* d_pairs, int n_pairs, int T, const int32_t* d_policy, double* d_out);
 
 // ---- the host frame of a rollout --------------------------------------------------------------------------
 // offsets of the scratch block, every part aligned to 16 bytes

@@ -3,10 +3,16 @@
 // two turnover tables.  Period t of ALL instances runs in two launches (sdp_staff_batch.hpp): the rows G and P of every
 // instance, then the scan.  This unit holds the pool of level tables, the validation, the host layout (per-period boxes,
 // groups of instances per (period, table), instance blocks), the plan, the launcher and what the entry points of
-// sdpgpu_batch.hip forward to on a batch whose instance 0 is of the STAFF family.  Errors go to the sink the caller names (the
-// batch's last error, or the create error).
+// sdpgpu_batch.hip forward to on a batch whose instance 0 is of the STAFF family -- and, at the end, the rest of the sweep's loop
+// body for all instances: the visited staff numbers, the (s, S) fit on the device and the rollout of hiring rules on a sampled
+// tree (sdp_staff_batch_sim.hpp) on the shared host frame.  Errors go to the sink the caller names (the batch's last error, or
+// the create error).
 #include "sdpgpu_sim_host.hpp"
+#include "sdp_fit_pair.hpp"
 #include "sdp_staff_batch.hpp"
+#include "sdp_staff_batch_sim.hpp"
+
+#include <map>
 
 namespace sdpgpu_detail {
 
@@ -45,6 +51,7 @@ struct Table {
   std::vector<double> p;  // transposed: p[j * rows + y], zero behind a row's length
   std::vector<int32_t> len;
   int32_t rows = 0, maxj = 0;
+  bool nonneg = false;    // staff_batch_simulate has looked at the table and found no negative or NaN entry
 };
 
 }  // namespace
@@ -80,6 +87,14 @@ struct StaffBatch {
   std::vector<hipEvent_t> ev_period;       // [T + 1] when profiling
   bool timed = false, periods_timed = false;
   int32_t period_launches = 0, periods_run = 0;
+  // ---- fit and rollout (staff_batch_fit_ss, staff_batch_simulate) ----
+  std::vector<int64_t> reach_lo, reach_hi;  // [i * T + t]: the reachable intervals, made once the tables are frozen
+  sdp::FitPair* d_fit_pairs = nullptr;      // [i * T + t]
+  double* d_fit = nullptr;                  // N x T x 2
+  std::string* sim_err = nullptr;           // the sink of the call in progress, for the shared host frame (sim_fail below)
+  char* d_sim_scratch = nullptr;            // sim_scratch of sdpgpu_sim_host.hpp
+  size_t sim_scratch_bytes = 0;
+  hipEvent_t sim_ev0 = nullptr, sim_ev1 = nullptr;
 };
 
 namespace {
@@ -391,7 +406,7 @@ void staff_batch_delete(StaffBatch* s) {
   if (!s) return;
   {
     DeviceScope dev;
-    if (s->allocated || s->d_tabs || !s->owned.empty()) {
+    if (s->allocated || s->d_tabs || !s->owned.empty() || s->d_sim_scratch) {
       (void)dev.enter(s->device);
       if (s->stream) (void)hipStreamSynchronize(s->stream);
     }
@@ -407,6 +422,11 @@ void staff_batch_delete(StaffBatch* s) {
     if (s->d_policy) (void)hipFree(s->d_policy);
     if (s->d_gp) (void)hipFree(s->d_gp);
     if (s->d_ini_out) (void)hipFree(s->d_ini_out);
+    if (s->d_fit_pairs) (void)hipFree(s->d_fit_pairs);
+    if (s->d_fit) (void)hipFree(s->d_fit);
+    if (s->d_sim_scratch) (void)hipFree(s->d_sim_scratch);
+    if (s->sim_ev0) (void)hipEventDestroy(s->sim_ev0);
+    if (s->sim_ev1) (void)hipEventDestroy(s->sim_ev1);
     if (s->stream && s->own_stream) (void)hipStreamDestroy(s->stream);
   }
   delete s;
@@ -635,6 +655,261 @@ double staff_batch_period_ms(StaffBatch* s, std::string* err, int32_t period) {
   float ms = 0;
   if (hipEventElapsedTime(&ms, s->ev_period[(size_t)period], s->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
   return ms;
+}
+
+// =================================================================================================
+// Fit and rollout: getOptTable's intervals, FitsS.getSinglesS and SimulatesS.simulatesS for every instance ("Workforce
+// batch: fit and rollout").  The rollout's host frame is RolloutFrame with the batch as its owner.
+// =================================================================================================
+
+// the error sink and the timing events of the shared host helpers (sim_scratch, RolloutFrame) for this owner
+template <class... A>
+int sim_fail(StaffBatch* s, int code, const char* fmt, A... a) {
+  return sfail(s->sim_err, code, fmt, a...);
+}
+inline hipError_t sim_events(StaffBatch* s, hipEvent_t* ev0, hipEvent_t* ev1) {
+  hipError_t e = hipSuccess;
+  if (!s->sim_ev0 && (e = hipEventCreate(&s->sim_ev0)) != hipSuccess) return e;
+  if (!s->sim_ev1 && (e = hipEventCreate(&s->sim_ev1)) != hipSuccess) return e;
+  *ev0 = s->sim_ev0;
+  *ev1 = s->sim_ev1;
+  return hipSuccess;
+}
+
+namespace {
+
+constexpr int32_t kStaffBatchSimMaxRules = 64;
+constexpr int64_t kStaffBatchSimMaxSums = (int64_t)1 << 28;  // leaf sums of a call: 2 GiB
+
+// staff_reach_intervals (sdpgpu_staff.hip) for instance i over the pool's tables, periods 1 .. upto; reads the tables of the
+// periods before `upto`.  -1 in *missing_t: all were there.
+void reach_of(const StaffBatch* s, int i, int upto, std::vector<int64_t>* lo_out, std::vector<int64_t>* hi_out, int* missing_t) {
+  const sdpgpu_desc& d = s->d[0];
+  *missing_t = -1;
+  int64_t L = (int64_t)d.ini_inventory, H = L;
+  lo_out->assign((size_t)upto, 0);
+  hi_out->assign((size_t)upto, -1);
+  for (int t = 0; t < upto; ++t) {
+    (*lo_out)[(size_t)t] = L;
+    (*hi_out)[(size_t)t] = H;
+    if (t + 1 == upto) break;
+    const int32_t id = s->use[(size_t)i * s->T + t];
+    if (id < 0) {
+      *missing_t = t;
+      return;
+    }
+    const Table& tb = s->pool[(size_t)id];
+    const int64_t rows = tb.rows;
+    int64_t low = INT64_MAX;
+    const int64_t top = H + (s->A - 1);
+    for (int64_t y = L; y <= std::min(top, rows - 1); ++y) low = std::min(low, y - tb.len[(size_t)y] + 1);
+    if (top > rows - 1) low = std::min(low, std::max(L, rows) - tb.len[(size_t)rows - 1] + 1);
+    L = low;
+    H = top;
+    if (d.clamp_inventory) {
+      auto cl = [&](int64_t v) {
+        v = v > (int64_t)d.max_inventory ? (int64_t)d.max_inventory : v;
+        return v < (int64_t)d.min_inventory ? (int64_t)d.min_inventory : v;
+      };
+      L = cl(L);
+      H = cl(H);
+    }
+  }
+}
+
+// the intervals of every (instance, period), once (the tables are frozen: the device tables exist); instances that walk the same
+// tables share one computation
+void reach_all(StaffBatch* s) {
+  if (!s->reach_lo.empty()) return;
+  const int N = s->N, T = s->T;
+  s->reach_lo.assign((size_t)N * T, 0);
+  s->reach_hi.assign((size_t)N * T, -1);
+  std::map<std::vector<int32_t>, int> seen;
+  std::vector<int64_t> lo, hi;
+  for (int i = 0; i < N; ++i) {
+    const std::vector<int32_t> key(s->use.begin() + (size_t)i * T, s->use.begin() + (size_t)(i + 1) * T);
+    const auto at = seen.find(key);
+    if (at != seen.end()) {
+      std::copy_n(s->reach_lo.begin() + (size_t)at->second * T, T, s->reach_lo.begin() + (size_t)i * T);
+      std::copy_n(s->reach_hi.begin() + (size_t)at->second * T, T, s->reach_hi.begin() + (size_t)i * T);
+      continue;
+    }
+    int missing = -1;
+    reach_of(s, i, T, &lo, &hi, &missing);  // (laid out: no table is missing)
+    std::copy_n(lo.begin(), T, s->reach_lo.begin() + (size_t)i * T);
+    std::copy_n(hi.begin(), T, s->reach_hi.begin() + (size_t)i * T);
+    seen.emplace(key, i);
+  }
+}
+
+// the walk down a row stops at the first threshold above u: right only when the running sums never decrease.  Every table an
+// (instance, period) uses is looked at once.
+int check_tables(StaffBatch* s, std::string* err, const char* who) {
+  for (size_t k = 0; k < s->use.size(); ++k) {
+    Table& tb = s->pool[(size_t)s->use[k]];
+    if (tb.nonneg) continue;
+    for (size_t e = 0; e < tb.p.size(); ++e)
+      if (!(tb.p[e] >= 0.0))
+        return sfail(err, SDPGPU_ERR_ARG, "%s: table %d of the pool holds a negative or NaN probability (level %zu, turnover %zu)", who, (int)s->use[k],
+                     e % (size_t)tb.rows, e / (size_t)tb.rows);
+    tb.nonneg = true;
+  }
+  return SDPGPU_OK;
+}
+
+}  // namespace
+
+int staff_batch_reachable(StaffBatch* s, std::string* err, int32_t instance, int32_t period, int64_t* lo, int64_t* hi) {
+  const char* who = "sdpgpu_batch_staff_reachable";
+  if (instance < 0 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, s->N - 1);
+  if (period < 1 || period > s->T) return sfail(err, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, s->T);
+  if (!lo || !hi) return sfail(err, SDPGPU_ERR_ARG, "%s: null output (lo, hi)", who);
+  std::vector<int64_t> l, h;
+  int missing = -1;
+  reach_of(s, instance, period, &l, &h, &missing);
+  if (missing >= 0)
+    return sfail(err, SDPGPU_ERR_STATE, "%s: level table of instance %d, period %d not set (the staff numbers of period %d follow from the tables "
+                 "before it)", who, instance, missing + 1, period);
+  *lo = l[(size_t)period - 1];
+  *hi = h[(size_t)period - 1];
+  return SDPGPU_OK;
+}
+
+int staff_batch_fit_ss(StaffBatch* s, std::string* err, double max_order_quantity, double* out) {
+  const char* who = "sdpgpu_batch_staff_fit_ss";
+  if (!out) return sfail(err, SDPGPU_ERR_ARG, "%s: out is null", who);
+  if (!std::isfinite(max_order_quantity) || max_order_quantity < 0)
+    return sfail(err, SDPGPU_ERR_ARG, "%s: max_order_quantity = %g (a finite limit >= 0; the drivers pass Integer.MAX_VALUE)", who, max_order_quantity);
+  if (!s->solved) return sfail(err, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+  const int N = s->N, T = s->T;
+  reach_all(s);
+  std::vector<sdp::FitPair> pairs((size_t)N * T);
+  for (int i = 0; i < N; ++i)
+    for (int t = 0; t < T; ++t) {
+      const int64_t L = s->reach_lo[(size_t)i * T + t], H = s->reach_hi[(size_t)i * T + t], x0 = s->x_lo[(size_t)t];
+      if (L < x0 || H < L || H - x0 >= s->nx[(size_t)t])  // (the visited numbers lie inside the period's box by construction)
+        return sfail(err, SDPGPU_ERR_INTERNAL, "%s: instance %d, period %d: staff numbers %lld .. %lld outside the box %lld .. %lld", who, i, t + 1,
+                     (long long)L, (long long)H, (long long)x0, (long long)(x0 + s->nx[(size_t)t] - 1));
+      pairs[(size_t)i * T + t] = sdp::FitPair{(int64_t)policy_row(s, i, t), (double)x0, max_order_quantity, (int32_t)(L - x0), (int32_t)(H - L + 1)};
+    }
+  DeviceScope dev;
+  SHIP_TRY(err, dev.enter(s->device));
+  if (!s->d_fit_pairs) SHIP_TRY(err, hipMalloc((void**)&s->d_fit_pairs, pairs.size() * sizeof(sdp::FitPair)));
+  if (!s->d_fit) SHIP_TRY(err, hipMalloc((void**)&s->d_fit, pairs.size() * 2 * sizeof(double)));
+  SHIP_TRY(err, hipMemcpyAsync(s->d_fit_pairs, pairs.data(), pairs.size() * sizeof(sdp::FitPair), hipMemcpyHostToDevice, s->stream));
+  SHIP_TRY(err, launch_fit_singles(s->stream, s->d_fit_pairs, N * T, T, s->d_policy, s->d_fit));
+  SHIP_TRY(err, hipMemcpyAsync(out, s->d_fit, pairs.size() * 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  SHIP_TRY(err, hipStreamSynchronize(s->stream));
+  return SDPGPU_OK;
+}
+
+int staff_batch_simulate(StaffBatch* s, std::string* err, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
+                         int32_t n_rules, sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid, int32_t* out_demand) {
+  const char* who = "sdpgpu_batch_staff_simulate";
+  const int N = s->N, T = s->T;
+  if (!sample_nums) return sfail(err, SDPGPU_ERR_ARG, "%s: sample_nums is null", who);
+  if (!results) return sfail(err, SDPGPU_ERR_ARG, "%s: results is null", who);
+  if (n_rules < 1 || n_rules > kStaffBatchSimMaxRules) return sfail(err, SDPGPU_ERR_ARG, "%s: n_rules = %d (1 .. %d)", who, n_rules, kStaffBatchSimMaxRules);
+  if (!ss && n_rules != 1) return sfail(err, SDPGPU_ERR_ARG, "%s: n_rules = %d with ss == NULL (the table policy is one rule)", who, n_rules);
+  int64_t leaves = 1;
+  for (int t = 0; t < T; ++t) {
+    if (sample_nums[t] < 1) return sfail(err, SDPGPU_ERR_ARG, "%s: sample_nums[%d] = %d (at least 1)", who, t, sample_nums[t]);
+    leaves *= sample_nums[t];
+    if (leaves > kSimMaxPaths) return sfail(err, SDPGPU_ERR_ARG, "%s: sample_nums gives more than %d leaves (product up to index %d)", who, kSimMaxPaths, t);
+  }
+  const int64_t n_pairs = (int64_t)N * n_rules;
+  if (n_pairs * leaves > kStaffBatchSimMaxSums)
+    return sfail(err, SDPGPU_ERR_ARG, "%s: %d instances x n_rules %d x %lld leaves (sample_nums) exceed %lld leaf sums (2 GiB)", who, N, n_rules,
+                 (long long)leaves, (long long)kStaffBatchSimMaxSums);
+  for (int i = 0; i < N; ++i)
+    for (int t = 0; t < T; ++t)
+      if (s->use[(size_t)i * T + t] < 0)
+        return sfail(err, SDPGPU_ERR_STATE, "%s: level table of instance %d, period %d not set (sdpgpu_batch_use_level_pmf)", who, i, t + 1);
+  if (!(ini_x >= 0 && ini_x <= 1e9) || ini_x != std::floor(ini_x))
+    return sfail(err, SDPGPU_ERR_ARG, "%s: ini_x = %g (a staff number: an integer in 0 .. 1e9)", who, ini_x);
+  std::vector<int32_t> levels;
+  if (ss) {
+    levels.resize((size_t)n_pairs * T * 2);
+    for (int i = 0; i < N; ++i)
+      for (int r = 0; r < n_rules; ++r)
+        for (int t = 0; t < T; ++t) {
+          const size_t k = (((size_t)i * n_rules + r) * T + t) * 2;
+          const double lo = ss[k], up = ss[k + 1];
+          // (int) of a double: toward zero; what it cannot represent is refused
+          if (!std::isfinite(lo) || !std::isfinite(up) || !(lo > -2147483649.0 && lo < 2147483648.0) || !(up > -2147483649.0 && up < 2147483648.0))
+            return sfail(err, SDPGPU_ERR_ARG, "%s: ss[%d][%d][%d] = (%g, %g) is not finite or outside int32", who, i, r, t, lo, up);
+          const int32_t si = (int32_t)lo, Si = (int32_t)up;
+          if ((int64_t)Si < (int64_t)si - 1)
+            return sfail(err, SDPGPU_ERR_ARG, "%s: ss[%d][%d][%d] = (%g, %g): S < s - 1 would hire a negative number at x = s - 1", who, i, r, t, lo, up);
+          levels[k] = si;
+          levels[k + 1] = Si;
+        }
+  }
+  int rc = layout(s, err);  // host arithmetic: the periods' boxes
+  if (rc) return rc;
+  if (!ss) {
+    const double lo = (double)s->x_lo[0], hi = lo + (double)(s->nx[0] - 1);
+    if (ini_x < lo || ini_x > hi) return sfail(err, SDPGPU_ERR_ARG, "%s: ini_x = %g outside period 1's staff numbers %g .. %g", who, ini_x, lo, hi);
+    if (!s->solved) return sfail(err, SDPGPU_ERR_STATE, "%s: nothing has been solved (the table policy needs sdpgpu_batch_solve; a level rule does not)", who);
+  }
+  rc = check_tables(s, err, who);
+  if (rc) return rc;
+
+  s->sim_err = err;
+  rc = no_device(s, who);
+  if (rc) return rc;
+  DeviceScope dev;
+  SHIP_TRY(err, dev.enter(s->device));
+  rc = allocate(s, err);  // (a level rule needs the device tables, not a solve)
+  if (rc) return rc;
+  const uint32_t n = (uint32_t)leaves;
+  // what the instances share of a period: the tree level and the box (the instance's fields are filled in by the kernel)
+  std::vector<sdp::StaffSimPeriod> per((size_t)T);
+  uint32_t stride = n;
+  for (int t = 0; t < T; ++t) {
+    sdp::StaffSimPeriod& q = per[(size_t)t];
+    std::memset(&q, 0, sizeof q);
+    stride /= (uint32_t)sample_nums[t];
+    q.x_lo = (int32_t)s->x_lo[(size_t)t];
+    q.nx = (int32_t)s->nx[(size_t)t];
+    q.K = (uint32_t)sample_nums[t];
+    q.stride = stride;
+    q.half_bits = make_stream(sample_nums[t], 0, 0).half_bits;
+  }
+  const sdpgpu_desc& d = s->d[0];
+  sdp::StaffSimLaunch L{};
+  L.T = T;
+  L.n_rules = (int32_t)n_pairs;
+  L.clamp = d.clamp_inventory;
+  L.min_x = (int32_t)d.min_inventory;
+  L.max_x = (int32_t)d.max_inventory;
+  L.ini_x = (int32_t)ini_x;
+  L.n_leaves = n;
+  L.seed_lo = (uint32_t)(seed & 0xffffffffu);
+  L.seed_hi = (uint32_t)(seed >> 32);
+
+  RolloutFrame<StaffBatch> f(s, n, (size_t)n_pairs);
+  const size_t sums = f.nr * n;
+  const auto p_per = f.put(per.data(), per.size());
+  const auto p_ss = f.put(levels.data(), levels.size());
+  const auto p_flag = f.take<uint8_t>(out_valid ? sums : 0);
+  const auto p_dem = f.take<int32_t>(out_demand ? sums * (size_t)T : 0);
+  rc = f.begin();
+  if (rc) return rc;
+  L.waves_per_rule = f.W;
+  const dim3 grid((unsigned)((f.nr * f.W + 3) / 4));  // (at most 2^28 / 64 + n x rules waves)
+  rc = f.start();
+  if (rc) return rc;
+  if (ss)
+    hipLaunchKernelGGL((sdp::staff_batch_sim_kernel<sdp::StaffLevelRule>), grid, dim3(256), 0, s->stream, L, (int32_t)N, n_rules, f[p_per], s->d_inst,
+                       s->d_tabs, sdp::StaffLevelRule{f[p_ss]}, f.d_sum, f[p_flag], f[p_dem], f.d_part, f.d_cnt);
+  else
+    hipLaunchKernelGGL((sdp::staff_batch_sim_kernel<sdp::StaffTableRule>), grid, dim3(256), 0, s->stream, L, (int32_t)N, n_rules, f[p_per], s->d_inst,
+                       s->d_tabs, sdp::StaffTableRule{s->d_policy}, f.d_sum, f[p_flag], f[p_dem], f.d_part, f.d_cnt);
+  SHIP_TRY(err, hipGetLastError());
+  f.download(out_valid, f[p_flag], sums);
+  f.download(out_demand, f[p_dem], sums * (size_t)T * sizeof(int32_t));
+  return f.finish(results, out_sum);
 }
 
 }  // namespace sdpgpu_detail

@@ -109,10 +109,7 @@ int sdpgpu_staff_simulate(sdpgpu_handle* h, const int32_t* sample_nums, uint64_t
       q.pad = 0;
     }
     sdp::StaffSimLaunch L{};
-    L.K = h->d.fixed_order_cost;
-    L.v = h->d.unit_order_cost;
-    L.salary = h->d.holding_cost;
-    L.pen = h->d.penalty_cost;
+    L.c = sdp::StaffSimCosts{h->d.fixed_order_cost, h->d.unit_order_cost, h->d.holding_cost, h->d.penalty_cost};
     L.T = T;
     L.n_rules = n_rules;
     L.clamp = h->d.clamp_inventory;

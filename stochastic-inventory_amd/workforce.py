@@ -323,6 +323,7 @@ class StaffRecursionBatch:
         self._tables = {}
         self._initial = None
         self._grid = {}
+        self.last_results = None
 
     def __len__(self):
         return len(self.functors)
@@ -389,11 +390,42 @@ class StaffRecursionBatch:
         """Instance i's rows {period, iniStaffNum, action} of the visited states in comparator order -- what
         StaffRecursion.getOptTable gives for a handle of the instance."""
         self._solve()
-        f = self.functors[i]
         rows = []
-        for period, (L, H) in enumerate(staff_reach_intervals(f, [self._lens[k] for k in self.use[i]]), start=1):
+        for period in range(1, self.T + 1):
+            L, H = self._batch.reachable(i, period)  # (staff_reach_intervals above states the same intervals in numpy)
             x_lo = int(self._batch.grid(i, period)[0])
             pol = self._table(i, period)[1]
             x = np.arange(L, H + 1, dtype=np.int64)
             rows.append(np.stack([np.full(len(x), float(period)), x.astype(np.float64), pol[x - x_lo].astype(np.float64)], axis=1))
         return np.concatenate(rows, axis=0) if rows else np.zeros((0, 3))
+
+    # ---- the rest of WorkforceTesting.main's loop body (WorkforceTesting.java:112-165), for all instances at once ----
+    def defaultSampleNums(self) -> List[int]:
+        """SimulatesS.defaultSampleNums: 10 children in the first four periods, one from the fifth on."""
+        return [10 if t <= 3 else 1 for t in range(self.T)]
+
+    def fitSinglesS(self, maxOrderQuantity: float = 2 ** 31 - 1) -> np.ndarray:
+        """`new FitsS(maxOrderQuantity, T).getSinglesS(getOptTable())` of every instance, on the device: (n, T, 2).  No policy
+        table comes to the host."""
+        self._solve()
+        return self._batch.fit_ss(maxOrderQuantity)
+
+    def _rollout(self, ss, sampleNums, seed):
+        k = self.defaultSampleNums() if sampleNums is None else sampleNums
+        res = self._batch.staff_simulate(k, seed, int(self.functors[0].iniStaffNum), ss)
+        self.last_results = res
+        return np.array([[r.mean for r in row] for row in res])
+
+    def simulatesS(self, optimalsS, sampleNums=None, seed: int = 12345):
+        """`SimulatesS.simulatesS(initialState, optimalsS[i])` of every instance in one rollout launch, from (1, iniStaffNum):
+        optimalsS of shape (n, T, 2) gives means (n,), (n, R, T, 2) gives (n, R) -- R rules per instance on the same uniforms
+        (the fitted levels and the MIP's, say).  All instances see common random numbers.  The SdpgpuSimResults stay in
+        `last_results` [n][R]."""
+        ss = np.asarray(optimalsS, dtype=np.float64)
+        means = self._rollout(ss, sampleNums, seed)
+        return means[:, 0] if ss.ndim == 3 else means
+
+    def simulateTable(self, sampleNums=None, seed: int = 12345) -> np.ndarray:
+        """The same rollout under every instance's own policy table (solved first if it has not been): means (n,)."""
+        self._solve()
+        return self._rollout(None, sampleNums, seed)[:, 0]

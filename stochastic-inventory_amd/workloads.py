@@ -209,6 +209,30 @@ def workforce_testing_sweep(T: int = 8, maxHire: int = 1000) -> List[StaffWorklo
     return out
 
 
+def workforce_testing_loop(sweep=None, mip_levels=None, sampleNums=None, seed: int = 12345, device: int = -1) -> dict:
+    """The loop body of WorkforceTesting.main (WorkforceTesting.java:112-165) for a whole sweep (default:
+    workforce_testing_sweep()) behind ONE batch: solve, FitsS(Integer.MAX_VALUE, T).getSinglesS, and the rollouts of the
+    fitted levels -- and, when `mip_levels` (n, T, 2) is given, of the caller's (MIP) levels in a second rule slot of the same
+    launch, on the same uniforms.  No per-instance handle and no policy table on the host.  Returns
+        opt[n], hires[n]      V_1(iniStaffNum) and its hire count
+        levels[n, T, 2]       the fitted (s, S)
+        sim[n, R]             the rollout means, R = 1 or 2 (slot 1: mip_levels)
+        gapPercent[n, R]      (sim - opt) * 100 / opt"""
+    from .workforce import StaffRecursionBatch
+    sweep = workforce_testing_sweep() if sweep is None else list(sweep)
+    with StaffRecursionBatch([w.functor for w in sweep], [w.level_pmf for w in sweep], sweep[0].T, device=device) as rec:
+        opt, hires = rec.initial()
+        levels = rec.fitSinglesS(2 ** 31 - 1)
+        rules = levels[:, None]
+        if mip_levels is not None:
+            mip = np.asarray(mip_levels, dtype=np.float64)
+            if mip.shape != levels.shape:
+                raise ValueError(f"mip_levels of shape {mip.shape}: expected {levels.shape}")
+            rules = np.stack([levels, mip], axis=1)
+        sim = rec.simulatesS(rules, sampleNums, seed)
+    return {"opt": opt, "hires": hires, "levels": levels, "sim": sim, "gapPercent": (sim - opt[:, None]) * 100 / opt[:, None]}
+
+
 # capacitated.CLSP's three lambdas (CLSP.java:251-272) as the HIP device text a driver hands to sdpgpu_create_custom when its
 # lambdas are its own: params = {K, v, h, pi, minInventory, maxInventory, maxOrderQuantity}.  bench.py's `custom_clsp` entry
 # runs configs[1] through this text, i.e. through the reference's actual plugin API (arbitrary closures) instead of the
