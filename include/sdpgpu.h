@@ -811,6 +811,17 @@ int32_t sdpgpu_f1_screen_start(sdpgpu_handle* h, int32_t period);
  * kernel's cut-off did not run), out[1] = RS of the handle.  sdpgpu_stats.fp64_ops_executed prices those steps at the RS rows
  * that ran.  Waits for the handle's stream, as sdpgpu_f1_screen_get does. */
 int sdpgpu_f1_screen_rows_get(sdpgpu_handle* h, int32_t period, int64_t out[2]);
+/* Additive to ABI 6: the launch forms of the F1 level kernel.  The waves of a level launch are independent tasks;
+ * a form decides which wave runs which task, and when, and nothing else -- no table, counter or plan depends on it.
+ * SDPGPU_F1_LEVEL_FORM=<0|1|2> at create time: 0 = four tasks per 256-thread workgroup in index order, 1 = one wave per
+ * workgroup, 2 = resident waves that claim tasks from a counter; 1 and 2 start band 0 and then the last bands first, the
+ * longest tasks (unset: 2; anything else: SDPGPU_ERR_ARG from sdpgpu_create, with a reason; so for the diagnostics
+ * SDPGPU_F1_LEVEL_WGS=<n >= 1>, the most workgroups form 2 launches, and SDPGPU_F1_LEVEL_ROUNDS=<q>, the round count the
+ * planner's band search starts at).  A period-T launch without the cut-off or with all four rows screened runs as form 1
+ * where form 2 is asked for (the claim loop would cost it a wave per SIMD).  For period t of the last solve: out[0] = the form
+ * that ran, out[1] = the workgroups of its level launch, out[2] = the threads of each; where the level kernel did not run the
+ * period: the handle's form, 0, 0.  Host-side: what the launcher recorded, no device read. */
+int sdpgpu_f1_level_form_get(sdpgpu_handle* h, int32_t period, int64_t out[3]);
 /* Host arithmetic, no handle: the executed fp64 operations per nominal cell that sdpgpu_stats_get charges a level period which
  * counted its steps -- ops_cell for each of the (steps_run - steps_screened) exact steps; for a screened step the
  * screen_rows * levels * (3 with a future term, 2 without) + screen_rows operations of a lane plus the table's levels / 64

@@ -376,6 +376,7 @@ EXPORTS = {
     "sdpgpu_f1_screen_get": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "sdpgpu_f1_screen_start": (C.c_int32, [_P, C.c_int32]),
     "sdpgpu_f1_screen_rows_get": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
+    "sdpgpu_f1_level_form_get": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int64)]),
     "sdpgpu_f1_level_ops_model": (C.c_double, [C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
                                                C.c_int64, C.c_int64]),
     "sdpgpu_f1_decided_start": (C.c_int64, [_P, C.c_int32]),

@@ -227,6 +227,7 @@ struct LevelParams {
   int32_t n_chunks;   // chunk rows: ceil((A - 1) / band) + n_ablocks
   int32_t cut_start;  // CUT: the step of a task's first cut-off test (a multiple of S, >= S)
   int32_t screen_start;  // CUT: the step a screened level block starts at (a multiple of S; 0: no block is screened)
+  int32_t form;       // THE LAUNCH FORMS: 0 = four tasks per workgroup, 1 = one wave per workgroup, 2 = waves claim tasks
 };
 
 template <int S>
@@ -243,124 +244,164 @@ __host__ __device__ inline int level_chunks(int n_actions, int band, int n_abloc
   return (n_actions - 1 + band - 1) / band + n_ablocks;
 }
 
-template <int R, int S, bool FUTURE, bool KEYED_IN, bool CUT, int RS = R, int SG = 1>
+// THE LAUNCH FORMS (LevelParams::form; the host: SDPGPU_F1_LEVEL_FORM / kF1LevelForm, sdpgpu_internal.hpp).  The waves of a
+// workgroup are independent tasks -- there is no workgroup barrier -- but a workgroup gives its LDS and its wave slots back
+// only when its slowest wave ends, and tasks differ in length (the cut-off stops the blocks of high bands later).  Which
+// wave runs which task, and when, is all that a form decides:
+//   0  four tasks per 256-thread workgroup, task = blockIdx.x * 4 + wave, in index order;
+//   1  the same instantiation launched with ONE wave per workgroup (64 threads, level_wave_lds bytes, n_tasks workgroups): a
+//      slot and its LDS are free the moment the wave ends;
+//   2  resident waves that claim tasks (CLAIM): each wave, on its own, takes the next index from the word `claim` (lane 0,
+//      one vector atomic; zeroed on the stream before the launch), runs that task in its own LDS region and leaves when the
+//      index reaches n_tasks.  No wave waits for another, and nothing depends on how many workgroups are resident: one that
+//      starts late finds the queue empty.  Everything a task keeps -- slot fill, prefetch slot, c0, test schedule, the
+//      screen's mode rule, the tallies -- is set up again for every task, as at kernel entry.
+// Forms 1 and 2 take the longest tasks first: band 0, then from the last band down (index c, q = c / n_ablocks: band 0 for
+// q = 0, else band n_bands - q; action block c % n_ablocks).  The cut-off stops the blocks of higher bands later, so length
+// grows with the band -- except band 0, the ordering region near level 0, where screens fail and blocks are walked exactly:
+// its first action block is the longest task of a launch by half (profiles/f1_level_forms_ab.txt, the timeline).  No result
+// can see the order or the form: chunk rows are per (task, state), the NaN row goes where no other task writes, key and
+// counter atomics commute, and the counters are added per task.
+//   Forms 0 and 1 are one instantiation (CLAIM = false: the form is a wave-uniform field, the loop below is left after one
+// turn) with the registers of the kernel that knew no forms; the claim loop is an instantiation of its own, because as a
+// run-time branch it costs every instantiation registers and the period-T ones their third wave per SIMD
+// (profiles/f1_level_forms_resources.txt).
+__device__ __forceinline__ int level_task_of(const LevelParams& L, int c) {
+  const int q = c / L.n_ablocks;  // 0: band 0; q >= 1: band n_bands - q
+  return q == 0 ? c : L.n_tasks - L.n_ablocks * q + c % L.n_ablocks;
+}
+
+template <int R, int S, bool FUTURE, bool KEYED_IN, bool CUT, int RS = R, int SG = 1, bool CLAIM = false>
 __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, LevelParams L, const double* __restrict__ v_next,
                                                               const unsigned long long* __restrict__ k_next,
                                                               double* __restrict__ out_val, int32_t* __restrict__ out_idx,
                                                               unsigned long long* __restrict__ k_cur,
                                                               const double* __restrict__ pmf_p,
                                                               const double* __restrict__ u_row,
-                                                              unsigned long long* __restrict__ cut_count) {
+                                                              unsigned long long* __restrict__ cut_count,
+                                                              unsigned* __restrict__ claim) {
   constexpr int DB = LevelShape<S>::DB, ROW = LevelShape<S>::ROW, NA = 64 * R;
   static_assert(RS >= 1 && R % RS == 0 && (CUT || RS == R), "screen rows divide R; only the cut-off screens");
   static_assert(SG >= 1 && (RS * S) % SG == 0, "a step's cells, RW S of them in either pass, fall into whole groups of SG");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int task = blockIdx.x * 4 + wave;
-  if (task >= L.n_tasks) return;  // no workgroup barrier below
-  const bool MAXDIR = W.maxdir != 0;
-  const double ident = MAXDIR ? -1.7976931348623157e308 : 1.7976931348623157e308;
-  const int ab = task % L.n_ablocks;
-  const int b = task / L.n_ablocks;
-  const int kb = ab * NA;
-  const int yb = L.lo + b * L.band;
-  const int ye = min(yb + L.band, L.y_hi);
-  const int i_min = yb - kb - NA + 1;  // slot q holds state i_min + q; states i_min .. ye - 1 - kb
-  const int n_slot = ye - yb + NA - 1;
-  char* mine = smem + (size_t)wave * level_wave_lds(L.band, R, S);
-  double* s_row = reinterpret_cast<double*>(mine);
-  double* s_val = s_row + DB * ROW;
-  int* s_idx = reinterpret_cast<int*>(s_val + L.band + NA);
-  // THE PREFETCH SLOT: what the build of ONE table reads from memory, loaded while the table before it is walked.  The
-  // table of block y and steps j .. j + DB - 1 needs V(clamp(y + s - j')) for s < S and DB steps j': the DB + S - 1
-  // consecutive entries w[q] = V(clamp(y - j - (DB - 1) + q)), of which row t, level s takes w[DB - 1 - t + s].  Lane t holds
-  // w[t] and w[64 + t] (as stored: a key is decoded where it is used, so that nothing waits for the load here) and its
-  // row's p_j; the tag (pf_y, pf_j) says whose they are.  A table whose tag does not match is built from direct loads.
-  // Period T (no future term) has only p_j to fetch, and holding it costs its CUT instantiation the third wave per SIMD
-  // (166 -> 189 VGPRs): it stays as it was.
-  constexpr bool PF = FUTURE;
-  static_assert(DB + S - 1 > 64 && DB + S - 1 <= 128, "two window entries per lane");
-  [[maybe_unused]] unsigned long long pf_w0 = 0, pf_w1 = 0;
-  [[maybe_unused]] double pf_p = 0.0;
-  [[maybe_unused]] int pf_y = INT32_MIN, pf_j = 0;
-  [[maybe_unused]] int pf_stop = INT32_MAX;  // CUT: the step the block before stopped at (a guess at where this one will)
-  [[maybe_unused]] auto prefetch = [&](int y, int j) {
-    const int m = y - j - (DB - 1);
-    pf_p = pmf_p[j + min(lane, min(DB, L.d_pad - j) - 1)];
-    pf_w0 = level_v_word<KEYED_IN>(W, v_next, k_next, m + lane);
-    pf_w1 = level_v_word<KEYED_IN>(W, v_next, k_next, m + 64 + min(lane, DB + S - 2 - 64));
-    pf_y = y;
-    pf_j = j;
-  };
-  if constexpr (PF) prefetch(yb, 0);  // (the slot fill below covers it)
-  if constexpr (CUT) {
-    // every slot starts at U(i) = Q(i, 0) with action 0 (see THE CUT-OFF above); a slot of no state of the slab -- the
-    // ends of the range, and the slots past n_slot that the last, ragged band's level blocks still address -- at a value
-    // every sum exceeds, so that it never holds a block back (it is never written out)
-    for (int q = lane; q < L.band + NA; q += 64) {
-      const int i = i_min + q;
-      const bool in = i >= L.lo && i - L.lo < L.n_states;
-      s_val[q] = in ? u_row[i] : -__builtin_huge_val();
-      s_idx[q] = 0;
+  for (;;) {  // (CLAIM: one turn per task claimed; else one turn)
+    int task;
+    if constexpr (CLAIM) {
+      unsigned got = 0;
+      if (lane == 0) got = atomicAdd(claim, 1u);
+      got = __builtin_amdgcn_readfirstlane(got);
+      if (got >= (unsigned)L.n_tasks) return;
+      task = level_task_of(L, (int)got);
+    } else {
+      // (the workgroup's own wave count: 4, or 1 in form 1)
+      task = (int)(blockIdx.x * (blockDim.x >> 6)) + wave;
+      if (task >= L.n_tasks) return;  // no workgroup barrier below
+      if (L.form != 0) task = level_task_of(L, task);
     }
-  } else {
-    for (int q = lane; q < n_slot; q += 64) {
-      s_val[q] = ident;
-      s_idx[q] = 0;
+    const bool MAXDIR = W.maxdir != 0;
+    const double ident = MAXDIR ? -1.7976931348623157e308 : 1.7976931348623157e308;
+    const int ab = task % L.n_ablocks;
+    const int b = task / L.n_ablocks;
+    const int kb = ab * NA;
+    const int yb = L.lo + b * L.band;
+    const int ye = min(yb + L.band, L.y_hi);
+    const int i_min = yb - kb - NA + 1;  // slot q holds state i_min + q; states i_min .. ye - 1 - kb
+    const int n_slot = ye - yb + NA - 1;
+    char* mine = smem + (size_t)wave * level_wave_lds(L.band, R, S);
+    double* s_row = reinterpret_cast<double*>(mine);
+    double* s_val = s_row + DB * ROW;
+    int* s_idx = reinterpret_cast<int*>(s_val + L.band + NA);
+    // THE PREFETCH SLOT: what the build of ONE table reads from memory, loaded while the table before it is walked.  The
+    // table of block y and steps j .. j + DB - 1 needs V(clamp(y + s - j')) for s < S and DB steps j': the DB + S - 1
+    // consecutive entries w[q] = V(clamp(y - j - (DB - 1) + q)), of which row t, level s takes w[DB - 1 - t + s].  Lane t holds
+    // w[t] and w[64 + t] (as stored: a key is decoded where it is used, so that nothing waits for the load here) and its
+    // row's p_j; the tag (pf_y, pf_j) says whose they are.  A table whose tag does not match is built from direct loads.
+    // Period T (no future term) has only p_j to fetch, and holding it costs its CUT instantiation the third wave per SIMD
+    // (166 -> 189 VGPRs): it stays as it was.
+    constexpr bool PF = FUTURE;
+    static_assert(DB + S - 1 > 64 && DB + S - 1 <= 128, "two window entries per lane");
+    [[maybe_unused]] unsigned long long pf_w0 = 0, pf_w1 = 0;
+    [[maybe_unused]] double pf_p = 0.0;
+    [[maybe_unused]] int pf_y = INT32_MIN, pf_j = 0;
+    [[maybe_unused]] int pf_stop = INT32_MAX;  // CUT: the step the block before stopped at (a guess at where this one will)
+    [[maybe_unused]] auto prefetch = [&](int y, int j) {
+      const int m = y - j - (DB - 1);
+      pf_p = pmf_p[j + min(lane, min(DB, L.d_pad - j) - 1)];
+      pf_w0 = level_v_word<KEYED_IN>(W, v_next, k_next, m + lane);
+      pf_w1 = level_v_word<KEYED_IN>(W, v_next, k_next, m + 64 + min(lane, DB + S - 2 - 64));
+      pf_y = y;
+      pf_j = j;
+    };
+    if constexpr (PF) prefetch(yb, 0);  // (the slot fill below covers it)
+    if constexpr (CUT) {
+      // every slot starts at U(i) = Q(i, 0) with action 0 (see THE CUT-OFF above); a slot of no state of the slab -- the
+      // ends of the range, and the slots past n_slot that the last, ragged band's level blocks still address -- at a value
+      // every sum exceeds, so that it never holds a block back (it is never written out)
+      for (int q = lane; q < L.band + NA; q += 64) {
+        const int i = i_min + q;
+        const bool in = i >= L.lo && i - L.lo < L.n_states;
+        s_val[q] = in ? u_row[i] : -__builtin_huge_val();
+        s_idx[q] = 0;
+      }
+    } else {
+      for (int q = lane; q < n_slot; q += 64) {
+        s_val[q] = ident;
+        s_idx[q] = 0;
+      }
     }
-  }
-  double c0[R];
-  bool kreal[R];
+    double c0[R];
+    bool kreal[R];
 #pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int k = kb + lane + 64 * r;
-    kreal[r] = k < W.n_actions;
-    const double a = (double)k * W.step;
-    if (W.c_tab)  // (a padded action reads the last entry: finite, never selected)
-      c0[r] = W.c_tab[k < W.n_actions ? k : W.n_actions - 1];
-    else
-      c0[r] = (a > 0 ? W.K : 0.0) + W.v * a;
-  }
-  // SCREEN ROWS: screen row q carries the c0 of the lowest live action of rows q G .. (q + 1) G - 1 -- its base row, except
-  // that lane 0 of action block 0 skips action 0 (a group whose base row is padded has nothing live: any finite c0 will do)
-  [[maybe_unused]] double c0s[RS];
-  if constexpr (RS < R) {
-#pragma unroll
-    for (int q = 0; q < RS; ++q) c0s[q] = q == 0 && kb + lane == 0 ? c0[1] : c0[q * (R / RS)];
-  }
-  // CUT: the test schedule (wave-uniform, scalar registers).  A block's first test comes `dec` steps before the step its
-  // predecessor stopped at, then one every S steps; a block that passes its first test moves the next block's twice as
-  // far down, and after a block that ran to the end the next one is tested once, S steps before the end (a sum only grows,
-  // so a block that could have stopped earlier still passes there): where nothing ever stops, one test per block.
-  [[maybe_unused]] int cut_first = L.cut_start, cut_dec = S, cut_once = 0;
-  [[maybe_unused]] unsigned cut_steps = 0, cut_tests = 0;
-  // CUT: the screen's mode rule (wave-uniform, scalar registers; THE SCREEN above).  scr_run counts the stopped blocks since
-  // the last one that ran to the end or failed its screen; a block is screened when scr_run >= scr_need.
-  [[maybe_unused]] int scr_run = 0, scr_need = 1;
-  [[maybe_unused]] unsigned scr_hit = 0, scr_miss = 0, scr_exact = 0, scr_steps = 0;
-
-  for (int y0 = yb; y0 < ye; y0 += S) {
-    // Priority by progress, as in f1_cells: the four waves of a workgroup free its LDS only together, and a plan
-    // of two rounds of equal tasks loses a tenth of the issue rate when the resident waves of a SIMD drift apart by age
-    // (the one left behind then runs alone, at 0.6 of the rate, while the slot of the finished one stays empty).
-    if (W.prio_fair) prio_by_progress((unsigned)(y0 - yb), (unsigned)(ye - yb));
-    double acc[R][S];
-    [[maybe_unused]] int cut_fail = 0;
-    int stop_at = -1;  // CUT: the step the block stopped at
-    // CUT: the step this pass over the block starts at -- L.screen_start for a screened block, 0 for an exact one (and for
-    // the second pass over a block whose screen failed)
-    [[maybe_unused]] int scr_from = 0;
-    if constexpr (CUT) scr_from = scr_run >= scr_need ? L.screen_start : 0;
-    [[maybe_unused]] bool again = false;
-    // ONE PASS over the block from step j_first is the text of sdp_window_level_pass.hpp.  A collapsed instantiation (RS < R)
-    // walks a screened pass here, over the RS screen rows, and leaves the loop below to the exact walks: the screen stopped
-    // the block (done), or it failed and the block is walked from step 0.  (In front of the loop and not a branch inside it:
-    // there the R S sums of the exact walk stay live through the screened pass, 279 VGPRs and one wave per SIMD.)
+    for (int r = 0; r < R; ++r) {
+      const int k = kb + lane + 64 * r;
+      kreal[r] = k < W.n_actions;
+      const double a = (double)k * W.step;
+      if (W.c_tab)  // (a padded action reads the last entry: finite, never selected)
+        c0[r] = W.c_tab[k < W.n_actions ? k : W.n_actions - 1];
+      else
+        c0[r] = (a > 0 ? W.K : 0.0) + W.v * a;
+    }
+    // SCREEN ROWS: screen row q carries the c0 of the lowest live action of rows q G .. (q + 1) G - 1 -- its base row, except
+    // that lane 0 of action block 0 skips action 0 (a group whose base row is padded has nothing live: any finite c0 will do)
+    [[maybe_unused]] double c0s[RS];
     if constexpr (RS < R) {
-      if (scr_from > 0) {
-        const int j_first = scr_from;
-        double acs[RS][S];
+#pragma unroll
+      for (int q = 0; q < RS; ++q) c0s[q] = q == 0 && kb + lane == 0 ? c0[1] : c0[q * (R / RS)];
+    }
+    // CUT: the test schedule (wave-uniform, scalar registers).  A block's first test comes `dec` steps before the step its
+    // predecessor stopped at, then one every S steps; a block that passes its first test moves the next block's twice as
+    // far down, and after a block that ran to the end the next one is tested once, S steps before the end (a sum only grows,
+    // so a block that could have stopped earlier still passes there): where nothing ever stops, one test per block.
+    [[maybe_unused]] int cut_first = L.cut_start, cut_dec = S, cut_once = 0;
+    [[maybe_unused]] unsigned cut_steps = 0, cut_tests = 0;
+    // CUT: the screen's mode rule (wave-uniform, scalar registers; THE SCREEN above).  scr_run counts the stopped blocks since
+    // the last one that ran to the end or failed its screen; a block is screened when scr_run >= scr_need.
+    [[maybe_unused]] int scr_run = 0, scr_need = 1;
+    [[maybe_unused]] unsigned scr_hit = 0, scr_miss = 0, scr_exact = 0, scr_steps = 0;
+
+    for (int y0 = yb; y0 < ye; y0 += S) {
+      // Priority by progress, as in f1_cells: the four waves of a workgroup free its LDS only together, and a plan
+      // of two rounds of equal tasks loses a tenth of the issue rate when the resident waves of a SIMD drift apart by age
+      // (the one left behind then runs alone, at 0.6 of the rate, while the slot of the finished one stays empty).
+      if (W.prio_fair) prio_by_progress((unsigned)(y0 - yb), (unsigned)(ye - yb));
+      double acc[R][S];
+      [[maybe_unused]] int cut_fail = 0;
+      int stop_at = -1;  // CUT: the step the block stopped at
+      // CUT: the step this pass over the block starts at -- L.screen_start for a screened block, 0 for an exact one (and for
+      // the second pass over a block whose screen failed)
+      [[maybe_unused]] int scr_from = 0;
+      if constexpr (CUT) scr_from = scr_run >= scr_need ? L.screen_start : 0;
+      [[maybe_unused]] bool again = false;
+      // ONE PASS over the block from step j_first is the text of sdp_window_level_pass.hpp.  A collapsed instantiation (RS < R)
+      // walks a screened pass here, over the RS screen rows, and leaves the loop below to the exact walks: the screen stopped
+      // the block (done), or it failed and the block is walked from step 0.  (In front of the loop and not a branch inside it:
+      // there the R S sums of the exact walk stay live through the screened pass, 279 VGPRs and one wave per SIMD.)
+      if constexpr (RS < R) {
+        if (scr_from > 0) {
+          const int j_first = scr_from;
+          double acs[RS][S];
 #define SDP_LEVEL_PASS_ROWS RS
 #define SDP_LEVEL_PASS_C0 c0s
 #define SDP_LEVEL_PASS_ACC acs
@@ -368,22 +409,22 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
 #undef SDP_LEVEL_PASS_ROWS
 #undef SDP_LEVEL_PASS_C0
 #undef SDP_LEVEL_PASS_ACC
-        const unsigned walked = (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);
-        cut_steps += walked;
-        scr_steps += walked;
-        if (stop_at >= 0) {
-          ++scr_hit;
-          scr_need = 1;
-        } else {  // the screen has failed, as below
-          ++scr_miss;
-          scr_need = min(2 * scr_need, 8);
-          scr_run = 0;
-          scr_from = 0;
+          const unsigned walked = (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);
+          cut_steps += walked;
+          scr_steps += walked;
+          if (stop_at >= 0) {
+            ++scr_hit;
+            scr_need = 1;
+          } else {  // the screen has failed, as below
+            ++scr_miss;
+            scr_need = min(2 * scr_need, 8);
+            scr_run = 0;
+            scr_from = 0;
+          }
         }
       }
-    }
-    if (RS == R || stop_at < 0) do {
-      const int j_first = CUT ? scr_from : 0;
+      if (RS == R || stop_at < 0) do {
+        const int j_first = CUT ? scr_from : 0;
 #define SDP_LEVEL_PASS_ROWS R
 #define SDP_LEVEL_PASS_C0 c0
 #define SDP_LEVEL_PASS_ACC acc
@@ -391,90 +432,93 @@ __global__ __launch_bounds__(256) void window_f1_level_kernel(WinParams W, Level
 #undef SDP_LEVEL_PASS_ROWS
 #undef SDP_LEVEL_PASS_C0
 #undef SDP_LEVEL_PASS_ACC
-      if constexpr (CUT) {
-        again = false;
-        cut_steps += (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);
-        if (j_first > 0) scr_steps += (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);  // (RS = R: screened here)
-        if (j_first == 0) {
-          ++scr_exact;
-        } else if (stop_at >= 0) {
-          ++scr_hit;
-          scr_need = 1;
-        } else {  // the screen has failed: nothing is known about the block, walk it again from step 0
-          ++scr_miss;
-          scr_need = min(2 * scr_need, 8);
-          scr_run = 0;
-          scr_from = 0;
-          again = true;
+        if constexpr (CUT) {
+          again = false;
+          cut_steps += (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);
+          if (j_first > 0) scr_steps += (unsigned)((stop_at < 0 ? L.d_pad : stop_at) - j_first);  // (RS = R: screened here)
+          if (j_first == 0) {
+            ++scr_exact;
+          } else if (stop_at >= 0) {
+            ++scr_hit;
+            scr_need = 1;
+          } else {  // the screen has failed: nothing is known about the block, walk it again from step 0
+            ++scr_miss;
+            scr_need = min(2 * scr_need, 8);
+            scr_run = 0;
+            scr_from = 0;
+            again = true;
+          }
         }
+      } while (CUT && again);
+      if constexpr (CUT) {
+        scr_run = stop_at >= 0 ? scr_run + 1 : 0;
+        if constexpr (PF) pf_stop = stop_at < 0 ? INT32_MAX : stop_at;
+        if (stop_at >= 0) {  // no cell of the block can win or tie: nothing to put into the slots
+          cut_dec = cut_fail == 0 ? min(2 * cut_dec, 8 * S) : S;
+          cut_first = max(S, stop_at - cut_dec);
+          cut_once = 0;
+          continue;
+        }
+        cut_first = max(S, L.d_pad - S);
+        cut_dec = S;
+        cut_once = 1;
       }
-    } while (CUT && again);
-    if constexpr (CUT) {
-      scr_run = stop_at >= 0 ? scr_run + 1 : 0;
-      if constexpr (PF) pf_stop = stop_at < 0 ? INT32_MAX : stop_at;
-      if (stop_at >= 0) {  // no cell of the block can win or tie: nothing to put into the slots
-        cut_dec = cut_fail == 0 ? min(2 * cut_dec, 8 * S) : S;
-        cut_first = max(S, stop_at - cut_dec);
-        cut_once = 0;
-        continue;
-      }
-      cut_first = max(S, L.d_pad - S);
-      cut_dec = S;
-      cut_once = 1;
-    }
-    // into the per-state slots: cell (r, s) is state y0 + s - k, slot (y0 - yb) + s - lane - 64 r + NA - 1
-    const int sb = (y0 - yb) - lane + NA - 1;
-    const int ib = y0 - kb - lane - L.lo;  // state - lo of cell (0, 0)
+      // into the per-state slots: cell (r, s) is state y0 + s - k, slot (y0 - yb) + s - lane - 64 r + NA - 1
+      const int sb = (y0 - yb) - lane + NA - 1;
+      const int ib = y0 - kb - lane - L.lo;  // state - lo of cell (0, 0)
 #pragma unroll
-    for (int s = 0; s < S; ++s) {
+      for (int s = 0; s < S; ++s) {
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        const int rel = ib + s - 64 * r;
-        if (kreal[r] && rel >= 0 && rel < L.n_states) {
-          const int q = sb + s - 64 * r;
-          const double cur = s_val[q];
-          if (MAXDIR ? (acc[r][s] > cur) : (acc[r][s] < cur)) {
-            s_val[q] = acc[r][s];
-            s_idx[q] = kb + lane + 64 * r;
+        for (int r = 0; r < R; ++r) {
+          const int rel = ib + s - 64 * r;
+          if (kreal[r] && rel >= 0 && rel < L.n_states) {
+            const int q = sb + s - 64 * r;
+            const double cur = s_val[q];
+            if (MAXDIR ? (acc[r][s] > cur) : (acc[r][s] < cur)) {
+              s_val[q] = acc[r][s];
+              s_idx[q] = kb + lane + 64 * r;
+            }
           }
         }
       }
     }
-  }
 
-  // every state of the task's range that has a real action here: its piece, in chunk row (b - band(i)) + ab
-  __builtin_amdgcn_wave_barrier();
-  for (int q = lane; q < n_slot; q += 64) {
-    const int i = i_min + q;
-    const int rel = i - L.lo;
-    if (rel < 0 || rel >= L.n_states) continue;
-    const int kf = max(kb, yb - i);  // lowest action of the piece
-    if (kf >= W.n_actions) continue;
-    const int c = (b - rel / L.band) + ab;
-    const double v = s_val[q];
-    const int64_t o = (int64_t)c * W.partial_stride + i;
-    out_val[o] = v;
-    out_idx[o] = s_idx[q];
-    if (kb > 0 && yb - i == kb) {  // both boundaries at action kf: row c - 1 holds no piece of this state
-      out_val[o - W.partial_stride] = __builtin_nan("");
-      out_idx[o - W.partial_stride] = 0;
-    }
-    if (MAXDIR)
-      atomicMax(k_cur + i, f64_key(v));
-    else
-      atomicMin(k_cur + i, f64_key(v));
-  }
-  if constexpr (CUT) {  // what ran, for sdpgpu_stats: demand steps of level blocks, and cut-off tests
-    if (lane == 0) {
-      atomicAdd(cut_count, (unsigned long long)cut_steps);
-      atomicAdd(cut_count + 1, (unsigned long long)cut_tests);
-      if (L.screen_start > 0) {
-        atomicAdd(cut_count + 2, (unsigned long long)scr_hit);
-        atomicAdd(cut_count + 3, (unsigned long long)scr_miss);
-        atomicAdd(cut_count + 5, (unsigned long long)scr_steps);
+    // every state of the task's range that has a real action here: its piece, in chunk row (b - band(i)) + ab
+    __builtin_amdgcn_wave_barrier();
+    for (int q = lane; q < n_slot; q += 64) {
+      const int i = i_min + q;
+      const int rel = i - L.lo;
+      if (rel < 0 || rel >= L.n_states) continue;
+      const int kf = max(kb, yb - i);  // lowest action of the piece
+      if (kf >= W.n_actions) continue;
+      const int c = (b - rel / L.band) + ab;
+      const double v = s_val[q];
+      const int64_t o = (int64_t)c * W.partial_stride + i;
+      out_val[o] = v;
+      out_idx[o] = s_idx[q];
+      if (kb > 0 && yb - i == kb) {  // both boundaries at action kf: row c - 1 holds no piece of this state
+        out_val[o - W.partial_stride] = __builtin_nan("");
+        out_idx[o - W.partial_stride] = 0;
       }
-      atomicAdd(cut_count + 4, (unsigned long long)scr_exact);
+      if (MAXDIR)
+        atomicMax(k_cur + i, f64_key(v));
+      else
+        atomicMin(k_cur + i, f64_key(v));
     }
+    if constexpr (CUT) {  // what ran, for sdpgpu_stats: demand steps of level blocks, and cut-off tests
+      if (lane == 0) {
+        atomicAdd(cut_count, (unsigned long long)cut_steps);
+        atomicAdd(cut_count + 1, (unsigned long long)cut_tests);
+        if (L.screen_start > 0) {
+          atomicAdd(cut_count + 2, (unsigned long long)scr_hit);
+          atomicAdd(cut_count + 3, (unsigned long long)scr_miss);
+          atomicAdd(cut_count + 5, (unsigned long long)scr_steps);
+        }
+        atomicAdd(cut_count + 4, (unsigned long long)scr_exact);
+      }
+    }
+    if constexpr (!CLAIM) return;
+    __builtin_amdgcn_wave_barrier();  // (the next task's slot fill stays behind this task's read-out)
   }
 }
 

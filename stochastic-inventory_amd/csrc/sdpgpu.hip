@@ -396,6 +396,7 @@ int run_period_impl(sdpgpu_handle* h, int period, int part, int64_t range_lo, in
   p.lvl_steps_planned = 0;
   p.lvl_cut = false;
   p.lvl_screen_start = 0;
+  p.lvl_form = -1;
   p.pre_ops = 0;
   DevParams P = make_params(h, period);
   const double* v_next = period < h->T ? h->d_values + h->per[period].v_off : nullptr;
@@ -689,6 +690,34 @@ int sdpgpu_create(const sdpgpu_desc* desc, sdpgpu_handle** out) {
       }
       h->f1_step_group = group[0] - '0';
     }
+    if (const char* e = std::getenv("SDPGPU_F1_LEVEL_FORM")) {
+      const std::string form(e);
+      if (form != "0" && form != "1" && form != "2") {
+        delete h;
+        return fail(nullptr, SDPGPU_ERR_ARG, "SDPGPU_F1_LEVEL_FORM=%s: the launch forms of the F1 level kernel are 0, 1 or 2", e);
+      }
+      h->f1_level_form = form[0] - '0';
+    }
+    // (diagnostics of the launch forms: a whole decimal number in range and nothing else)
+    auto whole = [](const char* e, long lo, long hi, int* out) {
+      char* end = nullptr;
+      const long v = std::strtol(e, &end, 10);
+      if (!(*e >= '0' && *e <= '9') || *end || v < lo || v > hi) return false;
+      *out = (int)v;
+      return true;
+    };
+    if (const char* e = std::getenv("SDPGPU_F1_LEVEL_WGS")) {
+      if (!whole(e, 1, 1 << 20, &h->f1_level_wgs)) {
+        delete h;
+        return fail(nullptr, SDPGPU_ERR_ARG, "SDPGPU_F1_LEVEL_WGS=%s: the workgroups of form 2 of the F1 level kernel are 1 .. 1048576", e);
+      }
+    }
+    if (const char* e = std::getenv("SDPGPU_F1_LEVEL_ROUNDS")) {
+      if (!whole(e, 1, 64, &h->f1_level_rounds)) {
+        delete h;
+        return fail(nullptr, SDPGPU_ERR_ARG, "SDPGPU_F1_LEVEL_ROUNDS=%s: the rounds the F1 level planner starts at are 1 .. 64", e);
+      }
+    }
     if (const char* e = std::getenv("SDPGPU_F1_SCREEN_LOG2")) {
       const int b = std::atoi(e);
       if (b >= 1 && b <= 1000) h->f1_screen_mass = std::ldexp(1.0, -b);
@@ -846,6 +875,7 @@ void sdpgpu_destroy(sdpgpu_handle* h) {
   if (h->d_jobs) (void)hipFree(h->d_jobs);
   if (h->d_f1_u) (void)hipFree(h->d_f1_u);
   if (h->d_cut_count) (void)hipFree(h->d_cut_count);
+  if (h->d_level_claim) (void)hipFree(h->d_level_claim);
   if (h->d_diag) (void)hipFree(h->d_diag);
   if (h->d_rowtab) (void)hipFree(h->d_rowtab);
   if (h->d_rowperm) (void)hipFree(h->d_rowperm);
@@ -1776,6 +1806,18 @@ int sdpgpu_f1_screen_rows_get(sdpgpu_handle* h, int32_t period, int64_t out[2]) 
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   HIP_TRY(h, hipMemcpy(&c, h->d_cut_count + (size_t)(period - 1) * kCutCounters + 5, sizeof c, hipMemcpyDeviceToHost));
   out[0] = (int64_t)c;
+  return SDPGPU_OK;
+}
+
+int sdpgpu_f1_level_form_get(sdpgpu_handle* h, int32_t period, int64_t out[3]) {
+  if (!h || !out) return SDPGPU_ERR_ARG;
+  h->err.clear();
+  if (period < 1 || period > h->T) return fail(h, SDPGPU_ERR_ARG, "period %d out of 1..%d", period, h->T);
+  const PeriodInfo& p = h->per[period - 1];
+  const bool ran = h->allocated && p.lvl_form >= 0;  // (host-side: what the launcher recorded, no device read)
+  out[0] = ran ? p.lvl_form : h->f1_level_form;
+  out[1] = ran ? p.lvl_wgs : 0;
+  out[2] = ran ? p.lvl_threads : 0;
   return SDPGPU_OK;
 }
 

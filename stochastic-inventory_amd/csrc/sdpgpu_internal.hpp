@@ -67,6 +67,17 @@ constexpr int kF1ScreenRows = 2;
 // SDPGPU_F1_STEP_GROUP=<1|2|4> at create time; 1 is the kernel without the groups, instruction for instruction.  The default
 // is the fastest SG under which the bench contract holds on the full line with 3 % to spare (profiles/f1_step_groups_ab.txt).
 constexpr int kF1StepGroup = 4;
+// THE LAUNCH FORMS of the F1 level kernel (sdp_window.hpp): which wave runs which task, and when -- 0 = four tasks per
+// 256-thread workgroup in index order, 1 = one wave per workgroup, 2 = resident waves that claim tasks; 1 and 2 start band 0
+// and then the last bands first.  No table, counter or plan depends on the form.  SDPGPU_F1_LEVEL_FORM=<0|1|2> at create
+// time.  The default is the fastest form under which the bench contract holds on the full line with 3 % to spare
+// (profiles/f1_level_forms_ab.txt: 13.45 ms against the 16.49 ms of form 0 on the target grid).  Where form 2 would cost an
+// instantiation its third wave per SIMD (period T without the cut-off or with all rows screened) the launcher takes form 1.
+constexpr int kF1LevelForm = 2;
+// the wave slots the level planner sizes its rounds against (two waves per SIMD), and the workgroups of four waves that fill
+// them: form 2 launches no more than these (SDPGPU_F1_LEVEL_WGS=<n> caps its grid elsewhere: tests, measurements)
+constexpr int kLevelWaveSlots = 2048;
+constexpr int kLevelResidentWgs = kLevelWaveSlots / 4;
 // Executed fp64 operations per nominal cell of a level period that counted its steps (sdpgpu_stats_get): an exact step costs
 // ops_cell per cell; a screened step walks RS of the R rows -- RS S (3 or 2) + RS operations per lane and the table's S / 64
 // products, spread over the R S nominal cells (RS = R: ops_cell itself) --; a test is one compare per cell.  `screened` of the
@@ -174,6 +185,7 @@ struct PeriodInfo {
   int32_t lvl_screen_start = 0;  // the step screened level blocks started at in the last launch (0: the screen was off)
   int32_t lvl_r = 0, lvl_s = 0;  // the level launch's register block (R action rows x S levels per lane)
   bool lvl_future = false;       // the level launch had a future term
+  int32_t lvl_form = -1, lvl_wgs = 0, lvl_threads = 0;  // its launch form, workgroups and threads each (sdpgpu_f1_level_form_get)
   double pre_ops = 0;  // fp64 operations of the cut-off's pre-pass (Q(i, 0) of every state), in total
   // the decided split of the last launch: its boundary (live states [lo, dec_c), decided [dec_c, hi)) and the live launch's
   // chunk rows; -1: the launch did not split (sdpgpu_f1_decided_get; flush_pending makes two finalize jobs of a split period)
@@ -247,6 +259,10 @@ struct sdpgpu_handle {
   double f1_screen_mass = kF1ScreenMass;
   int f1_screen_rows = kF1ScreenRows;  // SDPGPU_F1_SCREEN_ROWS: action rows of a screened pass (1, 2 or 4 = all)
   int f1_step_group = kF1StepGroup;    // SDPGPU_F1_STEP_GROUP: cells a step of the level kernel takes together (1, 2 or 4)
+  int f1_level_form = kF1LevelForm;    // SDPGPU_F1_LEVEL_FORM: the launch form of the level kernel (0, 1 or 2)
+  int f1_level_wgs = kLevelResidentWgs;  // SDPGPU_F1_LEVEL_WGS: the most workgroups form 2 launches (diagnostic)
+  int f1_level_rounds = 1;             // SDPGPU_F1_LEVEL_ROUNDS: the round count plan_level's band search starts at (diagnostic)
+  unsigned* d_level_claim = nullptr;   // [T]: form 2's claim word of each period's level launch, zeroed before it
   // SDPGPU_F1_DECIDED=1: the decided split wherever the level kernel runs with the cut-off; unset or 0: never (opt-in:
   // f1_decided_on, sdpgpu_window.hip)
   int f1_decided = 0;

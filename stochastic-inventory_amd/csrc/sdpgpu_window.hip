@@ -200,8 +200,9 @@ static WinPlan plan_level(const sdpgpu_handle* h, int period, int64_t lo, int64_
   while (4 * sdp::level_wave_lds(band_max + S, R, S) <= kLdsLegacy) band_max += S;
   if (band_max < S) return pl;
   int band = band_max;
-  for (int64_t q = 1; q <= 64; ++q) {
-    const int64_t per_round = std::max<int64_t>(1, 2048 * q / nb);
+  // (SDPGPU_F1_LEVEL_ROUNDS, a diagnostic, starts the search at more rounds: finer tasks for the launch forms that claim them)
+  for (int64_t q = h->f1_level_rounds; q <= 64; ++q) {
+    const int64_t per_round = std::max<int64_t>(1, kLevelWaveSlots * q / nb);
     const int64_t want = ((ny + per_round - 1) / per_round + S - 1) / S * S;
     if (want <= band_max) {
       band = (int)want;
@@ -786,8 +787,8 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
       out_idx += hi - live_hi;
     }
     unsigned long long* k_cur = h->d_keys + (size_t)(period - 1) * h->key_stride;
-    if (!grid_ok((pl.n_tasks + 3) / 4)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((pl.n_tasks + 3) / 4));
+    const int64_t wgs4 = ((int64_t)pl.n_tasks + 3) / 4;
+    if (!grid_ok(wgs4)) return hipErrorInvalidValue;  // (every launch form: at most these work-items)
     bool launched = false;
     // THE CUT-OFF (sdp_window.hpp): once per period, MIN only, every term >= 0, and SDPGPU_F1_CUTOFF=0 turns it off
     const bool cut = f1_cutoff_on(h, period, lo, hi);
@@ -884,22 +885,52 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
     const int screen_rows = L.screen_start > 0 ? h->f1_screen_rows : pl.R;
     // THE STEP GROUPS (sdp_window.hpp): the order of a step's instructions and nothing else -- every launch form takes them
     const int step_group = h->f1_step_group;
-#define SDP_LVL_GO(RR, SS, FU, KI, CU, RS, SG)                                                                                 \
+    // THE LAUNCH FORMS (sdp_window.hpp): four tasks per workgroup; one wave per workgroup, its LDS one wave's; or no more
+    // workgroups than are resident at once, whose waves claim the tasks from the period's word of d_level_claim.  The
+    // claim loop costs the period-T instantiations that have three waves per SIMD -- no cut-off, or the cut-off with all R
+    // rows screened -- the third (profiles/f1_level_forms_resources.txt): where form 2 is asked for, they run as form 1.
+    L.form = h->f1_level_form;
+    if (L.form == 2 && !future && (!cut || screen_rows == pl.R)) L.form = 1;
+    const int64_t n_wgs = L.form == 1 ? pl.n_tasks : L.form == 2 ? std::min<int64_t>(wgs4, h->f1_level_wgs) : wgs4;
+    const dim3 grid((unsigned)n_wgs), block(L.form == 1 ? 64 : 256);
+    const size_t lvl_smem = L.form == 1 ? pl.smem / 4 : pl.smem;
+    unsigned* claim = nullptr;
+    if (L.form == 2) {
+      if (!h->d_level_claim) {
+        hipError_t e = hipMalloc((void**)&h->d_level_claim, (size_t)h->T * sizeof(unsigned));
+        if (e != hipSuccess) return e;
+      }
+      claim = h->d_level_claim + (period - 1);
+      hipError_t e = hipMemsetAsync(claim, 0, sizeof(unsigned), st);
+      if (e != hipSuccess) return e;
+    }
+    p.lvl_form = L.form;
+    p.lvl_wgs = (int32_t)n_wgs;
+    p.lvl_threads = (int32_t)block.x;
+#define SDP_LVL_GO(RR, SS, FU, KI, CU, RS, SG, CL)                                                                             \
   do {                                                                                                                         \
     static LdsMark mark;                                                                                                       \
-    hipError_t ea = lds_allow(sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS, SG>, pl.smem, &mark);                        \
+    hipError_t ea = lds_allow(sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS, SG, CL>, lvl_smem, &mark);                   \
     if (ea != hipSuccess) return ea;                                                                                           \
-    hipLaunchKernelGGL((sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS, SG>), grid, dim3(256), pl.smem, st, W, L, v_next,  \
-                       k_next, out_val, out_idx, k_cur, pmf_p, u_row, cut_count);                                              \
+    hipLaunchKernelGGL((sdp::window_f1_level_kernel<RR, SS, FU, KI, CU, RS, SG, CL>), grid, block, lvl_smem, st, W, L, v_next, \
+                       k_next, out_val, out_idx, k_cur, pmf_p, u_row, cut_count, claim);                                       \
+  } while (0)
+/* (form 2 never reaches the period-T instantiations it leaves to form 1, above: they have no claim loop) */
+#define SDP_LVL_F(RR, SS, FU, KI, CU, RS, SG)                                    \
+  do {                                                                           \
+    if (L.form == 2)                                                             \
+      SDP_LVL_GO(RR, SS, FU, KI, CU, RS, SG, ((FU) || ((CU) && (RS) < (RR))));   \
+    else                                                                         \
+      SDP_LVL_GO(RR, SS, FU, KI, CU, RS, SG, false);                             \
   } while (0)
 #define SDP_LVL_G(RR, SS, FU, KI, CU, RS)      \
   do {                                         \
     if (step_group == 4)                       \
-      SDP_LVL_GO(RR, SS, FU, KI, CU, RS, 4);   \
+      SDP_LVL_F(RR, SS, FU, KI, CU, RS, 4);    \
     else if (step_group == 2)                  \
-      SDP_LVL_GO(RR, SS, FU, KI, CU, RS, 2);   \
+      SDP_LVL_F(RR, SS, FU, KI, CU, RS, 2);    \
     else                                       \
-      SDP_LVL_GO(RR, SS, FU, KI, CU, RS, 1);   \
+      SDP_LVL_F(RR, SS, FU, KI, CU, RS, 1);    \
   } while (0)
 #define SDP_LVL_C(RR, SS, FU, KI)            \
   do {                                       \
@@ -926,6 +957,7 @@ hipError_t launch_window(sdpgpu_handle* h, const DevParams& P, int period, const
 #undef SDP_LVL_R
 #undef SDP_LVL_C
 #undef SDP_LVL_G
+#undef SDP_LVL_F
 #undef SDP_LVL_GO
     if (!launched) return hipErrorInvalidValue;
     hipError_t e = hipGetLastError();

@@ -598,6 +598,14 @@ class SdpEngine:
         self._check(self._lib.sdpgpu_f1_screen_rows_get(self._h, period, out))
         return tuple(int(v) for v in out)
 
+    def f1_level_form(self, period: int):
+        """The launch form of the F1 level kernel in `period` of the last solve: (form -- SDPGPU_F1_LEVEL_FORM: 0 four tasks per
+        workgroup, 1 one wave per workgroup, 2 waves that claim tasks --, workgroups launched, threads per workgroup); (the
+        handle's form, 0, 0) where the level kernel did not run the period."""
+        out = (C.c_int64 * 3)()
+        self._check(self._lib.sdpgpu_f1_level_form_get(self._h, period, out))
+        return tuple(int(v) for v in out)
+
     def f1_screen_start(self, period: int) -> int:
         """Host arithmetic: the step the screen's rule gives for the pmf of `period` (0: no screen)."""
         return int(self._lib.sdpgpu_f1_screen_start(self._h, period))
