@@ -20,40 +20,9 @@ from ._abi import SdpgpuBatchPlan, SdpgpuBatchStaffPlan, SdpgpuBatchStats, Sdpgp
 from .engine import _dp, _ip, split_pmf
 
 
-class SdpBatch:
-    """N independent problems on one GPU -- of one shape, or (ragged=True) each with its own bounds and order limit;
-    results per instance are those of N SdpEngines, bit for bit."""
-
-    def __init__(self, descs: Sequence[SdpgpuDesc], pmfs, ragged: bool = False, *, device: int = -1):
-        self._lib = _abi.load()
-        self._b = C.c_void_p()
-        descs = list(descs)
-        if len(descs) != len(pmfs):
-            raise ValueError(f"{len(descs)} descriptors but {len(pmfs)} pmfs")
-        arr = (SdpgpuDesc * max(len(descs), 1))()
-        for i, d in enumerate(descs):
-            C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(SdpgpuDesc))
-            if device >= 0:
-                arr[i].device = device
-        self.n = len(descs)
-        self.ragged = bool(ragged)
-        create = self._lib.sdpgpu_batch_create_ragged if self.ragged else self._lib.sdpgpu_batch_create
-        rc = create(arr, self.n, C.byref(self._b))
-        if rc:
-            raise SdpgpuError(rc, self._lib.sdpgpu_batch_last_error(None).decode())
-        self.T = int(arr[0].periods)
-        self.step = float(arr[0].step)
-        self.num_states = int((arr[0].max_inventory - arr[0].min_inventory) / arr[0].step) + 1  # (of instance 0)
-        try:
-            for i, pmf in enumerate(pmfs):
-                tiles = split_pmf(pmf)
-                if len(tiles) != self.T:
-                    raise ValueError(f"pmf of instance {i} has {len(tiles)} periods, the descriptors say {self.T}")
-                for t, (d, p) in enumerate(tiles):
-                    self._check(self._lib.sdpgpu_batch_set_pmf(self._b, i, t, _dp(d), _dp(p), len(d)))
-        except Exception:
-            self.close()
-            raise
+class _Batch:
+    """What the two kinds of batch share: one sdpgpu_batch (self._b) of self.n instances, its life time, its stream and timing,
+    the solve and the calls that read no table shape."""
 
     def _check(self, rc: int):
         if rc:
@@ -91,16 +60,68 @@ class SdpBatch:
     def synchronize(self):
         self._check(self._lib.sdpgpu_batch_synchronize(self._b))
 
-    def num_states_of(self, i: int) -> int:
-        """States of instance i's own grid."""
-        n = int(self._lib.sdpgpu_batch_num_states(self._b, i))
+    def num_actions_of(self, i: int) -> int:
+        """Actions of instance i (order quantities 0 .. maxOrderQuantity in steps; hires 0 .. maxHireNum)."""
+        n = int(self._lib.sdpgpu_batch_num_actions(self._b, i))
         if n < 0:
             raise IndexError(f"instance {i} outside 0 .. {self.n - 1}")
         return n
 
-    def num_actions_of(self, i: int) -> int:
-        """Actions (order quantities 0 .. maxOrderQuantity in steps) of instance i."""
-        n = int(self._lib.sdpgpu_batch_num_actions(self._b, i))
+    def initial(self):
+        """(values[n], action_index[n]): V_1 at every instance's initial state (ini_inventory_i; iniStaffNum) and its action
+        index (of a workforce batch: the hire count), all instances, one copy."""
+        val = np.empty(self.n, dtype=np.float64)
+        act = np.empty(self.n, dtype=np.int32)
+        self._check(self._lib.sdpgpu_batch_initial(self._b, _dp(val), _ip(act)))
+        return val, act
+
+    def stats(self) -> SdpgpuBatchStats:
+        st = SdpgpuBatchStats()
+        self._check(self._lib.sdpgpu_batch_stats_get(self._b, C.byref(st)))
+        return st
+
+    def period_ms(self, period: int) -> float:
+        return float(self._lib.sdpgpu_batch_period_ms(self._b, period))
+
+
+class SdpBatch(_Batch):
+    """N independent problems on one GPU -- of one shape, or (ragged=True) each with its own bounds and order limit;
+    results per instance are those of N SdpEngines, bit for bit."""
+
+    def __init__(self, descs: Sequence[SdpgpuDesc], pmfs, ragged: bool = False, *, device: int = -1):
+        self._lib = _abi.load()
+        self._b = C.c_void_p()
+        descs = list(descs)
+        if len(descs) != len(pmfs):
+            raise ValueError(f"{len(descs)} descriptors but {len(pmfs)} pmfs")
+        arr = (SdpgpuDesc * max(len(descs), 1))()
+        for i, d in enumerate(descs):
+            C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(SdpgpuDesc))
+            if device >= 0:
+                arr[i].device = device
+        self.n = len(descs)
+        self.ragged = bool(ragged)
+        create = self._lib.sdpgpu_batch_create_ragged if self.ragged else self._lib.sdpgpu_batch_create
+        rc = create(arr, self.n, C.byref(self._b))
+        if rc:
+            raise SdpgpuError(rc, self._lib.sdpgpu_batch_last_error(None).decode())
+        self.T = int(arr[0].periods)
+        self.step = float(arr[0].step)
+        self.num_states = int((arr[0].max_inventory - arr[0].min_inventory) / arr[0].step) + 1  # (of instance 0)
+        try:
+            for i, pmf in enumerate(pmfs):
+                tiles = split_pmf(pmf)
+                if len(tiles) != self.T:
+                    raise ValueError(f"pmf of instance {i} has {len(tiles)} periods, the descriptors say {self.T}")
+                for t, (d, p) in enumerate(tiles):
+                    self._check(self._lib.sdpgpu_batch_set_pmf(self._b, i, t, _dp(d), _dp(p), len(d)))
+        except Exception:
+            self.close()
+            raise
+
+    def num_states_of(self, i: int) -> int:
+        """States of instance i's own grid."""
+        n = int(self._lib.sdpgpu_batch_num_states(self._b, i))
         if n < 0:
             raise IndexError(f"instance {i} outside 0 .. {self.n - 1}")
         return n
@@ -121,21 +142,6 @@ class SdpBatch:
         out = np.empty(self.num_states_of(i), dtype=np.int32)
         self._check(self._lib.sdpgpu_batch_policy(self._b, i, period, _ip(out), len(out)))
         return out
-
-    def initial(self):
-        """(values[n], action_index[n]): V_1(ini_inventory_i) and its action index, all instances, one copy."""
-        val = np.empty(self.n, dtype=np.float64)
-        act = np.empty(self.n, dtype=np.int32)
-        self._check(self._lib.sdpgpu_batch_initial(self._b, _dp(val), _ip(act)))
-        return val, act
-
-    def stats(self) -> SdpgpuBatchStats:
-        st = SdpgpuBatchStats()
-        self._check(self._lib.sdpgpu_batch_stats_get(self._b, C.byref(st)))
-        return st
-
-    def period_ms(self, period: int) -> float:
-        return float(self._lib.sdpgpu_batch_period_ms(self._b, period))
 
     # ---- simulation of all instances (sdpgpu_batch_simulate*; Simulation.java:53-74 for the whole sweep) ----
     def _ini(self, ini_x):
@@ -282,7 +288,7 @@ class SdpBatch:
         return out
 
 
-class StaffBatch:
+class StaffBatch(_Batch):
     """N workforce (STAFF family) instances of ONE shape in the separable mode -- the sweep of WorkforceTesting.main
     (WorkforceTesting.java:36-41): period t of all instances in two kernel launches, every instance's tables bit for bit
     those of its own separable handle (SdpEngine with kernel = KERNEL_SEPARABLE).
@@ -336,53 +342,11 @@ class StaffBatch:
             self.close()
             raise
 
-    def _check(self, rc: int):
-        if rc:
-            raise SdpgpuError(rc, self._lib.sdpgpu_batch_last_error(self._b).decode())
-
-    def close(self):
-        if getattr(self, "_b", None) is not None and self._b:
-            self._lib.sdpgpu_batch_destroy(self._b)
-            self._b = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __len__(self):
-        return self.n
-
-    def set_stream(self, hip_stream: int):
-        self._check(self._lib.sdpgpu_batch_set_stream(self._b, C.c_void_p(hip_stream)))
-
-    def set_profiling(self, on: bool):
-        self._check(self._lib.sdpgpu_batch_set_profiling(self._b, 1 if on else 0))
-
-    def solve(self, sync: bool = True):
-        self._check(self._lib.sdpgpu_batch_solve(self._b, 1 if sync else 0))
-
-    def synchronize(self):
-        self._check(self._lib.sdpgpu_batch_synchronize(self._b))
-
     def grid(self, i: int, period: int):
         """(x_lo, nx): staff number of state index 0 and the number of states of instance i in `period` (1-based)."""
         x_lo, nx = C.c_double(), C.c_int64()
         self._check(self._lib.sdpgpu_batch_grid(self._b, i, period, C.byref(x_lo), C.byref(nx)))
         return float(x_lo.value), int(nx.value)
-
-    def num_actions_of(self, i: int) -> int:
-        n = int(self._lib.sdpgpu_batch_num_actions(self._b, i))
-        if n < 0:
-            raise IndexError(f"instance {i} outside 0 .. {self.n - 1}")
-        return n
 
     def plan(self, period: int) -> SdpgpuBatchStaffPlan:
         """The two launches of one period (1-based) for the whole batch: host arithmetic, no device needed."""
@@ -455,18 +419,3 @@ class StaffBatch:
         if want_demands:
             out.append(dem)
         return out[0] if len(out) == 1 else tuple(out)
-
-    def initial(self):
-        """(values[n], hires[n]): V_1(iniStaffNum) and its hire count, all instances, one copy."""
-        val = np.empty(self.n, dtype=np.float64)
-        act = np.empty(self.n, dtype=np.int32)
-        self._check(self._lib.sdpgpu_batch_initial(self._b, _dp(val), _ip(act)))
-        return val, act
-
-    def stats(self) -> SdpgpuBatchStats:
-        st = SdpgpuBatchStats()
-        self._check(self._lib.sdpgpu_batch_stats_get(self._b, C.byref(st)))
-        return st
-
-    def period_ms(self, period: int) -> float:
-        return float(self._lib.sdpgpu_batch_period_ms(self._b, period))

@@ -4,10 +4,12 @@
 // 810 instances with 27 order limits; sdpgpu_batch_create_ragged).  Period t of ALL instances runs in one launch of
 // window_f1_batch_kernel (sdp_batch.hpp); this file holds the validation, the host layout with its prefix-sum arenas, the
 // plan of a period, the task table, the launcher and the entry points.  Separate from sdpgpu_handle on purpose: a batch has no
-// slabs, no exchange, no user functors -- and the handle does not grow.
+// slabs, no exchange, no user functors -- and the handle does not grow.  What a batch of either family needs around a solve --
+// error text, stream, the timing events of a sweep, read-outs, the rollouts' scratch block -- is its BatchFrame
+// (sdpgpu_batch_frame.hpp).
 // A batch whose instance 0 is of the STAFF family (the workforce sweep in the separable mode) lives in sdpgpu_staffbatch.hip:
 // sdpgpu_batch_create makes it there, and every entry point below forwards to it or refuses by name.
-#include "sdpgpu_sim_host.hpp"
+#include "sdpgpu_batch_frame.hpp"
 #include "sdp_batch.hpp"
 #include "sdp_batch_sim.hpp"
 #include "sdp_fitss.hpp"
@@ -27,10 +29,11 @@ struct BatchPlan {
 };
 
 struct sdpgpu_batch {
+  sdpgpu_detail::BatchFrame f;     // error text, stream, events, staging and scratch blocks: of a staff batch too
   std::vector<sdpgpu_desc> d;
   int32_t N = 0, T = 0;
   // instance 0 of the STAFF family: the whole state of the batch lives in sdpgpu_staffbatch.hip, every entry point below forwards
-  // to it or refuses by name; N, T and err are the only other members in use
+  // to it or refuses by name; N, T and the frame are the only other members in use
   sdpgpu_detail::StaffBatch* staff = nullptr;
   bool ragged = false;             // sdpgpu_batch_create_ragged: bounds and order limit are the instance's own
   std::vector<int32_t> nxs, As;    // [i]: states and actions of instance i
@@ -40,7 +43,7 @@ struct sdpgpu_batch {
   std::vector<std::vector<double>> pmf_p;  // [i * T + t]
   std::vector<char> pmf_set;
   int win_r = 0, win_s = 0, win_nch = 0;   // SDPGPU_WIN_R / _S / _NCH, read at create time as for a handle
-  bool laid_out = false, allocated = false, solved = false, profiling = false;
+  bool laid_out = false, allocated = false, solved = false;
   std::vector<BatchPlan> plan;             // [t]
   std::vector<sdp::BatchInst> inst;        // [t * N + rank], longest demand first
   std::vector<size_t> pmf_off;             // [i * T + t]
@@ -52,9 +55,6 @@ struct sdpgpu_batch {
   std::vector<sdp::FinalizeJob> jobs;
   int64_t cells = 0;
   // device
-  int device = -1;
-  hipStream_t stream = nullptr;
-  bool own_stream = false, stream_given = false;
   double* d_values = nullptr;
   int32_t* d_policy = nullptr;
   double* d_pmf = nullptr;
@@ -65,10 +65,6 @@ struct sdpgpu_batch {
   int32_t* d_chunk_idx = nullptr;
   sdp::FinalizeJob* d_jobs = nullptr;
   int64_t* d_ini_off = nullptr;  // [2 N]: value and policy offsets of every instance's period-1 initial state
-  char* d_ini_out = nullptr;     // N doubles, then N int32
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<hipEvent_t> ev_period;  // [T + 1] when profiling
-  bool timed = false, periods_timed = false;
   int32_t period_launches = 0, finalize_launches = 0, periods_run = 0;
   // ---- simulation (sdp_batch_sim.hpp) ----
   sdpgpu_detail::SamplerSpecs samp;  // [i * T + t]: a distribution spec, or none = the pmf tile
@@ -76,10 +72,7 @@ struct sdpgpu_batch {
   sdp::SimSampler* d_samp = nullptr;
   double* d_thr = nullptr;
   sdp::SimInst* d_sim_inst = nullptr;  // [i], for the table rule and the level rules alike
-  char* d_sim_scratch = nullptr;  // grow-only: start states, wave partials, means, path sums, an explicit rule, demands
-  size_t sim_scratch_bytes = 0;
-  hipEvent_t sim_ev0 = nullptr, sim_ev1 = nullptr;
-  bool sim_timed = false;
+  bool sim_timed = false;  // (the frame's scratch block: start states, wave partials, means, path sums, an explicit rule, demands)
   // ---- (s, S) level rules (sdp_fitss.hpp) ----
   sdp::FitPair* d_fit_pairs = nullptr;  // [i * T + t]: the reachable slice of every (instance, period)
   double* d_fit = nullptr;              // the last device fit, N x T x 2*levels (sized for three levels)
@@ -87,19 +80,13 @@ struct sdpgpu_batch {
   double* d_gy = nullptr;               // the G rows, laid out as the policy rows; made on first request after a solve
   sdp::GyPair* d_gy_pairs = nullptr;    // [i * T + t]
   bool gy_valid = false;
-  std::string err;
 };
 
 int sdpgpu_detail::bfail(sdpgpu_batch* b, int code, const char* fmt, ...) {
-  char buf[640];
   va_list ap;
   va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
+  vfail_to(b ? &b->f.err : &g_create_error, code, fmt, ap);
   va_end(ap);
-  if (b)
-    b->err = buf;
-  else
-    g_create_error = buf;
   return code;
 }
 
@@ -119,11 +106,7 @@ using namespace sdpgpu_detail;
 #define STAFF_FORWARD(b, who, call) \
   if ((b)->staff) return guarded(b, who, [&]() -> int { return call; })
 
-#define BHIP_TRY(b, expr)                                                                              \
-  do {                                                                                                 \
-    hipError_t e_ = (expr);                                                                            \
-    if (e_ != hipSuccess) return bfail(b, SDPGPU_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
+#define BHIP_TRY(b, expr) SIM_TRY(b, expr)  // (reports through bfail: sim_fail of an sdpgpu_batch)
 
 inline int rup(int v, int r) { return (v + r - 1) / r * r; }
 
@@ -348,11 +331,7 @@ int allocate(sdpgpu_batch* b) {
   if (b->allocated) return SDPGPU_OK;
   int rc = layout(b);
   if (rc) return rc;
-  if ((rc = no_device(b, nullptr))) return rc;
-  if (!b->stream && !b->stream_given) {
-    BHIP_TRY(b, hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
-    b->own_stream = true;
-  }
+  if ((rc = b->f.open(b->N))) return rc;
   const int N = b->N, T = b->T;
   BHIP_TRY(b, hipMalloc((void**)&b->d_values, std::max<size_t>(b->values_elems, 1) * sizeof(double)));
   BHIP_TRY(b, hipMalloc((void**)&b->d_policy, std::max<size_t>(b->policy_elems, 1) * sizeof(int32_t)));
@@ -394,10 +373,7 @@ int allocate(sdpgpu_batch* b) {
     }
     BHIP_TRY(b, hipMalloc((void**)&b->d_ini_off, offs.size() * sizeof(int64_t)));
     BHIP_TRY(b, hipMemcpy(b->d_ini_off, offs.data(), offs.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-    BHIP_TRY(b, hipMalloc((void**)&b->d_ini_out, (size_t)N * 12));
   }
-  BHIP_TRY(b, hipEventCreate(&b->ev0));
-  BHIP_TRY(b, hipEventCreate(&b->ev1));
   b->allocated = true;
   return SDPGPU_OK;
 }
@@ -411,7 +387,7 @@ hipError_t launch_rs(sdpgpu_batch* b, const sdp::BatchLaunch& L, const BatchPlan
     static LdsMark mark;                                                                                             \
     hipError_t ea = lds_allow(sdp::window_f1_batch_kernel<R, S, FU, KI>, pl.smem, &mark);                            \
     if (ea != hipSuccess) return ea;                                                                                 \
-    hipLaunchKernelGGL((sdp::window_f1_batch_kernel<R, S, FU, KI>), grid, dim3(256), pl.smem, b->stream, L, inst,    \
+    hipLaunchKernelGGL((sdp::window_f1_batch_kernel<R, S, FU, KI>), grid, dim3(256), pl.smem, b->f.stream, L, inst,    \
                        tasks, b->d_values, b->d_policy, b->d_pmf, b->d_keys, b->d_chunk_val, b->d_chunk_idx);        \
   } while (0)
   if (!future)
@@ -476,22 +452,22 @@ int batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out, bool r
   if (n < 1 || n > 1000000) return bfail(nullptr, SDPGPU_ERR_ARG, "batch_create: n = %d instances (1 .. 1000000)", n);
   return guarded((sdpgpu_batch*)nullptr, "sdpgpu_batch_create", [&]() -> int {
     if (!ragged && descs[0].family == SDPGPU_FAMILY_STAFF) {  // the family of instance 0 selects the kind of batch
-      StaffBatch* sb = nullptr;
       std::string why;
-      const int rc = staff_batch_new(descs, n, &sb, &why);
-      g_create_error = why;
-      if (rc) return rc;
-      sdpgpu_batch* b = nullptr;
+      sdpgpu_batch* b = new sdpgpu_batch();  // (first: the staff batch works on its frame)
+      int rc = SDPGPU_OK;
       try {
-        b = new sdpgpu_batch();
+        rc = staff_batch_new(descs, n, &b->f, &b->staff, &why);
+        g_create_error = why;
       } catch (...) {
-        staff_batch_delete(sb);
+        delete b;
         throw;
       }
-      b->staff = sb;
+      if (rc) {
+        delete b;
+        return rc;
+      }
       b->N = n;
       b->T = descs[0].periods;
-      b->device = descs[0].device;
       *out = b;
       return SDPGPU_OK;
     }
@@ -554,7 +530,8 @@ int batch_create(const sdpgpu_desc* descs, int32_t n, sdpgpu_batch** out, bool r
         pb += (size_t)b->nxs[(size_t)k] * (size_t)d.periods;
       }
       b->sum_nx = (int64_t)sum_nx;
-      b->device = d.device;
+      b->f.device = d.device;
+      b->f.T = d.periods;
       b->d0.assign((size_t)n * b->T, 0.0);
       b->pmf_p.resize((size_t)n * b->T);
       b->pmf_set.assign((size_t)n * b->T, 0);
@@ -594,7 +571,7 @@ int32_t sdpgpu_batch_num_actions(const sdpgpu_batch* b, int32_t instance) {
 
 int sdpgpu_batch_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_plan* out) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_REFUSE(b, "sdpgpu_batch_plan_period");
   if (!out) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_plan_period: out is null");
   if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_plan_period: period %d outside 1 .. %d", period, b->T);
@@ -622,47 +599,17 @@ void sdpgpu_batch_destroy(sdpgpu_batch* b) {
     delete b;
     return;
   }
-  {
-    DeviceScope dev;
-    if (b->allocated || b->d_values || b->d_pmf) {
-      (void)dev.enter(b->device);
-      if (b->stream) (void)hipStreamSynchronize(b->stream);
-    }
-    if (b->ev0) (void)hipEventDestroy(b->ev0);
-    if (b->ev1) (void)hipEventDestroy(b->ev1);
-    for (hipEvent_t e : b->ev_period)
-      if (e) (void)hipEventDestroy(e);
-    if (b->d_values) (void)hipFree(b->d_values);
-    if (b->d_policy) (void)hipFree(b->d_policy);
-    if (b->d_pmf) (void)hipFree(b->d_pmf);
-    if (b->d_inst) (void)hipFree(b->d_inst);
-    if (b->d_tasks) (void)hipFree(b->d_tasks);
-    if (b->d_keys) (void)hipFree(b->d_keys);
-    if (b->d_chunk_val) (void)hipFree(b->d_chunk_val);
-    if (b->d_chunk_idx) (void)hipFree(b->d_chunk_idx);
-    if (b->d_jobs) (void)hipFree(b->d_jobs);
-    if (b->d_ini_off) (void)hipFree(b->d_ini_off);
-    if (b->d_ini_out) (void)hipFree(b->d_ini_out);
-    if (b->d_samp) (void)hipFree(b->d_samp);
-    if (b->d_thr) (void)hipFree(b->d_thr);
-    if (b->d_sim_inst) (void)hipFree(b->d_sim_inst);
-    if (b->d_sim_scratch) (void)hipFree(b->d_sim_scratch);
-    if (b->d_fit_pairs) (void)hipFree(b->d_fit_pairs);
-    if (b->d_fit) (void)hipFree(b->d_fit);
-    if (b->d_gy) (void)hipFree(b->d_gy);
-    if (b->d_gy_pairs) (void)hipFree(b->d_gy_pairs);
-    if (b->sim_ev0) (void)hipEventDestroy(b->sim_ev0);
-    if (b->sim_ev1) (void)hipEventDestroy(b->sim_ev1);
-    if (b->stream && b->own_stream) (void)hipStreamDestroy(b->stream);
-  }
+  b->f.close(b->allocated || b->d_values || b->d_pmf,
+             {b->d_values, b->d_policy, b->d_pmf, b->d_inst, b->d_tasks, b->d_keys, b->d_chunk_val, b->d_chunk_idx, b->d_jobs, b->d_ini_off,
+              b->d_samp, b->d_thr, b->d_sim_inst, b->d_fit_pairs, b->d_fit, b->d_gy, b->d_gy_pairs});
   delete b;
 }
 
-const char* sdpgpu_batch_last_error(const sdpgpu_batch* b) { return b ? b->err.c_str() : g_create_error.c_str(); }
+const char* sdpgpu_batch_last_error(const sdpgpu_batch* b) { return b ? b->f.err.c_str() : g_create_error.c_str(); }
 
 int sdpgpu_batch_set_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, const double* demand, const double* prob, int32_t n) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_REFUSE(b, "sdpgpu_batch_set_pmf");
   return guarded(b, "sdpgpu_batch_set_pmf", [&]() -> int {
     if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "batch_set_pmf: instance %d outside 0 .. %d", instance, b->N - 1);
@@ -693,152 +640,107 @@ int sdpgpu_batch_set_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, const dou
 
 int sdpgpu_batch_set_stream(sdpgpu_batch* b, void* hip_stream) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  STAFF_FORWARD(b, "sdpgpu_batch_set_stream", staff_batch_set_stream(b->staff, &b->err, hip_stream));
-  if (b->own_stream && b->stream) {
-    DeviceScope dev;
-    BHIP_TRY(b, dev.enter(b->device));
-    (void)hipStreamSynchronize(b->stream);
-    (void)hipStreamDestroy(b->stream);
-  }
-  b->stream = (hipStream_t)hip_stream;
-  b->own_stream = false;
-  b->stream_given = true;
-  return SDPGPU_OK;
+  b->f.err.clear();
+  return b->f.set_stream(hip_stream);
 }
 
 int sdpgpu_batch_set_profiling(sdpgpu_batch* b, int32_t on) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  if (b->staff) return staff_batch_set_profiling(b->staff, on);
-  b->profiling = on != 0;
+  b->f.err.clear();
+  b->f.profiling = on != 0;
   return SDPGPU_OK;
 }
 
 int sdpgpu_batch_solve(sdpgpu_batch* b, int32_t sync) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  STAFF_FORWARD(b, "sdpgpu_batch_solve", staff_batch_solve(b->staff, &b->err, sync));
+  b->f.err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_solve", staff_batch_solve(b->staff, sync));
   return guarded(b, "sdpgpu_batch_solve", [&]() -> int {
     int rc = layout(b);  // (argument and state errors before the device is touched)
     if (rc) return rc;
     DeviceScope dev;
-    BHIP_TRY(b, dev.enter(b->device));
+    BHIP_TRY(b, dev.enter(b->f.device));
     rc = allocate(b);
     if (rc) return rc;
-    const int T = b->T;
-    if (b->profiling && b->ev_period.empty()) {
-      b->ev_period.assign((size_t)T + 1, nullptr);
-      for (hipEvent_t& e : b->ev_period) BHIP_TRY(b, hipEventCreate(&e));
-    }
     b->period_launches = b->finalize_launches = b->periods_run = 0;
-    b->periods_timed = false;
     b->gy_valid = false;  // (the G rows are those of the tables about to be replaced)
-    BHIP_TRY(b, hipEventRecord(b->ev0, b->stream));
+    if ((rc = b->f.sweep_begin())) return rc;
     if (b->any_chunked) {  // key rows back to the reduction identity
       const int64_t nk = (int64_t)b->key_elems;
       if (!grid_ok((nk + 255) / 256)) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "key rows too long for one launch");
-      BHIP_TRY(b, launch_key_fill(b->d_keys, nk, (int)(b->d[0].direction == SDPGPU_MAX), b->stream));
+      BHIP_TRY(b, launch_key_fill(b->d_keys, nk, (int)(b->d[0].direction == SDPGPU_MAX), b->f.stream));
       b->finalize_launches++;
     }
-    for (int t = T - 1; t >= 0; --t) {
-      if (b->profiling) BHIP_TRY(b, hipEventRecord(b->ev_period[(size_t)t + 1], b->stream));
+    for (int t = b->T - 1; t >= 0; --t) {
+      if ((rc = b->f.period_mark(t))) return rc;
       hipError_t e = launch_period(b, t);
       if (e != hipSuccess) return bfail(b, SDPGPU_ERR_DEVICE, "batch period %d: %s", t + 1, hipGetErrorString(e));
       b->period_launches++;
       b->periods_run++;
     }
-    if (b->profiling) BHIP_TRY(b, hipEventRecord(b->ev_period[0], b->stream));
+    if ((rc = b->f.period_mark(-1))) return rc;
     if (b->any_chunked && b->total_final > 0) {  // V_t = unkey(K_t), policy = action of the lowest chunk that attains it: one launch
       if (!grid_ok((b->total_final + 255) / 256)) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "finalize pass too long for one launch");
-      BHIP_TRY(b, launch_finalize(b->d_jobs, (int)b->jobs.size(), b->total_final, b->stream));
+      BHIP_TRY(b, launch_finalize(b->d_jobs, (int)b->jobs.size(), b->total_final, b->f.stream));
       b->finalize_launches++;
     }
-    BHIP_TRY(b, hipEventRecord(b->ev1, b->stream));
-    b->timed = true;
-    b->periods_timed = b->profiling;
     b->solved = true;
-    if (sync) BHIP_TRY(b, hipStreamSynchronize(b->stream));
-    return SDPGPU_OK;
+    return b->f.sweep_end(sync != 0);
   });
 }
 
 int sdpgpu_batch_synchronize(sdpgpu_batch* b) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  STAFF_FORWARD(b, "sdpgpu_batch_synchronize", staff_batch_synchronize(b->staff, &b->err));
-  if (!b->allocated) return SDPGPU_OK;
-  DeviceScope dev;
-  BHIP_TRY(b, dev.enter(b->device));
-  BHIP_TRY(b, hipStreamSynchronize(b->stream));
-  return SDPGPU_OK;
+  b->f.err.clear();
+  return b->f.synchronize(b->staff ? staff_batch_allocated(b->staff) : b->allocated);
 }
 
 static int read_check(sdpgpu_batch* b, const char* who, int32_t instance, int32_t period, const void* out, int64_t n, bool is_values) {
-  if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, b->N - 1);
-  if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, b->T);
-  const int32_t nx = b->nxs[(size_t)instance];  // the instance's own count
-  if (!out || n < 0 || n > nx) return bfail(b, SDPGPU_ERR_ARG, "%s: bad output (n = %lld, the grid has %d states)", who, (long long)n, nx);
-  if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
-  if (is_values && !b->d[0].store_all_values && period > 2)
-    return bfail(b, SDPGPU_ERR_STATE, "%s: V_%d was overwritten (store_all_values = 0 keeps two ping-pong tables: periods 1 and 2 survive)", who, period);
-  return SDPGPU_OK;
+  const int32_t nx = instance >= 0 && instance < b->N ? b->nxs[(size_t)instance] : 0;  // the instance's own count
+  char states[64];
+  std::snprintf(states, sizeof states, "the grid has %d states", nx);
+  return read_check(&b->f, who, instance, b->N, period, out, n, nx, states, b->solved, false, is_values && !b->d[0].store_all_values);
 }
 
 int sdpgpu_batch_values(sdpgpu_batch* b, int32_t instance, int32_t period, double* out, int64_t n) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  STAFF_FORWARD(b, "sdpgpu_batch_values", staff_batch_values(b->staff, &b->err, instance, period, out, n));
+  b->f.err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_values", staff_batch_values(b->staff, instance, period, out, n));
   int rc = read_check(b, "sdpgpu_batch_values", instance, period, out, n, true);
   if (rc) return rc;
-  DeviceScope dev;
-  BHIP_TRY(b, dev.enter(b->device));
-  BHIP_TRY(b, hipStreamSynchronize(b->stream));
-  BHIP_TRY(b, hipMemcpy(out, b->d_values + value_row(b, instance, period - 1), (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  return SDPGPU_OK;
+  return b->f.read_row(out, b->d_values + value_row(b, instance, period - 1), (size_t)n * sizeof(double));
 }
 
 int sdpgpu_batch_policy(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* out, int64_t n) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  STAFF_FORWARD(b, "sdpgpu_batch_policy", staff_batch_policy(b->staff, &b->err, instance, period, out, n));
+  b->f.err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_policy", staff_batch_policy(b->staff, instance, period, out, n));
   int rc = read_check(b, "sdpgpu_batch_policy", instance, period, out, n, false);
   if (rc) return rc;
-  DeviceScope dev;
-  BHIP_TRY(b, dev.enter(b->device));
-  BHIP_TRY(b, hipStreamSynchronize(b->stream));
-  BHIP_TRY(b, hipMemcpy(out, b->d_policy + policy_row(b, instance, period - 1), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return SDPGPU_OK;
+  return b->f.read_row(out, b->d_policy + policy_row(b, instance, period - 1), (size_t)n * sizeof(int32_t));
 }
 
 int sdpgpu_batch_initial(sdpgpu_batch* b, double* out_value, int32_t* out_action_index) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  STAFF_FORWARD(b, "sdpgpu_batch_initial", staff_batch_initial(b->staff, &b->err, out_value, out_action_index));
+  b->f.err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_initial", staff_batch_initial(b->staff, out_value, out_action_index));
   if (!out_value || !out_action_index) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_initial: null output");
   if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "sdpgpu_batch_initial before sdpgpu_batch_solve");
   return guarded(b, "sdpgpu_batch_initial", [&]() -> int {
     DeviceScope dev;
-    BHIP_TRY(b, dev.enter(b->device));
+    BHIP_TRY(b, dev.enter(b->f.device));
     const int N = b->N;
-    double* dv = reinterpret_cast<double*>(b->d_ini_out);
-    int32_t* di = reinterpret_cast<int32_t*>(b->d_ini_out + (size_t)N * 8);
-    hipLaunchKernelGGL(sdp::batch_initial_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, b->d_values, b->d_policy,
-                       b->d_ini_off, b->d_ini_off + N, N, dv, di);
+    hipLaunchKernelGGL(sdp::batch_initial_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->f.stream, b->d_values, b->d_policy,
+                       b->d_ini_off, b->d_ini_off + N, N, b->f.ini_value(), b->f.ini_action(N));
     BHIP_TRY(b, hipGetLastError());
-    std::vector<char> host((size_t)N * 12);
-    BHIP_TRY(b, hipMemcpyAsync(host.data(), b->d_ini_out, host.size(), hipMemcpyDeviceToHost, b->stream));
-    BHIP_TRY(b, hipStreamSynchronize(b->stream));
-    std::memcpy(out_value, host.data(), (size_t)N * 8);
-    std::memcpy(out_action_index, host.data() + (size_t)N * 8, (size_t)N * 4);
-    return SDPGPU_OK;
+    return b->f.initial_download(out_value, out_action_index, N);
   });
 }
 
 int sdpgpu_batch_stats_get(sdpgpu_batch* b, sdpgpu_batch_stats* out) {
   if (!b || !out) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  STAFF_FORWARD(b, "sdpgpu_batch_stats_get", staff_batch_stats(b->staff, &b->err, out));
+  b->f.err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_stats_get", staff_batch_stats(b->staff, out));
   return guarded(b, "sdpgpu_batch_stats_get", [&]() -> int {
     std::memset(out, 0, sizeof *out);
     out->instances = b->N;
@@ -858,63 +760,44 @@ int sdpgpu_batch_stats_get(sdpgpu_batch* b, sdpgpu_batch_stats* out) {
       }
       out->cells_evaluated = b->solved ? b->cells : 0;
     }
-    if (b->timed) {
-      DeviceScope dev;
-      BHIP_TRY(b, dev.enter(b->device));
-      BHIP_TRY(b, hipEventSynchronize(b->ev1));
-      float ms = 0;
-      BHIP_TRY(b, hipEventElapsedTime(&ms, b->ev0, b->ev1));
-      out->solve_ms = ms;
-    }
-    return SDPGPU_OK;
+    return b->f.solve_ms(&out->solve_ms);
   });
 }
 
 double sdpgpu_batch_period_ms(sdpgpu_batch* b, int32_t period) {
   if (!b) return -1.0;
-  b->err.clear();
-  if (b->staff) return staff_batch_period_ms(b->staff, &b->err, period);
-  if (period < 1 || period > b->T || !b->periods_timed) {
-    (void)bfail(b, SDPGPU_ERR_STATE, "sdpgpu_batch_period_ms: period %d has no timing (sdpgpu_batch_set_profiling before the solve)", period);
-    return -1.0;
-  }
-  DeviceScope dev;
-  if (dev.enter(b->device) != hipSuccess) return -1.0;
-  // period t was launched between the events t and t - 1 (the sweep runs t = T .. 1)
-  if (hipEventSynchronize(b->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, b->ev_period[(size_t)period], b->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
-  return ms;
+  b->f.err.clear();
+  return b->f.period_ms(period);
 }
 
 // ---- the staff batch's own calls (sdpgpu_staffbatch.hip) ----
 int sdpgpu_batch_add_level_pmf(sdpgpu_batch* b, const double* prob, const int32_t* row_len, int32_t n_rows, int32_t row_stride,
                                int32_t* out_table) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_ONLY(b, "sdpgpu_batch_add_level_pmf");
   return guarded(b, "sdpgpu_batch_add_level_pmf",
-                 [&]() -> int { return staff_batch_add_table(b->staff, &b->err, prob, row_len, n_rows, row_stride, out_table); });
+                 [&]() -> int { return staff_batch_add_table(b->staff, prob, row_len, n_rows, row_stride, out_table); });
 }
 
 int sdpgpu_batch_use_level_pmf(sdpgpu_batch* b, int32_t instance, int32_t t, int32_t table) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_ONLY(b, "sdpgpu_batch_use_level_pmf");
-  return guarded(b, "sdpgpu_batch_use_level_pmf", [&]() -> int { return staff_batch_use_table(b->staff, &b->err, instance, t, table); });
+  return guarded(b, "sdpgpu_batch_use_level_pmf", [&]() -> int { return staff_batch_use_table(b->staff, instance, t, table); });
 }
 
 int sdpgpu_batch_set_overhead(sdpgpu_batch* b, int32_t instance, int32_t t, double min_staff) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_ONLY(b, "sdpgpu_batch_set_overhead");
-  return guarded(b, "sdpgpu_batch_set_overhead", [&]() -> int { return staff_batch_set_min_staff(b->staff, &b->err, instance, t, min_staff); });
+  return guarded(b, "sdpgpu_batch_set_overhead", [&]() -> int { return staff_batch_set_min_staff(b->staff, instance, t, min_staff); });
 }
 
 int sdpgpu_batch_grid(sdpgpu_batch* b, int32_t instance, int32_t period, double* x_lo, int64_t* nx) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
-  STAFF_FORWARD(b, "sdpgpu_batch_grid", staff_batch_grid(b->staff, &b->err, instance, period, x_lo, nx));
+  b->f.err.clear();
+  STAFF_FORWARD(b, "sdpgpu_batch_grid", staff_batch_grid(b->staff, instance, period, x_lo, nx));
   if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: instance %d outside 0 .. %d", instance, b->N - 1);
   if (period < 1 || period > b->T) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: period %d outside 1 .. %d", period, b->T);
   if (!x_lo || !nx) return bfail(b, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: null output");
@@ -925,32 +808,32 @@ int sdpgpu_batch_grid(sdpgpu_batch* b, int32_t instance, int32_t period, double*
 
 int sdpgpu_batch_staff_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_staff_plan* out) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_ONLY(b, "sdpgpu_batch_staff_plan_period");
-  return guarded(b, "sdpgpu_batch_staff_plan_period", [&]() -> int { return staff_batch_plan(b->staff, &b->err, period, out); });
+  return guarded(b, "sdpgpu_batch_staff_plan_period", [&]() -> int { return staff_batch_plan(b->staff, period, out); });
 }
 
 int sdpgpu_batch_staff_reachable(sdpgpu_batch* b, int32_t instance, int32_t period, int64_t* lo, int64_t* hi) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_ONLY(b, "sdpgpu_batch_staff_reachable");
-  return guarded(b, "sdpgpu_batch_staff_reachable", [&]() -> int { return staff_batch_reachable(b->staff, &b->err, instance, period, lo, hi); });
+  return guarded(b, "sdpgpu_batch_staff_reachable", [&]() -> int { return staff_batch_reachable(b->staff, instance, period, lo, hi); });
 }
 
 int sdpgpu_batch_staff_fit_ss(sdpgpu_batch* b, double max_order_quantity, double* out) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_ONLY(b, "sdpgpu_batch_staff_fit_ss");
-  return guarded(b, "sdpgpu_batch_staff_fit_ss", [&]() -> int { return staff_batch_fit_ss(b->staff, &b->err, max_order_quantity, out); });
+  return guarded(b, "sdpgpu_batch_staff_fit_ss", [&]() -> int { return staff_batch_fit_ss(b->staff, max_order_quantity, out); });
 }
 
 int sdpgpu_batch_staff_simulate(sdpgpu_batch* b, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss, int32_t n_rules,
                                 sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid, int32_t* out_demand) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_ONLY(b, "sdpgpu_batch_staff_simulate");
   return guarded(b, "sdpgpu_batch_staff_simulate", [&]() -> int {
-    return staff_batch_simulate(b->staff, &b->err, sample_nums, seed, ini_x, ss, n_rules, results, out_sum, out_valid, out_demand);
+    return staff_batch_simulate(b->staff, sample_nums, seed, ini_x, ss, n_rules, results, out_sum, out_valid, out_demand);
   });
 }
 
@@ -1043,7 +926,7 @@ extern "C" {
 
 int sdpgpu_batch_set_sampler(sdpgpu_batch* b, int32_t instance, int32_t t, const sdpgpu_dist_spec* spec) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_REFUSE(b, "sdpgpu_batch_set_sampler");
   return guarded(b, "sdpgpu_batch_set_sampler", [&]() -> int {
     if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "batch_set_sampler: instance %d outside 0 .. %d", instance, b->N - 1);
@@ -1065,7 +948,7 @@ int sdpgpu_batch_set_sampler(sdpgpu_batch* b, int32_t instance, int32_t t, const
 
 int sdpgpu_batch_sample_demands(sdpgpu_batch* b, int32_t instance, int32_t n_paths, uint64_t seed, double* out_demand, double* out_u) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_REFUSE(b, "sdpgpu_batch_sample_demands");
   return guarded(b, "sdpgpu_batch_sample_demands", [&]() -> int {
     const char* who = "sdpgpu_batch_sample_demands";
@@ -1078,7 +961,7 @@ int sdpgpu_batch_sample_demands(sdpgpu_batch* b, int32_t instance, int32_t n_pat
     rc = layout(b);  // (every pmf set: the tile samplers read them)
     if (rc) return rc;
     DeviceScope dev;
-    BHIP_TRY(b, dev.enter(b->device));
+    BHIP_TRY(b, dev.enter(b->f.device));
     rc = allocate(b);
     if (rc) return rc;
     rc = sim_upload_samplers(b);
@@ -1086,24 +969,24 @@ int sdpgpu_batch_sample_demands(sdpgpu_batch* b, int32_t instance, int32_t n_pat
     const size_t elems = (size_t)n_paths * b->T;
     Carve c;
     const size_t o_dem = c.take(elems * 8), o_u = c.take(out_u ? elems * 8 : 0);
-    rc = sim_scratch(b, c.at);
+    rc = sim_scratch(&b->f, c.at);
     if (rc) return rc;
-    double* d_dem = reinterpret_cast<double*>(b->d_sim_scratch + o_dem);
-    double* d_u = out_u ? reinterpret_cast<double*>(b->d_sim_scratch + o_u) : nullptr;
+    double* d_dem = reinterpret_cast<double*>(b->f.d_sim_scratch + o_dem);
+    double* d_u = out_u ? reinterpret_cast<double*>(b->f.d_sim_scratch + o_u) : nullptr;
     const sdp::SimLaunch L = sim_launch_params(b, n_paths, seed, 0);
-    hipLaunchKernelGGL(sdp::batch_sim_draw_kernel, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, b->stream, L, (int)instance, b->d_samp,
+    hipLaunchKernelGGL(sdp::batch_sim_draw_kernel, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, b->f.stream, L, (int)instance, b->d_samp,
                        b->d_thr, d_dem, d_u);
     BHIP_TRY(b, hipGetLastError());
-    BHIP_TRY(b, hipMemcpyAsync(out_demand, d_dem, elems * 8, hipMemcpyDeviceToHost, b->stream));
-    if (out_u) BHIP_TRY(b, hipMemcpyAsync(out_u, d_u, elems * 8, hipMemcpyDeviceToHost, b->stream));
-    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(out_demand, d_dem, elems * 8, hipMemcpyDeviceToHost, b->f.stream));
+    if (out_u) BHIP_TRY(b, hipMemcpyAsync(out_u, d_u, elems * 8, hipMemcpyDeviceToHost, b->f.stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->f.stream));
     return SDPGPU_OK;
   });
 }
 
 double sdpgpu_batch_simulate_ms(sdpgpu_batch* b) {
   if (!b) return -1.0;
-  b->err.clear();
+  b->f.err.clear();
   if (b->staff) {
     (void)bfail(b, SDPGPU_ERR_UNSUPPORTED, "sdpgpu_batch_simulate_ms: not available on a batch of the staff family (SDPGPU_FAMILY_STAFF)");
     return -1.0;
@@ -1113,10 +996,10 @@ double sdpgpu_batch_simulate_ms(sdpgpu_batch* b) {
     return -1.0;
   }
   DeviceScope dev;
-  if (dev.enter(b->device) != hipSuccess) return -1.0;
-  if (hipEventSynchronize(b->sim_ev1) != hipSuccess) return -1.0;
+  if (dev.enter(b->f.device) != hipSuccess) return -1.0;
+  if (hipEventSynchronize(b->f.sim_ev1) != hipSuccess) return -1.0;
   float ms = 0;
-  if (hipEventElapsedTime(&ms, b->sim_ev0, b->sim_ev1) != hipSuccess) return -1.0;
+  if (hipEventElapsedTime(&ms, b->f.sim_ev0, b->f.sim_ev1) != hipSuccess) return -1.0;
   return ms;
 }
 
@@ -1209,11 +1092,11 @@ int fit_launch(sdpgpu_batch* b, const char* who, int32_t levels) {
   const dim3 grid((unsigned)((n_pairs + 255) / 256));
   const double step = b->d[0].step;
   if (levels == 1)
-    hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<1>), grid, dim3(256), 0, b->stream, b->d_fit_pairs, n_pairs, b->T, step, b->d_policy, b->d_fit);
+    hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<1>), grid, dim3(256), 0, b->f.stream, b->d_fit_pairs, n_pairs, b->T, step, b->d_policy, b->d_fit);
   else if (levels == 2)
-    hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<2>), grid, dim3(256), 0, b->stream, b->d_fit_pairs, n_pairs, b->T, step, b->d_policy, b->d_fit);
+    hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<2>), grid, dim3(256), 0, b->f.stream, b->d_fit_pairs, n_pairs, b->T, step, b->d_policy, b->d_fit);
   else
-    hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<3>), grid, dim3(256), 0, b->stream, b->d_fit_pairs, n_pairs, b->T, step, b->d_policy, b->d_fit);
+    hipLaunchKernelGGL((sdp::batch_fit_ss_kernel<3>), grid, dim3(256), 0, b->f.stream, b->d_fit_pairs, n_pairs, b->T, step, b->d_policy, b->d_fit);
   BHIP_TRY(b, hipGetLastError());
   return SDPGPU_OK;
 }
@@ -1230,7 +1113,7 @@ extern "C" {
 
 int sdpgpu_batch_reachable(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t* lo, int32_t* hi) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_REFUSE(b, "sdpgpu_batch_reachable");
   const char* who = "sdpgpu_batch_reachable";
   if (instance < 0 || instance >= b->N) return bfail(b, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, b->N - 1);
@@ -1275,7 +1158,7 @@ int sdpgpu_fit_min_square(double max_order_quantity, double lb, int32_t up_index
 
 int sdpgpu_batch_fit_ss(sdpgpu_batch* b, int32_t levels, double* out) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_REFUSE(b, "sdpgpu_batch_fit_ss");
   return guarded(b, "sdpgpu_batch_fit_ss", [&]() -> int {
     const char* who = "sdpgpu_batch_fit_ss";
@@ -1285,11 +1168,11 @@ int sdpgpu_batch_fit_ss(sdpgpu_batch* b, int32_t levels, double* out) {
     if (rc) return rc;
     if (!b->solved) return bfail(b, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
     DeviceScope dev;
-    BHIP_TRY(b, dev.enter(b->device));
+    BHIP_TRY(b, dev.enter(b->f.device));
     rc = fit_launch(b, who, levels);
     if (rc) return rc;
-    BHIP_TRY(b, hipMemcpyAsync(out, b->d_fit, (size_t)b->N * b->T * 2 * levels * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipMemcpyAsync(out, b->d_fit, (size_t)b->N * b->T * 2 * levels * sizeof(double), hipMemcpyDeviceToHost, b->f.stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->f.stream));
     return SDPGPU_OK;
   });
 }
@@ -1313,10 +1196,10 @@ template <class RULE>
 void sim_launch(sdpgpu_batch* b, bool sampled, dim3 grid, const sdp::SimLaunch& L, const double* d_ini, RULE rule, const double* d_dem,
                 double* d_part, double* d_sum) {
   if (sampled)
-    hipLaunchKernelGGL((sdp::batch_sim_kernel<RULE, true>), grid, dim3(256), 0, b->stream, L, b->d_sim_inst, d_ini, rule, nullptr, b->d_samp,
+    hipLaunchKernelGGL((sdp::batch_sim_kernel<RULE, true>), grid, dim3(256), 0, b->f.stream, L, b->d_sim_inst, d_ini, rule, nullptr, b->d_samp,
                        b->d_thr, d_part, d_sum);
   else
-    hipLaunchKernelGGL((sdp::batch_sim_kernel<RULE, false>), grid, dim3(256), 0, b->stream, L, b->d_sim_inst, d_ini, rule, d_dem, nullptr,
+    hipLaunchKernelGGL((sdp::batch_sim_kernel<RULE, false>), grid, dim3(256), 0, b->f.stream, L, b->d_sim_inst, d_ini, rule, d_dem, nullptr,
                        nullptr, d_part, d_sum);
 }
 
@@ -1345,7 +1228,7 @@ int sim_run(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, con
     return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: %d instances x %d paths are too many for one launch", who, N, n_paths);
 
   DeviceScope dev;
-  BHIP_TRY(b, dev.enter(b->device));
+  BHIP_TRY(b, dev.enter(b->f.device));
   rc = allocate(b);
   if (rc) return rc;
   if (!b->d_sim_inst) {
@@ -1358,9 +1241,9 @@ int sim_run(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, con
     BHIP_TRY(b, hipMalloc((void**)&b->d_sim_inst, inst.size() * sizeof(sdp::SimInst)));
     BHIP_TRY(b, hipMemcpy(b->d_sim_inst, inst.data(), inst.size() * sizeof(sdp::SimInst), hipMemcpyHostToDevice));
   }
-  if (!b->sim_ev0) {
-    BHIP_TRY(b, hipEventCreate(&b->sim_ev0));
-    BHIP_TRY(b, hipEventCreate(&b->sim_ev1));
+  if (!b->f.sim_ev0) {
+    BHIP_TRY(b, hipEventCreate(&b->f.sim_ev0));
+    BHIP_TRY(b, hipEventCreate(&b->f.sim_ev1));
   }
   if (sampled && (rc = sim_upload_samplers(b))) return rc;
   const size_t ss_elems = rule.ss ? (size_t)N * T * 2 * levels : 0;
@@ -1369,21 +1252,21 @@ int sim_run(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, con
   Carve c;
   const size_t o_ini = c.take((size_t)N * 8), o_part = c.take((size_t)waves * 8), o_mean = c.take((size_t)N * 8);
   const size_t o_sum = c.take(sum_bytes), o_ss = c.take(ss_elems * 8), o_dem = c.take(dem_elems * 8);
-  rc = sim_scratch(b, c.at);
+  rc = sim_scratch(&b->f, c.at);
   if (rc) return rc;
-  char* base = b->d_sim_scratch;
+  char* base = b->f.d_sim_scratch;
   double* d_ini = reinterpret_cast<double*>(base + o_ini);
   double* d_part = reinterpret_cast<double*>(base + o_part);
   double* d_mean = reinterpret_cast<double*>(base + o_mean);
   double* d_sum = out_sum ? reinterpret_cast<double*>(base + o_sum) : nullptr;
   const double* d_rule = reinterpret_cast<double*>(base + o_ss);
   double* d_dem = sampled ? nullptr : reinterpret_cast<double*>(base + o_dem);
-  BHIP_TRY(b, hipMemcpyAsync(d_ini, ini.data(), (size_t)N * 8, hipMemcpyHostToDevice, b->stream));
-  if (rule.ss) BHIP_TRY(b, hipMemcpyAsync(base + o_ss, rule.ss, ss_elems * 8, hipMemcpyHostToDevice, b->stream));
-  if (!sampled) BHIP_TRY(b, hipMemcpyAsync(d_dem, demand, dem_elems * 8, hipMemcpyHostToDevice, b->stream));
+  BHIP_TRY(b, hipMemcpyAsync(d_ini, ini.data(), (size_t)N * 8, hipMemcpyHostToDevice, b->f.stream));
+  if (rule.ss) BHIP_TRY(b, hipMemcpyAsync(base + o_ss, rule.ss, ss_elems * 8, hipMemcpyHostToDevice, b->f.stream));
+  if (!sampled) BHIP_TRY(b, hipMemcpyAsync(d_dem, demand, dem_elems * 8, hipMemcpyHostToDevice, b->f.stream));
   const sdp::SimLaunch L = sim_launch_params(b, n_paths, seed, stride);
   const dim3 grid((unsigned)((waves + 3) / 4));
-  BHIP_TRY(b, hipEventRecord(b->sim_ev0, b->stream));
+  BHIP_TRY(b, hipEventRecord(b->f.sim_ev0, b->f.stream));
   if (!rule.table && !rule.ss) {
     rc = fit_launch(b, who, levels);
     if (rc) return rc;
@@ -1398,13 +1281,13 @@ int sim_run(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, con
   else
     sim_launch(b, sampled, grid, L, d_ini, sdp::LevelRule<3>{d_rule}, d_dem, d_part, d_sum);
   BHIP_TRY(b, hipGetLastError());
-  hipLaunchKernelGGL(sdp::batch_sim_mean_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->stream, d_part, N, (int)wpi, n_paths, d_mean);
+  hipLaunchKernelGGL(sdp::batch_sim_mean_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, b->f.stream, d_part, N, (int)wpi, n_paths, d_mean);
   BHIP_TRY(b, hipGetLastError());
-  BHIP_TRY(b, hipEventRecord(b->sim_ev1, b->stream));
+  BHIP_TRY(b, hipEventRecord(b->f.sim_ev1, b->f.stream));
   b->sim_timed = true;
-  BHIP_TRY(b, hipMemcpyAsync(out_mean, d_mean, (size_t)N * 8, hipMemcpyDeviceToHost, b->stream));
-  if (out_sum) BHIP_TRY(b, hipMemcpyAsync(out_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost, b->stream));
-  BHIP_TRY(b, hipStreamSynchronize(b->stream));
+  BHIP_TRY(b, hipMemcpyAsync(out_mean, d_mean, (size_t)N * 8, hipMemcpyDeviceToHost, b->f.stream));
+  if (out_sum) BHIP_TRY(b, hipMemcpyAsync(out_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost, b->f.stream));
+  BHIP_TRY(b, hipStreamSynchronize(b->f.stream));
   return SDPGPU_OK;
 }
 
@@ -1412,7 +1295,7 @@ int sim_run(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, con
 int sim_entry(sdpgpu_batch* b, const char* who, SimRule rule, int32_t n_paths, const double* demand, int64_t stride, bool sampled, uint64_t seed,
               const double* ini_x, double* out_mean, double* out_sum) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   if (b->staff)
     return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: not available on a batch of the staff family (SDPGPU_FAMILY_STAFF): a hiring rule is rolled out on a "
                  "sampled tree (sdpgpu_batch_staff_simulate)", who);
@@ -1486,7 +1369,7 @@ int gy_fill(sdpgpu_batch* b) {
   if (!b->d_gy) BHIP_TRY(b, hipMalloc((void**)&b->d_gy, std::max<size_t>(b->policy_elems, 1) * sizeof(double)));
   if (!grid_ok((int64_t)N * T)) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "G rows: %d instances x %d periods are too many for one launch", N, T);
   const double step = b->d[0].step;
-  hipLaunchKernelGGL(sdp::gy_kernel, dim3((unsigned)(N * T)), dim3(256), 0, b->stream, b->d_gy_pairs, step, 1.0 / step, b->d_pmf, b->d_values,
+  hipLaunchKernelGGL(sdp::gy_kernel, dim3((unsigned)(N * T)), dim3(256), 0, b->f.stream, b->d_gy_pairs, step, 1.0 / step, b->d_pmf, b->d_values,
                      b->d_gy);
   BHIP_TRY(b, hipGetLastError());
   b->gy_valid = true;
@@ -1559,37 +1442,37 @@ int batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t
   if (tasks.size() > (size_t)INT32_MAX / 2) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: too many tasks in one launch", who);
 
   DeviceScope dev;
-  BHIP_TRY(b, dev.enter(b->device));
+  BHIP_TRY(b, dev.enter(b->f.device));
   if (source == 1 && (rc = gy_fill(b))) return rc;
   const double* base = source == 0 ? b->d_values : b->d_gy;
   for (int i = 0; i < N; ++i) rows[(size_t)i].g = base + row_off[(size_t)i];
   Carve c;
   const size_t o_rows = c.take(rows.size() * sizeof(sdp::ConvexityRow)), o_tasks = c.take(std::max<size_t>(tasks.size(), 1) * sizeof(sdp::ConvexityTask));
   const size_t o_keys = c.take((size_t)N * 8), o_out = c.take((size_t)N * sizeof(sdp::ConvexityOut));
-  rc = sim_scratch(b, c.at);
+  rc = sim_scratch(&b->f, c.at);
   if (rc) return rc;
-  char* sb = b->d_sim_scratch;
+  char* sb = b->f.d_sim_scratch;
   sdp::ConvexityRow* d_rows = reinterpret_cast<sdp::ConvexityRow*>(sb + o_rows);
   sdp::ConvexityTask* d_tasks = reinterpret_cast<sdp::ConvexityTask*>(sb + o_tasks);
   unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(sb + o_keys);
   sdp::ConvexityOut* d_out = reinterpret_cast<sdp::ConvexityOut*>(sb + o_out);
-  BHIP_TRY(b, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(sdp::ConvexityRow), hipMemcpyHostToDevice, b->stream));
-  if (!tasks.empty()) BHIP_TRY(b, hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(sdp::ConvexityTask), hipMemcpyHostToDevice, b->stream));
+  BHIP_TRY(b, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(sdp::ConvexityRow), hipMemcpyHostToDevice, b->f.stream));
+  if (!tasks.empty()) BHIP_TRY(b, hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(sdp::ConvexityTask), hipMemcpyHostToDevice, b->f.stream));
   const dim3 per_row((unsigned)((N + 255) / 256));
-  hipLaunchKernelGGL(sdp::convexity_key_fill_kernel, per_row, dim3(256), 0, b->stream, d_keys, N);
+  hipLaunchKernelGGL(sdp::convexity_key_fill_kernel, per_row, dim3(256), 0, b->f.stream, d_keys, N);
   BHIP_TRY(b, hipGetLastError());
   if (!tasks.empty()) {
     static LdsMark mark;
     const size_t smem = sdp::convexity_lds(n_max);
     BHIP_TRY(b, lds_allow(sdp::convexity_kernel, smem, &mark));
-    hipLaunchKernelGGL(sdp::convexity_kernel, dim3((unsigned)tasks.size()), dim3(256), smem, b->stream, d_rows, d_tasks, d_keys);
+    hipLaunchKernelGGL(sdp::convexity_kernel, dim3((unsigned)tasks.size()), dim3(256), smem, b->f.stream, d_rows, d_tasks, d_keys);
     BHIP_TRY(b, hipGetLastError());
   }
-  hipLaunchKernelGGL(sdp::convexity_finish_kernel, per_row, dim3(256), 0, b->stream, d_rows, d_keys, N, d_out);
+  hipLaunchKernelGGL(sdp::convexity_finish_kernel, per_row, dim3(256), 0, b->f.stream, d_rows, d_keys, N, d_out);
   BHIP_TRY(b, hipGetLastError());
   std::vector<sdp::ConvexityOut> host((size_t)N);  // (out is written only once everything has succeeded)
-  BHIP_TRY(b, hipMemcpyAsync(host.data(), d_out, host.size() * sizeof(sdp::ConvexityOut), hipMemcpyDeviceToHost, b->stream));
-  BHIP_TRY(b, hipStreamSynchronize(b->stream));
+  BHIP_TRY(b, hipMemcpyAsync(host.data(), d_out, host.size() * sizeof(sdp::ConvexityOut), hipMemcpyDeviceToHost, b->f.stream));
+  BHIP_TRY(b, hipStreamSynchronize(b->f.stream));
   std::memcpy(out, host.data(), host.size() * sizeof(sdp::ConvexityOut));
   return SDPGPU_OK;
 }
@@ -1615,7 +1498,7 @@ int sdpgpu_check_convexity(int32_t kind, const double* g, int64_t n, double K, i
 
 int sdpgpu_batch_gy(sdpgpu_batch* b, int32_t instance, int32_t period, double* out, int64_t n) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_REFUSE(b, "sdpgpu_batch_gy");
   return guarded(b, "sdpgpu_batch_gy", [&]() -> int {
     const char* who = "sdpgpu_batch_gy";
@@ -1624,10 +1507,10 @@ int sdpgpu_batch_gy(sdpgpu_batch* b, int32_t instance, int32_t period, double* o
     if (!gy_period_kept(b, period))
       return bfail(b, SDPGPU_ERR_STATE, "%s: G_%d needs V_%d, which was overwritten (store_all_values = 0 keeps G_1 and G_%d)", who, period, period + 1, b->T);
     DeviceScope dev;
-    BHIP_TRY(b, dev.enter(b->device));
+    BHIP_TRY(b, dev.enter(b->f.device));
     rc = gy_fill(b);
     if (rc) return rc;
-    BHIP_TRY(b, hipStreamSynchronize(b->stream));
+    BHIP_TRY(b, hipStreamSynchronize(b->f.stream));
     BHIP_TRY(b, hipMemcpy(out, b->d_gy + policy_row(b, instance, period - 1), (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return SDPGPU_OK;
   });
@@ -1636,7 +1519,7 @@ int sdpgpu_batch_gy(sdpgpu_batch* b, int32_t instance, int32_t period, double* o
 int sdpgpu_batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t period, const double* x_lo, const double* x_hi,
                                  const double* K, const int32_t* capacity, sdpgpu_convexity* out) {
   if (!b) return SDPGPU_ERR_ARG;
-  b->err.clear();
+  b->f.err.clear();
   STAFF_REFUSE(b, "sdpgpu_batch_check_convexity");
   return guarded(b, "sdpgpu_batch_check_convexity",
                  [&]() -> int { return batch_check_convexity(b, kind, source, period, x_lo, x_hi, K, capacity, out); });

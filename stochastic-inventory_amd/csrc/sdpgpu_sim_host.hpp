@@ -1,7 +1,7 @@
 // sdpgpu_sim_host.hpp -- what the host code of the simulation translation units shares.  By every rollout owner (sdpgpu_batch.hip:
 // an sdpgpu_batch; the handle rollouts sdpgpu_simsample.hip, sdpgpu_cashrulesim.hip, sdpgpu_xrsim.hip, sdpgpu_staffsim.hip,
-// sdpgpu_customsim.hip: an sdpgpu_handle; sdpgpu_multisim.hip: an sdpgpu_multi_policy; sdpgpu_staffbatch.hip: a StaffBatch, whose
-// pairs (instance, rule) are the frame's rules): the exception barrier, the device scope, the path-count refusals, the stream
+// sdpgpu_customsim.hip: an sdpgpu_handle; sdpgpu_multisim.hip: an sdpgpu_multi_policy; sdpgpu_staffbatch.hip: the BatchFrame of a
+// staff batch (sdpgpu_batch_frame.hpp), whose pairs (instance, rule) are the frame's rules): the exception barrier, the device scope, the path-count refusals, the stream
 // record, the threshold table of a pmf tile and the grow-only scratch block.  By the handle, staff-batch
 // and policy rollouts: RolloutFrame, the ONE host frame of a rollout call -- the carving of the scratch block with typed access
 // and uploads, the two timing events, the zeroed counters, the fixed-order reduction of every rule, the downloads and the
@@ -235,31 +235,30 @@ inline int check_solved(sdpgpu_handle* h, const char* who, const char* prefix = 
 // ---- sdpgpu_staffbatch.hip -------------------------------------------------------------------------------
 // A batch of STAFF instances in the separable mode (pool of level tables, groups per (period, table), two launches per period
 // for all instances: sdp_staff_batch.hpp): what the sdpgpu_batch_* entry points of sdpgpu_batch.hip forward to when instance 0
-// is of that family.  `err` is the batch's error sink (staff_batch_new: the create error).
+// is of that family.  It reports through `frame`, the BatchFrame of the sdpgpu_batch that holds it (sdpgpu_batch_frame.hpp), which
+// also carries its stream, profiling switch and period times; the create-time refusals go to `why`.
 struct StaffBatch;
-int staff_batch_new(const sdpgpu_desc* descs, int32_t n, StaffBatch** out, std::string* why);
+struct BatchFrame;
+int staff_batch_new(const sdpgpu_desc* descs, int32_t n, BatchFrame* frame, StaffBatch** out, std::string* why);
 void staff_batch_delete(StaffBatch* s);
-int staff_batch_add_table(StaffBatch* s, std::string* err, const double* prob, const int32_t* row_len, int32_t n_rows, int32_t row_stride,
+int staff_batch_add_table(StaffBatch* s, const double* prob, const int32_t* row_len, int32_t n_rows, int32_t row_stride,
                           int32_t* out_table);
-int staff_batch_use_table(StaffBatch* s, std::string* err, int32_t instance, int32_t t, int32_t table);
-int staff_batch_set_min_staff(StaffBatch* s, std::string* err, int32_t instance, int32_t t, double min_staff);
-int staff_batch_grid(const StaffBatch* s, std::string* err, int32_t instance, int32_t period, double* x_lo, int64_t* nx);
+int staff_batch_use_table(StaffBatch* s, int32_t instance, int32_t t, int32_t table);
+int staff_batch_set_min_staff(StaffBatch* s, int32_t instance, int32_t t, double min_staff);
+int staff_batch_grid(const StaffBatch* s, int32_t instance, int32_t period, double* x_lo, int64_t* nx);
 int64_t staff_batch_num_states(const StaffBatch* s, int32_t instance);
 int32_t staff_batch_num_actions(const StaffBatch* s, int32_t instance);
-int staff_batch_plan(StaffBatch* s, std::string* err, int32_t period, sdpgpu_batch_staff_plan* out);
-int staff_batch_set_stream(StaffBatch* s, std::string* err, void* hip_stream);
-int staff_batch_set_profiling(StaffBatch* s, int32_t on);
-int staff_batch_solve(StaffBatch* s, std::string* err, int32_t sync);
-int staff_batch_synchronize(StaffBatch* s, std::string* err);
-int staff_batch_values(StaffBatch* s, std::string* err, int32_t instance, int32_t period, double* out, int64_t n);
-int staff_batch_policy(StaffBatch* s, std::string* err, int32_t instance, int32_t period, int32_t* out, int64_t n);
-int staff_batch_initial(StaffBatch* s, std::string* err, double* out_value, int32_t* out_action_index);
-int staff_batch_stats(StaffBatch* s, std::string* err, sdpgpu_batch_stats* out);
-double staff_batch_period_ms(StaffBatch* s, std::string* err, int32_t period);
+int staff_batch_plan(StaffBatch* s, int32_t period, sdpgpu_batch_staff_plan* out);
+int staff_batch_solve(StaffBatch* s, int32_t sync);
+bool staff_batch_allocated(const StaffBatch* s);  // the device tables exist: a synchronise has something to wait for
+int staff_batch_values(StaffBatch* s, int32_t instance, int32_t period, double* out, int64_t n);
+int staff_batch_policy(StaffBatch* s, int32_t instance, int32_t period, int32_t* out, int64_t n);
+int staff_batch_initial(StaffBatch* s, double* out_value, int32_t* out_action_index);
+int staff_batch_stats(StaffBatch* s, sdpgpu_batch_stats* out);
 // steps 2-5 of WorkforceTesting.main's loop body for the whole batch ("Workforce batch: fit and rollout")
-int staff_batch_reachable(StaffBatch* s, std::string* err, int32_t instance, int32_t period, int64_t* lo, int64_t* hi);
-int staff_batch_fit_ss(StaffBatch* s, std::string* err, double max_order_quantity, double* out);
-int staff_batch_simulate(StaffBatch* s, std::string* err, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
+int staff_batch_reachable(StaffBatch* s, int32_t instance, int32_t period, int64_t* lo, int64_t* hi);
+int staff_batch_fit_ss(StaffBatch* s, double max_order_quantity, double* out);
+int staff_batch_simulate(StaffBatch* s, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
                          int32_t n_rules, sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid, int32_t* out_demand);
 
 // sdpgpu_batch.hip: one launch of batch_fit_ss_kernel<1> (sdp_fitss.hpp) at step 1 over the slices pairs[i * T + t] of a policy

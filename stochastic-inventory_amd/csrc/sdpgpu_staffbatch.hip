@@ -5,9 +5,9 @@
 // groups of instances per (period, table), instance blocks), the plan, the launcher and what the entry points of
 // sdpgpu_batch.hip forward to on a batch whose instance 0 is of the STAFF family -- and, at the end, the rest of the sweep's loop
 // body for all instances: the visited staff numbers, the (s, S) fit on the device and the rollout of hiring rules on a sampled
-// tree (sdp_staff_batch_sim.hpp) on the shared host frame.  Errors go to the sink the caller names (the batch's last error, or
-// the create error).
-#include "sdpgpu_sim_host.hpp"
+// tree (sdp_staff_batch_sim.hpp) on the shared host frame.  Stream, events, staging block and error text are the BatchFrame of
+// the sdpgpu_batch that holds this batch (sdpgpu_batch_frame.hpp); only the create-time refusals go to the caller's string.
+#include "sdpgpu_batch_frame.hpp"
 #include "sdp_fit_pair.hpp"
 #include "sdp_staff_batch.hpp"
 #include "sdp_staff_batch_sim.hpp"
@@ -20,22 +20,6 @@ int validate(const sdpgpu_desc& d);               // sdpgpu.hip
 int32_t full_action_count(const sdpgpu_desc& d);  // sdpgpu.hip
 
 namespace {
-
-int sfail(std::string* sink, int code, const char* fmt, ...) {
-  char buf[640];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (sink) *sink = buf;
-  return code;
-}
-
-#define SHIP_TRY(err, expr)                                                                              \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) return sfail(err, SDPGPU_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 // launch of one period for the whole batch
 struct PeriodPlan {
@@ -57,13 +41,14 @@ struct Table {
 }  // namespace
 
 struct StaffBatch {
+  BatchFrame* f = nullptr;         // of the sdpgpu_batch that holds this batch
   std::vector<sdpgpu_desc> d;
   int32_t N = 0, T = 0, A = 0;
   std::vector<Table> pool;
   std::vector<int32_t> use;        // [i * T + t]: pool id, -1 = none yet
   std::vector<double> min_staff;   // [i * T + t]
   std::vector<char> min_set;
-  bool laid_out = false, allocated = false, solved = false, profiling = false;
+  bool laid_out = false, allocated = false, solved = false;
   std::vector<int64_t> x_lo, nx, row_pre;  // [t]: the period's box (shared by the instances), prefix sums of nx
   int64_t sum_nx = 0, nx_max = 0, lev_max = 0;
   std::vector<PeriodPlan> plan;            // [t]
@@ -72,9 +57,6 @@ struct StaffBatch {
   std::vector<size_t> blk_off;             // [t]
   int64_t cells = 0;
   // device
-  int device = -1;
-  hipStream_t stream = nullptr;
-  bool own_stream = false, stream_given = false;
   std::vector<void*> owned;                // pool tables and row lengths
   sdp::StaffBatchTable* d_tabs = nullptr;
   sdp::StaffBatchInst* d_inst = nullptr;
@@ -82,19 +64,11 @@ struct StaffBatch {
   double* d_values = nullptr;
   int32_t* d_policy = nullptr;
   double* d_gp = nullptr;                  // [N][2][lev_max]
-  char* d_ini_out = nullptr;               // N doubles, then N int32
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::vector<hipEvent_t> ev_period;       // [T + 1] when profiling
-  bool timed = false, periods_timed = false;
   int32_t period_launches = 0, periods_run = 0;
   // ---- fit and rollout (staff_batch_fit_ss, staff_batch_simulate) ----
   std::vector<int64_t> reach_lo, reach_hi;  // [i * T + t]: the reachable intervals, made once the tables are frozen
   sdp::FitPair* d_fit_pairs = nullptr;      // [i * T + t]
   double* d_fit = nullptr;                  // N x T x 2
-  std::string* sim_err = nullptr;           // the sink of the call in progress, for the shared host frame (sim_fail below)
-  char* d_sim_scratch = nullptr;            // sim_scratch of sdpgpu_sim_host.hpp
-  size_t sim_scratch_bytes = 0;
-  hipEvent_t sim_ev0 = nullptr, sim_ev1 = nullptr;
 };
 
 namespace {
@@ -140,21 +114,21 @@ int64_t cells_of(const Table& tb, int64_t x0, int64_t nx, int64_t nA) {
   return cells;
 }
 
-int layout(StaffBatch* s, std::string* err) {
+int layout(StaffBatch* s) {
   if (s->laid_out) return SDPGPU_OK;
   const int N = s->N, T = s->T;
   const sdpgpu_desc& d0 = s->d[0];
   for (int i = 0; i < N; ++i)
     for (int t = 0; t < T; ++t)
       if (s->use[(size_t)i * T + t] < 0)
-        return sfail(err, SDPGPU_ERR_STATE, "level table of instance %d, period %d not set (sdpgpu_batch_use_level_pmf)", i, t + 1);
+        return s->f->fail(SDPGPU_ERR_STATE, "level table of instance %d, period %d not set (sdpgpu_batch_use_level_pmf)", i, t + 1);
   for (int i = 0; i < N; ++i)
     for (int t = 0; t < T; ++t) {
       const size_t k = (size_t)i * T + t;
       if (!s->min_set[k]) s->min_staff[k] = s->d[(size_t)i].overhead_cost;
       const double m = s->min_staff[k];
       if (m != std::floor(m) || std::fabs(m) > 1e9)
-        return sfail(err, SDPGPU_ERR_ARG, "minStaffNum of instance %d, period %d (sdpgpu_batch_set_overhead) must be an integer", i, t + 1);
+        return s->f->fail(SDPGPU_ERR_ARG, "minStaffNum of instance %d, period %d (sdpgpu_batch_set_overhead) must be an integer", i, t + 1);
     }
   int missing = -1;
   boxes_of(s, 0, T, &s->x_lo, &s->nx, &missing);
@@ -164,7 +138,7 @@ int layout(StaffBatch* s, std::string* err) {
       boxes_of(s, i, T, &lo, &nx, &missing);
       for (int t = 0; t < T; ++t)
         if (lo[(size_t)t] != s->x_lo[(size_t)t])
-          return sfail(err, SDPGPU_ERR_UNSUPPORTED, "instance %d: its level tables put the staff range of period %d at %lld .., instance 0's at %lld .. "
+          return s->f->fail(SDPGPU_ERR_UNSUPPORTED, "instance %d: its level tables put the staff range of period %d at %lld .., instance 0's at %lld .. "
                        "(clamp_inventory = 0: the longest rows of the tables of a period must leave the instances one staff range)",
                        i, t + 1, (long long)lo[(size_t)t], (long long)s->x_lo[(size_t)t]);
     }
@@ -175,16 +149,16 @@ int layout(StaffBatch* s, std::string* err) {
     const int64_t nx = s->nx[(size_t)t], levels = nx + s->A - 1;
     // (levels and staff numbers are 32-bit in the kernels, V_{t+1} is addressed by 32-bit byte offsets)
     if (nx >= 2147483647LL || levels >= 2147483647LL || s->x_lo[(size_t)t] + levels >= 2147483647LL)
-      return sfail(err, SDPGPU_ERR_UNSUPPORTED, "period %d: %lld states + %d actions reach 2^31 levels", t + 1, (long long)nx, s->A);
+      return s->f->fail(SDPGPU_ERR_UNSUPPORTED, "period %d: %lld states + %d actions reach 2^31 levels", t + 1, (long long)nx, s->A);
     if (nx * 8 >= 2147483647LL)
-      return sfail(err, SDPGPU_ERR_UNSUPPORTED, "period %d: a value table of %lld states reaches 2 GiB (the G kernel uses 32-bit byte offsets)", t + 1, (long long)nx);
+      return s->f->fail(SDPGPU_ERR_UNSUPPORTED, "period %d: a value table of %lld states reaches 2 GiB (the G kernel uses 32-bit byte offsets)", t + 1, (long long)nx);
     s->row_pre[(size_t)t] = (size_t)s->sum_nx;
     s->sum_nx += nx;
     s->nx_max = std::max(s->nx_max, nx);
     s->lev_max = std::max(s->lev_max, levels);
   }
   if ((double)s->sum_nx * N > 4.0e9 || (double)s->lev_max * 2 * N > 4.0e9)
-    return sfail(err, SDPGPU_ERR_UNSUPPORTED, "batch tables of %d instances x %lld states (all periods) are too large", N, (long long)s->sum_nx);
+    return s->f->fail(SDPGPU_ERR_UNSUPPORTED, "batch tables of %d instances x %lld states (all periods) are too large", N, (long long)s->sum_nx);
   s->plan.assign((size_t)T, PeriodPlan());
   s->inst.assign((size_t)T * N, sdp::StaffBatchInst());
   s->blk.clear();
@@ -225,7 +199,7 @@ int layout(StaffBatch* s, std::string* err) {
     pl.tiles = (s->nx[(size_t)t] + 63) / 64;
     // (a dispatch carries at most 2^32 - 1 work-items)
     if (pl.blocks * pl.g_blocks * 64 >= 4294967296LL || !grid_ok((int64_t)N * pl.tiles) || pl.blocks * pl.R >= 2147483647LL)
-      return sfail(err, SDPGPU_ERR_UNSUPPORTED, "period %d: %lld G tasks / %lld scan workgroups do not fit one launch", t + 1,
+      return s->f->fail(SDPGPU_ERR_UNSUPPORTED, "period %d: %lld G tasks / %lld scan workgroups do not fit one launch", t + 1,
                    (long long)(pl.blocks * pl.g_blocks), (long long)((int64_t)N * pl.tiles));
     for (int i = 0; i < N; ++i) {
       const sdpgpu_desc& d = s->d[(size_t)i];
@@ -246,46 +220,35 @@ int layout(StaffBatch* s, std::string* err) {
   return SDPGPU_OK;
 }
 
-int allocate(StaffBatch* s, std::string* err) {
+int allocate(StaffBatch* s) {
   if (s->allocated) return SDPGPU_OK;
-  int rc = layout(s, err);
+  int rc = layout(s);
   if (rc) return rc;
-  int ndev = 0;
-  const hipError_t ec = hipGetDeviceCount(&ndev);
-  if (ec != hipSuccess || ndev < 1)
-    return sfail(err, SDPGPU_ERR_DEVICE, "no HIP device available (%s); this library has no CPU path", ec == hipSuccess ? "device count 0" : hipGetErrorString(ec));
-  if (!s->stream && !s->stream_given) {
-    SHIP_TRY(err, hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    s->own_stream = true;
-  }
-  const int N = s->N, T = s->T;
+  if ((rc = s->f->open(s->N))) return rc;
+  const int N = s->N;
   std::vector<sdp::StaffBatchTable> tabs(s->pool.size());
   for (size_t k = 0; k < s->pool.size(); ++k) {
     const Table& tb = s->pool[k];
     double* p = nullptr;
     int32_t* len = nullptr;
-    SHIP_TRY(err, hipMalloc((void**)&p, tb.p.size() * sizeof(double)));
+    SIM_TRY(s->f, hipMalloc((void**)&p, tb.p.size() * sizeof(double)));
     s->owned.push_back(p);
-    SHIP_TRY(err, hipMalloc((void**)&len, tb.len.size() * sizeof(int32_t)));
+    SIM_TRY(s->f, hipMalloc((void**)&len, tb.len.size() * sizeof(int32_t)));
     s->owned.push_back(len);
-    SHIP_TRY(err, hipMemcpy(p, tb.p.data(), tb.p.size() * sizeof(double), hipMemcpyHostToDevice));
-    SHIP_TRY(err, hipMemcpy(len, tb.len.data(), tb.len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    SIM_TRY(s->f, hipMemcpy(p, tb.p.data(), tb.p.size() * sizeof(double), hipMemcpyHostToDevice));
+    SIM_TRY(s->f, hipMemcpy(len, tb.len.data(), tb.len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     tabs[k] = sdp::StaffBatchTable{p, len, tb.rows, tb.maxj};
   }
-  SHIP_TRY(err, hipMalloc((void**)&s->d_tabs, std::max<size_t>(tabs.size(), 1) * sizeof(sdp::StaffBatchTable)));
-  SHIP_TRY(err, hipMemcpy(s->d_tabs, tabs.data(), tabs.size() * sizeof(sdp::StaffBatchTable), hipMemcpyHostToDevice));
-  SHIP_TRY(err, hipMalloc((void**)&s->d_inst, s->inst.size() * sizeof(sdp::StaffBatchInst)));
-  SHIP_TRY(err, hipMemcpy(s->d_inst, s->inst.data(), s->inst.size() * sizeof(sdp::StaffBatchInst), hipMemcpyHostToDevice));
-  SHIP_TRY(err, hipMalloc((void**)&s->d_blk, std::max<size_t>(s->blk.size(), 1) * sizeof(int32_t)));
-  SHIP_TRY(err, hipMemcpy(s->d_blk, s->blk.data(), s->blk.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  SIM_TRY(s->f, hipMalloc((void**)&s->d_tabs, std::max<size_t>(tabs.size(), 1) * sizeof(sdp::StaffBatchTable)));
+  SIM_TRY(s->f, hipMemcpy(s->d_tabs, tabs.data(), tabs.size() * sizeof(sdp::StaffBatchTable), hipMemcpyHostToDevice));
+  SIM_TRY(s->f, hipMalloc((void**)&s->d_inst, s->inst.size() * sizeof(sdp::StaffBatchInst)));
+  SIM_TRY(s->f, hipMemcpy(s->d_inst, s->inst.data(), s->inst.size() * sizeof(sdp::StaffBatchInst), hipMemcpyHostToDevice));
+  SIM_TRY(s->f, hipMalloc((void**)&s->d_blk, std::max<size_t>(s->blk.size(), 1) * sizeof(int32_t)));
+  SIM_TRY(s->f, hipMemcpy(s->d_blk, s->blk.data(), s->blk.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   const size_t v_elems = s->d[0].store_all_values ? (size_t)N * (size_t)s->sum_nx : (size_t)N * 2 * (size_t)s->nx_max;
-  SHIP_TRY(err, hipMalloc((void**)&s->d_values, v_elems * sizeof(double)));
-  SHIP_TRY(err, hipMalloc((void**)&s->d_policy, (size_t)N * (size_t)s->sum_nx * sizeof(int32_t)));
-  SHIP_TRY(err, hipMalloc((void**)&s->d_gp, (size_t)N * 2 * (size_t)s->lev_max * sizeof(double)));
-  SHIP_TRY(err, hipMalloc((void**)&s->d_ini_out, (size_t)N * 12));
-  SHIP_TRY(err, hipEventCreate(&s->ev0));
-  SHIP_TRY(err, hipEventCreate(&s->ev1));
-  (void)T;
+  SIM_TRY(s->f, hipMalloc((void**)&s->d_values, v_elems * sizeof(double)));
+  SIM_TRY(s->f, hipMalloc((void**)&s->d_policy, (size_t)N * (size_t)s->sum_nx * sizeof(int32_t)));
+  SIM_TRY(s->f, hipMalloc((void**)&s->d_gp, (size_t)N * 2 * (size_t)s->lev_max * sizeof(double)));
   s->allocated = true;
   return SDPGPU_OK;
 }
@@ -296,9 +259,9 @@ hipError_t launch_g(StaffBatch* s, const sdp::StaffBatchLaunch& L, const PeriodP
   const sdp::StaffBatchInst* inst = s->d_inst + (size_t)t * s->N;
   const int32_t* blk = s->d_blk + s->blk_off[(size_t)t];
   if (t + 1 < s->T)
-    hipLaunchKernelGGL((sdp::staff_batch_g_kernel<R, U, true>), grid, dim3(64), 0, s->stream, L, inst, s->d_tabs, blk, s->d_values, s->d_gp);
+    hipLaunchKernelGGL((sdp::staff_batch_g_kernel<R, U, true>), grid, dim3(64), 0, s->f->stream, L, inst, s->d_tabs, blk, s->d_values, s->d_gp);
   else
-    hipLaunchKernelGGL((sdp::staff_batch_g_kernel<R, U, false>), grid, dim3(64), 0, s->stream, L, inst, s->d_tabs, blk, s->d_values, s->d_gp);
+    hipLaunchKernelGGL((sdp::staff_batch_g_kernel<R, U, false>), grid, dim3(64), 0, s->f->stream, L, inst, s->d_tabs, blk, s->d_values, s->d_gp);
   return hipGetLastError();
 }
 
@@ -324,7 +287,7 @@ hipError_t launch_period(StaffBatch* s, int t) {
   L.lev_stride = s->lev_max;
   hipError_t e = pl.R == 1 ? launch_g<1, sdp::kStaffBatchU1>(s, L, pl, t) : launch_g<sdp::kStaffBatchR, sdp::kStaffBatchUR>(s, L, pl, t);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(sdp::staff_batch_min_kernel, dim3((unsigned)((int64_t)s->N * pl.tiles)), dim3(256), 0, s->stream, L,
+  hipLaunchKernelGGL(sdp::staff_batch_min_kernel, dim3((unsigned)((int64_t)s->N * pl.tiles)), dim3(256), 0, s->f->stream, L,
                      s->d_inst + (size_t)t * s->N, s->d_gp, s->d_values, s->d_policy);
   return hipGetLastError();
 }
@@ -349,38 +312,35 @@ const char* shape_mismatch(const sdpgpu_desc& a, const sdpgpu_desc& c, char* buf
   return nullptr;
 }
 
-int read_check(StaffBatch* s, std::string* err, const char* who, int32_t instance, int32_t period, const void* out, int64_t n, bool is_values) {
-  if (instance < 0 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, s->N - 1);
-  if (period < 1 || period > s->T) return sfail(err, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, s->T);
-  if (!s->solved) return sfail(err, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
-  const int64_t nx = s->nx[(size_t)period - 1];  // the period's own count
-  if (!out || n < 0 || n > nx) return sfail(err, SDPGPU_ERR_ARG, "%s: bad output (n = %lld, period %d has %lld states)", who, (long long)n, period, (long long)nx);
-  if (is_values && !s->d[0].store_all_values && period > 2)
-    return sfail(err, SDPGPU_ERR_STATE, "%s: V_%d was overwritten (store_all_values = 0 keeps two ping-pong tables: periods 1 and 2 survive)", who, period);
-  return SDPGPU_OK;
+int read_check(StaffBatch* s, const char* who, int32_t instance, int32_t period, const void* out, int64_t n, bool is_values) {
+  // the period's own count (the boxes exist once a solve has laid them out: `solved` is looked at first)
+  const int64_t nx = s->solved && period >= 1 && period <= s->T ? s->nx[(size_t)period - 1] : 0;
+  char states[64];
+  std::snprintf(states, sizeof states, "period %d has %lld states", period, (long long)nx);
+  return read_check(s->f, who, instance, s->N, period, out, n, nx, states, s->solved, true, is_values && !s->d[0].store_all_values);
 }
 
 }  // namespace
 
-int staff_batch_new(const sdpgpu_desc* descs, int32_t n, StaffBatch** out, std::string* why) {
+int staff_batch_new(const sdpgpu_desc* descs, int32_t n, BatchFrame* frame, StaffBatch** out, std::string* why) {
   for (int32_t k = 0; k < n; ++k) {
     const sdpgpu_desc& d = descs[k];
     g_create_error.clear();
     int rc = validate(d);
     if (rc) {
       const std::string inner = g_create_error;
-      return sfail(why, rc, "instance %d: %s", k, inner.c_str());
+      return fail_to(why, rc, "instance %d: %s", k, inner.c_str());
     }
     if (d.family != SDPGPU_FAMILY_STAFF)
-      return sfail(why, SDPGPU_ERR_UNSUPPORTED, "instance %d: family %d -- instance 0 makes this a batch of the staff family (SDPGPU_FAMILY_STAFF); a batch holds one family", k, d.family);
+      return fail_to(why, SDPGPU_ERR_UNSUPPORTED, "instance %d: family %d -- instance 0 makes this a batch of the staff family (SDPGPU_FAMILY_STAFF); a batch holds one family", k, d.family);
     if (d.world_size != 1)
-      return sfail(why, SDPGPU_ERR_UNSUPPORTED, "instance %d: world_size %d -- a batch runs on one device (split the instance list per rank on the host)", k, d.world_size);
+      return fail_to(why, SDPGPU_ERR_UNSUPPORTED, "instance %d: world_size %d -- a batch runs on one device (split the instance list per rank on the host)", k, d.world_size);
     if (d.kernel != SDPGPU_KERNEL_SEPARABLE)
-      return sfail(why, SDPGPU_ERR_UNSUPPORTED, "instance %d: kernel %d -- a staff batch runs the separable mode only (SDPGPU_KERNEL_SEPARABLE, never chosen "
+      return fail_to(why, SDPGPU_ERR_UNSUPPORTED, "instance %d: kernel %d -- a staff batch runs the separable mode only (SDPGPU_KERNEL_SEPARABLE, never chosen "
                    "automatically); the exact cell-by-cell tables come from one handle per instance", k, d.kernel);
     char buf[160];
     if (const char* mis = shape_mismatch(descs[0], d, buf, sizeof buf))
-      return sfail(why, SDPGPU_ERR_ARG, "instance %d: %s (the instances of a staff batch share one shape and iniStaffNum)", k, mis);
+      return fail_to(why, SDPGPU_ERR_ARG, "instance %d: %s (the instances of a staff batch share one shape and iniStaffNum)", k, mis);
   }
   const sdpgpu_desc& d = descs[0];
   const int32_t A = full_action_count(d);
@@ -390,7 +350,9 @@ int staff_batch_new(const sdpgpu_desc* descs, int32_t n, StaffBatch** out, std::
     s->N = n;
     s->T = d.periods;
     s->A = A;
-    s->device = d.device;
+    s->f = frame;
+    frame->device = d.device;
+    frame->T = d.periods;
     s->use.assign((size_t)n * s->T, -1);
     s->min_staff.assign((size_t)n * s->T, 0.0);
     s->min_set.assign((size_t)n * s->T, 0);
@@ -404,52 +366,29 @@ int staff_batch_new(const sdpgpu_desc* descs, int32_t n, StaffBatch** out, std::
 
 void staff_batch_delete(StaffBatch* s) {
   if (!s) return;
-  {
-    DeviceScope dev;
-    if (s->allocated || s->d_tabs || !s->owned.empty() || s->d_sim_scratch) {
-      (void)dev.enter(s->device);
-      if (s->stream) (void)hipStreamSynchronize(s->stream);
-    }
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    for (hipEvent_t e : s->ev_period)
-      if (e) (void)hipEventDestroy(e);
-    for (void* q : s->owned) (void)hipFree(q);
-    if (s->d_tabs) (void)hipFree(s->d_tabs);
-    if (s->d_inst) (void)hipFree(s->d_inst);
-    if (s->d_blk) (void)hipFree(s->d_blk);
-    if (s->d_values) (void)hipFree(s->d_values);
-    if (s->d_policy) (void)hipFree(s->d_policy);
-    if (s->d_gp) (void)hipFree(s->d_gp);
-    if (s->d_ini_out) (void)hipFree(s->d_ini_out);
-    if (s->d_fit_pairs) (void)hipFree(s->d_fit_pairs);
-    if (s->d_fit) (void)hipFree(s->d_fit);
-    if (s->d_sim_scratch) (void)hipFree(s->d_sim_scratch);
-    if (s->sim_ev0) (void)hipEventDestroy(s->sim_ev0);
-    if (s->sim_ev1) (void)hipEventDestroy(s->sim_ev1);
-    if (s->stream && s->own_stream) (void)hipStreamDestroy(s->stream);
-  }
+  s->f->close(s->allocated || s->d_tabs || !s->owned.empty() || s->f->d_sim_scratch,
+              {s->d_tabs, s->d_inst, s->d_blk, s->d_values, s->d_policy, s->d_gp, s->d_fit_pairs, s->d_fit}, s->owned);
   delete s;
 }
 
-int staff_batch_add_table(StaffBatch* s, std::string* err, const double* prob, const int32_t* row_len, int32_t n_rows, int32_t row_stride,
+int staff_batch_add_table(StaffBatch* s, const double* prob, const int32_t* row_len, int32_t n_rows, int32_t row_stride,
                           int32_t* out_table) {
   if (!prob || !out_table || n_rows < 1 || row_stride < 1)
-    return sfail(err, SDPGPU_ERR_ARG, "batch_add_level_pmf: bad argument (prob %s, out_table %s, rows=%d stride=%d)", prob ? "set" : "null",
+    return s->f->fail(SDPGPU_ERR_ARG, "batch_add_level_pmf: bad argument (prob %s, out_table %s, rows=%d stride=%d)", prob ? "set" : "null",
                  out_table ? "set" : "null", n_rows, row_stride);
-  if (s->allocated) return sfail(err, SDPGPU_ERR_STATE, "level tables are frozen once the device tables exist");
+  if (s->allocated) return s->f->fail(SDPGPU_ERR_STATE, "level tables are frozen once the device tables exist");
   Table tb;
   tb.len.resize((size_t)n_rows);
   int32_t maxj = 1;
   for (int32_t y = 0; y < n_rows; ++y) {
     const int32_t n = row_len ? row_len[y] : y + 1;
     if (n < 1 || n > y + 1 || n > row_stride)
-      return sfail(err, SDPGPU_ERR_ARG, "batch_add_level_pmf: row %d has %d entries (1 .. min(y + 1, row_stride) allowed)", y, n);
+      return s->f->fail(SDPGPU_ERR_ARG, "batch_add_level_pmf: row %d has %d entries (1 .. min(y + 1, row_stride) allowed)", y, n);
     tb.len[(size_t)y] = n;
     maxj = std::max(maxj, n);
   }
   if ((int64_t)n_rows * maxj * 8 >= 2147483647LL)
-    return sfail(err, SDPGPU_ERR_UNSUPPORTED, "batch_add_level_pmf: a table of %d x %d entries reaches 2 GiB (the G kernel uses 32-bit byte offsets)", n_rows, maxj);
+    return s->f->fail(SDPGPU_ERR_UNSUPPORTED, "batch_add_level_pmf: a table of %d x %d entries reaches 2 GiB (the G kernel uses 32-bit byte offsets)", n_rows, maxj);
   tb.p.assign((size_t)n_rows * (size_t)maxj, 0.0);
   for (int32_t y = 0; y < n_rows; ++y)
     for (int32_t j = 0; j < tb.len[(size_t)y]; ++j) tb.p[(size_t)j * (size_t)n_rows + (size_t)y] = prob[(size_t)y * (size_t)row_stride + (size_t)j];
@@ -460,39 +399,39 @@ int staff_batch_add_table(StaffBatch* s, std::string* err, const double* prob, c
   return SDPGPU_OK;
 }
 
-int staff_batch_use_table(StaffBatch* s, std::string* err, int32_t instance, int32_t t, int32_t table) {
-  if (instance < -1 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "batch_use_level_pmf: instance %d outside 0 .. %d (-1: every instance)", instance, s->N - 1);
-  if (t < -1 || t >= s->T) return sfail(err, SDPGPU_ERR_ARG, "batch_use_level_pmf: period index %d outside 0 .. %d (-1: every period)", t, s->T - 1);
+int staff_batch_use_table(StaffBatch* s, int32_t instance, int32_t t, int32_t table) {
+  if (instance < -1 || instance >= s->N) return s->f->fail(SDPGPU_ERR_ARG, "batch_use_level_pmf: instance %d outside 0 .. %d (-1: every instance)", instance, s->N - 1);
+  if (t < -1 || t >= s->T) return s->f->fail(SDPGPU_ERR_ARG, "batch_use_level_pmf: period index %d outside 0 .. %d (-1: every period)", t, s->T - 1);
   if (table < 0 || table >= (int32_t)s->pool.size())
-    return sfail(err, SDPGPU_ERR_ARG, "batch_use_level_pmf: table %d is not in the pool (%d tables, sdpgpu_batch_add_level_pmf)", table, (int)s->pool.size());
-  if (s->allocated) return sfail(err, SDPGPU_ERR_STATE, "level tables are frozen once the device tables exist");
+    return s->f->fail(SDPGPU_ERR_ARG, "batch_use_level_pmf: table %d is not in the pool (%d tables, sdpgpu_batch_add_level_pmf)", table, (int)s->pool.size());
+  if (s->allocated) return s->f->fail(SDPGPU_ERR_STATE, "level tables are frozen once the device tables exist");
   for (int i = instance < 0 ? 0 : instance; i < (instance < 0 ? s->N : instance + 1); ++i)
     for (int u = t < 0 ? 0 : t; u < (t < 0 ? s->T : t + 1); ++u) s->use[(size_t)i * s->T + u] = table;
   s->laid_out = false;
   return SDPGPU_OK;
 }
 
-int staff_batch_set_min_staff(StaffBatch* s, std::string* err, int32_t instance, int32_t t, double min_staff) {
-  if (instance < 0 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "batch_set_overhead: instance %d outside 0 .. %d", instance, s->N - 1);
-  if (t < 0 || t >= s->T) return sfail(err, SDPGPU_ERR_ARG, "batch_set_overhead: period index %d outside 0 .. %d", t, s->T - 1);
+int staff_batch_set_min_staff(StaffBatch* s, int32_t instance, int32_t t, double min_staff) {
+  if (instance < 0 || instance >= s->N) return s->f->fail(SDPGPU_ERR_ARG, "batch_set_overhead: instance %d outside 0 .. %d", instance, s->N - 1);
+  if (t < 0 || t >= s->T) return s->f->fail(SDPGPU_ERR_ARG, "batch_set_overhead: period index %d outside 0 .. %d", t, s->T - 1);
   if (!(min_staff == std::floor(min_staff)) || std::fabs(min_staff) > 1e9)
-    return sfail(err, SDPGPU_ERR_ARG, "batch_set_overhead: minStaffNum %g of instance %d, period %d must be an integer", min_staff, instance, t + 1);
-  if (s->allocated) return sfail(err, SDPGPU_ERR_STATE, "minStaffNum is frozen once the device tables exist");
+    return s->f->fail(SDPGPU_ERR_ARG, "batch_set_overhead: minStaffNum %g of instance %d, period %d must be an integer", min_staff, instance, t + 1);
+  if (s->allocated) return s->f->fail(SDPGPU_ERR_STATE, "minStaffNum is frozen once the device tables exist");
   s->min_staff[(size_t)instance * s->T + t] = min_staff;
   s->min_set[(size_t)instance * s->T + t] = 1;
   s->laid_out = false;
   return SDPGPU_OK;
 }
 
-int staff_batch_grid(const StaffBatch* s, std::string* err, int32_t instance, int32_t period, double* x_lo, int64_t* nx) {
-  if (instance < 0 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: instance %d outside 0 .. %d", instance, s->N - 1);
-  if (period < 1 || period > s->T) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: period %d outside 1 .. %d", period, s->T);
-  if (!x_lo || !nx) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_grid: null output");
+int staff_batch_grid(const StaffBatch* s, int32_t instance, int32_t period, double* x_lo, int64_t* nx) {
+  if (instance < 0 || instance >= s->N) return s->f->fail(SDPGPU_ERR_ARG, "sdpgpu_batch_grid: instance %d outside 0 .. %d", instance, s->N - 1);
+  if (period < 1 || period > s->T) return s->f->fail(SDPGPU_ERR_ARG, "sdpgpu_batch_grid: period %d outside 1 .. %d", period, s->T);
+  if (!x_lo || !nx) return s->f->fail(SDPGPU_ERR_ARG, "sdpgpu_batch_grid: null output");
   std::vector<int64_t> lo, n;
   int missing = -1;
   boxes_of(s, instance, period, &lo, &n, &missing);
   if (missing >= 0)
-    return sfail(err, SDPGPU_ERR_STATE, "sdpgpu_batch_grid: level table of instance %d, period %d not set (clamp_inventory = 0: the staff range of period %d "
+    return s->f->fail(SDPGPU_ERR_STATE, "sdpgpu_batch_grid: level table of instance %d, period %d not set (clamp_inventory = 0: the staff range of period %d "
                  "grows from the tables before it)", instance, missing + 1, period);
   *x_lo = (double)lo[(size_t)period - 1];
   *nx = n[(size_t)period - 1];
@@ -509,11 +448,11 @@ int64_t staff_batch_num_states(const StaffBatch* s, int32_t instance) {
 
 int32_t staff_batch_num_actions(const StaffBatch* s, int32_t instance) { return instance >= 0 && instance < s->N ? s->A : -1; }
 
-int staff_batch_plan(StaffBatch* s, std::string* err, int32_t period, sdpgpu_batch_staff_plan* out) {
-  if (!out) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_staff_plan_period: out is null");
-  if (period < 1 || period > s->T) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_staff_plan_period: period %d outside 1 .. %d", period, s->T);
+int staff_batch_plan(StaffBatch* s, int32_t period, sdpgpu_batch_staff_plan* out) {
+  if (!out) return s->f->fail(SDPGPU_ERR_ARG, "sdpgpu_batch_staff_plan_period: out is null");
+  if (period < 1 || period > s->T) return s->f->fail(SDPGPU_ERR_ARG, "sdpgpu_batch_staff_plan_period: period %d outside 1 .. %d", period, s->T);
   std::memset(out, 0, sizeof *out);
-  int rc = layout(s, err);
+  int rc = layout(s);
   if (rc) return rc;
   const PeriodPlan& pl = s->plan[(size_t)period - 1];
   out->tables = pl.tables;
@@ -529,152 +468,67 @@ int staff_batch_plan(StaffBatch* s, std::string* err, int32_t period, sdpgpu_bat
   return SDPGPU_OK;
 }
 
-int staff_batch_set_stream(StaffBatch* s, std::string* err, void* hip_stream) {
-  if (s->own_stream && s->stream) {
-    DeviceScope dev;
-    SHIP_TRY(err, dev.enter(s->device));
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipStreamDestroy(s->stream);
-  }
-  s->stream = (hipStream_t)hip_stream;
-  s->own_stream = false;
-  s->stream_given = true;
-  return SDPGPU_OK;
-}
-
-int staff_batch_set_profiling(StaffBatch* s, int32_t on) {
-  s->profiling = on != 0;
-  return SDPGPU_OK;
-}
-
-int staff_batch_solve(StaffBatch* s, std::string* err, int32_t sync) {
-  int rc = layout(s, err);  // (argument and state errors before the device is touched)
+int staff_batch_solve(StaffBatch* s, int32_t sync) {
+  int rc = layout(s);  // (argument and state errors before the device is touched)
   if (rc) return rc;
   DeviceScope dev;
-  SHIP_TRY(err, dev.enter(s->device));
-  rc = allocate(s, err);
+  SIM_TRY(s->f, dev.enter(s->f->device));
+  rc = allocate(s);
   if (rc) return rc;
-  const int T = s->T;
-  if (s->profiling && s->ev_period.empty()) {
-    s->ev_period.assign((size_t)T + 1, nullptr);
-    for (hipEvent_t& e : s->ev_period) SHIP_TRY(err, hipEventCreate(&e));
-  }
   s->period_launches = s->periods_run = 0;
-  s->periods_timed = false;
-  SHIP_TRY(err, hipEventRecord(s->ev0, s->stream));
-  for (int t = T - 1; t >= 0; --t) {
-    if (s->profiling) SHIP_TRY(err, hipEventRecord(s->ev_period[(size_t)t + 1], s->stream));
+  if ((rc = s->f->sweep_begin())) return rc;
+  for (int t = s->T - 1; t >= 0; --t) {
+    if ((rc = s->f->period_mark(t))) return rc;
     const hipError_t e = launch_period(s, t);
-    if (e != hipSuccess) return sfail(err, SDPGPU_ERR_DEVICE, "staff batch period %d: %s", t + 1, hipGetErrorString(e));
+    if (e != hipSuccess) return s->f->fail(SDPGPU_ERR_DEVICE, "staff batch period %d: %s", t + 1, hipGetErrorString(e));
     s->period_launches += 2;
     s->periods_run++;
   }
-  if (s->profiling) SHIP_TRY(err, hipEventRecord(s->ev_period[0], s->stream));
-  SHIP_TRY(err, hipEventRecord(s->ev1, s->stream));
-  s->timed = true;
-  s->periods_timed = s->profiling;
+  if ((rc = s->f->period_mark(-1))) return rc;
   s->solved = true;
-  if (sync) SHIP_TRY(err, hipStreamSynchronize(s->stream));
-  return SDPGPU_OK;
+  return s->f->sweep_end(sync != 0);
 }
 
-int staff_batch_synchronize(StaffBatch* s, std::string* err) {
-  if (!s->allocated) return SDPGPU_OK;
-  DeviceScope dev;
-  SHIP_TRY(err, dev.enter(s->device));
-  SHIP_TRY(err, hipStreamSynchronize(s->stream));
-  return SDPGPU_OK;
-}
+bool staff_batch_allocated(const StaffBatch* s) { return s->allocated; }
 
-int staff_batch_values(StaffBatch* s, std::string* err, int32_t instance, int32_t period, double* out, int64_t n) {
-  int rc = read_check(s, err, "sdpgpu_batch_values", instance, period, out, n, true);
+int staff_batch_values(StaffBatch* s, int32_t instance, int32_t period, double* out, int64_t n) {
+  int rc = read_check(s, "sdpgpu_batch_values", instance, period, out, n, true);
   if (rc) return rc;
-  DeviceScope dev;
-  SHIP_TRY(err, dev.enter(s->device));
-  SHIP_TRY(err, hipStreamSynchronize(s->stream));
-  SHIP_TRY(err, hipMemcpy(out, s->d_values + value_row(s, instance, period - 1), (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-  return SDPGPU_OK;
+  return s->f->read_row(out, s->d_values + value_row(s, instance, period - 1), (size_t)n * sizeof(double));
 }
 
-int staff_batch_policy(StaffBatch* s, std::string* err, int32_t instance, int32_t period, int32_t* out, int64_t n) {
-  int rc = read_check(s, err, "sdpgpu_batch_policy", instance, period, out, n, false);
+int staff_batch_policy(StaffBatch* s, int32_t instance, int32_t period, int32_t* out, int64_t n) {
+  int rc = read_check(s, "sdpgpu_batch_policy", instance, period, out, n, false);
   if (rc) return rc;
-  DeviceScope dev;
-  SHIP_TRY(err, dev.enter(s->device));
-  SHIP_TRY(err, hipStreamSynchronize(s->stream));
-  SHIP_TRY(err, hipMemcpy(out, s->d_policy + policy_row(s, instance, period - 1), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return SDPGPU_OK;
+  return s->f->read_row(out, s->d_policy + policy_row(s, instance, period - 1), (size_t)n * sizeof(int32_t));
 }
 
-int staff_batch_initial(StaffBatch* s, std::string* err, double* out_value, int32_t* out_action_index) {
-  if (!out_value || !out_action_index) return sfail(err, SDPGPU_ERR_ARG, "sdpgpu_batch_initial: null output");
-  if (!s->solved) return sfail(err, SDPGPU_ERR_STATE, "sdpgpu_batch_initial before sdpgpu_batch_solve");
+int staff_batch_initial(StaffBatch* s, double* out_value, int32_t* out_action_index) {
+  if (!out_value || !out_action_index) return s->f->fail(SDPGPU_ERR_ARG, "sdpgpu_batch_initial: null output");
+  if (!s->solved) return s->f->fail(SDPGPU_ERR_STATE, "sdpgpu_batch_initial before sdpgpu_batch_solve");
   DeviceScope dev;
-  SHIP_TRY(err, dev.enter(s->device));
+  SIM_TRY(s->f, dev.enter(s->f->device));
   const int N = s->N;
   const int ini_idx = (int)((int64_t)s->d[0].ini_inventory - s->x_lo[0]);  // (validated at create: inside period 1's box)
-  double* dv = reinterpret_cast<double*>(s->d_ini_out);
-  int32_t* di = reinterpret_cast<int32_t*>(s->d_ini_out + (size_t)N * 8);
-  hipLaunchKernelGGL(sdp::staff_batch_initial_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->d_inst, N, ini_idx,
-                     s->d_values, s->d_policy, dv, di);
-  SHIP_TRY(err, hipGetLastError());
-  std::vector<char> host((size_t)N * 12);
-  SHIP_TRY(err, hipMemcpyAsync(host.data(), s->d_ini_out, host.size(), hipMemcpyDeviceToHost, s->stream));
-  SHIP_TRY(err, hipStreamSynchronize(s->stream));
-  std::memcpy(out_value, host.data(), (size_t)N * 8);
-  std::memcpy(out_action_index, host.data() + (size_t)N * 8, (size_t)N * 4);
-  return SDPGPU_OK;
+  hipLaunchKernelGGL(sdp::staff_batch_initial_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->f->stream, s->d_inst, N, ini_idx,
+                     s->d_values, s->d_policy, s->f->ini_value(), s->f->ini_action(N));
+  SIM_TRY(s->f, hipGetLastError());
+  return s->f->initial_download(out_value, out_action_index, N);
 }
 
-int staff_batch_stats(StaffBatch* s, std::string* err, sdpgpu_batch_stats* out) {
+int staff_batch_stats(StaffBatch* s, sdpgpu_batch_stats* out) {
   std::memset(out, 0, sizeof *out);
   out->instances = s->N;
   out->periods_run = s->periods_run;
   out->period_launches = s->period_launches;
   out->cells_evaluated = s->solved ? s->cells : 0;
-  if (s->timed) {
-    DeviceScope dev;
-    SHIP_TRY(err, dev.enter(s->device));
-    SHIP_TRY(err, hipEventSynchronize(s->ev1));
-    float ms = 0;
-    SHIP_TRY(err, hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    out->solve_ms = ms;
-  }
-  return SDPGPU_OK;
-}
-
-double staff_batch_period_ms(StaffBatch* s, std::string* err, int32_t period) {
-  if (period < 1 || period > s->T || !s->periods_timed) {
-    (void)sfail(err, SDPGPU_ERR_STATE, "sdpgpu_batch_period_ms: period %d has no timing (sdpgpu_batch_set_profiling before the solve)", period);
-    return -1.0;
-  }
-  DeviceScope dev;
-  if (dev.enter(s->device) != hipSuccess) return -1.0;
-  // period t was launched between the events t and t - 1 (the sweep runs t = T .. 1)
-  if (hipEventSynchronize(s->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, s->ev_period[(size_t)period], s->ev_period[(size_t)period - 1]) != hipSuccess) return -1.0;
-  return ms;
+  return s->f->solve_ms(&out->solve_ms);
 }
 
 // =================================================================================================
 // Fit and rollout: getOptTable's intervals, FitsS.getSinglesS and SimulatesS.simulatesS for every instance ("Workforce
-// batch: fit and rollout").  The rollout's host frame is RolloutFrame with the batch as its owner.
+// batch: fit and rollout").  The rollout's host frame is RolloutFrame with the batch's frame as its owner.
 // =================================================================================================
-
-// the error sink and the timing events of the shared host helpers (sim_scratch, RolloutFrame) for this owner
-template <class... A>
-int sim_fail(StaffBatch* s, int code, const char* fmt, A... a) {
-  return sfail(s->sim_err, code, fmt, a...);
-}
-inline hipError_t sim_events(StaffBatch* s, hipEvent_t* ev0, hipEvent_t* ev1) {
-  hipError_t e = hipSuccess;
-  if (!s->sim_ev0 && (e = hipEventCreate(&s->sim_ev0)) != hipSuccess) return e;
-  if (!s->sim_ev1 && (e = hipEventCreate(&s->sim_ev1)) != hipSuccess) return e;
-  *ev0 = s->sim_ev0;
-  *ev1 = s->sim_ev1;
-  return hipSuccess;
-}
 
 namespace {
 
@@ -744,13 +598,13 @@ void reach_all(StaffBatch* s) {
 
 // the walk down a row stops at the first threshold above u: right only when the running sums never decrease.  Every table an
 // (instance, period) uses is looked at once.
-int check_tables(StaffBatch* s, std::string* err, const char* who) {
+int check_tables(StaffBatch* s, const char* who) {
   for (size_t k = 0; k < s->use.size(); ++k) {
     Table& tb = s->pool[(size_t)s->use[k]];
     if (tb.nonneg) continue;
     for (size_t e = 0; e < tb.p.size(); ++e)
       if (!(tb.p[e] >= 0.0))
-        return sfail(err, SDPGPU_ERR_ARG, "%s: table %d of the pool holds a negative or NaN probability (level %zu, turnover %zu)", who, (int)s->use[k],
+        return s->f->fail(SDPGPU_ERR_ARG, "%s: table %d of the pool holds a negative or NaN probability (level %zu, turnover %zu)", who, (int)s->use[k],
                      e % (size_t)tb.rows, e / (size_t)tb.rows);
     tb.nonneg = true;
   }
@@ -759,28 +613,28 @@ int check_tables(StaffBatch* s, std::string* err, const char* who) {
 
 }  // namespace
 
-int staff_batch_reachable(StaffBatch* s, std::string* err, int32_t instance, int32_t period, int64_t* lo, int64_t* hi) {
+int staff_batch_reachable(StaffBatch* s, int32_t instance, int32_t period, int64_t* lo, int64_t* hi) {
   const char* who = "sdpgpu_batch_staff_reachable";
-  if (instance < 0 || instance >= s->N) return sfail(err, SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, s->N - 1);
-  if (period < 1 || period > s->T) return sfail(err, SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, s->T);
-  if (!lo || !hi) return sfail(err, SDPGPU_ERR_ARG, "%s: null output (lo, hi)", who);
+  if (instance < 0 || instance >= s->N) return s->f->fail(SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, s->N - 1);
+  if (period < 1 || period > s->T) return s->f->fail(SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, s->T);
+  if (!lo || !hi) return s->f->fail(SDPGPU_ERR_ARG, "%s: null output (lo, hi)", who);
   std::vector<int64_t> l, h;
   int missing = -1;
   reach_of(s, instance, period, &l, &h, &missing);
   if (missing >= 0)
-    return sfail(err, SDPGPU_ERR_STATE, "%s: level table of instance %d, period %d not set (the staff numbers of period %d follow from the tables "
+    return s->f->fail(SDPGPU_ERR_STATE, "%s: level table of instance %d, period %d not set (the staff numbers of period %d follow from the tables "
                  "before it)", who, instance, missing + 1, period);
   *lo = l[(size_t)period - 1];
   *hi = h[(size_t)period - 1];
   return SDPGPU_OK;
 }
 
-int staff_batch_fit_ss(StaffBatch* s, std::string* err, double max_order_quantity, double* out) {
+int staff_batch_fit_ss(StaffBatch* s, double max_order_quantity, double* out) {
   const char* who = "sdpgpu_batch_staff_fit_ss";
-  if (!out) return sfail(err, SDPGPU_ERR_ARG, "%s: out is null", who);
+  if (!out) return s->f->fail(SDPGPU_ERR_ARG, "%s: out is null", who);
   if (!std::isfinite(max_order_quantity) || max_order_quantity < 0)
-    return sfail(err, SDPGPU_ERR_ARG, "%s: max_order_quantity = %g (a finite limit >= 0; the drivers pass Integer.MAX_VALUE)", who, max_order_quantity);
-  if (!s->solved) return sfail(err, SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+    return s->f->fail(SDPGPU_ERR_ARG, "%s: max_order_quantity = %g (a finite limit >= 0; the drivers pass Integer.MAX_VALUE)", who, max_order_quantity);
+  if (!s->solved) return s->f->fail(SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
   const int N = s->N, T = s->T;
   reach_all(s);
   std::vector<sdp::FitPair> pairs((size_t)N * T);
@@ -788,45 +642,45 @@ int staff_batch_fit_ss(StaffBatch* s, std::string* err, double max_order_quantit
     for (int t = 0; t < T; ++t) {
       const int64_t L = s->reach_lo[(size_t)i * T + t], H = s->reach_hi[(size_t)i * T + t], x0 = s->x_lo[(size_t)t];
       if (L < x0 || H < L || H - x0 >= s->nx[(size_t)t])  // (the visited numbers lie inside the period's box by construction)
-        return sfail(err, SDPGPU_ERR_INTERNAL, "%s: instance %d, period %d: staff numbers %lld .. %lld outside the box %lld .. %lld", who, i, t + 1,
+        return s->f->fail(SDPGPU_ERR_INTERNAL, "%s: instance %d, period %d: staff numbers %lld .. %lld outside the box %lld .. %lld", who, i, t + 1,
                      (long long)L, (long long)H, (long long)x0, (long long)(x0 + s->nx[(size_t)t] - 1));
       pairs[(size_t)i * T + t] = sdp::FitPair{(int64_t)policy_row(s, i, t), (double)x0, max_order_quantity, (int32_t)(L - x0), (int32_t)(H - L + 1)};
     }
   DeviceScope dev;
-  SHIP_TRY(err, dev.enter(s->device));
-  if (!s->d_fit_pairs) SHIP_TRY(err, hipMalloc((void**)&s->d_fit_pairs, pairs.size() * sizeof(sdp::FitPair)));
-  if (!s->d_fit) SHIP_TRY(err, hipMalloc((void**)&s->d_fit, pairs.size() * 2 * sizeof(double)));
-  SHIP_TRY(err, hipMemcpyAsync(s->d_fit_pairs, pairs.data(), pairs.size() * sizeof(sdp::FitPair), hipMemcpyHostToDevice, s->stream));
-  SHIP_TRY(err, launch_fit_singles(s->stream, s->d_fit_pairs, N * T, T, s->d_policy, s->d_fit));
-  SHIP_TRY(err, hipMemcpyAsync(out, s->d_fit, pairs.size() * 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  SHIP_TRY(err, hipStreamSynchronize(s->stream));
+  SIM_TRY(s->f, dev.enter(s->f->device));
+  if (!s->d_fit_pairs) SIM_TRY(s->f, hipMalloc((void**)&s->d_fit_pairs, pairs.size() * sizeof(sdp::FitPair)));
+  if (!s->d_fit) SIM_TRY(s->f, hipMalloc((void**)&s->d_fit, pairs.size() * 2 * sizeof(double)));
+  SIM_TRY(s->f, hipMemcpyAsync(s->d_fit_pairs, pairs.data(), pairs.size() * sizeof(sdp::FitPair), hipMemcpyHostToDevice, s->f->stream));
+  SIM_TRY(s->f, launch_fit_singles(s->f->stream, s->d_fit_pairs, N * T, T, s->d_policy, s->d_fit));
+  SIM_TRY(s->f, hipMemcpyAsync(out, s->d_fit, pairs.size() * 2 * sizeof(double), hipMemcpyDeviceToHost, s->f->stream));
+  SIM_TRY(s->f, hipStreamSynchronize(s->f->stream));
   return SDPGPU_OK;
 }
 
-int staff_batch_simulate(StaffBatch* s, std::string* err, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
+int staff_batch_simulate(StaffBatch* s, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
                          int32_t n_rules, sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid, int32_t* out_demand) {
   const char* who = "sdpgpu_batch_staff_simulate";
   const int N = s->N, T = s->T;
-  if (!sample_nums) return sfail(err, SDPGPU_ERR_ARG, "%s: sample_nums is null", who);
-  if (!results) return sfail(err, SDPGPU_ERR_ARG, "%s: results is null", who);
-  if (n_rules < 1 || n_rules > kStaffBatchSimMaxRules) return sfail(err, SDPGPU_ERR_ARG, "%s: n_rules = %d (1 .. %d)", who, n_rules, kStaffBatchSimMaxRules);
-  if (!ss && n_rules != 1) return sfail(err, SDPGPU_ERR_ARG, "%s: n_rules = %d with ss == NULL (the table policy is one rule)", who, n_rules);
+  if (!sample_nums) return s->f->fail(SDPGPU_ERR_ARG, "%s: sample_nums is null", who);
+  if (!results) return s->f->fail(SDPGPU_ERR_ARG, "%s: results is null", who);
+  if (n_rules < 1 || n_rules > kStaffBatchSimMaxRules) return s->f->fail(SDPGPU_ERR_ARG, "%s: n_rules = %d (1 .. %d)", who, n_rules, kStaffBatchSimMaxRules);
+  if (!ss && n_rules != 1) return s->f->fail(SDPGPU_ERR_ARG, "%s: n_rules = %d with ss == NULL (the table policy is one rule)", who, n_rules);
   int64_t leaves = 1;
   for (int t = 0; t < T; ++t) {
-    if (sample_nums[t] < 1) return sfail(err, SDPGPU_ERR_ARG, "%s: sample_nums[%d] = %d (at least 1)", who, t, sample_nums[t]);
+    if (sample_nums[t] < 1) return s->f->fail(SDPGPU_ERR_ARG, "%s: sample_nums[%d] = %d (at least 1)", who, t, sample_nums[t]);
     leaves *= sample_nums[t];
-    if (leaves > kSimMaxPaths) return sfail(err, SDPGPU_ERR_ARG, "%s: sample_nums gives more than %d leaves (product up to index %d)", who, kSimMaxPaths, t);
+    if (leaves > kSimMaxPaths) return s->f->fail(SDPGPU_ERR_ARG, "%s: sample_nums gives more than %d leaves (product up to index %d)", who, kSimMaxPaths, t);
   }
   const int64_t n_pairs = (int64_t)N * n_rules;
   if (n_pairs * leaves > kStaffBatchSimMaxSums)
-    return sfail(err, SDPGPU_ERR_ARG, "%s: %d instances x n_rules %d x %lld leaves (sample_nums) exceed %lld leaf sums (2 GiB)", who, N, n_rules,
+    return s->f->fail(SDPGPU_ERR_ARG, "%s: %d instances x n_rules %d x %lld leaves (sample_nums) exceed %lld leaf sums (2 GiB)", who, N, n_rules,
                  (long long)leaves, (long long)kStaffBatchSimMaxSums);
   for (int i = 0; i < N; ++i)
     for (int t = 0; t < T; ++t)
       if (s->use[(size_t)i * T + t] < 0)
-        return sfail(err, SDPGPU_ERR_STATE, "%s: level table of instance %d, period %d not set (sdpgpu_batch_use_level_pmf)", who, i, t + 1);
+        return s->f->fail(SDPGPU_ERR_STATE, "%s: level table of instance %d, period %d not set (sdpgpu_batch_use_level_pmf)", who, i, t + 1);
   if (!(ini_x >= 0 && ini_x <= 1e9) || ini_x != std::floor(ini_x))
-    return sfail(err, SDPGPU_ERR_ARG, "%s: ini_x = %g (a staff number: an integer in 0 .. 1e9)", who, ini_x);
+    return s->f->fail(SDPGPU_ERR_ARG, "%s: ini_x = %g (a staff number: an integer in 0 .. 1e9)", who, ini_x);
   std::vector<int32_t> levels;
   if (ss) {
     levels.resize((size_t)n_pairs * T * 2);
@@ -837,30 +691,29 @@ int staff_batch_simulate(StaffBatch* s, std::string* err, const int32_t* sample_
           const double lo = ss[k], up = ss[k + 1];
           // (int) of a double: toward zero; what it cannot represent is refused
           if (!std::isfinite(lo) || !std::isfinite(up) || !(lo > -2147483649.0 && lo < 2147483648.0) || !(up > -2147483649.0 && up < 2147483648.0))
-            return sfail(err, SDPGPU_ERR_ARG, "%s: ss[%d][%d][%d] = (%g, %g) is not finite or outside int32", who, i, r, t, lo, up);
+            return s->f->fail(SDPGPU_ERR_ARG, "%s: ss[%d][%d][%d] = (%g, %g) is not finite or outside int32", who, i, r, t, lo, up);
           const int32_t si = (int32_t)lo, Si = (int32_t)up;
           if ((int64_t)Si < (int64_t)si - 1)
-            return sfail(err, SDPGPU_ERR_ARG, "%s: ss[%d][%d][%d] = (%g, %g): S < s - 1 would hire a negative number at x = s - 1", who, i, r, t, lo, up);
+            return s->f->fail(SDPGPU_ERR_ARG, "%s: ss[%d][%d][%d] = (%g, %g): S < s - 1 would hire a negative number at x = s - 1", who, i, r, t, lo, up);
           levels[k] = si;
           levels[k + 1] = Si;
         }
   }
-  int rc = layout(s, err);  // host arithmetic: the periods' boxes
+  int rc = layout(s);  // host arithmetic: the periods' boxes
   if (rc) return rc;
   if (!ss) {
     const double lo = (double)s->x_lo[0], hi = lo + (double)(s->nx[0] - 1);
-    if (ini_x < lo || ini_x > hi) return sfail(err, SDPGPU_ERR_ARG, "%s: ini_x = %g outside period 1's staff numbers %g .. %g", who, ini_x, lo, hi);
-    if (!s->solved) return sfail(err, SDPGPU_ERR_STATE, "%s: nothing has been solved (the table policy needs sdpgpu_batch_solve; a level rule does not)", who);
+    if (ini_x < lo || ini_x > hi) return s->f->fail(SDPGPU_ERR_ARG, "%s: ini_x = %g outside period 1's staff numbers %g .. %g", who, ini_x, lo, hi);
+    if (!s->solved) return s->f->fail(SDPGPU_ERR_STATE, "%s: nothing has been solved (the table policy needs sdpgpu_batch_solve; a level rule does not)", who);
   }
-  rc = check_tables(s, err, who);
+  rc = check_tables(s, who);
   if (rc) return rc;
 
-  s->sim_err = err;
-  rc = no_device(s, who);
+  rc = no_device(s->f, who);
   if (rc) return rc;
   DeviceScope dev;
-  SHIP_TRY(err, dev.enter(s->device));
-  rc = allocate(s, err);  // (a level rule needs the device tables, not a solve)
+  SIM_TRY(s->f, dev.enter(s->f->device));
+  rc = allocate(s);  // (a level rule needs the device tables, not a solve)
   if (rc) return rc;
   const uint32_t n = (uint32_t)leaves;
   // what the instances share of a period: the tree level and the box (the instance's fields are filled in by the kernel)
@@ -888,7 +741,7 @@ int staff_batch_simulate(StaffBatch* s, std::string* err, const int32_t* sample_
   L.seed_lo = (uint32_t)(seed & 0xffffffffu);
   L.seed_hi = (uint32_t)(seed >> 32);
 
-  RolloutFrame<StaffBatch> f(s, n, (size_t)n_pairs);
+  RolloutFrame<BatchFrame> f(s->f, n, (size_t)n_pairs);
   const size_t sums = f.nr * n;
   const auto p_per = f.put(per.data(), per.size());
   const auto p_ss = f.put(levels.data(), levels.size());
@@ -901,12 +754,12 @@ int staff_batch_simulate(StaffBatch* s, std::string* err, const int32_t* sample_
   rc = f.start();
   if (rc) return rc;
   if (ss)
-    hipLaunchKernelGGL((sdp::staff_batch_sim_kernel<sdp::StaffLevelRule>), grid, dim3(256), 0, s->stream, L, (int32_t)N, n_rules, f[p_per], s->d_inst,
+    hipLaunchKernelGGL((sdp::staff_batch_sim_kernel<sdp::StaffLevelRule>), grid, dim3(256), 0, s->f->stream, L, (int32_t)N, n_rules, f[p_per], s->d_inst,
                        s->d_tabs, sdp::StaffLevelRule{f[p_ss]}, f.d_sum, f[p_flag], f[p_dem], f.d_part, f.d_cnt);
   else
-    hipLaunchKernelGGL((sdp::staff_batch_sim_kernel<sdp::StaffTableRule>), grid, dim3(256), 0, s->stream, L, (int32_t)N, n_rules, f[p_per], s->d_inst,
+    hipLaunchKernelGGL((sdp::staff_batch_sim_kernel<sdp::StaffTableRule>), grid, dim3(256), 0, s->f->stream, L, (int32_t)N, n_rules, f[p_per], s->d_inst,
                        s->d_tabs, sdp::StaffTableRule{s->d_policy}, f.d_sum, f[p_flag], f[p_dem], f.d_part, f.d_cnt);
-  SHIP_TRY(err, hipGetLastError());
+  SIM_TRY(s->f, hipGetLastError());
   f.download(out_valid, f[p_flag], sums);
   f.download(out_demand, f[p_dem], sums * (size_t)T * sizeof(int32_t));
   return f.finish(results, out_sum);

@@ -130,6 +130,29 @@ def test_results_before_a_solve_are_a_state_error(sia, lib):
         lib.sdpgpu_batch_destroy(b)
 
 
+def test_a_good_call_after_a_failed_one_leaves_no_error_text(sia, lib):
+    """Every entry point clears the batch's last error on entry: the text belongs to the call that failed."""
+    rc, b, _ = _create(lib, _descs(sia, 2), 2)
+    assert rc == 0
+    try:
+        err = lambda: lib.sdpgpu_batch_last_error(b).decode()
+        v = np.zeros(51)
+        pl = sia.SdpgpuBatchPlan()
+        x_lo, nx = C.c_double(), C.c_int64()
+        failing = [lambda: lib.sdpgpu_batch_values(b, 0, 1, _dp(v), 51), lambda: lib.sdpgpu_batch_solve(b, 1),
+                   lambda: lib.sdpgpu_batch_plan_period(b, 4, C.byref(pl)), lambda: lib.sdpgpu_batch_period_ms(b, 1),
+                   lambda: lib.sdpgpu_batch_grid(b, 2, 1, C.byref(x_lo), C.byref(nx))]
+        good = [lambda: lib.sdpgpu_batch_synchronize(b), lambda: lib.sdpgpu_batch_set_profiling(b, 1),
+                lambda: lib.sdpgpu_batch_grid(b, 1, 1, C.byref(x_lo), C.byref(nx)),
+                lambda: lib.sdpgpu_batch_set_pmf(b, 0, 0, _dp(np.arange(4.0)), _dp(np.full(4, 0.25)), 4)]
+        for k, bad in enumerate(failing):
+            assert bad() != 0 and err() != ""
+            assert good[k % len(good)]() == 0 and err() == ""
+        assert (x_lo.value, nx.value) == (-20.0, 51)
+    finally:
+        lib.sdpgpu_batch_destroy(b)
+
+
 def test_python_wrapper_raises_with_the_library_text(sia):
     descs = [sia.BackorderFunctor(minInventory=-5, maxInventory=5 + i, maxOrderQuantity=3).to_desc(2) for i in range(2)]
     tile = np.array([[0.0, 0.5], [1.0, 0.5]])

@@ -205,6 +205,27 @@ def test_use_level_pmf_and_missing_tables(sia, lib, batch3):
     assert lib.sdpgpu_batch_staff_plan_period(b, 1, C.byref(pl)) == 0 and pl.tables == 1
 
 
+def test_a_good_call_after_a_failed_one_leaves_no_error_text(sia, lib, batch3):
+    """Every entry point clears the batch's last error on entry, the forwarded ones included."""
+    b = batch3
+    table = sia.staff_level_pmf([0.3], 13)[0]
+    v = np.zeros(13)
+    pl = sia.SdpgpuBatchStaffPlan()
+    x_lo, nx, lo, hi = C.c_double(), C.c_int64(), C.c_int64(), C.c_int64()
+    failing = [lambda: lib.sdpgpu_batch_values(b, 0, 1, _dp(v), 1), lambda: lib.sdpgpu_batch_solve(b, 1),
+               lambda: lib.sdpgpu_batch_staff_plan_period(b, 4, C.byref(pl)), lambda: lib.sdpgpu_batch_period_ms(b, 1),
+               lambda: lib.sdpgpu_batch_use_level_pmf(b, 0, 0, 7), lambda: lib.sdpgpu_batch_set_overhead(b, 0, 0, 0.5),
+               lambda: lib.sdpgpu_batch_staff_fit_ss(b, 10.0, _dp(v)), lambda: lib.sdpgpu_batch_plan_period(b, 1, None)]
+    good = [lambda: lib.sdpgpu_batch_synchronize(b), lambda: lib.sdpgpu_batch_set_profiling(b, 1),
+            lambda: lib.sdpgpu_batch_grid(b, 1, 1, C.byref(x_lo), C.byref(nx)), lambda: _add(lib, b, table)[0],
+            lambda: lib.sdpgpu_batch_set_overhead(b, 0, 0, 5.0),
+            lambda: lib.sdpgpu_batch_staff_reachable(b, 0, 1, C.byref(lo), C.byref(hi))]
+    for k, bad in enumerate(failing):
+        assert bad() != 0 and _err(lib, b) != ""
+        assert good[k % len(good)]() == 0 and _err(lib, b) == ""
+    assert (x_lo.value, nx.value, lo.value, hi.value) == (0.0, 1, 0, 0)
+
+
 def test_set_overhead_takes_integers(sia, lib, batch3):
     b = batch3
     assert lib.sdpgpu_batch_set_overhead(b, 1, 2, 7.0) == 0
