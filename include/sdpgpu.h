@@ -1145,6 +1145,122 @@ int sdpgpu_batch_gy(sdpgpu_batch* b, int32_t instance, int32_t period, double* o
 int sdpgpu_batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t period, const double* x_lo,
                                  const double* x_hi, const double* K, const int32_t* capacity, sdpgpu_convexity* out);
 
+/* ---- cash structure tables: G(y, R), H, GB - GA - K, F - G and their checks -----------------------------------------------
+ * What the cash drivers do after a solve (CashConstraintDraw.main :187-297, CheckFG.main :100-198, CheckMonotony.main
+ * :132-257, SingleCrossTesting.main :85-178): a table over a window of (cash R, level y) start states from a recursion whose
+ * drawn period ignores the action, post-processed by CashRecursion.java:227-404.  In the drawn period every action yields the
+ * same sum, so an entry is the ACTION-0 sum of the handle's own cell statements against the handle's own V_{period+1}.
+ * Additive to ABI 6.  DESIGN 4, "Cash structure tables".
+ *
+ * Scope of a handle: family CASH with cash_formula 1, step 1, an integer cash grid (cash_round_mult = cash_round_div = 1),
+ * world_size 1, no user functor; anything else SDPGPU_ERR_UNSUPPORTED naming the field, before any device call.
+ *
+ * sdpgpu_cash_g_table: out[i * n_x + j] is the entry of cash R = cash_lo + i and level y = x_lo + j
+ * (SingleCrossTesting.java:154-165, resultTable[rowIndex][columnIndex]) of `period` (any of 1 .. T).  The entry sums over
+ * the demand index ascending from 0.0 (CashRecursion.java:110-122): acc += p * imm, then for period < T
+ * acc += (p * gamma) * V_{period+1}(next), with imm and next the CASH cell statements for base = y, fixed = 0.0, the period's
+ * overhead, salvage at period T only, the penalty statement, both clamps and the quantiser unchanged, and
+ *   kind SDPGPU_CASH_G  (0; SingleCrossTesting.java:110-131,159; CheckFG.java:139-181): var = 0.0; stored acc - v * y
+ *   kind SDPGPU_CASH_GA (1; CashConstraintDraw.java:193-214,264-274): var = v * y; stored acc
+ *   kind SDPGPU_CASH_GB (2; :217-229): as GA with ncash = ncash - K between ncash = R + inc and the cash clamps
+ * x_lo, cash_lo whole numbers, the window inside [min_inventory, max_inventory] x [min_cash, max_cash], n_x, n_r >= 1, else
+ * SDPGPU_ERR_ARG naming the argument; more than SDPGPU_CASH_G_MAX_AXIS points on an axis is SDPGPU_ERR_UNSUPPORTED.
+ * SDPGPU_ERR_STATE before a solve and for a period whose V_{period+1} a ping-pong handle (store_all_values = 0) has
+ * overwritten. */
+#define SDPGPU_CASH_G 0
+#define SDPGPU_CASH_GA 1
+#define SDPGPU_CASH_GB 2
+#define SDPGPU_CASH_G_MAX_AXIS 65536 /* points per axis of a G window (the launch's grid dimensions) */
+int sdpgpu_cash_g_table(sdpgpu_handle* h, int32_t kind, int32_t period, double x_lo, int32_t n_x, double cash_lo, int32_t n_r,
+                        double* out);
+
+/* The request mask of sdpgpu_cash_structure / _host.  A check bit forms the table it reads; check slot 0 = H,
+ * 1 = GB - GA - K, 2 = F - G - v j. */
+#define SDPGPU_CSTRUCT_H 0x1            /* getH (CashRecursion.java:270-295), and the optyIndex table the reference drops */
+#define SDPGPU_CSTRUCT_GAGB 0x2         /* getMinusGAGB (:227-244) */
+#define SDPGPU_CSTRUCT_FG 0x4           /* getMinusFG (:252-262) */
+#define SDPGPU_CSTRUCT_SINGLE_CROSS 0x8 /* checkSingleCrossing (:298-318) on H */
+#define SDPGPU_CSTRUCT_NONINC(slot) (0x10 << (slot)) /* checkNonIncreasing (:363-379) on table `slot` */
+#define SDPGPU_CSTRUCT_NONDEC(slot) (0x80 << (slot)) /* checkNonDecreasing (:386-404) on table `slot` */
+#define SDPGPU_CSTRUCT_ALL 0x3ff
+/* Derived tables and checks work on windows of at most SDPGPU_CSTRUCT_MAX_AXIS points per axis (three indices of 11 bits in
+ * a violation key) and SDPGPU_CSTRUCT_MAX_POINTS points in all (the tables of one call: at most 64 MiB of device memory);
+ * beyond them SDPGPU_ERR_UNSUPPORTED. */
+#define SDPGPU_CSTRUCT_MAX_AXIS 2048
+#define SDPGPU_CSTRUCT_MAX_POINTS (1 << 20)
+
+typedef struct sdpgpu_cash_structure_in {
+  int32_t source;   /* 0: the tables of the solved handle, formed on the device (G, GA, GB by sdpgpu_cash_g_table's kernel, F =
+                       V_period on the window: CheckFG.java:183-196); 1: the caller's tables g / ga / gb / f */
+  int32_t mask;     /* SDPGPU_CSTRUCT_* bits, 1 .. SDPGPU_CSTRUCT_ALL */
+  int32_t device;   /* source 1 on the device: where the tables are uploaded when the handle is NULL (-1: the current one) */
+  int32_t period;   /* source 0: the drawn period (the drivers' `period = 1`, SingleCrossTesting.java:91) */
+  int32_t n_r, n_x; /* RLength, xLength (CashRecursion.java:271-272): rows = cash, columns = levels */
+  double x_lo;      /* source 0: minInventorys, the level of column 0 (SingleCrossTesting.java:85) */
+  double min_cash;  /* minCash: `cash = minCash + i` (CashRecursion.java:232, :275); source 0: the cash of row 0 */
+  double fix_cost;  /* fixCost (CashRecursion.java:227, :252, :270) */
+  double vari_cost; /* variCost (the same lines) */
+  const double* g;  /* source 1: resultG  (CashRecursion.java:270, :252), n_r * n_x, row-major; read by H and F - G */
+  const double* ga; /* source 1: resultGA (:227) */
+  const double* gb; /* source 1: resultGB (:227) */
+  const double* f;  /* source 1: resultF  (:252) */
+  /* source 1: a derived table the caller already holds -- resultH of checkSingleCrossing (:298), arr of checkNonIncreasing /
+   * checkNonDecreasing (:363, :386).  A slot given here is not formed (its sources are not read, optyIndex is not written):
+   * the checks of that slot read the caller's table as it stands. */
+  const double* h;
+  const double* gagb;
+  const double* fg;
+} sdpgpu_cash_structure_in;
+
+/* One check's verdict.  holds = 1: the indices are -1 and value 0.0.  holds = 0: the FIRST violation in the reference's loop
+ * order.  checkSingleCrossing (:302-310): row i whose last passing column is j, the failing entry resultH[i1][j1] = value.
+ * checkNonIncreasing (:367-370): (i, j), (i1, j1) = (i, j + 1), value = arr[i][j + 1] - arr[i][j].  checkNonDecreasing
+ * (:393-395): (i, j), (i1, j1) = (i + 1, j), value = arr[i + 1][j] - arr[i][j]. */
+typedef struct sdpgpu_cash_verdict {
+  int32_t holds;
+  int32_t i, j, i1, j1;
+  int32_t reserved;
+  double value;
+} sdpgpu_cash_verdict;
+
+typedef struct sdpgpu_cash_structure_out {
+  double* g;  /* optional host copies, n_r * n_x each, of every table the call formed or read (NULL: not copied) */
+  double* ga;
+  double* gb;
+  double* f;
+  double* h;          /* `values` of getH (CashRecursion.java:291) */
+  int32_t* opt_y;     /* optyIndex of getH (:279, :287) */
+  double* gagb;       /* `values` of getMinusGAGB (:240) */
+  double* fg;         /* `values` of getMinusFG (:258) */
+  sdpgpu_cash_verdict single_crossing;   /* checkSingleCrossing (:298-318) on H */
+  sdpgpu_cash_verdict non_increasing[3]; /* checkNonIncreasing (:363-379) on slot 0 / 1 / 2 */
+  sdpgpu_cash_verdict non_decreasing[3]; /* checkNonDecreasing (:386-404) */
+  double kernel_ms;   /* device path: HIP-event time of the call's kernels (0.0 from the host entry point) */
+} sdpgpu_cash_structure_out;
+
+/* The requests, each the reference's loops as they stand, fp64, left to right, no FMA:
+ *   H: row i is cash = min_cash + i; ybound = min(n_x - 1, j + max(0, (int)((cash - K) / v))); candidates k = j + 1 .. ybound
+ *      with cashIndex = (int)(cash - K - v * (k - j)) used directly as a ROW index; cashIndex < 0 is skipped; the candidate is
+ *      G[cashIndex][k] - G[i][j] - K, strict > from the initial -K, the first candidate wins ties.  cashIndex >= n_r, where
+ *      Java would throw, is SDPGPU_ERR_ARG naming (i, j, k), found before any table is written.
+ *   GB - GA - K: a running maximum (strict >) of GB[i][k], k in [j, min(j + Qbound + 1, n_x)), Qbound = max(0, (int)((cash -
+ *      K) / v)), started at GB[i][j]; then - GA[i][j] - K.
+ *   F - G - v j: F[i][j] - G[i][j] - v * j with j the COLUMN INDEX.
+ *   checkSingleCrossing: an entry passes iff it is > -0.1 (a NaN fails); lastColumnEnd carries from row to row and a row
+ *      without a passing entry leaves it unchanged.
+ *   checkNonIncreasing: loops i then j, passes iff arr[i][j + 1] - arr[i][j] < 0.1.
+ *   checkNonDecreasing: loops j then i, passes iff arr[i + 1][j] - arr[i][j] > -0.1.
+ * (int) is Java's narrowing: NaN gives 0, out-of-range values saturate; int sums wrap.  A NaN that is STORED -- an entry of a
+ * table formed here, a verdict's value -- is the one NaN of Double.doubleToLongBits, 0x7ff8000000000000 (which NaN an operation
+ * yields differs between processors, and Java defines none); a caller's table is copied as it stands.
+ *
+ * sdpgpu_cash_structure runs them on the device; h may be NULL for source 1 (errors then through sdpgpu_last_error(NULL)).
+ * sdpgpu_cash_structure_host runs them on the caller's tables (source 1 only) with the plain loops and no device: what the
+ * device path is held to bit for bit -- the per-element predicates and arithmetic are functions shared by both.  A table the
+ * mask needs and the caller left NULL, n_r or n_x < 1, a mask outside 1 .. SDPGPU_CSTRUCT_ALL: SDPGPU_ERR_ARG. */
+int sdpgpu_cash_structure(sdpgpu_handle* h, const sdpgpu_cash_structure_in* in, sdpgpu_cash_structure_out* out);
+int sdpgpu_cash_structure_host(const sdpgpu_cash_structure_in* in, sdpgpu_cash_structure_out* out);
+
 /* ---- sampled simulation on a handle: demand paths drawn ON the device, rolled and reduced there ------------------------
  * What every driver does after its solve -- `new Simulation(distributions, sampleNum, recursion)
  * .simulateSDPGivenSamplNum(initialState)` (Simulation.java:53-74; CashSimulation.java:85-118 for the cash classes;

@@ -22,6 +22,8 @@ from .recursion import (CLSP, CashLeadtimeRecursion, CashRecursion, CashRecursio
 from .simulation import CashSimulation, CashSimulationXR, RiskSimulation, Sampling, SimulateFitsS, Simulation, SimulationBatch
 from .workforce import SimulatesS, StaffFunctor, StaffRecursion, StaffRecursionBatch, StaffState
 from .structure import CheckKConvexity
+from . import cash_structure
+from .cash_structure import CashStructure
 from .states import CashLeadtimeState, CashState, CashStateXR, LeadtimeState, OptDirection, RiskState, State
 
 __all__ = [
@@ -34,6 +36,6 @@ __all__ = [
     "MultiPolicy", "CashSimulationMulti", "CashSimulationMultiXR",
     "multiv_solve", "multiv_alpha_list", "MultiVResult", "CashRecursionV", "CashStateMultiYR", "CashStateR",
     "GetPmf", "PoissonDist", "GammaDist", "NormalDist", "UniformIntDist", "DiscreteDistribution", "Simulation", "SimulationBatch", "RiskSimulation", "CashSimulation", "CashSimulationXR", "RecursionG", "Sampling",
-    "FitsS", "FindsSOverDraft", "SimulateFitsS", "CheckKConvexity", "SdpgpuConvexity",
+    "FitsS", "FindsSOverDraft", "SimulateFitsS", "CheckKConvexity", "SdpgpuConvexity", "CashStructure", "cash_structure",
     "State", "LeadtimeState", "CashState", "CashStateXR", "CashLeadtimeState", "RiskState", "OptDirection", "java_round",
 ]

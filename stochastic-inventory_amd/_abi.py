@@ -313,6 +313,47 @@ class SdpgpuSimResult(C.Structure):
                 ("mean", C.c_double), ("m2", C.c_double), ("kernel_ms", C.c_double)]
 PMF_GETPMF, PMF_CLSP = 0, 1
 
+CASH_G, CASH_GA, CASH_GB = 0, 1, 2  # SDPGPU_CASH_*: the kinds of sdpgpu_cash_g_table
+# SDPGPU_CSTRUCT_*: the request mask of sdpgpu_cash_structure; slot 0 = H, 1 = GB - GA - K, 2 = F - G - v j
+CSTRUCT_H, CSTRUCT_GAGB, CSTRUCT_FG, CSTRUCT_SINGLE_CROSS, CSTRUCT_ALL = 0x1, 0x2, 0x4, 0x8, 0x3ff
+CSTRUCT_MAX_AXIS, CSTRUCT_MAX_POINTS = 2048, 1 << 20
+
+
+def CSTRUCT_NONINC(slot: int) -> int:
+    return 0x10 << slot
+
+
+def CSTRUCT_NONDEC(slot: int) -> int:
+    return 0x80 << slot
+
+
+class SdpgpuCashStructureIn(C.Structure):
+    """struct sdpgpu_cash_structure_in (include/sdpgpu.h)."""
+
+    _fields_ = [("source", C.c_int32), ("mask", C.c_int32), ("device", C.c_int32), ("period", C.c_int32), ("n_r", C.c_int32),
+                ("n_x", C.c_int32), ("x_lo", C.c_double), ("min_cash", C.c_double), ("fix_cost", C.c_double), ("vari_cost", C.c_double),
+                ("g", C.POINTER(C.c_double)), ("ga", C.POINTER(C.c_double)), ("gb", C.POINTER(C.c_double)), ("f", C.POINTER(C.c_double)),
+                ("h", C.POINTER(C.c_double)), ("gagb", C.POINTER(C.c_double)), ("fg", C.POINTER(C.c_double))]
+
+
+class SdpgpuCashVerdict(C.Structure):
+    """struct sdpgpu_cash_verdict (include/sdpgpu.h)."""
+
+    _fields_ = [("holds", C.c_int32), ("i", C.c_int32), ("j", C.c_int32), ("i1", C.c_int32), ("j1", C.c_int32), ("reserved", C.c_int32),
+                ("value", C.c_double)]
+
+    def as_tuple(self):
+        return (self.holds, self.i, self.j, self.i1, self.j1, self.value)
+
+
+class SdpgpuCashStructureOut(C.Structure):
+    """struct sdpgpu_cash_structure_out (include/sdpgpu.h)."""
+
+    _fields_ = [("g", C.POINTER(C.c_double)), ("ga", C.POINTER(C.c_double)), ("gb", C.POINTER(C.c_double)), ("f", C.POINTER(C.c_double)),
+                ("h", C.POINTER(C.c_double)), ("opt_y", C.POINTER(C.c_int32)), ("gagb", C.POINTER(C.c_double)), ("fg", C.POINTER(C.c_double)),
+                ("single_crossing", SdpgpuCashVerdict), ("non_increasing", SdpgpuCashVerdict * 3), ("non_decreasing", SdpgpuCashVerdict * 3),
+                ("kernel_ms", C.c_double)]
+
 
 # every symbol include/sdpgpu.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
@@ -432,6 +473,9 @@ EXPORTS = {
     "sdpgpu_check_convexity": (C.c_int, [C.c_int32, _DP, C.c_int64, C.c_double, C.c_int32, C.POINTER(SdpgpuConvexity)]),
     "sdpgpu_batch_gy": (C.c_int, [_P, C.c_int32, C.c_int32, _DP, C.c_int64]),
     "sdpgpu_batch_check_convexity": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _DP, _DP, _DP, _IP, C.POINTER(SdpgpuConvexity)]),
+    "sdpgpu_cash_g_table": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_int32, _DP]),
+    "sdpgpu_cash_structure": (C.c_int, [_P, C.POINTER(SdpgpuCashStructureIn), C.POINTER(SdpgpuCashStructureOut)]),
+    "sdpgpu_cash_structure_host": (C.c_int, [C.POINTER(SdpgpuCashStructureIn), C.POINTER(SdpgpuCashStructureOut)]),
     "sdpgpu_set_sampler": (C.c_int, [_P, C.c_int32, C.POINTER(SdpgpuDistSpec)]),
     "sdpgpu_simulate_sampled": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_double,
                                           C.POINTER(SdpgpuSimResult), _DP, C.POINTER(C.c_uint8)]),

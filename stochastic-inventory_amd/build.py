@@ -33,7 +33,8 @@ def sources():
                                             "sdpgpu_staff.hip", "sdpgpu_sparse.hip", "sdpgpu_comm.hip", "sdpgpu_pmf.hip",
                                             "sdpgpu_batch.hip", "sdpgpu_simsample.hip", "sdpgpu_staffsim.hip",
                                             "sdpgpu_cashrulesim.hip", "sdpgpu_xrsim.hip", "sdpgpu_customsim.hip",
-                                            "sdpgpu_multisim.hip", "sdpgpu_staffbatch.hip", "sdpgpu_multiv.hip")]
+                                            "sdpgpu_multisim.hip", "sdpgpu_staffbatch.hip", "sdpgpu_multiv.hip",
+                                            "sdpgpu_cashstruct.hip")]
 
 
 def deps():

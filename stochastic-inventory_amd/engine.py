@@ -448,6 +448,25 @@ class SdpEngine:
             float(fix_order_cost), float(vari_cost), res, None if sums is None else _dp(sums)))
         return (list(res), sums) if want_sums else list(res)
 
+    def cash_g_table(self, kind: int, period: int, x_lo: float, x_hi: float, cash_lo: float, cash_hi: float) -> np.ndarray:
+        """CASH family, formula 1: the table G (kind _abi.CASH_G), GA (CASH_GA) or GB (CASH_GB) of `period` over the window of
+        levels x_lo .. x_hi and cash cash_lo .. cash_hi, both ends included (sdpgpu_cash_g_table; DESIGN 4, "Cash structure
+        tables").  Returns out[R - cash_lo, y - x_lo], the drivers' resultTable[rowIndex][columnIndex].  Needs a solve."""
+        n_x, n_r = int(x_hi - x_lo) + 1, int(cash_hi - cash_lo) + 1
+        out = np.empty((max(n_r, 1), max(n_x, 1)), dtype=np.float64)
+        self._check(self._lib.sdpgpu_cash_g_table(self._h, int(kind), int(period), float(x_lo), n_x, float(cash_lo), n_r, _dp(out)))
+        return out
+
+    def cash_structure(self, mask: int, period: int, x_lo: float, x_hi: float, cash_lo: float, cash_hi: float, *, fix_cost: float = None,
+                       vari_cost: float = None, want_tables: bool = True):
+        """The derived tables and checks `mask` names (_abi.CSTRUCT_*; cash_structure.mask_of) of the solved handle's G, GA, GB
+        and F = V_period over the window, all formed on the device (sdpgpu_cash_structure, source 0).  fix_cost / vari_cost
+        default to the descriptor's.  Returns a cash_structure.CashStructure; want_tables=False copies no table back."""
+        from . import cash_structure as cs
+        return cs.run(mask, source=0, handle=self._h, period=period, x_lo=x_lo, n_x=int(x_hi - x_lo) + 1, n_r=int(cash_hi - cash_lo) + 1,
+                      min_cash=cash_lo, fix_cost=self.desc.fixed_order_cost if fix_cost is None else fix_cost,
+                      vari_cost=self.desc.unit_order_cost if vari_cost is None else vari_cost, want_tables=want_tables)
+
     def xr_simulate(self, n_paths: int = None, seed: int = 0, ini_x: float = 0.0, ini_r: float = 0.0, levels=None, *, vari_cost: float = None,
                     demand=None, mode="lhs", first_path: int = 0, discount=None, want_sums: bool = False, want_demands: bool = False):
         """CASH family with cash_formula 2: roll the policy table (levels=None; needs a solve) or Chao's a* levels -- shape

@@ -26,6 +26,7 @@ from typing import Callable, Dict, Optional
 
 import numpy as np
 
+from .cash_structure import CashStructureMethods
 from .engine import SdpEngine
 from .states import OptDirection
 
@@ -260,14 +261,40 @@ class LeadtimeRecursion(_GpuRecursionBase):
         return 4
 
 
-class CashRecursion(_GpuRecursionBase):
+class CashRecursion(_GpuRecursionBase, CashStructureMethods):
     """sdp.cash.CashRecursion (CashRecursion.java:39-56): discounted future term
-    `p * discountFactor * V` (CashRecursion.java:120); rows {period, x, cash, Q} (:209-218)."""
+    `p * discountFactor * V` (CashRecursion.java:120); rows {period, x, cash, Q} (:209-218).  The table methods of
+    CashRecursion.java:227-404 (getH, getMinusGAGB, getMinusFG, getH3Column, checkSingleCrossing, checkNonIncreasing,
+    checkNonDecreasing) come from cash_structure.CashStructureMethods and run on the host entry point."""
 
     def __init__(self, optDirection, pmf, getFeasibleAction=None, stateTransition=None, immediateValue=None,
                  discountFactor: float = 1.0, *, functor=None, device: int = -1, kernel: int = 0):
         super().__init__(optDirection, pmf, getFeasibleAction, stateTransition, immediateValue, functor=functor,
                          discountFactor=discountFactor, device=device, kernel=kernel)
+
+    _G_KINDS = {"G": 0, "GA": 1, "GB": 2}
+
+    def drawG(self, kind, minInventorys, maxInventorys, minCash, maxCash, period: int = 1):
+        """The sweep of the drivers' second recursion (isForDrawGy; SingleCrossTesting.java:149-165, CashConstraintDraw.java
+        :255-283) from THIS handle: kind "G", "GA" or "GB" (or 0, 1, 2).  Returns (resultTable[R - minCash][y - minInventorys],
+        yG), yG being the drivers' rows [cash, inventory, value], cash outer."""
+        self._solve()
+        k = self._G_KINDS[kind] if isinstance(kind, str) else int(kind)
+        table = self._engine.cash_g_table(k, period, minInventorys, maxInventorys, minCash, maxCash)
+        n_r, n_x = table.shape
+        yG = np.empty((n_r * n_x, 3), dtype=np.float64)
+        yG[:, 0] = np.repeat(float(minCash) + np.arange(n_r, dtype=np.float64), n_x)
+        yG[:, 1] = np.tile(float(minInventorys) + np.arange(n_x, dtype=np.float64), n_r)
+        yG[:, 2] = table.reshape(-1)
+        return table, yG
+
+    def structure(self, mask, minInventorys, maxInventorys, minCash, maxCash, period: int = 1, *, fixCost=None, variCost=None,
+                  want_tables: bool = True):
+        """The device path from the solved handle: the derived tables and checks `mask` names (cash_structure.mask_of) on the
+        window, G / GA / GB / F never leaving the device unless want_tables.  -> cash_structure.CashStructure."""
+        self._solve()
+        return self._engine.cash_structure(mask, period, minInventorys, maxInventorys, minCash, maxCash, fix_cost=fixCost, vari_cost=variCost,
+                                           want_tables=want_tables)
 
     def _opt_columns(self, period, idx, q):
         x_lo, nx, nc, nq = self._engine.grid(period)

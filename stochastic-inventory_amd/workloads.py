@@ -409,6 +409,55 @@ def fitss_sweep(levels: int = 3, patterns=None) -> List[Workload]:
     return out
 
 
+SINGLE_CROSS_DEMANDS = [  # SingleCrossTesting.java:35-40
+    [15, 15, 15, 15, 15, 15, 15, 15, 15, 15],
+    [21.15, 18.9, 17.7, 16.5, 15.15, 13.95, 12.75, 11.55, 10.35, 9.15], [6.6, 9.3, 11.1, 12.9, 16.8, 21.6, 24, 26.4, 31.5, 33.9],
+    [12.1, 10, 7.9, 7, 7.9, 10, 12.1, 13, 12.1, 10], [15.7, 10, 4.3, 2, 4.3, 10, 15.7, 18, 15.7, 10],
+    [41.8, 6.6, 2, 21.8, 44.8, 9.6, 2.6, 17, 30, 35.4], [4.08, 12.16, 37.36, 21.44, 39.12, 35.68, 19.84, 22.48, 29.04, 12.4],
+    [4.7, 8.1, 23.6, 39.4, 16.4, 28.7, 50.8, 39.1, 75.4, 69.4], [4.4, 11.6, 26.4, 14.4, 14.6, 19.8, 7.4, 18.3, 20.4, 11.4],
+    [4.9, 18.8, 6.4, 27.9, 45.3, 22.4, 22.3, 51.7, 29.1, 54.7]]
+
+
+def single_cross_testing(patterns=None, prices=(5, 6, 7), T: int = 2, max_inventory: float = 200, min_cash: float = -100,
+                         max_cash: float = 1500, max_inventorys: int = 30, window_cash: int = 30) -> List[Workload]:
+    """The 30 instances of cash.singleItem.SingleCrossTesting.main (SingleCrossTesting.java:35-91): 10 demand patterns x 3
+    prices, T = 2, K = 10, v = 1, h = 0, no salvage, orders up to 150, inventory 0..200 x cash -100..1500, Poisson demand
+    through GetPmf at 0.999.  Every workload carries its window -- levels 0 .. 30, cash 0 .. (int) K + 30 -- as
+    `window = (minInventorys, maxInventorys, minCash, maxCash)` and the drawn `period` (1).  The keyword arguments shrink the
+    grid and the window for tests."""
+    from .pmf import GetPmf, PoissonDist
+    out = []
+    K = 10.0
+    for ip in (patterns if patterns is not None else range(1, len(SINGLE_CROSS_DEMANDS) + 1)):
+        mean = SINGLE_CROSS_DEMANDS[ip - 1][:T]
+        tiles = [np.asarray(t, dtype=np.float64) for t in GetPmf([PoissonDist(m) for m in mean], 0.999, 1).getpmf()]
+        for price in prices:
+            f = CashFunctor(price=price, fixOrderCost=K, variCost=1, holdingCost=0, overheadCost=0, salvageValue=0, penaltyCost=0,
+                            discountFactor=1.0, maxOrderQuantity=150, minInventoryState=0, maxInventoryState=max_inventory,
+                            minCashState=min_cash, maxCashState=max_cash, cashRoundMult=1.0, cashRoundDiv=1.0, cashRoundIntDiv=True,
+                            cashFormula=1, iniInventory=0, iniCash=0)
+            w = Workload(f"single_cross_p{ip}_price{price:g}", f, OptDirection.MAX, tiles, "SingleCrossTesting.main instance")
+            w.pattern, w.period = ip, 1
+            w.window = (0, max_inventorys, 0, int(K) + window_cash)
+            out.append(w)
+    return out
+
+
+def check_fg() -> Workload:
+    """cash.singleItem.CheckFG.main's instance and window (CheckFG.java:30-47, :100-106): Poisson(8) x 3 at 0.9999, K = 10,
+    v = 1, price 8, salvage 0.5, orders up to 200, inventory 0..500 x cash -100..2000; levels 0 .. 100, cash 0 .. 90."""
+    from .pmf import GetPmf, PoissonDist
+    tiles = [np.asarray(t, dtype=np.float64) for t in GetPmf([PoissonDist(8)] * 3, 0.9999, 1).getpmf()]
+    f = CashFunctor(price=8, fixOrderCost=10, variCost=1, holdingCost=0, overheadCost=0, salvageValue=0.5, penaltyCost=0,
+                    discountFactor=1.0, maxOrderQuantity=200, minInventoryState=0, maxInventoryState=500, minCashState=-100,
+                    maxCashState=2000, cashRoundMult=1.0, cashRoundDiv=1.0, cashRoundIntDiv=True, cashFormula=1, iniInventory=0,
+                    iniCash=13)
+    w = Workload("check_fg", f, OptDirection.MAX, tiles, "CheckFG.main instance")
+    w.period = 1
+    w.window = (0, 100, 0, 10 + 80)
+    return w
+
+
 def by_name(name: str, **kw) -> Workload:
     table = {"cfg1": cfg1_sS, "cfg2": cfg2_clsp, "cfg3": cfg3_cash, "cfg3t": cfg3_tenths, "cfg4": cfg4_leadtime,
              "cfg4p": cfg4_pipeline, "target": target_grid, "f5_spl": f5_single_product_leadtime, "staff": staff_testing,
