@@ -962,7 +962,8 @@ int sdpgpu_batch_plan_period(sdpgpu_batch* b, int32_t period, sdpgpu_batch_plan*
  * length is never read) and returns the table's id; a table of 2 GiB or more is SDPGPU_ERR_UNSUPPORTED.
  * sdpgpu_batch_use_level_pmf makes period index t (0-based) of `instance` integrate over table `table`; instance = -1: every
  * instance, t = -1: every period.  sdpgpu_batch_set_overhead sets minStaffNum[t] of one instance (an integer value).  Tables
- * and overheads are frozen once the device tables exist (SDPGPU_ERR_STATE).
+ * are frozen once the device tables exist (SDPGPU_ERR_STATE); minStaffNum, on which no staff range, plan or arena depends, may
+ * still be set then: the batch counts as unsolved until the next sdpgpu_batch_solve, which runs with the new value.
  *
  * On a STAFF batch these entry points keep their meaning: sdpgpu_batch_destroy, _last_error, _num_actions, _num_states (the
  * states of period T: the largest staff range, and every period's when clamped; -1 while an unclamped batch lacks a table it
@@ -1384,6 +1385,60 @@ int sdpgpu_batch_staff_fit_ss(sdpgpu_batch* b, double max_order_quantity, double
 int sdpgpu_batch_staff_simulate(sdpgpu_batch* b, const int32_t* sample_nums, uint64_t seed, double ini_x, const double* ss,
                                 int32_t n_rules, sdpgpu_sim_result* results, double* out_sum, uint8_t* out_valid,
                                 int32_t* out_demand);
+
+/* ---- workforce structure rows: G(y) of the STAFF family and CheckKConvexity on them --------------------------------------
+ * The last step of WorkforcePlanning.main (WorkforcePlanning.java:165-211): a second StaffRecursion whose lambdas ignore the
+ * action in period 1 (:171-195), `getExpectedValue(new StaffState(1, y), y)` for y = minX .. maxX through
+ * StaffRecursion.java:127-172 (:200-205), and CheckKConvexity.check(yG, fixCost) (:208-209).  Here no second recursion is
+ * built: an entry is one serial sum against the V_{t+1} a solved handle or batch already holds, for ANY period.  Definition and
+ * the relation to the reference: DESIGN 4, "Workforce structure rows".  Additive to ABI 6.
+ *
+ * G_t(y) for period t in 1 .. T and level y in 0 .. n_rows_t - 1, row = pmfs[t - 1][y] with len(y) entries, in fp64 without
+ * FMA, j ascending from g = 0.0:
+ *     n = y - j;  pen = n > minStaff_t ? 0.0 : unitPenalty * (double)(minStaff_t - n)
+ *     g += p_row[j] * (((0.0 + unitVariCost * (double)y) + salary * (double)n) + pen)
+ *     if t < T:  g += p_row[j] * V_{t+1}(nn),   nn = n, clamped (upper bound first, then lower) when clamp_inventory = 1
+ * hireUpStaffNum is not an argument: the reference never reads it.  G_1(y) equals the loop of StaffRecursion.java:127-172 run at
+ * every period over the driver's second lambdas, bit for bit, when no state x of periods 2 .. T that those sums reach has
+ * x + policy(x) > n_rows - 1 (that loop skips such actions, :148-149; the solved recursion integrates them over the last row,
+ * :93-94).  (In the Java text the inner call at :161 has one argument, i.e. the method of :81-118 with the second lambdas, which
+ * differ from the solved ones in periods 2 .. T only by the missing clamp.)
+ * A level y >= n_rows_t is SDPGPU_ERR_ARG (the reference `continue`s past every action there).  A level is OFF THE GRID when a
+ * successor nn, j < len(y), lies outside the stored grid [x_lo, x_lo + nx) of period t + 1, zero-probability entries included:
+ * SDPGPU_ERR_ARG naming the first such level and successor; nothing is written.
+ *
+ * sdpgpu_staff_gy_host: the sum on the host, no device, the tables from anywhere: prob[y * row_stride + j] with row_len[y]
+ * entries in row y (NULL: y + 1), v_next[nn - v_x_lo] for v_nx staff numbers (NULL: period T, no future term), the clamp flag
+ * and its bounds; out[k] = G(y_lo + k), k < n.  What the device calls are held to, bit for bit (one function for both sides).
+ * Errors through sdpgpu_batch_last_error(NULL).
+ * sdpgpu_staff_gy: the same levels of `period` of a solved STAFF handle, AUTO or SEPARABLE alike (it reads V only), in ONE
+ * launch (lanes of a wave = 64 consecutive levels, each walking its row serially).  SDPGPU_ERR_STATE before a solve and, on a
+ * ping-pong handle (store_all_values = 0), once V_{period+1} has been overwritten; SDPGPU_ERR_UNSUPPORTED for world_size > 1,
+ * another family or a user functor.
+ * sdpgpu_staff_gy_range: the first maximal run *y_lo .. *y_hi of levels of `period` that are not off the grid (*y_lo > *y_hi:
+ * none).  Host arithmetic only.
+ * sdpgpu_staff_check_convexity: CheckKConvexity (kind as sdpgpu_check_convexity) on one row of the handle: source 0 = V_period
+ * over the staff numbers lo .. hi, source 1 = G_period over the levels lo .. hi, formed and checked on the device; bit for bit
+ * sdpgpu_check_convexity on the read-back row.  More than 8192 points: SDPGPU_ERR_UNSUPPORTED.
+ * sdpgpu_batch_staff_gy: n levels from y_lo of G_period of one instance of a solved STAFF batch.  The rows of ALL instances and
+ * periods -- per row the first run of levels that are not off the grid -- are formed in ONE launch at the first request after
+ * a solve and kept on the device; a re-solve drops them (sdpgpu_batch_set_overhead may change minStaffNum between solves).
+ * Every row is bit for bit sdpgpu_staff_gy on a separable handle of the instance.  SDPGPU_ERR_STATE before a solve and for a
+ * period whose V_{period+1} was overwritten (store_all_values = 0 keeps G_1 and G_T).
+ * sdpgpu_batch_staff_check_convexity: the check on one row of EVERY instance in one launch; lo / hi (n each, or both NULL: the
+ * period's staff numbers for source 0, the kept levels for source 1), K NULL = each instance's fixed_order_cost, capacity NULL =
+ * (int)max_order_quantity; out: n structs, written only on success.
+ * sdpgpu_batch_gy and sdpgpu_batch_check_convexity keep refusing a STAFF batch; the two calls here refuse a backorder batch. */
+int sdpgpu_staff_gy_host(double unit_vari_cost, double salary, double unit_penalty, int32_t min_staff, const double* prob,
+                         const int32_t* row_len, int32_t n_rows, int32_t row_stride, const double* v_next, int32_t v_x_lo,
+                         int64_t v_nx, int32_t clamp, int32_t min_x, int32_t max_x, int32_t y_lo, int32_t n, double* out);
+int sdpgpu_staff_gy(sdpgpu_handle* h, int32_t period, int32_t y_lo, int32_t n, double* out);
+int sdpgpu_staff_gy_range(sdpgpu_handle* h, int32_t period, int32_t* y_lo, int32_t* y_hi);
+int sdpgpu_staff_check_convexity(sdpgpu_handle* h, int32_t kind, int32_t source, int32_t period, int32_t lo, int32_t hi, double K,
+                                 int32_t capacity, sdpgpu_convexity* out);
+int sdpgpu_batch_staff_gy(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t y_lo, int32_t n, double* out);
+int sdpgpu_batch_staff_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t period, const int32_t* lo,
+                                       const int32_t* hi, const double* K, const int32_t* capacity, sdpgpu_convexity* out);
 
 /* ---- CASH family: (s, C, S) ordering rules rolled out along sampled demand paths -------------------------------------
  * What CashSimulation.simulatesCS with (s, C1(x), C2(x), S) (CashSimulation.java:996-1042), simulatesCS with (s, C1(x), S)

@@ -482,6 +482,14 @@ EXPORTS = {
     "sdpgpu_sample_demands": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, _DP]),
     "sdpgpu_staff_simulate": (C.c_int, [_P, _IP, C.c_uint64, C.c_double, _DP, C.c_int32, C.POINTER(SdpgpuSimResult), _DP,
                                         C.POINTER(C.c_uint8), _IP]),
+    "sdpgpu_staff_gy_host": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int32, _DP, _IP, C.c_int32, C.c_int32, _DP, C.c_int32, C.c_int64,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP]),
+    "sdpgpu_staff_gy": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _DP]),
+    "sdpgpu_staff_gy_range": (C.c_int, [_P, C.c_int32, _IP, _IP]),
+    "sdpgpu_staff_check_convexity": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32,
+                                               C.POINTER(SdpgpuConvexity)]),
+    "sdpgpu_batch_staff_gy": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _DP]),
+    "sdpgpu_batch_staff_check_convexity": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _IP, _IP, _DP, _IP, C.POINTER(SdpgpuConvexity)]),
     "sdpgpu_cash_rule_simulate": (C.c_int, [_P, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64, _DP, C.c_double, C.c_double, C.c_int32, _IP,
                                             _DP, _DP, _DP, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(SdpgpuSimResult),
                                             _DP]),

@@ -380,6 +380,39 @@ class StaffBatch(_Batch):
         self._check(self._lib.sdpgpu_batch_staff_fit_ss(self._b, float(max_order_quantity), _dp(out)))
         return out
 
+    # ---- structure rows (sdpgpu_batch_staff_gy / _check_convexity; WorkforcePlanning.java:165-211) ----
+    def staff_gy(self, i: int, period: int, y_lo: int, y_hi: int) -> np.ndarray:
+        """G_period(y) of instance i for the levels y_lo .. y_hi, both ends included: SdpEngine.staff_gy of a separable handle
+        of the instance, bit for bit.  The rows of ALL instances and periods are formed in one launch at the first request
+        after a solve and kept on the device until the next solve."""
+        n = int(y_hi) - int(y_lo) + 1
+        out = np.empty(max(n, 0), dtype=np.float64)
+        self._check(self._lib.sdpgpu_batch_staff_gy(self._b, int(i), int(period), int(y_lo), n, _dp(out)))
+        return out
+
+    def staff_check_convexity(self, kind: int, source="gy", period: int = 1, lo=None, hi=None, K=None, capacity=None) -> np.ndarray:
+        """CheckKConvexity.check (kind 0) or checkCK (kind 1) on one row of EVERY instance in one launch: the rows V_period
+        (source "values", over the staff numbers lo .. hi) or G_period ("gy", over the levels lo .. hi); lo / hi scalars or one
+        per instance, None = the whole row; K None = each instance's fixed hiring cost, capacity None = its hire limit.
+        Returns a structured array [n] with the fields of sdpgpu_convexity."""
+        from .structure import CONVEXITY_DTYPE
+        src = {"values": 0, "gy": 1}.get(source, source)
+        if not isinstance(src, (int, np.integer)):
+            raise ValueError(f"source {source!r}: 'values' or 'gy'")
+        if (lo is None) != (hi is None):
+            raise ValueError("lo and hi are given together, or neither")
+
+        def per_instance(v, dtype):
+            return None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (self.n,)))
+
+        a, c = per_instance(lo, np.int32), per_instance(hi, np.int32)
+        k, cap = per_instance(K, np.float64), per_instance(capacity, np.int32)
+        out = np.zeros(self.n, dtype=CONVEXITY_DTYPE)
+        self._check(self._lib.sdpgpu_batch_staff_check_convexity(
+            self._b, int(kind), int(src), int(period), None if a is None else _ip(a), None if c is None else _ip(c),
+            None if k is None else _dp(k), None if cap is None else _ip(cap), out.ctypes.data_as(C.POINTER(SdpgpuConvexity))))
+        return out
+
     def staff_simulate(self, sample_nums, seed: int, ini_x: int, ss=None, want_sums: bool = False, want_demands: bool = False):
         """SdpEngine.staff_simulate for every instance in one rollout launch (sdpgpu_batch_staff_simulate; DESIGN 4, "Workforce
         batch: fit and rollout").  ss = None: every instance's own policy table (one rule), else (s, S) levels of shape

@@ -34,7 +34,7 @@ def sources():
                                             "sdpgpu_batch.hip", "sdpgpu_simsample.hip", "sdpgpu_staffsim.hip",
                                             "sdpgpu_cashrulesim.hip", "sdpgpu_xrsim.hip", "sdpgpu_customsim.hip",
                                             "sdpgpu_multisim.hip", "sdpgpu_staffbatch.hip", "sdpgpu_multiv.hip",
-                                            "sdpgpu_cashstruct.hip")]
+                                            "sdpgpu_cashstruct.hip", "sdpgpu_staffstruct.hip")]
 
 
 def deps():

@@ -837,6 +837,22 @@ int sdpgpu_batch_staff_simulate(sdpgpu_batch* b, const int32_t* sample_nums, uin
   });
 }
 
+int sdpgpu_batch_staff_gy(sdpgpu_batch* b, int32_t instance, int32_t period, int32_t y_lo, int32_t n, double* out) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->f.err.clear();
+  STAFF_ONLY(b, "sdpgpu_batch_staff_gy");
+  return guarded(b, "sdpgpu_batch_staff_gy", [&]() -> int { return staff_batch_gy(b->staff, instance, period, y_lo, n, out); });
+}
+
+int sdpgpu_batch_staff_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t period, const int32_t* lo, const int32_t* hi,
+                                       const double* K, const int32_t* capacity, sdpgpu_convexity* out) {
+  if (!b) return SDPGPU_ERR_ARG;
+  b->f.err.clear();
+  STAFF_ONLY(b, "sdpgpu_batch_staff_check_convexity");
+  return guarded(b, "sdpgpu_batch_staff_check_convexity",
+                 [&]() -> int { return staff_batch_check_convexity(b->staff, kind, source, period, lo, hi, K, capacity, out); });
+}
+
 }  // extern "C"
 
 // =================================================================================================
@@ -1382,6 +1398,64 @@ int convexity_kind_check(sdpgpu_batch* b, const char* who, int32_t kind) {
   return SDPGPU_OK;
 }
 
+// The device part of a check, for the rows of a batch and (convexity_on_device) of a staff handle: the tasks of the rows, the
+// carving of ONE scratch block, and the launches behind its uploads.
+struct ConvexityWork {
+  std::vector<sdp::ConvexityTask> tasks;
+  int n_max = 1;
+  size_t o_rows = 0, o_tasks = 0, o_keys = 0, o_out = 0, bytes = 0;
+};
+
+double convexity_triples(const sdp::ConvexityRow& R) {
+  double triples = 0;
+  for (int o = 0; o < R.n; ++o)
+    triples += (double)(R.kind == sdp::kConvexityCheck ? sdp::convexity_count<sdp::kConvexityCheck>(R.n, R.capacity, o)
+                                                       : sdp::convexity_count<sdp::kConvexityCheckCK>(R.n, R.capacity, o));
+  return triples;
+}
+
+void convexity_plan(int kind, const std::vector<sdp::ConvexityRow>& rows, double triples, ConvexityWork* w) {
+  // tiles of about equal triple counts: enough of them to fill the device several times over, none below what pays for
+  // staging its row
+  const int64_t target = (int64_t)std::min(std::max(triples / 16384.0, 16384.0), 4194304.0);
+  for (size_t i = 0; i < rows.size(); ++i) {
+    sdp::convexity_tasks((int32_t)i, kind, rows[i].n, rows[i].capacity, target, &w->tasks);
+    w->n_max = std::max(w->n_max, (int)rows[i].n);
+  }
+  Carve c;
+  w->o_rows = c.take(rows.size() * sizeof(sdp::ConvexityRow));
+  w->o_tasks = c.take(std::max<size_t>(w->tasks.size(), 1) * sizeof(sdp::ConvexityTask));
+  w->o_keys = c.take(rows.size() * 8);
+  w->o_out = c.take(rows.size() * sizeof(sdp::ConvexityOut));
+  w->bytes = c.at;
+}
+
+// rows (their g set) and tasks go up, the key fill, the check and the finish run, the structs come down: all on `st`, which the
+// caller synchronises before it reads host_out.  sb: w.bytes of device memory.
+hipError_t convexity_launch(hipStream_t st, const std::vector<sdp::ConvexityRow>& rows, const ConvexityWork& w, char* sb, sdp::ConvexityOut* host_out) {
+  const int N = (int)rows.size();
+  sdp::ConvexityRow* d_rows = reinterpret_cast<sdp::ConvexityRow*>(sb + w.o_rows);
+  sdp::ConvexityTask* d_tasks = reinterpret_cast<sdp::ConvexityTask*>(sb + w.o_tasks);
+  unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(sb + w.o_keys);
+  sdp::ConvexityOut* d_out = reinterpret_cast<sdp::ConvexityOut*>(sb + w.o_out);
+  hipError_t e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(sdp::ConvexityRow), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  if (!w.tasks.empty() && (e = hipMemcpyAsync(d_tasks, w.tasks.data(), w.tasks.size() * sizeof(sdp::ConvexityTask), hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+  const dim3 per_row((unsigned)((N + 255) / 256));
+  hipLaunchKernelGGL(sdp::convexity_key_fill_kernel, per_row, dim3(256), 0, st, d_keys, N);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (!w.tasks.empty()) {
+    static LdsMark mark;
+    const size_t smem = sdp::convexity_lds(w.n_max);
+    if ((e = lds_allow(sdp::convexity_kernel, smem, &mark)) != hipSuccess) return e;
+    hipLaunchKernelGGL(sdp::convexity_kernel, dim3((unsigned)w.tasks.size()), dim3(256), smem, st, d_rows, d_tasks, d_keys);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(sdp::convexity_finish_kernel, per_row, dim3(256), 0, st, d_rows, d_keys, N, d_out);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  return hipMemcpyAsync(host_out, d_out, (size_t)N * sizeof(sdp::ConvexityOut), hipMemcpyDeviceToHost, st);
+}
+
 int batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t period, const double* x_lo, const double* x_hi, const double* K,
                           const int32_t* capacity, sdpgpu_convexity* out) {
   const char* who = "sdpgpu_batch_check_convexity";
@@ -1404,8 +1478,6 @@ int batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t
   // the rows: a window of every instance's row, its K, its capacity
   std::vector<int64_t> row_off((size_t)N);
   std::vector<sdp::ConvexityRow> rows((size_t)N);
-  std::vector<sdp::ConvexityTask> tasks;
-  int n_max = 1;
   double triples = 0;
   for (int i = 0; i < N; ++i) {
     const sdpgpu_desc& d = b->d[(size_t)i];
@@ -1430,54 +1502,64 @@ int batch_check_convexity(sdpgpu_batch* b, int32_t kind, int32_t source, int32_t
     R.capacity = capacity ? capacity[i] : (int32_t)d.max_order_quantity;
     R.kind = kind;
     rows[(size_t)i] = R;
-    n_max = std::max(n_max, (int)n);
-    for (int o = 0; o < (int)n; ++o)
-      triples += (double)(kind == sdp::kConvexityCheck ? sdp::convexity_count<sdp::kConvexityCheck>((int)n, R.capacity, o)
-                                                        : sdp::convexity_count<sdp::kConvexityCheckCK>((int)n, R.capacity, o));
+    triples += convexity_triples(R);
   }
-  // tiles of about equal triple counts: enough of them to fill the device several times over, none below what pays for
-  // staging its row
-  const int64_t target = (int64_t)std::min(std::max(triples / 16384.0, 16384.0), 4194304.0);
-  for (int i = 0; i < N; ++i) sdp::convexity_tasks(i, kind, rows[(size_t)i].n, rows[(size_t)i].capacity, target, &tasks);
-  if (tasks.size() > (size_t)INT32_MAX / 2) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: too many tasks in one launch", who);
+  ConvexityWork w;
+  convexity_plan(kind, rows, triples, &w);
+  if (w.tasks.size() > (size_t)INT32_MAX / 2) return bfail(b, SDPGPU_ERR_UNSUPPORTED, "%s: too many tasks in one launch", who);
 
   DeviceScope dev;
   BHIP_TRY(b, dev.enter(b->f.device));
   if (source == 1 && (rc = gy_fill(b))) return rc;
   const double* base = source == 0 ? b->d_values : b->d_gy;
   for (int i = 0; i < N; ++i) rows[(size_t)i].g = base + row_off[(size_t)i];
-  Carve c;
-  const size_t o_rows = c.take(rows.size() * sizeof(sdp::ConvexityRow)), o_tasks = c.take(std::max<size_t>(tasks.size(), 1) * sizeof(sdp::ConvexityTask));
-  const size_t o_keys = c.take((size_t)N * 8), o_out = c.take((size_t)N * sizeof(sdp::ConvexityOut));
-  rc = sim_scratch(&b->f, c.at);
+  rc = sim_scratch(&b->f, w.bytes);
   if (rc) return rc;
-  char* sb = b->f.d_sim_scratch;
-  sdp::ConvexityRow* d_rows = reinterpret_cast<sdp::ConvexityRow*>(sb + o_rows);
-  sdp::ConvexityTask* d_tasks = reinterpret_cast<sdp::ConvexityTask*>(sb + o_tasks);
-  unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(sb + o_keys);
-  sdp::ConvexityOut* d_out = reinterpret_cast<sdp::ConvexityOut*>(sb + o_out);
-  BHIP_TRY(b, hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(sdp::ConvexityRow), hipMemcpyHostToDevice, b->f.stream));
-  if (!tasks.empty()) BHIP_TRY(b, hipMemcpyAsync(d_tasks, tasks.data(), tasks.size() * sizeof(sdp::ConvexityTask), hipMemcpyHostToDevice, b->f.stream));
-  const dim3 per_row((unsigned)((N + 255) / 256));
-  hipLaunchKernelGGL(sdp::convexity_key_fill_kernel, per_row, dim3(256), 0, b->f.stream, d_keys, N);
-  BHIP_TRY(b, hipGetLastError());
-  if (!tasks.empty()) {
-    static LdsMark mark;
-    const size_t smem = sdp::convexity_lds(n_max);
-    BHIP_TRY(b, lds_allow(sdp::convexity_kernel, smem, &mark));
-    hipLaunchKernelGGL(sdp::convexity_kernel, dim3((unsigned)tasks.size()), dim3(256), smem, b->f.stream, d_rows, d_tasks, d_keys);
-    BHIP_TRY(b, hipGetLastError());
-  }
-  hipLaunchKernelGGL(sdp::convexity_finish_kernel, per_row, dim3(256), 0, b->f.stream, d_rows, d_keys, N, d_out);
-  BHIP_TRY(b, hipGetLastError());
   std::vector<sdp::ConvexityOut> host((size_t)N);  // (out is written only once everything has succeeded)
-  BHIP_TRY(b, hipMemcpyAsync(host.data(), d_out, host.size() * sizeof(sdp::ConvexityOut), hipMemcpyDeviceToHost, b->f.stream));
+  BHIP_TRY(b, convexity_launch(b->f.stream, rows, w, b->f.d_sim_scratch, host.data()));
   BHIP_TRY(b, hipStreamSynchronize(b->f.stream));
   std::memcpy(out, host.data(), host.size() * sizeof(sdp::ConvexityOut));
   return SDPGPU_OK;
 }
 
 }  // namespace
+
+static_assert(sdpgpu_detail::kConvexityMaxPoints == sdp::kConvexityMaxRow, "the limit the staff units refuse by is the kernel's");
+
+// sdpgpu_sim_host.hpp: the check on rows that already lie on the device, for the staff units
+int sdpgpu_detail::convexity_on_device(hipStream_t st, int32_t kind, const ConvexitySpec* specs, int32_t n_rows, sdpgpu_convexity* out, std::string* why) {
+  std::vector<sdp::ConvexityRow> rows((size_t)n_rows);
+  double triples = 0;
+  for (int i = 0; i < n_rows; ++i) {
+    if (specs[i].n > sdp::kConvexityMaxRow)
+      return fail_to(why, SDPGPU_ERR_UNSUPPORTED, "row %d: %d points exceed the kernel's %d (a workgroup keeps the row in LDS): narrow the window", i,
+                     specs[i].n, sdp::kConvexityMaxRow);
+    sdp::ConvexityRow R{};
+    R.g = specs[i].g;
+    R.K = specs[i].K;
+    R.n = specs[i].n;
+    R.capacity = specs[i].capacity;
+    R.kind = kind;
+    rows[(size_t)i] = R;
+    triples += convexity_triples(R);
+  }
+  ConvexityWork w;
+  convexity_plan(kind, rows, triples, &w);
+  if (w.tasks.size() > (size_t)INT32_MAX / 2) return fail_to(why, SDPGPU_ERR_UNSUPPORTED, "too many tasks in one launch");
+  struct Block {
+    char* p = nullptr;
+    ~Block() {
+      if (p) (void)hipFree(p);
+    }
+  } blk;
+  hipError_t e = hipMalloc((void**)&blk.p, w.bytes);
+  std::vector<sdp::ConvexityOut> host((size_t)n_rows);  // (out is written only once everything has succeeded)
+  if (e == hipSuccess) e = convexity_launch(st, rows, w, blk.p, host.data());
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail_to(why, SDPGPU_ERR_DEVICE, "convexity check: %s", hipGetErrorString(e));
+  std::memcpy(out, host.data(), host.size() * sizeof(sdp::ConvexityOut));
+  return SDPGPU_OK;
+}
 
 extern "C" {
 

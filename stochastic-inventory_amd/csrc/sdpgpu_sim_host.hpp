@@ -265,6 +265,35 @@ int staff_batch_simulate(StaffBatch* s, const int32_t* sample_nums, uint64_t see
 // arena, out[(i * T + t) * 2 + {0, 1}] -- for the staff batch, whose unit fills the slices and owns the buffers
 hipError_t launch_fit_singles(hipStream_t st, const sdp::FitPair* d_pairs, int n_pairs, int T, const int32_t* d_policy, double* d_out);
 
+// sdpgpu_batch.hip: CheckKConvexity (sdp_structure.hpp: key fill, convexity_kernel over convexity_tasks, finish) on n_rows rows
+// that already lie on the device, all of one kind -- for the staff units, whose rows are V_t or G_t of a handle or of every
+// instance of a staff batch.  The launches go to `st` behind whatever wrote the rows; the call returns once the structs are in
+// `out`, written only on success.  A failure leaves its reason in *why.
+constexpr int32_t kConvexityMaxPoints = 8192;  // sdp::kConvexityMaxRow, for the callers' refusals before any device call
+struct ConvexitySpec {
+  const double* g;  // device
+  double K;
+  int32_t n, capacity;
+};
+int convexity_on_device(hipStream_t st, int32_t kind, const ConvexitySpec* specs, int32_t n_rows, sdpgpu_convexity* out, std::string* why);
+
+// ---- sdpgpu_staffstruct.hip --------------------------------------------------------------------------------
+// the G(y) rows of the STAFF family (sdp_staff_structure.hpp) and the checks on them, for a handle; what a staff batch shares
+// with it: the one launch of staff_gy_kernel over `n_rows` row records (blocks of 64 levels, highest level first), which
+// uploads the records and the block table into `d_rows` / `d_blocks` first
+}  // namespace sdpgpu_detail
+namespace sdp {
+struct StaffGyRow;
+struct StaffGyBlock;
+}  // namespace sdp
+namespace sdpgpu_detail {
+int64_t staff_gy_blocks(const sdp::StaffGyRow* rows, int32_t n_rows, std::vector<sdp::StaffGyBlock>* blocks);
+hipError_t launch_staff_gy(hipStream_t st, const sdp::StaffGyRow* rows, int32_t n_rows, const std::vector<sdp::StaffGyBlock>& blocks,
+                           sdp::StaffGyRow* d_rows, sdp::StaffGyBlock* d_blocks);
+int staff_batch_gy(StaffBatch* s, int32_t instance, int32_t period, int32_t y_lo, int32_t n, double* out);
+int staff_batch_check_convexity(StaffBatch* s, int32_t kind, int32_t source, int32_t period, const int32_t* lo, const int32_t* hi, const double* K,
+                                const int32_t* capacity, sdpgpu_convexity* out);
+
 // ---- the host frame of a rollout --------------------------------------------------------------------------
 // offsets of the scratch block, every part aligned to 16 bytes
 struct Carve {

@@ -11,6 +11,7 @@
 #include "sdp_fit_pair.hpp"
 #include "sdp_staff_batch.hpp"
 #include "sdp_staff_batch_sim.hpp"
+#include "sdp_staff_structure.hpp"
 
 #include <map>
 
@@ -69,6 +70,14 @@ struct StaffBatch {
   std::vector<int64_t> reach_lo, reach_hi;  // [i * T + t]: the reachable intervals, made once the tables are frozen
   sdp::FitPair* d_fit_pairs = nullptr;      // [i * T + t]
   double* d_fit = nullptr;                  // N x T x 2
+  // ---- structure rows (staff_batch_gy, staff_batch_check_convexity; sdp_staff_structure.hpp) ----
+  bool inst_stale = false;                  // minStaffNum changed behind the device copy of `inst`: the next solve uploads it again
+  bool gy_valid = false;                    // the G rows below are those of the tables the last solve left
+  std::vector<size_t> gy_off;               // [i * T + t]: the row of (instance, period) in d_gy, one entry per table row
+  std::vector<int32_t> gy_lo, gy_hi;        // [i * T + t]: the levels made -- the first run that is not off the grid (lo > hi: none)
+  std::vector<sdp::StaffGyRow> gy_rows;     // the upload sources of the one launch, kept while the stream may read them
+  std::vector<sdp::StaffGyBlock> gy_blocks;
+  char* d_gy = nullptr;                     // [the rows' doubles][the records][the blocks]
 };
 
 namespace {
@@ -220,8 +229,20 @@ int layout(StaffBatch* s) {
   return SDPGPU_OK;
 }
 
+// sdpgpu_batch_set_overhead since the instance records went up: the records laid out again (same size, new minStaffNum) replace
+// the device copy.  Every user of d_inst comes through allocate(), so none of them launches on the old values.
+int refresh_inst(StaffBatch* s) {
+  if (!s->inst_stale) return SDPGPU_OK;
+  int rc = layout(s);
+  if (rc) return rc;
+  SIM_TRY(s->f, hipStreamSynchronize(s->f->stream));  // (an earlier launch may still be reading the old records)
+  SIM_TRY(s->f, hipMemcpy(s->d_inst, s->inst.data(), s->inst.size() * sizeof(sdp::StaffBatchInst), hipMemcpyHostToDevice));
+  s->inst_stale = false;
+  return SDPGPU_OK;
+}
+
 int allocate(StaffBatch* s) {
-  if (s->allocated) return SDPGPU_OK;
+  if (s->allocated) return refresh_inst(s);
   int rc = layout(s);
   if (rc) return rc;
   if ((rc = s->f->open(s->N))) return rc;
@@ -367,7 +388,7 @@ int staff_batch_new(const sdpgpu_desc* descs, int32_t n, BatchFrame* frame, Staf
 void staff_batch_delete(StaffBatch* s) {
   if (!s) return;
   s->f->close(s->allocated || s->d_tabs || !s->owned.empty() || s->f->d_sim_scratch,
-              {s->d_tabs, s->d_inst, s->d_blk, s->d_values, s->d_policy, s->d_gp, s->d_fit_pairs, s->d_fit}, s->owned);
+              {s->d_tabs, s->d_inst, s->d_blk, s->d_values, s->d_policy, s->d_gp, s->d_fit_pairs, s->d_fit, s->d_gy}, s->owned);
   delete s;
 }
 
@@ -416,10 +437,16 @@ int staff_batch_set_min_staff(StaffBatch* s, int32_t instance, int32_t t, double
   if (t < 0 || t >= s->T) return s->f->fail(SDPGPU_ERR_ARG, "batch_set_overhead: period index %d outside 0 .. %d", t, s->T - 1);
   if (!(min_staff == std::floor(min_staff)) || std::fabs(min_staff) > 1e9)
     return s->f->fail(SDPGPU_ERR_ARG, "batch_set_overhead: minStaffNum %g of instance %d, period %d must be an integer", min_staff, instance, t + 1);
-  if (s->allocated) return s->f->fail(SDPGPU_ERR_STATE, "minStaffNum is frozen once the device tables exist");
+  // (the staff ranges, plans and arenas do not depend on minStaffNum: once the device tables exist, whatever uses the instance
+  // records next -- a solve, a level-rule rollout -- lays them out again and uploads them over the old ones: refresh_inst)
   s->min_staff[(size_t)instance * s->T + t] = min_staff;
   s->min_set[(size_t)instance * s->T + t] = 1;
   s->laid_out = false;
+  if (s->allocated) {  // (the value and policy tables answer the old value: the batch is unsolved until the next solve)
+    s->inst_stale = true;
+    s->solved = false;
+    s->gy_valid = false;
+  }
   return SDPGPU_OK;
 }
 
@@ -475,6 +502,7 @@ int staff_batch_solve(StaffBatch* s, int32_t sync) {
   SIM_TRY(s->f, dev.enter(s->f->device));
   rc = allocate(s);
   if (rc) return rc;
+  s->gy_valid = false;  // (the G rows are those of the tables about to be replaced)
   s->period_launches = s->periods_run = 0;
   if ((rc = s->f->sweep_begin())) return rc;
   for (int t = s->T - 1; t >= 0; --t) {
@@ -763,6 +791,193 @@ int staff_batch_simulate(StaffBatch* s, const int32_t* sample_nums, uint64_t see
   f.download(out_valid, f[p_flag], sums);
   f.download(out_demand, f[p_dem], sums * (size_t)T * sizeof(int32_t));
   return f.finish(results, out_sum);
+}
+
+// =================================================================================================
+// Structure rows: G_t(y) of every (instance, period) in ONE launch, kept until the next solve, and CheckKConvexity on a row of
+// every instance ("Workforce structure rows"; sdp_staff_structure.hpp)
+// =================================================================================================
+namespace {
+
+sdp::StaffGyCost gy_cost(const StaffBatch* s, int i, int t) {
+  const sdpgpu_desc& d = s->d[(size_t)i];
+  sdp::StaffGyCost c{};
+  c.v = d.unit_order_cost;
+  c.salary = d.holding_cost;
+  c.pen = d.penalty_cost;
+  c.min_staff = (int32_t)s->min_staff[(size_t)i * s->T + t];
+  c.clamp = d.clamp_inventory;
+  c.min_x = (int32_t)d.min_inventory;
+  c.max_x = (int32_t)d.max_inventory;
+  return c;
+}
+
+// G of period index t exists when V of t + 1 does: every period with store_all_values, else t = 0 (V_2 survives) and t = T - 1
+bool gy_kept(const StaffBatch* s, int t) { return s->d[0].store_all_values || t == 0 || t == s->T - 1; }
+
+const Table& gy_table(const StaffBatch* s, int i, int t) { return s->pool[(size_t)s->use[(size_t)i * s->T + t]]; }
+
+// level y of (i, t) is off the grid of period index t + 1
+bool gy_off_grid(const StaffBatch* s, int i, int t, int y, int* bad_j, int* bad_nn) {
+  if (t + 1 >= s->T) return false;
+  return sdp::staff_gy_first_off_grid(gy_cost(s, i, t), y, gy_table(s, i, t).len[(size_t)y], s->x_lo[(size_t)t + 1], s->nx[(size_t)t + 1], bad_j, bad_nn);
+}
+
+// where the rows lie and which levels of each are made: host arithmetic, once per batch (the tables are frozen by then)
+void gy_layout(StaffBatch* s) {
+  if (!s->gy_off.empty()) return;
+  const int N = s->N, T = s->T;
+  s->gy_off.assign((size_t)N * T + 1, 0);
+  s->gy_lo.assign((size_t)N * T, 0);
+  s->gy_hi.assign((size_t)N * T, -1);
+  for (int i = 0; i < N; ++i)
+    for (int t = 0; t < T; ++t) {
+      const size_t k = (size_t)i * T + t;
+      const int32_t rows = gy_table(s, i, t).rows;
+      s->gy_off[k + 1] = s->gy_off[k] + (size_t)rows;
+      int bj, bn;
+      int32_t y = 0;
+      while (y < rows && gy_off_grid(s, i, t, y, &bj, &bn)) ++y;
+      if (y >= rows) continue;
+      s->gy_lo[k] = y;
+      while (y < rows && !gy_off_grid(s, i, t, y, &bj, &bn)) ++y;
+      s->gy_hi[k] = y - 1;
+    }
+}
+
+// the G rows of every (instance, period) on the device, once per solve
+int gy_fill(StaffBatch* s) {
+  if (s->gy_valid) return SDPGPU_OK;
+  const int N = s->N, T = s->T;
+  gy_layout(s);
+  Carve c;
+  const size_t o_g = c.take(std::max<size_t>(s->gy_off.back(), 1) * sizeof(double));
+  const size_t o_rows = c.take(std::max<size_t>((size_t)N * T, 1) * sizeof(sdp::StaffGyRow));
+  // (blocks of 64 levels: no more than one per 64 entries of a row, plus one per row)
+  const size_t o_blk = c.take((s->gy_off.back() / 64 + (size_t)N * T + 1) * sizeof(sdp::StaffGyBlock));
+  if (!s->d_gy) SIM_TRY(s->f, hipMalloc((void**)&s->d_gy, c.at));
+  double* d_g = reinterpret_cast<double*>(s->d_gy + o_g);
+  SIM_TRY(s->f, hipStreamSynchronize(s->f->stream));  // (an earlier launch may still be reading the records below)
+  s->gy_rows.clear();
+  for (int i = 0; i < N; ++i)
+    for (int t = 0; t < T; ++t) {
+      const size_t k = (size_t)i * T + t;
+      if (!gy_kept(s, t) || s->gy_hi[k] < s->gy_lo[k]) continue;  // (a row whose V_{t+1} is gone is not made)
+      const int32_t id = s->use[k];
+      sdp::StaffGyRow R{};
+      R.pT = static_cast<const double*>(s->owned[(size_t)id * 2]);
+      R.row_len = static_cast<const int32_t*>(s->owned[(size_t)id * 2 + 1]);
+      R.v_next = t + 1 < T ? s->d_values + value_row(s, i, t + 1) : nullptr;
+      R.c = gy_cost(s, i, t);
+      R.n_rows = s->pool[(size_t)id].rows;
+      R.y_lo = s->gy_lo[k];
+      R.n = s->gy_hi[k] - s->gy_lo[k] + 1;
+      R.next_x_lo = t + 1 < T ? (int32_t)s->x_lo[(size_t)t + 1] : 0;
+      R.out = d_g + s->gy_off[k] + (size_t)R.y_lo;
+      s->gy_rows.push_back(R);
+    }
+  staff_gy_blocks(s->gy_rows.data(), (int32_t)s->gy_rows.size(), &s->gy_blocks);
+  SIM_TRY(s->f, launch_staff_gy(s->f->stream, s->gy_rows.data(), (int32_t)s->gy_rows.size(), s->gy_blocks, reinterpret_cast<sdp::StaffGyRow*>(s->d_gy + o_rows),
+                                reinterpret_cast<sdp::StaffGyBlock*>(s->d_gy + o_blk)));
+  s->gy_valid = true;
+  return SDPGPU_OK;
+}
+
+// the refusals of a level window of (i, period): rows of the table, V_{period+1} held, none off the grid
+int gy_check_window(StaffBatch* s, const char* who, int i, int32_t period, int32_t y_lo, int64_t n) {
+  const int t = period - 1;
+  const int32_t rows = gy_table(s, i, t).rows;
+  if (n < 0) return s->f->fail(SDPGPU_ERR_ARG, "%s: n = %lld (at least 0)", who, (long long)n);
+  if (y_lo < 0) return s->f->fail(SDPGPU_ERR_ARG, "%s: y_lo = %d (levels start at 0)", who, y_lo);
+  if ((int64_t)y_lo + n > rows)
+    return s->f->fail(SDPGPU_ERR_ARG, "%s: instance %d: level %d is not a row of period %d's table (n_rows = %d: levels 0 .. %d)", who, i, std::max(y_lo, rows),
+                      period, rows, rows - 1);
+  if (!gy_kept(s, t))
+    return s->f->fail(SDPGPU_ERR_STATE, "%s: G_%d needs V_%d, which was overwritten (store_all_values = 0 keeps G_1 and G_%d)", who, period, period + 1, s->T);
+  gy_layout(s);
+  const size_t k = (size_t)i * s->T + t;
+  for (int64_t y = y_lo; y < y_lo + n; ++y) {
+    if (y >= s->gy_lo[k] && y <= s->gy_hi[k]) continue;
+    int bj = 0, bn = 0;
+    if (gy_off_grid(s, i, t, (int)y, &bj, &bn))
+      return s->f->fail(SDPGPU_ERR_ARG, "%s: instance %d: level %d of period %d is off the grid: its successor %d (j = %d) lies outside period %d's staff numbers "
+                        "%lld .. %lld", who, i, (int)y, period, bn, bj, period + 1, (long long)s->x_lo[(size_t)t + 1],
+                        (long long)(s->x_lo[(size_t)t + 1] + s->nx[(size_t)t + 1] - 1));
+    return s->f->fail(SDPGPU_ERR_ARG, "%s: instance %d: level %d of period %d lies behind an off-grid level: the rows kept are the first run %d .. %d", who, i,
+                      (int)y, period, s->gy_lo[k], s->gy_hi[k]);
+  }
+  return SDPGPU_OK;
+}
+
+}  // namespace
+
+int staff_batch_gy(StaffBatch* s, int32_t instance, int32_t period, int32_t y_lo, int32_t n, double* out) {
+  const char* who = "sdpgpu_batch_staff_gy";
+  if (instance < 0 || instance >= s->N) return s->f->fail(SDPGPU_ERR_ARG, "%s: instance %d outside 0 .. %d", who, instance, s->N - 1);
+  if (period < 1 || period > s->T) return s->f->fail(SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, s->T);
+  if (!s->solved) return s->f->fail(SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+  if (!out) return s->f->fail(SDPGPU_ERR_ARG, "%s: out is null", who);
+  int rc = gy_check_window(s, who, instance, period, y_lo, n);
+  if (rc || n == 0) return rc;
+  DeviceScope dev;
+  SIM_TRY(s->f, dev.enter(s->f->device));
+  if ((rc = gy_fill(s))) return rc;
+  const double* d_g = reinterpret_cast<const double*>(s->d_gy);
+  return s->f->read_row(out, d_g + s->gy_off[(size_t)instance * s->T + (period - 1)] + y_lo, (size_t)n * sizeof(double));
+}
+
+int staff_batch_check_convexity(StaffBatch* s, int32_t kind, int32_t source, int32_t period, const int32_t* lo, const int32_t* hi, const double* K,
+                                const int32_t* capacity, sdpgpu_convexity* out) {
+  const char* who = "sdpgpu_batch_staff_check_convexity";
+  const int N = s->N;
+  if (kind != 0 && kind != 1) return s->f->fail(SDPGPU_ERR_ARG, "%s: kind = %d (0: CheckKConvexity.check, 1: CheckKConvexity.checkCK)", who, kind);
+  if (source != 0 && source != 1) return s->f->fail(SDPGPU_ERR_ARG, "%s: source = %d (0: the value rows V_period, 1: the rows G_period)", who, source);
+  if (period < 1 || period > s->T) return s->f->fail(SDPGPU_ERR_ARG, "%s: period %d outside 1 .. %d", who, period, s->T);
+  if (!out) return s->f->fail(SDPGPU_ERR_ARG, "%s: out is null", who);
+  if ((lo == nullptr) != (hi == nullptr)) return s->f->fail(SDPGPU_ERR_ARG, "%s: lo and hi are given together, or both NULL (the whole row)", who);
+  if (!s->solved) return s->f->fail(SDPGPU_ERR_STATE, "%s before sdpgpu_batch_solve", who);
+  const int t = period - 1;
+  if (source == 0 && !s->d[0].store_all_values && period > 2)
+    return s->f->fail(SDPGPU_ERR_STATE, "%s: V_%d was overwritten (store_all_values = 0 keeps two ping-pong tables: periods 1 and 2 survive)", who, period);
+  if (source == 1) gy_layout(s);
+  std::vector<ConvexitySpec> specs((size_t)N);
+  std::vector<int64_t> row_off((size_t)N);
+  for (int i = 0; i < N; ++i) {
+    const size_t k = (size_t)i * s->T + t;
+    int64_t a, c;
+    if (source == 0) {
+      const int64_t x0 = s->x_lo[(size_t)t], x1 = x0 + s->nx[(size_t)t] - 1;
+      a = lo ? lo[i] : x0;
+      c = hi ? hi[i] : x1;
+      if (a > c || a < x0 || c > x1)
+        return s->f->fail(SDPGPU_ERR_ARG, "%s: instance %d: the window %lld .. %lld is not a run of period %d's staff numbers %lld .. %lld", who, i, (long long)a,
+                          (long long)c, period, (long long)x0, (long long)x1);
+      row_off[(size_t)i] = (int64_t)value_row(s, i, t) + (a - x0);
+    } else {
+      a = lo ? lo[i] : s->gy_lo[k];
+      c = hi ? hi[i] : s->gy_hi[k];
+      if (a > c) return s->f->fail(SDPGPU_ERR_ARG, "%s: instance %d: the window %lld .. %lld is empty", who, i, (long long)a, (long long)c);
+      const int rc = gy_check_window(s, who, i, period, (int32_t)a, c - a + 1);
+      if (rc) return rc;
+      row_off[(size_t)i] = (int64_t)s->gy_off[k] + a;
+    }
+    if (c - a + 1 > kConvexityMaxPoints)
+      return s->f->fail(SDPGPU_ERR_UNSUPPORTED, "%s: instance %d: a row of %lld points exceeds the kernel's %d (a workgroup keeps the row in LDS): narrow "
+                        "the window", who, i, (long long)(c - a + 1), kConvexityMaxPoints);
+    specs[(size_t)i].K = K ? K[i] : s->d[(size_t)i].fixed_order_cost;
+    specs[(size_t)i].n = (int32_t)(c - a + 1);
+    specs[(size_t)i].capacity = capacity ? capacity[i] : (int32_t)s->d[(size_t)i].max_order_quantity;
+  }
+  DeviceScope dev;
+  SIM_TRY(s->f, dev.enter(s->f->device));
+  int rc = SDPGPU_OK;
+  if (source == 1 && (rc = gy_fill(s))) return rc;
+  const double* base = source == 0 ? s->d_values : reinterpret_cast<const double*>(s->d_gy);
+  for (int i = 0; i < N; ++i) specs[(size_t)i].g = base + row_off[(size_t)i];
+  std::string why;
+  rc = convexity_on_device(s->f->stream, kind, specs.data(), N, out, &why);
+  if (rc) return s->f->fail(rc, "%s: %s", who, why.c_str());
+  return SDPGPU_OK;
 }
 
 }  // namespace sdpgpu_detail

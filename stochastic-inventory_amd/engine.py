@@ -448,6 +448,49 @@ class SdpEngine:
             float(fix_order_cost), float(vari_cost), res, None if sums is None else _dp(sums)))
         return (list(res), sums) if want_sums else list(res)
 
+    # -- STAFF family: the G(y) rows and CheckKConvexity on them ("Workforce structure rows") -----------------------
+    def staff_gy_range(self, period: int):
+        """(y_lo, y_hi): the first run of levels of `period` none of whose successors leaves period + 1's stored staff numbers
+        (sdpgpu_staff_gy_range; y_lo > y_hi: none).  Host arithmetic, no device."""
+        lo, hi = C.c_int32(), C.c_int32()
+        self._check(self._lib.sdpgpu_staff_gy_range(self._h, int(period), C.byref(lo), C.byref(hi)))
+        return int(lo.value), int(hi.value)
+
+    def staff_gy(self, period: int, y_lo: int = None, y_hi: int = None) -> np.ndarray:
+        """G_period(y) for the levels y_lo .. y_hi, both ends included (default: staff_gy_range(period)), of a solved STAFF
+        handle in one kernel launch (sdpgpu_staff_gy): the cost of standing at hire-up-to level y, the sum
+        WorkforcePlanning.main draws, against the handle's own V_{period+1}."""
+        if y_lo is None or y_hi is None:
+            r_lo, r_hi = self.staff_gy_range(period)
+            y_lo, y_hi = (r_lo if y_lo is None else y_lo), (r_hi if y_hi is None else y_hi)
+        n = int(y_hi) - int(y_lo) + 1
+        out = np.empty(max(n, 0), dtype=np.float64)
+        self._check(self._lib.sdpgpu_staff_gy(self._h, int(period), int(y_lo), n, _dp(out)))
+        return out
+
+    def staff_check_convexity(self, kind: int, source="gy", period: int = 1, lo: int = None, hi: int = None, K: float = None,
+                              capacity: int = None) -> np.ndarray:
+        """CheckKConvexity.check (kind 0) or checkCK (kind 1) on one row of a solved STAFF handle, formed and checked on the
+        device (sdpgpu_staff_check_convexity): source "values" = V_period over the staff numbers lo .. hi (default: the
+        period's grid), "gy" = G_period over the levels lo .. hi (default: staff_gy_range).  K defaults to the fixed hiring
+        cost, capacity to the hire limit.  Returns a structured scalar with the fields of sdpgpu_convexity."""
+        from .structure import CONVEXITY_DTYPE
+        src = {"values": 0, "gy": 1}.get(source, source)
+        if not isinstance(src, (int, np.integer)):
+            raise ValueError(f"source {source!r}: 'values' or 'gy'")
+        if lo is None or hi is None:
+            if src == 0:
+                x_lo, nx = self.grid(period)[:2]
+                d_lo, d_hi = int(x_lo), int(x_lo) + int(nx) - 1
+            else:
+                d_lo, d_hi = self.staff_gy_range(period)
+            lo, hi = (d_lo if lo is None else lo), (d_hi if hi is None else hi)
+        out = np.zeros(1, dtype=CONVEXITY_DTYPE)
+        self._check(self._lib.sdpgpu_staff_check_convexity(
+            self._h, int(kind), int(src), int(period), int(lo), int(hi), float(self.desc.fixed_order_cost if K is None else K),
+            int(self.desc.max_order_quantity if capacity is None else capacity), out.ctypes.data_as(C.POINTER(_abi.SdpgpuConvexity))))
+        return out[0]
+
     def cash_g_table(self, kind: int, period: int, x_lo: float, x_hi: float, cash_lo: float, cash_hi: float) -> np.ndarray:
         """CASH family, formula 1: the table G (kind _abi.CASH_G), GA (CASH_GA) or GB (CASH_GB) of `period` over the window of
         levels x_lo .. x_hi and cash cash_lo .. cash_hi, both ends included (sdpgpu_cash_g_table; DESIGN 4, "Cash structure

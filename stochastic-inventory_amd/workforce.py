@@ -8,9 +8,12 @@ Same names, argument meaning and behaviour for the path the drivers solve -- `ge
 (WorkforcePlanning.java:104-112, WorkforceTesting.java:116-124): the turnover pmf of a period is picked by the
 hire-up-to level, `pmfs[t][min(iniStaffNum + orderQty, pmfs[t].length - 1)]` (StaffRecursion.java:92-95).  As with the
 other mirrors the three lambdas are kept for the caller's own use and a `functor` descriptor names the closed-form
-family the device evaluates.  The G(y)-drawing variants (`getExpectedValue(state, hireUpStaffNum)`,
-`getExpectedValue2`, `getExpectedValueNoHireFirst`, StaffRecursion.java:127-330) are plotting helpers over special
-period-1 lambdas and are not built.  There is no CPU fallback.
+family the device evaluates.  The G(y)-drawing variant the driver uses (`getExpectedValue(state, hireUpStaffNum)` on a
+second recursion with special period-1 lambdas, WorkforcePlanning.java:165-211) lives in `StaffRecursion.drawGy` and
+`.checkK`: a G entry is one sum against this recursion's own V_{t+1}, formed on the device for any period (DESIGN 4,
+"Workforce structure rows"); the method itself keeps raising NotImplementedError.  `getExpectedValue2` and
+`getExpectedValueNoHireFirst` (StaffRecursion.java:175-330), which no driver calls, are not built.  There is no CPU
+fallback.
 """
 from __future__ import annotations
 
@@ -183,6 +186,21 @@ class StaffRecursion:
 
     def getAction(self, state: StaffState) -> int:
         return self._lookup(state)[1]
+
+    def drawGy(self, minX: int, maxX: int, period: int = 1) -> np.ndarray:
+        """The driver's `yG` (WorkforcePlanning.java:199-206) as an (n, 2) array: rows {y, G_period(y)} for y = minX .. maxX,
+        formed on the device against this recursion's own V_{period+1} (SdpEngine.staff_gy)."""
+        self._lookup(StaffState(1, self.functor.iniStaffNum))
+        g = self._engine.staff_gy(period, int(minX), int(maxX))
+        return np.stack([np.arange(int(minX), int(maxX) + 1, dtype=np.float64), g], axis=1)
+
+    def checkK(self, period: int = 1, source: str = "gy", kind: int = 0, fixCost: Optional[float] = None, capacity: Optional[int] = None,
+               minX: Optional[int] = None, maxX: Optional[int] = None):
+        """`CheckKConvexity.check(yG, fixCost)` (WorkforcePlanning.java:208-209; kind 1: checkCK) on G_period ("gy") or V_period
+        ("values"), formed and checked on the device (SdpEngine.staff_check_convexity).  fixCost defaults to the functor's,
+        capacity to the hire limit, the window to the whole row.  Returns the sdpgpu_convexity record."""
+        self._lookup(StaffState(1, self.functor.iniStaffNum))
+        return self._engine.staff_check_convexity(kind, source, period, minX, maxX, fixCost, capacity)
 
     def getOptTable(self) -> np.ndarray:
         """Rows {period, iniStaffNum, action} of the visited states in comparator order (StaffRecursion.java:245-254)."""
@@ -398,6 +416,21 @@ class StaffRecursionBatch:
             x = np.arange(L, H + 1, dtype=np.int64)
             rows.append(np.stack([np.full(len(x), float(period)), x.astype(np.float64), pol[x - x_lo].astype(np.float64)], axis=1))
         return np.concatenate(rows, axis=0) if rows else np.zeros((0, 3))
+
+    # ---- the structure step of WorkforcePlanning.main (WorkforcePlanning.java:165-211), per instance ----
+    def drawGy(self, i: int, minX: int, maxX: int, period: int = 1) -> np.ndarray:
+        """StaffRecursion.drawGy of instance i: rows {y, G_period(y)}, y = minX .. maxX.  The rows of all instances and periods
+        are formed in one launch at the first request after the solve."""
+        self._solve()
+        g = self._batch.staff_gy(i, period, int(minX), int(maxX))
+        return np.stack([np.arange(int(minX), int(maxX) + 1, dtype=np.float64), g], axis=1)
+
+    def checkK(self, i: Optional[int] = None, period: int = 1, source: str = "gy", kind: int = 0, fixCost=None, capacity=None, minX=None,
+               maxX=None):
+        """StaffRecursion.checkK for every instance in one launch: the records [n], or instance i's alone."""
+        self._solve()
+        out = self._batch.staff_check_convexity(kind, source, period, minX, maxX, fixCost, capacity)
+        return out if i is None else out[i]
 
     # ---- the rest of WorkforceTesting.main's loop body (WorkforceTesting.java:112-165), for all instances at once ----
     def defaultSampleNums(self) -> List[int]:

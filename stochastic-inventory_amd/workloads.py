@@ -179,6 +179,18 @@ def staff_testing(T: int = 8, maxHire: int = 1000, rate: float = 0.1) -> StaffWo
     return StaffWorkload(f"staff_testing0_{maxHire + 1}hires_x{T}", f, np.repeat(one, T, axis=0), "WorkforceTesting.main[0] via StaffRecursion")
 
 
+def workforce_planning(maxHire: int = 500, maxX: int = 600) -> StaffWorkload:
+    """WorkforcePlanning.main's own instance (WorkforcePlanning.java:33-69): T = 3, turnover 0.5, staff numbers clamped to
+    0 .. 600, hires 0 .. 500, a table of 601 levels -- the instance whose G(y) the driver draws and checks (:165-211)."""
+    from .pmf import staff_level_pmf
+    from .workforce import StaffFunctor
+    T = 3
+    f = StaffFunctor(fixCost=100, unitVariCost=10, salary=20, unitPenalty=80, minStaffNum=[40] * T, maxHireNum=maxHire, minX=0,
+                     maxX=maxX, clampStaff=True, iniStaffNum=0)
+    return StaffWorkload(f"staff_planning_{maxX + 1}levels_{maxHire + 1}hires_x{T}", f, staff_level_pmf([0.5] * T, maxX + 1),
+                         "WorkforcePlanning.main via StaffRecursion")
+
+
 def workforce_testing_sweep(T: int = 8, maxHire: int = 1000) -> List[StaffWorkload]:
     """WorkforceTesting.main's 216 instances in its loop order (WorkforceTesting.java:17-51): 2 turnover rates (the loop stops
     at iRate < 2) x 3 fixCost x 3 salary x 3 unitPenalty x 4 minStaffNum rows; one shape (T = 8, hires 0..1000, no clamp,
